@@ -1,6 +1,6 @@
 """Level-2 sharding over real GPUs: ONE contact island (a box stack) split into x-slab worlds, one rank per GPU, the halo exchange issued by
 the library (avn_comm_init: RCCL ncclSend / ncclRecv on the world's stream after every colour launch).  Every rank also steps the UNSPLIT
-island on its own GPU and compares its slab against it: the split must be bit-identical.  Used by `bench.py --gpus N` (N > 1, the `level2`
+island on its own GPU and compares its slab against it: the split must be bit-identical.  Used by `bench.py --gpus N --full` (N > 1, the `level2`
 object of the JSON line) and by tools/level2_multi_gpu.py.  Strong scaling: the island's size is fixed as N grows."""
 from __future__ import annotations
 

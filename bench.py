@@ -2,7 +2,10 @@
 """bench.py — physics substeps/second of the MI355X hot path on BASELINE.json's cfg2 (100k-cuboid box stack).
 
 Contract (driver): `python bench.py --gpus N --steps K --warmup W`; for N > 1 launched by torch.distributed.run with
-one rank per GPU.  Rank 0 prints ONE JSON line.
+one rank per GPU.  Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps and prints the headline
+(`value`, `ms_per_step`, `config`); `--full` adds every secondary figure described below (per-phase device times, roofline,
+solver_iterations = 8, PCIe-inclusive, closed loop, CPU baseline, and with N > 1 the sharded and level-2 legs).
+`--dump-outputs DIR` writes the bodies and contact impulses of the last timed step as DIR/<name>.npy.
 
 A "step" = one pass of the hot path over the device-resident world (`avn_step`): AABB update + sweep-and-prune
 broad phase + solver-body/constraint preparation + S substeps (integrate, warm start, biased solve, integrate
@@ -82,6 +85,28 @@ def setup_world(world, lib, sc, pairs_from=None):
                 offsets=offs)
 
 
+DUMP_CAP_BYTES = 64_000_000
+
+
+def dump_outputs(world, out_dir, prefix="", cap=DUMP_CAP_BYTES):
+    """--dump-outputs: what a caller of avn_step receives after the last timed step -- the bodies (avn_bodies_download) and the
+    contact impulses (avn_impulses_download) -- as out_dir/<prefix><name>.npy in the world's float type.  Above `cap` bytes in all,
+    the same fixed, seeded sample of rows is kept of every array with the same row count (rows stay aligned across arrays)."""
+    arrays = dict(world.bodies_download())
+    arrays.update(world.impulses_download())
+    total = sum(a.nbytes for a in arrays.values())
+    if total > cap:
+        keep = {}
+        for n in sorted({len(a) for a in arrays.values()}):
+            k = max(1, int(n * cap / total))
+            keep[n] = np.sort(np.random.default_rng(n).choice(n, size=k, replace=False))
+        arrays = {name: a[keep[len(a)]] for name, a in arrays.items()}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(out_dir, prefix + name + ".npy"), np.ascontiguousarray(a))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -97,6 +122,11 @@ def main():
     ap.add_argument("--no-level2", action="store_true", help="N > 1: skip the one-island-over-all-GPUs leg (level-2 sharding over RCCL)")
     ap.add_argument("--cpu-seconds", type=float, default=20.0, help="budget of the CPU oracle sample (split between the 1-thread and the multi-thread run)")
     ap.add_argument("--cpu-threads", type=int, default=0, help="threads of the multi-thread CPU sample (default min(64, host cores))")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run every secondary measurement (per-phase device times, roofline, PMC traffic, solver_iterations = 8, "
+                         "PCIe-inclusive, closed loop, CPU baseline; with N > 1 the sharded and level-2 legs); without it the run stops after the timed steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (bodies, contact impulses) as DIR/<name>.npy in the world's float type")
     args = ap.parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
@@ -170,6 +200,40 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=coll_device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs:   # before anything below steps the world again; N > 1: every rank writes its own sub-world, the cap is shared
+        dump_outputs(w, args.dump_outputs, "" if world_size == 1 else f"rank{rank}_", DUMP_CAP_BYTES // world_size)
+
+    def headline():
+        total_substeps = world_size * args.steps * substeps
+        return {
+            "metric": "physics substeps/sec at N dynamic bodies (3D)",
+            "value": round(total_substeps / elapsed, 3),
+            "unit": "substeps/s",
+            "n_gpus": world_size,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": round(elapsed / args.steps * 1e3, 4),
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "f32",
+            "data": "synthetic",
+            "config": {"workload": args.scene, "dynamic_bodies_per_gpu": sc.n - 1, "manifolds_per_gpu": meta["n_manifolds"],
+                       "contact_points_per_gpu": meta["points"], "broadphase_pairs": meta["n_pairs"], "substeps": substeps,
+                       "solver_iterations": 1, "dt": 1.0 / 60.0, "colors_used": meta["colors_used"],
+                       "hip_graph": not args.no_graph, "sharding": ("single world" if world_size == 1 else
+                                    "avn_islands_partition: one interaction island (100k stack) per rank; per-step RCCL all-gather of rank bounds only"),
+                       "narrow_phase": "out of path: fixed synthetic face manifolds"},
+        }
+
+    if not args.full:   # a plain run: the headline only
+        if rank == 0:
+            print(json.dumps(headline()), flush=True)
+        if world_size > 1:
+            if pending[0] is not None:
+                pending[0][0].wait()
+            dist.destroy_process_group()
+        return
     # per-phase device times: the MEDIAN of 7 further steps, each read back on its own (one step's events are a noisy sample:
     # a step that finds new pairs runs the emit pass, a pair-set rebuild lands on another); not part of the timed region
     samples = []
@@ -715,25 +779,8 @@ def main():
 
     def make_line(level2_obj):
         total_substeps = world_size * args.steps * substeps
-        out = {
-            "metric": "physics substeps/sec at N dynamic bodies (3D)",
-            "value": round(total_substeps / elapsed, 3),
-            "unit": "substeps/s",
-            "n_gpus": world_size,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(elapsed / args.steps * 1e3, 4),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "f32",
-            "data": "synthetic",
-            "config": {"workload": args.scene, "dynamic_bodies_per_gpu": sc.n - 1, "manifolds_per_gpu": meta["n_manifolds"],
-                       "contact_points_per_gpu": pts, "broadphase_pairs": meta["n_pairs"], "substeps": substeps,
-                       "solver_iterations": 1, "dt": 1.0 / 60.0, "colors_used": meta["colors_used"],
-                       "hip_graph": not args.no_graph, "sharding": ("single world" if world_size == 1 else
-                                    "avn_islands_partition: one interaction island (100k stack) per rank; per-step RCCL all-gather of rank bounds only"),
-                       "narrow_phase": "out of path: fixed synthetic face manifolds"},
+        out = headline()
+        out.update({
             "device_ms": {"broad_phase": round(tm.broad_phase_ms, 4), "prepare": round(tm.prepare_ms, 4),
                           "substeps": round(tm.substeps_ms, 4), "finalize": round(tm.finalize_ms, 4),
                           "kernel_launches_per_step": tm.kernel_launches},
@@ -749,7 +796,7 @@ def main():
             "pcie_inclusive": pcie,
             "closed_loop": closed,
             "cpu_baseline": cpu,
-        }
+        })
         if sharded_holder:
             out["closed_loop_sharded"] = sharded_holder.get("result")
             if "device" in sharded_holder: out["closed_loop_sharded_device"] = sharded_holder["device"]

@@ -9,7 +9,8 @@ What runs here:
   * with tests/golden/avian/<scene>.npz present: the ORACLE (CPU) and, under -m gpu, the HIP path are stepped from the fixture's initial frame and held to it --
     pair sequences, colour lists and island ids bit-exact, bodies within the N1 tolerance -- for the first steps, then for as long as the
     trajectories stay together; ABSENT fixtures are reported loudly (skip reason + warning), never silently;
-  * always: every avian3d / bevy name the generator uses is checked against the reference's source (the check tests/test_rust_layer_cpu.py does for the shim);
+  * always: every avian3d / bevy name the generator uses is checked against the reference's source, as recorded in tests/golden/reference_facts.json
+    (tests/reference_facts.py; the check tests/test_rust_layer_cpu.py does for the shim);
   * always: the whole consumer side is exercised on fixtures written IN THE GENERATOR'S FORMAT from the oracle itself -- converter, reader, world construction,
     replay -- which the oracle must reproduce with tolerance 0 (CPU) and the HIP path too (-m gpu)."""
 import os
@@ -20,13 +21,13 @@ import numpy as np
 import pytest
 
 import avian_fixture_format as AF
+import reference_facts as R
 from avian_amd import scenes
 from helpers import hip_lib, oracle_lib
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(REPO, "tests", "golden", "avian")
 GEN = os.path.join(REPO, "integration", "rust", "avian_fixtures", "src", "main.rs")
-REF = "/root/reference"
 SCENES = ["cfg1", "large_pyramid", "many_pyramids", "joints", "sleeping"]
 EXACT_STEPS = 3                                        # integer structures and bodies are ASSERTED for this many steps ...
 def body_tol(step): return 2e-6 * 4.0 ** (step - 1)   # ... within N1's one-step 1e-7..1e-6 (libm sin/cos, FMA, SIMD quaternion product), growing as a pile amplifies it
@@ -61,31 +62,21 @@ def test_hip_matches_avian_fixture(scene):
 
 
 # ---- the generator only names things the reference has ---------------------------------------------------------------------------------------------------------
-def reference_text():
-    out = []
-    for root in (os.path.join(REF, "src"), os.path.join(REF, "benches", "src")):
-        for d, _, files in os.walk(root):
-            for f in files:
-                if f.endswith(".rs"): out.append(open(os.path.join(d, f), errors="replace").read())
-    return "\n".join(out)
-
-
-@pytest.mark.skipif(not os.path.isdir(REF), reason="the reference checkout is not on this machine")
 def test_every_avian_name_the_generator_uses_exists_in_the_reference():
-    src, ref = open(GEN).read(), reference_text()
+    src, ref = open(GEN).read(), R.ALL_RS   # (the reference's answers: tests/reference_facts.py)
     # (1) module paths of the `use avian3d::{...}` block
     for path in ("collision::contact_types::ContactId", "dynamics::solver::constraint_graph::ConstraintGraph", "dynamics::solver::islands::BodyIslandNode", "math::Scalar", "math::Vector"):
         *mods, name = path.split("::")
-        assert re.search(r"pub (struct|type|enum) " + name + r"\b", ref), f"avian3d::{path}: no such public item"
-        f = os.path.join(REF, "src", *mods[:-1], mods[-1] + ".rs"); d = os.path.join(REF, "src", *mods, "mod.rs")
-        assert os.path.exists(f) or os.path.exists(d), f"avian3d::{'::'.join(mods)}: no such module"
+        assert R.search(ref, r"pub (struct|type|enum) " + name + r"\b"), f"avian3d::{path}: no such public item"
+        f = "/".join(["src", *mods[:-1], mods[-1] + ".rs"]); d = "/".join(["src", *mods, "mod.rs"])
+        assert R.exists(f) or R.exists(d), f"avian3d::{'::'.join(mods)}: no such module"
     # (2) types, resources and components taken from the prelude: each must be a public item of the reference
     types = ["PhysicsPlugins", "RigidBody", "Collider", "Position", "Rotation", "LinearVelocity", "AngularVelocity", "SleepTimer", "Sleeping", "ComputedMass", "ComputedAngularInertia",
              "ComputedCenterOfMass", "Friction", "Restitution", "Gravity", "SubstepCount", "PhysicsSchedule", "PhysicsStepSystems", "ContactGraph", "ContactPair", "DistanceJoint", "FixedJoint",
              "RevoluteJoint", "SphericalJoint", "PrismaticJoint", "JointCollisionDisabled", "WakeBody"]
     for t in types:
         assert re.search(r"\b" + t + r"\b", src), f"the generator no longer uses {t}: drop it from this list"
-        assert re.search(r"pub (struct|enum|type) " + t + r"\b", ref), f"{t}: not a public item of the reference"
+        assert R.search(ref, r"pub (struct|enum|type) " + t + r"\b"), f"{t}: not a public item of the reference"
     # (3) methods and fields, each with the item that owns it
     members = {"fn cuboid": "Collider::cuboid", "fn shape": "Collider::shape", "fn inverse": "ComputedMass::inverse", "fn island_id": "IslandNode::island_id", "fn iter_active": "ContactGraph::iter_active",
                "fn iter_sleeping": "ContactGraph::iter_sleeping", "fn with_local_anchor2": "joints", "fn with_limits": "DistanceJoint / PrismaticJoint", "fn with_hinge_axis": "RevoluteJoint",
@@ -96,15 +87,15 @@ def test_every_avian_name_the_generator_uses_exists_in_the_reference():
     for decl, owner in members.items():
         name = decl.split()[-1]
         assert re.search(r"\b" + name + r"\b", src), f"the generator no longer uses {name}"
-        assert re.search(r"pub (const )?" + decl.replace("pub ", "").replace("fn ", r"fn ") + r"\b", ref), f"{owner}: `{decl}` is not public in the reference"
+        assert R.search(ref, r"pub (const )?" + decl.replace("pub ", "").replace("fn ", r"fn ") + r"\b"), f"{owner}: `{decl}` is not public in the reference"
     # (4) the scenes are the reference's: the bench constants the generator restates
-    bench = open(os.path.join(REF, "benches", "src", "dim3", "large_pyramid.rs")).read()
-    assert "(2.0 * i as f32 + 1.0) * shift * 0.99" in bench and "(2.0 * i as f32 + 1.0) * shift * 0.99" in src
-    many = open(os.path.join(REF, "benches", "src", "dim3", "many_pyramids.rs")).read()
-    assert "j as f32 * (base_width + 2.0 * h) + h" in many and "j as f32 * (base_width + 2.0 * h) + h" in src
+    bench = "benches/src/dim3/large_pyramid.rs"
+    assert R.contains(bench, "(2.0 * i as f32 + 1.0) * shift * 0.99") and "(2.0 * i as f32 + 1.0) * shift * 0.99" in src
+    many = "benches/src/dim3/many_pyramids.rs"
+    assert R.contains(many, "j as f32 * (base_width + 2.0 * h) + h") and "j as f32 * (base_width + 2.0 * h) + h" in src
     cargo = open(os.path.join(REPO, "integration", "rust", "avian_fixtures", "Cargo.toml")).read()
     for feat in ("3d", "f32", "parry-f32", "parallel", "simd"):   # benches/Cargo.toml:25-31
-        assert f'"{feat}"' in cargo and f'"{feat}"' in open(os.path.join(REF, "benches", "Cargo.toml")).read()
+        assert f'"{feat}"' in cargo and R.contains("benches/Cargo.toml", f'"{feat}"')
 
 
 # ---- the consumer side, end to end, on fixtures the oracle wrote in the generator's format ---------------------------------------------------------------

@@ -5,6 +5,8 @@ crate's documentation promises for a plugin the recipe disables must exist and b
 import os
 import re
 
+import reference_facts as R
+
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(REPO, "integration", "rust", "avian_mi355x", "src")
 SYS = os.path.join(REPO, "integration", "rust", "avian_mi355x-sys", "src", "lib.rs")
@@ -87,29 +89,25 @@ def test_every_promised_system_exists_and_is_registered():
 
 def test_host_shape_trampolines_use_the_reference_names_and_the_header_records():
     """host_shapes.rs answers avn_host_aabb_fn / avn_host_manifolds_fn with the reference's own SimpleCollider methods and ContactPoint fields: every one of them
-    must exist in /root/reference (when present here), the trampolines must be registered, and fill_colliders must route non-Ball / Cuboid shapes to the table."""
+    must exist in the reference (tests/reference_facts.py), the trampolines must be registered, and fill_colliders must route non-Ball / Cuboid shapes to the table."""
     src = sources()
     hs = src["host_shapes.rs"]
     for used in ("avn_host_shapes_set", "avn_host_aabb_query_f32", "avn_host_aabb_f32", "avn_host_manifold_query_f32", "avn_host_manifold_f32", "AVN_MAX_QUERY_POINTS"):
         assert f"ffi::{used}" in hs
     assert "AVN_SHAPE_HOST" in src["staging.rs"] and "host_shapes.colliders.insert" in src["staging.rs"]
     assert "host_shapes.register(raw)" in src["plugins.rs"] and "init_resource::<crate::host_shapes::HostShapeTable>" in src["plugins.rs"]
-    ref = "/root/reference/src"
-    if not os.path.isdir(ref):
-        return
-    collider_mod = open(os.path.join(ref, "collision", "collider", "mod.rs")).read()
-    contact_types = open(os.path.join(ref, "collision", "contact_types", "mod.rs")).read()
+    collider_mod, contact_types = "src/collision/collider/mod.rs", "src/collision/contact_types/mod.rs"
     for method in ("fn aabb(", "fn swept_aabb(", "fn contact_manifolds("):   # SimpleCollider (collider/mod.rs:263-320)
-        assert method in collider_mod and "." + method[3:] in hs, method
+        assert R.contains(collider_mod, method) and "." + method[3:] in hs, method
     for field in ("anchor1", "penetration", "feature_id1", "feature_id2"):
-        assert re.search(rf"pub {field}:", contact_types) and f"p.{field}" in hs, field
-    assert re.search(r"pub normal: Vector", contact_types) and "m.normal" in hs and "m.points" in hs
-    assert re.search(r"pub min: Vector", collider_mod) and "aabb.min" in hs and "aabb.max" in hs
+        assert R.search(contact_types, rf"pub {field}:") and f"p.{field}" in hs, field
+    assert R.search(contact_types, r"pub normal: Vector") and "m.normal" in hs and "m.points" in hs
+    assert R.search(collider_mod, r"pub min: Vector") and "aabb.min" in hs and "aabb.max" in hs
 
 
 def test_hook_trampolines_use_the_reference_names_and_the_header_records():
     """hooks.rs answers avn_filter_pairs_fn / avn_modify_contacts_fn with the application's CollisionHooks: the trait methods, the ContactPair / ContactManifold /
-    ContactPoint fields it reads and writes and the ActiveCollisionHooks bits the staging tests must exist in /root/reference (when present here); the context must be
+    ContactPoint fields it reads and writes and the ActiveCollisionHooks bits the staging tests must exist in the reference (tests/reference_facts.py); the context must be
     registered around avn_step by the (generic) solver system; a collider with hooks must no longer push the plugin out of the closed loop."""
     src = sources()
     hk = src["hooks.rs"]
@@ -121,24 +119,19 @@ def test_hook_trampolines_use_the_reference_names_and_the_header_records():
     mode = plugins[plugins.index("fn effective_mode"):plugins.index("impl<H: CollisionHooks + 'static> Plugin")]
     assert "colliders_with_hooks" not in mode, "hooks no longer decide the mode: they are called back inside the closed loop"
     assert "ActiveCollisionHooks::FILTER_PAIRS" in src["staging.rs"] and "ActiveCollisionHooks::MODIFY_CONTACTS" in src["staging.rs"]
-    ref = "/root/reference/src"
-    if not os.path.isdir(ref):
-        return
-    hooks_rs = open(os.path.join(ref, "collision", "hooks.rs")).read()
-    contact_types = open(os.path.join(ref, "collision", "contact_types", "mod.rs")).read()
-    broad = open(os.path.join(ref, "collision", "broad_phase.rs")).read()
-    assert "fn filter_pairs(&self, collider1: Entity, collider2: Entity, commands: &mut Commands) -> bool" in hooks_rs and ".filter_pairs(c1, c2, ctx.commands)" in hk
-    assert "fn modify_contacts(&self, contacts: &mut ContactPair, commands: &mut Commands) -> bool" in hooks_rs and ".modify_contacts(&mut pair, ctx.commands)" in hk
-    assert "const FILTER_PAIRS" in hooks_rs and "const MODIFY_CONTACTS" in hooks_rs
-    assert "for<'w, 's> SystemParamItem<'w, 's, H>: CollisionHooks" in broad   # (the bound the reference's own generic systems carry)
-    assert "pub fn new(collider1: Entity, collider2: Entity, contact_id: ContactId) -> Self" in contact_types and "ContactPair::new(" in hk
-    assert "pub fn new(anchor1: Vector, anchor2: Vector, world_point: Vector, penetration: Scalar) -> Self" in contact_types and "ContactPoint::new(" in hk
-    assert "pub fn new(points: impl IntoIterator<Item = ContactPoint>, normal: Vector) -> Self" in contact_types and "ContactManifold::new(" in hk
+    hooks_rs, contact_types, broad = "src/collision/hooks.rs", "src/collision/contact_types/mod.rs", "src/collision/broad_phase.rs"
+    assert R.contains(hooks_rs, "fn filter_pairs(&self, collider1: Entity, collider2: Entity, commands: &mut Commands) -> bool") and ".filter_pairs(c1, c2, ctx.commands)" in hk
+    assert R.contains(hooks_rs, "fn modify_contacts(&self, contacts: &mut ContactPair, commands: &mut Commands) -> bool") and ".modify_contacts(&mut pair, ctx.commands)" in hk
+    assert R.contains(hooks_rs, "const FILTER_PAIRS") and R.contains(hooks_rs, "const MODIFY_CONTACTS")
+    assert R.contains(broad, "for<'w, 's> SystemParamItem<'w, 's, H>: CollisionHooks")   # (the bound the reference's own generic systems carry)
+    assert R.contains(contact_types, "pub fn new(collider1: Entity, collider2: Entity, contact_id: ContactId) -> Self") and "ContactPair::new(" in hk
+    assert R.contains(contact_types, "pub fn new(anchor1: Vector, anchor2: Vector, world_point: Vector, penetration: Scalar) -> Self") and "ContactPoint::new(" in hk
+    assert R.contains(contact_types, "pub fn new(points: impl IntoIterator<Item = ContactPoint>, normal: Vector) -> Self") and "ContactManifold::new(" in hk
     for field in ("body1", "body2", "manifolds", "flags"):
-        assert re.search(rf"pub {field}:", contact_types) and f"pair.{field}" in hk, field
+        assert R.search(contact_types, rf"pub {field}:") and f"pair.{field}" in hk, field
     for field in ("friction", "restitution", "tangent_velocity", "normal", "points"):
-        assert re.search(rf"pub {field}:", contact_types) and (f"manifold.{field}" in hk or f"m.{field}" in hk), field
+        assert R.search(contact_types, rf"pub {field}:") and (f"manifold.{field}" in hk or f"m.{field}" in hk), field
     for field in ("anchor1", "anchor2", "penetration", "normal_speed", "feature_id1", "feature_id2"):
-        assert re.search(rf"pub {field}:", contact_types) and f"p.{field}" in hk, field
+        assert R.search(contact_types, rf"pub {field}:") and f"p.{field}" in hk, field
     for flag in ("TOUCHING", "GENERATE_CONSTRAINTS", "STATIC1", "STATIC2", "MODIFY_CONTACTS"):
-        assert f"const {flag} =" in contact_types and f"ContactPairFlags::{flag}" in hk, flag
+        assert R.contains(contact_types, f"const {flag} =") and f"ContactPairFlags::{flag}" in hk, flag

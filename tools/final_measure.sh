@@ -11,7 +11,7 @@ export TMPDIR=/tmp
 cd $R
 exec < /dev/null   # (nothing here may ever wait on stdin: a tool that did cost round 4 twenty GPU-minutes)
 M=$R/avian_amd/csrc/measure/libavian_mi355x.so   # the only build that reads AVN_* switches (round 5): every A/B below loads it through AVN_LIB_PATH
-timeout 900 python bench.py > $O/bench_cfg2.json 2> $O/bench.err
+timeout 900 python bench.py --full > $O/bench_cfg2.json 2> $O/bench.err
 tail -c 400 $O/bench_cfg2.json; echo
 cp $R/gpurun_out/bench_pmc_traffic.json $O/pmc_traffic.json 2>/dev/null
 for c in fetch write; do f=$(find $R/gpurun_out/pmc_$c -name "*counter_collection.csv" | head -1); [ -n "$f" ] && python - "$f" "$O/pmc_${c}_size_per_kernel.csv" <<'PY'
@@ -30,7 +30,7 @@ prof() {  # prof <tag> <cmd...>: rocprofv3 kernel-trace + stats, keep the stats 
   (cd /tmp && timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$tag -o p -- "$@" > $O/prof_$tag.log 2>&1)
   cp $(find $O/prof_$tag -name "*kernel_stats.csv" | head -1) $O/kernel_stats_$tag.csv 2>/dev/null
 }
-prof cfg2 python $R/bench.py --no-cpu-baseline --no-pcie --no-closed-loop --no-traffic --no-iters8
+prof cfg2 python $R/bench.py --full --no-cpu-baseline --no-pcie --no-closed-loop --no-traffic --no-iters8
 grep "^{" $O/prof_cfg2.log | tail -1 > $O/bench_under_rocprof.json
 prof cfg2_closed_loop python $R/tools/time_closed_loop.py 50 40 50 120
 f=$(find $O/prof_cfg2_closed_loop -name "*kernel_trace.csv" | head -1)
@@ -84,8 +84,8 @@ for t in cfg2 cfg2_closed_loop cfg3 scene_many scene_large; do rm -rf $O/prof_$t
 timeout 200 python tools/measure_floor.py > $O/color_pass_floor.json 2> $O/floor.err; tail -c 300 $O/color_pass_floor.json; echo
 timeout 400 python tools/time_configs.py $O/other_configs.json > $O/time_configs.log 2>&1
 timeout 400 python tools/bench_reference_scenes.py 300 4 $O/reference_scenes.json > $O/reference_scenes.log 2>&1; tail -2 $O/reference_scenes.log
-AVN_BENCH_SINGLE_DEVICE=1 AVN_BENCH_DIST_BACKEND=gloo timeout 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --steps 5 --warmup 2 > $O/bench_n2_single_device.json 2> $O/bench_n2.err; tail -c 300 $O/bench_n2_single_device.json; echo
+AVN_BENCH_SINGLE_DEVICE=1 AVN_BENCH_DIST_BACKEND=gloo timeout 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 --steps 5 --warmup 2 --full > $O/bench_n2_single_device.json 2> $O/bench_n2.err; tail -c 300 $O/bench_n2_single_device.json; echo
 timeout 200 python tools/level2_multi_gpu.py --steps 10 2> $O/level2.err | grep '^{' > $O/level2_world1.json; tail -c 300 $O/level2_world1.json; echo
-# round 6: the level-2 leg on the closed loop's own manifolds (overflow colour included), one rank: a smoke of the leg bench.py --gpus N runs, and the unsplit step time of that set
+# round 6: the level-2 leg on the closed loop's own manifolds (overflow colour included), one rank: a smoke of the leg bench.py --gpus N --full runs, and the unsplit step time of that set
 timeout 300 python tools/level2_multi_gpu.py --dims 100 50 100 --bits 64 --substeps 8 --steps 3 --warmup 1 --closed-loop-steps 6 2>> $O/level2.err | grep '^{' > $O/level2_cfg5_closed_loop_manifolds_world1.json
 ls -la $O

@@ -1,7 +1,7 @@
 #!/bin/bash
 # where the main stream idles inside / between frozen-manifold cfg2 steps (rocprofv3 kernel trace of the bench): gaps >= 3 us of the busiest queue over three steps
 R=$(cd $(dirname $0)/.. && pwd); O=$R/gpurun_out/frozen_gaps; mkdir -p $O
-(cd /tmp && export TMPDIR=/tmp && timeout 600 rocprofv3 --kernel-trace --output-format csv -d $O/prof -o p -- python $R/bench.py --no-cpu-baseline --no-pcie --no-closed-loop --no-traffic --no-iters8 > $O/run.log 2>&1)
+(cd /tmp && export TMPDIR=/tmp && timeout 600 rocprofv3 --kernel-trace --output-format csv -d $O/prof -o p -- python $R/bench.py --full --no-cpu-baseline --no-pcie --no-closed-loop --no-traffic --no-iters8 > $O/run.log 2>&1)
 f=$(find $O/prof -name "*kernel_trace.csv" | head -1)
 python - "$f" > $O/gaps.txt <<'PY'
 import csv, sys, collections
