@@ -9,7 +9,6 @@
 
 #include "avn_world.hpp"
 
-struct avn_world { avn::WorldBase* impl; };
 struct avn_constraint_graph { avn::ConstraintGraphHost g; };
 static thread_local std::string g_create_error;
 

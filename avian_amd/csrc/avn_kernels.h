@@ -44,6 +44,23 @@ template <class T> __device__ __forceinline__ void collider_pose(const BP<T>& bp
     rot = qnormalize(qmul(body_rot, quat<T>(bp.col_lrot[slot])));
     if (child) *child = true;
 }
+// the exact AABB of a cuboid / ball at a pose, no margins (update_aabb; the spatial queries' BVH and AABB test)
+template <class T> __device__ __forceinline__ void shape_aabb(uint32_t shape, V3<T> h, V3<T> pos, Q4<T> q, V3<T>& mn, V3<T>& mx) {
+    V3<T> he;
+    if (shape == AVN_SHAPE_BALL) he = V3<T>{h.x, h.x, h.x};
+    else {
+        // parry3d Cuboid::aabb: centre +- |R| * half_extents, R = nalgebra UnitQuaternion::to_rotation_matrix
+        T i = q.x, j = q.y, k = q.z, w = q.w;
+        T ww = w * w, ii = i * i, jj = j * j, kk = k * k;
+        T ij = i * j * T(2), wk = w * k * T(2), wj = w * j * T(2), ik = i * k * T(2), jk = j * k * T(2), wi = w * i * T(2);
+        T m00 = fabs_t(ww + ii - jj - kk), m01 = fabs_t(ij - wk), m02 = fabs_t(wj + ik);
+        T m10 = fabs_t(wk + ij), m11 = fabs_t(ww - ii + jj - kk), m12 = fabs_t(jk - wi);
+        T m20 = fabs_t(ik - wj), m21 = fabs_t(wi + jk), m22 = fabs_t(ww - ii - jj + kk);
+        he = V3<T>{(m00 * h.x + m01 * h.y) + m02 * h.z, (m10 * h.x + m11 * h.y) + m12 * h.z, (m20 * h.x + m21 * h.y) + m22 * h.z};
+    }
+    mn = pos - he;
+    mx = pos + he;
+}
 #define AVN_IV_DROPPED 0x80000000u
 #define AVN_IV_LONG 0x40000000u   // > SW_CAP sweep candidates: swept by k_sweep_long in chunks
 
@@ -385,5 +402,42 @@ template <class T> struct ConstraintsStage {
 template <class T> void launch_unpack_constraints(const DW<T>&, const ConstraintsStage<T>&, hipStream_t);
 template <class T> void launch_unpack_joints(const DW<T>&, T* r1, T* r2, T* cd, T* lag, T* force, T* rot_lag, T* torque, hipStream_t);
 template <class T> void launch_unpack_aabbs(const BP<T>&, T* mn, T* mx, uint32_t* interval_entities, hipStream_t);
+
+// k_spatial.hip -- spatial queries (include/avian_mi355x_spatial.h): an LBVH over the collider table, rebuilt by avn_spatial_update
+template <class T> struct SP {
+    uint32_t n;              // colliders = leaves; nodes 0 .. n-2 are internal (0 = root), n-1 .. 2n-2 the leaves in Morton order
+    Vec4<T>* pos;            // [n] snapshot pose of collider i: (position.xyz, 0)
+    Vec4<T>* rot;            // [n] rotation xyzw
+    Vec4<T>* he;             // [n] (half_extents.xyz | radius, 0)
+    uint4* info;             // [n] (entity, memberships, shape, 1 = candidate | 0 = AVN_SHAPE_HOST)
+    Vec4<T>* smin;           // [n] padded shape AABB of collider i (empty = +inf / -inf: host shapes, non-finite poses)
+    Vec4<T>* smax;
+    Vec4<T>* bmin;           // [2n-1] node boxes (a leaf: its collider's smin / smax)
+    Vec4<T>* bmax;
+    uint2* child;            // [n-1] children of internal node i (node indices)
+    uint32_t* parent;        // [2n-1] (root: AVN_SPATIAL_MISS)
+    uint32_t* leaf_col;      // [n] collider of leaf j
+    uint32_t* arrivals;      // [n-1] refit arrival counters (zeroed on the stream before the refit)
+    uint32_t* bounds;        // [8] order-preserving keys of the centroid bounds (min xyz, max xyz)
+    uint32_t *keys_a, *vals_a, *keys_b, *vals_b, *hist, *block_sums;   // the Morton sort's buffers
+};
+template <class T> struct SpatialHit { uint32_t collider, entity; T distance; T normal[3]; };   // == avn_spatial_hit_fNN
+enum { SPQ_CLOSEST = 0, SPQ_HITS = 1, SPQ_POINTS = 2, SPQ_AABBS = 3 };
+template <class T> struct SQ {
+    uint32_t n, cap;                 // queries; max_hits (SPQ_HITS) / cap (SPQ_POINTS, SPQ_AABBS)
+    const T* a;                      // [3n] origins / points / box mins
+    const T* b;                      // [3n] directions / box maxs
+    const T* max_distance;           // [n]
+    const uint8_t* solid;            // [n]
+    const uint32_t* mask;            // [n] or nullptr (LayerMask::ALL)
+    const uint32_t* excluded;        // [n_excluded] sorted entity indices
+    uint32_t n_excluded;
+    SpatialHit<T>* hits;             // SPQ_CLOSEST: [n]; SPQ_HITS: [n * cap]
+    uint32_t* ids;                   // [n * cap]
+    uint32_t* count;                 // [n]
+    unsigned long long* stats;       // [3]: node boxes tested, exact tests, stack overflow flag (zeroed by the launch)
+};
+template <class T> void launch_spatial_build(const DW<T>&, const BP<T>&, const SP<T>&, hipStream_t);
+template <class T> void launch_spatial_query(const SP<T>&, const SQ<T>&, int kind, hipStream_t);
 
 }  // namespace avn

@@ -1,0 +1,27 @@
+// avn_spatial.cpp — the extern "C" boundary of include/avian_mi355x_spatial.h over the C++ host world (world/spatial.hpp).
+// As in avn_abi.cpp, no exception or HIP error crosses it: every entry point returns avn_status.
+#include <new>
+
+#include "avn_world.hpp"
+
+#define SP_GUARD(expr)                                                  \
+    do {                                                                \
+        if (!w || !w->impl) return AVN_ERR_BAD_ARG;                     \
+        try { w->impl->bind(); return w->impl->expr; }                  \
+        catch (const std::bad_alloc&) { w->impl->error = "out of host memory"; return AVN_ERR_OOM; } \
+        catch (...) { w->impl->error = "unexpected C++ exception"; return AVN_ERR_STATE; }           \
+    } while (0)
+
+extern "C" {
+
+AVN_API avn_status avn_spatial_update(avn_world* w) { SP_GUARD(spatial_update()); }
+AVN_API avn_status avn_spatial_cast_rays(avn_world* w, const avn_spatial_rays* r, const avn_spatial_hits_out* o) { SP_GUARD(spatial_cast_rays(r, 0u, o)); }
+AVN_API avn_status avn_spatial_ray_hits(avn_world* w, const avn_spatial_rays* r, uint32_t max_hits, const avn_spatial_hits_out* o) {
+    if (w && w->impl && (max_hits == 0 || max_hits > AVN_SPATIAL_MAX_HITS)) { w->impl->error = "spatial_ray_hits: max_hits must be 1 .. AVN_SPATIAL_MAX_HITS"; return AVN_ERR_BAD_ARG; }
+    SP_GUARD(spatial_cast_rays(r, max_hits, o));
+}
+AVN_API avn_status avn_spatial_point_intersections(avn_world* w, const avn_spatial_points* p, uint32_t cap, const avn_spatial_ids_out* o) { SP_GUARD(spatial_point_intersections(p, cap, o)); }
+AVN_API avn_status avn_spatial_aabb_intersections(avn_world* w, const avn_spatial_aabbs* b, uint32_t cap, const avn_spatial_ids_out* o) { SP_GUARD(spatial_aabb_intersections(b, cap, o)); }
+AVN_API avn_status avn_spatial_stats_get(avn_world* w, avn_spatial_stats* o) { SP_GUARD(spatial_stats_get(o)); }
+
+}  // extern "C"

@@ -436,6 +436,7 @@ template <class T> struct World : WorldBase {
 #include "world/despawn.hpp"
 #include "world/dshard.hpp"
 #include "world/timers.hpp"
+#include "world/spatial.hpp"
 };
 
 template <class T> avn_status World<T>::diagnostics(avn_diagnostics* d) {

@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "avn_kernels.h"
+#include "../../include/avian_mi355x_spatial.h"
 
 namespace avn {
 
@@ -124,6 +125,12 @@ struct WorldBase {
     virtual avn_status dshard_bodies_pack(void*, size_t, size_t*) = 0;
     virtual avn_status dshard_bodies_unpack(uint32_t, const void*, size_t) = 0;
     virtual avn_status dshard_stats_get(avn_dshard_stats*) = 0;
+    // spatial queries (include/avian_mi355x_spatial.h; world/spatial.hpp)
+    virtual avn_status spatial_update() = 0;
+    virtual avn_status spatial_cast_rays(const avn_spatial_rays*, uint32_t max_hits, const avn_spatial_hits_out*) = 0;   // max_hits 0: the closest hit only
+    virtual avn_status spatial_point_intersections(const avn_spatial_points*, uint32_t, const avn_spatial_ids_out*) = 0;
+    virtual avn_status spatial_aabb_intersections(const avn_spatial_aabbs*, uint32_t, const avn_spatial_ids_out*) = 0;
+    virtual avn_status spatial_stats_get(avn_spatial_stats*) = 0;
 };
 
 // RCCL transport of the level-2 halo exchange (avn_comm.cpp; librccl is opened on first use)
@@ -137,6 +144,13 @@ struct Comm {
     avn_status all_gather(const void* send, void* recv, size_t bytes_per_rank, hipStream_t s, std::string& err);
 };
 avn_status comm_unique_id(uint8_t* out, std::string& err);
+
+}  // namespace avn
+
+// the opaque handle of the C ABI (avn_abi.cpp, avn_spatial.cpp)
+struct avn_world { avn::WorldBase* impl; };
+
+namespace avn {
 
 WorldBase* make_world_f32(const avn_config* cfg, avn_status* st, std::string* err);
 WorldBase* make_world_f64(const avn_config* cfg, avn_status* st, std::string* err);

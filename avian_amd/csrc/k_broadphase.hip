@@ -25,24 +25,7 @@
 namespace avn {
 
 // ---------------------------------------------------------------------------------------------------------
-// AABB
-template <class T> __device__ __forceinline__ void shape_aabb(uint32_t shape, V3<T> h, V3<T> pos, Q4<T> q, V3<T>& mn, V3<T>& mx) {
-    V3<T> he;
-    if (shape == AVN_SHAPE_BALL) he = V3<T>{h.x, h.x, h.x};
-    else {
-        // parry3d Cuboid::aabb: centre +- |R| * half_extents, R = nalgebra UnitQuaternion::to_rotation_matrix
-        T i = q.x, j = q.y, k = q.z, w = q.w;
-        T ww = w * w, ii = i * i, jj = j * j, kk = k * k;
-        T ij = i * j * T(2), wk = w * k * T(2), wj = w * j * T(2), ik = i * k * T(2), jk = j * k * T(2), wi = w * i * T(2);
-        T m00 = fabs_t(ww + ii - jj - kk), m01 = fabs_t(ij - wk), m02 = fabs_t(wj + ik);
-        T m10 = fabs_t(wk + ij), m11 = fabs_t(ww - ii + jj - kk), m12 = fabs_t(jk - wi);
-        T m20 = fabs_t(ik - wj), m21 = fabs_t(wi + jk), m22 = fabs_t(ww - ii - jj + kk);
-        he = V3<T>{(m00 * h.x + m01 * h.y) + m02 * h.z, (m10 * h.x + m11 * h.y) + m12 * h.z, (m20 * h.x + m21 * h.y) + m22 * h.z};
-    }
-    mn = pos - he;
-    mx = pos + he;
-}
-
+// AABB (shape_aabb: avn_kernels.h)
 template <class T>
 __global__ __launch_bounds__(256) void k_update_aabb(DW<T> w, BP<T> bp, StepParams<T> p, uint32_t* __restrict__ zero_words, uint32_t n_zero) {
     uint32_t c = blockIdx.x * 256 + threadIdx.x;

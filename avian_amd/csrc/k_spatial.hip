@@ -1,0 +1,455 @@
+// k_spatial.hip — spatial queries on the device (include/avian_mi355x_spatial.h): an LBVH over the collider table and one-lane-per-query
+// traversals for ray casts, ray hits, point and AABB intersections.
+//
+// avn_spatial_update (launch_spatial_build), all on the world's stream:
+//   1. k_sp_snapshot   one thread per collider: its pose (collider_pose), the exact shape AABB (shape_aabb), padded, as the leaf box;
+//                      integer atomics of order-preserving keys give the bounds of the box centres (deterministic, no float atomics)
+//   2. k_sp_morton     30-bit Morton code of the box centre in those bounds
+//   3. the hand-written stable radix sort of the codes with the collider index as value: the order of the unique 64-bit keys
+//      (Morton << 32 | collider index), so the tree is the same run to run
+//   4. k_sp_karras     the Karras (2012) hierarchy over the sorted keys: children and parents of every internal node
+//   5. k_sp_refit      one thread per leaf walks to the root; per internal node the SECOND arriving thread unions the two child boxes
+//                      (exact min / max) -- the hand-over between workgroups is an agent-scope release before the arrival counter's
+//                      atomic and an agent-scope acquire after it (L1 is per CU, L2 per XCD): never co-location
+//
+// Queries: one lane per query, a per-lane DFS stack in LDS (64 entries: the depth of a Karras tree over unique 64-bit keys is at most 64).
+// The BVH only culls; every answer is the exact per-collider test below, so the result equals a brute-force pass with the same tests.  A
+// leaf box is the exact shape AABB grown by 64 eps * its largest coordinate, and every node test of a query grows the node box by 64 eps
+// * the query's largest coordinate: the rounding of shape_aabb, of the local-frame transform and of the slab test are all a few eps of
+// those magnitudes, so no point that an exact test accepts lies outside the boxes the traversal tests.
+#include "avn_kernels.h"
+#include "../../include/avian_mi355x_spatial.h"
+
+namespace avn {
+
+#define SP_STACK 64
+#define SP_WAVE 64
+
+// order-preserving uint32 key of a float (min / max by integer atomics)
+__device__ __forceinline__ uint32_t sp_fkey(float f) { uint32_t u = __float_as_uint(f); return (u & 0x80000000u) ? ~u : (u | 0x80000000u); }
+__device__ __forceinline__ float sp_funkey(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k); }
+__device__ __forceinline__ uint32_t sp_expand10(uint32_t v) {
+    v = (v * 0x00010001u) & 0xFF0000FFu;
+    v = (v * 0x00000101u) & 0x0F00F00Fu;
+    v = (v * 0x00000011u) & 0xC30C30C3u;
+    v = (v * 0x00000005u) & 0x49249249u;
+    return v;
+}
+template <class T> __device__ __forceinline__ T sp_inf() { return (T)__builtin_huge_val(); }
+template <class T> __device__ __forceinline__ T sp_vget(const V3<T>& v, int i) { return i == 0 ? v.x : (i == 1 ? v.y : v.z); }
+template <class T> __device__ __forceinline__ T sp_maxabs(V3<T> v) { return smax(smax(fabs_t(v.x), fabs_t(v.y)), fabs_t(v.z)); }
+
+// ---------------------------------------------------------------------------------------------------------
+// build
+template <class T>
+__global__ __launch_bounds__(256) void k_sp_snapshot(DW<T> w, BP<T> bp, SP<T> sp) {
+    const uint32_t c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= sp.n) return;
+    const uint4 ci = bp.col_info[c];
+    const uint32_t shape = ci.z & 0xFFu;
+    const int body = (int)ci.y;
+    V3<T> pos; Q4<T> rot;
+    collider_pose<T>(bp, c, xyz<T>(w.pos[body]), quat<T>(w.rot[body]), pos, rot);
+    const V3<T> h = xyz<T>(bp.col_he[c]);
+    sp.pos[c] = make4<T>(pos, T(0));
+    sp.rot[c] = make4<T>(rot);
+    sp.he[c] = make4<T>(h, T(0));
+    const bool native = shape != AVN_SHAPE_HOST;
+    sp.info[c] = make_uint4(ci.x, bp.col_layers[c].x, shape, native ? 1u : 0u);
+    V3<T> mn{sp_inf<T>(), sp_inf<T>(), sp_inf<T>()}, mx{-sp_inf<T>(), -sp_inf<T>(), -sp_inf<T>()};
+    if (native) {
+        V3<T> a, b;
+        shape_aabb<T>(shape, h, pos, rot, a, b);
+        if (is_finite(a) && is_finite(b)) {
+            const T pad = T(64) * Limits<T>::eps * smax(sp_maxabs(a), sp_maxabs(b));
+            const V3<T> pp{pad, pad, pad};
+            mn = a - pp; mx = b + pp;
+            const V3<T> m = (a + b) * T(0.5);
+            atomicMin(&sp.bounds[0], sp_fkey((float)m.x)); atomicMin(&sp.bounds[1], sp_fkey((float)m.y)); atomicMin(&sp.bounds[2], sp_fkey((float)m.z));
+            atomicMax(&sp.bounds[3], sp_fkey((float)m.x)); atomicMax(&sp.bounds[4], sp_fkey((float)m.y)); atomicMax(&sp.bounds[5], sp_fkey((float)m.z));
+        }
+    }
+    sp.smin[c] = make4<T>(mn, T(0));
+    sp.smax[c] = make4<T>(mx, T(0));
+}
+
+template <class T>
+__global__ __launch_bounds__(256) void k_sp_morton(SP<T> sp) {
+    const uint32_t c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= sp.n) return;
+    const Vec4<T> a = sp.smin[c], b = sp.smax[c];
+    uint32_t code = 0;
+    if (a.x <= b.x) {   // (empty: host shapes and non-finite poses sort first, code 0)
+        float lo[3], hi[3], m[3] = {(float)((a.x + b.x) * T(0.5)), (float)((a.y + b.y) * T(0.5)), (float)((a.z + b.z) * T(0.5))};
+        for (int k = 0; k < 3; ++k) { lo[k] = sp_funkey(sp.bounds[k]); hi[k] = sp_funkey(sp.bounds[3 + k]); }
+        uint32_t q[3];
+        for (int k = 0; k < 3; ++k) {
+            const float ext = hi[k] - lo[k];
+            float f = ext > 0.0f ? (m[k] - lo[k]) / ext * 1024.0f : 0.0f;
+            f = f < 0.0f ? 0.0f : (f > 1023.0f ? 1023.0f : f);
+            q[k] = (uint32_t)f;
+        }
+        code = (sp_expand10(q[0]) << 2) | (sp_expand10(q[1]) << 1) | sp_expand10(q[2]);
+    }
+    sp.keys_a[c] = code;
+    sp.vals_a[c] = c;
+}
+
+// common prefix length of the 64-bit keys of sorted positions i and j (-1 outside the range)
+__device__ __forceinline__ int sp_delta(const uint32_t* __restrict__ code, const uint32_t* __restrict__ idx, uint32_t n, int i, int j) {
+    if (j < 0 || j >= (int)n) return -1;
+    const uint64_t ki = ((uint64_t)code[i] << 32) | idx[i], kj = ((uint64_t)code[j] << 32) | idx[j];
+    return __clzll((long long)(ki ^ kj));
+}
+// Karras, "Maximizing parallelism in the construction of BVHs, octrees, and k-d trees" (HPG 2012), Figure 4
+template <class T>
+__global__ __launch_bounds__(256) void k_sp_karras(SP<T> sp, const uint32_t* __restrict__ code, const uint32_t* __restrict__ idx) {
+    const uint32_t n = sp.n;
+    const uint32_t t = blockIdx.x * 256 + threadIdx.x;
+    if (t < n) sp.leaf_col[t] = idx[t];
+    if (t == 0) sp.parent[0] = AVN_SPATIAL_MISS;
+    if (t + 1 >= n) return;   // internal nodes 0 .. n-2
+    const int i = (int)t;
+    const int d = sp_delta(code, idx, n, i, i + 1) > sp_delta(code, idx, n, i, i - 1) ? 1 : -1;
+    const int dmin = sp_delta(code, idx, n, i, i - d);
+    int lmax = 2;
+    while (sp_delta(code, idx, n, i, i + lmax * d) > dmin) lmax *= 2;
+    int l = 0;
+    for (int s = lmax / 2; s >= 1; s /= 2)
+        if (sp_delta(code, idx, n, i, i + (l + s) * d) > dmin) l += s;
+    const int j = i + l * d;
+    const int dnode = sp_delta(code, idx, n, i, j);
+    int s = 0;
+    for (int div = 2;; div *= 2) {
+        const int st = (l + div - 1) / div;
+        if (sp_delta(code, idx, n, i, i + (s + st) * d) > dnode) s += st;
+        if (st <= 1) break;
+    }
+    const int gamma = i + s * d + (d < 0 ? -1 : 0);
+    const uint32_t left = (min(i, j) == gamma) ? (n - 1 + (uint32_t)gamma) : (uint32_t)gamma;
+    const uint32_t right = (max(i, j) == gamma + 1) ? (n - 1 + (uint32_t)gamma + 1) : (uint32_t)gamma + 1;
+    sp.child[i] = make_uint2(left, right);
+    sp.parent[left] = (uint32_t)i;
+    sp.parent[right] = (uint32_t)i;
+}
+
+// bottom-up refit.  The boxes of another workgroup's subtree are handed over through the arrival counter: plain stores of the box, an
+// agent-scope release fence and its wait, the counter's atomic; the second arriver's agent-scope acquire, then plain vector loads.
+template <class T>
+__global__ __launch_bounds__(256) void k_sp_refit(SP<T> sp) {
+    const uint32_t j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= sp.n) return;
+    Vec4<T>* bmin = sp.bmin;   // (no __restrict__ / const: loads of handed-over boxes stay ordinary vector loads behind the acquire)
+    Vec4<T>* bmax = sp.bmax;
+    const uint32_t leaf = sp.n - 1 + j;
+    const uint32_t c = sp.leaf_col[j];
+    Vec4<T> lo = sp.smin[c], hi = sp.smax[c];
+    bmin[leaf] = lo; bmax[leaf] = hi;
+    uint32_t node = sp.parent[leaf];
+    while (node != AVN_SPATIAL_MISS) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        const uint32_t before = __hip_atomic_fetch_add(&sp.arrivals[node], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (before == 0u) return;   // the sibling subtree is not done: its last thread carries on
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+        const uint2 ch = sp.child[node];
+        const Vec4<T> a0 = bmin[ch.x], a1 = bmax[ch.x], b0 = bmin[ch.y], b1 = bmax[ch.y];
+        lo = make4<T>(vmin(xyz<T>(a0), xyz<T>(b0)), T(0));
+        hi = make4<T>(vmax(xyz<T>(a1), xyz<T>(b1)), T(0));
+        bmin[node] = lo; bmax[node] = hi;
+        node = sp.parent[node];
+    }
+}
+
+template <class T> void launch_spatial_build(const DW<T>& w, const BP<T>& bp, const SP<T>& sp, hipStream_t s) {
+    const uint32_t n = sp.n;
+    if (n == 0) return;
+    const uint32_t nb = (n + 255) / 256;
+    // bounds: min keys start at ~0, max keys at 0 (one memset each half)
+    (void)hipMemsetAsync(sp.bounds, 0xFF, 3 * sizeof(uint32_t), s);
+    (void)hipMemsetAsync(sp.bounds + 3, 0x00, 5 * sizeof(uint32_t), s);
+    hipLaunchKernelGGL((k_sp_snapshot<T>), dim3(nb), dim3(256), 0, s, w, bp, sp);
+    hipLaunchKernelGGL((k_sp_morton<T>), dim3(nb), dim3(256), 0, s, sp);
+    uint32_t *ko = nullptr, *vo = nullptr;
+    launch_radix_sort<uint32_t>(sp.keys_a, sp.vals_a, sp.keys_b, sp.vals_b, n, sp.hist, sp.block_sums, nullptr, &ko, &vo, s);
+    hipLaunchKernelGGL((k_sp_karras<T>), dim3(nb), dim3(256), 0, s, sp, (const uint32_t*)ko, (const uint32_t*)vo);
+    if (n > 1) (void)hipMemsetAsync(sp.arrivals, 0, (size_t)(n - 1) * sizeof(uint32_t), s);
+    hipLaunchKernelGGL((k_sp_refit<T>), dim3(nb), dim3(256), 0, s, sp);
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// exact per-collider tests (the header's restatement of parry3d; tests/spatial_query_reference.py does the same operations in order)
+template <class T>
+__device__ __forceinline__ bool sp_ray_exact(uint32_t shape, V3<T> he, V3<T> pos, Q4<T> rot, V3<T> o, V3<T> d, T max_distance, bool solid, T& toi, V3<T>& normal) {
+    const Q4<T> ci = qinverse(rot);
+    const V3<T> ol = qrot(ci, o - pos);
+    const V3<T> dl = qrot(ci, d);
+    T t;
+    bool zero_normal = false;
+    V3<T> nl = vzero<T>();
+    if (shape == AVN_SHAPE_BALL) {
+        const T r = he.x;
+        const T a = dot(dl, dl), b = dot(ol, dl), c = dot(ol, ol) - r * r;
+        if (c > T(0) && b > T(0)) return false;
+        const T delta = b * b - a * c;
+        if (delta < T(0)) return false;
+        const T sq = sqrt_t(delta);
+        t = (-b - sq) / a;
+        if (t <= T(0)) {
+            if (solid) { t = T(0); zero_normal = true; }
+            else t = (-b + sq) / a;
+        }
+        if (!(t <= max_distance)) return false;
+        if (!zero_normal) {
+            const V3<T> p = ol + dl * t;
+            const T l = length(p);
+            if (l > T(0)) nl = p / l; else zero_normal = true;
+        }
+    } else {
+        T tmin = -sp_inf<T>(), tmax = sp_inf<T>();
+        int na = -1, fa = -1;
+        T nsg = T(0), fsg = T(0);
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            const T oi = sp_vget(ol, i), di = sp_vget(dl, i), hi = sp_vget(he, i);
+            if (di != T(0)) {
+                const T inv = T(1) / di;
+                T t1 = (-hi - oi) * inv, t2 = (hi - oi) * inv;
+                T sn = T(-1), sf = T(1);
+                if (inv < T(0)) { const T x = t1; t1 = t2; t2 = x; sn = T(1); sf = T(-1); }
+                if (t1 > tmin) { tmin = t1; na = i; nsg = sn; }
+                if (t2 < tmax) { tmax = t2; fa = i; fsg = sf; }
+            } else if (oi < -hi || oi > hi) {
+                return false;   // parallel to this slab and outside it
+            }
+        }
+        if (!(tmin <= tmax) || tmax < T(0)) return false;
+        int axis; T sg;
+        if (tmin < T(0)) {   // the origin is inside
+            if (solid) { t = T(0); zero_normal = true; axis = -1; sg = T(0); }
+            else { t = tmax; axis = fa; sg = fsg; }
+        } else { t = tmin; axis = na; sg = nsg; }
+        if (!(t <= max_distance)) return false;
+        if (axis < 0) zero_normal = true;
+        else nl = V3<T>{axis == 0 ? sg : T(0), axis == 1 ? sg : T(0), axis == 2 ? sg : T(0)};
+    }
+    toi = t;
+    normal = zero_normal ? vzero<T>() : qrot(rot, nl);
+    return true;
+}
+template <class T> __device__ __forceinline__ bool sp_point_exact(uint32_t shape, V3<T> he, V3<T> pos, Q4<T> rot, V3<T> p) {
+    const V3<T> pl = qrot(qinverse(rot), p - pos);
+    if (shape == AVN_SHAPE_BALL) return dot(pl, pl) <= he.x * he.x;
+    return fabs_t(pl.x) <= he.x && fabs_t(pl.y) <= he.y && fabs_t(pl.z) <= he.z;
+}
+template <class T> __device__ __forceinline__ bool sp_aabb_exact(uint32_t shape, V3<T> he, V3<T> pos, Q4<T> rot, V3<T> qmin, V3<T> qmax) {
+    V3<T> mn, mx;
+    shape_aabb<T>(shape, he, pos, rot, mn, mx);
+    return mn.x <= qmax.x && mn.y <= qmax.y && mn.z <= qmax.z && mx.x >= qmin.x && mx.y >= qmin.y && mx.z >= qmin.z;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// traversal
+template <class T> struct RayCtx { V3<T> o, d, inv; uint32_t zero; T tol; };
+// entry distance of the ray into the node box grown by tol (+inf = miss); the node test of every ray query
+template <class T> __device__ __forceinline__ T sp_ray_box(const RayCtx<T>& r, Vec4<T> lo4, Vec4<T> hi4, T limit) {
+    T tmin = -sp_inf<T>(), tmax = sp_inf<T>();
+    const V3<T> lo = xyz<T>(lo4), hi = xyz<T>(hi4);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        const T l = sp_vget(lo, i) - r.tol, h = sp_vget(hi, i) + r.tol, oi = sp_vget(r.o, i);
+        if (r.zero & (1u << i)) {
+            if (!(oi >= l && oi <= h)) return sp_inf<T>();
+        } else {
+            const T iv = sp_vget(r.inv, i);
+            T t1 = (l - oi) * iv, t2 = (h - oi) * iv;
+            if (iv < T(0)) { const T x = t1; t1 = t2; t2 = x; }
+            tmin = smax(tmin, t1);
+            tmax = smin(tmax, t2);
+        }
+    }
+    if (!(tmin <= tmax) || tmax < T(0) || !(tmin <= limit)) return sp_inf<T>();
+    return smax(tmin, T(0));
+}
+template <class T> __device__ __forceinline__ bool sp_point_box(V3<T> p, T tol, Vec4<T> lo, Vec4<T> hi) {
+    return p.x >= lo.x - tol && p.x <= hi.x + tol && p.y >= lo.y - tol && p.y <= hi.y + tol && p.z >= lo.z - tol && p.z <= hi.z + tol;
+}
+template <class T> __device__ __forceinline__ bool sp_box_box(V3<T> qmin, V3<T> qmax, Vec4<T> lo, Vec4<T> hi) {
+    return lo.x <= qmax.x && lo.y <= qmax.y && lo.z <= qmax.z && hi.x >= qmin.x && hi.y >= qmin.y && hi.z >= qmin.z;
+}
+__device__ __forceinline__ bool sp_excluded(const uint32_t* __restrict__ ex, uint32_t n, uint32_t e) {
+    uint32_t lo = 0, hi = n;
+    while (lo < hi) { const uint32_t m = (lo + hi) >> 1; if (ex[m] < e) lo = m + 1; else hi = m; }
+    return lo < n && ex[lo] == e;
+}
+
+// one lane per query; blocks of one wave, each lane with its own SP_STACK-entry column of the LDS stack
+template <class T, int KIND>
+__global__ __launch_bounds__(SP_WAVE) void k_sp_query(SP<T> sp, SQ<T> q) {
+    __shared__ uint32_t stack[SP_STACK * SP_WAVE];
+    const uint32_t lane = threadIdx.x;
+    const uint32_t qi = blockIdx.x * SP_WAVE + lane;
+    const bool active = qi < q.n;
+    uint32_t nodes_tested = 0, leaves_tested = 0, overflow = 0;
+    const uint32_t n = sp.n;
+    if (active) {
+        const uint32_t mask = q.mask ? q.mask[qi] : 0xFFFFFFFFu;
+        // per-query state
+        RayCtx<T> r;
+        V3<T> pa{T(0), T(0), T(0)}, pb{T(0), T(0), T(0)};
+        T max_distance = T(0), tol = T(0);
+        bool solid = false;
+        pa = V3<T>{q.a[3 * (size_t)qi], q.a[3 * (size_t)qi + 1], q.a[3 * (size_t)qi + 2]};
+        if (KIND != SPQ_POINTS) pb = V3<T>{q.b[3 * (size_t)qi], q.b[3 * (size_t)qi + 1], q.b[3 * (size_t)qi + 2]};
+        if (KIND == SPQ_CLOSEST || KIND == SPQ_HITS) {
+            max_distance = q.max_distance[qi];
+            solid = q.solid[qi] != 0;
+            r.o = pa; r.d = pb; r.zero = 0;
+            r.inv = V3<T>{pb.x != T(0) ? T(1) / pb.x : T(0), pb.y != T(0) ? T(1) / pb.y : T(0), pb.z != T(0) ? T(1) / pb.z : T(0)};
+            r.zero = (pb.x == T(0) ? 1u : 0u) | (pb.y == T(0) ? 2u : 0u) | (pb.z == T(0) ? 4u : 0u);
+            r.tol = T(64) * Limits<T>::eps * sp_maxabs(pa);
+        }
+        if (KIND == SPQ_POINTS) tol = T(64) * Limits<T>::eps * sp_maxabs(pa);
+        // results
+        T best = sp_inf<T>();
+        uint32_t best_c = AVN_SPATIAL_MISS;
+        V3<T> best_n = vzero<T>();
+        uint32_t found = 0;
+        SpatialHit<T>* hl = (KIND == SPQ_HITS) ? q.hits + (size_t)qi * q.cap : nullptr;
+        uint32_t* il = (KIND == SPQ_POINTS || KIND == SPQ_AABBS) ? q.ids + (size_t)qi * q.cap : nullptr;
+
+        // node test: entry distance for rays (+inf = miss), 0 / +inf for the others
+        auto test = [&](uint32_t node) -> T {
+            ++nodes_tested;
+            const Vec4<T> lo = sp.bmin[node], hi = sp.bmax[node];
+            if (KIND == SPQ_CLOSEST) return sp_ray_box(r, lo, hi, smin(best, max_distance));
+            if (KIND == SPQ_HITS) return sp_ray_box(r, lo, hi, max_distance);
+            if (KIND == SPQ_POINTS) return sp_point_box(pa, tol, lo, hi) ? T(0) : sp_inf<T>();
+            return sp_box_box(pa, pb, lo, hi) ? T(0) : sp_inf<T>();
+        };
+        auto leaf = [&](uint32_t node) {
+            const uint32_t c = sp.leaf_col[node - (n - 1)];
+            const uint4 info = sp.info[c];
+            if (!info.w || (info.y & mask) == 0u || (q.n_excluded && sp_excluded(q.excluded, q.n_excluded, info.x))) return;
+            ++leaves_tested;
+            const V3<T> pos = xyz<T>(sp.pos[c]), he = xyz<T>(sp.he[c]);
+            const Q4<T> rot = quat<T>(sp.rot[c]);
+            if (KIND == SPQ_CLOSEST || KIND == SPQ_HITS) {
+                T toi; V3<T> nrm;
+                if (!sp_ray_exact<T>(info.z, he, pos, rot, r.o, r.d, max_distance, solid, toi, nrm)) return;
+                if (KIND == SPQ_CLOSEST) {
+                    if (toi < best || (toi == best && c < best_c)) { best = toi; best_c = c; best_n = nrm; }
+                } else {
+                    const uint32_t k = q.cap;
+                    uint32_t m = found < k ? found : k;
+                    ++found;
+                    // nearest-k by (distance, collider), insertion into the query's own output records
+                    if (m == k) {
+                        const SpatialHit<T>& last = hl[k - 1];
+                        if (!(toi < last.distance || (toi == last.distance && c < last.collider))) return;
+                        m = k - 1;
+                    }
+                    while (m > 0 && (hl[m - 1].distance > toi || (hl[m - 1].distance == toi && hl[m - 1].collider > c))) { hl[m] = hl[m - 1]; --m; }
+                    SpatialHit<T> h;
+                    h.collider = c; h.entity = info.x; h.distance = toi; h.normal[0] = nrm.x; h.normal[1] = nrm.y; h.normal[2] = nrm.z;
+                    hl[m] = h;
+                }
+            } else {
+                const bool hit = KIND == SPQ_POINTS ? sp_point_exact<T>(info.z, he, pos, rot, pa) : sp_aabb_exact<T>(info.z, he, pos, rot, pa, pb);
+                if (!hit) return;
+                const uint32_t k = q.cap;
+                uint32_t m = found < k ? found : k;
+                ++found;
+                if (m == k) {
+                    if (k == 0 || c >= il[k - 1]) return;
+                    m = k - 1;
+                }
+                while (m > 0 && il[m - 1] > c) { il[m] = il[m - 1]; --m; }
+                il[m] = c;
+            }
+        };
+
+        if (n == 1) {
+            if (test(0) != sp_inf<T>()) leaf(0);
+        } else if (n > 1 && test(0) != sp_inf<T>()) {
+            uint32_t sp_top = 0, node = 0;
+            for (;;) {
+                const uint2 ch = sp.child[node];
+                T e0 = test(ch.x), e1 = test(ch.y);
+                const bool l0 = ch.x >= n - 1, l1 = ch.y >= n - 1;
+                if (l0 && e0 != sp_inf<T>()) { leaf(ch.x); e0 = sp_inf<T>(); }
+                if (l1 && e1 != sp_inf<T>()) { leaf(ch.y); e1 = sp_inf<T>(); }
+                const bool g0 = e0 != sp_inf<T>(), g1 = e1 != sp_inf<T>();
+                if (g0 && g1) {
+                    const bool first0 = !(e1 < e0);   // the nearer child first (ties: the left one)
+                    if (sp_top < SP_STACK) { stack[sp_top * SP_WAVE + lane] = first0 ? ch.y : ch.x; ++sp_top; }
+                    else overflow = 1;   // (cannot happen: the depth of the tree is at most 64)
+                    node = first0 ? ch.x : ch.y;
+                    continue;
+                }
+                if (g0) { node = ch.x; continue; }
+                if (g1) { node = ch.y; continue; }
+                if (sp_top == 0) break;
+                --sp_top;
+                node = stack[sp_top * SP_WAVE + lane];
+                // a node pushed before the best hit shrank: re-test its box against the current bound (closest hit only)
+                if (KIND == SPQ_CLOSEST) {
+                    for (;;) {
+                        if (test(node) != sp_inf<T>()) break;
+                        if (sp_top == 0) { node = AVN_SPATIAL_MISS; break; }
+                        --sp_top;
+                        node = stack[sp_top * SP_WAVE + lane];
+                    }
+                    if (node == AVN_SPATIAL_MISS) break;
+                }
+            }
+        }
+
+        // write the results
+        if (KIND == SPQ_CLOSEST) {
+            SpatialHit<T> h;
+            h.collider = best_c;
+            h.entity = best_c == AVN_SPATIAL_MISS ? AVN_SPATIAL_MISS : sp.info[best_c].x;
+            h.distance = best_c == AVN_SPATIAL_MISS ? T(0) : best;
+            h.normal[0] = best_n.x; h.normal[1] = best_n.y; h.normal[2] = best_n.z;
+            q.hits[qi] = h;
+        } else if (KIND == SPQ_HITS) {
+            SpatialHit<T> miss;
+            miss.collider = AVN_SPATIAL_MISS; miss.entity = AVN_SPATIAL_MISS; miss.distance = T(0); miss.normal[0] = miss.normal[1] = miss.normal[2] = T(0);
+            for (uint32_t m = found; m < q.cap; ++m) hl[m] = miss;
+            q.count[qi] = found;
+        } else {
+            for (uint32_t m = found; m < q.cap; ++m) il[m] = AVN_SPATIAL_MISS;
+            q.count[qi] = found;
+        }
+    }
+    // totals of the call: one atomic per wave
+    uint32_t a = nodes_tested, b = leaves_tested, o = overflow;
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) { a += __shfl_xor(a, off); b += __shfl_xor(b, off); o |= __shfl_xor(o, off); }
+    if (lane == 0) {
+        atomicAdd(&q.stats[0], (unsigned long long)a);
+        atomicAdd(&q.stats[1], (unsigned long long)b);
+        if (o) atomicOr(&q.stats[2], 1ull);
+    }
+}
+
+template <class T> void launch_spatial_query(const SP<T>& sp, const SQ<T>& q, int kind, hipStream_t s) {
+    (void)hipMemsetAsync(q.stats, 0, 4 * sizeof(unsigned long long), s);
+    if (q.n == 0) return;
+    const dim3 g((q.n + SP_WAVE - 1) / SP_WAVE), b(SP_WAVE);
+    switch (kind) {
+        case SPQ_CLOSEST: hipLaunchKernelGGL((k_sp_query<T, SPQ_CLOSEST>), g, b, 0, s, sp, q); break;
+        case SPQ_HITS: hipLaunchKernelGGL((k_sp_query<T, SPQ_HITS>), g, b, 0, s, sp, q); break;
+        case SPQ_POINTS: hipLaunchKernelGGL((k_sp_query<T, SPQ_POINTS>), g, b, 0, s, sp, q); break;
+        default: hipLaunchKernelGGL((k_sp_query<T, SPQ_AABBS>), g, b, 0, s, sp, q); break;
+    }
+}
+
+static_assert(sizeof(SpatialHit<float>) == sizeof(avn_spatial_hit_f32) && sizeof(SpatialHit<double>) == sizeof(avn_spatial_hit_f64), "hit record layout");
+template void launch_spatial_build<float>(const DW<float>&, const BP<float>&, const SP<float>&, hipStream_t);
+template void launch_spatial_build<double>(const DW<double>&, const BP<double>&, const SP<double>&, hipStream_t);
+template void launch_spatial_query<float>(const SP<float>&, const SQ<float>&, int, hipStream_t);
+template void launch_spatial_query<double>(const SP<double>&, const SQ<double>&, int, hipStream_t);
+
+}  // namespace avn

@@ -58,6 +58,7 @@
         return AVN_OK;
     }
     avn_status colliders_upload(const avn_colliders* c) override {
+        sp_valid = false;   // (the spatial-query snapshot names the old tables: avn_spatial_update again)
         slp_world_asleep = slp_world_idle = false;
         if (!have_bodies) { error = "colliders_upload before bodies_upload"; return AVN_ERR_STATE; }
         if (!c || (c->count && (!c->entity_index || !c->body || !c->shape || !c->half_extents))) { error = "colliders_upload: null array"; return AVN_ERR_BAD_ARG; }

@@ -18,6 +18,7 @@
     DevBuf b_dsp_a, b_dsp_b;
 
     avn_status despawn(const avn_despawn_list* d) override {
+        sp_valid = false;   // (the spatial-query snapshot names the old tables: avn_spatial_update again)
         slp_world_asleep = slp_world_idle = false;
         if (!d || (d->struct_size != sizeof(avn_despawn_list) && d->struct_size != AVN_DESPAWN_LIST_SIZE_R4) || (d->n_colliders && !d->collider_entities) || (d->n_bodies && !d->bodies)) { error = "despawn: bad argument"; return AVN_ERR_BAD_ARG; }
         if (d->struct_size == sizeof(avn_despawn_list) && d->n_joints && !d->joints) { error = "despawn: bad argument"; return AVN_ERR_BAD_ARG; }

@@ -178,6 +178,7 @@
     DevBuf b_col_lpos, b_col_lrot;
     bool tf_any = false;
     avn_status collider_transforms_upload(const avn_collider_transforms* t) override {
+        sp_valid = false;   // (the spatial-query snapshot names the old tables: avn_spatial_update again)
         HIPCHK(hipStreamSynchronize(stream)); HIPCHK(hipStreamSynchronize(stream_bp));
         if (!t || !t->count) { bp.col_lpos = nullptr; bp.col_lrot = nullptr; tf_any = false; return AVN_OK; }
         if (t->count != bp.n_colliders) { error = "collider_transforms_upload: count differs from the last colliders_upload"; return AVN_ERR_BAD_ARG; }

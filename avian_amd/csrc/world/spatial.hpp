@@ -1,0 +1,165 @@
+// world/spatial.hpp -- fragment of the body of `template <class T> struct World` (avn_world.hip includes it inside the class):
+// SpatialQueryPlugin (spatial_query/mod.rs:190-212) on the device -- include/avian_mi355x_spatial.h.  avn_spatial_update builds the LBVH of
+// k_spatial.hip from the poses in HBM; the queries stage their inputs, run one traversal launch and copy the answers back.
+
+    SP<T> sp{};
+    DevBuf b_sp_pos, b_sp_rot, b_sp_he, b_sp_info, b_sp_smin, b_sp_smax, b_sp_bmin, b_sp_bmax, b_sp_child, b_sp_parent, b_sp_leaf, b_sp_arr, b_sp_bounds,
+        b_sp_keys_a, b_sp_vals_a, b_sp_keys_b, b_sp_vals_b, b_sp_hist, b_sp_block_sums, b_sp_stats;
+    uint32_t sp_cap = 0;
+    bool sp_valid = false;      // a snapshot exists and no table changed since (bodies / colliders / collider transforms uploads and avn_despawn clear it)
+    uint32_t sp_host = 0;       // AVN_SHAPE_HOST colliders in the snapshot
+    unsigned long long sp_visits[3] = {0, 0, 0};   // last query call: node boxes tested, exact tests, stack overflow
+
+    avn_status sp_grow(uint32_t C) {
+        if (sp_cap && C <= sp_cap) return AVN_OK;
+        HIPCHK(hipStreamSynchronize(stream));   // (the old buffers may still be read by an update in flight)
+        const size_t cc = std::max<size_t>({(size_t)C, (size_t)sp_cap + sp_cap / 2, 64});
+        bool moved = false;
+        GROW(b_sp_pos, cc, sp.pos); GROW(b_sp_rot, cc, sp.rot); GROW(b_sp_he, cc, sp.he); GROW(b_sp_info, cc, sp.info);
+        GROW(b_sp_smin, cc, sp.smin); GROW(b_sp_smax, cc, sp.smax);
+        GROW(b_sp_bmin, 2 * cc, sp.bmin); GROW(b_sp_bmax, 2 * cc, sp.bmax); GROW(b_sp_child, cc, sp.child); GROW(b_sp_parent, 2 * cc, sp.parent);
+        GROW(b_sp_leaf, cc, sp.leaf_col); GROW(b_sp_arr, cc, sp.arrivals); GROW(b_sp_bounds, 8, sp.bounds);
+        GROW(b_sp_keys_a, cc, sp.keys_a); GROW(b_sp_vals_a, cc, sp.vals_a); GROW(b_sp_keys_b, cc, sp.keys_b); GROW(b_sp_vals_b, cc, sp.vals_b);
+        GROW(b_sp_hist, (size_t)256 * radix_blocks((uint32_t)cc) + 256, sp.hist);
+        GROW(b_sp_block_sums, scan_block_sums_needed(256 * radix_blocks((uint32_t)cc)) + 16, sp.block_sums);
+        HIPCHK(hipMemset(b_sp_block_sums.p, 0, b_sp_block_sums.cap));   // the one-launch scan's state: zero once, self-cleaning afterwards (avn_scan.h)
+        unsigned long long* dummy_s;
+        GROW(b_sp_stats, 4, dummy_s);
+        sp_cap = (uint32_t)cc;
+        return AVN_OK;
+    }
+
+    avn_status spatial_update() override {
+        if (!have_bodies || !have_colliders) { error = "spatial_update: before bodies_upload / colliders_upload"; return AVN_ERR_STATE; }
+        if (despawn_needs_bodies || despawn_needs_colliders) { error = "spatial_update: avn_despawn is still waiting for avn_bodies_upload / avn_colliders_upload"; return AVN_ERR_STATE; }
+        const uint32_t C = bp.n_colliders;
+        avn_status st = sp_grow(C);
+        if (st != AVN_OK) return st;
+        sp.n = C;
+        launch_spatial_build<T>(dw, bp, sp, stream);
+        HIPCHK(hipGetLastError());
+        sp_host = (uint32_t)hs_slots.size();
+        sp_valid = true;
+        return AVN_OK;
+    }
+
+    avn_status sp_check(uint32_t flags) {
+        if (!sp_valid) { error = "spatial query: no avn_spatial_update since the tables last changed"; return AVN_ERR_STATE; }
+        if (sp_host && !(flags & AVN_SPATIAL_SKIP_HOST_SHAPES)) {
+            error = "spatial query: the snapshot holds AVN_SHAPE_HOST colliders, which have no device geometry (AVN_SPATIAL_SKIP_HOST_SHAPES leaves them out)";
+            return AVN_ERR_STATE;
+        }
+        return AVN_OK;
+    }
+    // the shared excluded list, sorted on the host (read back first when it is a device array)
+    avn_status sp_excluded(const avn_spatial_filter& f, bool dev, std::vector<uint32_t>& ex) {
+        if (f.n_excluded && !f.excluded) { error = "spatial query: filter.excluded is NULL"; return AVN_ERR_BAD_ARG; }
+        ex.resize(f.n_excluded);
+        if (f.n_excluded) {
+            if (dev) HIPCHK(hipMemcpy(ex.data(), f.excluded, (size_t)f.n_excluded * 4, hipMemcpyDeviceToHost));
+            else std::memcpy(ex.data(), f.excluded, (size_t)f.n_excluded * 4);
+            std::sort(ex.begin(), ex.end());
+        }
+        return AVN_OK;
+    }
+    template <class U> avn_status sp_in(const void* p, size_t count, bool dev, const U** out) {
+        if (!p || count == 0) { *out = nullptr; return AVN_OK; }
+        if (dev) { *out = (const U*)p; return AVN_OK; }
+        return stage_in<U>(p, count, out);
+    }
+    template <class U> U* sp_out(void* p, size_t count, bool dev) { return dev ? (U*)p : stage_alloc<U>(count); }
+    // bytes the staging arena needs for a call (host pointers: inputs and outputs; always: the excluded list)
+    static size_t sp_stage_bytes(bool dev, size_t n, size_t in_bytes, size_t out_bytes, size_t n_excluded) {
+        return al(n_excluded * 4) + (dev ? 0 : in_bytes + out_bytes + al(n * 4) * 2) + 4096;
+    }
+    avn_status sp_run(SQ<T>& q, int kind) {
+        q.stats = b_sp_stats.as<unsigned long long>();
+        launch_spatial_query<T>(sp, q, kind, stream);
+        HIPCHK(hipGetLastError());
+        return AVN_OK;
+    }
+    avn_status sp_finish() {
+        HIPCHK(hipMemcpyAsync(sp_visits, b_sp_stats.p, sizeof sp_visits, hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+        if (sp_visits[2]) { error = "spatial query: traversal stack overflow"; return AVN_ERR_CAPACITY; }
+        return AVN_OK;
+    }
+
+    avn_status spatial_cast_rays(const avn_spatial_rays* r, uint32_t max_hits, const avn_spatial_hits_out* out) override {
+        if (!r || !out) { error = "spatial ray query: null argument"; return AVN_ERR_BAD_ARG; }
+        const uint32_t n = r->count;
+        const bool many = max_hits != 0;
+        if (n && (!r->origin || !r->direction || !r->max_distance || !r->solid || !out->hits || (many && !out->count))) { error = "spatial ray query: null array"; return AVN_ERR_BAD_ARG; }
+        if (max_hits > AVN_SPATIAL_MAX_HITS) { error = "spatial_ray_hits: max_hits above AVN_SPATIAL_MAX_HITS"; return AVN_ERR_BAD_ARG; }
+        avn_status st = sp_check(r->flags);
+        if (st != AVN_OK) return st;
+        const bool dev = (r->flags & AVN_SPATIAL_DEVICE_POINTERS) != 0;
+        std::vector<uint32_t> ex;
+        if ((st = sp_excluded(r->filter, dev, ex)) != AVN_OK) return st;
+        const size_t n_rec = (size_t)n * (many ? max_hits : 1);
+        if ((st = stage_reserve(sp_stage_bytes(dev, n, 2 * al(3 * sizeof(T) * n) + al(sizeof(T) * n) + al(n), al(n_rec * sizeof(SpatialHit<T>)), ex.size()))) != AVN_OK) return st;
+        SQ<T> q{};
+        q.n = n; q.cap = max_hits;
+        if ((st = sp_in<T>(r->origin, 3 * (size_t)n, dev, &q.a)) != AVN_OK) return st;
+        if ((st = sp_in<T>(r->direction, 3 * (size_t)n, dev, &q.b)) != AVN_OK) return st;
+        if ((st = sp_in<T>(r->max_distance, n, dev, &q.max_distance)) != AVN_OK) return st;
+        if ((st = sp_in<uint8_t>(r->solid, n, dev, &q.solid)) != AVN_OK) return st;
+        if ((st = sp_in<uint32_t>(r->filter.mask, n, dev, &q.mask)) != AVN_OK) return st;
+        if ((st = stage_in<uint32_t>(ex.data(), ex.size(), &q.excluded)) != AVN_OK) return st;
+        q.n_excluded = (uint32_t)ex.size();
+        q.hits = sp_out<SpatialHit<T>>(out->hits, n_rec, dev);
+        if (many) q.count = sp_out<uint32_t>(out->count, n, dev);
+        if ((st = sp_run(q, many ? SPQ_HITS : SPQ_CLOSEST)) != AVN_OK) return st;
+        if (!dev) {
+            if ((st = stage_out<SpatialHit<T>>(out->hits, q.hits, n_rec)) != AVN_OK) return st;
+            if (many && (st = stage_out<uint32_t>(out->count, q.count, n)) != AVN_OK) return st;
+        }
+        return sp_finish();
+    }
+
+    // point (kind SPQ_POINTS: a = points) and box (SPQ_AABBS: a = mins, b = maxs) intersections
+    avn_status sp_ids(int kind, uint32_t n, uint32_t flags, const void* a, const void* b, const avn_spatial_filter& f, uint32_t cap, const avn_spatial_ids_out* out) {
+        if (!out) { error = "spatial query: null argument"; return AVN_ERR_BAD_ARG; }
+        if (n && (!a || (kind == SPQ_AABBS && !b) || !out->count || (cap && !out->collider))) { error = "spatial query: null array"; return AVN_ERR_BAD_ARG; }
+        avn_status st = sp_check(flags);
+        if (st != AVN_OK) return st;
+        const bool dev = (flags & AVN_SPATIAL_DEVICE_POINTERS) != 0;
+        std::vector<uint32_t> ex;
+        if ((st = sp_excluded(f, dev, ex)) != AVN_OK) return st;
+        const size_t n_ids = (size_t)n * cap;
+        if ((st = stage_reserve(sp_stage_bytes(dev, n, 2 * al(3 * sizeof(T) * n), al(n_ids * 4), ex.size()))) != AVN_OK) return st;
+        SQ<T> q{};
+        q.n = n; q.cap = cap;
+        if ((st = sp_in<T>(a, 3 * (size_t)n, dev, &q.a)) != AVN_OK) return st;
+        if (kind == SPQ_AABBS && (st = sp_in<T>(b, 3 * (size_t)n, dev, &q.b)) != AVN_OK) return st;
+        if ((st = sp_in<uint32_t>(f.mask, n, dev, &q.mask)) != AVN_OK) return st;
+        if ((st = stage_in<uint32_t>(ex.data(), ex.size(), &q.excluded)) != AVN_OK) return st;
+        q.n_excluded = (uint32_t)ex.size();
+        q.ids = n_ids ? sp_out<uint32_t>(out->collider, n_ids, dev) : nullptr;
+        q.count = sp_out<uint32_t>(out->count, n, dev);
+        if ((st = sp_run(q, kind)) != AVN_OK) return st;
+        if (!dev) {
+            if ((st = stage_out<uint32_t>(out->collider, q.ids, n_ids)) != AVN_OK) return st;
+            if ((st = stage_out<uint32_t>(out->count, q.count, n)) != AVN_OK) return st;
+        }
+        return sp_finish();
+    }
+    avn_status spatial_point_intersections(const avn_spatial_points* p, uint32_t cap, const avn_spatial_ids_out* out) override {
+        if (!p) { error = "spatial_point_intersections: null argument"; return AVN_ERR_BAD_ARG; }
+        return sp_ids(SPQ_POINTS, p->count, p->flags, p->point, nullptr, p->filter, cap, out);
+    }
+    avn_status spatial_aabb_intersections(const avn_spatial_aabbs* b, uint32_t cap, const avn_spatial_ids_out* out) override {
+        if (!b) { error = "spatial_aabb_intersections: null argument"; return AVN_ERR_BAD_ARG; }
+        return sp_ids(SPQ_AABBS, b->count, b->flags, b->min, b->max, b->filter, cap, out);
+    }
+    avn_status spatial_stats_get(avn_spatial_stats* o) override {
+        if (!o) return AVN_ERR_BAD_ARG;
+        std::memset(o, 0, sizeof *o);
+        o->colliders = sp_valid ? sp.n : 0u;
+        o->nodes = sp_valid && sp.n ? 2 * sp.n - 1 : 0u;
+        o->host_skipped = sp_valid ? sp_host : 0u;
+        o->valid = sp_valid ? 1u : 0u;
+        o->nodes_visited = sp_visits[0];
+        o->leaves_visited = sp_visits[1];
+        return AVN_OK;
+    }

@@ -1,0 +1,235 @@
+"""ctypes binding of ``include/avian_mi355x_spatial.h``: device spatial queries (ray casts, ray hits, point and AABB intersections) over the
+colliders a :class:`avian_amd._ffi.World` holds on the device.
+
+Numpy arrays in and out (copied through the library's staging), or torch tensors on the world's GPU (``AVN_SPATIAL_DEVICE_POINTERS``: the
+library reads and writes the tensors in place).  These entry points are not part of ``_ffi.ABI_SYMBOLS``: they live in their own header.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import _ffi as F
+
+vp = C.c_void_p
+
+DEVICE_POINTERS = 1
+SKIP_HOST_SHAPES = 2
+MAX_HITS = 64
+MISS = 0xFFFFFFFF
+
+
+class avn_spatial_filter(C.Structure):
+    _fields_ = [("mask", vp), ("excluded", vp), ("n_excluded", C.c_uint32)]
+
+
+class avn_spatial_rays(C.Structure):
+    _fields_ = [("count", C.c_uint32), ("flags", C.c_uint32), ("origin", vp), ("direction", vp), ("max_distance", vp), ("solid", vp),
+                ("filter", avn_spatial_filter)]
+
+
+class avn_spatial_points(C.Structure):
+    _fields_ = [("count", C.c_uint32), ("flags", C.c_uint32), ("point", vp), ("filter", avn_spatial_filter)]
+
+
+class avn_spatial_aabbs(C.Structure):
+    _fields_ = [("count", C.c_uint32), ("flags", C.c_uint32), ("min", vp), ("max", vp), ("filter", avn_spatial_filter)]
+
+
+class avn_spatial_hit_f32(C.Structure):
+    _fields_ = [("collider", C.c_uint32), ("entity", C.c_uint32), ("distance", C.c_float), ("normal", C.c_float * 3)]
+
+
+class avn_spatial_hit_f64(C.Structure):
+    _fields_ = [("collider", C.c_uint32), ("entity", C.c_uint32), ("distance", C.c_double), ("normal", C.c_double * 3)]
+
+
+class avn_spatial_hits_out(C.Structure):
+    _fields_ = [("hits", vp), ("count", vp)]
+
+
+class avn_spatial_ids_out(C.Structure):
+    _fields_ = [("collider", vp), ("count", vp)]
+
+
+class avn_spatial_stats(C.Structure):
+    _fields_ = [("colliders", C.c_uint32), ("nodes", C.c_uint32), ("host_skipped", C.c_uint32), ("valid", C.c_uint32),
+                ("nodes_visited", C.c_uint64), ("leaves_visited", C.c_uint64)]
+
+
+STRUCTS = [avn_spatial_filter, avn_spatial_rays, avn_spatial_points, avn_spatial_aabbs, avn_spatial_hit_f32, avn_spatial_hit_f64,
+           avn_spatial_hits_out, avn_spatial_ids_out, avn_spatial_stats]
+SYMBOLS = ["avn_spatial_update", "avn_spatial_cast_rays", "avn_spatial_ray_hits", "avn_spatial_point_intersections",
+           "avn_spatial_aabb_intersections", "avn_spatial_stats_get"]
+
+
+def hit_dtype(bits: int) -> np.dtype:
+    """numpy mirror of avn_spatial_hit_fNN."""
+    s = np.float32 if bits == 32 else np.float64
+    return np.dtype([("collider", np.uint32), ("entity", np.uint32), ("distance", s), ("normal", s, (3,))], align=True)
+
+
+def _declare(dll):
+    for name in SYMBOLS:
+        getattr(dll, name).restype = C.c_int32
+    dll.avn_spatial_update.argtypes = [vp]
+    dll.avn_spatial_cast_rays.argtypes = [vp, vp, vp]
+    dll.avn_spatial_ray_hits.argtypes = [vp, vp, C.c_uint32, vp]
+    dll.avn_spatial_point_intersections.argtypes = [vp, vp, C.c_uint32, vp]
+    dll.avn_spatial_aabb_intersections.argtypes = [vp, vp, C.c_uint32, vp]
+    dll.avn_spatial_stats_get.argtypes = [vp, vp]
+
+
+class SpatialQuery:
+    """The spatial queries of one world (``SpatialQueryPipeline`` / ``SpatialQuery``).  Call :meth:`update` to snapshot the poses the
+    device holds; the queries answer against the last snapshot.
+
+    Arguments that are torch tensors on the GPU select the device-pointer path: every array of that call must then be a contiguous tensor on
+    the world's device (scalars in the world's dtype, ``solid`` uint8, masks / excluded entities int32 read as uint32), outputs come back
+    as tensors.  Otherwise everything is numpy."""
+
+    def __init__(self, world: F.World):
+        self.world = world
+        self.dll = world.lib.dll
+        if not hasattr(self.dll, "avn_spatial_update"):
+            raise ImportError(f"{world.lib.path} does not export the spatial queries (include/avian_mi355x_spatial.h)")
+        _declare(self.dll)
+        self.bits = world.cfg.scalar_bits
+        self.dtype = world.dtype
+        self.hit_dtype = hit_dtype(self.bits)
+        self._keep = []
+
+    # -- plumbing ------------------------------------------------------------------------------
+    def _check(self, st: int):
+        self._keep = []
+        self.world._check(st)
+
+    @staticmethod
+    def _is_tensor(a) -> bool:
+        return type(a).__module__.startswith("torch") and hasattr(a, "is_cuda") and a.is_cuda
+
+    def _arr(self, a, dt, dev, shape=None):
+        if a is None:
+            return None
+        if dev:
+            import torch
+            tdt = {np.float32: torch.float32, np.float64: torch.float64, np.uint8: torch.uint8, np.uint32: torch.int32}[dt]
+            t = a.to(tdt).contiguous()
+            if shape is not None:
+                t = t.reshape(shape)
+            self._keep.append(t)
+            return vp(t.data_ptr())
+        x = np.ascontiguousarray(a, dtype=dt)
+        if shape is not None:
+            x = x.reshape(shape)
+        self._keep.append(x)
+        return x.ctypes.data_as(vp)
+
+    def _out(self, shape, dt, dev, like=None):
+        if dev:
+            import torch
+            if dt is self.hit_dtype:
+                t = torch.empty(tuple(shape) + (self.hit_dtype.itemsize,), dtype=torch.uint8, device=like.device)
+            else:
+                t = torch.empty(shape, dtype={np.uint32: torch.int32}[dt], device=like.device)
+            return t, vp(t.data_ptr())
+        x = np.empty(shape, dt)
+        return x, x.ctypes.data_as(vp)
+
+    def _filter(self, n, mask, excluded, dev):
+        f = avn_spatial_filter()
+        f.mask = self._arr(mask, np.uint32, dev, (n,)) if mask is not None else None
+        if excluded is not None and len(excluded):
+            f.excluded = self._arr(excluded, np.uint32, dev)
+            f.n_excluded = len(excluded)
+        return f
+
+    def _flags(self, dev, skip_host_shapes):
+        return (DEVICE_POINTERS if dev else 0) | (SKIP_HOST_SHAPES if skip_host_shapes else 0)
+
+    @staticmethod
+    def _sync_torch(dev):
+        if dev:
+            import torch
+            torch.cuda.synchronize()   # the caller's writes to the inputs are complete before the library's stream reads them
+
+    # -- entry points --------------------------------------------------------------------------
+    def update(self):
+        """avn_spatial_update: the LBVH of every collider at the poses the device holds now."""
+        self._check(self.dll.avn_spatial_update(self.world.handle))
+
+    def _rays(self, origin, direction, max_distance, solid, mask, excluded, skip_host_shapes):
+        dev = self._is_tensor(origin)
+        n = int(origin.shape[0])
+        r = avn_spatial_rays()
+        r.count = n
+        r.flags = self._flags(dev, skip_host_shapes)
+        r.origin = self._arr(origin, self.dtype, dev, (n, 3))
+        r.direction = self._arr(direction, self.dtype, dev, (n, 3))
+        if max_distance is None:
+            max_distance = np.full(n, np.inf) if not dev else origin.new_full((n,), float("inf"))
+        if solid is None:
+            solid = np.ones(n, np.uint8) if not dev else origin.new_ones((n,))
+        r.max_distance = self._arr(max_distance, self.dtype, dev, (n,))
+        r.solid = self._arr(solid, np.uint8, dev, (n,))
+        r.filter = self._filter(n, mask, excluded, dev)
+        return r, n, dev
+
+    def cast_rays(self, origin, direction, max_distance=None, solid=None, mask=None, excluded=None, skip_host_shapes=False):
+        """SpatialQueryPipeline::cast_ray per ray: a structured array of hit records (``hit_dtype``; collider == MISS: no hit).  Device
+        tensors in: a uint8 tensor [n, itemsize] of the same records out."""
+        r, n, dev = self._rays(origin, direction, max_distance, solid, mask, excluded, skip_host_shapes)
+        hits, hp = self._out((n,), self.hit_dtype, dev, origin)
+        o = avn_spatial_hits_out(hp, None)
+        self._sync_torch(dev)
+        self._check(self.dll.avn_spatial_cast_rays(self.world.handle, C.byref(r), C.byref(o)))
+        return hits
+
+    def ray_hits(self, origin, direction, max_hits, max_distance=None, solid=None, mask=None, excluded=None, skip_host_shapes=False):
+        """SpatialQueryPipeline::ray_hits: (records [n, max_hits] nearest first, true hit counts [n])."""
+        r, n, dev = self._rays(origin, direction, max_distance, solid, mask, excluded, skip_host_shapes)
+        hits, hp = self._out((n, max(int(max_hits), 1)), self.hit_dtype, dev, origin)
+        cnt, cp = self._out((n,), np.uint32, dev, origin)
+        o = avn_spatial_hits_out(hp, cp)
+        self._sync_torch(dev)
+        self._check(self.dll.avn_spatial_ray_hits(self.world.handle, C.byref(r), int(max_hits), C.byref(o)))
+        return hits, cnt
+
+    def point_intersections(self, point, cap, mask=None, excluded=None, skip_host_shapes=False):
+        """SpatialQueryPipeline::point_intersections: (collider indices [n, cap] ascending, MISS-padded; true counts [n])."""
+        dev = self._is_tensor(point)
+        n = int(point.shape[0])
+        p = avn_spatial_points()
+        p.count = n
+        p.flags = self._flags(dev, skip_host_shapes)
+        p.point = self._arr(point, self.dtype, dev, (n, 3))
+        p.filter = self._filter(n, mask, excluded, dev)
+        ids, ip = self._out((n, int(cap)), np.uint32, dev, point)
+        cnt, cp = self._out((n,), np.uint32, dev, point)
+        o = avn_spatial_ids_out(ip, cp)
+        self._sync_torch(dev)
+        self._check(self.dll.avn_spatial_point_intersections(self.world.handle, C.byref(p), int(cap), C.byref(o)))
+        return ids, cnt
+
+    def aabb_intersections(self, aabb_min, aabb_max, cap, mask=None, excluded=None, skip_host_shapes=False):
+        """SpatialQueryPipeline::aabb_intersections_with_aabb: (collider indices [n, cap] ascending, MISS-padded; true counts [n])."""
+        dev = self._is_tensor(aabb_min)
+        n = int(aabb_min.shape[0])
+        b = avn_spatial_aabbs()
+        b.count = n
+        b.flags = self._flags(dev, skip_host_shapes)
+        b.min = self._arr(aabb_min, self.dtype, dev, (n, 3))
+        b.max = self._arr(aabb_max, self.dtype, dev, (n, 3))
+        b.filter = self._filter(n, mask, excluded, dev)
+        ids, ip = self._out((n, int(cap)), np.uint32, dev, aabb_min)
+        cnt, cp = self._out((n,), np.uint32, dev, aabb_min)
+        o = avn_spatial_ids_out(ip, cp)
+        self._sync_torch(dev)
+        self._check(self.dll.avn_spatial_aabb_intersections(self.world.handle, C.byref(b), int(cap), C.byref(o)))
+        return ids, cnt
+
+    def stats(self) -> avn_spatial_stats:
+        s = avn_spatial_stats()
+        self._check(self.dll.avn_spatial_stats_get(self.world.handle, C.byref(s)))
+        return s

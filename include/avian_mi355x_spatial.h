@@ -1,0 +1,149 @@
+/*
+ * avian_mi355x_spatial.h — device spatial queries: ray casts, point and AABB intersections against the colliders the world holds in HBM.
+ *
+ * Mirrors Avian's `SpatialQueryPlugin` (spatial_query/mod.rs:190-212), whose systems run in `PhysicsStepSystems::SpatialQuery` right after
+ * `Sleeping` (schedule/mod.rs:98-105): `update_spatial_query_pipeline` rebuilds a BVH of every collider from `Position` / `Rotation`
+ * (spatial_query/pipeline.rs:96-133), and the queries of `SpatialQueryPipeline` / the `raycast` system of `RayCaster` read it.
+ * Here the structure is an LBVH built on the device from the poses the device holds (avn_spatial_update); the queries traverse it one lane
+ * per query.  The BVH only culls: every answer comes from an exact per-collider test (below), so the result equals a brute-force pass
+ * over all colliders with the same tests, bit for bit.
+ *
+ * Conventions are those of avian_mi355x.h (scalar type = the world's, vectors interleaved xyz, quaternions xyzw, every call returns
+ * avn_status with a message in avn_last_error).  The calls are synchronous: they return once the outputs are written.  These entry
+ * points are plain `avn_spatial_*` functions of libavian_mi355x.so; they are not part of the AVN_FN list of the main header.
+ *
+ * Exact per-collider tests (restatements of parry3d's published algorithms; parry's source is not vendored, so the parity of these
+ * functions against parry is UNPINNED -- they are defined here and the device and the test suite's restatement agree bit for bit):
+ *  - pose: collider_pose (child colliders through ColliderTransform), then the ray / point in the collider's local frame with the
+ *    conjugate rotation (parry's Ray::inverse_transform_by): o_l = rot^-1 (o - pos), d_l = rot^-1 d.
+ *  - cuboid: parry's local-AABB slab clip (Aabb::cast_local_ray_and_get_normal).  Per axis with d != 0: t_near / t_far of the two
+ *    faces; the entry is the largest t_near (strict >, so at an edge or corner the first axis in x, y, z order gives the normal), the
+ *    exit the smallest t_far (strict <).  An axis with d == 0 is a parallel slab: a miss when the origin lies outside it.  A miss when
+ *    entry > exit or exit < 0.  Origin inside (entry < 0): solid -> distance 0, normal 0; not solid -> the exit distance and the exit
+ *    face's normal.  Otherwise the entry distance and the entry face's outward normal.
+ *  - ball: parry's ray_toi_with_ball: a = |d|^2, b = o.d, c = |o|^2 - r^2; a miss when c > 0 && b > 0 or b^2 - a c < 0; t = (-b - sqrt) / a;
+ *    t <= 0 (inside): solid -> 0 with normal 0, else (-b + sqrt) / a.  The normal is (o + d t) / |o + d t| (0 when that is 0).
+ *  - a hit counts when distance <= max_distance; the local normal is rotated back to world space.
+ *  - point containment: |p_l.i| <= he.i for a cuboid, |p_l|^2 <= r^2 for a ball.
+ *  - AABB: the collider's exact shape AABB at the snapshot pose (the broad phase's shape_aabb, no margins) intersects the query box
+ *    (min <= other.max && max >= other.min per axis).
+ *
+ * Snapshot rules:
+ *  - a query before any avn_spatial_update, or after avn_bodies_upload / avn_colliders_upload / avn_collider_transforms_upload /
+ *    avn_despawn changed the tables without a new update, returns AVN_ERR_STATE.  Steps do not invalidate the snapshot: queries answer
+ *    against the poses of the last update, as Avian's pipeline does between updates (SpatialQuery::update_pipeline).
+ *  - AVN_SHAPE_HOST colliders have no device geometry: if the snapshot holds any, queries return AVN_ERR_STATE unless the query sets
+ *    AVN_SPATIAL_SKIP_HOST_SHAPES; with the flag they are never candidates (avn_spatial_stats.host_skipped counts them).
+ *  - sensors, sleeping and static bodies' colliders are all candidates, as in Avian's pipeline.
+ *
+ * Filter (SpatialQueryFilter::test, query_filter.rs:97-101): a collider is a candidate when memberships & mask != 0 and its
+ * entity_index is not in the excluded list.  ONE excluded list is shared by every query of a call (a caster's own entity goes in it for
+ * RayCaster::ignore_self); per-query exclusion lists are not supported.
+ *
+ * Ties: closest hit = smallest (distance, collider index); ray_hits = the max_hits nearest by (distance, collider index), sorted, plus
+ * the true number of hits (Avian returns an arbitrary subset when truncated: nearest-k is a deterministic strengthening); point and AABB
+ * intersections = ascending collider index, the first `cap`, plus the true count.  A collider index is its slot in the last
+ * avn_colliders_upload.
+ */
+#ifndef AVIAN_MI355X_SPATIAL_H
+#define AVIAN_MI355X_SPATIAL_H
+
+#include "avian_mi355x.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* flags of a query */
+enum {
+    AVN_SPATIAL_DEVICE_POINTERS = 1,   /* every input and output array of the call (filter included) is a device pointer on the world's device;
+                                          the caller's writes to them must be complete before the call */
+    AVN_SPATIAL_SKIP_HOST_SHAPES = 2   /* AVN_SHAPE_HOST colliders are never candidates (else their presence is AVN_ERR_STATE) */
+};
+#define AVN_SPATIAL_MAX_HITS 64        /* largest max_hits of avn_spatial_ray_hits */
+#define AVN_SPATIAL_MISS 0xFFFFFFFFu   /* collider index of a miss */
+
+typedef struct avn_spatial_filter {
+    const uint32_t* mask;      /* [n] LayerMask per query; NULL = LayerMask::ALL */
+    const uint32_t* excluded;  /* [n_excluded] collider entity_index values excluded from every query of the call; NULL if n_excluded == 0 */
+    uint32_t n_excluded;
+} avn_spatial_filter;
+
+typedef struct avn_spatial_rays {
+    uint32_t count;              /* n */
+    uint32_t flags;              /* AVN_SPATIAL_* */
+    const void* origin;          /* [3n] */
+    const void* direction;       /* [3n] unit (the caller normalises, as Dir3 does) */
+    const void* max_distance;    /* [n] */
+    const uint8_t* solid;        /* [n] 1: an origin inside a shape hits at distance 0 */
+    avn_spatial_filter filter;
+} avn_spatial_rays;
+
+typedef struct avn_spatial_points {
+    uint32_t count;
+    uint32_t flags;
+    const void* point;           /* [3n] */
+    avn_spatial_filter filter;
+} avn_spatial_points;
+
+typedef struct avn_spatial_aabbs {
+    uint32_t count;
+    uint32_t flags;
+    const void* min;             /* [3n] */
+    const void* max;             /* [3n] */
+    avn_spatial_filter filter;
+} avn_spatial_aabbs;
+
+/* RayHitData (ray_caster.rs) with the collider's table index */
+typedef struct avn_spatial_hit_f32 {
+    uint32_t collider;   /* slot of the last avn_colliders_upload; AVN_SPATIAL_MISS = no hit (entity too; distance and normal 0) */
+    uint32_t entity;     /* entity_index as uploaded */
+    float distance;      /* time_of_impact */
+    float normal[3];     /* world space */
+} avn_spatial_hit_f32;
+typedef struct avn_spatial_hit_f64 {
+    uint32_t collider;
+    uint32_t entity;
+    double distance;
+    double normal[3];
+} avn_spatial_hit_f64;
+
+typedef struct avn_spatial_hits_out {
+    void* hits;          /* avn_spatial_hit_fNN [n] (cast_rays) or [n * max_hits] (ray_hits; unused slots are misses) */
+    uint32_t* count;     /* [n] true number of hits (ray_hits); ignored by cast_rays */
+} avn_spatial_hits_out;
+
+typedef struct avn_spatial_ids_out {
+    uint32_t* collider;  /* [n * cap] collider indices, ascending, AVN_SPATIAL_MISS past the count */
+    uint32_t* count;     /* [n] true number of colliders */
+} avn_spatial_ids_out;
+
+typedef struct avn_spatial_stats {
+    uint32_t colliders;        /* colliders in the snapshot */
+    uint32_t nodes;            /* BVH nodes (2 * colliders - 1) */
+    uint32_t host_skipped;     /* AVN_SHAPE_HOST colliders in the snapshot (never candidates) */
+    uint32_t valid;            /* 1: the snapshot can be queried */
+    uint64_t nodes_visited;    /* last query call: node boxes tested, all queries together */
+    uint64_t leaves_visited;   /* last query call: exact per-collider tests run, all queries together */
+} avn_spatial_stats;
+
+/* update_spatial_query_pipeline / SpatialQueryPipeline::update (pipeline.rs:96-133): builds the LBVH from the poses the device holds when the
+ * call runs, enqueued on the world's stream after any step work.  avn_step never calls it. */
+AVN_API avn_status avn_spatial_update(avn_world* w);
+/* SpatialQueryPipeline::cast_ray (pipeline.rs:162-231); RayCaster with max_hits = 1: per ray the closest hit within max_distance, or a miss */
+AVN_API avn_status avn_spatial_cast_rays(avn_world* w, const avn_spatial_rays* rays, const avn_spatial_hits_out* out);
+/* SpatialQueryPipeline::ray_hits (pipeline.rs:233-333); RayCaster / RayHits: per ray the max_hits nearest hits, sorted, plus the true count.
+ * 1 <= max_hits <= AVN_SPATIAL_MAX_HITS, else AVN_ERR_BAD_ARG. */
+AVN_API avn_status avn_spatial_ray_hits(avn_world* w, const avn_spatial_rays* rays, uint32_t max_hits, const avn_spatial_hits_out* out);
+/* SpatialQueryPipeline::point_intersections (pipeline.rs:628-689): per point the colliders containing it */
+AVN_API avn_status avn_spatial_point_intersections(avn_world* w, const avn_spatial_points* points, uint32_t cap, const avn_spatial_ids_out* out);
+/* SpatialQueryPipeline::aabb_intersections_with_aabb (pipeline.rs:691-742): per box the colliders whose shape AABB intersects it */
+AVN_API avn_status avn_spatial_aabb_intersections(avn_world* w, const avn_spatial_aabbs* boxes, uint32_t cap, const avn_spatial_ids_out* out);
+/* snapshot sizes and the traversal counters of the last query call */
+AVN_API avn_status avn_spatial_stats_get(avn_world* w, avn_spatial_stats* out);
+
+#ifdef __cplusplus
+}
+#endif
+
+#endif /* AVIAN_MI355X_SPATIAL_H */

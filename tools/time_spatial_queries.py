@@ -1,0 +1,125 @@
+#!/usr/bin/env python3
+"""Timing of the device spatial queries (include/avian_mi355x_spatial.h); prints one JSON object.
+
+  avn_spatial_update at cfg2 (100 k cuboids after 20 closed-loop steps) and cfg4 (10^6 mixed, sparse_mixed)
+  cast_rays, 10^6 random rays into cfg2: short (sensor-like, <= 2 m) and long (through the pile)
+  ray_hits k = 16, 64 k rays;  point and AABB intersections, 10^6 queries each
+
+Every figure is the median over `reps` warmed-up calls.  The queries take torch tensors on the GPU (AVN_SPATIAL_DEVICE_POINTERS: no
+staging copies), so a call is its launches plus one stream synchronisation; the update is timed with avn_synchronize behind it.  Device
+events bracket the calls on torch's stream after a synchronisation of it, which the library's own stream joins at the call's end.
+bytes_floor: the bytes each call must move at least (inputs, outputs, the snapshot records a query touches once), for a roofline fraction
+against MI355X's 8 TB/s HBM.
+usage: python tools/time_spatial_queries.py [reps]"""
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+R = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, R)
+import torch  # noqa: E402
+import avian_amd  # noqa: E402
+from avian_amd import _ffi as F, scenes  # noqa: E402
+from avian_amd.spatial_query import SpatialQuery  # noqa: E402
+
+HBM = 8.0e12
+
+
+def timed(fn, reps):
+    fn()   # warm-up
+    torch.cuda.synchronize()
+    out = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0 = time.perf_counter()
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        wall = (time.perf_counter() - t0) * 1e3
+        out.append(max(a.elapsed_time(b), 0.0) or wall)
+    return float(np.median(out))
+
+
+def world(sc, steps):
+    lib = avian_amd.load_library()
+    w = F.World(lib, F.default_config(32, substeps=4))
+    w.bodies_upload(**sc.body_kwargs()); w.colliders_upload(**sc.collider_kwargs())
+    w.existing_pairs_upload(np.zeros(0, np.uint64)); w.collider_materials_upload(friction=0.5)
+    if steps:
+        w.pipeline_enable()
+        for _ in range(steps):
+            w.step()
+    w.synchronize()
+    return w
+
+
+def main():
+    reps = int(sys.argv[1]) if len(sys.argv) > 1 else 10
+    dev = torch.device("cuda", 0)
+    res = {"reps": reps, "timing": "median ms per call (device events on torch's stream around a synchronous call)"}
+    w2 = world(scenes.box_stack(50, 40, 50), 20)
+    C = w2.n_colliders
+    sq = SpatialQuery(w2)
+
+    def upd():
+        sq.update(); w2.synchronize()
+    res["update_cfg2_ms"] = timed(upd, reps)
+    res["update_cfg2_colliders"] = C
+    b = w2.bodies_download()
+    pos = torch.from_numpy(b["position"]).to(dev)
+    g = torch.Generator(device=dev).manual_seed(1)
+    n = 1_000_000
+    o = pos[torch.randint(1, C, (n,), device=dev, generator=g)] + torch.randn(n, 3, device=dev, generator=g) * 0.7
+    d = torch.nn.functional.normalize(torch.randn(n, 3, device=dev, generator=g), dim=1)
+    solid = torch.ones(n, dtype=torch.uint8, device=dev)
+    short = torch.rand(n, device=dev, generator=g) * 2.0
+    long = torch.full((n,), 200.0, device=dev)
+    rec = 24
+    for name, md in (("short", short), ("long", long)):
+        ms = timed(lambda: sq.cast_rays(o, d, md, solid), reps)
+        st = sq.stats()
+        res[f"cast_rays_{name}_rays_per_s"] = n / (ms * 1e-3)
+        res[f"cast_rays_{name}_ms"] = ms
+        res[f"cast_rays_{name}_leaves_per_ray"] = st.leaves_visited / n
+        res[f"cast_rays_{name}_nodes_per_ray"] = st.nodes_visited / n
+        res[f"cast_rays_{name}_bytes_floor"] = n * (28 + 1 + rec)
+    nk = 65536
+    ms = timed(lambda: sq.ray_hits(o[:nk], d[:nk], 16, long[:nk], solid[:nk]), reps)
+    res["ray_hits_k16_64k_ms"] = ms
+    res["ray_hits_k16_64k_rays_per_s"] = nk / (ms * 1e-3)
+    res["ray_hits_k16_leaves_per_ray"] = sq.stats().leaves_visited / nk
+    res["ray_hits_k16_bytes_floor"] = nk * (28 + 1 + 16 * rec + 4)
+    p = o
+    ms = timed(lambda: sq.point_intersections(p, 8), reps)
+    res["points_1m_ms"] = ms
+    res["points_per_s"] = n / (ms * 1e-3)
+    res["points_bytes_floor"] = n * (12 + 8 * 4 + 4)
+    ext = torch.rand(n, 3, device=dev, generator=g)
+    lo, hi = p - ext, p + ext
+    ms = timed(lambda: sq.aabb_intersections(lo, hi, 16), reps)
+    res["aabbs_1m_ms"] = ms
+    res["aabbs_per_s"] = n / (ms * 1e-3)
+    res["aabbs_bytes_floor"] = n * (24 + 16 * 4 + 4)
+    res["update_bytes_floor_per_collider"] = 4 * 16 + 16 + 8 + 4 * 16 + 2 * 16 + 2 * 2 * 16 + 8 + 12
+    for k in [k for k in res if k.endswith("_bytes_floor")]:
+        msk = k.replace("_bytes_floor", "_ms") if k.replace("_bytes_floor", "_ms") in res else None
+        if msk:
+            res[k.replace("_bytes_floor", "_hbm_fraction")] = res[k] / (res[msk] * 1e-3) / HBM
+    del sq, w2
+    w4 = world(scenes.sparse_mixed(1_000_000), 0)
+    sq4 = SpatialQuery(w4)
+
+    def upd4():
+        sq4.update(); w4.synchronize()
+    res["update_cfg4_ms"] = timed(upd4, reps)
+    res["update_cfg4_colliders"] = w4.n_colliders
+    res["update_cfg2_hbm_fraction"] = res["update_bytes_floor_per_collider"] * C / (res["update_cfg2_ms"] * 1e-3) / HBM
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
