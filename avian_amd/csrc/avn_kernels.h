@@ -409,7 +409,7 @@ template <class T> struct SP {
     Vec4<T>* pos;            // [n] snapshot pose of collider i: (position.xyz, 0)
     Vec4<T>* rot;            // [n] rotation xyzw
     Vec4<T>* he;             // [n] (half_extents.xyz | radius, 0)
-    uint4* info;             // [n] (entity, memberships, shape, 1 = candidate | 0 = AVN_SHAPE_HOST)
+    uint4* info;             // [n] (entity, memberships, shape, 1 = candidate | 0 = AVN_SHAPE_HOST or a non-finite pose / shape AABB)
     Vec4<T>* smin;           // [n] padded shape AABB of collider i (empty = +inf / -inf: host shapes, non-finite poses)
     Vec4<T>* smax;
     Vec4<T>* bmin;           // [2n-1] node boxes (a leaf: its collider's smin / smax)

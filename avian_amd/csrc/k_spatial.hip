@@ -15,8 +15,11 @@
 // Queries: one lane per query, a per-lane DFS stack in LDS (64 entries: the depth of a Karras tree over unique 64-bit keys is at most 64).
 // The BVH only culls; every answer is the exact per-collider test below, so the result equals a brute-force pass with the same tests.  A
 // leaf box is the exact shape AABB grown by 64 eps * its largest coordinate, and every node test of a query grows the node box by 64 eps
-// * the query's largest coordinate: the rounding of shape_aabb, of the local-frame transform and of the slab test are all a few eps of
-// those magnitudes, so no point that an exact test accepts lies outside the boxes the traversal tests.
+// * the query's largest coordinate: the rounding of shape_aabb, of the local-frame transform, of the slab test and of the ball's
+// discriminant (taken as a (r^2 - |f|^2) with f = o_l - d_l (b / a), whose error grows with |o_l|, not with |o_l|^2 as parry's b^2 - a c
+// does) are all a few eps of those magnitudes, so no point that an exact test accepts lies outside the boxes the traversal tests.
+// Non-finite data never reaches an exact test: a collider with a non-finite position, rotation or shape AABB is not a candidate and has
+// an empty leaf box; a query with a non-finite origin, direction, point or box corner answers a miss / count 0 without traversing.
 #include "avn_kernels.h"
 #include "../../include/avian_mi355x_spatial.h"
 
@@ -54,13 +57,15 @@ __global__ __launch_bounds__(256) void k_sp_snapshot(DW<T> w, BP<T> bp, SP<T> sp
     sp.pos[c] = make4<T>(pos, T(0));
     sp.rot[c] = make4<T>(rot);
     sp.he[c] = make4<T>(h, T(0));
-    const bool native = shape != AVN_SHAPE_HOST;
-    sp.info[c] = make_uint4(ci.x, bp.col_layers[c].x, shape, native ? 1u : 0u);
+    // a candidate has device geometry and a finite position, rotation and shape AABB; the others get an empty leaf box and never reach
+    // an exact test
+    bool candidate = false;
     V3<T> mn{sp_inf<T>(), sp_inf<T>(), sp_inf<T>()}, mx{-sp_inf<T>(), -sp_inf<T>(), -sp_inf<T>()};
-    if (native) {
+    if (shape != AVN_SHAPE_HOST && is_finite(pos) && is_finite(V3<T>{rot.x, rot.y, rot.z}) && finite_t(rot.w)) {
         V3<T> a, b;
         shape_aabb<T>(shape, h, pos, rot, a, b);
         if (is_finite(a) && is_finite(b)) {
+            candidate = true;
             const T pad = T(64) * Limits<T>::eps * smax(sp_maxabs(a), sp_maxabs(b));
             const V3<T> pp{pad, pad, pad};
             mn = a - pp; mx = b + pp;
@@ -69,6 +74,7 @@ __global__ __launch_bounds__(256) void k_sp_snapshot(DW<T> w, BP<T> bp, SP<T> sp
             atomicMax(&sp.bounds[3], sp_fkey((float)m.x)); atomicMax(&sp.bounds[4], sp_fkey((float)m.y)); atomicMax(&sp.bounds[5], sp_fkey((float)m.z));
         }
     }
+    sp.info[c] = make_uint4(ci.x, bp.col_layers[c].x, shape, candidate ? 1u : 0u);
     sp.smin[c] = make4<T>(mn, T(0));
     sp.smax[c] = make4<T>(mx, T(0));
 }
@@ -86,7 +92,7 @@ __global__ __launch_bounds__(256) void k_sp_morton(SP<T> sp) {
         for (int k = 0; k < 3; ++k) {
             const float ext = hi[k] - lo[k];
             float f = ext > 0.0f ? (m[k] - lo[k]) / ext * 1024.0f : 0.0f;
-            f = f < 0.0f ? 0.0f : (f > 1023.0f ? 1023.0f : f);
+            f = f > 0.0f ? (f < 1023.0f ? f : 1023.0f) : 0.0f;   // (NaN -> 0: f64 centres beyond FLT_MAX are inf as floats)
             q[k] = (uint32_t)f;
         }
         code = (sp_expand10(q[0]) << 2) | (sp_expand10(q[1]) << 1) | sp_expand10(q[2]);
@@ -191,7 +197,10 @@ __device__ __forceinline__ bool sp_ray_exact(uint32_t shape, V3<T> he, V3<T> pos
         const T r = he.x;
         const T a = dot(dl, dl), b = dot(ol, dl), c = dot(ol, ol) - r * r;
         if (c > T(0) && b > T(0)) return false;
-        const T delta = b * b - a * c;
+        // b^2 - a c in its well-conditioned form: f is the origin's offset from the ray's closest point to the centre, so the rounding
+        // grows with |ol|, not |ol|^2 (parry's b^2 - a c cancels two terms of size |ol|^2 and misjudges far grazing rays)
+        const V3<T> f = ol - dl * (b / a);
+        const T delta = a * (r * r - dot(f, f));
         if (delta < T(0)) return false;
         const T sq = sqrt_t(delta);
         t = (-b - sq) / a;
@@ -233,6 +242,7 @@ __device__ __forceinline__ bool sp_ray_exact(uint32_t shape, V3<T> he, V3<T> pos
         if (axis < 0) zero_normal = true;
         else nl = V3<T>{axis == 0 ? sg : T(0), axis == 1 ? sg : T(0), axis == 2 ? sg : T(0)};
     }
+    if (!finite_t(t)) return false;   // a hit needs a finite distance (max_distance = +inf stays legal)
     toi = t;
     normal = zero_normal ? vzero<T>() : qrot(rot, nl);
     return true;
@@ -310,6 +320,8 @@ __global__ __launch_bounds__(SP_WAVE) void k_sp_query(SP<T> sp, SQ<T> q) {
             r.tol = T(64) * Limits<T>::eps * sp_maxabs(pa);
         }
         if (KIND == SPQ_POINTS) tol = T(64) * Limits<T>::eps * sp_maxabs(pa);
+        // a non-finite origin, direction, point or box corner answers a miss / count 0 without traversing the tree
+        const bool finite_query = is_finite(pa) && (KIND == SPQ_POINTS || is_finite(pb));
         // results
         T best = sp_inf<T>();
         uint32_t best_c = AVN_SPATIAL_MISS;
@@ -369,7 +381,8 @@ __global__ __launch_bounds__(SP_WAVE) void k_sp_query(SP<T> sp, SQ<T> q) {
             }
         };
 
-        if (n == 1) {
+        if (!finite_query) {
+        } else if (n == 1) {
             if (test(0) != sp_inf<T>()) leaf(0);
         } else if (n > 1 && test(0) != sp_inf<T>()) {
             uint32_t sp_top = 0, node = 0;

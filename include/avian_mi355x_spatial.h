@@ -21,12 +21,27 @@
  *    exit the smallest t_far (strict <).  An axis with d == 0 is a parallel slab: a miss when the origin lies outside it.  A miss when
  *    entry > exit or exit < 0.  Origin inside (entry < 0): solid -> distance 0, normal 0; not solid -> the exit distance and the exit
  *    face's normal.  Otherwise the entry distance and the entry face's outward normal.
- *  - ball: parry's ray_toi_with_ball: a = |d|^2, b = o.d, c = |o|^2 - r^2; a miss when c > 0 && b > 0 or b^2 - a c < 0; t = (-b - sqrt) / a;
- *    t <= 0 (inside): solid -> 0 with normal 0, else (-b + sqrt) / a.  The normal is (o + d t) / |o + d t| (0 when that is 0).
- *  - a hit counts when distance <= max_distance; the local normal is rotated back to world space.
+ *  - ball: parry's ray_toi_with_ball with its discriminant in a well-conditioned form: a = |d|^2, b = o.d, c = |o|^2 - r^2; a miss when
+ *    c > 0 && b > 0; delta = a (r^2 - |f|^2) with f = o - d (b / a), the offset of the ray's point nearest the centre; a miss when
+ *    delta < 0; t = (-b - sqrt(delta)) / a; t <= 0 (inside): solid -> 0 with normal 0, else (-b + sqrt(delta)) / a.  The normal is
+ *    (o + d t) / |o + d t| (0 when that is 0).  delta equals parry's b^2 - a c in exact arithmetic; parry's form rounds with an error of
+ *    eps |o|^2 (far from the ball it accepts rays that miss by a whole radius), this one with eps |o| r, so the two decide differently only
+ *    inside the band where parry's own rounding decides.
+ *  - a hit counts when its distance is finite and <= max_distance (max_distance = +inf is legal); the local normal is rotated back to
+ *    world space.
  *  - point containment: |p_l.i| <= he.i for a cuboid, |p_l|^2 <= r^2 for a ball.
  *  - AABB: the collider's exact shape AABB at the snapshot pose (the broad phase's shape_aabb, no margins) intersects the query box
  *    (min <= other.max && max >= other.min per axis).
+ *
+ * Non-finite inputs (NaN or inf components):
+ *  - a collider whose snapshot position, rotation or shape AABB is not finite is never a candidate (it keeps its collider index);
+ *  - a query whose origin, direction, point or box corner is not finite answers a miss (ray queries) or a count of 0, whatever the scene;
+ *  - a hit needs a finite distance.
+ *  Answers to finite inputs do not depend on these rules.
+ *
+ * Accuracy: every answer is the exact test above in the world's scalar type.  tests/spatial_exact_geometry.py states the forward-error
+ * bound the answers are held to against exact rational geometry (a few eps times the magnitudes of the ray, the pose, the shape and the
+ * distance; for balls, plus the grazing term of the square root).
  *
  * Snapshot rules:
  *  - a query before any avn_spatial_update, or after avn_bodies_upload / avn_colliders_upload / avn_collider_transforms_upload /

@@ -93,8 +93,14 @@ class Snapshot:
         self.memberships = np.ones(len(self.shape), np.uint32) if m is None else np.asarray(m, np.uint32)
         self.n = len(self.shape)
 
+    def finite(self):
+        """k_sp_snapshot's candidate flag: a finite position, rotation and shape AABB (the header's non-finite contract)."""
+        with np.errstate(all="ignore"):
+            mn, mx = shape_aabb(self.shape, self.he, self.pos, self.rot, self.dt)
+        return np.logical_and.reduce([np.isfinite(x) for x in self.pos + self.rot + mn + mx])
+
     def candidates(self, mask=0xFFFFFFFF, excluded=()):
-        ok = (self.shape != SHAPE_HOST) & ((self.memberships & np.uint32(mask)) != 0)
+        ok = (self.shape != SHAPE_HOST) & self.finite() & ((self.memberships & np.uint32(mask)) != 0)
         if len(excluded):
             ok &= ~np.isin(self.entity, np.asarray(excluded, np.uint32))
         return ok
@@ -129,7 +135,8 @@ def ray_exact(shape, he, pos, rot, o, d, max_distance, solid, dt):
         # ball (parry ray_toi_with_ball)
         r = he[0]
         a, b, c = dot(dl, dl), dot(ol, dl), dot(ol, ol) - r * r
-        delta = b * b - a * c
+        f = sub(ol, scale(dl, b / a))          # b^2 - a c in its well-conditioned form
+        delta = a * (r * r - dot(f, f))
         b_ok = ~((c > zero) & (b > zero)) & ~(delta < zero)
         sq = np.sqrt(delta)
         tb = (-b - sq) / a
@@ -167,7 +174,7 @@ def ray_exact(shape, he, pos, rot, o, d, max_distance, solid, dt):
         c_zero = axis < 0
         is_ball = shape == SHAPE_BALL
         toi = np.where(is_ball, tb, tc)
-        hit = np.where(is_ball, b_ok, c_ok) & (toi <= max_distance) & (shape != SHAPE_HOST)
+        hit = np.where(is_ball, b_ok, c_ok) & (toi <= max_distance) & np.isfinite(toi) & (shape != SHAPE_HOST)
         nloc = tuple(np.where(is_ball, x, y) for x, y in zip(nb, nl))
         zn = np.where(is_ball, b_zero, c_zero)
         nw = qrot(rot, nloc, dt)
@@ -191,11 +198,16 @@ def aabb_exact(shape, he, pos, rot, qmin, qmax, dt):
 
 
 # ---- brute-force queries ----------------------------------------------------------------------------------------------------------------
-def _masks(s: Snapshot, n, mask, excluded):
-    base = s.candidates(0xFFFFFFFF, excluded)
+def _masks(s: Snapshot, n, mask, excluded, finite_query):
+    """Candidates per (query, collider); a query whose inputs are not all finite has none (k_sp_query's guard)."""
+    base = s.candidates(0xFFFFFFFF, excluded)[None, :] & np.asarray(finite_query, bool).reshape(n, 1)
     if mask is None:
-        return np.broadcast_to(base, (n, s.n))
-    return base[None, :] & ((s.memberships[None, :] & np.asarray(mask, np.uint32)[:, None]) != 0)
+        return base
+    return base & ((s.memberships[None, :] & np.asarray(mask, np.uint32)[:, None]) != 0)
+
+
+def _finite_rows(*arrays):
+    return np.logical_and.reduce([np.isfinite(a).all(axis=1) for a in arrays])
 
 
 def _ray_all(s: Snapshot, origin, direction, max_distance, solid, mask, excluded, chunk):
@@ -204,7 +216,7 @@ def _ray_all(s: Snapshot, origin, direction, max_distance, solid, mask, excluded
     n = len(origin)
     max_distance = np.full(n, np.inf, dt) if max_distance is None else np.asarray(max_distance, dt)
     solid = np.ones(n, bool) if solid is None else np.asarray(solid) != 0
-    cand = _masks(s, n, mask, excluded)
+    cand = _masks(s, n, mask, excluded, _finite_rows(origin, direction))
     for a in range(0, n, chunk):
         b = min(n, a + chunk)
         o = tuple(origin[a:b, i][:, None] for i in range(3)); d = tuple(direction[a:b, i][:, None] for i in range(3))
@@ -260,7 +272,7 @@ def _ids(hits_rows, cap):
 def point_intersections(s: Snapshot, points, cap, mask=None, excluded=(), chunk=64):
     dt = s.dt
     points = np.asarray(points, dt).reshape(-1, 3)
-    cand = _masks(s, len(points), mask, excluded)
+    cand = _masks(s, len(points), mask, excluded, _finite_rows(points))
     rows = []
     for a in range(0, len(points), chunk):
         p = tuple(points[a:a + chunk, i][:, None] for i in range(3))
@@ -272,7 +284,7 @@ def aabb_intersections(s: Snapshot, qmin, qmax, cap, mask=None, excluded=()):
     dt = s.dt
     qmin = np.asarray(qmin, dt).reshape(-1, 3); qmax = np.asarray(qmax, dt).reshape(-1, 3)
     mn, mx = shape_aabb(s.shape, s.he, s.pos, s.rot, dt)
-    cand = _masks(s, len(qmin), mask, excluded)
+    cand = _masks(s, len(qmin), mask, excluded, _finite_rows(qmin, qmax))
     ok = np.ones((len(qmin), s.n), bool)
     for i in range(3):
         ok &= (mn[i][None, :] <= qmax[:, i][:, None]) & (mx[i][None, :] >= qmin[:, i][:, None])
@@ -303,3 +315,44 @@ def ray_queries(s: Snapshot, origin, direction, ks=(), max_distance=None, solid=
                 for j, rec in enumerate(recs[:k]):
                     h[a + r, j] = rec
     return closest, many
+
+
+# ---- the tree's node tests (k_spatial.hip: k_sp_snapshot's padded leaf box, sp_ray_box, sp_point_box) -------------------------------------
+def leaf_boxes(s: Snapshot):
+    """The leaf box of every collider: the shape AABB grown by 64 eps * its largest coordinate; empty (+inf / -inf) for non-candidates."""
+    dt = s.dt
+    with np.errstate(all="ignore"):
+        mn, mx = shape_aabb(s.shape, s.he, s.pos, s.rot, dt)
+        m = np.maximum.reduce([np.abs(x) for x in mn + mx])
+        pad = dt(64) * dt(np.finfo(dt).eps) * m
+        ok = (s.shape != SHAPE_HOST) & s.finite()
+        lo = tuple(np.where(ok, x - pad, dt(np.inf)) for x in mn)
+        hi = tuple(np.where(ok, x + pad, dt(-np.inf)) for x in mx)
+    return lo, hi
+
+
+def ray_box(o, d, lo, hi, limit, dt):
+    """sp_ray_box with the query's tolerance 64 eps * max |o|: the entry distance into the grown box, +inf for a miss (broadcasting)."""
+    with np.errstate(all="ignore"):
+        tol = dt(64) * dt(np.finfo(dt).eps) * np.maximum(np.maximum(np.abs(o[0]), np.abs(o[1])), np.abs(o[2]))
+        tmin, tmax = dt(-np.inf), dt(np.inf)
+        miss = np.zeros(np.broadcast(o[0], lo[0], limit).shape, bool)
+        for i in range(3):
+            l, h, oi, di = lo[i] - tol, hi[i] + tol, o[i], d[i]
+            zero = di == dt(0)
+            iv = np.where(zero, dt(0), dt(1) / np.where(zero, dt(1), di))
+            t1, t2 = (l - oi) * iv, (h - oi) * iv
+            neg = iv < dt(0)
+            t1, t2 = np.where(neg, t2, t1), np.where(neg, t1, t2)
+            miss |= zero & ~((oi >= l) & (oi <= h))
+            # smax / smin: NaN-ignoring (a NaN of t1 / t2 leaves the bound as it was)
+            tmin = np.where(zero | (tmin > t1) | np.isnan(t1), tmin, t1)
+            tmax = np.where(zero | (tmax < t2) | np.isnan(t2), tmax, t2)
+        miss |= ~(tmin <= tmax) | (tmax < dt(0)) | ~(tmin <= limit)
+        return np.where(miss, dt(np.inf), np.maximum(tmin, dt(0)))
+
+
+def point_box(p, lo, hi, dt):
+    """sp_point_box with the query's tolerance 64 eps * max |p| (broadcasting)."""
+    tol = dt(64) * dt(np.finfo(dt).eps) * np.maximum(np.maximum(np.abs(p[0]), np.abs(p[1])), np.abs(p[2]))
+    return np.logical_and.reduce([(p[i] >= lo[i] - tol) & (p[i] <= hi[i] + tol) for i in range(3)])
