@@ -5,7 +5,10 @@ restatement makes of it must equal the oracle's state after the system, bit for 
 physically inconsistent manifolds that reach every branch (speculative points, clamped friction, non-finite tangent masses, locked axes,
 dominance, sleeping / disabled / static / kinematic bodies, an overflow colour).  The reference holds no vectors for these rows
 (SURVEY.md §8c); two programs by one author agreeing is what the parity suite shows, a third written without looking at either is what can be
-added here."""
+added here.
+
+Joints: this file holds the distance and the fixed joint bit for bit.  Revolute, spherical and prismatic joints, joint damping, the velocity projection and the
+joint forces (rows a19-a23) have their independent check, with a tolerance from the reference's own rounding noise, in tests/test_joint_projection_cpu.py."""
 import numpy as np
 import pytest
 
