@@ -256,6 +256,7 @@ template <class T> struct World : WorldBase {
         std::memset(grid_blocks, 0, sizeof grid_blocks);
     }
     ~World() override {
+        (void)isl.split_join();   // (the asynchronous split walk of the last step reads pin_adj2's CSR: the worker is joined before any member is released)
         if (stream) (void)hipStreamSynchronize(stream);
         if (stream_bp) (void)hipStreamSynchronize(stream_bp);
         drop_graph();
@@ -270,6 +271,7 @@ template <class T> struct World : WorldBase {
         if (h_pg_error) (void)hipHostFree(h_pg_error);
         for (hipEvent_t e : {ev_np_fork, ev_np_old, ev_slot_clear}) if (e) (void)hipEventDestroy(e);
         for (hipEvent_t e : {ev_side_fork, ev_side_done}) if (e) (void)hipEventDestroy(e);
+        for (hipEvent_t e : {ev_adj, ev_adj_go}) if (e) (void)hipEventDestroy(e);
         if (stream_side) { (void)hipStreamSynchronize(stream_side); (void)hipStreamDestroy(stream_side); }
         if (stream) (void)hipStreamDestroy(stream);
     }

@@ -12,6 +12,8 @@
         }
         uint32_t n = b->count;
         bool moved = false;
+        // the sharded closed loop's owner table (dsh_owner / b_dsh_owner / dsh_list) is per body and fixed at avn_dshard_enable: k_pg_local_lists reads owner[body]
+        if (dsh_on && n != dw.n_bodies) { error = "bodies_upload: another body count inside a sharded closed loop (avn_dshard_enable named an owner per body): avn_dshard_enable(NULL), restart the loop (avn_pipeline_enable(0), uploads, avn_pipeline_enable(1)), avn_dshard_enable with the new owners"; return AVN_ERR_STATE; }
         if (despawn_needs_bodies && n != despawn_expected_bodies) { error = "bodies_upload: after avn_despawn exactly the remaining bodies must be uploaded"; return AVN_ERR_STATE; }
         const bool after_despawn = despawn_needs_bodies;   // (the library has renumbered everything it holds for exactly this upload)
         if (pipe_on && have_bodies && n < dw.n_bodies && !after_despawn) {
@@ -106,6 +108,7 @@
         incidence_dirty = true;
         have_bodies = true;
         despawn_needs_bodies = false;
+        if (dsh_on) { avn_status sd = dsh_apply_flags(); if (sd != AVN_OK) return sd; }   // (the pack wrote the uploader's flags: AVN_BODY_FOREIGN and the host's SolverBody mirror again)
         HIPCHK(hipStreamSynchronize(stream));  // host arrays are only borrowed for the call
         return AVN_OK;
     }

@@ -127,7 +127,8 @@
         h_changes.clear();
         if (!n_active) return AVN_OK;
         uint32_t* d_count = b_misc.as<uint32_t>() + 40;
-        const NpHostList hl = hs_begin(stream);
+        NpHostList hl;
+        { const avn_status sb = hs_begin(stream, &hl); if (sb != AVN_OK) return sb; }
         launch_narrow_phase<T>(dw, bp, ct, params, b_active.as<uint32_t>(), n_active, b_changes.as<avn_contact_change>(), d_count, stream, hl);
         ++launches;
         HIPCHK(hipGetLastError());
@@ -191,6 +192,7 @@
     void set_color_offsets(const uint32_t* offsets) {
         if (!use_handles && std::memcmp(color_offsets, offsets, sizeof color_offsets) != 0) graph_valid = false;  // (ranges captured as kernel arguments; handle mode reads them from the device)
         std::memcpy(color_offsets, offsets, sizeof color_offsets);
+        l2_built_for = 0xFFFFFFFFu;   // (level 2: the overflow colour's manifolds or its start may have changed under the same total count -- regroup by level)
         {
             const uint32_t n23 = color_offsets[AVN_COLOR_OVERFLOW_INDEX + 1] - color_offsets[AVN_COLOR_OVERFLOW_INDEX];
             const uint32_t need = (n23 + 63u) / 64u;

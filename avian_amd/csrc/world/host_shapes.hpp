@@ -77,13 +77,15 @@
     }
     // ---- update_contacts' half ----
     // before the step's first narrow-phase launch: the list is empty
-    NpHostList hs_begin(hipStream_t s) {
+    avn_status hs_begin(hipStream_t s, NpHostList* out) {
         hs_launches.clear();
         NpHostList l;
-        if (hs_any()) { (void)hipMemsetAsync(b_hs_cnt.p, 0, 4, s); l = hs_list(); }
-        if (hk_begin(l, s) != AVN_OK) l.hook = NpHookList();   // (collision hooks, world/hooks.hpp: phase 1 rides the same launches)
-        l.locals = tf_any;                                      // (child colliders: the HS instantiations compute their poses)
-        return l;
+        if (hs_any()) { HIPCHK(hipMemsetAsync(b_hs_cnt.p, 0, 4, s)); l = hs_list(); }
+        const avn_status st = hk_begin(l, s);   // (collision hooks, world/hooks.hpp: phase 1 rides the same launches; a failure fails the step instead of skipping the hooks)
+        if (st != AVN_OK) return st;
+        l.locals = tf_any;                       // (child colliders: the HS instantiations compute their poses)
+        *out = l;
+        return AVN_OK;
     }
     NpHookList hk_phase1() const { NpHookList h; if (hk_modify_active() && b_hk_cnt.p) { h.count = b_hk_cnt.as<uint32_t>(); h.phase = 1; } return h; }
     NpHostList hs_list(uint32_t host_only = 0) const {

@@ -32,6 +32,7 @@
         HIPCHK(hipStreamSynchronize(stream));
         l2_levels = std::max(n_levels, 1u);
         l2_level_of.assign(level_of, level_of + count);
+        l2_built_for = 0xFFFFFFFFu;   // (another assignment with the same manifold count and level count must still regroup l2_order)
         halo = HaloPlan(); halo_on = false;   // (a plan uploaded before counted other slots)
         drop_graph();
         return AVN_OK;
@@ -53,7 +54,7 @@
         l2_built_for = dw.n_manifolds;
         return AVN_OK;
     }
-    uint32_t l2_built_for = 0xFFFFFFFFu;
+    uint32_t l2_built_for = 0xFFFFFFFFu;   // dw.n_manifolds l2_order was grouped for; reset by every upload that can change the overflow colour or its levels
     DevBuf b_halo_send, b_halo_recv, b_halo_out, b_halo_in;
     bool halo_on = false;
 #ifdef AVN_MEASURE   // measurement build only (make measure): the default library has no switch that changes results
@@ -90,7 +91,8 @@
         b_halo_send.ensure(std::max<size_t>(halo.send.size(), 1) * 4, err); if (err != hipSuccess) { error = "hipMalloc failed"; return AVN_ERR_OOM; }
         b_halo_recv.ensure(std::max<size_t>(halo.recv.size(), 1) * 4, err); if (err != hipSuccess) { error = "hipMalloc failed"; return AVN_ERR_OOM; }
         b_halo_out.ensure(std::max<size_t>(halo.send.size(), 1) * 4 * sizeof(V), err); if (err != hipSuccess) { error = "hipMalloc failed"; return AVN_ERR_OOM; }
-        b_halo_in.ensure(std::max<size_t>(halo.recv.size(), 1) * 4 * sizeof(V), err);   // (record k of list entry i at 2 i: the joint slot, the LAST slot, spills into the doubled tail) if (err != hipSuccess) { error = "hipMalloc failed"; return AVN_ERR_OOM; }
+        // (record k of list entry i at 2 i: the joint slot, the LAST slot, spills into the doubled tail)
+        b_halo_in.ensure(std::max<size_t>(halo.recv.size(), 1) * 4 * sizeof(V), err); if (err != hipSuccess) { error = "hipMalloc failed"; return AVN_ERR_OOM; }
         if (!halo.send.empty()) HIPCHK(hipMemcpyAsync(b_halo_send.p, halo.send.data(), halo.send.size() * 4, hipMemcpyHostToDevice, stream));
         if (!halo.recv.empty()) HIPCHK(hipMemcpyAsync(b_halo_recv.p, halo.recv.data(), halo.recv.size() * 4, hipMemcpyHostToDevice, stream));
         HIPCHK(hipStreamSynchronize(stream));

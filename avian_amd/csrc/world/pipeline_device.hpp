@@ -402,7 +402,8 @@
         if (np_debug_step >= 0 && (uint32_t)np_debug_step != pipe_step_no) np_params.np_debug = 0u;
         ++pipe_step_no;
         const bool np_overlap = np_overlap_enabled && n_rows_old != 0 && bp.n_intervals != 0;
-        const NpHostList hs_hl = hs_begin(stream);   // (host shapes: the list of this step's pairs whose manifold the host computes -- empty world/host_shapes.hpp when there are none)
+        NpHostList hs_hl;
+        if ((st = hs_begin(stream, &hs_hl)) != AVN_OK) return st;   // (host shapes: the list of this step's pairs whose manifold the host computes -- empty world/host_shapes.hpp when there are none)
         if (np_overlap) {
             if (!ev_np_fork) { HIPCHK(hipEventCreateWithFlags(&ev_np_fork, hipEventDisableTiming | EV_FLAGS)); HIPCHK(hipEventCreateWithFlags(&ev_np_old, hipEventDisableTiming | EV_FLAGS)); }
             HIPCHK(hipEventRecord(ev_np_fork, stream));

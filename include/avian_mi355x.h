@@ -1129,7 +1129,10 @@ typedef struct avn_dshard_config {
     uint32_t n_ranks, rank;
     const int32_t* body_owner;   /* [n_bodies] the rank that simulates the body; -1 = nobody (static bodies: replicated) */
 } avn_dshard_config;
-/* after avn_pipeline_enable(1), before the first step (or between steps with an unchanged body count); cfg = NULL switches it off */
+/* after avn_pipeline_enable(1) and BEFORE the first step that creates a contact pair: afterwards the solver's handle lists are cut incrementally and a new owner
+ * table is refused (AVN_ERR_STATE).  cfg = NULL switches it off at any time; switching it on again then needs a restarted loop (avn_pipeline_enable(0), uploads,
+ * avn_pipeline_enable(1)).  Inside the sharded loop avn_bodies_upload with the SAME body count is allowed between steps (every rank uploads the same arrays; the
+ * owner table stays, foreign bodies stay foreign); another body count is refused (AVN_ERR_STATE, nothing is changed) -- as is avn_despawn. */
 AVN_API avn_status AVN_FN(dshard_enable)(avn_world* w, const avn_dshard_config* cfg);
 /* host-mediated exchange: this rank's bodies (ascending index) as 4 records of 4 scalars each -- (Position, inv mass) (Rotation) (LinearVelocity, gravity scale)
  * (AngularVelocity, linear damping) -- in the world's scalar type; *bytes = n_own x 16 scalars.  unpack writes the records of rank `from_rank`'s bodies. */

@@ -526,6 +526,7 @@ template <class S> struct World : WorldBase {
         if (!b || (b->count && (!b->position || !b->rotation || !b->linear_velocity || !b->angular_velocity || !b->inv_mass ||
                                 !b->inv_inertia_local || !b->rb_type))) { error = "bodies_upload: null array"; return AVN_ERR_BAD_ARG; }
         size_t n = b->count;
+        if (dsh_on && n != bodies.size()) { error = "bodies_upload: another body count inside a sharded closed loop (avn_dshard_enable named an owner per body)"; return AVN_ERR_STATE; }
         if (despawn_needs_bodies && n != bodies.size()) { error = "bodies_upload: after avn_despawn exactly the remaining bodies must be uploaded"; return AVN_ERR_STATE; }
         despawn_needs_bodies = false;
         if (n != bodies.size()) { local_acc_linear.clear(); local_acc_angular.clear(); }   // (header: dropped by an upload with another body count)

@@ -97,6 +97,60 @@ def compare_with_single(single, plan, worlds):
             assert np.array_equal(imp[k][pl.manifolds], gi[k]), f"impulses.{k} of a slab differ from the single world"
 
 
+# ---- re-planning a split that is already running (the level-grouped overflow order is a cache: world/level2.hpp l2_order / l2_built_for) -------------------------------
+def reverse_overflow(pm, offs):
+    """The same colour-major manifold set with the overflow colour's list reversed: the same manifolds, the same bodies, the same colour offsets -- and, because a
+    reversed DAG keeps its longest path, the same NUMBER of overflow levels -- but another solve order, another level per manifold and another per-body CSR."""
+    o0, o1, m = int(offs[F.COLOR_OVERFLOW_INDEX]), int(offs[F.COLOR_OVERFLOW_INDEX + 1]), len(pm["body1"])
+    perm = np.concatenate([np.arange(o0), np.arange(o1 - 1, o0 - 1, -1), np.arange(o1, m)])
+    return {k: np.asarray(v)[perm] for k, v in pm.items()}
+
+
+def replan_split(lib, sc, pm_new, offs, restitution, plan, worlds):
+    """Re-plan running split worlds for `pm_new` (the planner sees the positions the first plan saw, so every world keeps its bodies): per world the local manifolds,
+    then avn_halo_overflow_levels_upload, then avn_halo_plan_upload.  Asserts what makes this a test of the level cache: per world the same local manifold count and
+    colour offsets, the same number of overflow levels, and another level_of array."""
+    new = shard.level2_plan_lib(lib, sc.position, sc.rb_type, pm_new["body1"], pm_new["body2"], offs, len(worlds))
+    for a, b, w in zip(plan, new, worlds):
+        assert np.array_equal(a.bodies, b.bodies) and len(a.manifolds) == len(b.manifolds) and np.array_equal(a.color_offsets, b.color_offsets)
+        assert a.n_overflow_levels == b.n_overflow_levels > 1, (a.n_overflow_levels, b.n_overflow_levels)
+        assert len(a.overflow_level) == len(b.overflow_level) > 1 and not np.array_equal(a.overflow_level, b.overflow_level), "the re-plan must move manifolds to other levels"
+        scenes.upload_manifolds(w, shard.level2_local_manifolds(b, pm_new), b.color_offsets, sc.friction, restitution)
+        b.upload(w)
+    return new
+
+
+def replan_case(lib_split, libs_single, bits, world_size, keep, restitution, seed, control_lib=None, substeps=3):
+    """Split worlds on `lib_split` against unsplit worlds on each of `libs_single`: two steps, the overflow list reversed and re-planned on the RUNNING worlds
+    (every unsplit world gets the reversed set too), two more steps; bit-identical after every step.  control_lib: one more unsplit world that re-uploads the
+    UNCHANGED set at the same moment (so its warm start is reset alike) -- it must then differ from the re-planned one, or the re-plan would not matter."""
+    sc, pm, offs, _ = global_problem(libs_single[-1], 8, 4, 5, seed=seed)
+    offs = overflow_from(offs, keep)
+    singles = [make_single(l, bits, sc, pm, offs, restitution, substeps) for l in libs_single]
+    control = make_single(control_lib, bits, sc, pm, offs, restitution, substeps) if control_lib is not None else None
+    plan, worlds = make_split(lib_split, bits, sc, pm, offs, restitution, substeps, world_size)
+
+    def steps(n):
+        for _ in range(n):
+            for s in singles + ([control] if control is not None else []):
+                s.run_system("SOLVER")
+            step_split_in_process(plan, worlds, substeps, restitution > 0)
+            for s in singles:
+                compare_with_single(s, plan, worlds)
+    steps(2)
+    pm2 = reverse_overflow(pm, offs)
+    plan = replan_split(lib_split, sc, pm2, offs, restitution, plan, worlds)
+    for s in singles:
+        scenes.upload_manifolds(s, pm2, offs, sc.friction, restitution)
+    if control is not None:
+        scenes.upload_manifolds(control, pm, offs, sc.friction, restitution)
+    steps(2)
+    if control is not None:
+        a, b = singles[-1].bodies_download(), control.bodies_download()
+        assert any(not np.array_equal(a[k], b[k]) for k in a), "reversing the overflow list changed no bit: the script cannot see a stale level order"
+    assert float(np.abs(singles[0].bodies_download()["linear_velocity"]).max()) > 0.05
+
+
 def closed_loop_problem(lib, bits, dims, steps, substeps=4, friction=0.5):
     """avian_amd.level2_bench.closed_loop_island (the bench's `--gpus N` leg uses the same set): the device closed loop's own manifolds of a collapsing box stack in
     the host-uploaded form level 2 works on.  Returns (scene with the stepped body state, manifolds, offsets, warm-start impulses)."""

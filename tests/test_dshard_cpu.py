@@ -59,6 +59,22 @@ def test_a_manifold_between_two_ranks_fails_the_step_and_the_refusals():
         w.dshard_bodies_unpack(1, np.zeros((23, 16), np.float32))   # not that rank's body count
 
 
+
+@pytest.mark.parametrize("bits", [32, 64])
+def test_bodies_upload_between_sharded_steps_keeps_the_shares(bits):
+    """The oracle's mirror of avn_bodies_upload inside the sharded loop (has_solver_body keeps `foreign`), with the control that the edit matters."""
+    lib = oracle_lib()
+    bodies, colliders = piles(2, 24)
+    owner = owner_by_pile(bodies, 2, 24)
+    control = D.make_worlds(lib, bits, bodies, colliders, owner, 0)[0]
+    D.reupload_case(lib, bits, bodies, colliders, owner, 2, body=30, dv=(0.7, 0.3, -0.4), control=control)
+
+
+def test_another_body_count_inside_the_sharded_loop_is_refused():
+    lib = oracle_lib()
+    bodies, colliders = piles(2, 24)
+    D.refusals_case(lib, 32, bodies, colliders, owner_by_pile(bodies, 2, 24), 2, enable_is_refused=False)   # (the oracle keeps no incremental lists: it may re-enable)
+
 def test_two_processes_over_gloo(tmp_path):
     """world_size 2 on gloo: each process one rank, the bodies' records through one tensor all-gather per step; the merged result equals the single world"""
     out = str(tmp_path / "dshard.npz")

@@ -32,6 +32,25 @@ def test_piles_over_ranks_equal_the_single_world(bits, n_piles):
     assert ref.pipeline_stats().pairs_removed > 0 and all(w.dshard_stats().own_manifolds > 0 for w in ranks)
 
 
+
+@pytest.mark.parametrize("bits", [32, 64])
+def test_bodies_upload_between_sharded_steps_keeps_the_shares(bits):
+    """avn_bodies_upload inside the sharded loop: the pack rewrites bmeta from the uploader's flags and the host recomputes its SolverBody mirror -- AVN_BODY_FOREIGN
+    and `foreign` must be put back (dsh_apply_flags), or every rank simulates every body.  Ranks == the unsharded HIP world == the unsharded oracle given the same
+    edit, and every rank's own_manifolds stays a proper share that adds up to the whole.  (That the edit changes bits: tests/test_dshard_cpu.py.)"""
+    from helpers import oracle_lib
+    bodies, colliders = piles(2, 24)
+    owner = owner_by_pile(bodies, 2, 24)
+    orc = D.make_worlds(oracle_lib(), bits, bodies, colliders, owner, 0)[0]
+    D.reupload_case(hip_lib(), bits, bodies, colliders, owner, 2, body=30, dv=(0.7, 0.3, -0.4), also=[orc])
+
+
+def test_another_body_count_or_a_late_enable_inside_the_sharded_loop_is_refused():
+    """dsh_owner / b_dsh_owner / dsh_list are sized at avn_dshard_enable and k_pg_local_lists reads owner[body]: another body count is AVN_ERR_STATE, not a read past
+    the table.  avn_dshard_enable after the first pair-creating step is AVN_ERR_STATE as the header says.  The loop goes on unharmed."""
+    bodies, colliders = piles(2, 24)
+    D.refusals_case(hip_lib(), 32, bodies, colliders, owner_by_pile(bodies, 2, 24), 2, enable_is_refused=True)
+
 def test_many_pyramids_over_four_ranks_120_steps():
     sc = scenes.many_pyramids(10, 10, 10)
     owner = np.full(sc.n, -1, np.int32)

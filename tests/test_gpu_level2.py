@@ -52,6 +52,17 @@ def test_overflow_colour_on_shared_bodies_on_hip(bits, world_size, keep, restitu
         compare_with_single(ref, plan, worlds)
 
 
+@pytest.mark.parametrize("bits,world_size,keep,restitution", [(32, 2, 6, 0.0), (64, 3, 3, 0.3)])
+def test_replanning_running_split_worlds_with_the_overflow_list_reversed_on_hip(bits, world_size, keep, restitution):
+    """The level-grouped overflow order (l2_order / b_l2_order, keyed by l2_built_for) must be regrouped when the host re-plans RUNNING worlds: the global overflow
+    list reversed -- per world the same manifold count, the same number of levels, other levels (level2_helpers.replan_split asserts all three) --, local manifolds,
+    avn_halo_overflow_levels_upload and avn_halo_plan_upload again, step on.  Split HIP worlds == the unsplit HIP world == the unsplit oracle, both given the reversed
+    list.  (The script and that the reversal changes bits: tests/test_level2_cpu.py.)"""
+    from level2_helpers import replan_case
+    hip, orc = hip_lib(), oracle_lib()
+    replan_case(hip, [hip, orc], bits, world_size, keep, restitution, seed=bits + world_size)
+
+
 @pytest.mark.parametrize("bits,world_size,damped,keep", [(32, 2, True, None), (32, 3, False, None), (64, 2, True, 6), (32, 4, True, None)])
 def test_joints_on_shared_bodies_on_hip(bits, world_size, damped, keep):
     """Round 6: joints whose bodies are shared between slabs (the joint slot, avn_halo_joint_slot_set).  Split HIP worlds == the unsplit HIP world == the unsplit
@@ -183,6 +194,38 @@ for bits in (32, 64):
     ia, ib = plain.impulses_download(), looped.impulses_download()
     for k in ia:
         assert np.array_equal(ia[k], ib[k]), ("levels", bits, k)
+    # ... and re-planned while it runs: the overflow list reversed (same manifold count, same number of levels, other levels), manifolds + levels + plan again
+    from avian_amd import scenes
+    from level2_helpers import reverse_overflow
+    pm = reverse_overflow(pm, offs)
+    level_before = level.copy()
+    depth = np.zeros(sc.n, np.int64); level = np.zeros(o1 - o0, np.int64)
+    for m in range(o0, o1):
+        bb = [int(b) for b in (pm["body1"][m], pm["body2"][m]) if sc.rb_type[b] != F.RB_STATIC]
+        level[m - o0] = max(depth[b] for b in bb)
+        for b in bb:
+            depth[b] = level[m - o0] + 1
+    assert int(level.max()) + 1 == L and not np.array_equal(level, level_before)
+    so = [0]; bodies = []
+    for slot in range(23 + L):
+        m = np.arange(offs[slot], offs[slot + 1]) if slot < 23 else o0 + np.flatnonzero(level == slot - 23)
+        b = np.unique(np.concatenate([pm["body1"][m], pm["body2"][m]])) if len(m) else np.zeros(0, np.int64)
+        b = b[sc.rb_type[b] == F.RB_DYNAMIC]
+        bodies.append(b); so.append(so[-1] + len(b))
+    bodies = np.concatenate(bodies).astype(np.int32)
+    for w in (plain, looped):
+        scenes.upload_manifolds(w, pm, offs, sc.friction, 0.3)
+    looped.halo_overflow_levels_upload(L, level)
+    looped.halo_plan_upload([0], so, bodies, so, bodies)
+    for _ in range(2):
+        plain.step(); looped.step()
+    looped.synchronize(); plain.synchronize()
+    a, b = plain.bodies_download(), looped.bodies_download()
+    for k in a:
+        assert np.array_equal(a[k], b[k]), ("levels re-planned", bits, k)
+    ia, ib = plain.impulses_download(), looped.impulses_download()
+    for k in ia:
+        assert np.array_equal(ia[k], ib[k]), ("levels re-planned", bits, k)
 # round 6: the joint slot through the library's own exchange -- a jointed stack whose every jointed body travels rank 0 -> rank 0 after the joint systems of every substep
 from level2_helpers import stack_joints
 for bits in (32, 64):

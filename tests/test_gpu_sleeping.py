@@ -143,3 +143,38 @@ def test_a_world_entirely_asleep_steps_as_the_identity_and_can_be_woken():
         wo.step(); wh.step(); compare_step(s, wo, wh); compare_sleeping(s, wo, wh); s += 1
         if k == 0:
             assert wh.timers().kernel_launches > 0, "WakeBody ends the shortcut"
+
+
+DESTROY_DURING_SPLIT = r"""
+import sys
+sys.path.insert(0, %(tests)r); sys.path.insert(0, %(repo)r)
+import numpy as np
+from helpers import F, hip_lib, oracle_lib
+from pipeline_scenes import stack_and_projectile
+sc = stack_and_projectile(13, 13, 13, height=12.0)
+worlds = []
+for lib in (oracle_lib(), hip_lib()):
+    w = F.World(lib, F.default_config(32, substeps=4))
+    w.bodies_upload(**sc.body_kwargs()); w.colliders_upload(**sc.collider_kwargs())
+    w.existing_pairs_upload(np.zeros(0, np.uint64)); w.collider_materials_upload(friction=0.5)
+    w.pipeline_enable(); w.sleeping_enable(time_to_sleep=0.05, linear_threshold=3.0, angular_threshold=3.0)
+    worlds.append(w)
+wo, wh = worlds
+for s in range(12):
+    wo.step(); wh.step()
+    if wo.sleeping_stats().islands.splits:   # (the oracle walks the split candidate inside this step; the device world has handed the same walk to its worker thread)
+        wh.close()                           # avn_world_destroy straight after the step: nothing of the world has been read since
+        print("DESTROYED_AFTER_STEP", s)
+        break
+"""
+
+
+def test_destroying_a_world_right_after_a_step_that_started_a_split_walk():
+    """~World joins the island manager's asynchronous split walk before anything is released: the walk reads the pinned CSR block (pin_adj2) that the
+    world owns.  The 13 x 13 x 13 stack is the smallest known to split (after its 4th step); the oracle, stepped alongside, says in which step.  In a
+    child process under a timeout, once."""
+    import os, subprocess, sys
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    code = DESTROY_DURING_SPLIT % {"tests": os.path.join(repo, "tests"), "repo": repo}
+    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=120, cwd=repo)
+    assert r.returncode == 0 and "DESTROYED_AFTER_STEP" in r.stdout, r.stdout[-2000:] + r.stderr[-3000:]

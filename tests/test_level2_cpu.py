@@ -45,6 +45,16 @@ def test_overflow_colour_on_shared_bodies_equals_single_world(bits, world_size, 
     assert float(np.abs(single.bodies_download()["linear_velocity"]).max()) > 0.05
 
 
+@pytest.mark.parametrize("bits,world_size,keep,restitution", [(32, 2, 6, 0.0), (64, 3, 3, 0.3)])
+def test_replanning_running_split_worlds_with_the_overflow_list_reversed(bits, world_size, keep, restitution):
+    """A settled pile is re-planned while it runs: the same local manifold counts, the same number of overflow levels, other levels per manifold (asserted by
+    level2_helpers.replan_split).  The oracle groups by level on every pass and holds no order cache; this pins that, validates the script for the HIP tier
+    (tests/test_gpu_level2.py) and checks that the re-plan matters: a world that keeps the old list differs."""
+    from level2_helpers import replan_case
+    lib = oracle_lib()
+    replan_case(lib, [lib], bits, world_size, keep, restitution, seed=bits + world_size, control_lib=lib)
+
+
 @pytest.fixture(scope="module")
 def cfg5_problem():
     from level2_helpers import closed_loop_problem
