@@ -422,10 +422,14 @@ template <class T> struct SP {
     uint32_t *keys_a, *vals_a, *keys_b, *vals_b, *hist, *block_sums;   // the Morton sort's buffers
 };
 template <class T> struct SpatialHit { uint32_t collider, entity; T distance; T normal[3]; };   // == avn_spatial_hit_fNN
-enum { SPQ_CLOSEST = 0, SPQ_HITS = 1, SPQ_POINTS = 2, SPQ_AABBS = 3 };
+template <class T> struct SpatialProjection { uint32_t collider, entity, is_inside; T point[3]; T distance; };   // == avn_spatial_projection_fNN
+template <> struct SpatialProjection<double> { uint32_t collider, entity, is_inside, reserved; double point[3]; double distance; };   // (no implicit padding: every byte of a record is written)
+__device__ __forceinline__ void sp_clear_reserved(SpatialProjection<float>&) {}
+__device__ __forceinline__ void sp_clear_reserved(SpatialProjection<double>& r) { r.reserved = 0u; }
+enum { SPQ_CLOSEST = 0, SPQ_HITS = 1, SPQ_POINTS = 2, SPQ_AABBS = 3, SPQ_PROJECT = 4, SPQ_SHAPES = 5 };
 template <class T> struct SQ {
-    uint32_t n, cap;                 // queries; max_hits (SPQ_HITS) / cap (SPQ_POINTS, SPQ_AABBS)
-    const T* a;                      // [3n] origins / points / box mins
+    uint32_t n, cap;                 // queries; max_hits (SPQ_HITS) / cap (SPQ_POINTS, SPQ_AABBS, SPQ_SHAPES)
+    const T* a;                      // [3n] origins / points / box mins / query-shape positions
     const T* b;                      // [3n] directions / box maxs
     const T* max_distance;           // [n]
     const uint8_t* solid;            // [n]
@@ -436,6 +440,11 @@ template <class T> struct SQ {
     uint32_t* ids;                   // [n * cap]
     uint32_t* count;                 // [n]
     unsigned long long* stats;       // [3]: node boxes tested, exact tests, stack overflow flag (zeroed by the launch)
+    // SPQ_PROJECT (a = points, solid) and SPQ_SHAPES (a = positions): kernels of their own, k_sp_project / k_sp_shapes
+    const uint8_t* shape;            // [n] AVN_SHAPE_CUBOID / AVN_SHAPE_BALL of the query shape
+    const T* he;                     // [3n] half extents (ball: radius in x)
+    const T* rot;                    // [4n] xyzw
+    SpatialProjection<T>* proj;      // [n]
 };
 template <class T> void launch_spatial_build(const DW<T>&, const BP<T>&, const SP<T>&, hipStream_t);
 template <class T> void launch_spatial_query(const SP<T>&, const SQ<T>&, int kind, hipStream_t);

@@ -22,6 +22,8 @@ AVN_API avn_status avn_spatial_ray_hits(avn_world* w, const avn_spatial_rays* r,
 }
 AVN_API avn_status avn_spatial_point_intersections(avn_world* w, const avn_spatial_points* p, uint32_t cap, const avn_spatial_ids_out* o) { SP_GUARD(spatial_point_intersections(p, cap, o)); }
 AVN_API avn_status avn_spatial_aabb_intersections(avn_world* w, const avn_spatial_aabbs* b, uint32_t cap, const avn_spatial_ids_out* o) { SP_GUARD(spatial_aabb_intersections(b, cap, o)); }
+AVN_API avn_status avn_spatial_project_points(avn_world* w, const avn_spatial_solid_points* p, const avn_spatial_projections_out* o) { SP_GUARD(spatial_project_points(p, o)); }
+AVN_API avn_status avn_spatial_shape_intersections(avn_world* w, const avn_spatial_shapes* s, uint32_t cap, const avn_spatial_ids_out* o) { SP_GUARD(spatial_shape_intersections(s, cap, o)); }
 AVN_API avn_status avn_spatial_stats_get(avn_world* w, avn_spatial_stats* o) { SP_GUARD(spatial_stats_get(o)); }
 
 }  // extern "C"

@@ -1,5 +1,6 @@
 // k_spatial.hip — spatial queries on the device (include/avian_mi355x_spatial.h): an LBVH over the collider table and one-lane-per-query
-// traversals for ray casts, ray hits, point and AABB intersections.
+// traversals for ray casts, ray hits, point and AABB intersections (k_sp_query), point projection (k_sp_project) and shape intersections
+// (k_sp_shapes).
 //
 // avn_spatial_update (launch_spatial_build), all on the world's stream:
 //   1. k_sp_snapshot   one thread per collider: its pose (collider_pose), the exact shape AABB (shape_aabb), padded, as the leaf box;
@@ -20,7 +21,12 @@
 // does) are all a few eps of those magnitudes, so no point that an exact test accepts lies outside the boxes the traversal tests.
 // Non-finite data never reaches an exact test: a collider with a non-finite position, rotation or shape AABB is not a candidate and has
 // an empty leaf box; a query with a non-finite origin, direction, point or box corner answers a miss / count 0 without traversing.
+// Projection culls with a lower bound of the distance to the node box and shape intersections with the query shape's padded AABB: their
+// padding arguments are in DESIGN.md 4.4.5.
+#include <cstddef>
+
 #include "avn_kernels.h"
+#include "avn_narrow.h"
 #include "../../include/avian_mi355x_spatial.h"
 
 namespace avn {
@@ -447,6 +453,256 @@ __global__ __launch_bounds__(SP_WAVE) void k_sp_query(SP<T> sp, SQ<T> q) {
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// point projection and shape intersections (kernels of their own: the four query kinds above compile as before)
+
+// the header's projection of a point onto one collider: false when the distance is not finite
+template <class T>
+__device__ __forceinline__ bool sp_project_exact(uint32_t shape, V3<T> he, V3<T> pos, Q4<T> rot, V3<T> p, bool solid, T& distance, V3<T>& point, bool& is_inside) {
+    const V3<T> pl = qrot(qinverse(rot), p - pos);
+    V3<T> proj;
+    bool inside;
+    if (shape == AVN_SHAPE_BALL) {
+        const T r = he.x;
+        const T d2 = dot(pl, pl);
+        inside = d2 <= r * r;
+        if (!(solid && inside)) proj = d2 == T(0) ? V3<T>{T(0), r, T(0)} : pl * (r / sqrt_t(d2));
+    } else {
+        inside = fabs_t(pl.x) <= he.x && fabs_t(pl.y) <= he.y && fabs_t(pl.z) <= he.z;
+        if (!inside) {
+            proj = V3<T>{pl.x < -he.x ? -he.x : (pl.x > he.x ? he.x : pl.x), pl.y < -he.y ? -he.y : (pl.y > he.y ? he.y : pl.y),
+                         pl.z < -he.z ? -he.z : (pl.z > he.z ? he.z : pl.z)};
+        } else if (!solid) {
+            // the nearest face: the smallest he.i - |pl.i|, strict <, so the first axis in x, y, z order wins a tie
+            T m = he.x - fabs_t(pl.x);
+            int axis = 0;
+            const T my = he.y - fabs_t(pl.y), mz = he.z - fabs_t(pl.z);
+            if (my < m) { m = my; axis = 1; }
+            if (mz < m) { m = mz; axis = 2; }
+            proj = V3<T>{axis == 0 ? copysign_t(he.x, pl.x) : pl.x, axis == 1 ? copysign_t(he.y, pl.y) : pl.y, axis == 2 ? copysign_t(he.z, pl.z) : pl.z};
+        }
+    }
+    is_inside = inside;
+    if (solid && inside) { distance = T(0); point = p; return true; }
+    const V3<T> diff = pl - proj;
+    distance = sqrt_t(dot(diff, diff));
+    point = qrot(rot, proj) + pos;
+    return finite_t(distance);
+}
+// A lower bound of the projection distance of every collider under a node, or -1 for an empty box: the distance from the point to the
+// node box grown by the query's tolerance plus 64 eps * the box's largest coordinate, times (1 - 8 eps) for the rounding of this
+// function's own squares, sum and square root (DESIGN.md 4.4.5 has the argument).
+template <class T> __device__ __forceinline__ T sp_point_box_distance(V3<T> p, T tol, Vec4<T> lo, Vec4<T> hi) {
+    if (!(lo.x <= hi.x)) return T(-1);
+    const T m = smax(smax(smax(fabs_t(lo.x), fabs_t(lo.y)), smax(fabs_t(lo.z), fabs_t(hi.x))), smax(fabs_t(hi.y), fabs_t(hi.z)));
+    const T g = tol + T(64) * Limits<T>::eps * m;
+    const V3<T> d{smax(smax((lo.x - g) - p.x, p.x - (hi.x + g)), T(0)), smax(smax((lo.y - g) - p.y, p.y - (hi.y + g)), T(0)),
+                  smax(smax((lo.z - g) - p.z, p.z - (hi.z + g)), T(0))};
+    return sqrt_t(dot(d, d)) * (T(1) - T(8) * Limits<T>::eps);
+}
+
+template <class T>
+__global__ __launch_bounds__(SP_WAVE) void k_sp_project(SP<T> sp, SQ<T> q) {
+    __shared__ uint32_t stack[SP_STACK * SP_WAVE];
+    const uint32_t lane = threadIdx.x;
+    const uint32_t qi = blockIdx.x * SP_WAVE + lane;
+    uint32_t nodes_tested = 0, leaves_tested = 0, overflow = 0;
+    const uint32_t n = sp.n;
+    if (qi < q.n) {
+        const uint32_t mask = q.mask ? q.mask[qi] : 0xFFFFFFFFu;
+        const V3<T> p{q.a[3 * (size_t)qi], q.a[3 * (size_t)qi + 1], q.a[3 * (size_t)qi + 2]};
+        const bool solid = q.solid[qi] != 0;
+        const T tol = T(64) * Limits<T>::eps * sp_maxabs(p);
+        T best = sp_inf<T>();
+        uint32_t best_c = AVN_SPATIAL_MISS, best_in = 0;
+        V3<T> best_p = vzero<T>();
+        // the node's lower bound, or -1 when the node is culled: only a bound STRICTLY above the best distance culls, so a collider at the
+        // best distance with a lower index is still reached
+        auto test = [&](uint32_t node) -> T {
+            ++nodes_tested;
+            const T b = sp_point_box_distance<T>(p, tol, sp.bmin[node], sp.bmax[node]);
+            return b > best ? T(-1) : b;
+        };
+        auto leaf = [&](uint32_t node) {
+            const uint32_t c = sp.leaf_col[node - (n - 1)];
+            const uint4 info = sp.info[c];
+            if (!info.w || (info.y & mask) == 0u || (q.n_excluded && sp_excluded(q.excluded, q.n_excluded, info.x))) return;
+            ++leaves_tested;
+            T d; V3<T> pt; bool in;
+            if (!sp_project_exact<T>(info.z, xyz<T>(sp.he[c]), xyz<T>(sp.pos[c]), quat<T>(sp.rot[c]), p, solid, d, pt, in)) return;
+            if (d < best || (d == best && c < best_c)) { best = d; best_c = c; best_p = pt; best_in = in ? 1u : 0u; }
+        };
+        if (!is_finite(p)) {
+        } else if (n == 1) {
+            if (test(0) >= T(0)) leaf(0);
+        } else if (n > 1 && test(0) >= T(0)) {
+            uint32_t sp_top = 0, node = 0;
+            for (;;) {
+                const uint2 ch = sp.child[node];
+                T e0 = test(ch.x), e1 = test(ch.y);
+                const bool l0 = ch.x >= n - 1, l1 = ch.y >= n - 1;
+                if (l0 && e0 >= T(0)) { leaf(ch.x); e0 = T(-1); }
+                // (the first leaf may have shrunk the best distance below the second one's bound)
+                if (l1 && e1 >= T(0)) { if (!(e1 > best)) leaf(ch.y); e1 = T(-1); }
+                const bool g0 = e0 >= T(0) && !(e0 > best), g1 = e1 >= T(0) && !(e1 > best);
+                if (g0 && g1) {
+                    const bool first0 = !(e1 < e0);   // the nearer child first (ties: the left one)
+                    if (sp_top < SP_STACK) { stack[sp_top * SP_WAVE + lane] = first0 ? ch.y : ch.x; ++sp_top; }
+                    else overflow = 1;   // (cannot happen: the depth of the tree is at most 64)
+                    node = first0 ? ch.x : ch.y;
+                    continue;
+                }
+                if (g0) { node = ch.x; continue; }
+                if (g1) { node = ch.y; continue; }
+                // pop; a node pushed before the best distance shrank is re-tested against it
+                node = AVN_SPATIAL_MISS;
+                while (sp_top > 0) {
+                    --sp_top;
+                    const uint32_t cand = stack[sp_top * SP_WAVE + lane];
+                    if (test(cand) >= T(0)) { node = cand; break; }
+                }
+                if (node == AVN_SPATIAL_MISS) break;
+            }
+        }
+        SpatialProjection<T> r;
+        r.collider = best_c;
+        r.entity = best_c == AVN_SPATIAL_MISS ? AVN_SPATIAL_MISS : sp.info[best_c].x;
+        r.is_inside = best_in;
+        sp_clear_reserved(r);
+        r.point[0] = best_p.x; r.point[1] = best_p.y; r.point[2] = best_p.z;
+        r.distance = best_c == AVN_SPATIAL_MISS ? T(0) : best;
+        q.proj[qi] = r;
+    }
+    uint32_t a = nodes_tested, b = leaves_tested, o = overflow;
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) { a += __shfl_xor(a, off); b += __shfl_xor(b, off); o |= __shfl_xor(o, off); }
+    if (lane == 0) {
+        atomicAdd(&q.stats[0], (unsigned long long)a);
+        atomicAdd(&q.stats[1], (unsigned long long)b);
+        if (o) atomicOr(&q.stats[2], 1ull);
+    }
+}
+
+// the header's intersection test of a query shape (shape 1, isometry iso1 = make_isometry of its pose) with one collider (shape 2)
+template <class T>
+__device__ __forceinline__ bool sp_shape_exact(uint32_t shape1, V3<T> he1, const Iso<T>& iso1, uint32_t shape2, V3<T> he2, V3<T> pos2, Q4<T> rot2) {
+    const Iso<T> pos12 = iso_inv_mul(iso1, Iso<T>{rot2, pos2});
+    if (shape1 == AVN_SHAPE_BALL && shape2 == AVN_SHAPE_BALL) {
+        const T rr = he1.x + he2.x;
+        return na_dot(pos12.t, pos12.t) <= rr * rr;
+    }
+    if (shape1 == AVN_SHAPE_BALL || shape2 == AVN_SHAPE_BALL) {
+        // the ball's centre in the cuboid's frame
+        const bool ball1 = shape1 == AVN_SHAPE_BALL;
+        const V3<T> c = ball1 ? iso_inv_point(pos12, vzero<T>()) : pos12.t;
+        const V3<T> he = ball1 ? he2 : he1;
+        const T r = ball1 ? he1.x : he2.x;
+        if (fabs_t(c.x) <= he.x && fabs_t(c.y) <= he.y && fabs_t(c.z) <= he.z) return true;
+        const V3<T> cl{c.x < -he.x ? -he.x : (c.x > he.x ? he.x : c.x), c.y < -he.y ? -he.y : (c.y > he.y ? he.y : c.y), c.z < -he.z ? -he.z : (c.z > he.z ? he.z : c.z)};
+        const V3<T> d = c - cl;
+        return na_dot(d, d) <= r * r;
+    }
+    V3<T> dir;
+    if (sat_normal_oneway(he1, he2, pos12, dir) > T(0)) return false;
+    if (sat_normal_oneway(he2, he1, iso_inverse(pos12), dir) > T(0)) return false;
+    if (sat_edge_twoway(he1, he2, pos12, dir) > T(0)) return false;
+    return true;
+}
+
+template <class T>
+__global__ __launch_bounds__(SP_WAVE) void k_sp_shapes(SP<T> sp, SQ<T> q) {
+    __shared__ uint32_t stack[SP_STACK * SP_WAVE];
+    const uint32_t lane = threadIdx.x;
+    const uint32_t qi = blockIdx.x * SP_WAVE + lane;
+    uint32_t nodes_tested = 0, leaves_tested = 0, overflow = 0;
+    const uint32_t n = sp.n;
+    if (qi < q.n) {
+        const uint32_t mask = q.mask ? q.mask[qi] : 0xFFFFFFFFu;
+        const uint32_t shape1 = q.shape[qi];
+        const V3<T> pos1{q.a[3 * (size_t)qi], q.a[3 * (size_t)qi + 1], q.a[3 * (size_t)qi + 2]};
+        V3<T> he1{q.he[3 * (size_t)qi], q.he[3 * (size_t)qi + 1], q.he[3 * (size_t)qi + 2]};
+        const Q4<T> rot1{q.rot[4 * (size_t)qi], q.rot[4 * (size_t)qi + 1], q.rot[4 * (size_t)qi + 2], q.rot[4 * (size_t)qi + 3]};
+        if (shape1 == AVN_SHAPE_BALL) he1 = V3<T>{he1.x, he1.x, he1.x};   // (a ball has its radius in x: y and z are not read)
+        // a shape kind other than Ball / Cuboid, a non-finite pose or half extents, a negative half extent or a non-finite box: count 0
+        bool valid = shape1 <= AVN_SHAPE_BALL && is_finite(pos1) && is_finite(V3<T>{rot1.x, rot1.y, rot1.z}) && finite_t(rot1.w) && is_finite(he1) &&
+                     he1.x >= T(0) && he1.y >= T(0) && he1.z >= T(0);
+        V3<T> qmin = vzero<T>(), qmax = vzero<T>();
+        Iso<T> iso1{Q4<T>{T(0), T(0), T(0), T(1)}, pos1};
+        if (valid) {
+            // the query shape's exact AABB at its pose, grown as the leaf boxes are
+            V3<T> a, b;
+            shape_aabb<T>(shape1, he1, pos1, rot1, a, b);
+            valid = is_finite(a) && is_finite(b);
+            const T pad = T(64) * Limits<T>::eps * smax(sp_maxabs(a), sp_maxabs(b));
+            const V3<T> pp{pad, pad, pad};
+            qmin = a - pp; qmax = b + pp;
+            iso1 = make_isometry(pos1, rot1);
+        }
+        uint32_t found = 0;
+        uint32_t* il = q.ids + (size_t)qi * q.cap;
+        auto test = [&](uint32_t node) -> bool {
+            ++nodes_tested;
+            return sp_box_box(qmin, qmax, sp.bmin[node], sp.bmax[node]);
+        };
+        auto leaf = [&](uint32_t node) {
+            const uint32_t c = sp.leaf_col[node - (n - 1)];
+            const uint4 info = sp.info[c];
+            if (!info.w || (info.y & mask) == 0u || (q.n_excluded && sp_excluded(q.excluded, q.n_excluded, info.x))) return;
+            ++leaves_tested;
+            if (!sp_shape_exact<T>(shape1, he1, iso1, info.z, xyz<T>(sp.he[c]), xyz<T>(sp.pos[c]), quat<T>(sp.rot[c]))) return;
+            const uint32_t k = q.cap;
+            uint32_t m = found < k ? found : k;
+            ++found;
+            if (m == k) {
+                if (k == 0 || c >= il[k - 1]) return;
+                m = k - 1;
+            }
+            while (m > 0 && il[m - 1] > c) { il[m] = il[m - 1]; --m; }
+            il[m] = c;
+        };
+        if (!valid) {
+        } else if (n == 1) {
+            if (test(0)) leaf(0);
+        } else if (n > 1 && test(0)) {
+            uint32_t sp_top = 0, node = 0;
+            for (;;) {
+                const uint2 ch = sp.child[node];
+                bool g0 = test(ch.x), g1 = test(ch.y);
+                // one leaf call site: the SAT is emitted once
+                uint32_t pending = (ch.x >= n - 1 && g0 ? 1u : 0u) | (ch.y >= n - 1 && g1 ? 2u : 0u);
+                while (pending) {
+                    const bool first = (pending & 1u) != 0;
+                    leaf(first ? ch.x : ch.y);
+                    pending &= first ? ~1u : ~2u;
+                }
+                if (ch.x >= n - 1) g0 = false;
+                if (ch.y >= n - 1) g1 = false;
+                if (g0 && g1) {
+                    if (sp_top < SP_STACK) { stack[sp_top * SP_WAVE + lane] = ch.y; ++sp_top; }
+                    else overflow = 1;   // (cannot happen: the depth of the tree is at most 64)
+                    node = ch.x;
+                    continue;
+                }
+                if (g0) { node = ch.x; continue; }
+                if (g1) { node = ch.y; continue; }
+                if (sp_top == 0) break;
+                --sp_top;
+                node = stack[sp_top * SP_WAVE + lane];
+            }
+        }
+        for (uint32_t m = found; m < q.cap; ++m) il[m] = AVN_SPATIAL_MISS;
+        q.count[qi] = found;
+    }
+    uint32_t a = nodes_tested, b = leaves_tested, o = overflow;
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) { a += __shfl_xor(a, off); b += __shfl_xor(b, off); o |= __shfl_xor(o, off); }
+    if (lane == 0) {
+        atomicAdd(&q.stats[0], (unsigned long long)a);
+        atomicAdd(&q.stats[1], (unsigned long long)b);
+        if (o) atomicOr(&q.stats[2], 1ull);
+    }
+}
+
 template <class T> void launch_spatial_query(const SP<T>& sp, const SQ<T>& q, int kind, hipStream_t s) {
     (void)hipMemsetAsync(q.stats, 0, 4 * sizeof(unsigned long long), s);
     if (q.n == 0) return;
@@ -455,11 +711,16 @@ template <class T> void launch_spatial_query(const SP<T>& sp, const SQ<T>& q, in
         case SPQ_CLOSEST: hipLaunchKernelGGL((k_sp_query<T, SPQ_CLOSEST>), g, b, 0, s, sp, q); break;
         case SPQ_HITS: hipLaunchKernelGGL((k_sp_query<T, SPQ_HITS>), g, b, 0, s, sp, q); break;
         case SPQ_POINTS: hipLaunchKernelGGL((k_sp_query<T, SPQ_POINTS>), g, b, 0, s, sp, q); break;
+        case SPQ_PROJECT: hipLaunchKernelGGL((k_sp_project<T>), g, b, 0, s, sp, q); break;
+        case SPQ_SHAPES: hipLaunchKernelGGL((k_sp_shapes<T>), g, b, 0, s, sp, q); break;
         default: hipLaunchKernelGGL((k_sp_query<T, SPQ_AABBS>), g, b, 0, s, sp, q); break;
     }
 }
 
 static_assert(sizeof(SpatialHit<float>) == sizeof(avn_spatial_hit_f32) && sizeof(SpatialHit<double>) == sizeof(avn_spatial_hit_f64), "hit record layout");
+static_assert(sizeof(SpatialProjection<float>) == sizeof(avn_spatial_projection_f32) && sizeof(SpatialProjection<double>) == sizeof(avn_spatial_projection_f64) &&
+              offsetof(SpatialProjection<double>, point) == offsetof(avn_spatial_projection_f64, point) && offsetof(SpatialProjection<double>, reserved) == offsetof(avn_spatial_projection_f64, reserved) && offsetof(SpatialProjection<float>, distance) == offsetof(avn_spatial_projection_f32, distance),
+              "projection record layout");
 template void launch_spatial_build<float>(const DW<float>&, const BP<float>&, const SP<float>&, hipStream_t);
 template void launch_spatial_build<double>(const DW<double>&, const BP<double>&, const SP<double>&, hipStream_t);
 template void launch_spatial_query<float>(const SP<float>&, const SQ<float>&, int, hipStream_t);

@@ -152,6 +152,57 @@
         if (!b) { error = "spatial_aabb_intersections: null argument"; return AVN_ERR_BAD_ARG; }
         return sp_ids(SPQ_AABBS, b->count, b->flags, b->min, b->max, b->filter, cap, out);
     }
+    avn_status spatial_project_points(const avn_spatial_solid_points* p, const avn_spatial_projections_out* out) override {
+        if (!p || !out) { error = "spatial_project_points: null argument"; return AVN_ERR_BAD_ARG; }
+        const uint32_t n = p->count;
+        if (n && (!p->point || !p->solid || !out->projection)) { error = "spatial_project_points: null array"; return AVN_ERR_BAD_ARG; }
+        avn_status st = sp_check(p->flags);
+        if (st != AVN_OK) return st;
+        const bool dev = (p->flags & AVN_SPATIAL_DEVICE_POINTERS) != 0;
+        std::vector<uint32_t> ex;
+        if ((st = sp_excluded(p->filter, dev, ex)) != AVN_OK) return st;
+        if ((st = stage_reserve(sp_stage_bytes(dev, n, al(3 * sizeof(T) * n) + al(n), al((size_t)n * sizeof(SpatialProjection<T>)), ex.size()))) != AVN_OK) return st;
+        SQ<T> q{};
+        q.n = n;
+        if ((st = sp_in<T>(p->point, 3 * (size_t)n, dev, &q.a)) != AVN_OK) return st;
+        if ((st = sp_in<uint8_t>(p->solid, n, dev, &q.solid)) != AVN_OK) return st;
+        if ((st = sp_in<uint32_t>(p->filter.mask, n, dev, &q.mask)) != AVN_OK) return st;
+        if ((st = stage_in<uint32_t>(ex.data(), ex.size(), &q.excluded)) != AVN_OK) return st;
+        q.n_excluded = (uint32_t)ex.size();
+        q.proj = sp_out<SpatialProjection<T>>(out->projection, n, dev);
+        if ((st = sp_run(q, SPQ_PROJECT)) != AVN_OK) return st;
+        if (!dev && (st = stage_out<SpatialProjection<T>>(out->projection, q.proj, n)) != AVN_OK) return st;
+        return sp_finish();
+    }
+    avn_status spatial_shape_intersections(const avn_spatial_shapes* s, uint32_t cap, const avn_spatial_ids_out* out) override {
+        if (!s || !out) { error = "spatial_shape_intersections: null argument"; return AVN_ERR_BAD_ARG; }
+        const uint32_t n = s->count;
+        if (n && (!s->shape || !s->half_extents || !s->position || !s->rotation || !out->count || (cap && !out->collider))) { error = "spatial_shape_intersections: null array"; return AVN_ERR_BAD_ARG; }
+        avn_status st = sp_check(s->flags);
+        if (st != AVN_OK) return st;
+        const bool dev = (s->flags & AVN_SPATIAL_DEVICE_POINTERS) != 0;
+        std::vector<uint32_t> ex;
+        if ((st = sp_excluded(s->filter, dev, ex)) != AVN_OK) return st;
+        const size_t n_ids = (size_t)n * cap;
+        if ((st = stage_reserve(sp_stage_bytes(dev, n, 2 * al(3 * sizeof(T) * n) + al(4 * sizeof(T) * n) + al(n), al(n_ids * 4), ex.size()))) != AVN_OK) return st;
+        SQ<T> q{};
+        q.n = n; q.cap = cap;
+        if ((st = sp_in<uint8_t>(s->shape, n, dev, &q.shape)) != AVN_OK) return st;
+        if ((st = sp_in<T>(s->half_extents, 3 * (size_t)n, dev, &q.he)) != AVN_OK) return st;
+        if ((st = sp_in<T>(s->position, 3 * (size_t)n, dev, &q.a)) != AVN_OK) return st;
+        if ((st = sp_in<T>(s->rotation, 4 * (size_t)n, dev, &q.rot)) != AVN_OK) return st;
+        if ((st = sp_in<uint32_t>(s->filter.mask, n, dev, &q.mask)) != AVN_OK) return st;
+        if ((st = stage_in<uint32_t>(ex.data(), ex.size(), &q.excluded)) != AVN_OK) return st;
+        q.n_excluded = (uint32_t)ex.size();
+        q.ids = n_ids ? sp_out<uint32_t>(out->collider, n_ids, dev) : nullptr;
+        q.count = sp_out<uint32_t>(out->count, n, dev);
+        if ((st = sp_run(q, SPQ_SHAPES)) != AVN_OK) return st;
+        if (!dev) {
+            if ((st = stage_out<uint32_t>(out->collider, q.ids, n_ids)) != AVN_OK) return st;
+            if ((st = stage_out<uint32_t>(out->count, q.count, n)) != AVN_OK) return st;
+        }
+        return sp_finish();
+    }
     avn_status spatial_stats_get(avn_spatial_stats* o) override {
         if (!o) return AVN_ERR_BAD_ARG;
         std::memset(o, 0, sizeof *o);

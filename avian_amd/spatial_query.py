@@ -1,4 +1,5 @@
-"""ctypes binding of ``include/avian_mi355x_spatial.h``: device spatial queries (ray casts, ray hits, point and AABB intersections) over the
+"""ctypes binding of ``include/avian_mi355x_spatial.h``: device spatial queries (ray casts, ray hits, point and AABB intersections, point
+projection, shape intersections) over the
 colliders a :class:`avian_amd._ffi.World` holds on the device.
 
 Numpy arrays in and out (copied through the library's staging), or torch tensors on the world's GPU (``AVN_SPATIAL_DEVICE_POINTERS``: the
@@ -37,6 +38,27 @@ class avn_spatial_aabbs(C.Structure):
     _fields_ = [("count", C.c_uint32), ("flags", C.c_uint32), ("min", vp), ("max", vp), ("filter", avn_spatial_filter)]
 
 
+class avn_spatial_solid_points(C.Structure):
+    _fields_ = [("count", C.c_uint32), ("flags", C.c_uint32), ("point", vp), ("solid", vp), ("filter", avn_spatial_filter)]
+
+
+class avn_spatial_shapes(C.Structure):
+    _fields_ = [("count", C.c_uint32), ("flags", C.c_uint32), ("shape", vp), ("half_extents", vp), ("position", vp), ("rotation", vp),
+                ("filter", avn_spatial_filter)]
+
+
+class avn_spatial_projection_f32(C.Structure):
+    _fields_ = [("collider", C.c_uint32), ("entity", C.c_uint32), ("is_inside", C.c_uint32), ("point", C.c_float * 3), ("distance", C.c_float)]
+
+
+class avn_spatial_projection_f64(C.Structure):
+    _fields_ = [("collider", C.c_uint32), ("entity", C.c_uint32), ("is_inside", C.c_uint32), ("reserved", C.c_uint32), ("point", C.c_double * 3), ("distance", C.c_double)]
+
+
+class avn_spatial_projections_out(C.Structure):
+    _fields_ = [("projection", vp)]
+
+
 class avn_spatial_hit_f32(C.Structure):
     _fields_ = [("collider", C.c_uint32), ("entity", C.c_uint32), ("distance", C.c_float), ("normal", C.c_float * 3)]
 
@@ -59,15 +81,22 @@ class avn_spatial_stats(C.Structure):
 
 
 STRUCTS = [avn_spatial_filter, avn_spatial_rays, avn_spatial_points, avn_spatial_aabbs, avn_spatial_hit_f32, avn_spatial_hit_f64,
-           avn_spatial_hits_out, avn_spatial_ids_out, avn_spatial_stats]
+           avn_spatial_hits_out, avn_spatial_ids_out, avn_spatial_stats, avn_spatial_solid_points, avn_spatial_shapes,
+           avn_spatial_projection_f32, avn_spatial_projection_f64, avn_spatial_projections_out]
 SYMBOLS = ["avn_spatial_update", "avn_spatial_cast_rays", "avn_spatial_ray_hits", "avn_spatial_point_intersections",
-           "avn_spatial_aabb_intersections", "avn_spatial_stats_get"]
+           "avn_spatial_aabb_intersections", "avn_spatial_stats_get", "avn_spatial_project_points", "avn_spatial_shape_intersections"]
 
 
 def hit_dtype(bits: int) -> np.dtype:
     """numpy mirror of avn_spatial_hit_fNN."""
     s = np.float32 if bits == 32 else np.float64
     return np.dtype([("collider", np.uint32), ("entity", np.uint32), ("distance", s), ("normal", s, (3,))], align=True)
+
+
+def projection_dtype(bits: int) -> np.dtype:
+    """numpy mirror of avn_spatial_projection_fNN (f64: the 4 bytes after is_inside are the record's `reserved` word, always 0)."""
+    s = np.float32 if bits == 32 else np.float64
+    return np.dtype([("collider", np.uint32), ("entity", np.uint32), ("is_inside", np.uint32), ("point", s, (3,)), ("distance", s)], align=True)
 
 
 def _declare(dll):
@@ -79,6 +108,8 @@ def _declare(dll):
     dll.avn_spatial_point_intersections.argtypes = [vp, vp, C.c_uint32, vp]
     dll.avn_spatial_aabb_intersections.argtypes = [vp, vp, C.c_uint32, vp]
     dll.avn_spatial_stats_get.argtypes = [vp, vp]
+    dll.avn_spatial_project_points.argtypes = [vp, vp, vp]
+    dll.avn_spatial_shape_intersections.argtypes = [vp, vp, C.c_uint32, vp]
 
 
 class SpatialQuery:
@@ -98,6 +129,7 @@ class SpatialQuery:
         self.bits = world.cfg.scalar_bits
         self.dtype = world.dtype
         self.hit_dtype = hit_dtype(self.bits)
+        self.projection_dtype = projection_dtype(self.bits)
         self._keep = []
 
     # -- plumbing ------------------------------------------------------------------------------
@@ -129,8 +161,8 @@ class SpatialQuery:
     def _out(self, shape, dt, dev, like=None):
         if dev:
             import torch
-            if dt is self.hit_dtype:
-                t = torch.empty(tuple(shape) + (self.hit_dtype.itemsize,), dtype=torch.uint8, device=like.device)
+            if dt is self.hit_dtype or dt is self.projection_dtype:
+                t = torch.empty(tuple(shape) + (dt.itemsize,), dtype=torch.uint8, device=like.device)
             else:
                 t = torch.empty(shape, dtype={np.uint32: torch.int32}[dt], device=like.device)
             return t, vp(t.data_ptr())
@@ -227,6 +259,45 @@ class SpatialQuery:
         o = avn_spatial_ids_out(ip, cp)
         self._sync_torch(dev)
         self._check(self.dll.avn_spatial_aabb_intersections(self.world.handle, C.byref(b), int(cap), C.byref(o)))
+        return ids, cnt
+
+    def project_points(self, point, solid=None, mask=None, excluded=None, skip_host_shapes=False):
+        """SpatialQueryPipeline::project_point per point: a structured array of projection records (``projection_dtype``; collider == MISS:
+        no candidate).  ``solid`` defaults to 1.  Device tensors in: a uint8 tensor [n, itemsize] of the same records out."""
+        dev = self._is_tensor(point)
+        n = int(point.shape[0])
+        p = avn_spatial_solid_points()
+        p.count = n
+        p.flags = self._flags(dev, skip_host_shapes)
+        p.point = self._arr(point, self.dtype, dev, (n, 3))
+        if solid is None:
+            solid = np.ones(n, np.uint8) if not dev else point.new_ones((n,))
+        p.solid = self._arr(solid, np.uint8, dev, (n,))
+        p.filter = self._filter(n, mask, excluded, dev)
+        rec, rp = self._out((n,), self.projection_dtype, dev, point)
+        o = avn_spatial_projections_out(rp)
+        self._sync_torch(dev)
+        self._check(self.dll.avn_spatial_project_points(self.world.handle, C.byref(p), C.byref(o)))
+        return rec
+
+    def shape_intersections(self, shape, half_extents, position, rotation, cap, mask=None, excluded=None, skip_host_shapes=False):
+        """SpatialQueryPipeline::shape_intersections per query shape (AVN_SHAPE_CUBOID = 0 / AVN_SHAPE_BALL = 1, a ball's radius in
+        half_extents[:, 0]): (collider indices [n, cap] ascending, MISS-padded; true counts [n])."""
+        dev = self._is_tensor(position)
+        n = int(position.shape[0])
+        q = avn_spatial_shapes()
+        q.count = n
+        q.flags = self._flags(dev, skip_host_shapes)
+        q.shape = self._arr(shape, np.uint8, dev, (n,))
+        q.half_extents = self._arr(half_extents, self.dtype, dev, (n, 3))
+        q.position = self._arr(position, self.dtype, dev, (n, 3))
+        q.rotation = self._arr(rotation, self.dtype, dev, (n, 4))
+        q.filter = self._filter(n, mask, excluded, dev)
+        ids, ip = self._out((n, int(cap)), np.uint32, dev, position)
+        cnt, cp = self._out((n,), np.uint32, dev, position)
+        o = avn_spatial_ids_out(ip, cp)
+        self._sync_torch(dev)
+        self._check(self.dll.avn_spatial_shape_intersections(self.world.handle, C.byref(q), int(cap), C.byref(o)))
         return ids, cnt
 
     def stats(self) -> avn_spatial_stats:

@@ -1,5 +1,6 @@
 /*
- * avian_mi355x_spatial.h — device spatial queries: ray casts, point and AABB intersections against the colliders the world holds in HBM.
+ * avian_mi355x_spatial.h — device spatial queries: ray casts, point and AABB intersections, point projection and shape intersections against
+ * the colliders the world holds in HBM.  Of SpatialQueryPipeline's query families only the shape casts (cast_shape, shape_hits) are not here.
  *
  * Mirrors Avian's `SpatialQueryPlugin` (spatial_query/mod.rs:190-212), whose systems run in `PhysicsStepSystems::SpatialQuery` right after
  * `Sleeping` (schedule/mod.rs:98-105): `update_spatial_query_pipeline` rebuilds a BVH of every collider from `Position` / `Rotation`
@@ -32,10 +33,33 @@
  *  - point containment: |p_l.i| <= he.i for a cuboid, |p_l|^2 <= r^2 for a ball.
  *  - AABB: the collider's exact shape AABB at the snapshot pose (the broad phase's shape_aabb, no margins) intersects the query box
  *    (min <= other.max && max >= other.min per axis).
+ *  - point projection (SpatialQueryPipeline::project_point; parry's PointQuery::project_local_point of Ball and Cuboid plus the
+ *    nearest-collider search of a composite shape).  p_l = rot^-1 (p - pos) as above.
+ *      ball: d2 = |p_l|^2, inside = d2 <= r^2 (the containment predicate above).  solid && inside: the projection is the query point itself,
+ *        bit for bit, at distance 0.  Otherwise proj_l = p_l * (r / sqrt(d2)); when d2 == 0 (a hollow ball asked at its centre, where
+ *        every surface point is nearest) proj_l = (0, r, 0): THIS LIBRARY'S CHOICE, defined here.
+ *      cuboid: inside = |p_l.i| <= he.i on all axes.  Outside: each component clamped to [-he.i, he.i].  Inside and solid: the query point
+ *        itself, distance 0.  Inside and hollow: the axis with the smallest he.i - |p_l.i| (strict <: the first axis in x, y, z order
+ *        wins a tie) has its component set to copysign(he.i, p_l.i).
+ *      distance = sqrt(dot(diff, diff)), diff = p_l - proj_l (local frame); the world point is rot * proj_l + pos, rotated back as the ray
+ *      normal is.  A projection needs a finite distance.  The answer of a query is the smallest (distance, collider index): with solid = 1
+ *      a point inside several colliders answers the lowest-indexed one at distance 0, which is point_intersections' first collider.
+ *  - shape intersection (SpatialQueryPipeline::shape_intersections; parry's intersection_test of Ball / Cuboid pairs).  Shape 1 is the
+ *    query, shape 2 the collider: pos12 = iso_inv_mul(make_isometry(query position, query rotation), {collider rotation, collider
+ *    position}) in nalgebra's arithmetic (avn_narrow.h).  Touching counts as intersecting.
+ *      ball / ball: |pos12.t|^2 <= (r1 + r2)^2.
+ *      ball query / cuboid collider: c = iso_inv_point(pos12, 0), the ball's centre in the cuboid's frame; intersecting when c is inside
+ *        (the containment predicate) or |c - clamp(c)|^2 <= r^2.  Cuboid query / ball collider: the same with c = pos12.t.
+ *      cuboid / cuboid: parry's intersection_test_cuboid_cuboid, in this order: sat_normal_oneway(he1, he2, pos12) > 0 -> disjoint;
+ *        sat_normal_oneway(he2, he1, iso_inverse(pos12)) > 0 -> disjoint; sat_edge_twoway(he1, he2, pos12) > 0 -> disjoint (edge axes
+ *        whose norm is <= eps are skipped); otherwise intersecting.  The three functions are the narrow phase's.
  *
  * Non-finite inputs (NaN or inf components):
  *  - a collider whose snapshot position, rotation or shape AABB is not finite is never a candidate (it keeps its collider index);
- *  - a query whose origin, direction, point or box corner is not finite answers a miss (ray queries) or a count of 0, whatever the scene;
+ *  - a query whose origin, direction, point or box corner is not finite answers a miss (ray queries, projection) or a count of 0, whatever
+ *    the scene;
+ *  - a query shape whose kind is neither AVN_SHAPE_CUBOID nor AVN_SHAPE_BALL, whose position, rotation, half extents (a ball: its radius) or
+ *    AABB are not finite, or which has a negative half extent, answers a count of 0.  This is decided per query on the device;
  *  - a hit needs a finite distance.
  *  Answers to finite inputs do not depend on these rules.
  *
@@ -57,8 +81,8 @@
  *
  * Ties: closest hit = smallest (distance, collider index); ray_hits = the max_hits nearest by (distance, collider index), sorted, plus
  * the true number of hits (Avian returns an arbitrary subset when truncated: nearest-k is a deterministic strengthening); point and AABB
- * intersections = ascending collider index, the first `cap`, plus the true count.  A collider index is its slot in the last
- * avn_colliders_upload.
+ * intersections = ascending collider index, the first `cap`, plus the true count; shape intersections the same; a projection = the
+ * smallest (distance, collider index).  A collider index is its slot in the last avn_colliders_upload.
  */
 #ifndef AVIAN_MI355X_SPATIAL_H
 #define AVIAN_MI355X_SPATIAL_H
@@ -109,6 +133,25 @@ typedef struct avn_spatial_aabbs {
     avn_spatial_filter filter;
 } avn_spatial_aabbs;
 
+typedef struct avn_spatial_solid_points {
+    uint32_t count;
+    uint32_t flags;
+    const void* point;           /* [3n] */
+    const uint8_t* solid;        /* [n] 1: a point inside a shape projects onto itself at distance 0; 0: onto the shape's boundary */
+    avn_spatial_filter filter;
+} avn_spatial_solid_points;
+
+/* the query shapes of avn_spatial_shape_intersections (a later shape cast takes the same record) */
+typedef struct avn_spatial_shapes {
+    uint32_t count;
+    uint32_t flags;
+    const uint8_t* shape;        /* [n] AVN_SHAPE_CUBOID / AVN_SHAPE_BALL */
+    const void* half_extents;    /* [3n] (ball: radius in x, as in the collider table) */
+    const void* position;        /* [3n] */
+    const void* rotation;        /* [4n] xyzw, unit (the caller normalises) */
+    avn_spatial_filter filter;
+} avn_spatial_shapes;
+
 /* RayHitData (ray_caster.rs) with the collider's table index */
 typedef struct avn_spatial_hit_f32 {
     uint32_t collider;   /* slot of the last avn_colliders_upload; AVN_SPATIAL_MISS = no hit (entity too; distance and normal 0) */
@@ -122,6 +165,27 @@ typedef struct avn_spatial_hit_f64 {
     double distance;
     double normal[3];
 } avn_spatial_hit_f64;
+
+/* PointProjection (spatial_query/pipeline.rs) with the collider's table index and the distance */
+typedef struct avn_spatial_projection_f32 {
+    uint32_t collider;   /* AVN_SPATIAL_MISS = no candidate (entity too; the rest 0) */
+    uint32_t entity;
+    uint32_t is_inside;  /* 0 / 1: the point lies inside the collider (whatever `solid` says) */
+    float point[3];      /* world space */
+    float distance;      /* |point - projection| as computed in the collider's frame */
+} avn_spatial_projection_f32;
+typedef struct avn_spatial_projection_f64 {
+    uint32_t collider;
+    uint32_t entity;
+    uint32_t is_inside;
+    uint32_t reserved;   /* always written as 0: every byte of a record is defined */
+    double point[3];
+    double distance;
+} avn_spatial_projection_f64;
+
+typedef struct avn_spatial_projections_out {
+    void* projection;    /* avn_spatial_projection_fNN [n] */
+} avn_spatial_projections_out;
 
 typedef struct avn_spatial_hits_out {
     void* hits;          /* avn_spatial_hit_fNN [n] (cast_rays) or [n * max_hits] (ray_hits; unused slots are misses) */
@@ -154,6 +218,10 @@ AVN_API avn_status avn_spatial_ray_hits(avn_world* w, const avn_spatial_rays* ra
 AVN_API avn_status avn_spatial_point_intersections(avn_world* w, const avn_spatial_points* points, uint32_t cap, const avn_spatial_ids_out* out);
 /* SpatialQueryPipeline::aabb_intersections_with_aabb (pipeline.rs:691-742): per box the colliders whose shape AABB intersects it */
 AVN_API avn_status avn_spatial_aabb_intersections(avn_world* w, const avn_spatial_aabbs* boxes, uint32_t cap, const avn_spatial_ids_out* out);
+/* SpatialQueryPipeline::project_point (pipeline.rs:570-615) per point: the nearest collider's projection, or a miss when there is no candidate */
+AVN_API avn_status avn_spatial_project_points(avn_world* w, const avn_spatial_solid_points* points, const avn_spatial_projections_out* out);
+/* SpatialQueryPipeline::shape_intersections (pipeline.rs:744-826): per query shape the colliders intersecting it.  cap = 0 is legal (counts only) */
+AVN_API avn_status avn_spatial_shape_intersections(avn_world* w, const avn_spatial_shapes* shapes, uint32_t cap, const avn_spatial_ids_out* out);
 /* snapshot sizes and the traversal counters of the last query call */
 AVN_API avn_status avn_spatial_stats_get(avn_world* w, avn_spatial_stats* out);
 

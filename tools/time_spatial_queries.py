@@ -4,6 +4,8 @@
   avn_spatial_update at cfg2 (100 k cuboids after 20 closed-loop steps) and cfg4 (10^6 mixed, sparse_mixed)
   cast_rays, 10^6 random rays into cfg2: short (sensor-like, <= 2 m) and long (through the pile)
   ray_hits k = 16, 64 k rays;  point and AABB intersections, 10^6 queries each
+  project_points, 10^6 points into cfg2 (the points of point_intersections);  shape_intersections, 10^6 query shapes, half balls and half
+  cuboids with sizes like the AABB query's boxes, cap 16 -- reported beside the point and AABB figures of the same run
 
 Every figure is the median over `reps` warmed-up calls.  The queries take torch tensors on the GPU (AVN_SPATIAL_DEVICE_POINTERS: no
 staging copies), so a call is its launches plus one stream synchronisation; the update is timed with avn_synchronize behind it.  Device
@@ -98,12 +100,31 @@ def main():
     res["points_1m_ms"] = ms
     res["points_per_s"] = n / (ms * 1e-3)
     res["points_bytes_floor"] = n * (12 + 8 * 4 + 4)
+    st = sq.stats()
+    res["points_leaves_per_query"], res["points_nodes_per_query"] = st.leaves_visited / n, st.nodes_visited / n
     ext = torch.rand(n, 3, device=dev, generator=g)
     lo, hi = p - ext, p + ext
     ms = timed(lambda: sq.aabb_intersections(lo, hi, 16), reps)
     res["aabbs_1m_ms"] = ms
     res["aabbs_per_s"] = n / (ms * 1e-3)
     res["aabbs_bytes_floor"] = n * (24 + 16 * 4 + 4)
+    st = sq.stats()
+    res["aabbs_leaves_per_query"], res["aabbs_nodes_per_query"] = st.leaves_visited / n, st.nodes_visited / n
+    for name, sol in (("solid", solid), ("hollow", torch.zeros_like(solid))):
+        ms = timed(lambda: sq.project_points(p, sol), reps)
+        st = sq.stats()
+        res[f"project_{name}_1m_ms"] = ms
+        res[f"project_{name}_per_s"] = n / (ms * 1e-3)
+        res[f"project_{name}_leaves_per_query"], res[f"project_{name}_nodes_per_query"] = st.leaves_visited / n, st.nodes_visited / n
+    res["project_bytes_floor"] = n * (12 + 1 + 28)
+    kind = (torch.arange(n, device=dev) & 1).to(torch.uint8)                 # half cuboids (0), half balls (1)
+    rot = torch.nn.functional.normalize(torch.randn(n, 4, device=dev, generator=g), dim=1)
+    ms = timed(lambda: sq.shape_intersections(kind, ext, p, rot, 16), reps)
+    st = sq.stats()
+    res["shapes_1m_ms"] = ms
+    res["shapes_per_s"] = n / (ms * 1e-3)
+    res["shapes_leaves_per_query"], res["shapes_nodes_per_query"] = st.leaves_visited / n, st.nodes_visited / n
+    res["shapes_bytes_floor"] = n * (1 + 12 + 12 + 16 + 16 * 4 + 4)
     res["update_bytes_floor_per_collider"] = 4 * 16 + 16 + 8 + 4 * 16 + 2 * 16 + 2 * 2 * 16 + 8 + 12
     for k in [k for k in res if k.endswith("_bytes_floor")]:
         msk = k.replace("_bytes_floor", "_ms") if k.replace("_bytes_floor", "_ms") in res else None
