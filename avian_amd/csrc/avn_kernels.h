@@ -426,9 +426,11 @@ template <class T> struct SpatialProjection { uint32_t collider, entity, is_insi
 template <> struct SpatialProjection<double> { uint32_t collider, entity, is_inside, reserved; double point[3]; double distance; };   // (no implicit padding: every byte of a record is written)
 __device__ __forceinline__ void sp_clear_reserved(SpatialProjection<float>&) {}
 __device__ __forceinline__ void sp_clear_reserved(SpatialProjection<double>& r) { r.reserved = 0u; }
-enum { SPQ_CLOSEST = 0, SPQ_HITS = 1, SPQ_POINTS = 2, SPQ_AABBS = 3, SPQ_PROJECT = 4, SPQ_SHAPES = 5 };
+// == avn_spatial_shape_hit_fNN (60 / 112 bytes, no implicit padding)
+template <class T> struct SpatialShapeHit { uint32_t collider, entity; T distance; T point1[3], point2[3], normal1[3], normal2[3]; };
+enum { SPQ_CLOSEST = 0, SPQ_HITS = 1, SPQ_POINTS = 2, SPQ_AABBS = 3, SPQ_PROJECT = 4, SPQ_SHAPES = 5, SPQ_CAST = 6, SPQ_CAST_HITS = 7 };
 template <class T> struct SQ {
-    uint32_t n, cap;                 // queries; max_hits (SPQ_HITS) / cap (SPQ_POINTS, SPQ_AABBS, SPQ_SHAPES)
+    uint32_t n, cap;                 // queries; max_hits (SPQ_HITS, SPQ_CAST_HITS) / cap (SPQ_POINTS, SPQ_AABBS, SPQ_SHAPES)
     const T* a;                      // [3n] origins / points / box mins / query-shape positions
     const T* b;                      // [3n] directions / box maxs
     const T* max_distance;           // [n]
@@ -445,6 +447,8 @@ template <class T> struct SQ {
     const T* he;                     // [3n] half extents (ball: radius in x)
     const T* rot;                    // [4n] xyzw
     SpatialProjection<T>* proj;      // [n]
+    // SPQ_CAST / SPQ_CAST_HITS (the SPQ_SHAPES fields, b = directions, max_distance; cap = max_hits): k_sp_cast
+    SpatialShapeHit<T>* cast;        // SPQ_CAST: [n]; SPQ_CAST_HITS: [n * cap]
 };
 template <class T> void launch_spatial_build(const DW<T>&, const BP<T>&, const SP<T>&, hipStream_t);
 template <class T> void launch_spatial_query(const SP<T>&, const SQ<T>&, int kind, hipStream_t);

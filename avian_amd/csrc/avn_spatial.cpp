@@ -24,6 +24,11 @@ AVN_API avn_status avn_spatial_point_intersections(avn_world* w, const avn_spati
 AVN_API avn_status avn_spatial_aabb_intersections(avn_world* w, const avn_spatial_aabbs* b, uint32_t cap, const avn_spatial_ids_out* o) { SP_GUARD(spatial_aabb_intersections(b, cap, o)); }
 AVN_API avn_status avn_spatial_project_points(avn_world* w, const avn_spatial_solid_points* p, const avn_spatial_projections_out* o) { SP_GUARD(spatial_project_points(p, o)); }
 AVN_API avn_status avn_spatial_shape_intersections(avn_world* w, const avn_spatial_shapes* s, uint32_t cap, const avn_spatial_ids_out* o) { SP_GUARD(spatial_shape_intersections(s, cap, o)); }
+AVN_API avn_status avn_spatial_cast_shapes(avn_world* w, const avn_spatial_shape_casts* c, const avn_spatial_shape_hits_out* o) { SP_GUARD(spatial_cast_shapes(c, 0u, o)); }
+AVN_API avn_status avn_spatial_shape_hits(avn_world* w, const avn_spatial_shape_casts* c, uint32_t max_hits, const avn_spatial_shape_hits_out* o) {
+    if (w && w->impl && (max_hits == 0 || max_hits > AVN_SPATIAL_MAX_HITS)) { w->impl->error = "spatial_shape_hits: max_hits must be 1 .. AVN_SPATIAL_MAX_HITS"; return AVN_ERR_BAD_ARG; }
+    SP_GUARD(spatial_cast_shapes(c, max_hits, o));
+}
 AVN_API avn_status avn_spatial_stats_get(avn_world* w, avn_spatial_stats* o) { SP_GUARD(spatial_stats_get(o)); }
 
 }  // extern "C"

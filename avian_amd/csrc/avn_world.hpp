@@ -132,6 +132,7 @@ struct WorldBase {
     virtual avn_status spatial_aabb_intersections(const avn_spatial_aabbs*, uint32_t, const avn_spatial_ids_out*) = 0;
     virtual avn_status spatial_project_points(const avn_spatial_solid_points*, const avn_spatial_projections_out*) = 0;
     virtual avn_status spatial_shape_intersections(const avn_spatial_shapes*, uint32_t, const avn_spatial_ids_out*) = 0;
+    virtual avn_status spatial_cast_shapes(const avn_spatial_shape_casts*, uint32_t max_hits, const avn_spatial_shape_hits_out*) = 0;   // max_hits 0: the closest hit
     virtual avn_status spatial_stats_get(avn_spatial_stats*) = 0;
 };
 

@@ -1,6 +1,6 @@
 // k_spatial.hip — spatial queries on the device (include/avian_mi355x_spatial.h): an LBVH over the collider table and one-lane-per-query
-// traversals for ray casts, ray hits, point and AABB intersections (k_sp_query), point projection (k_sp_project) and shape intersections
-// (k_sp_shapes).
+// traversals for ray casts, ray hits, point and AABB intersections (k_sp_query), point projection (k_sp_project), shape intersections
+// (k_sp_shapes) and shape casts (k_sp_cast).
 //
 // avn_spatial_update (launch_spatial_build), all on the world's stream:
 //   1. k_sp_snapshot   one thread per collider: its pose (collider_pose), the exact shape AABB (shape_aabb), padded, as the leaf box;
@@ -22,7 +22,8 @@
 // Non-finite data never reaches an exact test: a collider with a non-finite position, rotation or shape AABB is not a candidate and has
 // an empty leaf box; a query with a non-finite origin, direction, point or box corner answers a miss / count 0 without traversing.
 // Projection culls with a lower bound of the distance to the node box and shape intersections with the query shape's padded AABB: their
-// padding arguments are in DESIGN.md 4.4.5.
+// padding arguments are in DESIGN.md 4.4.5.  A shape cast culls with the ray of the query AABB's centre against the node box grown by that
+// AABB's half widths.
 #include <cstddef>
 
 #include "avn_kernels.h"
@@ -703,6 +704,406 @@ __global__ __launch_bounds__(SP_WAVE) void k_sp_shapes(SP<T> sp, SQ<T> q) {
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// shape casts (a kernel of its own: the kernels above compile as before).  The header defines the per-pair tests, operation order
+// included; tests/spatial_cast_reference.py does the same operations in order.  DESIGN.md 4.4.6 has the padding argument.
+
+// the header's ball-ray test (solid) of a local ray: false = a miss; an origin inside answers t = 0 with `inside` set
+template <class T> __device__ __forceinline__ bool sp_ball_ray(V3<T> o, V3<T> d, T r, T& t, bool& inside) {
+    const T a = dot(d, d), b = dot(o, d), c = dot(o, o) - r * r;
+    if (c > T(0) && b > T(0)) return false;
+    const V3<T> f = o - d * (b / a);
+    const T delta = a * (r * r - dot(f, f));
+    if (delta < T(0)) return false;
+    t = (-b - sqrt_t(delta)) / a;
+    inside = t <= T(0);
+    if (inside) t = T(0);
+    return true;
+}
+// the header's slab clip (solid) of a local ray against the box of half extents h: axis = -1 when the origin is inside
+template <class T> __device__ __forceinline__ bool sp_slab_ray(V3<T> o, V3<T> d, V3<T> h, T& t, int& axis, T& sg) {
+    T tmin = -sp_inf<T>(), tmax = sp_inf<T>();
+    int na = -1;
+    T nsg = T(0);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        const T oi = sp_vget(o, i), di = sp_vget(d, i), hi = sp_vget(h, i);
+        if (di != T(0)) {
+            const T inv = T(1) / di;
+            T t1 = (-hi - oi) * inv, t2 = (hi - oi) * inv;
+            T sn = T(-1);
+            if (inv < T(0)) { const T x = t1; t1 = t2; t2 = x; sn = T(1); }
+            if (t1 > tmin) { tmin = t1; na = i; nsg = sn; }
+            if (t2 < tmax) tmax = t2;
+        } else if (oi < -hi || oi > hi) {
+            return false;
+        }
+    }
+    if (!(tmin <= tmax) || tmax < T(0)) return false;
+    if (tmin < T(0)) { t = T(0); axis = -1; sg = T(0); }
+    else { t = tmin; axis = na; sg = nsg; }
+    return true;
+}
+template <class T> __device__ __forceinline__ V3<T> sp_unit(int i, T s) { return V3<T>{i == 0 ? s : T(0), i == 1 ? s : T(0), i == 2 ? s : T(0)}; }
+
+// The ray (o, d) of a ball's centre against the cuboid `he` rounded by the ball's radius r, in the cuboid's frame: the union of the three
+// boxes he + r e_i, and for r > 0 the twelve clipped edge cylinders and the eight corner spheres, in that order; the smallest entry wins
+// (strict <), its primitive gives the normal.  pen: the origin is inside the winning primitive (distance 0, no normal).
+template <class T> __device__ __forceinline__ bool sp_round_box_ray(V3<T> o, V3<T> d, V3<T> he, T r, T& t_out, V3<T>& n_out, bool& pen_out) {
+    T best = sp_inf<T>();
+    V3<T> bn = vzero<T>();
+    bool bpen = false, found = false;
+    for (int i = 0; i < 3; ++i) {
+        const V3<T> h = he + sp_unit<T>(i, r);
+        T t, sg; int axis;
+        if (sp_slab_ray<T>(o, d, h, t, axis, sg) && t < best) { best = t; found = true; bpen = axis < 0; bn = axis < 0 ? vzero<T>() : sp_unit<T>(axis, sg); }
+    }
+    if (r > T(0)) {
+        // edge cylinders: edge direction k, the edge through (sa he_a, sb he_b) in the plane of a = k + 1, b = k + 2 (mod 3)
+        for (int e = 0; e < 12; ++e) {
+            const int k = e >> 2, ia = (k + 1) % 3, ib = (k + 2) % 3;
+            const T sa = (e & 1) ? T(1) : T(-1), sb = (e & 2) ? T(1) : T(-1);
+            const T oa = sp_vget(o, ia) - sa * sp_vget(he, ia), ob = sp_vget(o, ib) - sb * sp_vget(he, ib);
+            const T da = sp_vget(d, ia), db = sp_vget(d, ib), ok = sp_vget(o, k), dk = sp_vget(d, k), hk = sp_vget(he, k);
+            const T a = da * da + db * db;
+            if (!(a > T(0))) continue;   // parallel to the edge: the boxes and the corner spheres decide
+            const T b = oa * da + ob * db, c = (oa * oa + ob * ob) - r * r;
+            if (c > T(0) && b > T(0)) continue;
+            const T q = b / a;
+            const T fa = oa - da * q, fb = ob - db * q;
+            const T delta = a * (r * r - (fa * fa + fb * fb));
+            if (delta < T(0)) continue;
+            T t = (-b - sqrt_t(delta)) / a;
+            const bool inside = t <= T(0);
+            if (inside) t = T(0);
+            const T z = ok + dk * t;
+            if (!(fabs_t(z) <= hk)) continue;   // beyond the edge's extent: a corner sphere's
+            if (t < best) {
+                best = t; found = true; bpen = inside;
+                const T pa = oa + da * t, pb = ob + db * t;
+                const T l = sqrt_t(pa * pa + pb * pb);
+                if (inside || !(l > T(0))) bn = vzero<T>();
+                else {
+                    const T na = pa / l, nb = pb / l;
+                    bn = V3<T>{ia == 0 ? na : (ib == 0 ? nb : T(0)), ia == 1 ? na : (ib == 1 ? nb : T(0)), ia == 2 ? na : (ib == 2 ? nb : T(0))};
+                }
+            }
+        }
+        // corner spheres: bit 0 / 1 / 2 of s = the sign of x / y / z
+        for (int s = 0; s < 8; ++s) {
+            const V3<T> cen{(s & 1) ? he.x : -he.x, (s & 2) ? he.y : -he.y, (s & 4) ? he.z : -he.z};
+            const V3<T> oc = o - cen;
+            T t; bool inside;
+            if (!sp_ball_ray<T>(oc, d, r, t, inside)) continue;
+            if (t < best) {
+                best = t; found = true; bpen = inside;
+                const V3<T> p = oc + d * t;
+                const T l = length(p);
+                bn = (inside || !(l > T(0))) ? vzero<T>() : p / l;
+            }
+        }
+    }
+    if (!found) return false;
+    t_out = best; n_out = bn; pen_out = bpen;
+    return true;
+}
+
+template <class T> __device__ __forceinline__ V3<T> sp_sel3(int i, V3<T> a, V3<T> b, V3<T> c) { return i == 0 ? a : (i == 1 ? b : c); }
+// The swept SAT of the collider's cuboid he1 (at the origin of its own frame) and the query's cuboid he2 at pose q moving along dl:
+// the 15 axes in the order e_0..e_2 (collider faces), u_0..u_2 (query faces), e_a x u_b with b outer and a inner (sat_edge_twoway's
+// order).  kin = the axis of the largest entry, n = that axis oriented from the collider towards the query.
+template <class T> __device__ __forceinline__ bool sp_sat_cast(V3<T> he1, V3<T> he2, const Iso<T>& q, V3<T> dl, T& t_out, int& kin_out, V3<T>& n_out, bool& pen_out) {
+    const V3<T> u0 = iso_vec(q, V3<T>{T(1), T(0), T(0)}), u1 = iso_vec(q, V3<T>{T(0), T(1), T(0)}), u2 = iso_vec(q, V3<T>{T(0), T(0), T(1)});
+    T tin = -sp_inf<T>(), tout = sp_inf<T>();
+    int kin = -1;
+    V3<T> nin = vzero<T>();
+    for (int k = 0; k < 15; ++k) {
+        V3<T> ax;
+        if (k < 3) ax = sp_unit<T>(k, T(1));
+        else if (k < 6) ax = sp_sel3(k - 3, u0, u1, u2);
+        else {
+            const int b = (k - 6) / 3, a = (k - 6) % 3;
+            const V3<T> u = sp_sel3(b, u0, u1, u2);
+            const V3<T> axis = a == 0 ? V3<T>{T(0), -u.z, u.y} : (a == 1 ? V3<T>{u.z, T(0), -u.x} : V3<T>{-u.y, u.x, T(0)});
+            const T norm1 = na_norm(axis);
+            if (!(norm1 > Limits<T>::eps)) continue;
+            ax = axis / norm1;
+        }
+        const T s0 = na_dot(ax, q.t), v = na_dot(ax, dl);
+        const T r1 = fabs_t(ax.x) * he1.x + fabs_t(ax.y) * he1.y + fabs_t(ax.z) * he1.z;
+        const T r2 = fabs_t(na_dot(ax, u0)) * he2.x + fabs_t(na_dot(ax, u1)) * he2.y + fabs_t(na_dot(ax, u2)) * he2.z;
+        const T rr = r1 + r2;
+        if (v != T(0)) {
+            const T inv = T(1) / v;
+            T t1 = (-rr - s0) * inv, t2 = (rr - s0) * inv;
+            T sg = T(-1);
+            if (inv < T(0)) { const T x = t1; t1 = t2; t2 = x; sg = T(1); }
+            if (t1 > tin) { tin = t1; kin = k; nin = ax * sg; }
+            if (t2 < tout) tout = t2;
+        } else if (s0 < -rr || s0 > rr) {
+            return false;   // a parallel slab, separated
+        }
+    }
+    if (!(tin <= tout) || tout < T(0)) return false;
+    pen_out = tin < T(0);
+    t_out = pen_out ? T(0) : tin;
+    kin_out = kin; n_out = nin;
+    return true;
+}
+// the witnesses of sp_sat_cast's answer at the impact pose, in the collider's frame
+template <class T> struct CastWitness { V3<T> p1, p2; };
+template <class T> __device__ __forceinline__ V3<T> sp_clamp3(V3<T> p, V3<T> h) {
+    return V3<T>{p.x < -h.x ? -h.x : (p.x > h.x ? h.x : p.x), p.y < -h.y ? -h.y : (p.y > h.y ? h.y : p.y), p.z < -h.z ? -h.z : (p.z > h.z ? h.z : p.z)};
+}
+// When the support feature's witness falls outside the other shape's face or edge (parallel faces or edges: the contact is a polygon or a
+// segment), the witness is clamped onto the collider's cuboid and the query's witness is the query cuboid's closest point to it.
+template <class T> __device__ __forceinline__ CastWitness<T> sp_sat_witness(V3<T> he1, V3<T> he2, const Iso<T>& q, V3<T> tp, int kin, V3<T> n) {
+    const V3<T> s1 = cuboid_support_point(he1, n);
+    const V3<T> s2 = iso_vec(q, cuboid_support_point(he2, iso_inv_vec(q, -n))) + tp;
+    V3<T> p1, p2;
+    bool in;
+    if (kin < 3) {
+        // a face of the collider: the query's support vertex against the normal and its projection onto the face
+        p1 = V3<T>{kin == 0 ? n.x * he1.x : s2.x, kin == 1 ? n.y * he1.y : s2.y, kin == 2 ? n.z * he1.z : s2.z};
+        p2 = s2;
+        in = (kin == 0 || fabs_t(s2.x) <= he1.x) && (kin == 1 || fabs_t(s2.y) <= he1.y) && (kin == 2 || fabs_t(s2.z) <= he1.z);
+    } else if (kin < 6) {
+        // a face of the query: the collider's support vertex towards the query and its projection onto the face's plane
+        const T h = kin == 3 ? he2.x : (kin == 4 ? he2.y : he2.z);
+        p1 = s1;
+        p2 = s1 - n * (na_dot(s1 - tp, n) + h);
+        const V3<T> x = iso_inv_vec(q, s1 - tp);
+        in = (kin == 3 || fabs_t(x.x) <= he2.x) && (kin == 4 || fabs_t(x.y) <= he2.y) && (kin == 5 || fabs_t(x.z) <= he2.z);
+        if (!in) {
+            // start from the point of the query's face nearest the vertex
+            const V3<T> xl = iso_inv_vec(q, -n);
+            const V3<T> xc = sp_clamp3(x, he2);
+            const V3<T> xf{kin == 3 ? copysign_t(he2.x, xl.x) : xc.x, kin == 4 ? copysign_t(he2.y, xl.y) : xc.y, kin == 5 ? copysign_t(he2.z, xl.z) : xc.z};
+            p1 = iso_vec(q, xf) + tp;
+        }
+    } else {
+        // an edge pair: the closest points of the two support edges' lines, s1 + lambda e_a and s2 + mu u_b
+        const int b = (kin - 6) / 3, a = (kin - 6) % 3;
+        const V3<T> ea = sp_unit<T>(a, T(1));
+        const V3<T> ub = iso_vec(q, sp_unit<T>(b, T(1)));
+        const V3<T> w = s1 - s2;
+        const T bc = na_dot(ea, ub), cc = na_dot(ub, ub), dd = na_dot(ea, w), ee = na_dot(ub, w);
+        const T den = cc - bc * bc;
+        const bool cross = den > Limits<T>::eps;
+        const T lam = (bc * ee - cc * dd) / den, mu = (ee - bc * dd) / den;
+        // (edges too nearly parallel for the quotient: the middle of the collider's edge)
+        p1 = cross ? s1 + ea * lam : s1 - ea * na_dot(ea, s1);
+        p2 = s2 + ub * mu;
+        const V3<T> x = iso_inv_vec(q, p2 - tp);
+        in = cross && fabs_t(na_dot(ea, p1)) <= (a == 0 ? he1.x : (a == 1 ? he1.y : he1.z)) && fabs_t(b == 0 ? x.x : (b == 1 ? x.y : x.z)) <= (b == 0 ? he2.x : (b == 1 ? he2.y : he2.z));
+    }
+    if (in) return {p1, p2};
+    // onto the collider, onto the query, and once more: for faces whose edges are parallel this ends in the overlap of the two faces
+    p1 = sp_clamp3(p1, he1);
+    p2 = iso_vec(q, sp_clamp3(iso_inv_vec(q, p1 - tp), he2)) + tp;
+    p1 = sp_clamp3(p2, he1);
+    return {p1, iso_vec(q, sp_clamp3(iso_inv_vec(q, p1 - tp), he2)) + tp};
+}
+
+// The header's cast of the query shape (shape2, he2, pose iso2 = make_isometry of its position and rotation) along d against one collider
+// (shape 1).  World-space answer: toi, the witnesses p1 (collider) / p2 (query shape at the impact pose) and the collider's normal n1
+// (the record's normal2 is -n1); all zero when the shapes overlap at the start.
+template <class T>
+__device__ __forceinline__ bool sp_cast_exact(uint32_t shape2, V3<T> he2, const Iso<T>& iso2, V3<T> d, T max_distance, uint32_t shape1, V3<T> he1, V3<T> pos1, Q4<T> rot1,
+                                              T& toi, V3<T>& p1, V3<T>& p2, V3<T>& n1) {
+    const Iso<T> q = iso_inv_mul(Iso<T>{rot1, pos1}, iso2);
+    const V3<T> dl = na_qrot(qinverse(rot1), d);
+    const bool ball1 = shape1 == AVN_SHAPE_BALL, ball2 = shape2 == AVN_SHAPE_BALL;
+    T t; bool pen; V3<T> n;
+    int kin = -1;
+    if (ball1 && ball2) {
+        if (!sp_ball_ray<T>(q.t, dl, he1.x + he2.x, t, pen)) return false;
+    } else if (ball1 || ball2) {
+        // the ball's centre against the rounded cuboid, in the cuboid's frame (the query cuboid's: the ray reversed)
+        const V3<T> o = ball2 ? q.t : iso_inv_point(q, vzero<T>());
+        const V3<T> dd = ball2 ? dl : -iso_inv_vec(q, dl);
+        if (!sp_round_box_ray<T>(o, dd, ball2 ? he1 : he2, ball2 ? he2.x : he1.x, t, n, pen)) return false;
+    } else {
+        if (!sp_sat_cast<T>(he1, he2, q, dl, t, kin, n, pen)) return false;
+    }
+    if (!(t <= max_distance) || !finite_t(t)) return false;
+    toi = t;
+    V3<T> w1 = vzero<T>(), w2 = vzero<T>(), wn = vzero<T>();
+    if (!pen) {
+        const V3<T> c2 = iso2.t + d * t;   // the query shape's position at the impact
+        if (ball1 && ball2) {
+            const V3<T> p = q.t + dl * t;
+            const T l = length(p);
+            n = l > T(0) ? p / l : vzero<T>();
+            wn = na_qrot(rot1, n);
+            w1 = na_qrot(rot1, n * he1.x) + pos1;
+            w2 = c2 + (-wn) * he2.x;
+        } else if (ball2) {
+            const V3<T> pk = (q.t + dl * t) - n * he2.x;
+            wn = na_qrot(rot1, n);
+            w1 = na_qrot(rot1, pk) + pos1;
+            w2 = c2 + (-wn) * he2.x;
+        } else if (ball1) {
+            const V3<T> o = iso_inv_point(q, vzero<T>());
+            const V3<T> dd = -iso_inv_vec(q, dl);
+            const V3<T> pk = (o + dd * t) - n * he1.x;
+            wn = -na_qrot(iso2.r, n);
+            w2 = na_qrot(iso2.r, pk) + c2;
+            w1 = pos1 + wn * he1.x;
+        } else {
+            const CastWitness<T> wt = sp_sat_witness<T>(he1, he2, q, q.t + dl * t, kin, n);
+            wn = na_qrot(rot1, n);
+            w1 = na_qrot(rot1, wt.p1) + pos1;
+            w2 = na_qrot(rot1, wt.p2) + pos1;
+        }
+    }
+    p1 = w1; p2 = w2; n1 = wn;
+    return true;
+}
+
+template <class T> __device__ __forceinline__ void sp_put(SpatialShapeHit<T>& h, uint32_t c, uint32_t e, T t, V3<T> p1, V3<T> p2, V3<T> n1) {
+    h.collider = c; h.entity = e; h.distance = t;
+    h.point1[0] = p1.x; h.point1[1] = p1.y; h.point1[2] = p1.z;
+    h.point2[0] = p2.x; h.point2[1] = p2.y; h.point2[2] = p2.z;
+    h.normal1[0] = n1.x; h.normal1[1] = n1.y; h.normal1[2] = n1.z;
+    // normal2 = -normal1, a zero component staying +0 (a miss and an overlap at the start: every byte 0)
+    h.normal2[0] = n1.x == T(0) ? T(0) : -n1.x; h.normal2[1] = n1.y == T(0) ? T(0) : -n1.y; h.normal2[2] = n1.z == T(0) ? T(0) : -n1.z;
+}
+
+// one lane per cast; blocks of one wave; MANY: the nearest-k list (shape_hits), else the closest hit (cast_shapes)
+template <class T, bool MANY>
+__global__ __launch_bounds__(SP_WAVE) void k_sp_cast(SP<T> sp, SQ<T> q) {
+    __shared__ uint32_t stack[SP_STACK * SP_WAVE];
+    const uint32_t lane = threadIdx.x;
+    const uint32_t qi = blockIdx.x * SP_WAVE + lane;
+    uint32_t nodes_tested = 0, leaves_tested = 0, overflow = 0;
+    const uint32_t n = sp.n;
+    if (qi < q.n) {
+        const uint32_t mask = q.mask ? q.mask[qi] : 0xFFFFFFFFu;
+        const uint32_t shape2 = q.shape[qi];
+        const V3<T> pos2{q.a[3 * (size_t)qi], q.a[3 * (size_t)qi + 1], q.a[3 * (size_t)qi + 2]};
+        const V3<T> d{q.b[3 * (size_t)qi], q.b[3 * (size_t)qi + 1], q.b[3 * (size_t)qi + 2]};
+        V3<T> he2{q.he[3 * (size_t)qi], q.he[3 * (size_t)qi + 1], q.he[3 * (size_t)qi + 2]};
+        const Q4<T> rot2{q.rot[4 * (size_t)qi], q.rot[4 * (size_t)qi + 1], q.rot[4 * (size_t)qi + 2], q.rot[4 * (size_t)qi + 3]};
+        const T max_distance = q.max_distance[qi];
+        if (shape2 == AVN_SHAPE_BALL) he2 = V3<T>{he2.x, he2.x, he2.x};   // (a ball has its radius in x: y and z are not read)
+        // k_sp_shapes' rule, plus a finite direction and a max_distance that is not NaN: otherwise a miss / count 0
+        bool valid = shape2 <= AVN_SHAPE_BALL && is_finite(pos2) && is_finite(V3<T>{rot2.x, rot2.y, rot2.z}) && finite_t(rot2.w) && is_finite(he2) &&
+                     he2.x >= T(0) && he2.y >= T(0) && he2.z >= T(0) && is_finite(d) && max_distance == max_distance;
+        RayCtx<T> r;
+        r.o = r.d = r.inv = vzero<T>(); r.zero = 0; r.tol = T(0);
+        V3<T> hw = vzero<T>();
+        Iso<T> iso2{Q4<T>{T(0), T(0), T(0), T(1)}, pos2};
+        if (valid) {
+            // the cast ray: from the centre of the query shape's AABB at its pose (padded as a leaf box is) along d
+            V3<T> a, b;
+            shape_aabb<T>(shape2, he2, pos2, rot2, a, b);
+            valid = is_finite(a) && is_finite(b);
+            const T pad = T(64) * Limits<T>::eps * smax(sp_maxabs(a), sp_maxabs(b));
+            const V3<T> pp{pad, pad, pad};
+            const V3<T> qmin = a - pp, qmax = b + pp;
+            r.o = (qmin + qmax) * T(0.5);
+            hw = (qmax - qmin) * T(0.5);
+            r.d = d;
+            r.inv = V3<T>{d.x != T(0) ? T(1) / d.x : T(0), d.y != T(0) ? T(1) / d.y : T(0), d.z != T(0) ? T(1) / d.z : T(0)};
+            r.zero = (d.x == T(0) ? 1u : 0u) | (d.y == T(0) ? 2u : 0u) | (d.z == T(0) ? 4u : 0u);
+            r.tol = T(64) * Limits<T>::eps * sp_maxabs(r.o);
+            iso2 = make_isometry(pos2, rot2);
+        }
+        T best = sp_inf<T>();
+        uint32_t best_c = AVN_SPATIAL_MISS;
+        V3<T> best_p1 = vzero<T>(), best_p2 = vzero<T>(), best_n1 = vzero<T>();
+        uint32_t found = 0;
+        SpatialShapeHit<T>* hl = MANY ? q.cast + (size_t)qi * q.cap : nullptr;
+        // entry distance of the cast ray into the node box grown by the query AABB's half widths (+inf = culled: only an entry STRICTLY
+        // above the best distance culls, so a collider at the best distance with a lower index is still reached)
+        auto test = [&](uint32_t node) -> T {
+            ++nodes_tested;
+            const Vec4<T> lo = sp.bmin[node], hi = sp.bmax[node];
+            return sp_ray_box(r, make4<T>(lo.x - hw.x, lo.y - hw.y, lo.z - hw.z, T(0)), make4<T>(hi.x + hw.x, hi.y + hw.y, hi.z + hw.z, T(0)),
+                              MANY ? max_distance : smin(best, max_distance));
+        };
+        auto leaf = [&](uint32_t node) {
+            const uint32_t c = sp.leaf_col[node - (n - 1)];
+            const uint4 info = sp.info[c];
+            if (!info.w || (info.y & mask) == 0u || (q.n_excluded && sp_excluded(q.excluded, q.n_excluded, info.x))) return;
+            ++leaves_tested;
+            T toi; V3<T> p1, p2, n1;
+            if (!sp_cast_exact<T>(shape2, he2, iso2, d, max_distance, info.z, xyz<T>(sp.he[c]), xyz<T>(sp.pos[c]), quat<T>(sp.rot[c]), toi, p1, p2, n1)) return;
+            if (!MANY) {
+                if (toi < best || (toi == best && c < best_c)) { best = toi; best_c = c; best_p1 = p1; best_p2 = p2; best_n1 = n1; }
+            } else {
+                const uint32_t k = q.cap;
+                uint32_t m = found < k ? found : k;
+                ++found;
+                if (m == k) {
+                    const T ld = hl[k - 1].distance;
+                    if (!(toi < ld || (toi == ld && c < hl[k - 1].collider))) return;
+                    m = k - 1;
+                }
+                while (m > 0 && (hl[m - 1].distance > toi || (hl[m - 1].distance == toi && hl[m - 1].collider > c))) { hl[m] = hl[m - 1]; --m; }
+                SpatialShapeHit<T> h;
+                sp_put<T>(h, c, info.x, toi, p1, p2, n1);
+                hl[m] = h;
+            }
+        };
+        if (valid && n >= 1 && test(0) != sp_inf<T>()) {
+            uint32_t sp_top = 0, node = 0;
+            for (;;) {
+                // (a tree of one collider: its root is the leaf, handled by the same leaf call site)
+                uint2 ch = make_uint2(0u, 0u);
+                T e0 = T(0), e1 = sp_inf<T>();
+                if (n > 1) { ch = sp.child[node]; e0 = test(ch.x); e1 = test(ch.y); }
+                const bool l0 = ch.x >= n - 1, l1 = ch.y >= n - 1;
+                // one leaf call site: the pair tests are emitted once
+                uint32_t pending = (l0 && e0 != sp_inf<T>() ? 1u : 0u) | (l1 && e1 != sp_inf<T>() ? 2u : 0u);
+                while (pending) {
+                    const bool first = (pending & 1u) != 0;
+                    // (the first leaf may have shrunk the best distance below the second one's entry)
+                    if (first || MANY || !(e1 > best)) leaf(first ? ch.x : ch.y);
+                    pending &= first ? ~1u : ~2u;
+                }
+                const bool g0 = !l0 && e0 != sp_inf<T>() && (MANY || !(e0 > best)), g1 = !l1 && e1 != sp_inf<T>() && (MANY || !(e1 > best));
+                if (g0 && g1) {
+                    const bool first0 = !(e1 < e0);   // the nearer child first (ties: the left one)
+                    if (sp_top < SP_STACK) { stack[sp_top * SP_WAVE + lane] = first0 ? ch.y : ch.x; ++sp_top; }
+                    else overflow = 1;   // (cannot happen: the depth of the tree is at most 64)
+                    node = first0 ? ch.x : ch.y;
+                    continue;
+                }
+                if (g0) { node = ch.x; continue; }
+                if (g1) { node = ch.y; continue; }
+                // pop; a node pushed before the best distance shrank is re-tested against it (closest hit only)
+                node = AVN_SPATIAL_MISS;
+                while (sp_top > 0) {
+                    --sp_top;
+                    const uint32_t cand = stack[sp_top * SP_WAVE + lane];
+                    if (MANY || test(cand) != sp_inf<T>()) { node = cand; break; }
+                }
+                if (node == AVN_SPATIAL_MISS) break;
+            }
+        }
+        if (!MANY) {
+            SpatialShapeHit<T> h;
+            sp_put<T>(h, best_c, best_c == AVN_SPATIAL_MISS ? AVN_SPATIAL_MISS : sp.info[best_c].x, best_c == AVN_SPATIAL_MISS ? T(0) : best, best_p1, best_p2, best_n1);
+            q.cast[qi] = h;
+        } else {
+            SpatialShapeHit<T> miss;
+            sp_put<T>(miss, AVN_SPATIAL_MISS, AVN_SPATIAL_MISS, T(0), vzero<T>(), vzero<T>(), vzero<T>());
+            for (uint32_t m = found; m < q.cap; ++m) hl[m] = miss;
+            q.count[qi] = found;
+        }
+    }
+    uint32_t a = nodes_tested, b = leaves_tested, o = overflow;
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) { a += __shfl_xor(a, off); b += __shfl_xor(b, off); o |= __shfl_xor(o, off); }
+    if (lane == 0) {
+        atomicAdd(&q.stats[0], (unsigned long long)a);
+        atomicAdd(&q.stats[1], (unsigned long long)b);
+        if (o) atomicOr(&q.stats[2], 1ull);
+    }
+}
+
 template <class T> void launch_spatial_query(const SP<T>& sp, const SQ<T>& q, int kind, hipStream_t s) {
     (void)hipMemsetAsync(q.stats, 0, 4 * sizeof(unsigned long long), s);
     if (q.n == 0) return;
@@ -713,6 +1114,8 @@ template <class T> void launch_spatial_query(const SP<T>& sp, const SQ<T>& q, in
         case SPQ_POINTS: hipLaunchKernelGGL((k_sp_query<T, SPQ_POINTS>), g, b, 0, s, sp, q); break;
         case SPQ_PROJECT: hipLaunchKernelGGL((k_sp_project<T>), g, b, 0, s, sp, q); break;
         case SPQ_SHAPES: hipLaunchKernelGGL((k_sp_shapes<T>), g, b, 0, s, sp, q); break;
+        case SPQ_CAST: hipLaunchKernelGGL((k_sp_cast<T, false>), g, b, 0, s, sp, q); break;
+        case SPQ_CAST_HITS: hipLaunchKernelGGL((k_sp_cast<T, true>), g, b, 0, s, sp, q); break;
         default: hipLaunchKernelGGL((k_sp_query<T, SPQ_AABBS>), g, b, 0, s, sp, q); break;
     }
 }
@@ -721,6 +1124,12 @@ static_assert(sizeof(SpatialHit<float>) == sizeof(avn_spatial_hit_f32) && sizeof
 static_assert(sizeof(SpatialProjection<float>) == sizeof(avn_spatial_projection_f32) && sizeof(SpatialProjection<double>) == sizeof(avn_spatial_projection_f64) &&
               offsetof(SpatialProjection<double>, point) == offsetof(avn_spatial_projection_f64, point) && offsetof(SpatialProjection<double>, reserved) == offsetof(avn_spatial_projection_f64, reserved) && offsetof(SpatialProjection<float>, distance) == offsetof(avn_spatial_projection_f32, distance),
               "projection record layout");
+static_assert(sizeof(SpatialShapeHit<float>) == sizeof(avn_spatial_shape_hit_f32) && sizeof(SpatialShapeHit<double>) == sizeof(avn_spatial_shape_hit_f64) &&
+              sizeof(avn_spatial_shape_hit_f32) == 60 && sizeof(avn_spatial_shape_hit_f64) == 112 &&
+              offsetof(SpatialShapeHit<float>, distance) == offsetof(avn_spatial_shape_hit_f32, distance) && offsetof(SpatialShapeHit<double>, distance) == offsetof(avn_spatial_shape_hit_f64, distance) &&
+              offsetof(SpatialShapeHit<float>, point2) == offsetof(avn_spatial_shape_hit_f32, point2) && offsetof(SpatialShapeHit<double>, point2) == offsetof(avn_spatial_shape_hit_f64, point2) &&
+              offsetof(SpatialShapeHit<float>, normal2) == offsetof(avn_spatial_shape_hit_f32, normal2) && offsetof(SpatialShapeHit<double>, normal2) == offsetof(avn_spatial_shape_hit_f64, normal2),
+              "shape hit record layout");
 template void launch_spatial_build<float>(const DW<float>&, const BP<float>&, const SP<float>&, hipStream_t);
 template void launch_spatial_build<double>(const DW<double>&, const BP<double>&, const SP<double>&, hipStream_t);
 template void launch_spatial_query<float>(const SP<float>&, const SQ<float>&, int, hipStream_t);

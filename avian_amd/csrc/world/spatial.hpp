@@ -203,6 +203,42 @@
         }
         return sp_finish();
     }
+    // cast_shapes (max_hits == 0: the closest hit per cast) and shape_hits (the max_hits nearest, plus the true count)
+    avn_status spatial_cast_shapes(const avn_spatial_shape_casts* s, uint32_t max_hits, const avn_spatial_shape_hits_out* out) override {
+        if (!s || !out) { error = "spatial shape cast: null argument"; return AVN_ERR_BAD_ARG; }
+        const uint32_t n = s->count;
+        const bool many = max_hits != 0;
+        if (n && (!s->shape || !s->half_extents || !s->position || !s->rotation || !s->direction || !s->max_distance || !out->hits || (many && !out->count))) {
+            error = "spatial shape cast: null array"; return AVN_ERR_BAD_ARG;
+        }
+        if (max_hits > AVN_SPATIAL_MAX_HITS) { error = "spatial_shape_hits: max_hits above AVN_SPATIAL_MAX_HITS"; return AVN_ERR_BAD_ARG; }
+        avn_status st = sp_check(s->flags);
+        if (st != AVN_OK) return st;
+        const bool dev = (s->flags & AVN_SPATIAL_DEVICE_POINTERS) != 0;
+        std::vector<uint32_t> ex;
+        if ((st = sp_excluded(s->filter, dev, ex)) != AVN_OK) return st;
+        const size_t n_rec = (size_t)n * (many ? max_hits : 1);
+        if ((st = stage_reserve(sp_stage_bytes(dev, n, 3 * al(3 * sizeof(T) * n) + al(4 * sizeof(T) * n) + al(sizeof(T) * n) + al(n), al(n_rec * sizeof(SpatialShapeHit<T>)), ex.size()))) != AVN_OK) return st;
+        SQ<T> q{};
+        q.n = n; q.cap = max_hits;
+        if ((st = sp_in<uint8_t>(s->shape, n, dev, &q.shape)) != AVN_OK) return st;
+        if ((st = sp_in<T>(s->half_extents, 3 * (size_t)n, dev, &q.he)) != AVN_OK) return st;
+        if ((st = sp_in<T>(s->position, 3 * (size_t)n, dev, &q.a)) != AVN_OK) return st;
+        if ((st = sp_in<T>(s->rotation, 4 * (size_t)n, dev, &q.rot)) != AVN_OK) return st;
+        if ((st = sp_in<T>(s->direction, 3 * (size_t)n, dev, &q.b)) != AVN_OK) return st;
+        if ((st = sp_in<T>(s->max_distance, n, dev, &q.max_distance)) != AVN_OK) return st;
+        if ((st = sp_in<uint32_t>(s->filter.mask, n, dev, &q.mask)) != AVN_OK) return st;
+        if ((st = stage_in<uint32_t>(ex.data(), ex.size(), &q.excluded)) != AVN_OK) return st;
+        q.n_excluded = (uint32_t)ex.size();
+        q.cast = sp_out<SpatialShapeHit<T>>(out->hits, n_rec, dev);
+        if (many) q.count = sp_out<uint32_t>(out->count, n, dev);
+        if ((st = sp_run(q, many ? SPQ_CAST_HITS : SPQ_CAST)) != AVN_OK) return st;
+        if (!dev) {
+            if ((st = stage_out<SpatialShapeHit<T>>(out->hits, q.cast, n_rec)) != AVN_OK) return st;
+            if (many && (st = stage_out<uint32_t>(out->count, q.count, n)) != AVN_OK) return st;
+        }
+        return sp_finish();
+    }
     avn_status spatial_stats_get(avn_spatial_stats* o) override {
         if (!o) return AVN_ERR_BAD_ARG;
         std::memset(o, 0, sizeof *o);

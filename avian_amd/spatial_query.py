@@ -1,5 +1,5 @@
 """ctypes binding of ``include/avian_mi355x_spatial.h``: device spatial queries (ray casts, ray hits, point and AABB intersections, point
-projection, shape intersections) over the
+projection, shape intersections, shape casts) over the
 colliders a :class:`avian_amd._ffi.World` holds on the device.
 
 Numpy arrays in and out (copied through the library's staging), or torch tensors on the world's GPU (``AVN_SPATIAL_DEVICE_POINTERS``: the
@@ -47,6 +47,25 @@ class avn_spatial_shapes(C.Structure):
                 ("filter", avn_spatial_filter)]
 
 
+class avn_spatial_shape_casts(C.Structure):
+    _fields_ = [("count", C.c_uint32), ("flags", C.c_uint32), ("shape", vp), ("half_extents", vp), ("position", vp), ("rotation", vp),
+                ("direction", vp), ("max_distance", vp), ("filter", avn_spatial_filter)]
+
+
+class avn_spatial_shape_hit_f32(C.Structure):
+    _fields_ = [("collider", C.c_uint32), ("entity", C.c_uint32), ("distance", C.c_float), ("point1", C.c_float * 3), ("point2", C.c_float * 3),
+                ("normal1", C.c_float * 3), ("normal2", C.c_float * 3)]
+
+
+class avn_spatial_shape_hit_f64(C.Structure):
+    _fields_ = [("collider", C.c_uint32), ("entity", C.c_uint32), ("distance", C.c_double), ("point1", C.c_double * 3), ("point2", C.c_double * 3),
+                ("normal1", C.c_double * 3), ("normal2", C.c_double * 3)]
+
+
+class avn_spatial_shape_hits_out(C.Structure):
+    _fields_ = [("hits", vp), ("count", vp)]
+
+
 class avn_spatial_projection_f32(C.Structure):
     _fields_ = [("collider", C.c_uint32), ("entity", C.c_uint32), ("is_inside", C.c_uint32), ("point", C.c_float * 3), ("distance", C.c_float)]
 
@@ -82,9 +101,11 @@ class avn_spatial_stats(C.Structure):
 
 STRUCTS = [avn_spatial_filter, avn_spatial_rays, avn_spatial_points, avn_spatial_aabbs, avn_spatial_hit_f32, avn_spatial_hit_f64,
            avn_spatial_hits_out, avn_spatial_ids_out, avn_spatial_stats, avn_spatial_solid_points, avn_spatial_shapes,
-           avn_spatial_projection_f32, avn_spatial_projection_f64, avn_spatial_projections_out]
+           avn_spatial_projection_f32, avn_spatial_projection_f64, avn_spatial_projections_out, avn_spatial_shape_casts,
+           avn_spatial_shape_hit_f32, avn_spatial_shape_hit_f64, avn_spatial_shape_hits_out]
 SYMBOLS = ["avn_spatial_update", "avn_spatial_cast_rays", "avn_spatial_ray_hits", "avn_spatial_point_intersections",
-           "avn_spatial_aabb_intersections", "avn_spatial_stats_get", "avn_spatial_project_points", "avn_spatial_shape_intersections"]
+           "avn_spatial_aabb_intersections", "avn_spatial_stats_get", "avn_spatial_project_points", "avn_spatial_shape_intersections",
+           "avn_spatial_cast_shapes", "avn_spatial_shape_hits"]
 
 
 def hit_dtype(bits: int) -> np.dtype:
@@ -99,6 +120,13 @@ def projection_dtype(bits: int) -> np.dtype:
     return np.dtype([("collider", np.uint32), ("entity", np.uint32), ("is_inside", np.uint32), ("point", s, (3,)), ("distance", s)], align=True)
 
 
+def shape_hit_dtype(bits: int) -> np.dtype:
+    """numpy mirror of avn_spatial_shape_hit_fNN (60 / 112 bytes, no padding)."""
+    s = np.float32 if bits == 32 else np.float64
+    return np.dtype([("collider", np.uint32), ("entity", np.uint32), ("distance", s), ("point1", s, (3,)), ("point2", s, (3,)),
+                     ("normal1", s, (3,)), ("normal2", s, (3,))], align=True)
+
+
 def _declare(dll):
     for name in SYMBOLS:
         getattr(dll, name).restype = C.c_int32
@@ -110,6 +138,8 @@ def _declare(dll):
     dll.avn_spatial_stats_get.argtypes = [vp, vp]
     dll.avn_spatial_project_points.argtypes = [vp, vp, vp]
     dll.avn_spatial_shape_intersections.argtypes = [vp, vp, C.c_uint32, vp]
+    dll.avn_spatial_cast_shapes.argtypes = [vp, vp, vp]
+    dll.avn_spatial_shape_hits.argtypes = [vp, vp, C.c_uint32, vp]
 
 
 class SpatialQuery:
@@ -130,6 +160,7 @@ class SpatialQuery:
         self.dtype = world.dtype
         self.hit_dtype = hit_dtype(self.bits)
         self.projection_dtype = projection_dtype(self.bits)
+        self.shape_hit_dtype = shape_hit_dtype(self.bits)
         self._keep = []
 
     # -- plumbing ------------------------------------------------------------------------------
@@ -161,7 +192,7 @@ class SpatialQuery:
     def _out(self, shape, dt, dev, like=None):
         if dev:
             import torch
-            if dt is self.hit_dtype or dt is self.projection_dtype:
+            if dt is self.hit_dtype or dt is self.projection_dtype or dt is self.shape_hit_dtype:
                 t = torch.empty(tuple(shape) + (dt.itemsize,), dtype=torch.uint8, device=like.device)
             else:
                 t = torch.empty(shape, dtype={np.uint32: torch.int32}[dt], device=like.device)
@@ -299,6 +330,44 @@ class SpatialQuery:
         self._sync_torch(dev)
         self._check(self.dll.avn_spatial_shape_intersections(self.world.handle, C.byref(q), int(cap), C.byref(o)))
         return ids, cnt
+
+    def _casts(self, shape, half_extents, position, rotation, direction, max_distance, mask, excluded, skip_host_shapes):
+        dev = self._is_tensor(position)
+        n = int(position.shape[0])
+        q = avn_spatial_shape_casts()
+        q.count = n
+        q.flags = self._flags(dev, skip_host_shapes)
+        q.shape = self._arr(shape, np.uint8, dev, (n,))
+        q.half_extents = self._arr(half_extents, self.dtype, dev, (n, 3))
+        q.position = self._arr(position, self.dtype, dev, (n, 3))
+        q.rotation = self._arr(rotation, self.dtype, dev, (n, 4))
+        q.direction = self._arr(direction, self.dtype, dev, (n, 3))
+        if max_distance is None:
+            max_distance = np.full(n, np.inf) if not dev else position.new_full((n,), float("inf"))
+        q.max_distance = self._arr(max_distance, self.dtype, dev, (n,))
+        q.filter = self._filter(n, mask, excluded, dev)
+        return q, n, dev
+
+    def cast_shapes(self, shape, half_extents, position, rotation, direction, max_distance=None, mask=None, excluded=None, skip_host_shapes=False):
+        """SpatialQueryPipeline::cast_shape per cast (AVN_SHAPE_CUBOID = 0 / AVN_SHAPE_BALL = 1, a ball's radius in half_extents[:, 0]): a
+        structured array of shape-hit records (``shape_hit_dtype``; collider == MISS: no hit).  Device tensors in: a uint8 tensor
+        [n, itemsize] of the same records out."""
+        q, n, dev = self._casts(shape, half_extents, position, rotation, direction, max_distance, mask, excluded, skip_host_shapes)
+        hits, hp = self._out((n,), self.shape_hit_dtype, dev, position)
+        o = avn_spatial_shape_hits_out(hp, None)
+        self._sync_torch(dev)
+        self._check(self.dll.avn_spatial_cast_shapes(self.world.handle, C.byref(q), C.byref(o)))
+        return hits
+
+    def shape_hits(self, shape, half_extents, position, rotation, direction, max_hits, max_distance=None, mask=None, excluded=None, skip_host_shapes=False):
+        """SpatialQueryPipeline::shape_hits: (records [n, max_hits] nearest first, true hit counts [n])."""
+        q, n, dev = self._casts(shape, half_extents, position, rotation, direction, max_distance, mask, excluded, skip_host_shapes)
+        hits, hp = self._out((n, max(int(max_hits), 1)), self.shape_hit_dtype, dev, position)
+        cnt, cp = self._out((n,), np.uint32, dev, position)
+        o = avn_spatial_shape_hits_out(hp, cp)
+        self._sync_torch(dev)
+        self._check(self.dll.avn_spatial_shape_hits(self.world.handle, C.byref(q), int(max_hits), C.byref(o)))
+        return hits, cnt
 
     def stats(self) -> avn_spatial_stats:
         s = avn_spatial_stats()

@@ -1,6 +1,7 @@
 /*
- * avian_mi355x_spatial.h — device spatial queries: ray casts, point and AABB intersections, point projection and shape intersections against
- * the colliders the world holds in HBM.  Of SpatialQueryPipeline's query families only the shape casts (cast_shape, shape_hits) are not here.
+ * avian_mi355x_spatial.h — device spatial queries: ray casts, point and AABB intersections, point projection, shape intersections and shape
+ * casts against the colliders the world holds in HBM: every query family of SpatialQueryPipeline, for the shapes with device geometry (Ball,
+ * Cuboid).
  *
  * Mirrors Avian's `SpatialQueryPlugin` (spatial_query/mod.rs:190-212), whose systems run in `PhysicsStepSystems::SpatialQuery` right after
  * `Sleeping` (schedule/mod.rs:98-105): `update_spatial_query_pipeline` rebuilds a BVH of every collider from `Position` / `Rotation`
@@ -53,19 +54,57 @@
  *      cuboid / cuboid: parry's intersection_test_cuboid_cuboid, in this order: sat_normal_oneway(he1, he2, pos12) > 0 -> disjoint;
  *        sat_normal_oneway(he2, he1, iso_inverse(pos12)) > 0 -> disjoint; sat_edge_twoway(he1, he2, pos12) > 0 -> disjoint (edge axes
  *        whose norm is <= eps are skipped); otherwise intersecting.  The three functions are the narrow phase's.
+ *  - shape cast (SpatialQueryPipeline::cast_shape / shape_hits; parry's cast_shapes with target_distance = 0, compute_contact_on_penetration =
+ *    false).  Parry casts these pairs with an iterative GJK ray cast (ball / ball excepted) whose iteration cannot be restated bit for bit, so
+ *    the time of impact per pair is DEFINED HERE, in closed form, in the collider's frame (shape 1 = the collider, shape 2 = the cast shape):
+ *      q = iso_inv_mul({collider rotation, collider position}, make_isometry(query position, query rotation)),  d_l = na_qrot(rot_c^-1, d).
+ *      A local ball-ray test B(o, d, r) and slab clip S(o, d, h) are the ray tests above, solid: B: a, b, c as above, a miss when c > 0 &&
+ *      b > 0, delta = a (r^2 - |f|^2), a miss when delta < 0, t = (-b - sqrt(delta)) / a, t <= 0 -> inside, t = 0.  S: entry = the largest
+ *      t_near (strict >), exit = the smallest t_far, a miss when entry > exit or exit < 0, entry < 0 -> inside, t = 0.
+ *      ball / ball: B(q.t, d_l, r_c + r_q).  n = (q.t + d_l t) / |q.t + d_l t| (0 when that is 0); point1 = rot_c (n r_c) + pos_c.
+ *      ball and cuboid, in either role: the ray (o, dd) of the ball's centre against the cuboid rounded by the ball's radius r, in the
+ *        cuboid's frame.  A ball cast at a cuboid collider: o = q.t, dd = d_l.  A cuboid cast at a ball collider (the ray reversed in the
+ *        cuboid's, i.e. the query's, frame): o = iso_inv_point(q, 0), dd = -iso_inv_vec(q, d_l); the two sides of the record swap.  The
+ *        rounded cuboid is the union of, in this order: the three boxes he + r e_i (S; i = x, y, z), and when r > 0 the twelve edge
+ *        cylinders (edge direction k = x, y, z; a = k + 1, b = k + 2 mod 3; the edge through (sa he_a, sb he_b), e = 4 k + (sa > 0) + 2 (sb >
+ *        0); B on the (a, b) components alone, left out when those components of dd are both 0, accepted when |o_k + dd_k t| <= he_k) and the eight corner spheres (bit 0 / 1 / 2 of
+ *        the index = the sign of x / y / z; B).  The distance is the smallest entry over the primitives (strict <: the first in that order
+ *        wins a tie) and the normal is that primitive's: the entry face's, (p_a, p_b) / |(p_a, p_b)| of the cylinder, p / |p| of the sphere.
+ *        Every quadratic is B's nearest-point-offset form.  The cuboid's witness is (o + dd t) - n r, the ball's its centre - n_world r.
+ *      cuboid / cuboid: a swept SAT over 15 axes in the collider's frame: e_0..e_2, u_j = q.r e_j (j = 0..2), then e_a x u_b normalised, b
+ *        outer and a inner (sat_edge_twoway's order), skipped when its norm <= eps.  Per axis: s0 = axis . q.t, v = axis . d_l, R = sum
+ *        |axis_i| he_c.i + sum |axis . u_j| he_q.j.  v != 0: t1 = (-R - s0) / v, t2 = (R - s0) / v, swapped when 1 / v < 0; the entry is the
+ *        largest t1 (strict >, the first axis wins), the exit the smallest t2.  v == 0: a parallel slab, a miss when |s0| > R.  A miss when
+ *        entry > exit or exit < 0; entry < 0: overlapping at the start.  The normal n is the winning axis oriented from the collider towards
+ *        the query (-axis when 1 / v > 0).  Witnesses at the impact pose t' = q.t + d_l t.  A face axis of the collider: the query's support
+ *        vertex s2 = q.r support(he_q, q.r^-1 (-n)) + t' (cuboid_support_point's sign rule) and its projection onto the face (component k set
+ *        to n_k he_c.k).  A face axis of the query: s1 = support(he_c, n) and s1 - n ((s1 - t') . n + he_q.j).  An edge axis: the closest
+ *        points of the lines s1 + lambda e_a and s2 + mu u_b (den = |u_b|^2 - (e_a . u_b)^2; when den <= eps the collider's point is the
+ *        middle of its edge).  When faces or edges are parallel the contact is a segment or a polygon and such a witness can fall outside the
+ *        other shape's face or edge (|coordinate| > half extent on a tangential axis, or den <= eps).  Then, with C(p) the clamp of p to the
+ *        collider's cuboid and Q(p) the query cuboid's closest point to p (clamped in its frame at the impact pose), the witnesses are
+ *        point1 = C(Q(C(p))) and point2 = Q(point1), p being the collider-side witness (for a face axis of the query: the point of that face
+ *        nearest s1).  Each point then lies on its own shape; they coincide when the edges of the two faces are parallel (axis-aligned
+ *        stacks), and otherwise wherever the clamps land in the overlap.
+ *      all three: the shapes overlapping at the start answer distance 0 with points and normals 0 (the convention of a solid ray's normal);
+ *      a hit needs a finite distance <= max_distance; normal1 = rot_c n, point1 / point2 in world space through rot_c and pos_c (a cuboid
+ *      cast at a ball: through the query's isometry at pos_q + d t), normal2 = -normal1 with a zero component staying +0.
+ *    NOT covered: target_distance != 0, ignore_origin_penetration, compute_contact_on_penetration = true, predicates
+ *    (cast_shape_predicate), casts against AVN_SHAPE_HOST colliders, Rust declarations.
  *
  * Non-finite inputs (NaN or inf components):
  *  - a collider whose snapshot position, rotation or shape AABB is not finite is never a candidate (it keeps its collider index);
  *  - a query whose origin, direction, point or box corner is not finite answers a miss (ray queries, projection) or a count of 0, whatever
  *    the scene;
  *  - a query shape whose kind is neither AVN_SHAPE_CUBOID nor AVN_SHAPE_BALL, whose position, rotation, half extents (a ball: its radius) or
- *    AABB are not finite, or which has a negative half extent, answers a count of 0.  This is decided per query on the device;
+ *    AABB are not finite, or which has a negative half extent, answers a count of 0 (a shape cast: a miss / count 0; so does a cast whose
+ *    direction is not finite or whose max_distance is NaN).  This is decided per query on the device;
  *  - a hit needs a finite distance.
  *  Answers to finite inputs do not depend on these rules.
  *
  * Accuracy: every answer is the exact test above in the world's scalar type.  tests/spatial_exact_geometry.py states the forward-error
  * bound the answers are held to against exact rational geometry (a few eps times the magnitudes of the ray, the pose, the shape and the
- * distance; for balls, plus the grazing term of the square root).
+ * distance; for balls, plus the grazing term of the square root); tests/spatial_cast_exact_geometry.py does the same for shape casts.
  *
  * Snapshot rules:
  *  - a query before any avn_spatial_update, or after avn_bodies_upload / avn_colliders_upload / avn_collider_transforms_upload /
@@ -82,7 +121,9 @@
  * Ties: closest hit = smallest (distance, collider index); ray_hits = the max_hits nearest by (distance, collider index), sorted, plus
  * the true number of hits (Avian returns an arbitrary subset when truncated: nearest-k is a deterministic strengthening); point and AABB
  * intersections = ascending collider index, the first `cap`, plus the true count; shape intersections the same; a projection = the
- * smallest (distance, collider index).  A collider index is its slot in the last avn_colliders_upload.
+ * smallest (distance, collider index); cast_shapes = the smallest (distance, collider index); shape_hits = the max_hits nearest by (distance,
+ * collider index), sorted, plus the true number of hits (Avian's shape_hits repeats cast_shape, excluding each hit entity in turn: the same
+ * list in exact arithmetic, here with a deterministic tie rule).  A collider index is its slot in the last avn_colliders_upload.
  */
 #ifndef AVIAN_MI355X_SPATIAL_H
 #define AVIAN_MI355X_SPATIAL_H
@@ -99,7 +140,7 @@ enum {
                                           the caller's writes to them must be complete before the call */
     AVN_SPATIAL_SKIP_HOST_SHAPES = 2   /* AVN_SHAPE_HOST colliders are never candidates (else their presence is AVN_ERR_STATE) */
 };
-#define AVN_SPATIAL_MAX_HITS 64        /* largest max_hits of avn_spatial_ray_hits */
+#define AVN_SPATIAL_MAX_HITS 64        /* largest max_hits of avn_spatial_ray_hits / avn_spatial_shape_hits */
 #define AVN_SPATIAL_MISS 0xFFFFFFFFu   /* collider index of a miss */
 
 typedef struct avn_spatial_filter {
@@ -141,7 +182,7 @@ typedef struct avn_spatial_solid_points {
     avn_spatial_filter filter;
 } avn_spatial_solid_points;
 
-/* the query shapes of avn_spatial_shape_intersections (a later shape cast takes the same record) */
+/* the query shapes of avn_spatial_shape_intersections (avn_spatial_shape_casts carries the same fields) */
 typedef struct avn_spatial_shapes {
     uint32_t count;
     uint32_t flags;
@@ -183,6 +224,46 @@ typedef struct avn_spatial_projection_f64 {
     double distance;
 } avn_spatial_projection_f64;
 
+/* the casts of avn_spatial_cast_shapes / avn_spatial_shape_hits: the fields of avn_spatial_shapes plus a direction and a range per cast */
+typedef struct avn_spatial_shape_casts {
+    uint32_t count;
+    uint32_t flags;
+    const uint8_t* shape;        /* [n] AVN_SHAPE_CUBOID / AVN_SHAPE_BALL */
+    const void* half_extents;    /* [3n] (ball: radius in x) */
+    const void* position;        /* [3n] the shape's position at distance 0 */
+    const void* rotation;        /* [4n] xyzw, unit (the caller normalises) */
+    const void* direction;       /* [3n] unit (the caller normalises, as Dir3 does): distances are in units of |direction|, and the tree's
+                                    padding is only guaranteed for |direction| = 1 */
+    const void* max_distance;    /* [n] (+inf is legal) */
+    avn_spatial_filter filter;
+} avn_spatial_shape_casts;
+
+/* ShapeHitData (shape_caster.rs) with the collider's table index.  Index 1 is the collider that was hit, index 2 the cast shape at the impact
+ * pose; everything in world space.  60 / 112 bytes, no implicit padding: every byte of a record is written. */
+typedef struct avn_spatial_shape_hit_f32 {
+    uint32_t collider;   /* AVN_SPATIAL_MISS = no hit (entity too; the rest 0) */
+    uint32_t entity;
+    float distance;      /* the distance travelled along `direction` at the impact */
+    float point1[3];     /* the witness on the collider */
+    float point2[3];     /* the witness on the cast shape */
+    float normal1[3];    /* the collider's outward normal at point1 */
+    float normal2[3];    /* -normal1 (a zero component stays +0) */
+} avn_spatial_shape_hit_f32;
+typedef struct avn_spatial_shape_hit_f64 {
+    uint32_t collider;
+    uint32_t entity;
+    double distance;
+    double point1[3];
+    double point2[3];
+    double normal1[3];
+    double normal2[3];
+} avn_spatial_shape_hit_f64;
+
+typedef struct avn_spatial_shape_hits_out {
+    void* hits;          /* avn_spatial_shape_hit_fNN [n] (cast_shapes) or [n * max_hits] (shape_hits; unused slots are misses) */
+    uint32_t* count;     /* [n] true number of hits (shape_hits); ignored by cast_shapes */
+} avn_spatial_shape_hits_out;
+
 typedef struct avn_spatial_projections_out {
     void* projection;    /* avn_spatial_projection_fNN [n] */
 } avn_spatial_projections_out;
@@ -222,6 +303,11 @@ AVN_API avn_status avn_spatial_aabb_intersections(avn_world* w, const avn_spatia
 AVN_API avn_status avn_spatial_project_points(avn_world* w, const avn_spatial_solid_points* points, const avn_spatial_projections_out* out);
 /* SpatialQueryPipeline::shape_intersections (pipeline.rs:744-826): per query shape the colliders intersecting it.  cap = 0 is legal (counts only) */
 AVN_API avn_status avn_spatial_shape_intersections(avn_world* w, const avn_spatial_shapes* shapes, uint32_t cap, const avn_spatial_ids_out* out);
+/* SpatialQueryPipeline::cast_shape (pipeline.rs:335-374); ShapeCaster with max_hits = 1: per cast the closest hit within max_distance, or a miss */
+AVN_API avn_status avn_spatial_cast_shapes(avn_world* w, const avn_spatial_shape_casts* casts, const avn_spatial_shape_hits_out* out);
+/* SpatialQueryPipeline::shape_hits (pipeline.rs:443-487); ShapeCaster / ShapeHits: per cast the max_hits nearest hits, sorted, plus the true count.
+ * 1 <= max_hits <= AVN_SPATIAL_MAX_HITS, else AVN_ERR_BAD_ARG. */
+AVN_API avn_status avn_spatial_shape_hits(avn_world* w, const avn_spatial_shape_casts* casts, uint32_t max_hits, const avn_spatial_shape_hits_out* out);
 /* snapshot sizes and the traversal counters of the last query call */
 AVN_API avn_status avn_spatial_stats_get(avn_world* w, avn_spatial_stats* out);
 

@@ -6,6 +6,8 @@
   ray_hits k = 16, 64 k rays;  point and AABB intersections, 10^6 queries each
   project_points, 10^6 points into cfg2 (the points of point_intersections);  shape_intersections, 10^6 query shapes, half balls and half
   cuboids with sizes like the AABB query's boxes, cap 16 -- reported beside the point and AABB figures of the same run
+  cast_shapes, 10^6 casts into cfg2 from the rays' origins along the rays' directions, short (<= 2 m) and long (200 m), half balls and half
+  cuboids of half extent <= 0.25 m;  shape_hits k = 16, 64 k long casts -- reported beside cast_rays / ray_hits of the same run
 
 Every figure is the median over `reps` warmed-up calls.  The queries take torch tensors on the GPU (AVN_SPATIAL_DEVICE_POINTERS: no
 staging copies), so a call is its launches plus one stream synchronisation; the update is timed with avn_synchronize behind it.  Device
@@ -125,6 +127,20 @@ def main():
     res["shapes_per_s"] = n / (ms * 1e-3)
     res["shapes_leaves_per_query"], res["shapes_nodes_per_query"] = st.leaves_visited / n, st.nodes_visited / n
     res["shapes_bytes_floor"] = n * (1 + 12 + 12 + 16 + 16 * 4 + 4)
+    small = ext * 0.25
+    crec = 60
+    for name, md in (("short", short), ("long", long)):
+        ms = timed(lambda: sq.cast_shapes(kind, small, o, rot, d, md), reps)
+        st = sq.stats()
+        res[f"cast_shapes_{name}_ms"] = ms
+        res[f"cast_shapes_{name}_casts_per_s"] = n / (ms * 1e-3)
+        res[f"cast_shapes_{name}_leaves_per_cast"], res[f"cast_shapes_{name}_nodes_per_cast"] = st.leaves_visited / n, st.nodes_visited / n
+        res[f"cast_shapes_{name}_bytes_floor"] = n * (1 + 12 + 12 + 16 + 12 + 4 + crec)
+    ms = timed(lambda: sq.shape_hits(kind[:nk], small[:nk], o[:nk], rot[:nk], d[:nk], 16, long[:nk]), reps)
+    res["shape_hits_k16_64k_ms"] = ms
+    res["shape_hits_k16_64k_casts_per_s"] = nk / (ms * 1e-3)
+    res["shape_hits_k16_leaves_per_cast"] = sq.stats().leaves_visited / nk
+    res["shape_hits_k16_bytes_floor"] = nk * (1 + 12 + 12 + 16 + 12 + 4 + 16 * crec + 4)
     res["update_bytes_floor_per_collider"] = 4 * 16 + 16 + 8 + 4 * 16 + 2 * 16 + 2 * 2 * 16 + 8 + 12
     for k in [k for k in res if k.endswith("_bytes_floor")]:
         msk = k.replace("_bytes_floor", "_ms") if k.replace("_bytes_floor", "_ms") in res else None
