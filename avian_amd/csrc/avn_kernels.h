@@ -409,7 +409,8 @@ template <class T> struct SP {
     Vec4<T>* pos;            // [n] snapshot pose of collider i: (position.xyz, 0)
     Vec4<T>* rot;            // [n] rotation xyzw
     Vec4<T>* he;             // [n] (half_extents.xyz | radius, 0)
-    uint4* info;             // [n] (entity, memberships, shape, 1 = candidate | 0 = AVN_SHAPE_HOST or a non-finite pose / shape AABB)
+    uint4* info;             // [n] (entity, memberships, shape, 0 = AVN_SHAPE_HOST or a non-finite pose / shape AABB | candidate: 1, plus SP_INFO_SENSOR for an
+                             //      AVN_COLLIDER_SENSOR collider -- set on candidates only, so `!info.w` still means "not a candidate")
     Vec4<T>* smin;           // [n] padded shape AABB of collider i (empty = +inf / -inf: host shapes, non-finite poses)
     Vec4<T>* smax;
     Vec4<T>* bmin;           // [2n-1] node boxes (a leaf: its collider's smin / smax)
@@ -450,7 +451,39 @@ template <class T> struct SQ {
     // SPQ_CAST / SPQ_CAST_HITS (the SPQ_SHAPES fields, b = directions, max_distance; cap = max_hits): k_sp_cast
     SpatialShapeHit<T>* cast;        // SPQ_CAST: [n]; SPQ_CAST_HITS: [n * cap]
 };
+#define SP_INFO_SENSOR 2u
+// == avn_spatial_shape_contact_fNN (60 / 120 bytes, no implicit padding: the f64 record ends in two reserved words, always 0)
+template <class T> struct SpatialShapeContact { uint32_t collider, entity; T penetration; T normal[3], point[3], anchor1[3], anchor2[3]; };
+template <> struct SpatialShapeContact<double> { uint32_t collider, entity; double penetration; double normal[3], point[3], anchor1[3], anchor2[3]; uint32_t reserved[2]; };
+__device__ __forceinline__ void sp_clear_reserved(SpatialShapeContact<float>&) {}
+__device__ __forceinline__ void sp_clear_reserved(SpatialShapeContact<double>& r) { r.reserved[0] = r.reserved[1] = 0u; }
+// == avn_spatial_depenetration_fNN (24 / 40 bytes)
+template <class T> struct SpatialDepenetration { T fixup[3]; uint32_t count, iterations_run, truncated; };
+template <> struct SpatialDepenetration<double> { double fixup[3]; uint32_t count, iterations_run, truncated, reserved; };
+__device__ __forceinline__ void sp_clear_reserved(SpatialDepenetration<float>&) {}
+__device__ __forceinline__ void sp_clear_reserved(SpatialDepenetration<double>& r) { r.reserved = 0u; }
+// k_sp_contacts (a struct of its own: SQ<T> and the kernels that take it stay as they are).  q: the SPQ_SHAPES fields (a = positions, shape, he, rot,
+// mask, excluded, count, stats; cap = records per query)
+template <class T> struct SC {
+    SQ<T> q;
+    const T* prediction;             // [n], or nullptr: prediction_all for every query (depenetrate's skin_width)
+    T prediction_all;
+    uint32_t skip_sensors;           // AVN_SPATIAL_SKIP_SENSORS
+    uint32_t pad_unused;             // 1: slots past the count are written as misses (the caller's output); 0: left alone (depenetrate's own buffer)
+    SpatialShapeContact<T>* rec;     // [n * cap]
+};
+// k_sp_depenetrate over the records of a k_sp_contacts launch with cap = AVN_SPATIAL_MAX_HITS
+template <class T> struct SD {
+    uint32_t n;
+    const SpatialShapeContact<T>* rec;   // [n * AVN_SPATIAL_MAX_HITS]
+    const uint32_t* count;               // [n] true counts
+    T skin_width, max_error, rejection;
+    uint32_t iterations;
+    SpatialDepenetration<T>* out;        // [n]
+};
 template <class T> void launch_spatial_build(const DW<T>&, const BP<T>&, const SP<T>&, hipStream_t);
 template <class T> void launch_spatial_query(const SP<T>&, const SQ<T>&, int kind, hipStream_t);
+template <class T> void launch_spatial_contacts(const SP<T>&, const SC<T>&, hipStream_t);
+template <class T> void launch_spatial_depenetrate(const SD<T>&, hipStream_t);
 
 }  // namespace avn

@@ -29,6 +29,8 @@ AVN_API avn_status avn_spatial_shape_hits(avn_world* w, const avn_spatial_shape_
     if (w && w->impl && (max_hits == 0 || max_hits > AVN_SPATIAL_MAX_HITS)) { w->impl->error = "spatial_shape_hits: max_hits must be 1 .. AVN_SPATIAL_MAX_HITS"; return AVN_ERR_BAD_ARG; }
     SP_GUARD(spatial_cast_shapes(c, max_hits, o));
 }
+AVN_API avn_status avn_spatial_shape_contacts(avn_world* w, const avn_spatial_shape_contact_queries* q, uint32_t cap, const avn_spatial_shape_contacts_out* o) { SP_GUARD(spatial_shape_contacts(q, cap, o)); }
+AVN_API avn_status avn_spatial_depenetrate(avn_world* w, const avn_spatial_shapes* s, const avn_spatial_depenetration_config* c, const avn_spatial_depenetrations_out* o) { SP_GUARD(spatial_depenetrate(s, c, o)); }
 AVN_API avn_status avn_spatial_stats_get(avn_world* w, avn_spatial_stats* o) { SP_GUARD(spatial_stats_get(o)); }
 
 }  // extern "C"

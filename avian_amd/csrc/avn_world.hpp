@@ -133,6 +133,8 @@ struct WorldBase {
     virtual avn_status spatial_project_points(const avn_spatial_solid_points*, const avn_spatial_projections_out*) = 0;
     virtual avn_status spatial_shape_intersections(const avn_spatial_shapes*, uint32_t, const avn_spatial_ids_out*) = 0;
     virtual avn_status spatial_cast_shapes(const avn_spatial_shape_casts*, uint32_t max_hits, const avn_spatial_shape_hits_out*) = 0;   // max_hits 0: the closest hit
+    virtual avn_status spatial_shape_contacts(const avn_spatial_shape_contact_queries*, uint32_t cap, const avn_spatial_shape_contacts_out*) = 0;
+    virtual avn_status spatial_depenetrate(const avn_spatial_shapes*, const avn_spatial_depenetration_config*, const avn_spatial_depenetrations_out*) = 0;
     virtual avn_status spatial_stats_get(avn_spatial_stats*) = 0;
 };
 

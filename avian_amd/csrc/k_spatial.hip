@@ -1,6 +1,6 @@
 // k_spatial.hip — spatial queries on the device (include/avian_mi355x_spatial.h): an LBVH over the collider table and one-lane-per-query
 // traversals for ray casts, ray hits, point and AABB intersections (k_sp_query), point projection (k_sp_project), shape intersections
-// (k_sp_shapes) and shape casts (k_sp_cast).
+// (k_sp_shapes), shape casts (k_sp_cast), shape contacts (k_sp_contacts) and the depenetration over them (k_sp_depenetrate).
 //
 // avn_spatial_update (launch_spatial_build), all on the world's stream:
 //   1. k_sp_snapshot   one thread per collider: its pose (collider_pose), the exact shape AABB (shape_aabb), padded, as the leaf box;
@@ -81,7 +81,8 @@ __global__ __launch_bounds__(256) void k_sp_snapshot(DW<T> w, BP<T> bp, SP<T> sp
             atomicMax(&sp.bounds[3], sp_fkey((float)m.x)); atomicMax(&sp.bounds[4], sp_fkey((float)m.y)); atomicMax(&sp.bounds[5], sp_fkey((float)m.z));
         }
     }
-    sp.info[c] = make_uint4(ci.x, bp.col_layers[c].x, shape, candidate ? 1u : 0u);
+    // (the sensor bit rides on candidates only: every reader's `!info.w` keeps its meaning)
+    sp.info[c] = make_uint4(ci.x, bp.col_layers[c].x, shape, candidate ? (1u | ((((ci.z >> 8) & AVN_COLLIDER_SENSOR) != 0u) ? SP_INFO_SENSOR : 0u)) : 0u);
     sp.smin[c] = make4<T>(mn, T(0));
     sp.smax[c] = make4<T>(mx, T(0));
 }
@@ -1104,6 +1105,188 @@ __global__ __launch_bounds__(SP_WAVE) void k_sp_cast(SP<T> sp, SQ<T> q) {
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// shape contacts and depenetration (kernels of their own: the kernels above compile as before).  The header defines a contact; the pair
+// arithmetic is the narrow phase's contact_manifolds_pair_sink, untouched.  DESIGN.md 4.4.7.
+
+// the sink of contact_manifolds_pair_sink that keeps the running deepest raw point (ContactManifold::find_deepest_contact: Rust's max_by, the
+// later point wins a tie) instead of the 16-point manifold
+template <class T> struct SpDeepestSink {
+    V3<T> anchor1;
+    T penetration;
+    int count;
+    __device__ __forceinline__ int n() const { return count; }
+    __device__ __forceinline__ void put(V3<T> a1, T pen, uint32_t, uint32_t) {
+        if (count == 0 || !(penetration > pen)) { anchor1 = a1; penetration = pen; }
+        ++count;
+    }
+};
+
+// one lane per query shape; blocks of one wave; records inserted in ascending collider index as k_sp_shapes inserts ids
+template <class T>
+__global__ __launch_bounds__(SP_WAVE) void k_sp_contacts(SP<T> sp, SC<T> sc) {
+    __shared__ uint32_t stack[SP_STACK * SP_WAVE];
+    const SQ<T>& q = sc.q;
+    const uint32_t lane = threadIdx.x;
+    const uint32_t qi = blockIdx.x * SP_WAVE + lane;
+    uint32_t nodes_tested = 0, leaves_tested = 0, overflow = 0;
+    const uint32_t n = sp.n;
+    if (qi < q.n) {
+        const uint32_t mask = q.mask ? q.mask[qi] : 0xFFFFFFFFu;
+        const uint32_t shape1 = q.shape[qi];
+        const V3<T> pos1{q.a[3 * (size_t)qi], q.a[3 * (size_t)qi + 1], q.a[3 * (size_t)qi + 2]};
+        V3<T> he1{q.he[3 * (size_t)qi], q.he[3 * (size_t)qi + 1], q.he[3 * (size_t)qi + 2]};
+        const Q4<T> rot1{q.rot[4 * (size_t)qi], q.rot[4 * (size_t)qi + 1], q.rot[4 * (size_t)qi + 2], q.rot[4 * (size_t)qi + 3]};
+        const T pred = sc.prediction ? sc.prediction[qi] : sc.prediction_all;
+        if (shape1 == AVN_SHAPE_BALL) he1 = V3<T>{he1.x, he1.x, he1.x};   // (a ball has its radius in x: y and z are not read)
+        // k_sp_shapes' rule, plus a prediction distance that is finite and not negative: otherwise count 0
+        bool valid = shape1 <= AVN_SHAPE_BALL && is_finite(pos1) && is_finite(V3<T>{rot1.x, rot1.y, rot1.z}) && finite_t(rot1.w) && is_finite(he1) &&
+                     he1.x >= T(0) && he1.y >= T(0) && he1.z >= T(0) && finite_t(pred) && pred >= T(0);
+        V3<T> gmin = vzero<T>(), gmax = vzero<T>(), qmin = vzero<T>(), qmax = vzero<T>();
+        if (valid) {
+            // (b)'s box: the query shape's exact AABB grown by the prediction; the node test pads it as a leaf box is padded
+            V3<T> a, b;
+            shape_aabb<T>(shape1, he1, pos1, rot1, a, b);
+            valid = is_finite(a) && is_finite(b);
+            const V3<T> pv{pred, pred, pred};
+            gmin = a - pv; gmax = b + pv;
+            const T pad = T(64) * Limits<T>::eps * smax(sp_maxabs(gmin), sp_maxabs(gmax));
+            const V3<T> pp{pad, pad, pad};
+            qmin = gmin - pp; qmax = gmax + pp;
+        }
+        uint32_t found = 0;
+        SpatialShapeContact<T>* rl = sc.rec + (size_t)qi * q.cap;
+        auto test = [&](uint32_t node) -> bool {
+            ++nodes_tested;
+            return sp_box_box(qmin, qmax, sp.bmin[node], sp.bmax[node]);
+        };
+        auto leaf = [&](uint32_t node) {
+            const uint32_t c = sp.leaf_col[node - (n - 1)];
+            const uint4 info = sp.info[c];
+            if (!info.w || (info.y & mask) == 0u || (sc.skip_sensors && (info.w & SP_INFO_SENSOR)) || (q.n_excluded && sp_excluded(q.excluded, q.n_excluded, info.x))) return;
+            ++leaves_tested;
+            const V3<T> pos2 = xyz<T>(sp.pos[c]), he2 = xyz<T>(sp.he[c]);
+            const Q4<T> rot2 = quat<T>(sp.rot[c]);
+            // (b) the collider's exact box, by the snapshot's own arithmetic
+            V3<T> mn, mx;
+            shape_aabb<T>(info.z, he2, pos2, rot2, mn, mx);
+            if (!sp_box_box(gmin, gmax, make4<T>(mn, T(0)), make4<T>(mx, T(0)))) return;
+            // (c), (d)
+            SpDeepestSink<T> sink{vzero<T>(), T(0), 0};
+            V3<T> nrm;
+            if (!contact_manifolds_pair_sink<T, SpDeepestSink<T>>(shape1, he1, pos1, rot1, info.z, he2, pos2, rot2, pred, sink, nrm)) return;
+            const uint32_t k = q.cap;
+            uint32_t m = found < k ? found : k;
+            ++found;
+            if (m == k) {
+                if (k == 0 || c >= rl[k - 1].collider) return;
+                m = k - 1;
+            }
+            while (m > 0 && rl[m - 1].collider > c) { rl[m] = rl[m - 1]; --m; }
+            const V3<T> a1 = sink.anchor1, a2 = a1 + (pos1 - pos2), pt = pos1 + a1;
+            SpatialShapeContact<T> r;
+            r.collider = c; r.entity = info.x; r.penetration = sink.penetration;
+            r.normal[0] = -nrm.x; r.normal[1] = -nrm.y; r.normal[2] = -nrm.z;
+            r.point[0] = pt.x; r.point[1] = pt.y; r.point[2] = pt.z;
+            r.anchor1[0] = a1.x; r.anchor1[1] = a1.y; r.anchor1[2] = a1.z;
+            r.anchor2[0] = a2.x; r.anchor2[1] = a2.y; r.anchor2[2] = a2.z;
+            sp_clear_reserved(r);
+            rl[m] = r;
+        };
+        if (valid && n >= 1 && test(0)) {
+            uint32_t sp_top = 0, node = 0;
+            for (;;) {
+                // (a tree of one collider: its root is the leaf, handled by the same leaf call site)
+                uint2 ch = make_uint2(0u, 0u);
+                bool g0 = true, g1 = false;
+                if (n > 1) { ch = sp.child[node]; g0 = test(ch.x); g1 = test(ch.y); }
+                const bool l0 = ch.x >= n - 1, l1 = ch.y >= n - 1;
+                // one leaf call site: the manifold test is emitted once
+                uint32_t pending = (l0 && g0 ? 1u : 0u) | (l1 && g1 ? 2u : 0u);
+                while (pending) {
+                    const bool first = (pending & 1u) != 0;
+                    leaf(first ? ch.x : ch.y);
+                    pending &= first ? ~1u : ~2u;
+                }
+                if (l0) g0 = false;
+                if (l1) g1 = false;
+                if (g0 && g1) {
+                    if (sp_top < SP_STACK) { stack[sp_top * SP_WAVE + lane] = ch.y; ++sp_top; }
+                    else overflow = 1;   // (cannot happen: the depth of the tree is at most 64)
+                    node = ch.x;
+                    continue;
+                }
+                if (g0) { node = ch.x; continue; }
+                if (g1) { node = ch.y; continue; }
+                if (sp_top == 0) break;
+                --sp_top;
+                node = stack[sp_top * SP_WAVE + lane];
+            }
+        }
+        if (sc.pad_unused && found < q.cap) {
+            SpatialShapeContact<T> miss;
+            miss.collider = AVN_SPATIAL_MISS; miss.entity = AVN_SPATIAL_MISS; miss.penetration = T(0);
+            for (int i = 0; i < 3; ++i) miss.normal[i] = miss.point[i] = miss.anchor1[i] = miss.anchor2[i] = T(0);
+            sp_clear_reserved(miss);
+            for (uint32_t m = found; m < q.cap; ++m) rl[m] = miss;
+        }
+        q.count[qi] = found;
+    }
+    uint32_t a = nodes_tested, b = leaves_tested, o = overflow;
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) { a += __shfl_xor(a, off); b += __shfl_xor(b, off); o |= __shfl_xor(o, off); }
+    if (lane == 0) {
+        atomicAdd(&q.stats[0], (unsigned long long)a);
+        atomicAdd(&q.stats[1], (unsigned long long)b);
+        if (o) atomicOr(&q.stats[2], 1ull);
+    }
+}
+
+// Dir is f32: an f64 world rounds every normal component through float (Dir::new_unchecked(-manifold.normal.f32()), adjust_precision())
+__device__ __forceinline__ float sp_dir_round(float x) { return x; }
+__device__ __forceinline__ double sp_dir_round(double x) { return (double)(float)x; }
+
+// MoveAndSlide::depenetrate_intersections (move_and_slide.rs:982-1009), one lane per query over its contact records
+template <class T>
+__global__ __launch_bounds__(SP_WAVE) void k_sp_depenetrate(SD<T> d) {
+    const uint32_t qi = blockIdx.x * SP_WAVE + threadIdx.x;
+    if (qi >= d.n) return;
+    const uint32_t count = d.count[qi];
+    const uint32_t m = count < AVN_SPATIAL_MAX_HITS ? count : AVN_SPATIAL_MAX_HITS;
+    const SpatialShapeContact<T>* rl = d.rec + (size_t)qi * AVN_SPATIAL_MAX_HITS;
+    V3<T> fixup = vzero<T>();
+    uint32_t it = 0;
+    while (it < d.iterations) {
+        ++it;
+        T total_error = T(0);
+        for (uint32_t k = 0; k < m; ++k) {
+            const T dist = rl[k].penetration + d.skin_width;
+            if (dist > d.rejection) continue;
+            const V3<T> nv{sp_dir_round(rl[k].normal[0]), sp_dir_round(rl[k].normal[1]), sp_dir_round(rl[k].normal[2])};
+            const T diff = dist - (fixup.x * nv.x + fixup.y * nv.y + fixup.z * nv.z);
+            const T error = diff > T(0) ? diff : T(0);
+            total_error += error;
+            fixup = V3<T>{fixup.x + error * nv.x, fixup.y + error * nv.y, fixup.z + error * nv.z};
+        }
+        if (total_error < d.max_error) break;
+    }
+    SpatialDepenetration<T> r;
+    r.fixup[0] = fixup.x; r.fixup[1] = fixup.y; r.fixup[2] = fixup.z;
+    r.count = count; r.iterations_run = it; r.truncated = count > AVN_SPATIAL_MAX_HITS ? 1u : 0u;
+    sp_clear_reserved(r);
+    d.out[qi] = r;
+}
+
+template <class T> void launch_spatial_contacts(const SP<T>& sp, const SC<T>& sc, hipStream_t s) {
+    (void)hipMemsetAsync(sc.q.stats, 0, 4 * sizeof(unsigned long long), s);
+    if (sc.q.n == 0) return;
+    hipLaunchKernelGGL((k_sp_contacts<T>), dim3((sc.q.n + SP_WAVE - 1) / SP_WAVE), dim3(SP_WAVE), 0, s, sp, sc);
+}
+template <class T> void launch_spatial_depenetrate(const SD<T>& d, hipStream_t s) {
+    if (d.n == 0) return;
+    hipLaunchKernelGGL((k_sp_depenetrate<T>), dim3((d.n + SP_WAVE - 1) / SP_WAVE), dim3(SP_WAVE), 0, s, d);
+}
+
 template <class T> void launch_spatial_query(const SP<T>& sp, const SQ<T>& q, int kind, hipStream_t s) {
     (void)hipMemsetAsync(q.stats, 0, 4 * sizeof(unsigned long long), s);
     if (q.n == 0) return;
@@ -1130,9 +1313,24 @@ static_assert(sizeof(SpatialShapeHit<float>) == sizeof(avn_spatial_shape_hit_f32
               offsetof(SpatialShapeHit<float>, point2) == offsetof(avn_spatial_shape_hit_f32, point2) && offsetof(SpatialShapeHit<double>, point2) == offsetof(avn_spatial_shape_hit_f64, point2) &&
               offsetof(SpatialShapeHit<float>, normal2) == offsetof(avn_spatial_shape_hit_f32, normal2) && offsetof(SpatialShapeHit<double>, normal2) == offsetof(avn_spatial_shape_hit_f64, normal2),
               "shape hit record layout");
+static_assert(sizeof(SpatialShapeContact<float>) == sizeof(avn_spatial_shape_contact_f32) && sizeof(SpatialShapeContact<double>) == sizeof(avn_spatial_shape_contact_f64) &&
+              sizeof(avn_spatial_shape_contact_f32) == 60 && sizeof(avn_spatial_shape_contact_f64) == 120 &&
+              offsetof(SpatialShapeContact<float>, penetration) == offsetof(avn_spatial_shape_contact_f32, penetration) && offsetof(SpatialShapeContact<double>, penetration) == offsetof(avn_spatial_shape_contact_f64, penetration) &&
+              offsetof(SpatialShapeContact<float>, point) == offsetof(avn_spatial_shape_contact_f32, point) && offsetof(SpatialShapeContact<double>, point) == offsetof(avn_spatial_shape_contact_f64, point) &&
+              offsetof(SpatialShapeContact<float>, anchor2) == offsetof(avn_spatial_shape_contact_f32, anchor2) && offsetof(SpatialShapeContact<double>, anchor2) == offsetof(avn_spatial_shape_contact_f64, anchor2) &&
+              offsetof(SpatialShapeContact<double>, reserved) == offsetof(avn_spatial_shape_contact_f64, reserved),
+              "shape contact record layout");
+static_assert(sizeof(SpatialDepenetration<float>) == sizeof(avn_spatial_depenetration_f32) && sizeof(SpatialDepenetration<double>) == sizeof(avn_spatial_depenetration_f64) &&
+              sizeof(avn_spatial_depenetration_f32) == 24 && sizeof(avn_spatial_depenetration_f64) == 40 &&
+              offsetof(SpatialDepenetration<float>, truncated) == offsetof(avn_spatial_depenetration_f32, truncated) && offsetof(SpatialDepenetration<double>, truncated) == offsetof(avn_spatial_depenetration_f64, truncated),
+              "depenetration record layout");
 template void launch_spatial_build<float>(const DW<float>&, const BP<float>&, const SP<float>&, hipStream_t);
 template void launch_spatial_build<double>(const DW<double>&, const BP<double>&, const SP<double>&, hipStream_t);
 template void launch_spatial_query<float>(const SP<float>&, const SQ<float>&, int, hipStream_t);
 template void launch_spatial_query<double>(const SP<double>&, const SQ<double>&, int, hipStream_t);
+template void launch_spatial_contacts<float>(const SP<float>&, const SC<float>&, hipStream_t);
+template void launch_spatial_contacts<double>(const SP<double>&, const SC<double>&, hipStream_t);
+template void launch_spatial_depenetrate<float>(const SD<float>&, hipStream_t);
+template void launch_spatial_depenetrate<double>(const SD<double>&, hipStream_t);
 
 }  // namespace avn

@@ -4,7 +4,8 @@
 
     SP<T> sp{};
     DevBuf b_sp_pos, b_sp_rot, b_sp_he, b_sp_info, b_sp_smin, b_sp_smax, b_sp_bmin, b_sp_bmax, b_sp_child, b_sp_parent, b_sp_leaf, b_sp_arr, b_sp_bounds,
-        b_sp_keys_a, b_sp_vals_a, b_sp_keys_b, b_sp_vals_b, b_sp_hist, b_sp_block_sums, b_sp_stats;
+        b_sp_keys_a, b_sp_vals_a, b_sp_keys_b, b_sp_vals_b, b_sp_hist, b_sp_block_sums, b_sp_stats,
+        b_sp_crec, b_sp_ccount;   // depenetrate's contact records [n * AVN_SPATIAL_MAX_HITS] and counts [n]
     uint32_t sp_cap = 0;
     bool sp_valid = false;      // a snapshot exists and no table changed since (bodies / colliders / collider transforms uploads and avn_despawn clear it)
     uint32_t sp_host = 0;       // AVN_SHAPE_HOST colliders in the snapshot
@@ -237,6 +238,95 @@
             if ((st = stage_out<SpatialShapeHit<T>>(out->hits, q.cast, n_rec)) != AVN_OK) return st;
             if (many && (st = stage_out<uint32_t>(out->count, q.count, n)) != AVN_OK) return st;
         }
+        return sp_finish();
+    }
+    // the query-shape fields shared by shape_contacts and depenetrate, staged into sc.q (the SPQ_SHAPES fields); stage_reserve is the caller's
+    avn_status sp_contact_inputs(SC<T>& sc, uint32_t n, bool dev, const uint8_t* shape, const void* he, const void* pos, const void* rot, const avn_spatial_filter& f,
+                                 const std::vector<uint32_t>& ex) {
+        avn_status st;
+        SQ<T>& q = sc.q;
+        q.n = n;
+        if ((st = sp_in<uint8_t>(shape, n, dev, &q.shape)) != AVN_OK) return st;
+        if ((st = sp_in<T>(he, 3 * (size_t)n, dev, &q.he)) != AVN_OK) return st;
+        if ((st = sp_in<T>(pos, 3 * (size_t)n, dev, &q.a)) != AVN_OK) return st;
+        if ((st = sp_in<T>(rot, 4 * (size_t)n, dev, &q.rot)) != AVN_OK) return st;
+        if ((st = sp_in<uint32_t>(f.mask, n, dev, &q.mask)) != AVN_OK) return st;
+        if ((st = stage_in<uint32_t>(ex.data(), ex.size(), &q.excluded)) != AVN_OK) return st;
+        q.n_excluded = (uint32_t)ex.size();
+        q.stats = b_sp_stats.as<unsigned long long>();
+        return AVN_OK;
+    }
+    // MoveAndSlide::intersections: the deepest contact per collider within the prediction distance, ascending collider index
+    avn_status spatial_shape_contacts(const avn_spatial_shape_contact_queries* s, uint32_t cap, const avn_spatial_shape_contacts_out* out) override {
+        if (!s || !out) { error = "spatial_shape_contacts: null argument"; return AVN_ERR_BAD_ARG; }
+        const uint32_t n = s->count;
+        if (n && (!s->shape || !s->half_extents || !s->position || !s->rotation || !s->prediction_distance || !out->count || (cap && !out->contacts))) {
+            error = "spatial_shape_contacts: null array"; return AVN_ERR_BAD_ARG;
+        }
+        if (cap > AVN_SPATIAL_MAX_HITS) { error = "spatial_shape_contacts: cap above AVN_SPATIAL_MAX_HITS"; return AVN_ERR_BAD_ARG; }
+        avn_status st = sp_check(s->flags);
+        if (st != AVN_OK) return st;
+        const bool dev = (s->flags & AVN_SPATIAL_DEVICE_POINTERS) != 0;
+        std::vector<uint32_t> ex;
+        if ((st = sp_excluded(s->filter, dev, ex)) != AVN_OK) return st;
+        const size_t n_rec = (size_t)n * cap;
+        if ((st = stage_reserve(sp_stage_bytes(dev, n, 2 * al(3 * sizeof(T) * n) + al(4 * sizeof(T) * n) + al(sizeof(T) * n) + al(n), al(n_rec * sizeof(SpatialShapeContact<T>)), ex.size()))) != AVN_OK) return st;
+        SC<T> sc{};
+        if ((st = sp_contact_inputs(sc, n, dev, s->shape, s->half_extents, s->position, s->rotation, s->filter, ex)) != AVN_OK) return st;
+        if ((st = sp_in<T>(s->prediction_distance, n, dev, &sc.prediction)) != AVN_OK) return st;
+        sc.q.cap = cap;
+        sc.skip_sensors = (s->flags & AVN_SPATIAL_SKIP_SENSORS) ? 1u : 0u;
+        sc.pad_unused = 1u;
+        sc.rec = n_rec ? sp_out<SpatialShapeContact<T>>(out->contacts, n_rec, dev) : nullptr;
+        sc.q.count = sp_out<uint32_t>(out->count, n, dev);
+        launch_spatial_contacts<T>(sp, sc, stream);
+        HIPCHK(hipGetLastError());
+        if (!dev) {
+            if ((st = stage_out<SpatialShapeContact<T>>(out->contacts, sc.rec, n_rec)) != AVN_OK) return st;
+            if ((st = stage_out<uint32_t>(out->count, sc.q.count, n)) != AVN_OK) return st;
+        }
+        return sp_finish();
+    }
+    // MoveAndSlide::depenetrate: the contacts with prediction skin_width into a buffer the world keeps, then k_sp_depenetrate over them
+    avn_status spatial_depenetrate(const avn_spatial_shapes* s, const avn_spatial_depenetration_config* cfg, const avn_spatial_depenetrations_out* out) override {
+        if (!s || !cfg || !out) { error = "spatial_depenetrate: null argument"; return AVN_ERR_BAD_ARG; }
+        const uint32_t n = s->count;
+        if (n && (!s->shape || !s->half_extents || !s->position || !s->rotation || !out->depenetration)) { error = "spatial_depenetrate: null array"; return AVN_ERR_BAD_ARG; }
+        avn_status st = sp_check(s->flags);
+        if (st != AVN_OK) return st;
+        const bool dev = (s->flags & AVN_SPATIAL_DEVICE_POINTERS) != 0;
+        std::vector<uint32_t> ex;
+        if ((st = sp_excluded(s->filter, dev, ex)) != AVN_OK) return st;
+        if ((st = stage_reserve(sp_stage_bytes(dev, n, 2 * al(3 * sizeof(T) * n) + al(4 * sizeof(T) * n) + al(n), al((size_t)n * sizeof(SpatialDepenetration<T>)), ex.size()))) != AVN_OK) return st;
+        SpatialDepenetration<T>* d_out = sp_out<SpatialDepenetration<T>>(out->depenetration, n, dev);
+        if (cfg->iterations == 0) {
+            // depenetration disabled: zero vectors, no traversal (every byte of a record is 0)
+            if (n) HIPCHK(hipMemsetAsync(d_out, 0, (size_t)n * sizeof(SpatialDepenetration<T>), stream));
+            HIPCHK(hipMemsetAsync(b_sp_stats.p, 0, 4 * sizeof(unsigned long long), stream));
+        } else {
+            bool moved = false;
+            SC<T> sc{};
+            uint32_t* d_count;
+            GROW(b_sp_crec, std::max<size_t>((size_t)n * AVN_SPATIAL_MAX_HITS, 1), sc.rec);
+            GROW(b_sp_ccount, std::max<size_t>(n, 1), d_count);
+            if ((st = sp_contact_inputs(sc, n, dev, s->shape, s->half_extents, s->position, s->rotation, s->filter, ex)) != AVN_OK) return st;
+            sc.q.cap = AVN_SPATIAL_MAX_HITS;
+            sc.q.count = d_count;
+            sc.prediction = nullptr;
+            sc.prediction_all = (T)cfg->skin_width;
+            sc.pad_unused = 0u;   // (k_sp_depenetrate reads the first min(count, cap) records only)
+            sc.skip_sensors = (s->flags & AVN_SPATIAL_SKIP_SENSORS) ? 1u : 0u;
+            launch_spatial_contacts<T>(sp, sc, stream);
+            HIPCHK(hipGetLastError());
+            SD<T> d{};
+            d.n = n; d.rec = sc.rec; d.count = d_count;
+            d.skin_width = (T)cfg->skin_width; d.max_error = (T)cfg->max_depenetration_error; d.rejection = (T)cfg->penetration_rejection_threshold;
+            d.iterations = cfg->iterations;
+            d.out = d_out;
+            launch_spatial_depenetrate<T>(d, stream);
+            HIPCHK(hipGetLastError());
+        }
+        if (!dev && (st = stage_out<SpatialDepenetration<T>>(out->depenetration, d_out, n)) != AVN_OK) return st;
         return sp_finish();
     }
     avn_status spatial_stats_get(avn_spatial_stats* o) override {

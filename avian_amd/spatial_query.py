@@ -1,5 +1,5 @@
 """ctypes binding of ``include/avian_mi355x_spatial.h``: device spatial queries (ray casts, ray hits, point and AABB intersections, point
-projection, shape intersections, shape casts) over the
+projection, shape intersections, shape casts, shape contacts and depenetration) over the
 colliders a :class:`avian_amd._ffi.World` holds on the device.
 
 Numpy arrays in and out (copied through the library's staging), or torch tensors on the world's GPU (``AVN_SPATIAL_DEVICE_POINTERS``: the
@@ -17,6 +17,7 @@ vp = C.c_void_p
 
 DEVICE_POINTERS = 1
 SKIP_HOST_SHAPES = 2
+SKIP_SENSORS = 4      # shape_contacts / depenetrate only
 MAX_HITS = 64
 MISS = 0xFFFFFFFF
 
@@ -62,6 +63,42 @@ class avn_spatial_shape_hit_f64(C.Structure):
                 ("normal1", C.c_double * 3), ("normal2", C.c_double * 3)]
 
 
+class avn_spatial_shape_contact_queries(C.Structure):
+    _fields_ = [("count", C.c_uint32), ("flags", C.c_uint32), ("shape", vp), ("half_extents", vp), ("position", vp), ("rotation", vp),
+                ("prediction_distance", vp), ("filter", avn_spatial_filter)]
+
+
+class avn_spatial_shape_contact_f32(C.Structure):
+    _fields_ = [("collider", C.c_uint32), ("entity", C.c_uint32), ("penetration", C.c_float), ("normal", C.c_float * 3), ("point", C.c_float * 3),
+                ("anchor1", C.c_float * 3), ("anchor2", C.c_float * 3)]
+
+
+class avn_spatial_shape_contact_f64(C.Structure):
+    _fields_ = [("collider", C.c_uint32), ("entity", C.c_uint32), ("penetration", C.c_double), ("normal", C.c_double * 3), ("point", C.c_double * 3),
+                ("anchor1", C.c_double * 3), ("anchor2", C.c_double * 3), ("reserved", C.c_uint32 * 2)]
+
+
+class avn_spatial_shape_contacts_out(C.Structure):
+    _fields_ = [("contacts", vp), ("count", vp)]
+
+
+class avn_spatial_depenetration_config(C.Structure):
+    _fields_ = [("skin_width", C.c_double), ("max_depenetration_error", C.c_double), ("penetration_rejection_threshold", C.c_double),
+                ("iterations", C.c_uint32)]
+
+
+class avn_spatial_depenetration_f32(C.Structure):
+    _fields_ = [("fixup", C.c_float * 3), ("count", C.c_uint32), ("iterations_run", C.c_uint32), ("truncated", C.c_uint32)]
+
+
+class avn_spatial_depenetration_f64(C.Structure):
+    _fields_ = [("fixup", C.c_double * 3), ("count", C.c_uint32), ("iterations_run", C.c_uint32), ("truncated", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class avn_spatial_depenetrations_out(C.Structure):
+    _fields_ = [("depenetration", vp)]
+
+
 class avn_spatial_shape_hits_out(C.Structure):
     _fields_ = [("hits", vp), ("count", vp)]
 
@@ -102,10 +139,12 @@ class avn_spatial_stats(C.Structure):
 STRUCTS = [avn_spatial_filter, avn_spatial_rays, avn_spatial_points, avn_spatial_aabbs, avn_spatial_hit_f32, avn_spatial_hit_f64,
            avn_spatial_hits_out, avn_spatial_ids_out, avn_spatial_stats, avn_spatial_solid_points, avn_spatial_shapes,
            avn_spatial_projection_f32, avn_spatial_projection_f64, avn_spatial_projections_out, avn_spatial_shape_casts,
-           avn_spatial_shape_hit_f32, avn_spatial_shape_hit_f64, avn_spatial_shape_hits_out]
+           avn_spatial_shape_hit_f32, avn_spatial_shape_hit_f64, avn_spatial_shape_hits_out, avn_spatial_shape_contact_queries,
+           avn_spatial_shape_contact_f32, avn_spatial_shape_contact_f64, avn_spatial_shape_contacts_out, avn_spatial_depenetration_config,
+           avn_spatial_depenetration_f32, avn_spatial_depenetration_f64, avn_spatial_depenetrations_out]
 SYMBOLS = ["avn_spatial_update", "avn_spatial_cast_rays", "avn_spatial_ray_hits", "avn_spatial_point_intersections",
            "avn_spatial_aabb_intersections", "avn_spatial_stats_get", "avn_spatial_project_points", "avn_spatial_shape_intersections",
-           "avn_spatial_cast_shapes", "avn_spatial_shape_hits"]
+           "avn_spatial_cast_shapes", "avn_spatial_shape_hits", "avn_spatial_shape_contacts", "avn_spatial_depenetrate"]
 
 
 def hit_dtype(bits: int) -> np.dtype:
@@ -127,6 +166,21 @@ def shape_hit_dtype(bits: int) -> np.dtype:
                      ("normal1", s, (3,)), ("normal2", s, (3,))], align=True)
 
 
+def shape_contact_dtype(bits: int) -> np.dtype:
+    """numpy mirror of avn_spatial_shape_contact_fNN (60 / 120 bytes, no padding; f64: two reserved words at the end, always 0)."""
+    s = np.float32 if bits == 32 else np.float64
+    f = [("collider", np.uint32), ("entity", np.uint32), ("penetration", s), ("normal", s, (3,)), ("point", s, (3,)), ("anchor1", s, (3,)),
+         ("anchor2", s, (3,))]
+    return np.dtype(f + ([("reserved", np.uint32, (2,))] if bits == 64 else []), align=True)
+
+
+def depenetration_dtype(bits: int) -> np.dtype:
+    """numpy mirror of avn_spatial_depenetration_fNN (24 / 40 bytes; f64: a reserved word at the end, always 0)."""
+    s = np.float32 if bits == 32 else np.float64
+    f = [("fixup", s, (3,)), ("count", np.uint32), ("iterations_run", np.uint32), ("truncated", np.uint32)]
+    return np.dtype(f + ([("reserved", np.uint32)] if bits == 64 else []), align=True)
+
+
 def _declare(dll):
     for name in SYMBOLS:
         getattr(dll, name).restype = C.c_int32
@@ -140,6 +194,8 @@ def _declare(dll):
     dll.avn_spatial_shape_intersections.argtypes = [vp, vp, C.c_uint32, vp]
     dll.avn_spatial_cast_shapes.argtypes = [vp, vp, vp]
     dll.avn_spatial_shape_hits.argtypes = [vp, vp, C.c_uint32, vp]
+    dll.avn_spatial_shape_contacts.argtypes = [vp, vp, C.c_uint32, vp]
+    dll.avn_spatial_depenetrate.argtypes = [vp, vp, vp, vp]
 
 
 class SpatialQuery:
@@ -161,6 +217,8 @@ class SpatialQuery:
         self.hit_dtype = hit_dtype(self.bits)
         self.projection_dtype = projection_dtype(self.bits)
         self.shape_hit_dtype = shape_hit_dtype(self.bits)
+        self.shape_contact_dtype = shape_contact_dtype(self.bits)
+        self.depenetration_dtype = depenetration_dtype(self.bits)
         self._keep = []
 
     # -- plumbing ------------------------------------------------------------------------------
@@ -192,7 +250,7 @@ class SpatialQuery:
     def _out(self, shape, dt, dev, like=None):
         if dev:
             import torch
-            if dt is self.hit_dtype or dt is self.projection_dtype or dt is self.shape_hit_dtype:
+            if isinstance(dt, np.dtype):   # a record: bytes
                 t = torch.empty(tuple(shape) + (dt.itemsize,), dtype=torch.uint8, device=like.device)
             else:
                 t = torch.empty(shape, dtype={np.uint32: torch.int32}[dt], device=like.device)
@@ -208,8 +266,8 @@ class SpatialQuery:
             f.n_excluded = len(excluded)
         return f
 
-    def _flags(self, dev, skip_host_shapes):
-        return (DEVICE_POINTERS if dev else 0) | (SKIP_HOST_SHAPES if skip_host_shapes else 0)
+    def _flags(self, dev, skip_host_shapes, skip_sensors=False):
+        return (DEVICE_POINTERS if dev else 0) | (SKIP_HOST_SHAPES if skip_host_shapes else 0) | (SKIP_SENSORS if skip_sensors else 0)
 
     @staticmethod
     def _sync_torch(dev):
@@ -368,6 +426,51 @@ class SpatialQuery:
         self._sync_torch(dev)
         self._check(self.dll.avn_spatial_shape_hits(self.world.handle, C.byref(q), int(max_hits), C.byref(o)))
         return hits, cnt
+
+    def shape_contacts(self, shape, half_extents, position, rotation, prediction_distance, cap, mask=None, excluded=None, skip_host_shapes=False,
+                       skip_sensors=False):
+        """MoveAndSlide::intersections per query shape: (contact records [n, cap] in ascending collider index, ``shape_contact_dtype``, unused
+        slots MISS; true counts [n]).  ``prediction_distance`` is a scalar or [n].  Device tensors in: a uint8 tensor [n, cap, itemsize] out."""
+        dev = self._is_tensor(position)
+        n = int(position.shape[0])
+        q = avn_spatial_shape_contact_queries()
+        q.count = n
+        q.flags = self._flags(dev, skip_host_shapes, skip_sensors)
+        q.shape = self._arr(shape, np.uint8, dev, (n,))
+        q.half_extents = self._arr(half_extents, self.dtype, dev, (n, 3))
+        q.position = self._arr(position, self.dtype, dev, (n, 3))
+        q.rotation = self._arr(rotation, self.dtype, dev, (n, 4))
+        if not self._is_tensor(prediction_distance) and np.ndim(prediction_distance) == 0:
+            prediction_distance = np.full(n, prediction_distance) if not dev else position.new_full((n,), float(prediction_distance))
+        q.prediction_distance = self._arr(prediction_distance, self.dtype, dev, (n,))
+        q.filter = self._filter(n, mask, excluded, dev)
+        rec, rp = self._out((n, int(cap)), self.shape_contact_dtype, dev, position)
+        cnt, cp = self._out((n,), np.uint32, dev, position)
+        o = avn_spatial_shape_contacts_out(rp, cp)
+        self._sync_torch(dev)
+        self._check(self.dll.avn_spatial_shape_contacts(self.world.handle, C.byref(q), int(cap), C.byref(o)))
+        return rec, cnt
+
+    def depenetrate(self, shape, half_extents, position, rotation, skin_width, max_depenetration_error, penetration_rejection_threshold, iterations,
+                    mask=None, excluded=None, skip_host_shapes=False, skip_sensors=False):
+        """MoveAndSlide::depenetrate per query shape: a structured array of ``depenetration_dtype`` records (fixup, count, iterations_run,
+        truncated).  The caller applies PhysicsLengthUnit to the configuration.  Device tensors in: a uint8 tensor [n, itemsize] out."""
+        dev = self._is_tensor(position)
+        n = int(position.shape[0])
+        q = avn_spatial_shapes()
+        q.count = n
+        q.flags = self._flags(dev, skip_host_shapes, skip_sensors)
+        q.shape = self._arr(shape, np.uint8, dev, (n,))
+        q.half_extents = self._arr(half_extents, self.dtype, dev, (n, 3))
+        q.position = self._arr(position, self.dtype, dev, (n, 3))
+        q.rotation = self._arr(rotation, self.dtype, dev, (n, 4))
+        q.filter = self._filter(n, mask, excluded, dev)
+        cfg = avn_spatial_depenetration_config(float(skin_width), float(max_depenetration_error), float(penetration_rejection_threshold), int(iterations))
+        rec, rp = self._out((n,), self.depenetration_dtype, dev, position)
+        o = avn_spatial_depenetrations_out(rp)
+        self._sync_torch(dev)
+        self._check(self.dll.avn_spatial_depenetrate(self.world.handle, C.byref(q), C.byref(cfg), C.byref(o)))
+        return rec
 
     def stats(self) -> avn_spatial_stats:
         s = avn_spatial_stats()

@@ -1,7 +1,8 @@
 /*
  * avian_mi355x_spatial.h — device spatial queries: ray casts, point and AABB intersections, point projection, shape intersections and shape
  * casts against the colliders the world holds in HBM: every query family of SpatialQueryPipeline, for the shapes with device geometry (Ball,
- * Cuboid).
+ * Cuboid); plus the stateless half of the kinematic character controller (MoveAndSlide::intersections / depenetrate): shape contacts and
+ * depenetration.
  *
  * Mirrors Avian's `SpatialQueryPlugin` (spatial_query/mod.rs:190-212), whose systems run in `PhysicsStepSystems::SpatialQuery` right after
  * `Sleeping` (schedule/mod.rs:98-105): `update_spatial_query_pipeline` rebuilds a BVH of every collider from `Position` / `Rotation`
@@ -91,6 +92,34 @@
  *      cast at a ball: through the query's isometry at pos_q + d t), normal2 = -normal1 with a zero component staying +0.
  *    NOT covered: target_distance != 0, ignore_origin_penetration, compute_contact_on_penetration = true, predicates
  *    (cast_shape_predicate), casts against AVN_SHAPE_HOST colliders, Rust declarations.
+ *  - shape contacts (MoveAndSlide::intersections, character_controller/move_and_slide.rs:1032-1078).  Per query shape at its pose with a
+ *    prediction distance p, collider c contributes ONE contact iff all of (a)-(d) hold, evaluated in this order:
+ *      (a) c is a candidate and passes the filter (with AVN_SPATIAL_SKIP_SENSORS: and is not a sensor).
+ *      (b) the AABB precondition (Avian's aabb_intersections_with_aabb(shape.aabb().grow(p)); part of the definition, not a culling step):
+ *          [a, b] = shape_aabb of the query shape at its pose (the broad phase's shape_aabb, no margins), qmin = a - p, qmax = b + p per
+ *          component; [mn, mx] = shape_aabb of the collider at its snapshot pose, computed from the snapshot's pose and half extents with the
+ *          same function (not the padded leaf box); the boxes intersect: mn <= qmax && mx >= qmin per axis.
+ *      (c) contact_query::contact_manifolds(query as shape 1, collider as shape 2, prediction p) returns a manifold: the narrow phase's own
+ *          per-pair function (avn_contact_manifolds of avian_mi355x.h is its batch form), poses through make_isometry.
+ *      (d) the manifold's deepest raw point exists: ContactManifold::find_deepest_contact, Rust's max_by over the raw points in emission
+ *          order, where the LATER point wins a tie.  As a fold over the raw points (at most 16), best = the first point, then
+ *          if (!(best.penetration > pt.penetration)) best = pt.
+ *    The record: penetration = best.penetration; normal = -manifold.normal per component (from the collider towards the query shape, the
+ *    direction MoveAndSlide::intersections hands to its callback); anchor1 = best.anchor1 (relative to the query shape's position);
+ *    anchor2 = anchor1 + (query position - collider position); point = query position + anchor1.
+ *    Per query the records come in ascending collider index, the first `cap`, plus the true count (Avian's order is its BVH's traversal
+ *    order, which is arbitrary: ascending index is a deterministic strengthening).  Unused slots: both ids AVN_SPATIAL_MISS, the rest 0.
+ *  - depenetration (MoveAndSlide::depenetrate = intersections with prediction skin_width, then depenetrate_intersections,
+ *    move_and_slide.rs:982-1009).  With the contacts of the query in ascending collider index (at most AVN_SPATIAL_MAX_HITS of them; with
+ *    more, `truncated` is 1 and the fixup comes from the first AVN_SPATIAL_MAX_HITS) and the configuration cast once to the world's scalar:
+ *      fixup = 0;  repeat up to `iterations` times:  total_error = 0;  for each contact in order:  dist = penetration + skin_width;
+ *      skipped when dist > penetration_rejection_threshold;  error = max(dist - (fixup.x n.x + fixup.y n.y + fixup.z n.z), 0) (a NaN
+ *      difference gives 0);  total_error += error;  fixup += error * n (per component);  after the pass: stop when total_error <
+ *      max_depenetration_error.  iterations_run counts the passes started.  Avian hands the normal over as a Dir, which is f32: in an f64
+ *      world every component of n is rounded through float before use (the contact records keep the full-precision normal).  The caller
+ *      applies PhysicsLengthUnit to max_depenetration_error and penetration_rejection_threshold.
+ *    NOT covered: cast_move, ignore_origin_penetration, the move_and_slide loop, project_velocity, query shapes other than Ball / Cuboid,
+ *    contacts against AVN_SHAPE_HOST colliders, predicates, Rust declarations.
  *
  * Non-finite inputs (NaN or inf components):
  *  - a collider whose snapshot position, rotation or shape AABB is not finite is never a candidate (it keeps its collider index);
@@ -98,7 +127,8 @@
  *    the scene;
  *  - a query shape whose kind is neither AVN_SHAPE_CUBOID nor AVN_SHAPE_BALL, whose position, rotation, half extents (a ball: its radius) or
  *    AABB are not finite, or which has a negative half extent, answers a count of 0 (a shape cast: a miss / count 0; so does a cast whose
- *    direction is not finite or whose max_distance is NaN).  This is decided per query on the device;
+ *    direction is not finite or whose max_distance is NaN; shape contacts: so does a prediction_distance that is NaN, infinite or
+ *    negative; depenetration: a zero fixup with count 0).  This is decided per query on the device;
  *  - a hit needs a finite distance.
  *  Answers to finite inputs do not depend on these rules.
  *
@@ -112,7 +142,9 @@
  *    against the poses of the last update, as Avian's pipeline does between updates (SpatialQuery::update_pipeline).
  *  - AVN_SHAPE_HOST colliders have no device geometry: if the snapshot holds any, queries return AVN_ERR_STATE unless the query sets
  *    AVN_SPATIAL_SKIP_HOST_SHAPES; with the flag they are never candidates (avn_spatial_stats.host_skipped counts them).
- *  - sensors, sleeping and static bodies' colliders are all candidates, as in Avian's pipeline.
+ *  - sensors, sleeping and static bodies' colliders are all candidates, as in Avian's pipeline.  MoveAndSlide's collider query is
+ *    Without<Sensor>: avn_spatial_shape_contacts and avn_spatial_depenetrate (and only they) accept AVN_SPATIAL_SKIP_SENSORS, with which a
+ *    collider uploaded with AVN_COLLIDER_SENSOR is never a candidate.
  *
  * Filter (SpatialQueryFilter::test, query_filter.rs:97-101): a collider is a candidate when memberships & mask != 0 and its
  * entity_index is not in the excluded list.  ONE excluded list is shared by every query of a call (a caster's own entity goes in it for
@@ -138,9 +170,11 @@ extern "C" {
 enum {
     AVN_SPATIAL_DEVICE_POINTERS = 1,   /* every input and output array of the call (filter included) is a device pointer on the world's device;
                                           the caller's writes to them must be complete before the call */
-    AVN_SPATIAL_SKIP_HOST_SHAPES = 2   /* AVN_SHAPE_HOST colliders are never candidates (else their presence is AVN_ERR_STATE) */
+    AVN_SPATIAL_SKIP_HOST_SHAPES = 2,  /* AVN_SHAPE_HOST colliders are never candidates (else their presence is AVN_ERR_STATE) */
+    AVN_SPATIAL_SKIP_SENSORS = 4       /* avn_spatial_shape_contacts / avn_spatial_depenetrate only: AVN_COLLIDER_SENSOR colliders are never
+                                          candidates (MoveAndSlide's Without<Sensor>); the other queries ignore the flag */
 };
-#define AVN_SPATIAL_MAX_HITS 64        /* largest max_hits of avn_spatial_ray_hits / avn_spatial_shape_hits */
+#define AVN_SPATIAL_MAX_HITS 64        /* largest max_hits of avn_spatial_ray_hits / avn_spatial_shape_hits, largest cap of avn_spatial_shape_contacts */
 #define AVN_SPATIAL_MISS 0xFFFFFFFFu   /* collider index of a miss */
 
 typedef struct avn_spatial_filter {
@@ -259,6 +293,72 @@ typedef struct avn_spatial_shape_hit_f64 {
     double normal2[3];
 } avn_spatial_shape_hit_f64;
 
+/* the queries of avn_spatial_shape_contacts: the fields of avn_spatial_shapes plus a prediction distance per query */
+typedef struct avn_spatial_shape_contact_queries {
+    uint32_t count;
+    uint32_t flags;              /* AVN_SPATIAL_*, AVN_SPATIAL_SKIP_SENSORS included */
+    const uint8_t* shape;        /* [n] AVN_SHAPE_CUBOID / AVN_SHAPE_BALL */
+    const void* half_extents;    /* [3n] (ball: radius in x) */
+    const void* position;        /* [3n] */
+    const void* rotation;        /* [4n] xyzw, unit (the caller normalises) */
+    const void* prediction_distance;   /* [n] finite and >= 0 (else the query answers count 0) */
+    avn_spatial_filter filter;
+} avn_spatial_shape_contact_queries;
+
+/* The deepest contact of the query shape with one collider (MoveAndSlide::intersections' callback arguments) with the collider's table index.
+ * 60 / 120 bytes, no implicit padding: every byte of a record is written. */
+typedef struct avn_spatial_shape_contact_f32 {
+    uint32_t collider;   /* AVN_SPATIAL_MISS = an unused slot (entity too; the rest 0) */
+    uint32_t entity;
+    float penetration;   /* ContactPoint::penetration of the deepest point (negative: a gap within the prediction distance) */
+    float normal[3];     /* -manifold.normal: from the collider towards the query shape, world space */
+    float point[3];      /* query position + anchor1 */
+    float anchor1[3];    /* relative to the query shape's position, world orientation */
+    float anchor2[3];    /* relative to the collider's position */
+} avn_spatial_shape_contact_f32;
+typedef struct avn_spatial_shape_contact_f64 {
+    uint32_t collider;
+    uint32_t entity;
+    double penetration;
+    double normal[3];
+    double point[3];
+    double anchor1[3];
+    double anchor2[3];
+    uint32_t reserved[2];   /* always written as 0 */
+} avn_spatial_shape_contact_f64;
+
+typedef struct avn_spatial_shape_contacts_out {
+    void* contacts;      /* avn_spatial_shape_contact_fNN [n * cap], ascending collider index per query; NULL is legal when cap == 0 */
+    uint32_t* count;     /* [n] true number of contacts */
+} avn_spatial_shape_contacts_out;
+
+/* DepenetrationConfig (move_and_slide.rs); cast once to the world's scalar.  The caller applies PhysicsLengthUnit. */
+typedef struct avn_spatial_depenetration_config {
+    double skin_width;                        /* the prediction distance of the contacts, added to every penetration */
+    double max_depenetration_error;           /* a pass whose total error is below this ends the iteration */
+    double penetration_rejection_threshold;   /* contacts with penetration + skin_width above this are ignored */
+    uint32_t iterations;                      /* depenetration_iterations; 0 answers zero vectors without traversing */
+} avn_spatial_depenetration_config;
+
+/* 24 / 40 bytes, every byte written */
+typedef struct avn_spatial_depenetration_f32 {
+    float fixup[3];            /* the offset to add to the query shape's position */
+    uint32_t count;            /* true number of contacts of the query */
+    uint32_t iterations_run;   /* passes started */
+    uint32_t truncated;        /* 1: count > AVN_SPATIAL_MAX_HITS, the fixup comes from the first AVN_SPATIAL_MAX_HITS contacts */
+} avn_spatial_depenetration_f32;
+typedef struct avn_spatial_depenetration_f64 {
+    double fixup[3];
+    uint32_t count;
+    uint32_t iterations_run;
+    uint32_t truncated;
+    uint32_t reserved;         /* always written as 0 */
+} avn_spatial_depenetration_f64;
+
+typedef struct avn_spatial_depenetrations_out {
+    void* depenetration; /* avn_spatial_depenetration_fNN [n] */
+} avn_spatial_depenetrations_out;
+
 typedef struct avn_spatial_shape_hits_out {
     void* hits;          /* avn_spatial_shape_hit_fNN [n] (cast_shapes) or [n * max_hits] (shape_hits; unused slots are misses) */
     uint32_t* count;     /* [n] true number of hits (shape_hits); ignored by cast_shapes */
@@ -308,6 +408,13 @@ AVN_API avn_status avn_spatial_cast_shapes(avn_world* w, const avn_spatial_shape
 /* SpatialQueryPipeline::shape_hits (pipeline.rs:443-487); ShapeCaster / ShapeHits: per cast the max_hits nearest hits, sorted, plus the true count.
  * 1 <= max_hits <= AVN_SPATIAL_MAX_HITS, else AVN_ERR_BAD_ARG. */
 AVN_API avn_status avn_spatial_shape_hits(avn_world* w, const avn_spatial_shape_casts* casts, uint32_t max_hits, const avn_spatial_shape_hits_out* out);
+/* MoveAndSlide::intersections (move_and_slide.rs:1032-1078): per query shape the deepest contact with every collider nearer than its
+ * prediction distance, ascending collider index, the first `cap`, plus the true count.  0 <= cap <= AVN_SPATIAL_MAX_HITS, else AVN_ERR_BAD_ARG. */
+AVN_API avn_status avn_spatial_shape_contacts(avn_world* w, const avn_spatial_shape_contact_queries* queries, uint32_t cap, const avn_spatial_shape_contacts_out* out);
+/* MoveAndSlide::depenetrate (move_and_slide.rs:868-897, 982-1009): the contacts of every query shape with prediction skin_width, then the Gauss-Seidel
+ * depenetration over them.  shapes->flags may carry AVN_SPATIAL_SKIP_SENSORS.  The world keeps a device buffer of
+ * count * AVN_SPATIAL_MAX_HITS contact records for this call (3.8 KB per query in f32, 7.7 KB in f64); it grows and is never shrunk. */
+AVN_API avn_status avn_spatial_depenetrate(avn_world* w, const avn_spatial_shapes* shapes, const avn_spatial_depenetration_config* config, const avn_spatial_depenetrations_out* out);
 /* snapshot sizes and the traversal counters of the last query call */
 AVN_API avn_status avn_spatial_stats_get(avn_world* w, avn_spatial_stats* out);
 

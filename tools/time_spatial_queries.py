@@ -6,6 +6,8 @@
   ray_hits k = 16, 64 k rays;  point and AABB intersections, 10^6 queries each
   project_points, 10^6 points into cfg2 (the points of point_intersections);  shape_intersections, 10^6 query shapes, half balls and half
   cuboids with sizes like the AABB query's boxes, cap 16 -- reported beside the point and AABB figures of the same run
+  shape_contacts (prediction 0.05 m, cap 16) and depenetrate (skin 0.05 m, 4 iterations) with the SAME 10^6 query shapes as
+  shape_intersections, which shares the traversal and has the cheaper leaf: the yardstick of the two
   cast_shapes, 10^6 casts into cfg2 from the rays' origins along the rays' directions, short (<= 2 m) and long (200 m), half balls and half
   cuboids of half extent <= 0.25 m;  shape_hits k = 16, 64 k long casts -- reported beside cast_rays / ray_hits of the same run
 
@@ -127,6 +129,22 @@ def main():
     res["shapes_per_s"] = n / (ms * 1e-3)
     res["shapes_leaves_per_query"], res["shapes_nodes_per_query"] = st.leaves_visited / n, st.nodes_visited / n
     res["shapes_bytes_floor"] = n * (1 + 12 + 12 + 16 + 16 * 4 + 4)
+    # shape contacts and depenetration: the same query shapes (leaves = colliders that passed the filter, before the AABB precondition)
+    pred = torch.full((n,), 0.05, device=dev)
+    ms = timed(lambda: sq.shape_contacts(kind, ext, p, rot, pred, 16), reps)
+    st = sq.stats()
+    res["contacts_1m_ms"] = ms
+    res["contacts_per_s"] = n / (ms * 1e-3)
+    res["contacts_leaves_per_query"], res["contacts_nodes_per_query"] = st.leaves_visited / n, st.nodes_visited / n
+    res["contacts_bytes_floor"] = n * (1 + 12 + 12 + 16 + 4 + 16 * 60 + 4)
+    res["contacts_over_shapes"] = ms / res["shapes_1m_ms"]
+    ms = timed(lambda: sq.depenetrate(kind, ext, p, rot, 0.05, 1e-4, 0.5, 4), reps)
+    st = sq.stats()
+    res["depenetrate_1m_ms"] = ms
+    res["depenetrate_per_s"] = n / (ms * 1e-3)
+    res["depenetrate_leaves_per_query"], res["depenetrate_nodes_per_query"] = st.leaves_visited / n, st.nodes_visited / n
+    res["depenetrate_bytes_floor"] = n * (1 + 12 + 12 + 16 + 24)
+    res["depenetrate_over_shapes"] = ms / res["shapes_1m_ms"]
     small = ext * 0.25
     crec = 60
     for name, md in (("short", short), ("long", long)):
