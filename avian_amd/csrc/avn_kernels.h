@@ -471,6 +471,7 @@ template <class T> struct SC {
     uint32_t skip_sensors;           // AVN_SPATIAL_SKIP_SENSORS
     uint32_t pad_unused;             // 1: slots past the count are written as misses (the caller's output); 0: left alone (depenetrate's own buffer)
     SpatialShapeContact<T>* rec;     // [n * cap]
+    const uint32_t* self_entity;     // [n] or nullptr (the entry points of 4.4.7): a collider with this entity_index is not a candidate of the query
 };
 // k_sp_depenetrate over the records of a k_sp_contacts launch with cap = AVN_SPATIAL_MAX_HITS
 template <class T> struct SD {
@@ -481,9 +482,57 @@ template <class T> struct SD {
     uint32_t iterations;
     SpatialDepenetration<T>* out;        // [n]
 };
+// move and slide.  == avn_spatial_move_hit_fNN (64 / 120 bytes), avn_spatial_slide_hit_fNN (48 / 80), avn_spatial_slide_fNN (36 / 64)
+template <class T> struct SpatialMoveHit { uint32_t collider, entity; T distance, collision_distance; T point1[3], point2[3], normal1[3], normal2[3]; };
+template <class T> struct SpatialSlideHit { uint32_t collider, entity, iteration, kind; T point[3], normal[3]; T distance, collision_distance; };
+template <class T> struct SpatialSlide { T position[3], velocity[3]; uint32_t iterations_run, hit_count, flags; };
+template <> struct SpatialSlide<double> { double position[3], velocity[3]; uint32_t iterations_run, hit_count, flags, reserved; };
+__device__ __forceinline__ void sp_clear_reserved(SpatialSlide<float>&) {}
+__device__ __forceinline__ void sp_clear_reserved(SpatialSlide<double>& r) { r.reserved = 0u; }
+// k_sp_project_velocity
+template <class T> struct SV {
+    uint32_t n, stride;
+    const T* velocity;               // [3n]
+    const float* normals;            // [n * stride * 3]
+    const uint32_t* count;           // [n]
+    T* out;                          // [3n]
+};
+// k_sp_cast_move + k_sp_cast_move_resolve.  q: the SPQ_SHAPES fields (a = positions, shape, he, rot, mask, excluded, stats)
+#define SP_SLIDE_VALID 1u
+#define SP_SLIDE_LIVE 2u
+#define SP_SLIDE_TRUNCATED 4u
+#define SP_SLIDE_PLANES 34           // plane slots per character: AVN_SPATIAL_MAX_PLANES of the configuration, the sweep's, one to spare
+template <class T> struct SM {
+    SQ<T> q;
+    const T* movement;               // [3n]
+    const T* skin;                   // [n], or nullptr: skin_all
+    T skin_all;
+    const uint32_t* self_entity;     // [n] or nullptr
+    const uint32_t* state;           // [n] or nullptr: the slide's flags -- a lane without SP_SLIDE_LIVE answers a miss without traversing
+    SpatialMoveHit<T>* out;          // [n]
+    uint32_t* pending;               // [n * AVN_SPATIAL_MAX_HITS] colliders that overlap the query at its start, in traversal order: the traversal's hand-over
+    uint32_t* pending_count;         // [n] true number of them                                                    to k_sp_cast_move_resolve
+};
+// the per-character state of avn_spatial_move_and_slide, in buffers the world owns, and the phases' parameters
+enum { SPL_BEGIN = 0, SPL_DEPENETRATE = 1, SPL_SWEEP = 2, SPL_ADVANCE = 3, SPL_PLANES = 4, SPL_END = 5 };
+template <class T> struct SL {
+    uint32_t n, hit_cap, n_planes, max_planes, iteration, depen_iterations;
+    const uint8_t* shape; const T *he, *pos_in, *rot, *vel_in;           // the call's inputs
+    T *pos, *vel, *time_left, *movement, *pred;                          // [3n] [3n] [n] [3n] [n]
+    uint32_t *flags, *iters, *hit_count, *plane_count;                   // [n]
+    float* planes;                                                       // [n * SP_SLIDE_PLANES * 3]
+    const float* cfg_planes;                                             // [3 * n_planes]
+    T delta_time, skin, threshold, max_error, rejection;
+    const SpatialShapeContact<T>* rec; const uint32_t* count;            // the contacts of the last k_sp_contacts launch, cap AVN_SPATIAL_MAX_HITS
+    const SpatialMoveHit<T>* mh;                                         // [n] the last k_sp_cast_move launch
+    SpatialSlideHit<T>* hits; SpatialSlide<T>* out;                      // the call's outputs
+};
+template <class T> void launch_spatial_project_velocity(const SV<T>&, hipStream_t);
+template <class T> void launch_spatial_cast_move(const SP<T>&, const SM<T>&, bool zero_stats, hipStream_t);
+template <class T> void launch_spatial_slide_phase(const SL<T>&, int phase, hipStream_t);
 template <class T> void launch_spatial_build(const DW<T>&, const BP<T>&, const SP<T>&, hipStream_t);
 template <class T> void launch_spatial_query(const SP<T>&, const SQ<T>&, int kind, hipStream_t);
-template <class T> void launch_spatial_contacts(const SP<T>&, const SC<T>&, hipStream_t);
+template <class T> void launch_spatial_contacts(const SP<T>&, const SC<T>&, hipStream_t, bool zero_stats = true);
 template <class T> void launch_spatial_depenetrate(const SD<T>&, hipStream_t);
 
 }  // namespace avn

@@ -31,6 +31,11 @@ AVN_API avn_status avn_spatial_shape_hits(avn_world* w, const avn_spatial_shape_
 }
 AVN_API avn_status avn_spatial_shape_contacts(avn_world* w, const avn_spatial_shape_contact_queries* q, uint32_t cap, const avn_spatial_shape_contacts_out* o) { SP_GUARD(spatial_shape_contacts(q, cap, o)); }
 AVN_API avn_status avn_spatial_depenetrate(avn_world* w, const avn_spatial_shapes* s, const avn_spatial_depenetration_config* c, const avn_spatial_depenetrations_out* o) { SP_GUARD(spatial_depenetrate(s, c, o)); }
+AVN_API avn_status avn_spatial_project_velocities(avn_world* w, const avn_spatial_velocity_projections* p, const avn_spatial_velocities_out* o) { SP_GUARD(spatial_project_velocities(p, o)); }
+AVN_API avn_status avn_spatial_cast_moves(avn_world* w, const avn_spatial_moves* m, const avn_spatial_move_hits_out* o) { SP_GUARD(spatial_cast_moves(m, o)); }
+AVN_API avn_status avn_spatial_move_and_slide(avn_world* w, const avn_spatial_characters* c, const avn_spatial_move_and_slide_config* cfg, uint32_t hit_cap, const avn_spatial_slides_out* o) {
+    SP_GUARD(spatial_move_and_slide(c, cfg, hit_cap, o));
+}
 AVN_API avn_status avn_spatial_stats_get(avn_world* w, avn_spatial_stats* o) { SP_GUARD(spatial_stats_get(o)); }
 
 }  // extern "C"

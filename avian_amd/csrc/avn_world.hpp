@@ -135,6 +135,9 @@ struct WorldBase {
     virtual avn_status spatial_cast_shapes(const avn_spatial_shape_casts*, uint32_t max_hits, const avn_spatial_shape_hits_out*) = 0;   // max_hits 0: the closest hit
     virtual avn_status spatial_shape_contacts(const avn_spatial_shape_contact_queries*, uint32_t cap, const avn_spatial_shape_contacts_out*) = 0;
     virtual avn_status spatial_depenetrate(const avn_spatial_shapes*, const avn_spatial_depenetration_config*, const avn_spatial_depenetrations_out*) = 0;
+    virtual avn_status spatial_project_velocities(const avn_spatial_velocity_projections*, const avn_spatial_velocities_out*) = 0;
+    virtual avn_status spatial_cast_moves(const avn_spatial_moves*, const avn_spatial_move_hits_out*) = 0;
+    virtual avn_status spatial_move_and_slide(const avn_spatial_characters*, const avn_spatial_move_and_slide_config*, uint32_t hit_cap, const avn_spatial_slides_out*) = 0;
     virtual avn_status spatial_stats_get(avn_spatial_stats*) = 0;
 };
 

@@ -1,6 +1,7 @@
 // k_spatial.hip — spatial queries on the device (include/avian_mi355x_spatial.h): an LBVH over the collider table and one-lane-per-query
 // traversals for ray casts, ray hits, point and AABB intersections (k_sp_query), point projection (k_sp_project), shape intersections
-// (k_sp_shapes), shape casts (k_sp_cast), shape contacts (k_sp_contacts) and the depenetration over them (k_sp_depenetrate).
+// (k_sp_shapes), shape casts (k_sp_cast), shape contacts (k_sp_contacts), the depenetration over them (k_sp_depenetrate), velocity
+// projection (k_sp_project_velocity), cast_move (k_sp_cast_move) and the phases of the move-and-slide loop (k_sp_slide).
 //
 // avn_spatial_update (launch_spatial_build), all on the world's stream:
 //   1. k_sp_snapshot   one thread per collider: its pose (collider_pose), the exact shape AABB (shape_aabb), padded, as the leaf box;
@@ -1138,6 +1139,7 @@ __global__ __launch_bounds__(SP_WAVE) void k_sp_contacts(SP<T> sp, SC<T> sc) {
         V3<T> he1{q.he[3 * (size_t)qi], q.he[3 * (size_t)qi + 1], q.he[3 * (size_t)qi + 2]};
         const Q4<T> rot1{q.rot[4 * (size_t)qi], q.rot[4 * (size_t)qi + 1], q.rot[4 * (size_t)qi + 2], q.rot[4 * (size_t)qi + 3]};
         const T pred = sc.prediction ? sc.prediction[qi] : sc.prediction_all;
+        const uint32_t self = sc.self_entity ? sc.self_entity[qi] : AVN_SPATIAL_MISS;
         if (shape1 == AVN_SHAPE_BALL) he1 = V3<T>{he1.x, he1.x, he1.x};   // (a ball has its radius in x: y and z are not read)
         // k_sp_shapes' rule, plus a prediction distance that is finite and not negative: otherwise count 0
         bool valid = shape1 <= AVN_SHAPE_BALL && is_finite(pos1) && is_finite(V3<T>{rot1.x, rot1.y, rot1.z}) && finite_t(rot1.w) && is_finite(he1) &&
@@ -1163,7 +1165,7 @@ __global__ __launch_bounds__(SP_WAVE) void k_sp_contacts(SP<T> sp, SC<T> sc) {
         auto leaf = [&](uint32_t node) {
             const uint32_t c = sp.leaf_col[node - (n - 1)];
             const uint4 info = sp.info[c];
-            if (!info.w || (info.y & mask) == 0u || (sc.skip_sensors && (info.w & SP_INFO_SENSOR)) || (q.n_excluded && sp_excluded(q.excluded, q.n_excluded, info.x))) return;
+            if (!info.w || (info.y & mask) == 0u || (sc.skip_sensors && (info.w & SP_INFO_SENSOR)) || (self != AVN_SPATIAL_MISS && info.x == self) || (q.n_excluded && sp_excluded(q.excluded, q.n_excluded, info.x))) return;
             ++leaves_tested;
             const V3<T> pos2 = xyz<T>(sp.pos[c]), he2 = xyz<T>(sp.he[c]);
             const Q4<T> rot2 = quat<T>(sp.rot[c]);
@@ -1277,14 +1279,454 @@ __global__ __launch_bounds__(SP_WAVE) void k_sp_depenetrate(SD<T> d) {
     d.out[qi] = r;
 }
 
-template <class T> void launch_spatial_contacts(const SP<T>& sp, const SC<T>& sc, hipStream_t s) {
-    (void)hipMemsetAsync(sc.q.stats, 0, 4 * sizeof(unsigned long long), s);
+template <class T> void launch_spatial_contacts(const SP<T>& sp, const SC<T>& sc, hipStream_t s, bool zero_stats) {
+    if (zero_stats) (void)hipMemsetAsync(sc.q.stats, 0, 4 * sizeof(unsigned long long), s);
     if (sc.q.n == 0) return;
     hipLaunchKernelGGL((k_sp_contacts<T>), dim3((sc.q.n + SP_WAVE - 1) / SP_WAVE), dim3(SP_WAVE), 0, s, sp, sc);
 }
 template <class T> void launch_spatial_depenetrate(const SD<T>& d, hipStream_t s) {
     if (d.n == 0) return;
     hipLaunchKernelGGL((k_sp_depenetrate<T>), dim3((d.n + SP_WAVE - 1) / SP_WAVE), dim3(SP_WAVE), 0, s, d);
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// move and slide (kernels of their own: the kernels above compile as before).  The header defines project_velocity, cast_move and the loop,
+// operation order included; tests/spatial_move_reference.py does the same operations in order.  DESIGN.md 4.4.8.
+
+// Scalar::total_cmp as an integer key
+__device__ __forceinline__ long long sp_total_key(float x) { const int b = __float_as_int(x); return b < 0 ? (b ^ 0x7FFFFFFF) : b; }
+__device__ __forceinline__ long long sp_total_key(double x) { const long long b = __double_as_longlong(x); return b < 0 ? (b ^ 0x7FFFFFFFFFFFFFFFll) : b; }
+template <class T> __device__ __forceinline__ T sp_dot3(V3<T> a, V3<T> b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
+// glam's cross
+template <class T> __device__ __forceinline__ V3<T> sp_cross3(V3<T> a, V3<T> b) { return V3<T>{a.y * b.z - b.y * a.z, a.z * b.x - b.z * a.x, a.x * b.y - b.x * a.y}; }
+template <class T> __device__ __forceinline__ V3<T> sp_plane(const float* __restrict__ p, uint32_t k) { return V3<T>{(T)p[3 * k], (T)p[3 * k + 1], (T)p[3 * k + 2]}; }
+
+// Dir::new_and_length(v as f32): false when the length is not finite or not > 0
+template <class T> __device__ __forceinline__ bool sp_dir_and_length(V3<T> v, V3<T>& dir, T& dist) {
+    const float x = (float)v.x, y = (float)v.y, z = (float)v.z;
+    const float len = sqrt_t(x * x + y * y + z * z);
+    if (!(finite_t(len) && len > 0.0f)) return false;
+    dir = V3<T>{(T)(x / len), (T)(y / len), (T)(z / len)};
+    dist = (T)len;
+    return true;
+}
+
+// project_velocity (velocity_project.rs:122-324) over the `cnt` normals at nrm (xyz interleaved, f32)
+template <class T> __device__ __forceinline__ V3<T> sp_project_velocity(V3<T> v, const float* __restrict__ nrm, uint32_t cnt) {
+    bool ok = is_finite(v);
+    for (uint32_t k = 0; k < cnt; ++k) ok = ok && finite_t(nrm[3 * k]) && finite_t(nrm[3 * k + 1]) && finite_t(nrm[3 * k + 2]);
+    if (!ok) return v;
+    const T eps = T(0.005);
+    const V3<T> x0{-v.x, -v.y, -v.z};
+    V3<T> s = x0, n1 = vzero<T>(), n2 = vzero<T>();
+    int cone = 0;   // 0: Origin, 1: Ray(n1), 2: Wedge(n1, n2)
+    for (int it = 0; it < 10; ++it) {
+        if (sp_dot3(s, s) < eps * eps || cnt == 0) break;
+        uint32_t best = 0;
+        T best_dot = sp_dot3(sp_plane<T>(nrm, 0), s);
+        for (uint32_t k = 1; k < cnt; ++k) {
+            const T d = sp_dot3(sp_plane<T>(nrm, k), s);
+            if (!(sp_total_key(best_dot) > sp_total_key(d))) { best_dot = d; best = k; }   // the last maximum
+        }
+        if (best_dot <= eps) break;
+        const V3<T> n = sp_plane<T>(nrm, best);
+        if (cone == 0) {
+            const T d = sp_dot3(n, x0);
+            s = V3<T>{x0.x - d * n.x, x0.y - d * n.y, x0.z - d * n.z};
+            n1 = n; cone = 1;
+        } else if (cone == 1) {
+            const V3<T> c = sp_cross3(n, n1);
+            const T d = sp_dot3(x0, c), cc = sp_dot3(c, c);
+            s = V3<T>{d * c.x / cc, d * c.y / cc, d * c.z / cc};
+            if (d > T(0)) { n2 = n1; n1 = n; } else n2 = n;
+            cone = 2;
+        } else {
+            const V3<T> c1 = sp_cross3(n1, n);
+            const T q1 = sp_dot3(c1, c1), d1 = sp_dot3(x0, c1);
+            const V3<T> c2 = sp_cross3(n, n2);
+            const T q2 = sp_dot3(c2, c2), d2 = sp_dot3(x0, c2);
+            if (d1 <= T(0) && d2 <= T(0)) { s = vzero<T>(); break; }   // inside the solid wedge
+            if (d1 * fabs_t(d1) * q2 > d2 * fabs_t(d2) * q1) { n2 = n; s = V3<T>{d1 * c1.x / q1, d1 * c1.y / q1, d1 * c1.z / q1}; }
+            else { n1 = n; s = V3<T>{d2 * c2.x / q2, d2 * c2.y / q2, d2 * c2.z / q2}; }
+        }
+    }
+    return V3<T>{-s.x, -s.y, -s.z};
+}
+
+template <class T>
+__global__ __launch_bounds__(SP_WAVE) void k_sp_project_velocity(SV<T> p) {
+    const uint32_t qi = blockIdx.x * SP_WAVE + threadIdx.x;
+    if (qi >= p.n) return;
+    const V3<T> v{p.velocity[3 * (size_t)qi], p.velocity[3 * (size_t)qi + 1], p.velocity[3 * (size_t)qi + 2]};
+    const uint32_t c = p.count[qi];
+    const V3<T> r = sp_project_velocity<T>(v, p.normals + (size_t)qi * p.stride * 3, c < p.stride ? c : p.stride);
+    p.out[3 * (size_t)qi] = r.x; p.out[3 * (size_t)qi + 1] = r.y; p.out[3 * (size_t)qi + 2] = r.z;
+}
+
+template <class T> __device__ __forceinline__ void sp_put_move(SpatialMoveHit<T>& h, uint32_t c, uint32_t e, T safe, T dist, V3<T> p1, V3<T> p2, V3<T> n1) {
+    h.collider = c; h.entity = e; h.distance = safe; h.collision_distance = dist;
+    h.point1[0] = p1.x; h.point1[1] = p1.y; h.point1[2] = p1.z;
+    h.point2[0] = p2.x; h.point2[1] = p2.y; h.point2[2] = p2.z;
+    h.normal1[0] = n1.x; h.normal1[1] = n1.y; h.normal1[2] = n1.z;
+    h.normal2[0] = n1.x == T(0) ? T(0) : -n1.x; h.normal2[1] = n1.y == T(0) ? T(0) : -n1.y; h.normal2[2] = n1.z == T(0) ? T(0) : -n1.z;
+}
+
+// MoveAndSlide::cast_move in two launches.  k_sp_cast_move is k_sp_cast's closest-hit traversal over the ordinary hits; a collider that
+// overlaps the query at the start is only noted in the query's pending list.  k_sp_cast_move_resolve, one lane per query and no traversal,
+// applies the origin-penetration rule to the pending colliders with the narrow phase's contact_manifolds_pair_sink, merges them with the
+// traversal's hit by (distance, collider index) and pulls the distance back.  The contact manifold so stays out of the traversal's live
+// range (fused into the leaf the kernel needed 256 VGPRs + 13 / 72 AGPRs, one wave per SIMD: profiles/spatial_moves_resource_usage.txt).
+template <class T>
+__global__ __launch_bounds__(SP_WAVE) void k_sp_cast_move(SP<T> sp, SM<T> m) {
+    __shared__ uint32_t stack[SP_STACK * SP_WAVE];
+    const SQ<T>& q = m.q;
+    const uint32_t lane = threadIdx.x;
+    const uint32_t qi = blockIdx.x * SP_WAVE + lane;
+    uint32_t nodes_tested = 0, leaves_tested = 0, overflow = 0;
+    const uint32_t n = sp.n;
+    if (qi < q.n) {
+        const uint32_t mask = q.mask ? q.mask[qi] : 0xFFFFFFFFu;
+        const uint32_t self = m.self_entity ? m.self_entity[qi] : AVN_SPATIAL_MISS;
+        const uint32_t shape2 = q.shape[qi];
+        const V3<T> pos2{q.a[3 * (size_t)qi], q.a[3 * (size_t)qi + 1], q.a[3 * (size_t)qi + 2]};
+        const V3<T> mv{m.movement[3 * (size_t)qi], m.movement[3 * (size_t)qi + 1], m.movement[3 * (size_t)qi + 2]};
+        V3<T> he2{q.he[3 * (size_t)qi], q.he[3 * (size_t)qi + 1], q.he[3 * (size_t)qi + 2]};
+        const Q4<T> rot2{q.rot[4 * (size_t)qi], q.rot[4 * (size_t)qi + 1], q.rot[4 * (size_t)qi + 2], q.rot[4 * (size_t)qi + 3]};
+        const T skin = m.skin ? m.skin[qi] : m.skin_all;
+        if (shape2 == AVN_SHAPE_BALL) he2 = V3<T>{he2.x, he2.x, he2.x};
+        // k_sp_shapes' rule, plus a finite movement and a skin width that is finite and not negative; a slide's finished character: a miss
+        bool valid = shape2 <= AVN_SHAPE_BALL && is_finite(pos2) && is_finite(V3<T>{rot2.x, rot2.y, rot2.z}) && finite_t(rot2.w) && is_finite(he2) &&
+                     he2.x >= T(0) && he2.y >= T(0) && he2.z >= T(0) && is_finite(mv) && finite_t(skin) && skin >= T(0) &&
+                     (!m.state || (m.state[qi] & SP_SLIDE_LIVE));
+        V3<T> d{T(1), T(0), T(0)};
+        T dist = T(0);
+        if (valid && !sp_dir_and_length<T>(mv, d, dist)) { d = V3<T>{T(1), T(0), T(0)}; dist = T(0); }
+        RayCtx<T> r;
+        r.o = r.d = r.inv = vzero<T>(); r.zero = 0; r.tol = T(0);
+        V3<T> hw = vzero<T>();
+        Iso<T> iso2{Q4<T>{T(0), T(0), T(0), T(1)}, pos2};
+        if (valid) {
+            V3<T> a, b;
+            shape_aabb<T>(shape2, he2, pos2, rot2, a, b);
+            valid = is_finite(a) && is_finite(b);
+            const T pad = T(64) * Limits<T>::eps * smax(sp_maxabs(a), sp_maxabs(b));
+            const V3<T> pp{pad, pad, pad};
+            const V3<T> qmin = a - pp, qmax = b + pp;
+            r.o = (qmin + qmax) * T(0.5);
+            hw = (qmax - qmin) * T(0.5);
+            r.d = d;
+            r.inv = V3<T>{d.x != T(0) ? T(1) / d.x : T(0), d.y != T(0) ? T(1) / d.y : T(0), d.z != T(0) ? T(1) / d.z : T(0)};
+            r.zero = (d.x == T(0) ? 1u : 0u) | (d.y == T(0) ? 2u : 0u) | (d.z == T(0) ? 4u : 0u);
+            r.tol = T(64) * Limits<T>::eps * sp_maxabs(r.o);
+            iso2 = make_isometry(pos2, rot2);
+        }
+        T best = sp_inf<T>();
+        uint32_t best_c = AVN_SPATIAL_MISS;
+        V3<T> best_p1 = vzero<T>(), best_p2 = vzero<T>(), best_n1 = vzero<T>();
+        uint32_t n_pending = 0;
+        uint32_t* pend = m.pending + (size_t)qi * AVN_SPATIAL_MAX_HITS;
+        auto test = [&](uint32_t node) -> T {
+            ++nodes_tested;
+            const Vec4<T> lo = sp.bmin[node], hi = sp.bmax[node];
+            return sp_ray_box(r, make4<T>(lo.x - hw.x, lo.y - hw.y, lo.z - hw.z, T(0)), make4<T>(hi.x + hw.x, hi.y + hw.y, hi.z + hw.z, T(0)), smin(best, dist));
+        };
+        auto leaf = [&](uint32_t node) {
+            const uint32_t c = sp.leaf_col[node - (n - 1)];
+            const uint4 info = sp.info[c];
+            if (!info.w || (info.w & SP_INFO_SENSOR) || (info.y & mask) == 0u || (self != AVN_SPATIAL_MISS && info.x == self) ||
+                (q.n_excluded && sp_excluded(q.excluded, q.n_excluded, info.x))) return;
+            ++leaves_tested;
+            const V3<T> pos1 = xyz<T>(sp.pos[c]), he1 = xyz<T>(sp.he[c]);
+            const Q4<T> rot1 = quat<T>(sp.rot[c]);
+            T toi; V3<T> p1, p2, n1;
+            if (!sp_cast_exact<T>(shape2, he2, iso2, d, dist, info.z, he1, pos1, rot1, toi, p1, p2, n1)) return;
+            if (toi == T(0) && n1.x == T(0) && n1.y == T(0) && n1.z == T(0)) {
+                // overlapping at the start: the pair's contact decides, in k_sp_cast_move_resolve
+                if (n_pending < AVN_SPATIAL_MAX_HITS) pend[n_pending] = c;
+                else overflow |= 2u;
+                ++n_pending;
+                return;
+            }
+            if (toi < best || (toi == best && c < best_c)) { best = toi; best_c = c; best_p1 = p1; best_p2 = p2; best_n1 = n1; }
+        };
+        if (valid && n >= 1 && test(0) != sp_inf<T>()) {
+            uint32_t sp_top = 0, node = 0;
+            for (;;) {
+                uint2 ch = make_uint2(0u, 0u);
+                T e0 = T(0), e1 = sp_inf<T>();
+                if (n > 1) { ch = sp.child[node]; e0 = test(ch.x); e1 = test(ch.y); }
+                const bool l0 = ch.x >= n - 1, l1 = ch.y >= n - 1;
+                // one leaf call site: the pair tests are emitted once
+                uint32_t pending = (l0 && e0 != sp_inf<T>() ? 1u : 0u) | (l1 && e1 != sp_inf<T>() ? 2u : 0u);
+                while (pending) {
+                    const bool first = (pending & 1u) != 0;
+                    if (first || !(e1 > best)) leaf(first ? ch.x : ch.y);
+                    pending &= first ? ~1u : ~2u;
+                }
+                const bool g0 = !l0 && e0 != sp_inf<T>() && !(e0 > best), g1 = !l1 && e1 != sp_inf<T>() && !(e1 > best);
+                if (g0 && g1) {
+                    const bool first0 = !(e1 < e0);
+                    if (sp_top < SP_STACK) { stack[sp_top * SP_WAVE + lane] = first0 ? ch.y : ch.x; ++sp_top; }
+                    else overflow = 1;   // (cannot happen: the depth of the tree is at most 64)
+                    node = first0 ? ch.x : ch.y;
+                    continue;
+                }
+                if (g0) { node = ch.x; continue; }
+                if (g1) { node = ch.y; continue; }
+                node = AVN_SPATIAL_MISS;
+                while (sp_top > 0) {
+                    --sp_top;
+                    const uint32_t cand = stack[sp_top * SP_WAVE + lane];
+                    if (test(cand) != sp_inf<T>()) { node = cand; break; }
+                }
+                if (node == AVN_SPATIAL_MISS) break;
+            }
+        }
+        // the traversal's own answer (the hit's distance, not yet pulled back) and the pending count: k_sp_cast_move_resolve finishes the record
+        SpatialMoveHit<T> h;
+        if (best_c == AVN_SPATIAL_MISS) sp_put_move<T>(h, AVN_SPATIAL_MISS, AVN_SPATIAL_MISS, T(0), T(0), vzero<T>(), vzero<T>(), vzero<T>());
+        else sp_put_move<T>(h, best_c, sp.info[best_c].x, best, dist, best_p1, best_p2, best_n1);
+        m.out[qi] = h;
+        m.pending_count[qi] = n_pending;
+    }
+    uint32_t a = nodes_tested, b = leaves_tested, o = overflow;
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) { a += __shfl_xor(a, off); b += __shfl_xor(b, off); o |= __shfl_xor(o, off); }
+    if (lane == 0) {
+        atomicAdd(&q.stats[0], (unsigned long long)a);
+        atomicAdd(&q.stats[1], (unsigned long long)b);
+        if (o) atomicOr(&q.stats[2], (unsigned long long)o);   // bit 0: stack overflow; bit 1: more than AVN_SPATIAL_MAX_HITS pending colliders
+    }
+}
+
+template <class T>
+__global__ __launch_bounds__(SP_WAVE) void k_sp_cast_move_resolve(SP<T> sp, SM<T> m) {
+    const SQ<T>& q = m.q;
+    const uint32_t qi = blockIdx.x * SP_WAVE + threadIdx.x;
+    if (qi >= q.n) return;
+    SpatialMoveHit<T> h = m.out[qi];
+    const uint32_t count = m.pending_count[qi];
+    const uint32_t np = count < AVN_SPATIAL_MAX_HITS ? count : AVN_SPATIAL_MAX_HITS;
+    if (h.collider == AVN_SPATIAL_MISS && np == 0) return;   // a miss, an invalid query, a slide's finished character: the record stands
+    const uint32_t shape2 = q.shape[qi];
+    const V3<T> pos2{q.a[3 * (size_t)qi], q.a[3 * (size_t)qi + 1], q.a[3 * (size_t)qi + 2]};
+    const V3<T> mv{m.movement[3 * (size_t)qi], m.movement[3 * (size_t)qi + 1], m.movement[3 * (size_t)qi + 2]};
+    V3<T> he2{q.he[3 * (size_t)qi], q.he[3 * (size_t)qi + 1], q.he[3 * (size_t)qi + 2]};
+    const Q4<T> rot2{q.rot[4 * (size_t)qi], q.rot[4 * (size_t)qi + 1], q.rot[4 * (size_t)qi + 2], q.rot[4 * (size_t)qi + 3]};
+    const T skin = m.skin ? m.skin[qi] : m.skin_all;
+    if (shape2 == AVN_SHAPE_BALL) he2 = V3<T>{he2.x, he2.x, he2.x};
+    V3<T> d{T(1), T(0), T(0)};
+    T dist = T(0);
+    if (!sp_dir_and_length<T>(mv, d, dist)) { d = V3<T>{T(1), T(0), T(0)}; dist = T(0); }
+    T best = h.collider == AVN_SPATIAL_MISS ? sp_inf<T>() : h.distance;
+    uint32_t best_c = h.collider, best_e = h.entity;
+    V3<T> best_p1{h.point1[0], h.point1[1], h.point1[2]}, best_p2{h.point2[0], h.point2[1], h.point2[2]}, best_n1{h.normal1[0], h.normal1[1], h.normal1[2]};
+    const uint32_t* pend = m.pending + (size_t)qi * AVN_SPATIAL_MAX_HITS;
+    for (uint32_t k = 0; k < np; ++k) {
+        const uint32_t c = pend[k];
+        // a hit at distance 0 only matters when it beats the best by (distance, collider index)
+        if (!(T(0) < best || (best == T(0) && c < best_c))) continue;
+        const uint4 info = sp.info[c];
+        const V3<T> pos1 = xyz<T>(sp.pos[c]), he1 = xyz<T>(sp.he[c]);
+        const Q4<T> rot1 = quat<T>(sp.rot[c]);
+        // the pair's contact at prediction 0, the query as shape 1
+        V3<T> p1 = vzero<T>(), p2 = vzero<T>(), n1 = vzero<T>();
+        SpDeepestSink<T> sink{vzero<T>(), T(0), 0};
+        V3<T> nrm;
+        if (contact_manifolds_pair_sink<T, SpDeepestSink<T>>(shape2, he2, pos2, rot2, info.z, he1, pos1, rot1, T(0), sink, nrm)) {
+            const V3<T> cn{-nrm.x, -nrm.y, -nrm.z};
+            if (d.x * cn.x + d.y * cn.y + d.z * cn.z >= T(0)) continue;   // on its way out: ignored by this cast
+            const V3<T> a1 = sink.anchor1, a2 = a1 + (pos2 - pos1);
+            n1 = cn; p1 = pos1 + a2; p2 = pos2 + a1;
+        }
+        best = T(0); best_c = c; best_e = info.x; best_p1 = p1; best_p2 = p2; best_n1 = n1;
+    }
+    if (best_c == AVN_SPATIAL_MISS) return;   // every pending collider was ignored and nothing else was hit: the miss stands
+    // pull_back: at least skin_width away from the hit along the movement
+    T safe = T(0);
+    if (dist != T(0)) {
+        const T dp = d.x * (-best_n1.x) + d.y * (-best_n1.y) + d.z * (-best_n1.z);
+        const T dm = dp > T(0.005) ? dp : T(0.005);
+        const T x = best - skin / dm;
+        safe = x > T(0) ? x : T(0);
+    }
+    sp_put_move<T>(h, best_c, best_e, safe, dist, best_p1, best_p2, best_n1);
+    m.out[qi] = h;
+}
+
+template <class T> __device__ __forceinline__ void sp_log_hit(const SL<T>& l, uint32_t qi, uint32_t collider, uint32_t entity, uint32_t kind, V3<T> point, V3<T> normal, T distance, T collision_distance) {
+    const uint32_t k = l.hit_count[qi];
+    l.hit_count[qi] = k + 1;
+    if (k >= l.hit_cap) return;
+    SpatialSlideHit<T> h;
+    h.collider = collider; h.entity = entity; h.iteration = l.iteration; h.kind = kind;
+    h.point[0] = point.x; h.point[1] = point.y; h.point[2] = point.z;
+    h.normal[0] = normal.x; h.normal[1] = normal.y; h.normal[2] = normal.z;
+    h.distance = distance; h.collision_distance = collision_distance;
+    l.hits[(size_t)qi * l.hit_cap + k] = h;
+}
+
+// The phases of MoveAndSlide::move_and_slide (move_and_slide.rs:475-608) between the traversal launches, one lane per character over the state
+// the world keeps.  A finished character is inert: its flags lose SP_SLIDE_LIVE, k_sp_cast_move answers it a miss and its prediction distance
+// is NaN, so k_sp_contacts answers it count 0, both without traversing.
+template <class T, int PHASE>
+__global__ __launch_bounds__(SP_WAVE) void k_sp_slide(SL<T> l) {
+    const uint32_t qi = blockIdx.x * SP_WAVE + threadIdx.x;
+    if (qi >= l.n) return;
+    const size_t q3 = 3 * (size_t)qi;
+    if (PHASE == SPL_BEGIN) {
+        const uint32_t shape = l.shape[qi];
+        const V3<T> pos{l.pos_in[q3], l.pos_in[q3 + 1], l.pos_in[q3 + 2]};
+        V3<T> he{l.he[q3], l.he[q3 + 1], l.he[q3 + 2]};
+        const Q4<T> rot{l.rot[4 * (size_t)qi], l.rot[4 * (size_t)qi + 1], l.rot[4 * (size_t)qi + 2], l.rot[4 * (size_t)qi + 3]};
+        if (shape == AVN_SHAPE_BALL) he = V3<T>{he.x, he.x, he.x};
+        bool valid = shape <= AVN_SHAPE_BALL && is_finite(pos) && is_finite(V3<T>{rot.x, rot.y, rot.z}) && finite_t(rot.w) && is_finite(he) && he.x >= T(0) && he.y >= T(0) && he.z >= T(0);
+        if (valid) {
+            V3<T> a, b;
+            shape_aabb<T>(shape, he, pos, rot, a, b);
+            valid = is_finite(a) && is_finite(b);
+        }
+        for (int i = 0; i < 3; ++i) { l.pos[q3 + i] = l.pos_in[q3 + i]; l.vel[q3 + i] = l.vel_in[q3 + i]; l.movement[q3 + i] = T(0); }
+        l.time_left[qi] = l.delta_time;
+        l.flags[qi] = valid ? (SP_SLIDE_VALID | SP_SLIDE_LIVE) : 0u;
+        l.iters[qi] = 0u; l.hit_count[qi] = 0u; l.plane_count[qi] = 0u;
+        l.pred[qi] = T(0);
+        return;
+    }
+    const uint32_t flags = l.flags[qi];
+    if (PHASE == SPL_DEPENETRATE) {
+        // position += depenetrate_intersections over the contacts of the launch before (k_sp_depenetrate's loop)
+        if (!(flags & SP_SLIDE_VALID)) return;
+        V3<T> fixup = vzero<T>();
+        if (l.depen_iterations) {
+            const uint32_t count = l.count[qi];
+            const uint32_t m = count < AVN_SPATIAL_MAX_HITS ? count : AVN_SPATIAL_MAX_HITS;
+            if (count > AVN_SPATIAL_MAX_HITS) l.flags[qi] = flags | SP_SLIDE_TRUNCATED;
+            const SpatialShapeContact<T>* rl = l.rec + (size_t)qi * AVN_SPATIAL_MAX_HITS;
+            uint32_t it = 0;
+            while (it < l.depen_iterations) {
+                ++it;
+                T total_error = T(0);
+                for (uint32_t k = 0; k < m; ++k) {
+                    const T dist = rl[k].penetration + l.skin;
+                    if (dist > l.rejection) continue;
+                    const V3<T> nv{sp_dir_round(rl[k].normal[0]), sp_dir_round(rl[k].normal[1]), sp_dir_round(rl[k].normal[2])};
+                    const T diff = dist - (fixup.x * nv.x + fixup.y * nv.y + fixup.z * nv.z);
+                    const T error = diff > T(0) ? diff : T(0);
+                    total_error += error;
+                    fixup = V3<T>{fixup.x + error * nv.x, fixup.y + error * nv.y, fixup.z + error * nv.z};
+                }
+                if (total_error < l.max_error) break;
+            }
+        }
+        l.pos[q3] += fixup.x; l.pos[q3 + 1] += fixup.y; l.pos[q3 + 2] += fixup.z;
+        return;
+    }
+    if (PHASE == SPL_END) {
+        SpatialSlide<T> r;
+        for (int i = 0; i < 3; ++i) { r.position[i] = l.pos[q3 + i]; r.velocity[i] = l.vel[q3 + i]; }
+        r.iterations_run = l.iters[qi]; r.hit_count = l.hit_count[qi]; r.flags = (flags & SP_SLIDE_TRUNCATED) ? 1u : 0u;
+        sp_clear_reserved(r);
+        l.out[qi] = r;
+        SpatialSlideHit<T> miss;
+        miss.collider = AVN_SPATIAL_MISS; miss.entity = AVN_SPATIAL_MISS; miss.iteration = 0u; miss.kind = 0u;
+        for (int i = 0; i < 3; ++i) miss.point[i] = miss.normal[i] = T(0);
+        miss.distance = miss.collision_distance = T(0);
+        for (uint32_t k = r.hit_count; k < l.hit_cap; ++k) l.hits[(size_t)qi * l.hit_cap + k] = miss;
+        return;
+    }
+    if (!(flags & SP_SLIDE_LIVE)) {
+        if (PHASE == SPL_ADVANCE) l.pred[qi] = __builtin_nan("");   // inert: the contacts launch answers count 0 without traversing
+        return;
+    }
+    const V3<T> vel{l.vel[q3], l.vel[q3 + 1], l.vel[q3 + 2]};
+    if (PHASE == SPL_SWEEP) {
+        const T tl = l.time_left[qi];
+        const V3<T> sweep{tl * vel.x, tl * vel.y, tl * vel.z};
+        V3<T> dir; T dist;
+        l.movement[q3] = sweep.x; l.movement[q3 + 1] = sweep.y; l.movement[q3 + 2] = sweep.z;
+        if (!sp_dir_and_length<T>(sweep, dir, dist) || dist < T(1e-4)) { l.flags[qi] = flags & ~SP_SLIDE_LIVE; return; }
+        l.iters[qi] += 1u;
+        return;
+    }
+    if (PHASE == SPL_ADVANCE) {
+        const SpatialMoveHit<T> h = l.mh[qi];
+        const V3<T> sweep{l.movement[q3], l.movement[q3 + 1], l.movement[q3 + 2]};
+        const V3<T> pos{l.pos[q3], l.pos[q3 + 1], l.pos[q3 + 2]};
+        if (h.collider == AVN_SPATIAL_MISS) {
+            // no collision: the full distance, and the loop ends
+            l.pos[q3] = pos.x + sweep.x; l.pos[q3 + 1] = pos.y + sweep.y; l.pos[q3 + 2] = pos.z + sweep.z;
+            l.flags[qi] = flags & ~SP_SLIDE_LIVE;
+            l.pred[qi] = __builtin_nan("");
+            return;
+        }
+        V3<T> dir; T dist;
+        (void)sp_dir_and_length<T>(sweep, dir, dist);   // (valid: SPL_SWEEP checked it)
+        const V3<T> point{h.point2[0] + pos.x, h.point2[1] + pos.y, h.point2[2] + pos.z};
+        const T tl = l.time_left[qi];
+        l.time_left[qi] = tl - tl * (h.distance / dist);
+        l.pos[q3] = pos.x + dir.x * h.distance; l.pos[q3 + 1] = pos.y + dir.y * h.distance; l.pos[q3 + 2] = pos.z + dir.z * h.distance;
+        float* pl = l.planes + (size_t)qi * SP_SLIDE_PLANES * 3;
+        for (uint32_t k = 0; k < 3 * l.n_planes; ++k) pl[k] = l.cfg_planes[k];
+        const float nx = (float)h.normal1[0], ny = (float)h.normal1[1], nz = (float)h.normal1[2];
+        sp_log_hit<T>(l, qi, h.collider, h.entity, 0u, point, V3<T>{(T)nx, (T)ny, (T)nz}, h.distance, h.collision_distance);
+        pl[3 * l.n_planes] = nx; pl[3 * l.n_planes + 1] = ny; pl[3 * l.n_planes + 2] = nz;
+        l.plane_count[qi] = l.n_planes + 1;
+        l.pred[qi] = l.skin * T(2);
+        return;
+    }
+    if (PHASE == SPL_PLANES) {
+        const uint32_t count = l.count[qi];
+        const uint32_t m = count < AVN_SPATIAL_MAX_HITS ? count : AVN_SPATIAL_MAX_HITS;
+        if (count > AVN_SPATIAL_MAX_HITS) l.flags[qi] = flags | SP_SLIDE_TRUNCATED;
+        const SpatialShapeContact<T>* rl = l.rec + (size_t)qi * AVN_SPATIAL_MAX_HITS;
+        float* pl = l.planes + (size_t)qi * SP_SLIDE_PLANES * 3;
+        uint32_t np = l.plane_count[qi];
+        const T safe = l.mh[qi].distance, cd = l.mh[qi].collision_distance;
+        for (uint32_t k = 0; k < m; ++k) {
+            const float nx = (float)rl[k].normal[0], ny = (float)rl[k].normal[1], nz = (float)rl[k].normal[2];
+            const V3<T> nv{(T)nx, (T)ny, (T)nz};
+            bool similar = false;
+            for (uint32_t e = 0; e < np && !similar; ++e) {
+                const float ex = pl[3 * e], ey = pl[3 * e + 1], ez = pl[3 * e + 2];
+                if ((T)(nx * ex + ny * ey + nz * ez) >= l.threshold) {
+                    // keep the more blocking version of the plane
+                    if (sp_dot3(nv, vel) < sp_dot3(V3<T>{(T)ex, (T)ey, (T)ez}, vel)) { pl[3 * e] = nx; pl[3 * e + 1] = ny; pl[3 * e + 2] = nz; }
+                    similar = true;
+                }
+            }
+            if (similar || np >= l.max_planes) continue;
+            sp_log_hit<T>(l, qi, rl[k].collider, rl[k].entity, 1u, V3<T>{rl[k].point[0], rl[k].point[1], rl[k].point[2]}, nv, safe, cd);
+            pl[3 * np] = nx; pl[3 * np + 1] = ny; pl[3 * np + 2] = nz;
+            ++np;
+        }
+        l.plane_count[qi] = np;
+        const V3<T> pv = sp_project_velocity<T>(vel, pl, np);
+        l.vel[q3] = pv.x; l.vel[q3 + 1] = pv.y; l.vel[q3 + 2] = pv.z;
+    }
+}
+
+template <class T> void launch_spatial_project_velocity(const SV<T>& p, hipStream_t s) {
+    if (p.n == 0) return;
+    hipLaunchKernelGGL((k_sp_project_velocity<T>), dim3((p.n + SP_WAVE - 1) / SP_WAVE), dim3(SP_WAVE), 0, s, p);
+}
+template <class T> void launch_spatial_cast_move(const SP<T>& sp, const SM<T>& m, bool zero_stats, hipStream_t s) {
+    if (zero_stats) (void)hipMemsetAsync(m.q.stats, 0, 4 * sizeof(unsigned long long), s);
+    if (m.q.n == 0) return;
+    hipLaunchKernelGGL((k_sp_cast_move<T>), dim3((m.q.n + SP_WAVE - 1) / SP_WAVE), dim3(SP_WAVE), 0, s, sp, m);
+    hipLaunchKernelGGL((k_sp_cast_move_resolve<T>), dim3((m.q.n + SP_WAVE - 1) / SP_WAVE), dim3(SP_WAVE), 0, s, sp, m);
+}
+template <class T> void launch_spatial_slide_phase(const SL<T>& l, int phase, hipStream_t s) {
+    if (l.n == 0) return;
+    const dim3 g((l.n + SP_WAVE - 1) / SP_WAVE), b(SP_WAVE);
+    switch (phase) {
+        case SPL_BEGIN: hipLaunchKernelGGL((k_sp_slide<T, SPL_BEGIN>), g, b, 0, s, l); break;
+        case SPL_DEPENETRATE: hipLaunchKernelGGL((k_sp_slide<T, SPL_DEPENETRATE>), g, b, 0, s, l); break;
+        case SPL_SWEEP: hipLaunchKernelGGL((k_sp_slide<T, SPL_SWEEP>), g, b, 0, s, l); break;
+        case SPL_ADVANCE: hipLaunchKernelGGL((k_sp_slide<T, SPL_ADVANCE>), g, b, 0, s, l); break;
+        case SPL_PLANES: hipLaunchKernelGGL((k_sp_slide<T, SPL_PLANES>), g, b, 0, s, l); break;
+        default: hipLaunchKernelGGL((k_sp_slide<T, SPL_END>), g, b, 0, s, l); break;
+    }
 }
 
 template <class T> void launch_spatial_query(const SP<T>& sp, const SQ<T>& q, int kind, hipStream_t s) {
@@ -1324,12 +1766,35 @@ static_assert(sizeof(SpatialDepenetration<float>) == sizeof(avn_spatial_depenetr
               sizeof(avn_spatial_depenetration_f32) == 24 && sizeof(avn_spatial_depenetration_f64) == 40 &&
               offsetof(SpatialDepenetration<float>, truncated) == offsetof(avn_spatial_depenetration_f32, truncated) && offsetof(SpatialDepenetration<double>, truncated) == offsetof(avn_spatial_depenetration_f64, truncated),
               "depenetration record layout");
+static_assert(sizeof(SpatialMoveHit<float>) == sizeof(avn_spatial_move_hit_f32) && sizeof(SpatialMoveHit<double>) == sizeof(avn_spatial_move_hit_f64) &&
+              sizeof(avn_spatial_move_hit_f32) == 64 && sizeof(avn_spatial_move_hit_f64) == 120 &&
+              offsetof(SpatialMoveHit<float>, collision_distance) == offsetof(avn_spatial_move_hit_f32, collision_distance) && offsetof(SpatialMoveHit<double>, collision_distance) == offsetof(avn_spatial_move_hit_f64, collision_distance) &&
+              offsetof(SpatialMoveHit<float>, point2) == offsetof(avn_spatial_move_hit_f32, point2) && offsetof(SpatialMoveHit<double>, point2) == offsetof(avn_spatial_move_hit_f64, point2) &&
+              offsetof(SpatialMoveHit<float>, normal2) == offsetof(avn_spatial_move_hit_f32, normal2) && offsetof(SpatialMoveHit<double>, normal2) == offsetof(avn_spatial_move_hit_f64, normal2),
+              "move hit record layout");
+static_assert(sizeof(SpatialSlideHit<float>) == sizeof(avn_spatial_slide_hit_f32) && sizeof(SpatialSlideHit<double>) == sizeof(avn_spatial_slide_hit_f64) &&
+              sizeof(avn_spatial_slide_hit_f32) == 48 && sizeof(avn_spatial_slide_hit_f64) == 80 &&
+              offsetof(SpatialSlideHit<float>, point) == offsetof(avn_spatial_slide_hit_f32, point) && offsetof(SpatialSlideHit<double>, point) == offsetof(avn_spatial_slide_hit_f64, point) &&
+              offsetof(SpatialSlideHit<float>, collision_distance) == offsetof(avn_spatial_slide_hit_f32, collision_distance) && offsetof(SpatialSlideHit<double>, collision_distance) == offsetof(avn_spatial_slide_hit_f64, collision_distance),
+              "slide hit record layout");
+static_assert(sizeof(SpatialSlide<float>) == sizeof(avn_spatial_slide_f32) && sizeof(SpatialSlide<double>) == sizeof(avn_spatial_slide_f64) &&
+              sizeof(avn_spatial_slide_f32) == 36 && sizeof(avn_spatial_slide_f64) == 64 &&
+              offsetof(SpatialSlide<float>, flags) == offsetof(avn_spatial_slide_f32, flags) && offsetof(SpatialSlide<double>, flags) == offsetof(avn_spatial_slide_f64, flags) &&
+              offsetof(SpatialSlide<double>, reserved) == offsetof(avn_spatial_slide_f64, reserved),
+              "slide record layout");
+static_assert(SP_SLIDE_PLANES >= AVN_SPATIAL_MAX_PLANES + 1, "plane slots");
 template void launch_spatial_build<float>(const DW<float>&, const BP<float>&, const SP<float>&, hipStream_t);
 template void launch_spatial_build<double>(const DW<double>&, const BP<double>&, const SP<double>&, hipStream_t);
 template void launch_spatial_query<float>(const SP<float>&, const SQ<float>&, int, hipStream_t);
 template void launch_spatial_query<double>(const SP<double>&, const SQ<double>&, int, hipStream_t);
-template void launch_spatial_contacts<float>(const SP<float>&, const SC<float>&, hipStream_t);
-template void launch_spatial_contacts<double>(const SP<double>&, const SC<double>&, hipStream_t);
+template void launch_spatial_contacts<float>(const SP<float>&, const SC<float>&, hipStream_t, bool);
+template void launch_spatial_contacts<double>(const SP<double>&, const SC<double>&, hipStream_t, bool);
+template void launch_spatial_project_velocity<float>(const SV<float>&, hipStream_t);
+template void launch_spatial_project_velocity<double>(const SV<double>&, hipStream_t);
+template void launch_spatial_cast_move<float>(const SP<float>&, const SM<float>&, bool, hipStream_t);
+template void launch_spatial_cast_move<double>(const SP<double>&, const SM<double>&, bool, hipStream_t);
+template void launch_spatial_slide_phase<float>(const SL<float>&, int, hipStream_t);
+template void launch_spatial_slide_phase<double>(const SL<double>&, int, hipStream_t);
 template void launch_spatial_depenetrate<float>(const SD<float>&, hipStream_t);
 template void launch_spatial_depenetrate<double>(const SD<double>&, hipStream_t);
 

@@ -5,7 +5,9 @@
     SP<T> sp{};
     DevBuf b_sp_pos, b_sp_rot, b_sp_he, b_sp_info, b_sp_smin, b_sp_smax, b_sp_bmin, b_sp_bmax, b_sp_child, b_sp_parent, b_sp_leaf, b_sp_arr, b_sp_bounds,
         b_sp_keys_a, b_sp_vals_a, b_sp_keys_b, b_sp_vals_b, b_sp_hist, b_sp_block_sums, b_sp_stats,
-        b_sp_crec, b_sp_ccount;   // depenetrate's contact records [n * AVN_SPATIAL_MAX_HITS] and counts [n]
+        b_sp_crec, b_sp_ccount,   // depenetrate's contact records [n * AVN_SPATIAL_MAX_HITS] and counts [n]
+        b_sl_pos, b_sl_vel, b_sl_time, b_sl_move, b_sl_pred, b_sl_flags, b_sl_iters, b_sl_hits, b_sl_nplanes, b_sl_planes, b_sl_cfg, b_sl_mh,   // move_and_slide's per-character state
+        b_mv_pend, b_mv_pcount;   // cast_move's hand-over: the colliders overlapping each query at its start [n * AVN_SPATIAL_MAX_HITS], their counts [n]
     uint32_t sp_cap = 0;
     bool sp_valid = false;      // a snapshot exists and no table changed since (bodies / colliders / collider transforms uploads and avn_despawn clear it)
     uint32_t sp_host = 0;       // AVN_SHAPE_HOST colliders in the snapshot
@@ -82,6 +84,7 @@
     avn_status sp_finish() {
         HIPCHK(hipMemcpyAsync(sp_visits, b_sp_stats.p, sizeof sp_visits, hipMemcpyDeviceToHost, stream));
         HIPCHK(hipStreamSynchronize(stream));
+        if (sp_visits[2] & 2ull) { error = "spatial query: a move overlaps more than AVN_SPATIAL_MAX_HITS colliders at its start"; return AVN_ERR_CAPACITY; }
         if (sp_visits[2]) { error = "spatial query: traversal stack overflow"; return AVN_ERR_CAPACITY; }
         return AVN_OK;
     }
@@ -327,6 +330,130 @@
             HIPCHK(hipGetLastError());
         }
         if (!dev && (st = stage_out<SpatialDepenetration<T>>(out->depenetration, d_out, n)) != AVN_OK) return st;
+        return sp_finish();
+    }
+    // project_velocity per query: no snapshot, no traversal
+    avn_status spatial_project_velocities(const avn_spatial_velocity_projections* p, const avn_spatial_velocities_out* out) override {
+        if (!p || !out) { error = "spatial_project_velocities: null argument"; return AVN_ERR_BAD_ARG; }
+        const uint32_t n = p->count;
+        if (p->stride > AVN_SPATIAL_MAX_PLANES) { error = "spatial_project_velocities: stride above AVN_SPATIAL_MAX_PLANES"; return AVN_ERR_BAD_ARG; }
+        if (n && (!p->velocity || !p->normal_count || !out->velocity || (p->stride && !p->normals))) { error = "spatial_project_velocities: null array"; return AVN_ERR_BAD_ARG; }
+        const bool dev = (p->flags & AVN_SPATIAL_DEVICE_POINTERS) != 0;
+        const size_t n_nrm = (size_t)n * p->stride * 3;
+        avn_status st;
+        if ((st = stage_reserve(sp_stage_bytes(dev, n, al(3 * sizeof(T) * n) + al(n_nrm * 4), al(3 * sizeof(T) * n), 0))) != AVN_OK) return st;
+        SV<T> v{};
+        v.n = n; v.stride = p->stride;
+        if ((st = sp_in<T>(p->velocity, 3 * (size_t)n, dev, &v.velocity)) != AVN_OK) return st;
+        if ((st = sp_in<float>(p->normals, n_nrm, dev, &v.normals)) != AVN_OK) return st;
+        if ((st = sp_in<uint32_t>(p->normal_count, n, dev, &v.count)) != AVN_OK) return st;
+        v.out = sp_out<T>(out->velocity, 3 * (size_t)n, dev);
+        launch_spatial_project_velocity<T>(v, stream);
+        HIPCHK(hipGetLastError());
+        if (!dev && (st = stage_out<T>(out->velocity, v.out, 3 * (size_t)n)) != AVN_OK) return st;
+        HIPCHK(hipStreamSynchronize(stream));
+        return AVN_OK;
+    }
+    // MoveAndSlide::cast_move per move
+    avn_status spatial_cast_moves(const avn_spatial_moves* s, const avn_spatial_move_hits_out* out) override {
+        if (!s || !out) { error = "spatial_cast_moves: null argument"; return AVN_ERR_BAD_ARG; }
+        const uint32_t n = s->count;
+        if (n && (!s->shape || !s->half_extents || !s->position || !s->rotation || !s->movement || !s->skin_width || !out->hits)) { error = "spatial_cast_moves: null array"; return AVN_ERR_BAD_ARG; }
+        avn_status st = sp_check(s->flags);
+        if (st != AVN_OK) return st;
+        const bool dev = (s->flags & AVN_SPATIAL_DEVICE_POINTERS) != 0;
+        std::vector<uint32_t> ex;
+        if ((st = sp_excluded(s->filter, dev, ex)) != AVN_OK) return st;
+        if ((st = stage_reserve(sp_stage_bytes(dev, n, 3 * al(3 * sizeof(T) * n) + al(4 * sizeof(T) * n) + al(sizeof(T) * n) + al(n) + al(4 * (size_t)n), al((size_t)n * sizeof(SpatialMoveHit<T>)), ex.size()))) != AVN_OK) return st;
+        SC<T> sc{};   // (the shared staging of the query-shape fields)
+        if ((st = sp_contact_inputs(sc, n, dev, s->shape, s->half_extents, s->position, s->rotation, s->filter, ex)) != AVN_OK) return st;
+        SM<T> m{};
+        m.q = sc.q;
+        if ((st = sp_in<T>(s->movement, 3 * (size_t)n, dev, &m.movement)) != AVN_OK) return st;
+        if ((st = sp_in<T>(s->skin_width, n, dev, &m.skin)) != AVN_OK) return st;
+        if ((st = sp_in<uint32_t>(s->self_entity, n, dev, &m.self_entity)) != AVN_OK) return st;
+        m.out = sp_out<SpatialMoveHit<T>>(out->hits, n, dev);
+        bool moved = false;
+        GROW(b_mv_pend, std::max<size_t>((size_t)n * AVN_SPATIAL_MAX_HITS, 1), m.pending);
+        GROW(b_mv_pcount, std::max<size_t>(n, 1), m.pending_count);
+        launch_spatial_cast_move<T>(sp, m, true, stream);
+        HIPCHK(hipGetLastError());
+        if (!dev && (st = stage_out<SpatialMoveHit<T>>(out->hits, m.out, n)) != AVN_OK) return st;
+        return sp_finish();
+    }
+    // MoveAndSlide::move_and_slide per character: a fixed sequence of launches over the state buffers, no read-back inside the loop
+    avn_status spatial_move_and_slide(const avn_spatial_characters* s, const avn_spatial_move_and_slide_config* cfg, uint32_t hit_cap, const avn_spatial_slides_out* out) override {
+        if (!s || !cfg || !out) { error = "spatial_move_and_slide: null argument"; return AVN_ERR_BAD_ARG; }
+        const uint32_t n = s->count;
+        if (cfg->n_planes > AVN_SPATIAL_MAX_PLANES || cfg->max_planes > AVN_SPATIAL_MAX_PLANES || cfg->move_and_slide_iterations > AVN_SPATIAL_MAX_SLIDE_ITERATIONS ||
+            hit_cap > AVN_SPATIAL_MAX_HITS || (cfg->n_planes && !cfg->planes)) {
+            error = "spatial_move_and_slide: n_planes / max_planes above AVN_SPATIAL_MAX_PLANES, iterations above AVN_SPATIAL_MAX_SLIDE_ITERATIONS, hit_cap above AVN_SPATIAL_MAX_HITS or planes NULL";
+            return AVN_ERR_BAD_ARG;
+        }
+        if (n && (!s->shape || !s->half_extents || !s->position || !s->rotation || !s->velocity || !out->slides || (hit_cap && !out->hits))) { error = "spatial_move_and_slide: null array"; return AVN_ERR_BAD_ARG; }
+        avn_status st = sp_check(s->flags);
+        if (st != AVN_OK) return st;
+        const bool dev = (s->flags & AVN_SPATIAL_DEVICE_POINTERS) != 0;
+        std::vector<uint32_t> ex;
+        if ((st = sp_excluded(s->filter, dev, ex)) != AVN_OK) return st;
+        const size_t n_hits = (size_t)n * hit_cap;
+        if ((st = stage_reserve(sp_stage_bytes(dev, n, 3 * al(3 * sizeof(T) * n) + al(4 * sizeof(T) * n) + al(n) + al(4 * (size_t)n),
+                                               al((size_t)n * sizeof(SpatialSlide<T>)) + al(n_hits * sizeof(SpatialSlideHit<T>)), ex.size()))) != AVN_OK) return st;
+        SC<T> sc{};
+        if ((st = sp_contact_inputs(sc, n, dev, s->shape, s->half_extents, s->position, s->rotation, s->filter, ex)) != AVN_OK) return st;
+        SL<T> l{};
+        l.n = n; l.hit_cap = hit_cap; l.n_planes = cfg->n_planes; l.max_planes = cfg->max_planes; l.depen_iterations = cfg->depenetration_iterations;
+        l.shape = sc.q.shape; l.he = sc.q.he; l.pos_in = sc.q.a; l.rot = sc.q.rot;
+        if ((st = sp_in<T>(s->velocity, 3 * (size_t)n, dev, &l.vel_in)) != AVN_OK) return st;
+        const uint32_t* self = nullptr;
+        if ((st = sp_in<uint32_t>(s->self_entity, n, dev, &self)) != AVN_OK) return st;
+        l.out = sp_out<SpatialSlide<T>>(out->slides, n, dev);
+        l.hits = n_hits ? sp_out<SpatialSlideHit<T>>(out->hits, n_hits, dev) : nullptr;
+        bool moved = false;
+        const size_t nn = std::max<size_t>(n, 1);
+        uint32_t* d_count;
+        SpatialMoveHit<T>* d_mh;
+        float* d_cfg_planes;
+        GROW(b_sp_crec, nn * AVN_SPATIAL_MAX_HITS, sc.rec);
+        GROW(b_sp_ccount, nn, d_count);
+        GROW(b_sl_pos, 3 * nn, l.pos); GROW(b_sl_vel, 3 * nn, l.vel); GROW(b_sl_time, nn, l.time_left); GROW(b_sl_move, 3 * nn, l.movement); GROW(b_sl_pred, nn, l.pred);
+        GROW(b_sl_flags, nn, l.flags); GROW(b_sl_iters, nn, l.iters); GROW(b_sl_hits, nn, l.hit_count); GROW(b_sl_nplanes, nn, l.plane_count);
+        GROW(b_sl_planes, nn * SP_SLIDE_PLANES * 3, l.planes); GROW(b_sl_cfg, 3 * AVN_SPATIAL_MAX_PLANES, d_cfg_planes); GROW(b_sl_mh, nn, d_mh);
+        if (cfg->n_planes) HIPCHK(hipMemcpyAsync(d_cfg_planes, cfg->planes, (size_t)cfg->n_planes * 3 * sizeof(float), hipMemcpyHostToDevice, stream));
+        l.cfg_planes = d_cfg_planes;
+        l.delta_time = (T)cfg->delta_time; l.skin = (T)cfg->skin_width; l.threshold = (T)cfg->plane_similarity_dot_threshold;
+        l.max_error = (T)cfg->max_depenetration_error; l.rejection = (T)cfg->penetration_rejection_threshold;
+        l.rec = sc.rec; l.count = d_count; l.mh = d_mh;
+        // the sub-queries read the state: positions from l.pos, never sensors, never the character's own entity
+        sc.q.a = l.pos; sc.q.cap = AVN_SPATIAL_MAX_HITS; sc.q.count = d_count;
+        sc.skip_sensors = 1u; sc.pad_unused = 0u; sc.self_entity = self;
+        SM<T> m{};
+        GROW(b_mv_pend, nn * AVN_SPATIAL_MAX_HITS, m.pending);
+        GROW(b_mv_pcount, nn, m.pending_count);
+        m.q = sc.q; m.movement = l.movement; m.skin = nullptr; m.skin_all = l.skin; m.self_entity = self; m.state = l.flags; m.out = d_mh;
+        HIPCHK(hipMemsetAsync(b_sp_stats.p, 0, 4 * sizeof(unsigned long long), stream));
+        auto depenetrate = [&]() {
+            if (cfg->depenetration_iterations) { sc.prediction = nullptr; sc.prediction_all = l.skin; launch_spatial_contacts<T>(sp, sc, stream, false); }
+            launch_spatial_slide_phase<T>(l, SPL_DEPENETRATE, stream);
+        };
+        launch_spatial_slide_phase<T>(l, SPL_BEGIN, stream);
+        depenetrate();
+        for (uint32_t it = 0; it < cfg->move_and_slide_iterations; ++it) {
+            l.iteration = it;
+            launch_spatial_slide_phase<T>(l, SPL_SWEEP, stream);
+            launch_spatial_cast_move<T>(sp, m, false, stream);
+            launch_spatial_slide_phase<T>(l, SPL_ADVANCE, stream);
+            sc.prediction = l.pred;
+            launch_spatial_contacts<T>(sp, sc, stream, false);
+            launch_spatial_slide_phase<T>(l, SPL_PLANES, stream);
+        }
+        depenetrate();
+        launch_spatial_slide_phase<T>(l, SPL_END, stream);
+        HIPCHK(hipGetLastError());
+        if (!dev) {
+            if ((st = stage_out<SpatialSlide<T>>(out->slides, l.out, n)) != AVN_OK) return st;
+            if ((st = stage_out<SpatialSlideHit<T>>(out->hits, l.hits, n_hits)) != AVN_OK) return st;
+        }
         return sp_finish();
     }
     avn_status spatial_stats_get(avn_spatial_stats* o) override {

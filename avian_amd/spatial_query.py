@@ -1,5 +1,5 @@
 """ctypes binding of ``include/avian_mi355x_spatial.h``: device spatial queries (ray casts, ray hits, point and AABB intersections, point
-projection, shape intersections, shape casts, shape contacts and depenetration) over the
+projection, shape intersections, shape casts, shape contacts, depenetration, velocity projection, cast_move and move_and_slide) over the
 colliders a :class:`avian_amd._ffi.World` holds on the device.
 
 Numpy arrays in and out (copied through the library's staging), or torch tensors on the world's GPU (``AVN_SPATIAL_DEVICE_POINTERS``: the
@@ -19,6 +19,9 @@ DEVICE_POINTERS = 1
 SKIP_HOST_SHAPES = 2
 SKIP_SENSORS = 4      # shape_contacts / depenetrate only
 MAX_HITS = 64
+MAX_PLANES = 32
+MAX_SLIDE_ITERATIONS = 16
+SLIDE_TRUNCATED = 1
 MISS = 0xFFFFFFFF
 
 
@@ -99,6 +102,67 @@ class avn_spatial_depenetrations_out(C.Structure):
     _fields_ = [("depenetration", vp)]
 
 
+class avn_spatial_velocity_projections(C.Structure):
+    _fields_ = [("count", C.c_uint32), ("flags", C.c_uint32), ("stride", C.c_uint32), ("velocity", vp), ("normals", vp), ("normal_count", vp)]
+
+
+class avn_spatial_velocities_out(C.Structure):
+    _fields_ = [("velocity", vp)]
+
+
+class avn_spatial_moves(C.Structure):
+    _fields_ = [("count", C.c_uint32), ("flags", C.c_uint32), ("shape", vp), ("half_extents", vp), ("position", vp), ("rotation", vp),
+                ("movement", vp), ("skin_width", vp), ("self_entity", vp), ("filter", avn_spatial_filter)]
+
+
+class avn_spatial_move_hit_f32(C.Structure):
+    _fields_ = [("collider", C.c_uint32), ("entity", C.c_uint32), ("distance", C.c_float), ("collision_distance", C.c_float), ("point1", C.c_float * 3),
+                ("point2", C.c_float * 3), ("normal1", C.c_float * 3), ("normal2", C.c_float * 3)]
+
+
+class avn_spatial_move_hit_f64(C.Structure):
+    _fields_ = [("collider", C.c_uint32), ("entity", C.c_uint32), ("distance", C.c_double), ("collision_distance", C.c_double), ("point1", C.c_double * 3),
+                ("point2", C.c_double * 3), ("normal1", C.c_double * 3), ("normal2", C.c_double * 3)]
+
+
+class avn_spatial_move_hits_out(C.Structure):
+    _fields_ = [("hits", vp)]
+
+
+class avn_spatial_characters(C.Structure):
+    _fields_ = [("count", C.c_uint32), ("flags", C.c_uint32), ("shape", vp), ("half_extents", vp), ("position", vp), ("rotation", vp),
+                ("velocity", vp), ("self_entity", vp), ("filter", avn_spatial_filter)]
+
+
+class avn_spatial_move_and_slide_config(C.Structure):
+    _fields_ = [("delta_time", C.c_double), ("skin_width", C.c_double), ("max_depenetration_error", C.c_double), ("penetration_rejection_threshold", C.c_double),
+                ("plane_similarity_dot_threshold", C.c_double), ("planes", vp), ("n_planes", C.c_uint32), ("max_planes", C.c_uint32),
+                ("move_and_slide_iterations", C.c_uint32), ("depenetration_iterations", C.c_uint32)]
+
+
+class avn_spatial_slide_f32(C.Structure):
+    _fields_ = [("position", C.c_float * 3), ("projected_velocity", C.c_float * 3), ("iterations_run", C.c_uint32), ("hit_count", C.c_uint32), ("flags", C.c_uint32)]
+
+
+class avn_spatial_slide_f64(C.Structure):
+    _fields_ = [("position", C.c_double * 3), ("projected_velocity", C.c_double * 3), ("iterations_run", C.c_uint32), ("hit_count", C.c_uint32), ("flags", C.c_uint32),
+                ("reserved", C.c_uint32)]
+
+
+class avn_spatial_slide_hit_f32(C.Structure):
+    _fields_ = [("collider", C.c_uint32), ("entity", C.c_uint32), ("iteration", C.c_uint32), ("kind", C.c_uint32), ("point", C.c_float * 3), ("normal", C.c_float * 3),
+                ("distance", C.c_float), ("collision_distance", C.c_float)]
+
+
+class avn_spatial_slide_hit_f64(C.Structure):
+    _fields_ = [("collider", C.c_uint32), ("entity", C.c_uint32), ("iteration", C.c_uint32), ("kind", C.c_uint32), ("point", C.c_double * 3), ("normal", C.c_double * 3),
+                ("distance", C.c_double), ("collision_distance", C.c_double)]
+
+
+class avn_spatial_slides_out(C.Structure):
+    _fields_ = [("slides", vp), ("hits", vp)]
+
+
 class avn_spatial_shape_hits_out(C.Structure):
     _fields_ = [("hits", vp), ("count", vp)]
 
@@ -141,10 +205,14 @@ STRUCTS = [avn_spatial_filter, avn_spatial_rays, avn_spatial_points, avn_spatial
            avn_spatial_projection_f32, avn_spatial_projection_f64, avn_spatial_projections_out, avn_spatial_shape_casts,
            avn_spatial_shape_hit_f32, avn_spatial_shape_hit_f64, avn_spatial_shape_hits_out, avn_spatial_shape_contact_queries,
            avn_spatial_shape_contact_f32, avn_spatial_shape_contact_f64, avn_spatial_shape_contacts_out, avn_spatial_depenetration_config,
-           avn_spatial_depenetration_f32, avn_spatial_depenetration_f64, avn_spatial_depenetrations_out]
+           avn_spatial_depenetration_f32, avn_spatial_depenetration_f64, avn_spatial_depenetrations_out, avn_spatial_velocity_projections,
+           avn_spatial_velocities_out, avn_spatial_moves, avn_spatial_move_hit_f32, avn_spatial_move_hit_f64, avn_spatial_move_hits_out,
+           avn_spatial_characters, avn_spatial_move_and_slide_config, avn_spatial_slide_f32, avn_spatial_slide_f64, avn_spatial_slide_hit_f32,
+           avn_spatial_slide_hit_f64, avn_spatial_slides_out]
 SYMBOLS = ["avn_spatial_update", "avn_spatial_cast_rays", "avn_spatial_ray_hits", "avn_spatial_point_intersections",
            "avn_spatial_aabb_intersections", "avn_spatial_stats_get", "avn_spatial_project_points", "avn_spatial_shape_intersections",
-           "avn_spatial_cast_shapes", "avn_spatial_shape_hits", "avn_spatial_shape_contacts", "avn_spatial_depenetrate"]
+           "avn_spatial_cast_shapes", "avn_spatial_shape_hits", "avn_spatial_shape_contacts", "avn_spatial_depenetrate", "avn_spatial_project_velocities",
+           "avn_spatial_cast_moves", "avn_spatial_move_and_slide"]
 
 
 def hit_dtype(bits: int) -> np.dtype:
@@ -181,6 +249,27 @@ def depenetration_dtype(bits: int) -> np.dtype:
     return np.dtype(f + ([("reserved", np.uint32)] if bits == 64 else []), align=True)
 
 
+def move_hit_dtype(bits: int) -> np.dtype:
+    """numpy mirror of avn_spatial_move_hit_fNN (64 / 120 bytes, no padding)."""
+    s = np.float32 if bits == 32 else np.float64
+    return np.dtype([("collider", np.uint32), ("entity", np.uint32), ("distance", s), ("collision_distance", s), ("point1", s, (3,)), ("point2", s, (3,)),
+                     ("normal1", s, (3,)), ("normal2", s, (3,))], align=True)
+
+
+def slide_dtype(bits: int) -> np.dtype:
+    """numpy mirror of avn_spatial_slide_fNN (36 / 64 bytes; f64: a reserved word at the end, always 0)."""
+    s = np.float32 if bits == 32 else np.float64
+    f = [("position", s, (3,)), ("projected_velocity", s, (3,)), ("iterations_run", np.uint32), ("hit_count", np.uint32), ("flags", np.uint32)]
+    return np.dtype(f + ([("reserved", np.uint32)] if bits == 64 else []), align=True)
+
+
+def slide_hit_dtype(bits: int) -> np.dtype:
+    """numpy mirror of avn_spatial_slide_hit_fNN (48 / 80 bytes, no padding)."""
+    s = np.float32 if bits == 32 else np.float64
+    return np.dtype([("collider", np.uint32), ("entity", np.uint32), ("iteration", np.uint32), ("kind", np.uint32), ("point", s, (3,)), ("normal", s, (3,)),
+                     ("distance", s), ("collision_distance", s)], align=True)
+
+
 def _declare(dll):
     for name in SYMBOLS:
         getattr(dll, name).restype = C.c_int32
@@ -196,6 +285,9 @@ def _declare(dll):
     dll.avn_spatial_shape_hits.argtypes = [vp, vp, C.c_uint32, vp]
     dll.avn_spatial_shape_contacts.argtypes = [vp, vp, C.c_uint32, vp]
     dll.avn_spatial_depenetrate.argtypes = [vp, vp, vp, vp]
+    dll.avn_spatial_project_velocities.argtypes = [vp, vp, vp]
+    dll.avn_spatial_cast_moves.argtypes = [vp, vp, vp]
+    dll.avn_spatial_move_and_slide.argtypes = [vp, vp, vp, C.c_uint32, vp]
 
 
 class SpatialQuery:
@@ -219,6 +311,9 @@ class SpatialQuery:
         self.shape_hit_dtype = shape_hit_dtype(self.bits)
         self.shape_contact_dtype = shape_contact_dtype(self.bits)
         self.depenetration_dtype = depenetration_dtype(self.bits)
+        self.move_hit_dtype = move_hit_dtype(self.bits)
+        self.slide_dtype = slide_dtype(self.bits)
+        self.slide_hit_dtype = slide_hit_dtype(self.bits)
         self._keep = []
 
     # -- plumbing ------------------------------------------------------------------------------
@@ -253,7 +348,7 @@ class SpatialQuery:
             if isinstance(dt, np.dtype):   # a record: bytes
                 t = torch.empty(tuple(shape) + (dt.itemsize,), dtype=torch.uint8, device=like.device)
             else:
-                t = torch.empty(shape, dtype={np.uint32: torch.int32}[dt], device=like.device)
+                t = torch.empty(shape, dtype={np.uint32: torch.int32, np.float32: torch.float32, np.float64: torch.float64}[dt], device=like.device)
             return t, vp(t.data_ptr())
         x = np.empty(shape, dt)
         return x, x.ctypes.data_as(vp)
@@ -471,6 +566,82 @@ class SpatialQuery:
         self._sync_torch(dev)
         self._check(self.dll.avn_spatial_depenetrate(self.world.handle, C.byref(q), C.byref(cfg), C.byref(o)))
         return rec
+
+    def project_velocities(self, velocity, normals, normal_count=None):
+        """project_velocity (velocity_project.rs) per query: ``velocity`` [n, 3] in the world's dtype, ``normals`` [n, stride, 3] float32 unit
+        vectors (Dir is f32), ``normal_count`` [n] (default: stride).  Returns the projected velocities [n, 3].  Needs no snapshot."""
+        dev = self._is_tensor(velocity)
+        n = int(velocity.shape[0])
+        stride = int(normals.shape[1]) if n else 0
+        p = avn_spatial_velocity_projections()
+        p.count = n
+        p.flags = self._flags(dev, False)
+        p.stride = stride
+        p.velocity = self._arr(velocity, self.dtype, dev, (n, 3))
+        p.normals = self._arr(normals, np.float32, dev, (n, stride, 3)) if stride else None
+        if normal_count is None:
+            normal_count = np.full(n, stride, np.uint32) if not dev else velocity.new_full((n,), stride)
+        p.normal_count = self._arr(normal_count, np.uint32, dev, (n,))
+        res, rp = self._out((n, 3), self.dtype, dev, velocity)
+        o = avn_spatial_velocities_out(rp)
+        self._sync_torch(dev)
+        self._check(self.dll.avn_spatial_project_velocities(self.world.handle, C.byref(p), C.byref(o)))
+        return res
+
+    def cast_moves(self, shape, half_extents, position, rotation, movement, skin_width, self_entity=None, mask=None, excluded=None, skip_host_shapes=False):
+        """MoveAndSlide::cast_move per move: a structured array of ``move_hit_dtype`` records (collider == MISS: the way is free).  ``skin_width``
+        is a scalar or [n]; ``self_entity`` [n] is the entity each query never hits (MISS: none).  Device tensors in: a uint8 tensor
+        [n, itemsize] out."""
+        dev = self._is_tensor(position)
+        n = int(position.shape[0])
+        q = avn_spatial_moves()
+        q.count = n
+        q.flags = self._flags(dev, skip_host_shapes)
+        q.shape = self._arr(shape, np.uint8, dev, (n,))
+        q.half_extents = self._arr(half_extents, self.dtype, dev, (n, 3))
+        q.position = self._arr(position, self.dtype, dev, (n, 3))
+        q.rotation = self._arr(rotation, self.dtype, dev, (n, 4))
+        q.movement = self._arr(movement, self.dtype, dev, (n, 3))
+        if not self._is_tensor(skin_width) and np.ndim(skin_width) == 0:
+            skin_width = np.full(n, skin_width) if not dev else position.new_full((n,), float(skin_width))
+        q.skin_width = self._arr(skin_width, self.dtype, dev, (n,))
+        q.self_entity = self._arr(self_entity, np.uint32, dev, (n,)) if self_entity is not None else None
+        q.filter = self._filter(n, mask, excluded, dev)
+        rec, rp = self._out((n,), self.move_hit_dtype, dev, position)
+        o = avn_spatial_move_hits_out(rp)
+        self._sync_torch(dev)
+        self._check(self.dll.avn_spatial_cast_moves(self.world.handle, C.byref(q), C.byref(o)))
+        return rec
+
+    def move_and_slide(self, shape, half_extents, position, rotation, velocity, delta_time, skin_width, max_depenetration_error,
+                       penetration_rejection_threshold, depenetration_iterations, move_and_slide_iterations=4, max_planes=20,
+                       plane_similarity_dot_threshold=0.999, planes=None, hit_cap=0, self_entity=None, mask=None, excluded=None, skip_host_shapes=False):
+        """MoveAndSlide::move_and_slide per character: (``slide_dtype`` records [n], ``slide_hit_dtype`` records [n, hit_cap]: what on_hit would
+        have been called with).  ``planes`` [k, 3] float32 are the configuration's initial planes, shared by the call.  The caller applies
+        PhysicsLengthUnit to the configuration.  Device tensors in: uint8 tensors [n, itemsize] and [n, hit_cap, itemsize] out."""
+        dev = self._is_tensor(position)
+        n = int(position.shape[0])
+        q = avn_spatial_characters()
+        q.count = n
+        q.flags = self._flags(dev, skip_host_shapes)
+        q.shape = self._arr(shape, np.uint8, dev, (n,))
+        q.half_extents = self._arr(half_extents, self.dtype, dev, (n, 3))
+        q.position = self._arr(position, self.dtype, dev, (n, 3))
+        q.rotation = self._arr(rotation, self.dtype, dev, (n, 4))
+        q.velocity = self._arr(velocity, self.dtype, dev, (n, 3))
+        q.self_entity = self._arr(self_entity, np.uint32, dev, (n,)) if self_entity is not None else None
+        q.filter = self._filter(n, mask, excluded, dev)
+        pl = np.ascontiguousarray(np.zeros((0, 3)) if planes is None else planes, dtype=np.float32).reshape(-1, 3)   # (host memory, always)
+        self._keep.append(pl)
+        cfg = avn_spatial_move_and_slide_config(float(delta_time), float(skin_width), float(max_depenetration_error), float(penetration_rejection_threshold),
+                                                float(plane_similarity_dot_threshold), pl.ctypes.data_as(vp) if len(pl) else None, len(pl), int(max_planes),
+                                                int(move_and_slide_iterations), int(depenetration_iterations))
+        rec, rp = self._out((n,), self.slide_dtype, dev, position)
+        hits, hp = self._out((n, int(hit_cap)), self.slide_hit_dtype, dev, position)
+        o = avn_spatial_slides_out(rp, hp if hit_cap else None)
+        self._sync_torch(dev)
+        self._check(self.dll.avn_spatial_move_and_slide(self.world.handle, C.byref(q), C.byref(cfg), int(hit_cap), C.byref(o)))
+        return rec, hits
 
     def stats(self) -> avn_spatial_stats:
         s = avn_spatial_stats()

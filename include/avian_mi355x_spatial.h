@@ -1,8 +1,8 @@
 /*
  * avian_mi355x_spatial.h — device spatial queries: ray casts, point and AABB intersections, point projection, shape intersections and shape
  * casts against the colliders the world holds in HBM: every query family of SpatialQueryPipeline, for the shapes with device geometry (Ball,
- * Cuboid); plus the stateless half of the kinematic character controller (MoveAndSlide::intersections / depenetrate): shape contacts and
- * depenetration.
+ * Cuboid); plus the kinematic character controller (character_controller/move_and_slide.rs): shape contacts and depenetration
+ * (MoveAndSlide::intersections / depenetrate), project_velocity, cast_move and the move_and_slide loop.
  *
  * Mirrors Avian's `SpatialQueryPlugin` (spatial_query/mod.rs:190-212), whose systems run in `PhysicsStepSystems::SpatialQuery` right after
  * `Sleeping` (schedule/mod.rs:98-105): `update_spatial_query_pipeline` rebuilds a BVH of every collider from `Position` / `Rotation`
@@ -90,8 +90,8 @@
  *      all three: the shapes overlapping at the start answer distance 0 with points and normals 0 (the convention of a solid ray's normal);
  *      a hit needs a finite distance <= max_distance; normal1 = rot_c n, point1 / point2 in world space through rot_c and pos_c (a cuboid
  *      cast at a ball: through the query's isometry at pos_q + d t), normal2 = -normal1 with a zero component staying +0.
- *    NOT covered: target_distance != 0, ignore_origin_penetration, compute_contact_on_penetration = true, predicates
- *    (cast_shape_predicate), casts against AVN_SHAPE_HOST colliders, Rust declarations.
+ *    NOT covered: target_distance != 0, compute_contact_on_penetration = true, predicates (cast_shape_predicate) other than cast_move's,
+ *    casts against AVN_SHAPE_HOST colliders, Rust declarations.  (ignore_origin_penetration: avn_spatial_cast_moves, below.)
  *  - shape contacts (MoveAndSlide::intersections, character_controller/move_and_slide.rs:1032-1078).  Per query shape at its pose with a
  *    prediction distance p, collider c contributes ONE contact iff all of (a)-(d) hold, evaluated in this order:
  *      (a) c is a candidate and passes the filter (with AVN_SPATIAL_SKIP_SENSORS: and is not a sensor).
@@ -118,8 +118,57 @@
  *      max_depenetration_error.  iterations_run counts the passes started.  Avian hands the normal over as a Dir, which is f32: in an f64
  *      world every component of n is rounded through float before use (the contact records keep the full-precision normal).  The caller
  *      applies PhysicsLengthUnit to max_depenetration_error and penetration_rejection_threshold.
- *    NOT covered: cast_move, ignore_origin_penetration, the move_and_slide loop, project_velocity, query shapes other than Ball / Cuboid,
- *    contacts against AVN_SHAPE_HOST colliders, predicates, Rust declarations.
+ *    NOT covered: query shapes other than Ball / Cuboid, contacts against AVN_SHAPE_HOST colliders, predicates, Rust declarations.
+ *  - move and slide (MoveAndSlide::cast_move, project_velocity, move_and_slide; move_and_slide.rs:464-793, velocity_project.rs).  As above the
+ *    definitions are written out here with their operation order (no FMA contraction); parity with glam / parry is UNPINNED.  Common rules:
+ *      Sensors are never candidates (MoveAndSlide's collider query is Without<Sensor>; cast_move's predicate enforces it for the cast too).
+ *      self_entity [n]: a collider whose entity_index equals the query's self_entity is not a candidate of that query (NULL or
+ *        AVN_SPATIAL_MISS: none); the call's shared mask / excluded list still apply.
+ *      A Dir is f32, in an f64 world too: it is normalised or rounded in float and widened where the reference calls adjust_precision.
+ *        D(v) = Dir::new_and_length(v as f32): x, y, z = the components rounded to float; len = sqrt(x*x + y*y + z*z) in float, left to
+ *        right; valid iff len is finite and > 0; the direction is (x / len, y / len, z / len), the length is len widened.
+ *      Rust's a.max(b) is a > b ? a : b with the constant as b (a NaN gives the constant).  DOT_EPSILON = 0.005, MIN_DISTANCE = 1e-4, in the
+ *        world's scalar.  dot(a, b) = a.x*b.x + a.y*b.y + a.z*b.z, cross(a, b) = (a.y*b.z - b.y*a.z, a.z*b.x - b.z*a.x, a.x*b.y - b.x*a.y).
+ *    project_velocity(v, normals) = -C(-v) per component (a fully blocked velocity comes out with -0.0 components), C = project_onto_conical_hull:
+ *      x0 = -v, s = x0, cone = Origin; at most 10 rounds of: stop when dot(s, s) < DOT_EPSILON * DOT_EPSILON or there are no normals; the best
+ *      normal is the LAST maximum of dot(n_k, s) under total_cmp (n_k widened; a fold from k = 0 that takes k whenever the best is not
+ *      greater under the total order, where -0 < +0); stop when best_dot <= DOT_EPSILON; then with n the best normal
+ *        Origin: d = dot(n, x0), s = x0 - d * n per component, cone = Ray(n).
+ *        Ray(p): c = cross(n, p), d = dot(x0, c), s = d * c / dot(c, c) per component; cone = d > 0 ? Wedge(n, p) : Wedge(p, n).
+ *        Wedge(n1, n2): c1 = cross(n1, n), q1 = dot(c1, c1), d1 = dot(x0, c1); c2 = cross(n, n2), q2 = dot(c2, c2), d2 = dot(x0, c2);
+ *          d1 <= 0 && d2 <= 0: s = +0 and the iteration ends; else if d1 * |d1| * q2 > d2 * |d2| * q1: cone = Wedge(n1, n), s = d1 * c1 / q1;
+ *          else cone = Wedge(n, n2), s = d2 * c2 / q2.
+ *      A non-finite velocity, or a non-finite normal among the first normal_count, answers the input velocity unchanged.  A normal_count
+ *      above `stride` is read as `stride`.
+ *    cast_move(shape at position / rotation, movement, skin_width): (dir, dist) = D(movement), or ((1, 0, 0), 0) when that is not valid.  The
+ *      cast is the shape cast above along dir (widened) with max_distance = dist over the candidates (not sensors, not self_entity), with
+ *      Avian's ignore_origin_penetration = true as this ORIGIN-PENETRATION RULE: a collider whose pair test reports overlap at the start
+ *      (distance 0 with normal1 = 0) takes the shape contact of the pair, steps (c) and (d) above at prediction 0 with the query as shape 1.
+ *      With a contact, n = -manifold.normal (from the collider towards the query): when dir.x*n.x + dir.y*n.y + dir.z*n.z >= 0 (the
+ *      character is on its way out) the collider is ignored by this cast; otherwise it is a hit at distance 0 with normal1 = n, point1 =
+ *      collider position + anchor2, point2 = query position + anchor1 (the contact record's `point`).  Without a contact (e.g. a ball's
+ *      centre inside a cuboid) it is a hit at distance 0 with points and normals 0.  The answer is the smallest (distance, collider index)
+ *      over those and the ordinary hits; normal2 = -normal1 with a zero component staying +0.  Then
+ *        distance = dist == 0 ? 0 : max(hit.distance - skin_width / max(dot(dir, -normal1), DOT_EPSILON), 0)   (the safe distance)
+ *        collision_distance = dist: the reference stores the movement's length there, not the hit's distance; this library keeps that.
+ *      A non-finite movement, a skin_width that is NaN, infinite or negative, or an invalid query shape answers a miss.
+ *    move_and_slide, per character (move_and_slide.rs:475-608): position, velocity = the inputs, time_left = delta_time;
+ *      position += depenetrate(position) (the depenetration above with AVN_SPATIAL_SKIP_SENSORS and self_entity; depenetration_iterations =
+ *      0: a zero offset is added).  Then up to move_and_slide_iterations rounds: sweep = time_left * velocity per component; (dir, dist) =
+ *      D(sweep), not valid: stop; dist < MIN_DISTANCE: stop; hit = cast_move(position, sweep, skin_width) (iterations_run counts these
+ *      casts), a miss: position += sweep, stop.  point = hit.point2 + position (the position before the move: the reference adds them and so
+ *      does this library); time_left -= time_left * (hit.distance / dist); position += dir * hit.distance per component.  planes = the
+ *      configuration's, then hit.normal1 rounded to float (logged as kind 0; not deduplicated).  The shape contacts of the new position at
+ *      prediction 2 * skin_width in ascending collider index (the first AVN_SPATIAL_MAX_HITS; more sets flag bit 0), each with its normal n
+ *      rounded to float: the first existing plane e with (float dot(n, e)) widened >= plane_similarity_dot_threshold is replaced by n when
+ *      dot(n, velocity) < dot(e, velocity) (both widened) and the contact is done; otherwise, while fewer than max_planes planes exist, it
+ *      is logged (kind 1: the contact's own collider and entity -- the reference passes the sweep's entity: a stated strengthening -- its
+ *      point, n, the sweep's distance and collision_distance) and pushed.  on_hit is taken as `true`; a full plane list does not stop the
+ *      loop over the contacts (nor does the reference's).  velocity = project_velocity(velocity, planes).  After the rounds: position +=
+ *      depenetrate(position).  A character whose query shape is invalid or whose position is not finite answers its input position and
+ *      velocity with zero counts.  The hit log holds the first hit_cap records in call order; hit_count is the true number; unused slots
+ *      are misses (collider and entity AVN_SPATIAL_MISS, the rest 0).
+ *    NOT covered: on_hit callbacks that change position / velocity or return false, 2D, Rust declarations.
  *
  * Non-finite inputs (NaN or inf components):
  *  - a collider whose snapshot position, rotation or shape AABB is not finite is never a candidate (it keeps its collider index);
@@ -172,7 +221,8 @@ enum {
                                           the caller's writes to them must be complete before the call */
     AVN_SPATIAL_SKIP_HOST_SHAPES = 2,  /* AVN_SHAPE_HOST colliders are never candidates (else their presence is AVN_ERR_STATE) */
     AVN_SPATIAL_SKIP_SENSORS = 4       /* avn_spatial_shape_contacts / avn_spatial_depenetrate only: AVN_COLLIDER_SENSOR colliders are never
-                                          candidates (MoveAndSlide's Without<Sensor>); the other queries ignore the flag */
+                                          candidates (MoveAndSlide's Without<Sensor>); the other queries ignore the flag
+                                          (avn_spatial_cast_moves / avn_spatial_move_and_slide never see sensors, flag or not) */
 };
 #define AVN_SPATIAL_MAX_HITS 64        /* largest max_hits of avn_spatial_ray_hits / avn_spatial_shape_hits, largest cap of avn_spatial_shape_contacts */
 #define AVN_SPATIAL_MISS 0xFFFFFFFFu   /* collider index of a miss */
@@ -359,6 +409,122 @@ typedef struct avn_spatial_depenetrations_out {
     void* depenetration; /* avn_spatial_depenetration_fNN [n] */
 } avn_spatial_depenetrations_out;
 
+/* project_velocity (velocity_project.rs) per query: no snapshot is needed */
+#define AVN_SPATIAL_MAX_PLANES 32
+typedef struct avn_spatial_velocity_projections {
+    uint32_t count;              /* n */
+    uint32_t flags;              /* AVN_SPATIAL_DEVICE_POINTERS */
+    uint32_t stride;             /* normals per query in `normals`, <= AVN_SPATIAL_MAX_PLANES */
+    const void* velocity;        /* [3n] the world's scalar */
+    const float* normals;        /* [n * stride * 3] unit (Dir is f32) */
+    const uint32_t* normal_count;/* [n] each <= stride */
+} avn_spatial_velocity_projections;
+typedef struct avn_spatial_velocities_out {
+    void* velocity;              /* [3n] */
+} avn_spatial_velocities_out;
+
+/* the moves of avn_spatial_cast_moves: the fields of avn_spatial_shapes plus a movement, a skin width and the character's own entity */
+typedef struct avn_spatial_moves {
+    uint32_t count;
+    uint32_t flags;
+    const uint8_t* shape;        /* [n] AVN_SHAPE_CUBOID / AVN_SHAPE_BALL */
+    const void* half_extents;    /* [3n] (ball: radius in x) */
+    const void* position;        /* [3n] */
+    const void* rotation;        /* [4n] xyzw, unit */
+    const void* movement;        /* [3n] direction and length of the move */
+    const void* skin_width;      /* [n] finite and >= 0 (else a miss) */
+    const uint32_t* self_entity; /* [n] entity_index never hit by this query; NULL or AVN_SPATIAL_MISS = none */
+    avn_spatial_filter filter;
+} avn_spatial_moves;
+/* MoveHitData with the collider's table index.  64 / 120 bytes, no implicit padding: every byte of a record is written. */
+typedef struct avn_spatial_move_hit_f32 {
+    uint32_t collider;   /* AVN_SPATIAL_MISS = no hit (entity too; the rest 0) */
+    uint32_t entity;
+    float distance;             /* the safe distance: the hit's distance pulled back by the skin width */
+    float collision_distance;   /* the movement's length (the reference's field of that name) */
+    float point1[3], point2[3], normal1[3], normal2[3];
+} avn_spatial_move_hit_f32;
+typedef struct avn_spatial_move_hit_f64 {
+    uint32_t collider;
+    uint32_t entity;
+    double distance;
+    double collision_distance;
+    double point1[3], point2[3], normal1[3], normal2[3];
+} avn_spatial_move_hit_f64;
+typedef struct avn_spatial_move_hits_out {
+    void* hits;          /* avn_spatial_move_hit_fNN [n] */
+} avn_spatial_move_hits_out;
+
+/* the characters of avn_spatial_move_and_slide */
+typedef struct avn_spatial_characters {
+    uint32_t count;
+    uint32_t flags;
+    const uint8_t* shape;
+    const void* half_extents;    /* [3n] */
+    const void* position;        /* [3n] */
+    const void* rotation;        /* [4n] */
+    const void* velocity;        /* [3n] */
+    const uint32_t* self_entity; /* [n] or NULL */
+    avn_spatial_filter filter;
+} avn_spatial_characters;
+/* MoveAndSlideConfig; the doubles are cast once to the world's scalar.  The caller applies PhysicsLengthUnit.  The struct and `planes` are host
+ * memory whatever the flags say. */
+typedef struct avn_spatial_move_and_slide_config {
+    double delta_time;
+    double skin_width;
+    double max_depenetration_error;
+    double penetration_rejection_threshold;
+    double plane_similarity_dot_threshold;
+    const float* planes;                  /* [3 * n_planes] initial planes of every character of the call; NULL if n_planes == 0 */
+    uint32_t n_planes;                    /* <= AVN_SPATIAL_MAX_PLANES */
+    uint32_t max_planes;                  /* <= AVN_SPATIAL_MAX_PLANES */
+    uint32_t move_and_slide_iterations;   /* <= AVN_SPATIAL_MAX_SLIDE_ITERATIONS */
+    uint32_t depenetration_iterations;
+} avn_spatial_move_and_slide_config;
+#define AVN_SPATIAL_MAX_SLIDE_ITERATIONS 16
+#define AVN_SPATIAL_SLIDE_TRUNCATED 1u    /* flags bit 0: some contacts pass of the character exceeded AVN_SPATIAL_MAX_HITS records; the first were used */
+/* MoveAndSlideOutput plus counters.  36 / 64 bytes, every byte written. */
+typedef struct avn_spatial_slide_f32 {
+    float position[3];
+    float projected_velocity[3];
+    uint32_t iterations_run;   /* cast_move calls made */
+    uint32_t hit_count;        /* true number of on_hit calls */
+    uint32_t flags;            /* AVN_SPATIAL_SLIDE_* */
+} avn_spatial_slide_f32;
+typedef struct avn_spatial_slide_f64 {
+    double position[3];
+    double projected_velocity[3];
+    uint32_t iterations_run;
+    uint32_t hit_count;
+    uint32_t flags;
+    uint32_t reserved;         /* always written as 0 */
+} avn_spatial_slide_f64;
+/* MoveAndSlideHitData of one on_hit call.  48 / 80 bytes. */
+typedef struct avn_spatial_slide_hit_f32 {
+    uint32_t collider;         /* kind 0: the sweep's collider; kind 1: the contact plane's own collider */
+    uint32_t entity;
+    uint32_t iteration;        /* round of the loop, from 0 */
+    uint32_t kind;             /* 0: the sweep hit, 1: a contact plane */
+    float point[3];
+    float normal[3];           /* the Dir handed to on_hit (f32, widened) */
+    float distance;            /* the sweep's safe distance */
+    float collision_distance;
+} avn_spatial_slide_hit_f32;
+typedef struct avn_spatial_slide_hit_f64 {
+    uint32_t collider;
+    uint32_t entity;
+    uint32_t iteration;
+    uint32_t kind;
+    double point[3];
+    double normal[3];
+    double distance;
+    double collision_distance;
+} avn_spatial_slide_hit_f64;
+typedef struct avn_spatial_slides_out {
+    void* slides;        /* avn_spatial_slide_fNN [n] */
+    void* hits;          /* avn_spatial_slide_hit_fNN [n * hit_cap]; NULL is legal when hit_cap == 0 */
+} avn_spatial_slides_out;
+
 typedef struct avn_spatial_shape_hits_out {
     void* hits;          /* avn_spatial_shape_hit_fNN [n] (cast_shapes) or [n * max_hits] (shape_hits; unused slots are misses) */
     uint32_t* count;     /* [n] true number of hits (shape_hits); ignored by cast_shapes */
@@ -415,6 +581,17 @@ AVN_API avn_status avn_spatial_shape_contacts(avn_world* w, const avn_spatial_sh
  * depenetration over them.  shapes->flags may carry AVN_SPATIAL_SKIP_SENSORS.  The world keeps a device buffer of
  * count * AVN_SPATIAL_MAX_HITS contact records for this call (3.8 KB per query in f32, 7.7 KB in f64); it grows and is never shrunk. */
 AVN_API avn_status avn_spatial_depenetrate(avn_world* w, const avn_spatial_shapes* shapes, const avn_spatial_depenetration_config* config, const avn_spatial_depenetrations_out* out);
+/* project_velocity (velocity_project.rs:122) per query; needs no snapshot.  stride > AVN_SPATIAL_MAX_PLANES is AVN_ERR_BAD_ARG. */
+AVN_API avn_status avn_spatial_project_velocities(avn_world* w, const avn_spatial_velocity_projections* in, const avn_spatial_velocities_out* out);
+/* MoveAndSlide::cast_move (move_and_slide.rs:745-793) per move: the first collider on the way, the distance pulled back by the skin width.  The
+ * colliders that overlap a move's shape at its start go through a list of AVN_SPATIAL_MAX_HITS slots per move in a buffer the world keeps (it grows
+ * and is never shrunk); a move with more of them makes the call AVN_ERR_CAPACITY (avn_spatial_move_and_slide too). */
+AVN_API avn_status avn_spatial_cast_moves(avn_world* w, const avn_spatial_moves* moves, const avn_spatial_move_hits_out* out);
+/* MoveAndSlide::move_and_slide (move_and_slide.rs:464-609) per character, as a fixed sequence of launches with the per-character state in buffers
+ * the world keeps (they grow and are never shrunk).  0 <= hit_cap <= AVN_SPATIAL_MAX_HITS; limits exceeded are AVN_ERR_BAD_ARG.  The traversal
+ * counters of avn_spatial_stats are the totals of all the call's launches. */
+AVN_API avn_status avn_spatial_move_and_slide(avn_world* w, const avn_spatial_characters* characters, const avn_spatial_move_and_slide_config* config, uint32_t hit_cap,
+                                              const avn_spatial_slides_out* out);
 /* snapshot sizes and the traversal counters of the last query call */
 AVN_API avn_status avn_spatial_stats_get(avn_world* w, avn_spatial_stats* out);
 

@@ -10,6 +10,9 @@
   shape_intersections, which shares the traversal and has the cheaper leaf: the yardstick of the two
   cast_shapes, 10^6 casts into cfg2 from the rays' origins along the rays' directions, short (<= 2 m) and long (200 m), half balls and half
   cuboids of half extent <= 0.25 m;  shape_hits k = 16, 64 k long casts -- reported beside cast_rays / ray_hits of the same run
+  project_velocities, 10^6 velocities against 0 .. 4 planes;  cast_moves and move_and_slide (4 rounds) for a crowd of 262144 characters in cfg2,
+  beside the same work done through the older entry points (two depenetrate, then per round cast_shapes + shape_contacts), with the share of
+  characters still live in each round
 
 Every figure is the median over `reps` warmed-up calls.  The queries take torch tensors on the GPU (AVN_SPATIAL_DEVICE_POINTERS: no
 staging copies), so a call is its launches plus one stream synchronisation; the update is timed with avn_synchronize behind it.  Device
@@ -159,6 +162,53 @@ def main():
     res["shape_hits_k16_64k_casts_per_s"] = nk / (ms * 1e-3)
     res["shape_hits_k16_leaves_per_cast"] = sq.stats().leaves_visited / nk
     res["shape_hits_k16_bytes_floor"] = nk * (1 + 12 + 12 + 16 + 12 + 4 + 16 * crec + 4)
+    # move and slide: a crowd of nc characters (the small cast shapes at the rays' origins, 4 m/s along the rays' directions, a step of 0.1 s)
+    nc = 262144
+    ck, che, cp, cr = kind[:nc].contiguous(), small[:nc].contiguous(), o[:nc].contiguous(), rot[:nc].contiguous()
+    cv = (d[:nc] * 4.0).contiguous()
+    mcfg = dict(delta_time=0.1, skin_width=0.01, max_depenetration_error=1e-4, penetration_rejection_threshold=0.5, depenetration_iterations=4)
+    rounds = 4
+    nv = 1_000_000
+    pn = torch.nn.functional.normalize(torch.randn(nv, 4, 3, device=dev, generator=g), dim=2)
+    pc = torch.randint(0, 5, (nv,), device=dev, generator=g, dtype=torch.int32)
+    pv = torch.randn(nv, 3, device=dev, generator=g)
+    ms = timed(lambda: sq.project_velocities(pv, pn, pc), reps)
+    res["project_velocities_1m_ms"] = ms
+    res["project_velocities_per_s"] = nv / (ms * 1e-3)
+    res["project_velocities_bytes_floor"] = nv * (12 + 48 + 4 + 12)
+    skin = torch.full((nc,), 0.01, device=dev)
+    ms = timed(lambda: sq.cast_moves(ck, che, cp, cr, cv * 0.1, skin), reps)
+    st = sq.stats()
+    res["cast_moves_256k_ms"] = ms
+    res["cast_moves_per_s"] = nc / (ms * 1e-3)
+    res["cast_moves_leaves_per_move"], res["cast_moves_nodes_per_move"] = st.leaves_visited / nc, st.nodes_visited / nc
+    ms = timed(lambda: sq.cast_shapes(ck, che, cp, cr, d[:nc].contiguous(), torch.full((nc,), 0.4, device=dev)), reps)
+    res["cast_shapes_same_256k_ms"] = ms
+    res["cast_moves_over_cast_shapes"] = res["cast_moves_256k_ms"] / ms
+    slides = []
+    ms = timed(lambda: slides.append(sq.move_and_slide(ck, che, cp, cr, cv, **mcfg, move_and_slide_iterations=rounds, hit_cap=0)[0]), reps)
+    st = sq.stats()
+    res["move_and_slide_256k_ms"] = ms
+    res["move_and_slide_characters_per_s"] = nc / (ms * 1e-3)
+    res["move_and_slide_leaves_per_character"], res["move_and_slide_nodes_per_character"] = st.leaves_visited / nc, st.nodes_visited / nc
+    srec = slides[-1].cpu().numpy().reshape(-1).view(sq.slide_dtype)
+    res["move_and_slide_live_share_per_round"] = [float((srec["iterations_run"] > r).mean()) for r in range(rounds)]
+    res["move_and_slide_hits_per_character"] = float(srec["hit_count"].mean())
+    # the same work through the entry points of the parent commit: two depenetrate calls, then per round one cast_shapes and one shape_contacts
+    # call (cap AVN_SPATIAL_MAX_HITS, prediction 2 * skin_width) on the same characters, every character in every round
+    md4 = torch.full((nc,), 0.4, device=dev)
+    dn = d[:nc].contiguous()
+    pred2 = torch.full((nc,), 0.02, device=dev)
+
+    def composed():
+        sq.depenetrate(ck, che, cp, cr, 0.01, 1e-4, 0.5, 4, skip_sensors=True)
+        for _ in range(rounds):
+            sq.cast_shapes(ck, che, cp, cr, dn, md4)
+            sq.shape_contacts(ck, che, cp, cr, pred2, 64, skip_sensors=True)
+        sq.depenetrate(ck, che, cp, cr, 0.01, 1e-4, 0.5, 4, skip_sensors=True)
+    ms = timed(composed, reps)
+    res["composed_parent_calls_256k_ms"] = ms
+    res["move_and_slide_over_composed"] = res["move_and_slide_256k_ms"] / ms
     res["update_bytes_floor_per_collider"] = 4 * 16 + 16 + 8 + 4 * 16 + 2 * 16 + 2 * 2 * 16 + 8 + 12
     for k in [k for k in res if k.endswith("_bytes_floor")]:
         msk = k.replace("_bytes_floor", "_ms") if k.replace("_bytes_floor", "_ms") in res else None
