@@ -450,6 +450,26 @@ template <class T> struct SQ {
     SpatialProjection<T>* proj;      // [n]
     // SPQ_CAST / SPQ_CAST_HITS (the SPQ_SHAPES fields, b = directions, max_distance; cap = max_hits): k_sp_cast
     SpatialShapeHit<T>* cast;        // SPQ_CAST: [n]; SPQ_CAST_HITS: [n * cap]
+    // the per-query filter of a caster run (the PQ instantiations of k_sp_query / k_sp_cast only).  Lane i answers caster
+    // index[i]: every per-query array above is indexed by the caster, records are rows of `cap` slots and count is written by every kind
+    const uint32_t* index;           // [n] caster of each lane
+    const uint32_t* self_entity;     // [casters] AVN_SPATIAL_MISS: none
+    const uint32_t* ex_offset;       // [casters + 1] the caster's slice of `excluded`, sorted per slice
+    const uint32_t* kq;              // [casters] min(max_hits, cap)
+    const uint8_t* live;             // [casters] enabled && kq != 0 (else: count 0, no traversal)
+};
+// k_sp_reaim: the global origin / direction / shape rotation of every caster from its anchor's pose (include/avian_mi355x_spatial.h "Casters")
+template <class T> struct SCA {
+    uint32_t n;
+    const uint8_t* anchor_kind;      // [n] AVN_SPATIAL_ANCHOR_*
+    const uint32_t* anchor;          // [n] checked against the tables on the host before every launch
+    const T* origin;                 // [3n] local
+    const float* direction;          // [3n] local
+    const T* shape_rotation;         // [4n] local, or nullptr (ray casters)
+    T* g_origin;                     // [3n]
+    float* g_direction;              // [3n] what avn_spatial_caster_poses_get returns
+    T* g_direction_t;                // [3n] the same values widened: the casts' `b`
+    T* g_rotation;                   // [4n] or nullptr
 };
 #define SP_INFO_SENSOR 2u
 // == avn_spatial_shape_contact_fNN (60 / 120 bytes, no implicit padding: the f64 record ends in two reserved words, always 0)
@@ -532,6 +552,9 @@ template <class T> void launch_spatial_cast_move(const SP<T>&, const SM<T>&, boo
 template <class T> void launch_spatial_slide_phase(const SL<T>&, int phase, hipStream_t);
 template <class T> void launch_spatial_build(const DW<T>&, const BP<T>&, const SP<T>&, hipStream_t);
 template <class T> void launch_spatial_query(const SP<T>&, const SQ<T>&, int kind, hipStream_t);
+template <class T> void launch_spatial_reaim(const DW<T>&, const SP<T>&, const SCA<T>&, hipStream_t);
+// a caster group: kind SPQ_CLOSEST / SPQ_HITS / SPQ_CAST / SPQ_CAST_HITS with the per-query filter; q.stats is NOT zeroed (the run zeroes it once)
+template <class T> void launch_spatial_casters(const SP<T>&, const SQ<T>&, int kind, hipStream_t);
 template <class T> void launch_spatial_contacts(const SP<T>&, const SC<T>&, hipStream_t, bool zero_stats = true);
 template <class T> void launch_spatial_depenetrate(const SD<T>&, hipStream_t);
 

@@ -36,6 +36,12 @@ AVN_API avn_status avn_spatial_cast_moves(avn_world* w, const avn_spatial_moves*
 AVN_API avn_status avn_spatial_move_and_slide(avn_world* w, const avn_spatial_characters* c, const avn_spatial_move_and_slide_config* cfg, uint32_t hit_cap, const avn_spatial_slides_out* o) {
     SP_GUARD(spatial_move_and_slide(c, cfg, hit_cap, o));
 }
+AVN_API avn_status avn_spatial_ray_casters_upload(avn_world* w, const avn_spatial_ray_casters* c) { SP_GUARD(spatial_ray_casters_upload(c)); }
+AVN_API avn_status avn_spatial_shape_casters_upload(avn_world* w, const avn_spatial_shape_casters* c) { SP_GUARD(spatial_shape_casters_upload(c)); }
+AVN_API avn_status avn_spatial_casters_run(avn_world* w, uint32_t flags) { SP_GUARD(spatial_casters_run(flags)); }
+AVN_API avn_status avn_spatial_ray_caster_hits_get(avn_world* w, uint32_t flags, const avn_spatial_hits_out* o) { SP_GUARD(spatial_ray_caster_hits_get(flags, o)); }
+AVN_API avn_status avn_spatial_shape_caster_hits_get(avn_world* w, uint32_t flags, const avn_spatial_shape_hits_out* o) { SP_GUARD(spatial_shape_caster_hits_get(flags, o)); }
+AVN_API avn_status avn_spatial_caster_poses_get(avn_world* w, uint32_t kind, uint32_t flags, const avn_spatial_caster_poses_out* o) { SP_GUARD(spatial_caster_poses_get(kind, flags, o)); }
 AVN_API avn_status avn_spatial_stats_get(avn_world* w, avn_spatial_stats* o) { SP_GUARD(spatial_stats_get(o)); }
 
 }  // extern "C"

@@ -138,6 +138,12 @@ struct WorldBase {
     virtual avn_status spatial_project_velocities(const avn_spatial_velocity_projections*, const avn_spatial_velocities_out*) = 0;
     virtual avn_status spatial_cast_moves(const avn_spatial_moves*, const avn_spatial_move_hits_out*) = 0;
     virtual avn_status spatial_move_and_slide(const avn_spatial_characters*, const avn_spatial_move_and_slide_config*, uint32_t hit_cap, const avn_spatial_slides_out*) = 0;
+    virtual avn_status spatial_ray_casters_upload(const avn_spatial_ray_casters*) = 0;
+    virtual avn_status spatial_shape_casters_upload(const avn_spatial_shape_casters*) = 0;
+    virtual avn_status spatial_casters_run(uint32_t flags) = 0;
+    virtual avn_status spatial_ray_caster_hits_get(uint32_t flags, const avn_spatial_hits_out*) = 0;
+    virtual avn_status spatial_shape_caster_hits_get(uint32_t flags, const avn_spatial_shape_hits_out*) = 0;
+    virtual avn_status spatial_caster_poses_get(uint32_t kind, uint32_t flags, const avn_spatial_caster_poses_out*) = 0;
     virtual avn_status spatial_stats_get(avn_spatial_stats*) = 0;
 };
 

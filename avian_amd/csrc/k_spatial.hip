@@ -1,7 +1,8 @@
 // k_spatial.hip — spatial queries on the device (include/avian_mi355x_spatial.h): an LBVH over the collider table and one-lane-per-query
 // traversals for ray casts, ray hits, point and AABB intersections (k_sp_query), point projection (k_sp_project), shape intersections
 // (k_sp_shapes), shape casts (k_sp_cast), shape contacts (k_sp_contacts), the depenetration over them (k_sp_depenetrate), velocity
-// projection (k_sp_project_velocity), cast_move (k_sp_cast_move) and the phases of the move-and-slide loop (k_sp_slide).
+// projection (k_sp_project_velocity), cast_move (k_sp_cast_move), the phases of the move-and-slide loop (k_sp_slide), and the casters: their
+// re-aiming (k_sp_reaim) and the per-caster filter of k_sp_query / k_sp_cast (PQ).
 //
 // avn_spatial_update (launch_spatial_build), all on the world's stream:
 //   1. k_sp_snapshot   one thread per collider: its pose (collider_pose), the exact shape AABB (shape_aabb), padded, as the leaf box;
@@ -302,17 +303,23 @@ __device__ __forceinline__ bool sp_excluded(const uint32_t* __restrict__ ex, uin
     return lo < n && ex[lo] == e;
 }
 
-// one lane per query; blocks of one wave, each lane with its own SP_STACK-entry column of the LDS stack
-template <class T, int KIND>
+// one lane per query; blocks of one wave, each lane with its own SP_STACK-entry column of the LDS stack.  PQ (a caster run, SPQ_CLOSEST /
+// SPQ_HITS only): the lane answers caster q.index[lane's query] with that caster's own self_entity, excluded slice, live flag and k, into its
+// row of q.cap record slots; the instantiations without PQ compile as before.
+template <class T, int KIND, bool PQ = false>
 __global__ __launch_bounds__(SP_WAVE) void k_sp_query(SP<T> sp, SQ<T> q) {
     __shared__ uint32_t stack[SP_STACK * SP_WAVE];
     const uint32_t lane = threadIdx.x;
-    const uint32_t qi = blockIdx.x * SP_WAVE + lane;
-    const bool active = qi < q.n;
+    const uint32_t li = blockIdx.x * SP_WAVE + lane;
+    const bool active = li < q.n;
     uint32_t nodes_tested = 0, leaves_tested = 0, overflow = 0;
     const uint32_t n = sp.n;
     if (active) {
+        const uint32_t qi = PQ ? q.index[li] : li;
         const uint32_t mask = q.mask ? q.mask[qi] : 0xFFFFFFFFu;
+        const uint32_t self = PQ ? q.self_entity[qi] : AVN_SPATIAL_MISS;
+        const uint32_t ex0 = PQ ? q.ex_offset[qi] : 0u, ex_n = PQ ? q.ex_offset[qi + 1] - ex0 : 0u;
+        const uint32_t kq = PQ ? q.kq[qi] : q.cap;   // the list length of SPQ_HITS
         // per-query state
         RayCtx<T> r;
         V3<T> pa{T(0), T(0), T(0)}, pb{T(0), T(0), T(0)};
@@ -330,7 +337,7 @@ __global__ __launch_bounds__(SP_WAVE) void k_sp_query(SP<T> sp, SQ<T> q) {
         }
         if (KIND == SPQ_POINTS) tol = T(64) * Limits<T>::eps * sp_maxabs(pa);
         // a non-finite origin, direction, point or box corner answers a miss / count 0 without traversing the tree
-        const bool finite_query = is_finite(pa) && (KIND == SPQ_POINTS || is_finite(pb));
+        const bool finite_query = is_finite(pa) && (KIND == SPQ_POINTS || is_finite(pb)) && (!PQ || q.live[qi] != 0);
         // results
         T best = sp_inf<T>();
         uint32_t best_c = AVN_SPATIAL_MISS;
@@ -351,7 +358,8 @@ __global__ __launch_bounds__(SP_WAVE) void k_sp_query(SP<T> sp, SQ<T> q) {
         auto leaf = [&](uint32_t node) {
             const uint32_t c = sp.leaf_col[node - (n - 1)];
             const uint4 info = sp.info[c];
-            if (!info.w || (info.y & mask) == 0u || (q.n_excluded && sp_excluded(q.excluded, q.n_excluded, info.x))) return;
+            if (!info.w || (info.y & mask) == 0u || (!PQ && q.n_excluded && sp_excluded(q.excluded, q.n_excluded, info.x))) return;
+            if (PQ && ((self != AVN_SPATIAL_MISS && info.x == self) || (ex_n && sp_excluded(q.excluded + ex0, ex_n, info.x)))) return;
             ++leaves_tested;
             const V3<T> pos = xyz<T>(sp.pos[c]), he = xyz<T>(sp.he[c]);
             const Q4<T> rot = quat<T>(sp.rot[c]);
@@ -361,7 +369,7 @@ __global__ __launch_bounds__(SP_WAVE) void k_sp_query(SP<T> sp, SQ<T> q) {
                 if (KIND == SPQ_CLOSEST) {
                     if (toi < best || (toi == best && c < best_c)) { best = toi; best_c = c; best_n = nrm; }
                 } else {
-                    const uint32_t k = q.cap;
+                    const uint32_t k = kq;
                     uint32_t m = found < k ? found : k;
                     ++found;
                     // nearest-k by (distance, collider), insertion into the query's own output records
@@ -434,11 +442,19 @@ __global__ __launch_bounds__(SP_WAVE) void k_sp_query(SP<T> sp, SQ<T> q) {
             h.entity = best_c == AVN_SPATIAL_MISS ? AVN_SPATIAL_MISS : sp.info[best_c].x;
             h.distance = best_c == AVN_SPATIAL_MISS ? T(0) : best;
             h.normal[0] = best_n.x; h.normal[1] = best_n.y; h.normal[2] = best_n.z;
-            q.hits[qi] = h;
+            if (!PQ) q.hits[qi] = h;
+            else {
+                // the caster's row: the hit or a miss, then misses; count 0 or 1
+                SpatialHit<T>* row = q.hits + (size_t)qi * q.cap;
+                row[0] = h;
+                h.collider = AVN_SPATIAL_MISS; h.entity = AVN_SPATIAL_MISS; h.distance = T(0); h.normal[0] = h.normal[1] = h.normal[2] = T(0);
+                for (uint32_t m = 1; m < q.cap; ++m) row[m] = h;
+                q.count[qi] = best_c == AVN_SPATIAL_MISS ? 0u : 1u;
+            }
         } else if (KIND == SPQ_HITS) {
             SpatialHit<T> miss;
             miss.collider = AVN_SPATIAL_MISS; miss.entity = AVN_SPATIAL_MISS; miss.distance = T(0); miss.normal[0] = miss.normal[1] = miss.normal[2] = T(0);
-            for (uint32_t m = found; m < q.cap; ++m) hl[m] = miss;
+            for (uint32_t m = PQ ? (found < kq ? found : kq) : found; m < q.cap; ++m) hl[m] = miss;
             q.count[qi] = found;
         } else {
             for (uint32_t m = found; m < q.cap; ++m) il[m] = AVN_SPATIAL_MISS;
@@ -972,16 +988,21 @@ template <class T> __device__ __forceinline__ void sp_put(SpatialShapeHit<T>& h,
     h.normal2[0] = n1.x == T(0) ? T(0) : -n1.x; h.normal2[1] = n1.y == T(0) ? T(0) : -n1.y; h.normal2[2] = n1.z == T(0) ? T(0) : -n1.z;
 }
 
-// one lane per cast; blocks of one wave; MANY: the nearest-k list (shape_hits), else the closest hit (cast_shapes)
-template <class T, bool MANY>
+// one lane per cast; blocks of one wave; MANY: the nearest-k list (shape_hits), else the closest hit (cast_shapes).  PQ: a caster run, as in
+// k_sp_query
+template <class T, bool MANY, bool PQ = false>
 __global__ __launch_bounds__(SP_WAVE) void k_sp_cast(SP<T> sp, SQ<T> q) {
     __shared__ uint32_t stack[SP_STACK * SP_WAVE];
     const uint32_t lane = threadIdx.x;
-    const uint32_t qi = blockIdx.x * SP_WAVE + lane;
+    const uint32_t li = blockIdx.x * SP_WAVE + lane;
     uint32_t nodes_tested = 0, leaves_tested = 0, overflow = 0;
     const uint32_t n = sp.n;
-    if (qi < q.n) {
+    if (li < q.n) {
+        const uint32_t qi = PQ ? q.index[li] : li;
         const uint32_t mask = q.mask ? q.mask[qi] : 0xFFFFFFFFu;
+        const uint32_t self = PQ ? q.self_entity[qi] : AVN_SPATIAL_MISS;
+        const uint32_t ex0 = PQ ? q.ex_offset[qi] : 0u, ex_n = PQ ? q.ex_offset[qi + 1] - ex0 : 0u;
+        const uint32_t kq = PQ ? q.kq[qi] : q.cap;   // the list length of MANY
         const uint32_t shape2 = q.shape[qi];
         const V3<T> pos2{q.a[3 * (size_t)qi], q.a[3 * (size_t)qi + 1], q.a[3 * (size_t)qi + 2]};
         const V3<T> d{q.b[3 * (size_t)qi], q.b[3 * (size_t)qi + 1], q.b[3 * (size_t)qi + 2]};
@@ -991,7 +1012,7 @@ __global__ __launch_bounds__(SP_WAVE) void k_sp_cast(SP<T> sp, SQ<T> q) {
         if (shape2 == AVN_SHAPE_BALL) he2 = V3<T>{he2.x, he2.x, he2.x};   // (a ball has its radius in x: y and z are not read)
         // k_sp_shapes' rule, plus a finite direction and a max_distance that is not NaN: otherwise a miss / count 0
         bool valid = shape2 <= AVN_SHAPE_BALL && is_finite(pos2) && is_finite(V3<T>{rot2.x, rot2.y, rot2.z}) && finite_t(rot2.w) && is_finite(he2) &&
-                     he2.x >= T(0) && he2.y >= T(0) && he2.z >= T(0) && is_finite(d) && max_distance == max_distance;
+                     he2.x >= T(0) && he2.y >= T(0) && he2.z >= T(0) && is_finite(d) && max_distance == max_distance && (!PQ || q.live[qi] != 0);
         RayCtx<T> r;
         r.o = r.d = r.inv = vzero<T>(); r.zero = 0; r.tol = T(0);
         V3<T> hw = vzero<T>();
@@ -1028,14 +1049,15 @@ __global__ __launch_bounds__(SP_WAVE) void k_sp_cast(SP<T> sp, SQ<T> q) {
         auto leaf = [&](uint32_t node) {
             const uint32_t c = sp.leaf_col[node - (n - 1)];
             const uint4 info = sp.info[c];
-            if (!info.w || (info.y & mask) == 0u || (q.n_excluded && sp_excluded(q.excluded, q.n_excluded, info.x))) return;
+            if (!info.w || (info.y & mask) == 0u || (!PQ && q.n_excluded && sp_excluded(q.excluded, q.n_excluded, info.x))) return;
+            if (PQ && ((self != AVN_SPATIAL_MISS && info.x == self) || (ex_n && sp_excluded(q.excluded + ex0, ex_n, info.x)))) return;
             ++leaves_tested;
             T toi; V3<T> p1, p2, n1;
             if (!sp_cast_exact<T>(shape2, he2, iso2, d, max_distance, info.z, xyz<T>(sp.he[c]), xyz<T>(sp.pos[c]), quat<T>(sp.rot[c]), toi, p1, p2, n1)) return;
             if (!MANY) {
                 if (toi < best || (toi == best && c < best_c)) { best = toi; best_c = c; best_p1 = p1; best_p2 = p2; best_n1 = n1; }
             } else {
-                const uint32_t k = q.cap;
+                const uint32_t k = kq;
                 uint32_t m = found < k ? found : k;
                 ++found;
                 if (m == k) {
@@ -1088,11 +1110,18 @@ __global__ __launch_bounds__(SP_WAVE) void k_sp_cast(SP<T> sp, SQ<T> q) {
         if (!MANY) {
             SpatialShapeHit<T> h;
             sp_put<T>(h, best_c, best_c == AVN_SPATIAL_MISS ? AVN_SPATIAL_MISS : sp.info[best_c].x, best_c == AVN_SPATIAL_MISS ? T(0) : best, best_p1, best_p2, best_n1);
-            q.cast[qi] = h;
+            if (!PQ) q.cast[qi] = h;
+            else {
+                SpatialShapeHit<T>* row = q.cast + (size_t)qi * q.cap;
+                row[0] = h;
+                sp_put<T>(h, AVN_SPATIAL_MISS, AVN_SPATIAL_MISS, T(0), vzero<T>(), vzero<T>(), vzero<T>());
+                for (uint32_t m = 1; m < q.cap; ++m) row[m] = h;
+                q.count[qi] = best_c == AVN_SPATIAL_MISS ? 0u : 1u;
+            }
         } else {
             SpatialShapeHit<T> miss;
             sp_put<T>(miss, AVN_SPATIAL_MISS, AVN_SPATIAL_MISS, T(0), vzero<T>(), vzero<T>(), vzero<T>());
-            for (uint32_t m = found; m < q.cap; ++m) hl[m] = miss;
+            for (uint32_t m = PQ ? (found < kq ? found : kq) : found; m < q.cap; ++m) hl[m] = miss;
             q.count[qi] = found;
         }
     }
@@ -1729,6 +1758,48 @@ template <class T> void launch_spatial_slide_phase(const SL<T>& l, int phase, hi
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// casters: one thread per caster re-aims it from its anchor's pose, in the header's operation order.  The anchors were checked
+// against the tables by the host (world/spatial.hpp: casters_run) before the launch.
+template <class T>
+__global__ __launch_bounds__(256) void k_sp_reaim(DW<T> w, SP<T> sp, SCA<T> c) {
+    const uint32_t i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= c.n) return;
+    const uint32_t kind = c.anchor_kind[i], a = c.anchor[i];
+    const size_t i3 = 3 * (size_t)i, i4 = 4 * (size_t)i;
+    V3<T> go{c.origin[i3], c.origin[i3 + 1], c.origin[i3 + 2]};
+    float gd[3] = {c.direction[i3], c.direction[i3 + 1], c.direction[i3 + 2]};
+    Q4<T> gr{T(0), T(0), T(0), T(1)};
+    if (c.shape_rotation) gr = Q4<T>{c.shape_rotation[i4], c.shape_rotation[i4 + 1], c.shape_rotation[i4 + 2], c.shape_rotation[i4 + 3]};
+    if (kind != AVN_SPATIAL_ANCHOR_WORLD) {   // (a world anchor: the local values, bit for bit)
+        const bool body = kind == AVN_SPATIAL_ANCHOR_BODY;
+        const V3<T> pos = body ? xyz<T>(w.pos[a]) : xyz<T>(sp.pos[a]);
+        const Q4<T> rot = body ? quat<T>(w.rot[a]) : quat<T>(sp.rot[a]);
+        go = pos + qrot(rot, go);
+        const V3<T> d = qrot(rot, V3<T>{(T)gd[0], (T)gd[1], (T)gd[2]});
+        gd[0] = (float)d.x; gd[1] = (float)d.y; gd[2] = (float)d.z;
+        gr = qmul(gr, rot);
+    }
+    c.g_origin[i3] = go.x; c.g_origin[i3 + 1] = go.y; c.g_origin[i3 + 2] = go.z;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { c.g_direction[i3 + k] = gd[k]; c.g_direction_t[i3 + k] = (T)gd[k]; }
+    if (c.g_rotation) { c.g_rotation[i4] = gr.x; c.g_rotation[i4 + 1] = gr.y; c.g_rotation[i4 + 2] = gr.z; c.g_rotation[i4 + 3] = gr.w; }
+}
+template <class T> void launch_spatial_reaim(const DW<T>& w, const SP<T>& sp, const SCA<T>& c, hipStream_t s) {
+    if (c.n == 0) return;
+    hipLaunchKernelGGL((k_sp_reaim<T>), dim3((c.n + 255) / 256), dim3(256), 0, s, w, sp, c);
+}
+template <class T> void launch_spatial_casters(const SP<T>& sp, const SQ<T>& q, int kind, hipStream_t s) {
+    if (q.n == 0) return;
+    const dim3 g((q.n + SP_WAVE - 1) / SP_WAVE), b(SP_WAVE);
+    switch (kind) {
+        case SPQ_CLOSEST: hipLaunchKernelGGL((k_sp_query<T, SPQ_CLOSEST, true>), g, b, 0, s, sp, q); break;
+        case SPQ_HITS: hipLaunchKernelGGL((k_sp_query<T, SPQ_HITS, true>), g, b, 0, s, sp, q); break;
+        case SPQ_CAST: hipLaunchKernelGGL((k_sp_cast<T, false, true>), g, b, 0, s, sp, q); break;
+        default: hipLaunchKernelGGL((k_sp_cast<T, true, true>), g, b, 0, s, sp, q); break;
+    }
+}
+
 template <class T> void launch_spatial_query(const SP<T>& sp, const SQ<T>& q, int kind, hipStream_t s) {
     (void)hipMemsetAsync(q.stats, 0, 4 * sizeof(unsigned long long), s);
     if (q.n == 0) return;
@@ -1787,6 +1858,10 @@ template void launch_spatial_build<float>(const DW<float>&, const BP<float>&, co
 template void launch_spatial_build<double>(const DW<double>&, const BP<double>&, const SP<double>&, hipStream_t);
 template void launch_spatial_query<float>(const SP<float>&, const SQ<float>&, int, hipStream_t);
 template void launch_spatial_query<double>(const SP<double>&, const SQ<double>&, int, hipStream_t);
+template void launch_spatial_reaim<float>(const DW<float>&, const SP<float>&, const SCA<float>&, hipStream_t);
+template void launch_spatial_reaim<double>(const DW<double>&, const SP<double>&, const SCA<double>&, hipStream_t);
+template void launch_spatial_casters<float>(const SP<float>&, const SQ<float>&, int, hipStream_t);
+template void launch_spatial_casters<double>(const SP<double>&, const SQ<double>&, int, hipStream_t);
 template void launch_spatial_contacts<float>(const SP<float>&, const SC<float>&, hipStream_t, bool);
 template void launch_spatial_contacts<double>(const SP<double>&, const SC<double>&, hipStream_t, bool);
 template void launch_spatial_project_velocity<float>(const SV<float>&, hipStream_t);

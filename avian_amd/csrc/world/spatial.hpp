@@ -1,6 +1,7 @@
 // world/spatial.hpp -- fragment of the body of `template <class T> struct World` (avn_world.hip includes it inside the class):
 // SpatialQueryPlugin (spatial_query/mod.rs:190-212) on the device -- include/avian_mi355x_spatial.h.  avn_spatial_update builds the LBVH of
-// k_spatial.hip from the poses in HBM; the queries stage their inputs, run one traversal launch and copy the answers back.
+// k_spatial.hip from the poses in HBM; the queries stage their inputs, run one traversal launch and copy the answers back.  The casters
+// (RayCaster / ShapeCaster) keep their definitions and answers on the device: avn_spatial_casters_run only enqueues.
 
     SP<T> sp{};
     DevBuf b_sp_pos, b_sp_rot, b_sp_he, b_sp_info, b_sp_smin, b_sp_smax, b_sp_bmin, b_sp_bmax, b_sp_child, b_sp_parent, b_sp_leaf, b_sp_arr, b_sp_bounds,
@@ -35,6 +36,7 @@
     avn_status spatial_update() override {
         if (!have_bodies || !have_colliders) { error = "spatial_update: before bodies_upload / colliders_upload"; return AVN_ERR_STATE; }
         if (despawn_needs_bodies || despawn_needs_colliders) { error = "spatial_update: avn_despawn is still waiting for avn_bodies_upload / avn_colliders_upload"; return AVN_ERR_STATE; }
+        if (!sp_valid) cs_ran = false;   // (the tables changed since the last casters run: its results name the old ones)
         const uint32_t C = bp.n_colliders;
         avn_status st = sp_grow(C);
         if (st != AVN_OK) return st;
@@ -456,6 +458,203 @@
         }
         return sp_finish();
     }
+    // ---- casters (include/avian_mi355x_spatial.h "Casters") ----
+    // One table per kind: the definitions in one device allocation (`def`), the re-aimed queries and the records in another (`res`).  The casters
+    // with k = min(max_hits, hit_cap) <= 1 run in the closest-hit kernel, the others in the nearest-k kernel: two index lists made at upload.
+    struct CasterDef {   // the fields of avn_spatial_ray_casters / avn_spatial_shape_casters
+        uint32_t count, hit_cap;
+        const uint8_t* anchor_kind; const uint32_t* anchor; const void* origin; const float* direction; const void* max_distance; const uint32_t* max_hits;
+        const uint8_t *solid, *shape; const void *half_extents, *shape_rotation;
+        const uint8_t* enabled; const uint32_t *mask, *self_entity, *excluded_offset, *excluded;
+    };
+    struct CasterSet {
+        uint32_t n = 0, hit_cap = 0, n_closest = 0, n_many = 0;
+        bool any_body = false, any_collider = false;
+        uint32_t max_body = 0, max_collider = 0;   // the largest anchors, checked against the tables before every run
+        DevBuf def, res;
+        SCA<T> a{};
+        SQ<T> q{};                                 // every field but n / index / stats
+        const uint32_t *index_closest = nullptr, *index_many = nullptr;
+        void* records = nullptr;                   // SpatialHit<T> / SpatialShapeHit<T> [n * hit_cap]
+    };
+    CasterSet cs_ray, cs_shape;
+    DevBuf b_cs_stats;          // the run's own traversal counters: queries between a run and its getters do not disturb them
+    bool cs_ran = false;        // a run's results are on the device and the snapshot they answer against is still valid
+
+    void casters_clear() { cs_ray.n = cs_shape.n = 0; cs_ran = false; }
+
+    avn_status casters_upload(CasterSet& cs, const CasterDef& d, bool is_shape, const char* who) {
+        cs_ran = false;
+        if (d.count == 0) { cs.n = 0; return AVN_OK; }
+        const uint32_t n = d.count;
+        if (d.hit_cap == 0 || d.hit_cap > AVN_SPATIAL_MAX_HITS) { error = std::string(who) + ": hit_cap must be 1 .. AVN_SPATIAL_MAX_HITS"; return AVN_ERR_BAD_ARG; }
+        if (!d.anchor_kind || !d.anchor || !d.origin || !d.direction || !d.max_distance || !d.max_hits || (!is_shape && !d.solid) ||
+            (is_shape && (!d.shape || !d.half_extents || !d.shape_rotation))) { error = std::string(who) + ": null array"; return AVN_ERR_BAD_ARG; }
+        const uint32_t n_bodies = have_bodies ? dw.n_bodies : 0u, n_colliders = have_colliders ? bp.n_colliders : 0u;
+        bool any_body = false, any_collider = false;
+        uint32_t max_body = 0, max_collider = 0;
+        for (uint32_t i = 0; i < n; ++i) {
+            const uint32_t k = d.anchor_kind[i], a = d.anchor[i];
+            if (k > AVN_SPATIAL_ANCHOR_COLLIDER) { error = std::string(who) + ": unknown anchor kind"; return AVN_ERR_BAD_ARG; }
+            if ((k == AVN_SPATIAL_ANCHOR_BODY && a >= n_bodies) || (k == AVN_SPATIAL_ANCHOR_COLLIDER && a >= n_colliders)) {
+                error = std::string(who) + ": anchor " + std::to_string(a) + " of caster " + std::to_string(i) + " is outside its table"; return AVN_ERR_BAD_ARG;
+            }
+            if (k == AVN_SPATIAL_ANCHOR_BODY) { any_body = true; max_body = std::max(max_body, a); }
+            if (k == AVN_SPATIAL_ANCHOR_COLLIDER) { any_collider = true; max_collider = std::max(max_collider, a); }
+        }
+        std::vector<uint32_t> off(n + 1, 0u), ex;
+        if (d.excluded_offset) {
+            if (d.excluded_offset[0] != 0u) { error = std::string(who) + ": excluded_offset[0] must be 0"; return AVN_ERR_BAD_ARG; }
+            for (uint32_t i = 0; i < n; ++i) if (d.excluded_offset[i + 1] < d.excluded_offset[i]) { error = std::string(who) + ": excluded_offset must ascend"; return AVN_ERR_BAD_ARG; }
+            if (d.excluded_offset[n] && !d.excluded) { error = std::string(who) + ": excluded is NULL"; return AVN_ERR_BAD_ARG; }
+            off.assign(d.excluded_offset, d.excluded_offset + n + 1);
+            ex.assign(d.excluded, d.excluded + off[n]);
+            for (uint32_t i = 0; i < n; ++i) std::sort(ex.begin() + off[i], ex.begin() + off[i + 1]);
+        }
+        std::vector<uint32_t> kq(n), self(n, AVN_SPATIAL_MISS), closest, many;
+        std::vector<uint8_t> live(n);
+        for (uint32_t i = 0; i < n; ++i) {
+            kq[i] = std::min(d.max_hits[i], d.hit_cap);
+            live[i] = (!d.enabled || d.enabled[i]) && kq[i] != 0u;
+            if (d.self_entity) self[i] = d.self_entity[i];
+            (kq[i] <= 1u ? closest : many).push_back(i);
+        }
+        // the definitions: one host image, one copy
+        std::vector<uint8_t> img;
+        auto put = [&](const void* p, size_t bytes) { const size_t at = al(img.size()); img.resize(at + bytes); if (bytes) std::memcpy(img.data() + at, p, bytes); return at; };
+        const size_t o_kind = put(d.anchor_kind, n), o_anchor = put(d.anchor, 4 * (size_t)n), o_origin = put(d.origin, 3 * sizeof(T) * n), o_dir = put(d.direction, 12 * (size_t)n),
+                     o_md = put(d.max_distance, sizeof(T) * n), o_solid = is_shape ? 0 : put(d.solid, n), o_shape = is_shape ? put(d.shape, n) : 0,
+                     o_he = is_shape ? put(d.half_extents, 3 * sizeof(T) * n) : 0, o_rot = is_shape ? put(d.shape_rotation, 4 * sizeof(T) * n) : 0,
+                     o_mask = d.mask ? put(d.mask, 4 * (size_t)n) : 0, o_self = put(self.data(), 4 * (size_t)n), o_off = put(off.data(), 4 * (size_t)(n + 1)),
+                     o_ex = put(ex.data(), 4 * ex.size()), o_kq = put(kq.data(), 4 * (size_t)n), o_live = put(live.data(), n),
+                     o_closest = put(closest.data(), 4 * closest.size()), o_many = put(many.data(), 4 * many.size());
+        const size_t rec = is_shape ? sizeof(SpatialShapeHit<T>) : sizeof(SpatialHit<T>);
+        const size_t r_origin = 0, r_dir = r_origin + al(3 * sizeof(T) * n), r_dir_t = r_dir + al(12 * (size_t)n), r_rot = r_dir_t + al(3 * sizeof(T) * n),
+                     r_rec = r_rot + al(4 * sizeof(T) * n), r_count = r_rec + al(rec * n * d.hit_cap), r_end = r_count + al(4 * (size_t)n);
+        HIPCHK(hipStreamSynchronize(stream));   // (a run in flight may still read the old tables)
+        hipError_t err;
+        cs.n = 0;
+        cs.def.ensure(al(img.size()) + 64, err);
+        if (err == hipSuccess) cs.res.ensure(r_end, err);
+        if (err != hipSuccess) { error = std::string(who) + ": hipMalloc: " + hipGetErrorName(err); return AVN_ERR_OOM; }
+        HIPCHK(hipMemcpy(cs.def.p, img.data(), img.size(), hipMemcpyHostToDevice));
+        const char* D = (const char*)cs.def.p;
+        char* R = (char*)cs.res.p;
+        SCA<T>& a = cs.a;
+        a = SCA<T>{};
+        a.n = n; a.anchor_kind = (const uint8_t*)(D + o_kind); a.anchor = (const uint32_t*)(D + o_anchor); a.origin = (const T*)(D + o_origin);
+        a.direction = (const float*)(D + o_dir); a.shape_rotation = is_shape ? (const T*)(D + o_rot) : nullptr;
+        a.g_origin = (T*)(R + r_origin); a.g_direction = (float*)(R + r_dir); a.g_direction_t = (T*)(R + r_dir_t); a.g_rotation = is_shape ? (T*)(R + r_rot) : nullptr;
+        SQ<T>& q = cs.q;
+        q = SQ<T>{};
+        q.cap = d.hit_cap; q.a = a.g_origin; q.b = a.g_direction_t; q.max_distance = (const T*)(D + o_md);
+        q.solid = is_shape ? nullptr : (const uint8_t*)(D + o_solid);
+        q.mask = d.mask ? (const uint32_t*)(D + o_mask) : nullptr;
+        q.excluded = (const uint32_t*)(D + o_ex); q.n_excluded = 0;
+        q.count = (uint32_t*)(R + r_count);
+        if (is_shape) { q.shape = (const uint8_t*)(D + o_shape); q.he = (const T*)(D + o_he); q.rot = a.g_rotation; q.cast = (SpatialShapeHit<T>*)(R + r_rec); }
+        else q.hits = (SpatialHit<T>*)(R + r_rec);
+        q.self_entity = (const uint32_t*)(D + o_self); q.ex_offset = (const uint32_t*)(D + o_off); q.kq = (const uint32_t*)(D + o_kq); q.live = (const uint8_t*)(D + o_live);
+        cs.records = R + r_rec;
+        cs.index_closest = (const uint32_t*)(D + o_closest); cs.index_many = (const uint32_t*)(D + o_many);
+        cs.n_closest = (uint32_t)closest.size(); cs.n_many = (uint32_t)many.size();
+        cs.any_body = any_body; cs.any_collider = any_collider; cs.max_body = max_body; cs.max_collider = max_collider;
+        cs.hit_cap = d.hit_cap;
+        cs.n = n;
+        return AVN_OK;
+    }
+    avn_status spatial_ray_casters_upload(const avn_spatial_ray_casters* c) override {
+        if (!c) { error = "spatial_ray_casters_upload: null argument"; return AVN_ERR_BAD_ARG; }
+        const CasterDef d{c->count, c->hit_cap, c->anchor_kind, c->anchor, c->origin, c->direction, c->max_distance, c->max_hits, c->solid, nullptr, nullptr, nullptr,
+                          c->enabled, c->mask, c->self_entity, c->excluded_offset, c->excluded};
+        return casters_upload(cs_ray, d, false, "spatial_ray_casters_upload");
+    }
+    avn_status spatial_shape_casters_upload(const avn_spatial_shape_casters* c) override {
+        if (!c) { error = "spatial_shape_casters_upload: null argument"; return AVN_ERR_BAD_ARG; }
+        const CasterDef d{c->count, c->hit_cap, c->anchor_kind, c->anchor, c->origin, c->direction, c->max_distance, c->max_hits, nullptr, c->shape, c->half_extents,
+                          c->shape_rotation, c->enabled, c->mask, c->self_entity, c->excluded_offset, c->excluded};
+        return casters_upload(cs_shape, d, true, "spatial_shape_casters_upload");
+    }
+    // snapshot, re-aim, cast: enqueued on the world's stream, nothing read back
+    avn_status spatial_casters_run(uint32_t flags) override {
+        cs_ran = false;
+        if (flags & ~(uint32_t)AVN_SPATIAL_SKIP_HOST_SHAPES) { error = "spatial_casters_run: flags may only be AVN_SPATIAL_SKIP_HOST_SHAPES"; return AVN_ERR_BAD_ARG; }
+        avn_status st = spatial_update();
+        if (st != AVN_OK) return st;
+        for (const CasterSet* cs : {&cs_ray, &cs_shape}) {
+            if (cs->n && ((cs->any_body && cs->max_body >= dw.n_bodies) || (cs->any_collider && cs->max_collider >= bp.n_colliders))) {
+                error = "spatial_casters_run: a caster's anchor is outside the current body / collider table (upload the casters again)"; return AVN_ERR_STATE;
+            }
+        }
+        if ((cs_ray.n || cs_shape.n) && (st = sp_check(flags)) != AVN_OK) return st;   // (no casters: the run is the update)
+        if (!b_cs_stats.p) {
+            hipError_t err;
+            b_cs_stats.ensure(4 * sizeof(unsigned long long), err);
+            if (err != hipSuccess) { error = std::string("spatial_casters_run: hipMalloc: ") + hipGetErrorName(err); return AVN_ERR_OOM; }
+        }
+        unsigned long long* stats = b_cs_stats.as<unsigned long long>();
+        HIPCHK(hipMemsetAsync(stats, 0, 4 * sizeof(unsigned long long), stream));
+        for (CasterSet* cs : {&cs_ray, &cs_shape}) {
+            if (!cs->n) continue;
+            const bool is_shape = cs == &cs_shape;
+            launch_spatial_reaim<T>(dw, sp, cs->a, stream);
+            SQ<T> q = cs->q;
+            q.stats = stats;
+            q.n = cs->n_closest; q.index = cs->index_closest;
+            launch_spatial_casters<T>(sp, q, is_shape ? SPQ_CAST : SPQ_CLOSEST, stream);
+            q.n = cs->n_many; q.index = cs->index_many;
+            launch_spatial_casters<T>(sp, q, is_shape ? SPQ_CAST_HITS : SPQ_HITS, stream);
+        }
+        HIPCHK(hipGetLastError());
+        cs_ran = true;
+        return AVN_OK;
+    }
+    avn_status casters_results_check(const char* who) {
+        if (!sp_valid || !cs_ran) { error = std::string(who) + ": no avn_spatial_casters_run since the tables or the casters last changed"; return AVN_ERR_STATE; }
+        return AVN_OK;
+    }
+    // waits for the run; its counters become the ones avn_spatial_stats_get reports
+    avn_status casters_finish() {
+        HIPCHK(hipMemcpyAsync(sp_visits, b_cs_stats.p, sizeof sp_visits, hipMemcpyDeviceToHost, stream));
+        HIPCHK(hipStreamSynchronize(stream));
+        if (sp_visits[2]) { error = "spatial casters: traversal stack overflow"; return AVN_ERR_CAPACITY; }
+        return AVN_OK;
+    }
+    avn_status casters_hits_get(const CasterSet& cs, size_t rec, uint32_t flags, void* hits, uint32_t* count, const char* who) {
+        if (flags & ~(uint32_t)AVN_SPATIAL_DEVICE_POINTERS) { error = std::string(who) + ": flags may only be AVN_SPATIAL_DEVICE_POINTERS"; return AVN_ERR_BAD_ARG; }
+        avn_status st = casters_results_check(who);
+        if (st != AVN_OK) return st;
+        if (cs.n && (!hits || !count)) { error = std::string(who) + ": null array"; return AVN_ERR_BAD_ARG; }
+        const hipMemcpyKind kind = (flags & AVN_SPATIAL_DEVICE_POINTERS) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+        if (cs.n) {
+            HIPCHK(hipMemcpyAsync(hits, cs.records, rec * cs.n * cs.hit_cap, kind, stream));
+            HIPCHK(hipMemcpyAsync(count, cs.q.count, 4 * (size_t)cs.n, kind, stream));
+        }
+        return casters_finish();
+    }
+    avn_status spatial_ray_caster_hits_get(uint32_t flags, const avn_spatial_hits_out* out) override {
+        if (!out) { error = "spatial_ray_caster_hits_get: null argument"; return AVN_ERR_BAD_ARG; }
+        return casters_hits_get(cs_ray, sizeof(SpatialHit<T>), flags, out->hits, out->count, "spatial_ray_caster_hits_get");
+    }
+    avn_status spatial_shape_caster_hits_get(uint32_t flags, const avn_spatial_shape_hits_out* out) override {
+        if (!out) { error = "spatial_shape_caster_hits_get: null argument"; return AVN_ERR_BAD_ARG; }
+        return casters_hits_get(cs_shape, sizeof(SpatialShapeHit<T>), flags, out->hits, out->count, "spatial_shape_caster_hits_get");
+    }
+    avn_status spatial_caster_poses_get(uint32_t kind, uint32_t flags, const avn_spatial_caster_poses_out* out) override {
+        if (!out || kind > AVN_SPATIAL_CASTER_SHAPE || (flags & ~(uint32_t)AVN_SPATIAL_DEVICE_POINTERS)) { error = "spatial_caster_poses_get: bad argument"; return AVN_ERR_BAD_ARG; }
+        avn_status st = casters_results_check("spatial_caster_poses_get");
+        if (st != AVN_OK) return st;
+        const CasterSet& cs = kind == AVN_SPATIAL_CASTER_SHAPE ? cs_shape : cs_ray;
+        if (cs.n && (!out->origin || !out->direction || (cs.a.g_rotation && !out->rotation))) { error = "spatial_caster_poses_get: null array"; return AVN_ERR_BAD_ARG; }
+        const hipMemcpyKind mk = (flags & AVN_SPATIAL_DEVICE_POINTERS) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+        if (cs.n) {
+            HIPCHK(hipMemcpyAsync(out->origin, cs.a.g_origin, 3 * sizeof(T) * cs.n, mk, stream));
+            HIPCHK(hipMemcpyAsync(out->direction, cs.a.g_direction, 12 * (size_t)cs.n, mk, stream));
+            if (cs.a.g_rotation) HIPCHK(hipMemcpyAsync(out->rotation, cs.a.g_rotation, 4 * sizeof(T) * cs.n, mk, stream));
+        }
+        return casters_finish();
+    }
+
     avn_status spatial_stats_get(avn_spatial_stats* o) override {
         if (!o) return AVN_ERR_BAD_ARG;
         std::memset(o, 0, sizeof *o);

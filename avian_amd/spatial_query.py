@@ -1,6 +1,7 @@
 """ctypes binding of ``include/avian_mi355x_spatial.h``: device spatial queries (ray casts, ray hits, point and AABB intersections, point
 projection, shape intersections, shape casts, shape contacts, depenetration, velocity projection, cast_move and move_and_slide) over the
-colliders a :class:`avian_amd._ffi.World` holds on the device.
+colliders a :class:`avian_amd._ffi.World` holds on the device, and the persistent RayCaster / ShapeCaster tables re-aimed and cast by
+``casters_run``.
 
 Numpy arrays in and out (copied through the library's staging), or torch tensors on the world's GPU (``AVN_SPATIAL_DEVICE_POINTERS``: the
 library reads and writes the tensors in place).  These entry points are not part of ``_ffi.ABI_SYMBOLS``: they live in their own header.
@@ -23,6 +24,8 @@ MAX_PLANES = 32
 MAX_SLIDE_ITERATIONS = 16
 SLIDE_TRUNCATED = 1
 MISS = 0xFFFFFFFF
+ANCHOR_WORLD, ANCHOR_BODY, ANCHOR_COLLIDER = 0, 1, 2
+CASTER_RAY, CASTER_SHAPE = 0, 1
 
 
 class avn_spatial_filter(C.Structure):
@@ -200,6 +203,21 @@ class avn_spatial_stats(C.Structure):
                 ("nodes_visited", C.c_uint64), ("leaves_visited", C.c_uint64)]
 
 
+class avn_spatial_ray_casters(C.Structure):
+    _fields_ = [("count", C.c_uint32), ("hit_cap", C.c_uint32), ("anchor_kind", vp), ("anchor", vp), ("origin", vp), ("direction", vp), ("max_distance", vp),
+                ("max_hits", vp), ("solid", vp), ("enabled", vp), ("mask", vp), ("self_entity", vp), ("excluded_offset", vp), ("excluded", vp)]
+
+
+class avn_spatial_shape_casters(C.Structure):
+    _fields_ = [("count", C.c_uint32), ("hit_cap", C.c_uint32), ("anchor_kind", vp), ("anchor", vp), ("origin", vp), ("direction", vp), ("max_distance", vp),
+                ("max_hits", vp), ("shape", vp), ("half_extents", vp), ("shape_rotation", vp), ("enabled", vp), ("mask", vp), ("self_entity", vp),
+                ("excluded_offset", vp), ("excluded", vp)]
+
+
+class avn_spatial_caster_poses_out(C.Structure):
+    _fields_ = [("origin", vp), ("direction", vp), ("rotation", vp)]
+
+
 STRUCTS = [avn_spatial_filter, avn_spatial_rays, avn_spatial_points, avn_spatial_aabbs, avn_spatial_hit_f32, avn_spatial_hit_f64,
            avn_spatial_hits_out, avn_spatial_ids_out, avn_spatial_stats, avn_spatial_solid_points, avn_spatial_shapes,
            avn_spatial_projection_f32, avn_spatial_projection_f64, avn_spatial_projections_out, avn_spatial_shape_casts,
@@ -208,11 +226,12 @@ STRUCTS = [avn_spatial_filter, avn_spatial_rays, avn_spatial_points, avn_spatial
            avn_spatial_depenetration_f32, avn_spatial_depenetration_f64, avn_spatial_depenetrations_out, avn_spatial_velocity_projections,
            avn_spatial_velocities_out, avn_spatial_moves, avn_spatial_move_hit_f32, avn_spatial_move_hit_f64, avn_spatial_move_hits_out,
            avn_spatial_characters, avn_spatial_move_and_slide_config, avn_spatial_slide_f32, avn_spatial_slide_f64, avn_spatial_slide_hit_f32,
-           avn_spatial_slide_hit_f64, avn_spatial_slides_out]
+           avn_spatial_slide_hit_f64, avn_spatial_slides_out, avn_spatial_ray_casters, avn_spatial_shape_casters, avn_spatial_caster_poses_out]
 SYMBOLS = ["avn_spatial_update", "avn_spatial_cast_rays", "avn_spatial_ray_hits", "avn_spatial_point_intersections",
            "avn_spatial_aabb_intersections", "avn_spatial_stats_get", "avn_spatial_project_points", "avn_spatial_shape_intersections",
            "avn_spatial_cast_shapes", "avn_spatial_shape_hits", "avn_spatial_shape_contacts", "avn_spatial_depenetrate", "avn_spatial_project_velocities",
-           "avn_spatial_cast_moves", "avn_spatial_move_and_slide"]
+           "avn_spatial_cast_moves", "avn_spatial_move_and_slide", "avn_spatial_ray_casters_upload", "avn_spatial_shape_casters_upload",
+           "avn_spatial_casters_run", "avn_spatial_ray_caster_hits_get", "avn_spatial_shape_caster_hits_get", "avn_spatial_caster_poses_get"]
 
 
 def hit_dtype(bits: int) -> np.dtype:
@@ -288,6 +307,12 @@ def _declare(dll):
     dll.avn_spatial_project_velocities.argtypes = [vp, vp, vp]
     dll.avn_spatial_cast_moves.argtypes = [vp, vp, vp]
     dll.avn_spatial_move_and_slide.argtypes = [vp, vp, vp, C.c_uint32, vp]
+    dll.avn_spatial_ray_casters_upload.argtypes = [vp, vp]
+    dll.avn_spatial_shape_casters_upload.argtypes = [vp, vp]
+    dll.avn_spatial_casters_run.argtypes = [vp, C.c_uint32]
+    dll.avn_spatial_ray_caster_hits_get.argtypes = [vp, C.c_uint32, vp]
+    dll.avn_spatial_shape_caster_hits_get.argtypes = [vp, C.c_uint32, vp]
+    dll.avn_spatial_caster_poses_get.argtypes = [vp, C.c_uint32, C.c_uint32, vp]
 
 
 class SpatialQuery:
@@ -315,6 +340,7 @@ class SpatialQuery:
         self.slide_dtype = slide_dtype(self.bits)
         self.slide_hit_dtype = slide_hit_dtype(self.bits)
         self._keep = []
+        self._casters = {CASTER_RAY: (0, 1), CASTER_SHAPE: (0, 1)}   # (count, hit_cap) of the last uploads
 
     # -- plumbing ------------------------------------------------------------------------------
     def _check(self, st: int):
@@ -642,6 +668,102 @@ class SpatialQuery:
         self._sync_torch(dev)
         self._check(self.dll.avn_spatial_move_and_slide(self.world.handle, C.byref(q), C.byref(cfg), int(hit_cap), C.byref(o)))
         return rec, hits
+
+    # -- casters ---------------------------------------------------------------------------------
+    def _caster_common(self, c, n, hit_cap, anchor_kind, anchor, origin, direction, max_distance, max_hits, enabled, mask, self_entity, ignore_self,
+                       excluded):
+        c.count = n
+        c.hit_cap = int(hit_cap)
+        anchor_kind = np.full(n, ANCHOR_WORLD, np.uint8) if anchor_kind is None else anchor_kind
+        c.anchor_kind = self._arr(anchor_kind, np.uint8, False, (n,))
+        c.anchor = self._arr(np.zeros(n, np.uint32) if anchor is None else anchor, np.uint32, False, (n,))
+        c.origin = self._arr(origin, self.dtype, False, (n, 3))
+        c.direction = self._arr(direction, np.float32, False, (n, 3))
+        c.max_distance = self._arr(np.full(n, np.inf) if max_distance is None else max_distance, self.dtype, False, (n,))
+        mh = np.full(n, MISS, np.uint32) if max_hits is None else np.minimum(np.asarray(max_hits, np.uint64), MISS).astype(np.uint32)   # (Avian's default: u32::MAX)
+        c.max_hits = self._arr(mh, np.uint32, False, (n,))
+        c.enabled = self._arr(enabled, np.uint8, False, (n,)) if enabled is not None else None
+        c.mask = self._arr(mask, np.uint32, False, (n,)) if mask is not None else None
+        if self_entity is not None:
+            own = np.asarray(self_entity, np.uint32).reshape(n)
+            if ignore_self is not None:   # RayCaster::ignore_self = false: the caster may hit its own entity
+                own = np.where(np.broadcast_to(np.asarray(ignore_self, bool), (n,)), own, np.uint32(MISS)).astype(np.uint32)
+            c.self_entity = self._arr(own, np.uint32, False, (n,))
+        if excluded is not None:
+            if len(excluded) != n:
+                raise ValueError("excluded: one array of entity indices per caster")
+            off = np.zeros(n + 1, np.uint32)
+            off[1:] = np.cumsum([len(e) for e in excluded])
+            flat = np.concatenate([np.asarray(e, np.uint32).reshape(-1) for e in excluded]) if n else np.zeros(0, np.uint32)
+            c.excluded_offset = self._arr(off, np.uint32, False)
+            c.excluded = self._arr(flat if len(flat) else np.zeros(1, np.uint32), np.uint32, False)
+
+    def ray_casters_upload(self, origin, direction, anchor_kind=None, anchor=None, max_distance=None, max_hits=None, solid=None, hit_cap=1, enabled=None,
+                           mask=None, self_entity=None, ignore_self=None, excluded=None):
+        """avn_spatial_ray_casters_upload: the world's RayCasters (numpy only: configuration).  ``origin`` [n, 3] and ``direction`` [n, 3]
+        (float32) are local to the anchor (``anchor_kind`` ANCHOR_WORLD / ANCHOR_BODY / ANCHOR_COLLIDER, ``anchor`` the table index);
+        ``max_hits`` defaults to u32::MAX (read as ``hit_cap``); ``self_entity`` [n] with ``ignore_self`` (a bool or [n], default True) is the
+        entity a caster never hits; ``excluded`` is a list of n arrays of entity indices.  n == 0 clears the table."""
+        n = int(np.asarray(origin).reshape(-1, 3).shape[0])
+        c = avn_spatial_ray_casters()
+        self._caster_common(c, n, hit_cap, anchor_kind, anchor, origin, direction, max_distance, max_hits, enabled, mask, self_entity, ignore_self, excluded)
+        c.solid = self._arr(np.ones(n, np.uint8) if solid is None else solid, np.uint8, False, (n,))
+        self._check(self.dll.avn_spatial_ray_casters_upload(self.world.handle, C.byref(c)))
+        self._casters[CASTER_RAY] = (n, max(int(hit_cap), 1))   # (only now: a rejected upload leaves the library's table, and the getters' sizes, as they were)
+
+    def shape_casters_upload(self, shape, half_extents, origin, shape_rotation, direction, anchor_kind=None, anchor=None, max_distance=None, max_hits=None,
+                             hit_cap=1, enabled=None, mask=None, self_entity=None, ignore_self=None, excluded=None):
+        """avn_spatial_shape_casters_upload: the world's ShapeCasters (AVN_SHAPE_CUBOID = 0 / AVN_SHAPE_BALL = 1, a ball's radius in
+        half_extents[:, 0]; ``shape_rotation`` [n, 4] xyzw, local); the other arguments as in :meth:`ray_casters_upload`."""
+        n = int(np.asarray(origin).reshape(-1, 3).shape[0])
+        c = avn_spatial_shape_casters()
+        self._caster_common(c, n, hit_cap, anchor_kind, anchor, origin, direction, max_distance, max_hits, enabled, mask, self_entity, ignore_self, excluded)
+        c.shape = self._arr(shape, np.uint8, False, (n,))
+        c.half_extents = self._arr(half_extents, self.dtype, False, (n, 3))
+        c.shape_rotation = self._arr(shape_rotation, self.dtype, False, (n, 4))
+        self._check(self.dll.avn_spatial_shape_casters_upload(self.world.handle, C.byref(c)))
+        self._casters[CASTER_SHAPE] = (n, max(int(hit_cap), 1))
+
+    def casters_run(self, skip_host_shapes=False):
+        """avn_spatial_casters_run: a new snapshot, every caster re-aimed from its anchor's pose, the enabled ones cast.  Only enqueues: the
+        results stay on the device until :meth:`ray_caster_hits` / :meth:`shape_caster_hits` / :meth:`caster_poses` fetch them."""
+        self._check(self.dll.avn_spatial_casters_run(self.world.handle, SKIP_HOST_SHAPES if skip_host_shapes else 0))
+
+    def _like(self, device):
+        import torch
+        return torch.empty(0, device=torch.device("cuda", max(int(self.world.cfg.device), 0)) if device is True else device)
+
+    def _caster_hits(self, kind, fn, rec_dtype, out_cls, device):
+        n, cap = self._casters[kind]
+        dev = device is not None and device is not False
+        like = self._like(device) if dev else None
+        hits, hp = self._out((n, cap), rec_dtype, dev, like)
+        cnt, cp = self._out((n,), np.uint32, dev, like)
+        o = out_cls(hp, cp)
+        self._check(fn(self.world.handle, DEVICE_POINTERS if dev else 0, C.byref(o)))
+        return hits, cnt
+
+    def ray_caster_hits(self, device=None):
+        """RayHits of the last run: (records [n, hit_cap] nearest first, ``hit_dtype``; counts [n]).  ``device`` (True or a torch device): the
+        answers as tensors on the GPU (records as uint8 [n, hit_cap, itemsize]), copied device to device."""
+        return self._caster_hits(CASTER_RAY, self.dll.avn_spatial_ray_caster_hits_get, self.hit_dtype, avn_spatial_hits_out, device)
+
+    def shape_caster_hits(self, device=None):
+        """ShapeHits of the last run: (records [n, hit_cap], ``shape_hit_dtype``; counts [n]); ``device`` as in :meth:`ray_caster_hits`."""
+        return self._caster_hits(CASTER_SHAPE, self.dll.avn_spatial_shape_caster_hits_get, self.shape_hit_dtype, avn_spatial_shape_hits_out, device)
+
+    def caster_poses(self, kind, device=None):
+        """The re-aimed casters of the last run: (global origins [n, 3], global directions [n, 3] float32) for CASTER_RAY, plus the global shape
+        rotations [n, 4] for CASTER_SHAPE."""
+        n, _ = self._casters[kind]
+        dev = device is not None and device is not False
+        like = self._like(device) if dev else None
+        org, op = self._out((n, 3), self.dtype, dev, like)
+        dr, dp = self._out((n, 3), np.float32, dev, like)
+        rot, rp = self._out((n, 4), self.dtype, dev, like)
+        o = avn_spatial_caster_poses_out(op, dp, rp)
+        self._check(self.dll.avn_spatial_caster_poses_get(self.world.handle, int(kind), DEVICE_POINTERS if dev else 0, C.byref(o)))
+        return (org, dr, rot) if kind == CASTER_SHAPE else (org, dr)
 
     def stats(self) -> avn_spatial_stats:
         s = avn_spatial_stats()

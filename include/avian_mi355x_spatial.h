@@ -197,7 +197,8 @@
  *
  * Filter (SpatialQueryFilter::test, query_filter.rs:97-101): a collider is a candidate when memberships & mask != 0 and its
  * entity_index is not in the excluded list.  ONE excluded list is shared by every query of a call (a caster's own entity goes in it for
- * RayCaster::ignore_self); per-query exclusion lists are not supported.
+ * RayCaster::ignore_self); per-query exclusion lists are not supported by the batched entry points.  The casters below carry their own
+ * self_entity and excluded list per caster.
  *
  * Ties: closest hit = smallest (distance, collider index); ray_hits = the max_hits nearest by (distance, collider index), sorted, plus
  * the true number of hits (Avian returns an arbitrary subset when truncated: nearest-k is a deterministic strengthening); point and AABB
@@ -205,6 +206,34 @@
  * smallest (distance, collider index); cast_shapes = the smallest (distance, collider index); shape_hits = the max_hits nearest by (distance,
  * collider index), sorted, plus the true number of hits (Avian's shape_hits repeats cast_shape, excluding each hit entity in turn: the same
  * list in exact arithmetic, here with a deterministic tie rule).  A collider index is its slot in the last avn_colliders_upload.
+ *
+ * Casters (the RayCaster / ShapeCaster components, spatial_query/ray_caster.rs, shape_caster.rs, mod.rs:236-435): a caster is defined once
+ * (avn_spatial_ray_casters_upload / avn_spatial_shape_casters_upload), anchored to nothing, to a body or to a collider, and every
+ * avn_spatial_casters_run re-aims it from its anchor's pose and casts it; the hits stay on the device until a getter asks for them.
+ *  - the run, on the world's stream, in Avian's order (caster positions, pipeline update, raycast, shapecast): (a) a new snapshot, as
+ *    avn_spatial_update takes it; (b) every caster, disabled ones too, is re-aimed from the poses that snapshot was taken from: a body anchor
+ *    from the body's position and rotation, a collider anchor from the snapshot's collider pose (collider_pose: a child collider through its
+ *    ColliderTransform), a world anchor not at all (its global values are its local ones, bit for bit); (c) the enabled ones are cast.
+ *    The run reads nothing back and does not wait for the device (the buffers of a world that grew are reallocated first, which does wait).
+ *  - re-aiming (update_ray_caster_positions / update_shape_caster_positions, `Mul<Dir> for Rotation`, physics_transform/transform.rs:899-904),
+ *    with (pos, rot) the anchor's pose, qrot and qmul the functions collider_pose uses, T the world's scalar:
+ *      global_origin = pos + qrot(rot, origin)                       per component, the rotation first
+ *      global_direction = (float) qrot(rot, (T) direction)           widened, rotated in T, each component rounded to float; NOT renormalised
+ *                                                                    (Dir::new_unchecked); widened again where the cast consumes it
+ *      global_shape_rotation = qmul(shape_rotation, rot)             the shape's rotation on the LEFT, as the reference writes it; NOT renormalised
+ *    A non-finite anchor pose gives a non-finite query, which answers a miss without traversing (the rules above).
+ *  - candidates of a caster: the snapshot's candidate flag, memberships & the caster's mask != 0, the entity not in the caster's own excluded
+ *    list, entity != self_entity (RayCaster::ignore_self).  Sensors stay candidates.
+ *  - answers, per caster with k = min(max_hits, hit_cap): k == 1: what avn_spatial_cast_rays / avn_spatial_cast_shapes answer, the smallest
+ *    (distance, collider index), count 0 or 1.  k > 1: what avn_spatial_ray_hits / avn_spatial_shape_hits answer with max_hits = k: the nearest
+ *    k, sorted, and the TRUE number of hits in count.  k == 0, or a disabled caster: count 0, no traversal.  Records are [count, hit_cap] in
+ *    caster order; slots past the answer are misses (both ids AVN_SPATIAL_MISS, the rest 0).  Avian's ShapeCaster loop of casts that exclude
+ *    each hit in turn gives the same list; its RayCaster keeps an arbitrary subset when truncated (nearest-k: the strengthening above).
+ *    NOT covered: target_distance, compute_contact_on_penetration, ignore_origin_penetration of ShapeCaster (the cast is cast_shapes': an overlap at
+ *    the start answers distance 0), caster shapes other than Ball / Cuboid, ChildOf chains other than the two anchors, running the casters from
+ *    avn_step, Rust declarations.
+ *  - avn_despawn renumbers bodies and colliders: it drops every caster definition (a call rejected before it changed anything keeps them).  Other table uploads keep them; a run whose anchors no
+ *    longer fit the tables is AVN_ERR_STATE.
  */
 #ifndef AVIAN_MI355X_SPATIAL_H
 #define AVIAN_MI355X_SPATIAL_H
@@ -592,6 +621,69 @@ AVN_API avn_status avn_spatial_cast_moves(avn_world* w, const avn_spatial_moves*
  * counters of avn_spatial_stats are the totals of all the call's launches. */
 AVN_API avn_status avn_spatial_move_and_slide(avn_world* w, const avn_spatial_characters* characters, const avn_spatial_move_and_slide_config* config, uint32_t hit_cap,
                                               const avn_spatial_slides_out* out);
+
+/* anchors of a caster and the two kinds of caster */
+enum { AVN_SPATIAL_ANCHOR_WORLD = 0, AVN_SPATIAL_ANCHOR_BODY = 1, AVN_SPATIAL_ANCHOR_COLLIDER = 2 };
+enum { AVN_SPATIAL_CASTER_RAY = 0, AVN_SPATIAL_CASTER_SHAPE = 1 };
+/* RayCaster definitions (ray_caster.rs).  Host pointers only: configuration, not per-step data. */
+typedef struct avn_spatial_ray_casters {
+    uint32_t count;                  /* n; 0 clears the ray casters */
+    uint32_t hit_cap;                /* record slots per caster, 1 .. AVN_SPATIAL_MAX_HITS */
+    const uint8_t* anchor_kind;      /* [n] AVN_SPATIAL_ANCHOR_* */
+    const uint32_t* anchor;          /* [n] body-table / collider-table index (ignored for a world anchor) */
+    const void* origin;              /* [3n] local origin, the world's scalar */
+    const float* direction;          /* [3n] local direction, unit (Dir is f32 in an f64 world too) */
+    const void* max_distance;        /* [n] (+inf is legal) */
+    const uint32_t* max_hits;        /* [n] 0 is legal (count 0); above hit_cap is read as hit_cap (Avian's default is u32::MAX) */
+    const uint8_t* solid;            /* [n] */
+    const uint8_t* enabled;          /* [n]; NULL = all enabled */
+    const uint32_t* mask;            /* [n]; NULL = LayerMask::ALL */
+    const uint32_t* self_entity;     /* [n] entity_index the caster never hits (ignore_self); NULL or AVN_SPATIAL_MISS = none */
+    const uint32_t* excluded_offset; /* [n + 1] CSR offsets into `excluded`, ascending from 0; NULL = no excluded entities */
+    const uint32_t* excluded;        /* [excluded_offset[n]] entity_index values; the library sorts each caster's slice */
+} avn_spatial_ray_casters;
+/* ShapeCaster definitions (shape_caster.rs) */
+typedef struct avn_spatial_shape_casters {
+    uint32_t count;
+    uint32_t hit_cap;
+    const uint8_t* anchor_kind;
+    const uint32_t* anchor;
+    const void* origin;              /* [3n] */
+    const float* direction;          /* [3n] */
+    const void* max_distance;        /* [n] */
+    const uint32_t* max_hits;        /* [n] */
+    const uint8_t* shape;            /* [n] AVN_SHAPE_CUBOID / AVN_SHAPE_BALL */
+    const void* half_extents;        /* [3n] (ball: radius in x) */
+    const void* shape_rotation;      /* [4n] xyzw, local */
+    const uint8_t* enabled;
+    const uint32_t* mask;
+    const uint32_t* self_entity;
+    const uint32_t* excluded_offset;
+    const uint32_t* excluded;
+} avn_spatial_shape_casters;
+/* the re-aimed casters of the last run */
+typedef struct avn_spatial_caster_poses_out {
+    void* origin;        /* [3n] global origins, the world's scalar */
+    float* direction;    /* [3n] global directions */
+    void* rotation;      /* [4n] global shape rotations (AVN_SPATIAL_CASTER_SHAPE only; ignored for rays, may be NULL) */
+} avn_spatial_caster_poses_out;
+
+/* Define the world's ray / shape casters (each call replaces the kind's whole table; count == 0 clears it).  An anchor outside its table, a
+ * hit_cap outside 1 .. AVN_SPATIAL_MAX_HITS, an anchor kind above 2 or offsets that do not ascend are AVN_ERR_BAD_ARG.  The results of an
+ * earlier run are dropped. */
+AVN_API avn_status avn_spatial_ray_casters_upload(avn_world* w, const avn_spatial_ray_casters* casters);
+AVN_API avn_status avn_spatial_shape_casters_upload(avn_world* w, const avn_spatial_shape_casters* casters);
+/* update_ray_caster_positions / update_shape_caster_positions, update_spatial_query_pipeline, raycast, shapecast (mod.rs:236-435): snapshot,
+ * re-aim, cast, all enqueued; nothing is read back.  flags: 0 or AVN_SPATIAL_SKIP_HOST_SHAPES.  Without casters it is avn_spatial_update.
+ * An anchor outside the current tables is AVN_ERR_STATE. */
+AVN_API avn_status avn_spatial_casters_run(avn_world* w, uint32_t flags);
+/* RayHits / ShapeHits of the last run: hits [n * hit_cap] in caster order, count [n].  flags: 0 or AVN_SPATIAL_DEVICE_POINTERS.  The getters
+ * wait for the run, return AVN_ERR_CAPACITY if its traversal overflowed, and make avn_spatial_stats_get report the run's totals.  Before any
+ * run, or after a table change that invalidated the snapshot, AVN_ERR_STATE. */
+AVN_API avn_status avn_spatial_ray_caster_hits_get(avn_world* w, uint32_t flags, const avn_spatial_hits_out* out);
+AVN_API avn_status avn_spatial_shape_caster_hits_get(avn_world* w, uint32_t flags, const avn_spatial_shape_hits_out* out);
+/* the re-aimed origins, directions and (shapes) rotations of the last run; kind: AVN_SPATIAL_CASTER_* */
+AVN_API avn_status avn_spatial_caster_poses_get(avn_world* w, uint32_t kind, uint32_t flags, const avn_spatial_caster_poses_out* out);
 /* snapshot sizes and the traversal counters of the last query call */
 AVN_API avn_status avn_spatial_stats_get(avn_world* w, avn_spatial_stats* out);
 

@@ -13,13 +13,18 @@
   project_velocities, 10^6 velocities against 0 .. 4 planes;  cast_moves and move_and_slide (4 rounds) for a crowd of 262144 characters in cfg2,
   beside the same work done through the older entry points (two depenetrate, then per round cast_shapes + shape_contacts), with the share of
   characters still live in each round
+  casters: 65536 ray casters with max_hits 1, 16384 with max_hits 4 and 16384 shape casters on random bodies of cfg2, all with ignore_self:
+  casters_run + the getters through device pointers, beside the same answers through the older entry points (bodies_download, the re-aiming in
+  numpy, ray_hits / shape_hits with k + 1 and the caster's own entity dropped on the host, uploads included; and the cheaper cast_rays /
+  ray_hits / cast_shapes with k, which cannot ignore the own entity), the two alternating, in wall-clock windows closed by a device
+  synchronisation; the host-side duration of the casters_run call alone, and the share of the run that is the LBVH build
 
 Every figure is the median over `reps` warmed-up calls.  The queries take torch tensors on the GPU (AVN_SPATIAL_DEVICE_POINTERS: no
 staging copies), so a call is its launches plus one stream synchronisation; the update is timed with avn_synchronize behind it.  Device
 events bracket the calls on torch's stream after a synchronisation of it, which the library's own stream joins at the call's end.
 bytes_floor: the bytes each call must move at least (inputs, outputs, the snapshot records a query touches once), for a roofline fraction
 against MI355X's 8 TB/s HBM.
-usage: python tools/time_spatial_queries.py [reps]"""
+usage: python tools/time_spatial_queries.py [reps] [casters]      (`casters`: that leg alone)"""
 import json
 import os
 import sys
@@ -32,7 +37,7 @@ sys.path.insert(0, R)
 import torch  # noqa: E402
 import avian_amd  # noqa: E402
 from avian_amd import _ffi as F, scenes  # noqa: E402
-from avian_amd.spatial_query import SpatialQuery  # noqa: E402
+from avian_amd.spatial_query import ANCHOR_BODY, MISS, SpatialQuery  # noqa: E402
 
 HBM = 8.0e12
 
@@ -53,6 +58,118 @@ def timed(fn, reps):
     return float(np.median(out))
 
 
+def qrot_np(q, v):
+    """avn_math.h's qrot over rows, in the arrays' dtype."""
+    b, w = q[:, :3], q[:, 3:4]
+    return v * (w * w - (b * b).sum(1, keepdims=True)) + b * ((v * b).sum(1, keepdims=True) * 2) + np.cross(b, v) * (w * 2)
+
+
+def qmul_np(l, r):
+    """avn_math.h's qmul (f32: glam's association) over rows."""
+    lx, ly, lz, lw = l.T
+    rx, ry, rz, rw = r.T
+    return np.stack([(lw * rx + lx * rw) + (ly * rz + -(lz * ry)), (lw * ry + -(lx * rz)) + (ly * rw + lz * rx), (lw * rz + lx * ry) + (-(ly * rx) + lz * rw),
+                     (lw * rw + -(lx * rx)) + (-(ly * ry) + -(lz * rz))], 1)
+
+
+def drop_own(hits, own, k):
+    """The first k records of each row whose entity is not the caster's own (what ignore_self costs a host that has k + 1 records)."""
+    keep = hits["entity"] != own[:, None]
+    order = np.argsort(~keep, axis=1, kind="stable")[:, :k]
+    out = np.take_along_axis(hits, order, 1)
+    out[~np.take_along_axis(keep, order, 1)] = (MISS, MISS, *([0] * (len(hits.dtype.names) - 2)))
+    return out
+
+
+def casters_leg(res, w2, sq, sc, reps):
+    rng = np.random.default_rng(7)
+    ent = np.asarray(sc.collider_kwargs()["entity_index"], np.uint32)
+    cbody = np.asarray(sc.collider_kwargs()["body"], np.int64)
+    own_of_body = np.full(w2.n_bodies, MISS, np.uint32); own_of_body[cbody] = ent
+    n1, n4, ns = 65536, 16384, 16384
+    nr = n1 + n4
+
+    def table(n):
+        a = rng.integers(1, w2.n_bodies, n).astype(np.uint32)
+        d = rng.normal(size=(n, 3)); d /= np.linalg.norm(d, axis=1, keepdims=True)
+        return a, (rng.normal(size=(n, 3)) * 0.1).astype(np.float32), d.astype(np.float32), np.full(n, 2.0, np.float32), own_of_body[a]
+    ra, ro, rd, rmd, rown = table(nr)
+    rk = np.r_[np.ones(n1, np.uint32), np.full(n4, 4, np.uint32)]
+    sa, so, sd, smd, sown = table(ns)
+    skind = (np.arange(ns) & 1).astype(np.uint8)
+    she = rng.uniform(0.05, 0.25, (ns, 3)).astype(np.float32)
+    srot = rng.normal(size=(ns, 4)); srot = (srot / np.linalg.norm(srot, axis=1, keepdims=True)).astype(np.float32)
+    sq.ray_casters_upload(ro, rd, anchor_kind=np.full(nr, ANCHOR_BODY, np.uint8), anchor=ra, max_distance=rmd, max_hits=rk, hit_cap=4, self_entity=rown)
+    sq.shape_casters_upload(skind, she, so, srot, sd, anchor_kind=np.full(ns, ANCHOR_BODY, np.uint8), anchor=sa, max_distance=smd, max_hits=np.ones(ns, np.uint32), hit_cap=1,
+                            self_entity=sown)
+    got = {}
+
+    def casters():
+        sq.casters_run()
+        got["rays"] = sq.ray_caster_hits(device=True)
+        got["shapes"] = sq.shape_caster_hits(device=True)
+
+    def reaimed():
+        b = w2.bodies_download()
+        return (b["position"][ra] + qrot_np(b["rotation"][ra], ro), qrot_np(b["rotation"][ra], rd), b["position"][sa] + qrot_np(b["rotation"][sa], so), qrot_np(b["rotation"][sa], sd),
+                qmul_np(srot, b["rotation"][sa]))
+
+    def emulated():          # the same answers: k + 1 records, the own entity dropped on the host
+        go, gd, gso, gsd, gsr = reaimed()
+        sq.update()
+        solid = np.ones(nr, np.uint8)
+        h1, _ = sq.ray_hits(go[:n1], gd[:n1], 2, rmd[:n1], solid[:n1])
+        h4, _ = sq.ray_hits(go[n1:], gd[n1:], 5, rmd[n1:], solid[n1:])
+        hs, _ = sq.shape_hits(skind, she, gso, gsr, gsd, 2, smd)
+        got["emulated"] = drop_own(h1, rown[:n1], 1), drop_own(h4, rown[n1:], 4), drop_own(hs, sown, 1)
+
+    def emulated_hitting_itself():   # the cheaper calls with k, which cannot ignore the own entity
+        go, gd, gso, gsd, gsr = reaimed()
+        sq.update()
+        solid = np.ones(nr, np.uint8)
+        sq.cast_rays(go[:n1], gd[:n1], rmd[:n1], solid[:n1]); sq.ray_hits(go[n1:], gd[n1:], 4, rmd[n1:], solid[n1:]); sq.cast_shapes(skind, she, gso, gsr, gsd, smd)
+
+    def upd():
+        sq.update()
+
+    def run_only():
+        sq.casters_run()
+    fns = {"casters_run_and_getters": casters, "emulated_k_plus_1": emulated, "emulated_hitting_itself": emulated_hitting_itself, "update_alone": upd, "casters_run_alone": run_only}
+    times = {k: [] for k in fns}
+    enqueue = []
+    for it in range(reps + 1):       # (round 0 warms every variant up)
+        for name, fn in fns.items():  # the variants alternate
+            torch.cuda.synchronize(); w2.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            t1 = time.perf_counter()
+            w2.synchronize(); torch.cuda.synchronize()
+            if it:
+                times[name].append((time.perf_counter() - t0) * 1e3)
+                if name == "casters_run_alone":
+                    enqueue.append((t1 - t0) * 1e3)
+    for name in fns:
+        res[f"casters_{name}_ms"] = float(np.median(times[name]))
+    res["casters_run_host_side_ms"] = float(np.median(enqueue))
+    res["casters_build_share_of_run"] = res["casters_update_alone_ms"] / res["casters_casters_run_alone_ms"]
+    res["casters_emulated_over_casters"] = res["casters_emulated_k_plus_1_ms"] / res["casters_casters_run_and_getters_ms"]
+    res["casters_timing"] = "median ms over reps rounds after a warm-up round, wall clock between device synchronisations, the variants alternating inside a round"
+    res["casters_counts"] = {"ray_max_hits_1": n1, "ray_max_hits_4": n4, "shape": ns}
+    casters()
+    st = sq.stats()
+    res["casters_leaves_per_caster"], res["casters_nodes_per_caster"] = st.leaves_visited / (nr + ns), st.nodes_visited / (nr + ns)
+    hr = got["rays"][0].cpu().numpy().reshape(-1).view(sq.hit_dtype).reshape(nr, 4)
+    hsd = got["shapes"][0].cpu().numpy().reshape(-1).view(sq.shape_hit_dtype).reshape(ns, 1)
+    res["casters_hit_share"] = {"rays": float((hr[:, 0]["collider"] != MISS).mean()), "shapes": float((hsd[:, 0]["collider"] != MISS).mean())}
+    # the emulation re-aims in numpy's operation order, not the device's: the colliders agree except where a rounding decides
+    e1, e4, es = got["emulated"]
+    res["casters_emulation_agreement"] = {"rays_k1": float((e1[:, 0]["collider"] == hr[:n1, 0]["collider"]).mean()), "rays_k4": float((e4["collider"] == hr[n1:]["collider"]).mean()),
+                                          "shapes": float((es[:, 0]["collider"] == hsd[:, 0]["collider"]).mean())}
+    sq.ray_casters_upload(np.zeros((0, 3)), np.zeros((0, 3), np.float32))
+    sq.shape_casters_upload(np.zeros(0, np.uint8), np.zeros((0, 3)), np.zeros((0, 3)), np.zeros((0, 4)), np.zeros((0, 3), np.float32))
+    sq.update()
+
+
 def world(sc, steps):
     lib = avian_amd.load_library()
     w = F.World(lib, F.default_config(32, substeps=4))
@@ -70,9 +187,15 @@ def main():
     reps = int(sys.argv[1]) if len(sys.argv) > 1 else 10
     dev = torch.device("cuda", 0)
     res = {"reps": reps, "timing": "median ms per call (device events on torch's stream around a synchronous call)"}
-    w2 = world(scenes.box_stack(50, 40, 50), 20)
+    sc2 = scenes.box_stack(50, 40, 50)
+    w2 = world(sc2, 20)
     C = w2.n_colliders
     sq = SpatialQuery(w2)
+    if "casters" in sys.argv[2:]:
+        del res["timing"]          # (device events: the other legs'; this one's is res["casters_timing"])
+        casters_leg(res, w2, sq, sc2, reps)
+        print(json.dumps(res))
+        return
 
     def upd():
         sq.update(); w2.synchronize()
@@ -214,6 +337,7 @@ def main():
         msk = k.replace("_bytes_floor", "_ms") if k.replace("_bytes_floor", "_ms") in res else None
         if msk:
             res[k.replace("_bytes_floor", "_hbm_fraction")] = res[k] / (res[msk] * 1e-3) / HBM
+    casters_leg(res, w2, sq, sc2, reps)
     del sq, w2
     w4 = world(scenes.sparse_mixed(1_000_000), 0)
     sq4 = SpatialQuery(w4)
