@@ -193,6 +193,33 @@ class avn_diagnostics(C.Structure):
                [(n, C.c_uint32) for n in ("contact_constraint_count", "contact_count", "per_system_valid", "reserved0")]
 
 
+# include/avian_mi355x_ccd.h (plain avn_swept_ccd_* functions: not part of ABI_SYMBOLS; avian_amd/swept_ccd.py wraps them)
+class avn_swept_ccd(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("count", C.c_uint32), ("body", vp), ("mode", vp), ("include_dynamic", vp), ("linear_threshold", vp),
+                ("angular_threshold", vp)]
+
+
+class avn_swept_ccd_result_f32(C.Structure):
+    _fields_ = [("toi", C.c_float), ("hit_collider", C.c_uint32), ("hit_body", C.c_int32), ("tested", C.c_uint32)]
+
+
+class avn_swept_ccd_result_f64(C.Structure):
+    _fields_ = [("toi", C.c_double), ("hit_collider", C.c_uint32), ("hit_body", C.c_int32), ("tested", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class avn_swept_ccd_results_out(C.Structure):
+    _fields_ = [("results", vp), ("capacity", C.c_uint32), ("count", C.c_uint32)]
+
+
+SWEPT_CCD_SYMBOLS = ("avn_swept_ccd_upload", "avn_swept_ccd_results_get")
+
+
+def declare_swept_ccd(dll):
+    for name in SWEPT_CCD_SYMBOLS:
+        getattr(dll, name).restype = C.c_int32
+        getattr(dll, name).argtypes = [vp, vp]
+
+
 class avn_slab_in(C.Structure):
     _fields_ = [("n_colliders", C.c_uint32), ("aabb_min_x", vp), ("aabb_max_x", vp), ("prev_order", vp), ("n_prev", C.c_uint32),
                 ("n_ranks", C.c_uint32), ("rank", C.c_uint32)]

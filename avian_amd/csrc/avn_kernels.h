@@ -558,4 +558,31 @@ template <class T> void launch_spatial_casters(const SP<T>&, const SQ<T>&, int k
 template <class T> void launch_spatial_contacts(const SP<T>&, const SC<T>&, hipStream_t, bool zero_stats = true);
 template <class T> void launch_spatial_depenetrate(const SD<T>&, hipStream_t);
 
+// ---- k_ccd.hip: swept CCD (solve_swept_ccd, dynamics/ccd/mod.rs:523-687; include/avian_mi355x_ccd.h) as a pass over the contact rows ----
+#define CCD_NONE 0xFFFFFFFFu
+template <class T> struct SweptCcdResult;   // == avn_swept_ccd_result_fNN; every byte of a record is written
+template <> struct SweptCcdResult<float> { float toi; uint32_t hit_collider; int32_t hit_body; uint32_t tested; };
+template <> struct SweptCcdResult<double> { double toi; uint32_t hit_collider; int32_t hit_body; uint32_t tested; uint32_t reserved; };
+template <class T> struct CCD {
+    uint32_t n;                          // entries, in the order of Query<Entity, With<SweptCcd>>
+    const uint32_t* body;                // [n]
+    const uint32_t* include_dynamic;     // [n]
+    const T *lin2, *ang2;                // [n] the thresholds squared (Scalar::powi(2))
+    uint32_t* own;                       // [n_bodies] the body's own collider: its lowest slot without a ColliderTransform | CCD_NONE
+    uint32_t* entry;                     // [n_colliders] the entry whose own collider the slot is | CCD_NONE
+    uint32_t* ctr;                       // [1] candidates found
+    uint32_t cand_cap;
+    uint2* cand;                         // [cand_cap] (row, entry << 1 | side); side 0: the CCD collider is the row's slot 1
+    unsigned long long* cand_t;          // [cand_cap] bits of the candidate's time of impact | CCD_T_NONE | CCD_T_ORIGIN
+    unsigned long long *min_t, *min_key; // [n] the smallest accepted time's bits; among its candidates the smallest (incoming << 63 | ~seq)
+    SweptCcdResult<T>* rec;              // [n]
+    uint32_t *wkey_a, *wval_a, *wkey_b, *wval_b;   // [2n] the writes (target body | n_bodies = none, 2 entry + side) and the sort's second pair
+    uint32_t *hist, *block_sums;         // the sort's scratch
+};
+#define CCD_T_NONE 0xFFFFFFFFFFFFFFFFull
+#define CCD_T_ORIGIN 0ull                // t == 0: the origin-penetration rule decides (k_ccd_origin)
+template <class T> void launch_ccd_tables(const DW<T>&, const BP<T>&, const CCD<T>&, hipStream_t);   // CCD::own / CCD::entry from the collider table
+// the pass: candidates, times of impact, winners, the writes in list order.  n_rows: the contact table's row high-water mark.  Returns the launches issued.
+template <class T> uint32_t launch_ccd_pass(const DW<T>&, const BP<T>&, const CT<T>&, const PG&, const CCD<T>&, const StepParams<T>&, uint32_t n_rows, hipStream_t);
+
 }  // namespace avn

@@ -43,5 +43,8 @@ AVN_API avn_status avn_spatial_ray_caster_hits_get(avn_world* w, uint32_t flags,
 AVN_API avn_status avn_spatial_shape_caster_hits_get(avn_world* w, uint32_t flags, const avn_spatial_shape_hits_out* o) { SP_GUARD(spatial_shape_caster_hits_get(flags, o)); }
 AVN_API avn_status avn_spatial_caster_poses_get(avn_world* w, uint32_t kind, uint32_t flags, const avn_spatial_caster_poses_out* o) { SP_GUARD(spatial_caster_poses_get(kind, flags, o)); }
 AVN_API avn_status avn_spatial_stats_get(avn_world* w, avn_spatial_stats* o) { SP_GUARD(spatial_stats_get(o)); }
+// include/avian_mi355x_ccd.h (world/ccd.hpp)
+AVN_API avn_status avn_swept_ccd_upload(avn_world* w, const avn_swept_ccd* l) { if (w && w->impl) w->impl->touched(); SP_GUARD(swept_ccd_upload(l)); }
+AVN_API avn_status avn_swept_ccd_results_get(avn_world* w, avn_swept_ccd_results_out* o) { SP_GUARD(swept_ccd_results_get(o)); }
 
 }  // extern "C"

@@ -265,6 +265,7 @@ template <class T> struct World : WorldBase {
         for (auto& e : ev) if (e) (void)hipEventDestroy(e);
         for (auto& e : ev_bias) if (e) (void)hipEventDestroy(e);
         for (auto& e : ev_dg) if (e) (void)hipEventDestroy(e);
+        if (ev_ccd) (void)hipEventDestroy(ev_ccd);
         for (auto& e : ev_dgs) if (e) (void)hipEventDestroy(e);
         if (ev_counters) (void)hipEventDestroy(ev_counters);
         if (h_counters) (void)hipHostFree(h_counters);
@@ -439,6 +440,7 @@ template <class T> struct World : WorldBase {
 #include "world/dshard.hpp"
 #include "world/timers.hpp"
 #include "world/spatial.hpp"
+#include "world/ccd.hpp"
 };
 
 template <class T> avn_status World<T>::diagnostics(avn_diagnostics* d) {
@@ -455,7 +457,8 @@ template <class T> avn_status World<T>::diagnostics(avn_diagnostics* d) {
     if (dg_stamped[DG_PREP1]) d->prepare_constraints_ms = ms(np ? ev_dg[DG_NP1] : ev[1], ev_dg[DG_PREP1]);
     if (dg_stamped[DG_INC1]) d->update_velocity_increments_ms = ms(ev_dg[DG_PREP1], ev_dg[DG_INC1]);
     d->substeps_ms = ms(ev[2], ev[3]);
-    if (dg_stamped[DG_REST1]) d->apply_restitution_ms = ms(ev_dg[DG_SUB1], ev_dg[DG_REST1]);
+    if (ccd_stamped && dg_stamped[DG_SUB1]) d->swept_ccd_ms = ms(ev_dg[DG_SUB1], ev_ccd);   // (only a world with a SweptCcd list stamps it)
+    if (dg_stamped[DG_REST1]) d->apply_restitution_ms = ms(ccd_stamped ? ev_ccd : ev_dg[DG_SUB1], ev_dg[DG_REST1]);
     if (dg_stamped[DG_FIN1]) d->finalize_ms = ms(ev_dg[DG_REST1], ev_dg[DG_FIN1]);
     if (dg_stamped[DG_STORE1]) d->store_impulses_ms = ms(ev_dg[DG_FIN1], ev_dg[DG_STORE1]);
     if (dg_substeps && !cfg.use_graph && !islands_active()) {

@@ -23,6 +23,7 @@
 
 #include "avn_kernels.h"
 #include "../../include/avian_mi355x_spatial.h"
+#include "../../include/avian_mi355x_ccd.h"
 
 namespace avn {
 
@@ -145,6 +146,9 @@ struct WorldBase {
     virtual avn_status spatial_shape_caster_hits_get(uint32_t flags, const avn_spatial_shape_hits_out*) = 0;
     virtual avn_status spatial_caster_poses_get(uint32_t kind, uint32_t flags, const avn_spatial_caster_poses_out*) = 0;
     virtual avn_status spatial_stats_get(avn_spatial_stats*) = 0;
+    // swept CCD (include/avian_mi355x_ccd.h; world/ccd.hpp)
+    virtual avn_status swept_ccd_upload(const avn_swept_ccd*) = 0;
+    virtual avn_status swept_ccd_results_get(avn_swept_ccd_results_out*) = 0;
 };
 
 // RCCL transport of the level-2 halo exchange (avn_comm.cpp; librccl is opened on first use)

@@ -35,6 +35,7 @@
             cap_bodies = (uint32_t)c;
             if (pipe_dev) { avn_status sg = pg_bcol_grow(); if (sg != AVN_OK) return sg; }   // bodies spawned inside the closed loop: their colour masks start empty
         }
+        if (dw.n_bodies != n) ccd_clear();   // (header: the SweptCcd list names body indices of the old table)
         if (dw.n_bodies != n && dw.lacc_l) { dw.lacc_l = dw.lacc_a = nullptr; graph_valid = false; }   // (header: an upload with another body count drops the local accelerations)
         if (moved || dw.n_bodies != n) graph_valid = false;
         if (have_bodies && n < dw.n_bodies && !after_despawn) {

@@ -58,6 +58,7 @@
         return AVN_OK;
     }
     avn_status colliders_upload(const avn_colliders* c) override {
+        ccd_tables_dirty = true;   // (swept CCD's per-collider entry table names the old slots)
         sp_valid = false;   // (the spatial-query snapshot names the old tables: avn_spatial_update again)
         slp_world_asleep = slp_world_idle = false;
         if (!have_bodies) { error = "colliders_upload before bodies_upload"; return AVN_ERR_STATE; }

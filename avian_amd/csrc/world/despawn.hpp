@@ -28,6 +28,7 @@
         if (despawn_broken) { error = "despawn: an earlier avn_despawn failed half-way; restart the closed loop (avn_pipeline_enable(0), uploads, avn_pipeline_enable(1))"; return AVN_ERR_STATE; }
         pg_new_ids_count = 0; last_timers.pair_count = 0;   // (the last step's new-pair ids may name rows that leave now: avn_pipeline_new_pair_ids_get reports an empty list until the next step)
         const avn_status ds = despawn_body(d);
+        if (ds == AVN_OK || despawn_mutating) ccd_clear();   // (so would the SweptCcd list's bodies)
         if (ds == AVN_OK || despawn_mutating) casters_clear();   // (bodies and colliders are renumbered: the casters' anchors would name other ones; a rejected call keeps them)
         if (ds != AVN_OK && despawn_mutating) despawn_broken = true;
         despawn_mutating = false;

@@ -178,6 +178,7 @@
     DevBuf b_col_lpos, b_col_lrot;
     bool tf_any = false;
     avn_status collider_transforms_upload(const avn_collider_transforms* t) override {
+        ccd_tables_dirty = true;   // (a body's own collider is its lowest slot WITHOUT a transform)
         sp_valid = false;   // (the spatial-query snapshot names the old tables: avn_spatial_update again)
         HIPCHK(hipStreamSynchronize(stream)); HIPCHK(hipStreamSynchronize(stream_bp));
         if (!t || !t->count) { bp.col_lpos = nullptr; bp.col_lrot = nullptr; tf_any = false; return AVN_OK; }

@@ -289,6 +289,7 @@
         if ((st = run_substeps()) != AVN_OK) return st;
         HIPCHK(hipEventRecord(ev[3], stream));
         stamp(DG_SUB1);
+        if (ccd.n && (st = ccd_pass()) != AVN_OK) return st;   // solve_swept_ccd: after PostSubstep, before Restitution (ccd/mod.rs:257-261)
         launch_clear_increments<T>(dw, stream); ++launches;
         // restitution == 0 everywhere: every manifold would early-out.  (Level 2: the exchanges are collective and `any_restitution` is a
         // per-rank fact, so the pass always runs there; a rank without restitution launches kernels whose lanes all early-out.)
@@ -339,6 +340,7 @@
             case AVN_SYS_NARROW_PHASE: if ((st = narrow_phase()) != AVN_OK) return st; break;
             case AVN_SYS_SUBSTEP: substep(); break;
             case AVN_SYS_SOLVER: {
+                ccd_stamped = false;
                 HIPCHK(hipEventRecord(ev[0], stream)); HIPCHK(hipEventRecord(ev[1], stream));
                 if ((st = solver()) != AVN_OK) return st;
                 HIPCHK(hipEventRecord(ev[4], stream));
@@ -360,6 +362,7 @@
     avn_status run_system(avn_system sys) override {
         avn_status st = need_bodies();
         if (st != AVN_OK) return st;
+        if (sys == AVN_SYS_SOLVER && ccd.n && !ccd_closed_loop()) { error = "run_system: a SweptCcd list needs the device closed loop (avn_pipeline_enable(1)); avn_swept_ccd_upload(NULL) clears it"; return AVN_ERR_STATE; }
         if (despawn_needs_joints) { error = "run_system: avn_despawn removed joints: upload the remaining joints (avn_joints_upload) first"; return AVN_ERR_STATE; }
         if (despawn_broken) { error = "run_system: an avn_despawn failed half-way; restart the closed loop"; return AVN_ERR_STATE; }
         if ((st = rebuild_joint_schedules()) != AVN_OK) return st;
@@ -394,8 +397,9 @@
     avn_status step() override {
         avn_status st = need_bodies();
         if (st != AVN_OK) return st;
+        if (ccd.n && !ccd_closed_loop()) { error = "avn_step: a SweptCcd list needs the device closed loop (avn_pipeline_enable(1)); avn_swept_ccd_upload(NULL) clears it"; return AVN_ERR_STATE; }
         for (bool& b : dg_stamped) b = false;
-        dg_np = false;
+        dg_np = false; ccd_stamped = false;
         if (pipe_on) return pipe_dev ? pipeline_step_device() : pipeline_step();
         launches = 0;
         static const bool host_trace = avn_env("AVN_HOST_TRACE") != nullptr;   // debugging aid: where the HOST spends a step (us since the call)

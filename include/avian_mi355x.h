@@ -589,7 +589,7 @@ typedef struct avn_diagnostics {
     double apply_restitution_ms;           /* clear_velocity_increments + solve_restitution */
     double finalize_ms;                    /* writeback_solver_bodies + writeback_joint_forces */
     double store_impulses_ms;
-    double swept_ccd_ms;                   /* always 0: SweptCcd is outside the path */
+    double swept_ccd_ms;                   /* solve_swept_ccd: the pass of avian_mi355x_ccd.h, from the end of the substep loop; apply_restitution_ms then starts where it ends.  0 for a world without a SweptCcd list (nothing is launched or stamped) */
     double substeps_ms;                    /* the whole substep loop (always filled) */
     double broad_phase_ms;                 /* CollisionDiagnostics::broad_phase: update_aabb + collect_collision_pairs */
     double narrow_phase_ms;                /* CollisionDiagnostics::narrow_phase: update_contacts + the status-change processing (closed loop only) */

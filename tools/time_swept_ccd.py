@@ -1,0 +1,101 @@
+#!/usr/bin/env python3
+"""What swept CCD (include/avian_mi355x_ccd.h) costs on cfg2's settled device closed loop (50 x 40 x 50 unit cubes on a ground).
+
+usage: python tools/time_swept_ccd.py MODE [repeats]
+  nolist          no SweptCcd list: `repeats` windows of 100 steps without a synchronisation in between, after 100 settling steps.  Run it with
+                  AVN_LIB_PATH=<the parent commit's library> AVN_AB_OLDER_LIBRARY=1 for the other side of a same-box A/B: this tree adds no
+                  launch, event or allocation without a list, so the two must sit within the spread of their own repeats.
+  all             every body listed (the ground has no SolverBody and is skipped on the device): the same windows.
+  bullets         1 000 balls (r = 0.1, AVN_COLLIDER_SWEPT_CCD, SpeculativeMargin 0) parked over the pile from the start, listed, and fired
+                  down at 300 units / s after the settling steps: per step the wall time, swept_ccd_ms and the number of entries with a hit.
+  bullets_nolist  the same scene and shots without the list (what the steps cost when the bullets tunnel into the pile instead).
+One JSON line per run."""
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import avian_amd
+from avian_amd import _ffi as F, scenes
+
+SETTLE, WINDOW, N_BULLETS = 100, 100, 1000
+
+
+def tables(with_bullets):
+    sc = scenes.box_stack(50, 40, 50)
+    bodies, cols = sc.body_kwargs(), sc.collider_kwargs()
+    n = sc.n
+    bullets = np.zeros(0, np.uint32)
+    if with_bullets:
+        k = N_BULLETS
+        side = int(np.ceil(np.sqrt(k)))
+        gx, gz = np.meshgrid(np.arange(side), np.arange(side), indexing="ij")
+        pos = np.stack([(gx.ravel()[:k] - (side - 1) * 0.5) * 1.5, np.full(k, 40 * 0.99 + 6.0), (gz.ravel()[:k] - (side - 1) * 0.5) * 1.5], axis=1)
+        ident = np.tile([0.0, 0, 0, 1], (k, 1))
+        add = dict(position=pos, rotation=ident, linear_velocity=np.zeros((k, 3)), angular_velocity=np.zeros((k, 3)), inv_mass=np.full(k, 1 / 0.004),
+                   inv_inertia_local=np.tile([1 / 1.6e-5, 0, 0, 1 / 1.6e-5, 0, 1 / 1.6e-5], (k, 1)), rb_type=np.zeros(k, np.uint8))
+        bodies = {key: np.concatenate([np.asarray(v), add[key]]) for key, v in bodies.items()}
+        bodies["gravity_scale"] = np.concatenate([np.ones(n), np.zeros(k)])   # parked until they are fired
+        he = np.zeros((k, 3)); he[:, 0] = 0.1
+        cols = dict(entity_index=np.arange(n + k, dtype=np.uint32), body=np.arange(n + k, dtype=np.int32), shape=np.concatenate([cols["shape"], np.full(k, F.SHAPE_BALL, np.uint8)]),
+                    half_extents=np.concatenate([cols["half_extents"], he]), collider_flags=np.concatenate([np.zeros(n, np.uint8), np.full(k, F.COLLIDER_SWEPT_CCD, np.uint8)]),
+                    speculative_margin=np.concatenate([np.full(n, -1.0), np.zeros(k)]))
+        bullets = np.arange(n, n + k, dtype=np.uint32)
+    return bodies, cols, n, bullets
+
+
+def main():
+    mode = sys.argv[1] if len(sys.argv) > 1 else "nolist"
+    repeats = int(sys.argv[2]) if len(sys.argv) > 2 else 5
+    with_bullets = mode.startswith("bullets")
+    lib = avian_amd.load_library()
+    bodies, cols, n, bullets = tables(with_bullets)
+    w = F.World(lib, F.default_config(32, substeps=4))
+    w.bodies_upload(**bodies); w.colliders_upload(**cols)
+    w.existing_pairs_upload(np.zeros(0, np.uint64)); w.collider_materials_upload(friction=0.5)
+    w.pipeline_enable()
+    ccd = None
+    if mode in ("all", "bullets"):
+        from avian_amd.swept_ccd import SweptCcd
+        ccd = SweptCcd(w)
+        ccd.upload(bullets if mode == "bullets" else np.arange(n, dtype=np.uint32))
+    for _ in range(SETTLE):
+        w.step()
+    w.synchronize()
+    out = dict(mode=mode, library=os.path.relpath(lib.path), bodies=len(bodies["inv_mass"]), listed=0 if ccd is None else ccd.count)
+    if not with_bullets:
+        ms = []
+        for _ in range(repeats):
+            t0 = time.perf_counter()
+            for _ in range(WINDOW):
+                w.step()
+            w.synchronize()
+            ms.append((time.perf_counter() - t0) / WINDOW * 1e3)
+        out.update(window_steps=WINDOW, ms_per_step=[round(x, 4) for x in ms], median=round(float(np.median(ms)), 4), spread=round(max(ms) - min(ms), 4))
+        if ccd is not None:
+            rec = ccd.results()
+            out.update(swept_ccd_ms=round(w.diagnostics().swept_ccd_ms, 4), tested=int(rec["tested"].sum()), hits=int((rec["hit_body"] >= 0).sum()))
+    else:
+        state = w.bodies_download()
+        kw = dict(bodies)
+        for key in ("position", "rotation", "linear_velocity", "angular_velocity"):
+            kw[key] = state[key].astype(np.float64)
+        kw["linear_velocity"][bullets] = [0.0, -300.0, 0.0]
+        w.bodies_upload(**kw)
+        rows = []
+        for s in range(repeats * 2):
+            t0 = time.perf_counter(); w.step(); w.synchronize(); wall = (time.perf_counter() - t0) * 1e3
+            row = dict(step=s, wall_ms=round(wall, 3), device_step_ms=round(w.timers().step_ms, 3))
+            if ccd is not None:
+                rec = ccd.results()
+                row.update(swept_ccd_ms=round(w.diagnostics().swept_ccd_ms, 4), tested=int(rec["tested"].sum()), hits=int((rec["hit_body"] >= 0).sum()))
+            rows.append(row)
+        out.update(steps=rows, lowest_bullet_y=round(float(w.bodies_download()["position"][bullets, 1].min()), 3))
+    print(json.dumps(out), flush=True)
+
+
+if __name__ == "__main__":
+    main()
