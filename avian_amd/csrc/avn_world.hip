@@ -296,8 +296,10 @@ template <class T> struct World : WorldBase {
         if (const char* e = avn_env("AVN_ISLAND_MAX_MANIFOLDS")) island_max_manifolds = (size_t)strtoull(e, nullptr, 10);
         if (const char* e = avn_env("AVN_ISLAND_MAX_BODIES_TOTAL")) island_max_bodies_total = (size_t)strtoull(e, nullptr, 10);
         if (const char* e = avn_env("AVN_ISLAND_PACK_BODIES")) island_pack_bodies = std::min<uint32_t>(ISLAND_MAX_BODIES, std::max<uint32_t>(1u, (uint32_t)strtoul(e, nullptr, 10)));
-        // (CU masks -- 64 CUs for the broad phase, 192 for the solver -- were tried for the overlap below and lost: a colour launch
-        //  on 192 CUs is 12 % slower than on 256, more than the contention it avoids; tools/cumask_probe.hip)
+        // (Tried for the overlap below and lost: CU masks -- 64 CUs for the broad phase, 192 for the solver: a colour launch on 192 CUs is 12 % slower
+        //  than on 256, more than the contention it avoids; tools/cumask_probe.hip.  Round 7, priorities: `stream` at the greatest and `stream_bp` at the
+        //  least stream priority cost cfg2 ~1 % (2 582-2 614 against 2 610-2 636 substeps/s); s_setprio(3) in the colour passes, the warm start and
+        //  integrate_positions stayed inside the noise (2 626-2 649).  profiles/r07_prepare_priority_ab_same_box.txt)
         HIPCHK(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
         HIPCHK(hipStreamCreateWithFlags(&stream_bp, hipStreamNonBlocking));
         bs = stream;

@@ -120,113 +120,133 @@ template <class T> __device__ __forceinline__ V3<T> velocity_at_point(const Body
 // (plugin.rs:389-398) -- what k_gather_manifolds used to copy into the colour-major arrays first (64 us + 26 MB written and read back per
 // settled cfg2 step).  The headers the solve passes read every substep (m_bodies, m_n, m_tv, m_meta) are still laid out colour-major here;
 // the anchors / penetrations / warm-start impulses are only ever read by this kernel and are no longer copied.
+//
+// THE COUNTER (round 7): DW::constraint_count is ONE address, and a device-scope atomic on one address costs ~11.5 ns whoever issues it.  With one atomic
+// per wave -- 10 600 at cfg2 -- the kernel took 139 us for 422 MB, 3.0 TB/s, with waves parked in s_waitcnt (55 %) or stalled at issue (38 %); a form with
+// four lanes per manifold and so four times the waves took 490 us for the same bytes (profiles/r07_prepare_priority_ab_same_box.txt).  So a workgroup walks
+// PREP_TILES_PER_BLOCK tiles of 256 manifolds (stride = the grid: the resident workgroups sweep the arrays side by side), keeps its waves' counts in
+// scalar registers and issues ONE atomic at its end: 663 at cfg2, 72 us, 5.8 TB/s.  (With the counter out of the way the four-lane form reaches 80 us --
+// twice the load instructions for the same bytes -- and was not kept.)
+#define PREP_TILE 256
+#define PREP_TILES_PER_BLOCK 4
 template <class T, bool ROWS>
-__global__ __launch_bounds__(256) void k_prepare_contact_constraints(DW<T> w, StepParams<T> p, RowsView<T> rv) {
-    uint32_t m = blockIdx.x * 256 + threadIdx.x;
-    bool generated = false;
+__global__ __launch_bounds__(PREP_TILE) void k_prepare_contact_constraints(DW<T> w, StepParams<T> p, RowsView<T> rv) {
+    uint32_t count = 0;   // wave-uniform: the constraints this wave generated
     // handle mode: the live manifold count is the device's (the colour offsets k_pg_build_handles / the upload left); DW::n_manifolds may be the
     // host's UPPER BOUND of it -- the device closed loop launches this kernel before it has read the step's counts back
     uint32_t n_live = w.n_manifolds;
     if (ROWS) n_live = min(n_live, w.color_offsets[AVN_GRAPH_COLOR_COUNT]);
-    if (m < n_live) {
-        uint32_t row = 0;
-        if (ROWS) {
-            row = rv.handles[m];
-            const uint4 meta = rv.meta[row];
-            const uint32_t npr = (meta.w & 0xFFu) ? ((meta.w >> 8) & 0xFFu) : 0u;
-            w.m_bodies[m] = make_int2((int)rv.col_info[meta.x].y, (int)rv.col_info[meta.y].y);
-            w.m_n[m] = rv.rows[(size_t)row * AVN_CT_ROW_V4];
-            w.m_tv[m] = rv.rows[(size_t)row * AVN_CT_ROW_V4 + 1];
-            w.m_meta[m] = npr | (((meta.z & AVN_CP_GENERATE_CONSTRAINTS) ? (uint32_t)AVN_MANIFOLD_GENERATES_CONSTRAINTS : 0u) << 8);
-        }
-        uint32_t mm = w.m_meta[m];
-        uint32_t np = mm & 7u, mflags = mm >> 8;
-        int2 b = w.m_bodies[m];
-        uint32_t meta1 = w.bmeta[b.x], meta2 = w.bmeta[b.y];
-        bool skip = !(mflags & AVN_MANIFOLD_GENERATES_CONSTRAINTS) || !meta_active(meta1) || !meta_active(meta2) ||
-                    (meta_rb_type(meta1) != AVN_RB_DYNAMIC && meta_rb_type(meta2) != AVN_RB_DYNAMIC) || np == 0;
-        if (skip) {
-            w.c_h1[m] = make4<T>(0, 0, 0, bits_to_scalar(0u, T(0)));
-            w.c_reldom[m] = 0;
-        } else {
-            bool nobody1 = !meta_has_solver_body(meta1), nobody2 = !meta_has_solver_body(meta2);
-            // SolverBodyInertia (DUMMY rows were written by k_prepare_solver_bodies for bodies without a SolverBody)
-            Vec4<T> sa1 = w.si_a[b.x], sb1 = w.si_b[b.x], sa2 = w.si_a[b.y], sb2 = w.si_b[b.y];
-            uint32_t if1 = scalar_to_bits(sb1.w), if2 = scalar_to_bits(sb2.w);
-            int dom1 = (int)(int16_t)(if1 >> 16), dom2 = (int)(int16_t)(if2 >> 16);
-            int relative_dominance = dom1 - dom2;
-            V3<T> inv_mass1 = effective_inv_mass<T>(sa1.x, if1), inv_mass2 = effective_inv_mass<T>(sa2.x, if2);
-            Sym3<T> i1{sa1.y, sa1.z, sa1.w, sb1.x, sb1.y, sb1.z}, i2{sa2.y, sa2.z, sa2.w, sb2.x, sb2.y, sb2.z};
-            if (relative_dominance > 0) { inv_mass1 = vzero<T>(); i1 = sym_zero<T>(); }
-            else if (relative_dominance < 0) { inv_mass2 = vzero<T>(); i2 = sym_zero<T>(); }
-            SoftCoef<T> soft = relative_dominance != 0 ? p.soft_non_dynamic : p.soft_dynamic;
-            (void)soft;  // coefficients are step constants: only the choice is stored per manifold
-            V3<T> w_sum = inv_mass1 + inv_mass2;
-            Vec4<T> n4 = w.m_n[m];
-            V3<T> normal = xyz<T>(n4);
-            T friction = n4.w;
-            // compute_tangent_directions (contact/mod.rs:427-449) from the LinearVelocity COMPONENTS
-            V3<T> force_direction = -normal;
-            V3<T> relative_velocity = xyz<T>(w.lvel[b.x]) - xyz<T>(w.lvel[b.y]);
-            V3<T> tangent_velocity = relative_velocity - force_direction * dot(force_direction, relative_velocity);
-            V3<T> t0;
-            if (!try_normalize(tangent_velocity, t0)) t0 = any_orthonormal_vector(force_direction);
-            V3<T> t1 = cross(force_direction, t0);
-            bool warm = p.match_contacts != 0;
-            bool has_tangent = friction > T(0);
-            uint32_t S = w.m_stride;
-            // all twelve point records up front (slots >= np are allocated, merely unused): one memory level for the
-            // whole manifold instead of one per point iteration
-            Vec4<T> pa1[AVN_MAX_MANIFOLD_POINTS], pa2[AVN_MAX_MANIFOLD_POINTS], pww[AVN_MAX_MANIFOLD_POINTS];
-#pragma unroll
-            for (uint32_t k = 0; k < AVN_MAX_MANIFOLD_POINTS; ++k) {
-                if (ROWS) { const Vec4<T>* __restrict__ r = rv.rows + (size_t)row * AVN_CT_ROW_V4; pa1[k] = r[2 + k]; pa2[k] = r[6 + k]; pww[k] = r[10 + k]; }
-                else { uint32_t s = k * S + m; pa1[k] = w.mp_a1[s]; pa2[k] = w.mp_a2[s]; pww[k] = w.mp_w[s]; }
+    const uint32_t n_tiles = (n_live + PREP_TILE - 1u) / PREP_TILE;
+    for (uint32_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        const uint32_t m = tile * PREP_TILE + threadIdx.x;
+        bool generated = false;
+        if (m < n_live) {
+            uint32_t row = 0;
+            if (ROWS) {
+                row = rv.handles[m];
+                const uint4 meta = rv.meta[row];
+                const uint32_t npr = (meta.w & 0xFFu) ? ((meta.w >> 8) & 0xFFu) : 0u;
+                w.m_bodies[m] = make_int2((int)rv.col_info[meta.x].y, (int)rv.col_info[meta.y].y);
+                w.m_n[m] = rv.rows[(size_t)row * AVN_CT_ROW_V4];
+                w.m_tv[m] = rv.rows[(size_t)row * AVN_CT_ROW_V4 + 1];
+                w.m_meta[m] = npr | (((meta.z & AVN_CP_GENERATE_CONSTRAINTS) ? (uint32_t)AVN_MANIFOLD_GENERATES_CONSTRAINTS : 0u) << 8);
             }
+            uint32_t mm = w.m_meta[m];
+            uint32_t np = mm & 7u, mflags = mm >> 8;
+            int2 b = w.m_bodies[m];
+            uint32_t meta1 = w.bmeta[b.x], meta2 = w.bmeta[b.y];
+            bool skip = !(mflags & AVN_MANIFOLD_GENERATES_CONSTRAINTS) || !meta_active(meta1) || !meta_active(meta2) ||
+                        (meta_rb_type(meta1) != AVN_RB_DYNAMIC && meta_rb_type(meta2) != AVN_RB_DYNAMIC) || np == 0;
+            if (skip) {
+                w.c_h1[m] = make4<T>(0, 0, 0, bits_to_scalar(0u, T(0)));
+                w.c_reldom[m] = 0;
+            } else {
+                bool nobody1 = !meta_has_solver_body(meta1), nobody2 = !meta_has_solver_body(meta2);
+                // SolverBodyInertia (DUMMY rows were written by k_prepare_solver_bodies for bodies without a SolverBody)
+                Vec4<T> sa1 = w.si_a[b.x], sb1 = w.si_b[b.x], sa2 = w.si_a[b.y], sb2 = w.si_b[b.y];
+                uint32_t if1 = scalar_to_bits(sb1.w), if2 = scalar_to_bits(sb2.w);
+                int dom1 = (int)(int16_t)(if1 >> 16), dom2 = (int)(int16_t)(if2 >> 16);
+                int relative_dominance = dom1 - dom2;
+                V3<T> inv_mass1 = effective_inv_mass<T>(sa1.x, if1), inv_mass2 = effective_inv_mass<T>(sa2.x, if2);
+                Sym3<T> i1{sa1.y, sa1.z, sa1.w, sb1.x, sb1.y, sb1.z}, i2{sa2.y, sa2.z, sa2.w, sb2.x, sb2.y, sb2.z};
+                if (relative_dominance > 0) { inv_mass1 = vzero<T>(); i1 = sym_zero<T>(); }
+                else if (relative_dominance < 0) { inv_mass2 = vzero<T>(); i2 = sym_zero<T>(); }
+                SoftCoef<T> soft = relative_dominance != 0 ? p.soft_non_dynamic : p.soft_dynamic;
+                (void)soft;  // coefficients are step constants: only the choice is stored per manifold
+                V3<T> w_sum = inv_mass1 + inv_mass2;
+                Vec4<T> n4 = w.m_n[m];
+                V3<T> normal = xyz<T>(n4);
+                T friction = n4.w;
+                // compute_tangent_directions (contact/mod.rs:427-449) from the LinearVelocity COMPONENTS
+                V3<T> force_direction = -normal;
+                V3<T> relative_velocity = xyz<T>(w.lvel[b.x]) - xyz<T>(w.lvel[b.y]);
+                V3<T> tangent_velocity = relative_velocity - force_direction * dot(force_direction, relative_velocity);
+                V3<T> t0;
+                if (!try_normalize(tangent_velocity, t0)) t0 = any_orthonormal_vector(force_direction);
+                V3<T> t1 = cross(force_direction, t0);
+                bool warm = p.match_contacts != 0;
+                bool has_tangent = friction > T(0);
+                uint32_t S = w.m_stride;
+                // all twelve point records up front (slots >= np are allocated, merely unused): one memory level for the
+                // whole manifold instead of one per point iteration
+                Vec4<T> pa1[AVN_MAX_MANIFOLD_POINTS], pa2[AVN_MAX_MANIFOLD_POINTS], pww[AVN_MAX_MANIFOLD_POINTS];
 #pragma unroll
-            for (uint32_t k = 0; k < AVN_MAX_MANIFOLD_POINTS; ++k) {
-                if (k >= np) break;
-                uint32_t s = k * S + m;
-                Vec4<T> a1 = pa1[k], a2 = pa2[k], ww = pww[k];
-                V3<T> r1 = xyz<T>(a1), r2 = xyz<T>(a2);
-                T penetration = a1.w, normal_speed = a2.w;
-                // ContactNormalPart::generate
-                V3<T> r1_cross_n = cross(r1, normal), r2_cross_n = cross(r2, normal);
-                T k_linear = dot(normal, cmul(w_sum, normal));
-                T kk = k_linear + dot(r1_cross_n, smul(i1, r1_cross_n)) + dot(r2_cross_n, smul(i2, r2_cross_n));
-                T eff_mass = recip_or_zero(kk);
-                T ni = warm ? ww.x : T(0);
-                T k0 = 0, k1 = 0, k2 = 0, tx = 0, ty = 0;
-                if (has_tangent) {  // ContactTangentPart::generate
-                    V3<T> rt11 = cross(r1, t0), rt12 = cross(r2, t0), rt21 = cross(r1, t1), rt22 = cross(r2, t1);
-                    V3<T> i1_rt11 = smul(i1, rt11), i2_rt12 = smul(i2, rt12), i1_rt21 = smul(i1, rt21), i2_rt22 = smul(i2, rt22);
-                    T k_linear1 = dot(t0, cmul(w_sum, t0));
-                    T k_linear2 = dot(t1, cmul(w_sum, t1));
-                    k0 = k_linear1 + dot(rt11, i1_rt11) + dot(rt12, i2_rt12);
-                    k1 = k_linear2 + dot(rt21, i1_rt21) + dot(rt22, i2_rt22);
-                    k2 = T(2) * (dot(rt11, i1_rt21) + dot(rt12, i2_rt22));
-                    if (warm) { tx = ww.y; ty = ww.z; }
+                for (uint32_t k = 0; k < AVN_MAX_MANIFOLD_POINTS; ++k) {
+                    if (ROWS) { const Vec4<T>* __restrict__ r = rv.rows + (size_t)row * AVN_CT_ROW_V4; pa1[k] = r[2 + k]; pa2[k] = r[6 + k]; pww[k] = r[10 + k]; }
+                    else { uint32_t s = k * S + m; pa1[k] = w.mp_a1[s]; pa2[k] = w.mp_a2[s]; pww[k] = w.mp_w[s]; }
                 }
-                T initial_separation = -penetration - dot(r2 - r1, normal);
-                w.c_pa[s] = make4<T>(r1, initial_separation);
-                w.c_pb[s] = make4<T>(r2, eff_mass);
-                w.c_pc[s] = make4<T>(k0, k1, k2, normal_speed);
-                w.c_pd[s] = make4<T>(ni, T(0), tx, ty);
+#pragma unroll
+                for (uint32_t k = 0; k < AVN_MAX_MANIFOLD_POINTS; ++k) {
+                    if (k >= np) break;
+                    uint32_t s = k * S + m;
+                    Vec4<T> a1 = pa1[k], a2 = pa2[k], ww = pww[k];
+                    V3<T> r1 = xyz<T>(a1), r2 = xyz<T>(a2);
+                    T penetration = a1.w, normal_speed = a2.w;
+                    // ContactNormalPart::generate
+                    V3<T> r1_cross_n = cross(r1, normal), r2_cross_n = cross(r2, normal);
+                    T k_linear = dot(normal, cmul(w_sum, normal));
+                    T kk = k_linear + dot(r1_cross_n, smul(i1, r1_cross_n)) + dot(r2_cross_n, smul(i2, r2_cross_n));
+                    T eff_mass = recip_or_zero(kk);
+                    T ni = warm ? ww.x : T(0);
+                    T k0 = 0, k1 = 0, k2 = 0, tx = 0, ty = 0;
+                    if (has_tangent) {  // ContactTangentPart::generate
+                        V3<T> rt11 = cross(r1, t0), rt12 = cross(r2, t0), rt21 = cross(r1, t1), rt22 = cross(r2, t1);
+                        V3<T> i1_rt11 = smul(i1, rt11), i2_rt12 = smul(i2, rt12), i1_rt21 = smul(i1, rt21), i2_rt22 = smul(i2, rt22);
+                        T k_linear1 = dot(t0, cmul(w_sum, t0));
+                        T k_linear2 = dot(t1, cmul(w_sum, t1));
+                        k0 = k_linear1 + dot(rt11, i1_rt11) + dot(rt12, i2_rt12);
+                        k1 = k_linear2 + dot(rt21, i1_rt21) + dot(rt22, i2_rt22);
+                        k2 = T(2) * (dot(rt11, i1_rt21) + dot(rt12, i2_rt22));
+                        if (warm) { tx = ww.y; ty = ww.z; }
+                    }
+                    T initial_separation = -penetration - dot(r2 - r1, normal);
+                    w.c_pa[s] = make4<T>(r1, initial_separation);
+                    w.c_pb[s] = make4<T>(r2, eff_mass);
+                    w.c_pc[s] = make4<T>(k0, k1, k2, normal_speed);
+                    w.c_pd[s] = make4<T>(ni, T(0), tx, ty);
+                }
+                uint32_t cm = np;
+                if (relative_dominance > 0) cm |= AVN_CM_DOM1;
+                if (relative_dominance < 0) cm |= AVN_CM_DOM2;
+                if (relative_dominance != 0) cm |= AVN_CM_SOFT_ND;
+                if (has_tangent) cm |= AVN_CM_TANGENT;
+                if (nobody1) cm |= AVN_CM_NOBODY1;
+                if (nobody2) cm |= AVN_CM_NOBODY2;
+                w.c_h1[m] = make4<T>(t0, bits_to_scalar(cm, T(0)));
+                w.c_reldom[m] = (int16_t)relative_dominance;
+                generated = true;
             }
-            uint32_t cm = np;
-            if (relative_dominance > 0) cm |= AVN_CM_DOM1;
-            if (relative_dominance < 0) cm |= AVN_CM_DOM2;
-            if (relative_dominance != 0) cm |= AVN_CM_SOFT_ND;
-            if (has_tangent) cm |= AVN_CM_TANGENT;
-            if (nobody1) cm |= AVN_CM_NOBODY1;
-            if (nobody2) cm |= AVN_CM_NOBODY2;
-            w.c_h1[m] = make4<T>(t0, bits_to_scalar(cm, T(0)));
-            w.c_reldom[m] = (int16_t)relative_dominance;
-            generated = true;
         }
+        count += (uint32_t)__popcll(__ballot(generated));
     }
-    unsigned long long bal = __ballot(generated);
-    if ((threadIdx.x & 63) == 0 && bal) atomicAdd(w.constraint_count, (uint32_t)__popcll(bal));
+    __shared__ uint32_t wave_count[PREP_TILE / 64];
+    if ((threadIdx.x & 63) == 0) wave_count[threadIdx.x >> 6] = count;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t n = 0;
+        for (uint32_t i = 0; i < PREP_TILE / 64; ++i) n += wave_count[i];
+        if (n) atomicAdd(w.constraint_count, n);
+    }
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -1283,11 +1303,15 @@ __global__ __launch_bounds__(256) void k_store_contact_impulses(DW<T> w) {
 }
 
 // ---- launchers ------------------------------------------------------------------------------------------
+static uint32_t prepare_grid_blocks(uint32_t n_manifolds) {   // (handle mode: n_manifolds may be an upper bound of the live count; surplus workgroups find no tile)
+    const uint32_t tiles = (n_manifolds + PREP_TILE - 1u) / PREP_TILE;
+    return (tiles + PREP_TILES_PER_BLOCK - 1u) / PREP_TILES_PER_BLOCK;
+}
 template <class T> void launch_prepare_contact_constraints(const DW<T>& w, const StepParams<T>& p, hipStream_t s, bool count_clean, const RowsView<T>* rows) {
     if (!count_clean) (void)hipMemsetAsync(w.constraint_count, 0, sizeof(uint32_t), s);
     if (!w.n_manifolds) return;
-    if (rows) hipLaunchKernelGGL((k_prepare_contact_constraints<T, true>), dim3((w.n_manifolds + 255) / 256), dim3(256), 0, s, w, p, *rows);
-    else hipLaunchKernelGGL((k_prepare_contact_constraints<T, false>), dim3((w.n_manifolds + 255) / 256), dim3(256), 0, s, w, p, RowsView<T>{});
+    if (rows) hipLaunchKernelGGL((k_prepare_contact_constraints<T, true>), dim3(prepare_grid_blocks(w.n_manifolds)), dim3(PREP_TILE), 0, s, w, p, *rows);
+    else hipLaunchKernelGGL((k_prepare_contact_constraints<T, false>), dim3(prepare_grid_blocks(w.n_manifolds)), dim3(PREP_TILE), 0, s, w, p, RowsView<T>{});
 }
 template <class T> void launch_store_contact_impulses(const DW<T>& w, hipStream_t s) {
     if (w.n_manifolds) hipLaunchKernelGGL(k_store_contact_impulses<T>, dim3((w.n_manifolds + 255) / 256), dim3(256), 0, s, w);
