@@ -15,8 +15,8 @@
 //                      (exact min / max) -- the hand-over between workgroups is an agent-scope release before the arrival counter's
 //                      atomic and an agent-scope acquire after it (L1 is per CU, L2 per XCD): never co-location
 //
-// Queries: one lane per query, a per-lane DFS stack in LDS (64 entries: the depth of a Karras tree over unique 64-bit keys is at most 64).
-// The BVH only culls; every answer is the exact per-collider test below, so the result equals a brute-force pass with the same tests.  A
+// Queries: one lane per query, a per-lane DFS stack in LDS (64 entries: the depth of a Karras tree over unique 64-bit keys is at most 64);
+// the six traversal kernels share one walk (sp_walk) and hand it their node test and their leaf test.  The BVH only culls; every answer is the exact per-collider test below, so the result equals a brute-force pass with the same tests.  A
 // leaf box is the exact shape AABB grown by 64 eps * its largest coordinate, and every node test of a query grows the node box by 64 eps
 // * the query's largest coordinate: the rounding of shape_aabb, of the local-frame transform, of the slab test and of the ball's
 // discriminant (taken as a (r^2 - |f|^2) with f = o_l - d_l (b / a), whose error grows with |o_l|, not with |o_l|^2 as parry's b^2 - a c
@@ -49,6 +49,12 @@ __device__ __forceinline__ uint32_t sp_expand10(uint32_t v) {
     return v;
 }
 template <class T> __device__ __forceinline__ T sp_maxabs(V3<T> v) { return smax(smax(fabs_t(v.x), fabs_t(v.y)), fabs_t(v.z)); }
+// a box grown by 64 eps * its largest coordinate: a leaf box, and the box of a query shape
+template <class T> __device__ __forceinline__ void sp_pad_box(V3<T> a, V3<T> b, V3<T>& mn, V3<T>& mx) {
+    const T pad = T(64) * Limits<T>::eps * smax(sp_maxabs(a), sp_maxabs(b));
+    const V3<T> pp{pad, pad, pad};
+    mn = a - pp; mx = b + pp;
+}
 
 // ---------------------------------------------------------------------------------------------------------
 // build
@@ -74,9 +80,7 @@ __global__ __launch_bounds__(256) void k_sp_snapshot(DW<T> w, BP<T> bp, SP<T> sp
         shape_aabb<T>(shape, h, pos, rot, a, b);
         if (is_finite(a) && is_finite(b)) {
             candidate = true;
-            const T pad = T(64) * Limits<T>::eps * smax(sp_maxabs(a), sp_maxabs(b));
-            const V3<T> pp{pad, pad, pad};
-            mn = a - pp; mx = b + pp;
+            sp_pad_box(a, b, mn, mx);
             const V3<T> m = (a + b) * T(0.5);
             atomicMin(&sp.bounds[0], sp_fkey((float)m.x)); atomicMin(&sp.bounds[1], sp_fkey((float)m.y)); atomicMin(&sp.bounds[2], sp_fkey((float)m.z));
             atomicMax(&sp.bounds[3], sp_fkey((float)m.x)); atomicMax(&sp.bounds[4], sp_fkey((float)m.y)); atomicMax(&sp.bounds[5], sp_fkey((float)m.z));
@@ -302,39 +306,190 @@ __device__ __forceinline__ bool sp_excluded(const uint32_t* __restrict__ ex, uin
     return lo < n && ex[lo] == e;
 }
 
-// one lane per query; blocks of one wave, each lane with its own SP_STACK-entry column of the LDS stack.  PQ (a caster run, SPQ_CLOSEST /
-// SPQ_HITS only): the lane answers caster q.index[lane's query] with that caster's own self_entity, excluded slice, live flag and k, into its
-// row of q.cap record slots; the instantiations without PQ compile as before.
+// ---------------------------------------------------------------------------------------------------------
+// what the traversal kernels share: the loads of a query, the leaf filter, the output lists, the counters and the walk itself
+template <class T> __device__ __forceinline__ V3<T> sp_load3(const T* p, uint32_t i) { return V3<T>{p[3 * (size_t)i], p[3 * (size_t)i + 1], p[3 * (size_t)i + 2]}; }
+
+// the ray from o along d; the node test of a ray grows every node box by tol = 64 eps * the origin's largest coordinate
+template <class T> __device__ __forceinline__ RayCtx<T> sp_ray_ctx(V3<T> o, V3<T> d) {
+    RayCtx<T> r;
+    r.o = o; r.d = d;
+    r.inv = V3<T>{d.x != T(0) ? T(1) / d.x : T(0), d.y != T(0) ? T(1) / d.y : T(0), d.z != T(0) ? T(1) / d.z : T(0)};
+    r.zero = (d.x == T(0) ? 1u : 0u) | (d.y == T(0) ? 2u : 0u) | (d.z == T(0) ? 4u : 0u);
+    r.tol = T(64) * Limits<T>::eps * sp_maxabs(o);
+    return r;
+}
+
+// The query shape of lane i.  valid: a Ball or a Cuboid with a finite pose, finite half extents that are not negative and a finite AABB
+// [a, b] at its pose (shape_aabb: exact).  Every caller answers an invalid shape a miss / count 0 without traversing.
+template <class T> struct QShape { uint32_t shape; V3<T> he, pos; Q4<T> rot; V3<T> a, b; bool valid; };
+template <class T> __device__ __forceinline__ QShape<T> sp_load_shape(const uint8_t* shape, const T* pos, const T* he, const T* rot, uint32_t i) {
+    QShape<T> s;
+    s.shape = shape[i];
+    s.pos = sp_load3(pos, i);
+    s.he = sp_load3(he, i);
+    s.rot = Q4<T>{rot[4 * (size_t)i], rot[4 * (size_t)i + 1], rot[4 * (size_t)i + 2], rot[4 * (size_t)i + 3]};
+    if (s.shape == AVN_SHAPE_BALL) s.he = V3<T>{s.he.x, s.he.x, s.he.x};   // (a ball has its radius in x: y and z are not read)
+    s.a = s.b = vzero<T>();
+    s.valid = s.shape <= AVN_SHAPE_BALL && is_finite(s.pos) && is_finite(V3<T>{s.rot.x, s.rot.y, s.rot.z}) && finite_t(s.rot.w) && is_finite(s.he) &&
+              s.he.x >= T(0) && s.he.y >= T(0) && s.he.z >= T(0);
+    if (s.valid) {
+        shape_aabb<T>(s.shape, s.he, s.pos, s.rot, s.a, s.b);
+        s.valid = is_finite(s.a) && is_finite(s.b);
+    }
+    return s;
+}
+// the ray of a shape cast: from the centre of the query shape's padded AABB along d, against the node boxes grown by that AABB's half widths hw
+template <class T> __device__ __forceinline__ RayCtx<T> sp_cast_ray(const QShape<T>& s, V3<T> d, V3<T>& hw) {
+    V3<T> qmin, qmax;
+    sp_pad_box(s.a, s.b, qmin, qmax);
+    hw = (qmax - qmin) * T(0.5);
+    return sp_ray_ctx<T>((qmin + qmax) * T(0.5), d);
+}
+template <class T> __device__ __forceinline__ T sp_cast_box(const RayCtx<T>& r, V3<T> hw, Vec4<T> lo, Vec4<T> hi, T limit) {
+    return sp_ray_box(r, make4<T>(lo.x - hw.x, lo.y - hw.y, lo.z - hw.z, T(0)), make4<T>(hi.x + hw.x, hi.y + hw.y, hi.z + hw.z, T(0)), limit);
+}
+
+// the leaf filter: a candidate (live, with device geometry) in the query's mask that is neither the query's own entity nor in the sorted list ex
+__device__ __forceinline__ bool sp_leaf_ok(uint4 info, uint32_t mask, uint32_t self, const uint32_t* ex, uint32_t ex_n) {
+    return info.w && (info.y & mask) != 0u && !(self != AVN_SPATIAL_MISS && info.x == self) && !(ex_n && sp_excluded(ex, ex_n, info.x));
+}
+
+// The output lists: the best k of the `found` accepted so far, kept sorted by insertion into the query's own output slots.  Both return the
+// slot of the new entry, the worse ones moved up, or AVN_SPATIAL_MISS when it does not make the list.
+__device__ __forceinline__ uint32_t sp_collider_of(uint32_t id) { return id; }
+template <class T> __device__ __forceinline__ uint32_t sp_collider_of(const SpatialShapeContact<T>& r) { return r.collider; }
+// ascending collider index (ids, contact records)
+template <class E> __device__ __forceinline__ uint32_t sp_slot_by_collider(E* l, uint32_t k, uint32_t& found, uint32_t c) {
+    uint32_t m = found < k ? found : k;
+    ++found;
+    if (m == k) {
+        if (k == 0 || c >= sp_collider_of(l[k - 1])) return AVN_SPATIAL_MISS;
+        m = k - 1;
+    }
+    while (m > 0 && sp_collider_of(l[m - 1]) > c) { l[m] = l[m - 1]; --m; }
+    return m;
+}
+// nearest-k by (distance, collider) (ray hits, shape hits)
+template <class E, class T> __device__ __forceinline__ uint32_t sp_slot_by_distance(E* l, uint32_t k, uint32_t& found, T toi, uint32_t c) {
+    uint32_t m = found < k ? found : k;
+    ++found;
+    if (m == k) {
+        const T ld = l[k - 1].distance;
+        if (!(toi < ld || (toi == ld && c < l[k - 1].collider))) return AVN_SPATIAL_MISS;
+        m = k - 1;
+    }
+    while (m > 0 && (l[m - 1].distance > toi || (l[m - 1].distance == toi && l[m - 1].collider > c))) { l[m] = l[m - 1]; --m; }
+    return m;
+}
+
+// the records.  normal2 = -normal1, a zero component staying +0 (a miss and an overlap at the start: every byte 0)
+template <class T> __device__ __forceinline__ void sp_put(SpatialHit<T>& h, uint32_t c, uint32_t e, T t, V3<T> n) {
+    h.collider = c; h.entity = e; h.distance = t;
+    h.normal[0] = n.x; h.normal[1] = n.y; h.normal[2] = n.z;
+}
+template <class T> __device__ __forceinline__ void sp_put(SpatialShapeHit<T>& h, uint32_t c, uint32_t e, T t, V3<T> p1, V3<T> p2, V3<T> n1) {
+    h.collider = c; h.entity = e; h.distance = t;
+    h.point1[0] = p1.x; h.point1[1] = p1.y; h.point1[2] = p1.z;
+    h.point2[0] = p2.x; h.point2[1] = p2.y; h.point2[2] = p2.z;
+    h.normal1[0] = n1.x; h.normal1[1] = n1.y; h.normal1[2] = n1.z;
+    h.normal2[0] = n1.x == T(0) ? T(0) : -n1.x; h.normal2[1] = n1.y == T(0) ? T(0) : -n1.y; h.normal2[2] = n1.z == T(0) ? T(0) : -n1.z;
+}
+// the miss of every list
+__device__ __forceinline__ void sp_put_miss(uint32_t& id) { id = AVN_SPATIAL_MISS; }
+template <class T> __device__ __forceinline__ void sp_put_miss(SpatialHit<T>& h) { sp_put<T>(h, AVN_SPATIAL_MISS, AVN_SPATIAL_MISS, T(0), vzero<T>()); }
+template <class T> __device__ __forceinline__ void sp_put_miss(SpatialShapeHit<T>& h) { sp_put<T>(h, AVN_SPATIAL_MISS, AVN_SPATIAL_MISS, T(0), vzero<T>(), vzero<T>(), vzero<T>()); }
+template <class T> __device__ __forceinline__ void sp_put_miss(SpatialShapeContact<T>& r) {
+    r.collider = AVN_SPATIAL_MISS; r.entity = AVN_SPATIAL_MISS; r.penetration = T(0);
+    for (int i = 0; i < 3; ++i) r.normal[i] = r.point[i] = r.anchor1[i] = r.anchor2[i] = T(0);
+    sp_clear_reserved(r);
+}
+template <class E> __device__ __forceinline__ void sp_fill_miss(E* l, uint32_t from, uint32_t to) {
+    E miss;
+    sp_put_miss(miss);
+    for (uint32_t m = from; m < to; ++m) l[m] = miss;
+}
+
+// totals of the call, by every lane of the wave: one atomic per wave.  flags: bit 0 a stack overflow; bit 1 (k_sp_cast_move) more than
+// AVN_SPATIAL_MAX_HITS pending colliders
+__device__ __forceinline__ void sp_add_stats(unsigned long long* stats, uint32_t nodes_tested, uint32_t leaves_tested, uint32_t flags) {
+    uint32_t a = nodes_tested, b = leaves_tested, o = flags;
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) { a += __shfl_xor(a, off); b += __shfl_xor(b, off); o |= __shfl_xor(o, off); }
+    if (threadIdx.x == 0) {
+        atomicAdd(&stats[0], (unsigned long long)a);
+        atomicAdd(&stats[1], (unsigned long long)b);
+        if (o) atomicOr(&stats[2], (unsigned long long)o);
+    }
+}
+
+// The walk of every query kernel: one lane per query in blocks of one wave, a depth-first descent of the LBVH with the lane's own SP_STACK-
+// entry column of the LDS stack.  test(node) is the kernel's key of the node box, +inf = culled (the kinds without a distance answer 0 or
+// +inf); leaf(c) is its exact test of collider c.  The nearer child goes first, the left one on a tie, so the kinds without a distance go
+// left to right.  PRUNE (the closest-hit kinds, `best` their best distance so far): a leaf or a child whose key the leaf before it has left
+// STRICTLY above `best` is dropped, and a popped node is re-tested -- only strictly, so a collider at the best distance with a lower index is
+// still reached.  Without PRUNE a node is tested once: a re-test would count it twice.
+template <class T, bool PRUNE, class Test, class Leaf>
+__device__ __forceinline__ void sp_walk(const SP<T>& sp, uint32_t& overflow, const T& best, Test test, Leaf leaf) {
+    __shared__ uint32_t stack[SP_STACK * SP_WAVE];
+    const uint32_t n = sp.n, lane = threadIdx.x;
+    if (n == 0 || test(0u) == sp_inf<T>()) return;
+    uint32_t sp_top = 0, node = 0;
+    for (;;) {
+        // (a tree of one collider: its root is the leaf, handled by the same leaf call site)
+        uint2 ch = make_uint2(0u, 0u);
+        T e0 = T(0), e1 = sp_inf<T>();
+        if (n > 1) { ch = sp.child[node]; e0 = test(ch.x); e1 = test(ch.y); }
+        const bool l0 = ch.x >= n - 1, l1 = ch.y >= n - 1;
+        // one leaf call site: the pair tests are emitted once
+        uint32_t pending = (l0 && e0 != sp_inf<T>() ? 1u : 0u) | (l1 && e1 != sp_inf<T>() ? 2u : 0u);
+        while (pending) {
+            const bool first = (pending & 1u) != 0;
+            // (the first leaf may have shrunk the best distance below the second one's key)
+            if (first || !PRUNE || !(e1 > best)) leaf(sp.leaf_col[(first ? ch.x : ch.y) - (n - 1)]);
+            pending &= first ? ~1u : ~2u;
+        }
+        const bool g0 = !l0 && e0 != sp_inf<T>() && (!PRUNE || !(e0 > best)), g1 = !l1 && e1 != sp_inf<T>() && (!PRUNE || !(e1 > best));
+        if (g0 && g1) {
+            const bool first0 = !(e1 < e0);
+            if (sp_top < SP_STACK) { stack[sp_top * SP_WAVE + lane] = first0 ? ch.y : ch.x; ++sp_top; }
+            else overflow |= 1u;   // (cannot happen: the depth of a Karras tree over unique 64-bit keys is at most 64)
+            node = first0 ? ch.x : ch.y;
+            continue;
+        }
+        if (g0) { node = ch.x; continue; }
+        if (g1) { node = ch.y; continue; }
+        // pop; a node pushed before the best distance shrank is re-tested against it
+        node = AVN_SPATIAL_MISS;
+        while (sp_top > 0) {
+            --sp_top;
+            const uint32_t cand = stack[sp_top * SP_WAVE + lane];
+            if (!PRUNE || test(cand) != sp_inf<T>()) { node = cand; break; }
+        }
+        if (node == AVN_SPATIAL_MISS) break;
+    }
+}
+
+// one lane per query.  PQ (a caster run, SPQ_CLOSEST / SPQ_HITS only): the lane answers caster q.index[lane's query] with that caster's own
+// self_entity, excluded slice, live flag and k, into its row of q.cap record slots.
 template <class T, int KIND, bool PQ = false>
 __global__ __launch_bounds__(SP_WAVE) void k_sp_query(SP<T> sp, SQ<T> q) {
-    __shared__ uint32_t stack[SP_STACK * SP_WAVE];
-    const uint32_t lane = threadIdx.x;
-    const uint32_t li = blockIdx.x * SP_WAVE + lane;
-    const bool active = li < q.n;
+    constexpr bool RAY = KIND == SPQ_CLOSEST || KIND == SPQ_HITS;
+    const uint32_t li = blockIdx.x * SP_WAVE + threadIdx.x;
     uint32_t nodes_tested = 0, leaves_tested = 0, overflow = 0;
-    const uint32_t n = sp.n;
-    if (active) {
+    if (li < q.n) {
         const uint32_t qi = PQ ? q.index[li] : li;
         const uint32_t mask = q.mask ? q.mask[qi] : 0xFFFFFFFFu;
         const uint32_t self = PQ ? q.self_entity[qi] : AVN_SPATIAL_MISS;
-        const uint32_t ex0 = PQ ? q.ex_offset[qi] : 0u, ex_n = PQ ? q.ex_offset[qi + 1] - ex0 : 0u;
+        const uint32_t ex0 = PQ ? q.ex_offset[qi] : 0u, ex_n = PQ ? q.ex_offset[qi + 1] - ex0 : q.n_excluded;
         const uint32_t kq = PQ ? q.kq[qi] : q.cap;   // the list length of SPQ_HITS
-        // per-query state
-        RayCtx<T> r;
-        V3<T> pa{T(0), T(0), T(0)}, pb{T(0), T(0), T(0)};
-        T max_distance = T(0), tol = T(0);
-        bool solid = false;
-        pa = V3<T>{q.a[3 * (size_t)qi], q.a[3 * (size_t)qi + 1], q.a[3 * (size_t)qi + 2]};
-        if (KIND != SPQ_POINTS) pb = V3<T>{q.b[3 * (size_t)qi], q.b[3 * (size_t)qi + 1], q.b[3 * (size_t)qi + 2]};
-        if (KIND == SPQ_CLOSEST || KIND == SPQ_HITS) {
-            max_distance = q.max_distance[qi];
-            solid = q.solid[qi] != 0;
-            r.o = pa; r.d = pb; r.zero = 0;
-            r.inv = V3<T>{pb.x != T(0) ? T(1) / pb.x : T(0), pb.y != T(0) ? T(1) / pb.y : T(0), pb.z != T(0) ? T(1) / pb.z : T(0)};
-            r.zero = (pb.x == T(0) ? 1u : 0u) | (pb.y == T(0) ? 2u : 0u) | (pb.z == T(0) ? 4u : 0u);
-            r.tol = T(64) * Limits<T>::eps * sp_maxabs(pa);
-        }
-        if (KIND == SPQ_POINTS) tol = T(64) * Limits<T>::eps * sp_maxabs(pa);
+        // per-query state: a ray from pa along pb, the point pa, or the box [pa, pb]
+        const V3<T> pa = sp_load3(q.a, qi);
+        const V3<T> pb = KIND != SPQ_POINTS ? sp_load3(q.b, qi) : vzero<T>();
+        const T max_distance = RAY ? q.max_distance[qi] : T(0);
+        const bool solid = RAY && q.solid[qi] != 0;
+        const RayCtx<T> r = sp_ray_ctx<T>(pa, pb);
+        const T tol = T(64) * Limits<T>::eps * sp_maxabs(pa);
         // a non-finite origin, direction, point or box corner answers a miss / count 0 without traversing the tree
         const bool finite_query = is_finite(pa) && (KIND == SPQ_POINTS || is_finite(pb)) && (!PQ || q.live[qi] != 0);
         // results
@@ -342,8 +497,8 @@ __global__ __launch_bounds__(SP_WAVE) void k_sp_query(SP<T> sp, SQ<T> q) {
         uint32_t best_c = AVN_SPATIAL_MISS;
         V3<T> best_n = vzero<T>();
         uint32_t found = 0;
-        SpatialHit<T>* hl = (KIND == SPQ_HITS) ? q.hits + (size_t)qi * q.cap : nullptr;
-        uint32_t* il = (KIND == SPQ_POINTS || KIND == SPQ_AABBS) ? q.ids + (size_t)qi * q.cap : nullptr;
+        SpatialHit<T>* hl = RAY ? q.hits + (size_t)qi * q.cap : nullptr;
+        uint32_t* il = RAY ? nullptr : q.ids + (size_t)qi * q.cap;
 
         // node test: entry distance for rays (+inf = miss), 0 / +inf for the others
         auto test = [&](uint32_t node) -> T {
@@ -354,125 +509,55 @@ __global__ __launch_bounds__(SP_WAVE) void k_sp_query(SP<T> sp, SQ<T> q) {
             if (KIND == SPQ_POINTS) return sp_point_box(pa, tol, lo, hi) ? T(0) : sp_inf<T>();
             return sp_box_box(pa, pb, lo, hi) ? T(0) : sp_inf<T>();
         };
-        auto leaf = [&](uint32_t node) {
-            const uint32_t c = sp.leaf_col[node - (n - 1)];
+        auto leaf = [&](uint32_t c) {
             const uint4 info = sp.info[c];
-            if (!info.w || (info.y & mask) == 0u || (!PQ && q.n_excluded && sp_excluded(q.excluded, q.n_excluded, info.x))) return;
-            if (PQ && ((self != AVN_SPATIAL_MISS && info.x == self) || (ex_n && sp_excluded(q.excluded + ex0, ex_n, info.x)))) return;
+            if (!sp_leaf_ok(info, mask, self, q.excluded + ex0, ex_n)) return;
             ++leaves_tested;
             const V3<T> pos = xyz<T>(sp.pos[c]), he = xyz<T>(sp.he[c]);
             const Q4<T> rot = quat<T>(sp.rot[c]);
-            if (KIND == SPQ_CLOSEST || KIND == SPQ_HITS) {
+            if (RAY) {
                 T toi; V3<T> nrm;
                 if (!sp_ray_exact<T>(info.z, he, pos, rot, r.o, r.d, max_distance, solid, toi, nrm)) return;
                 if (KIND == SPQ_CLOSEST) {
                     if (toi < best || (toi == best && c < best_c)) { best = toi; best_c = c; best_n = nrm; }
                 } else {
-                    const uint32_t k = kq;
-                    uint32_t m = found < k ? found : k;
-                    ++found;
-                    // nearest-k by (distance, collider), insertion into the query's own output records
-                    if (m == k) {
-                        const SpatialHit<T>& last = hl[k - 1];
-                        if (!(toi < last.distance || (toi == last.distance && c < last.collider))) return;
-                        m = k - 1;
-                    }
-                    while (m > 0 && (hl[m - 1].distance > toi || (hl[m - 1].distance == toi && hl[m - 1].collider > c))) { hl[m] = hl[m - 1]; --m; }
+                    const uint32_t m = sp_slot_by_distance(hl, kq, found, toi, c);
+                    if (m == AVN_SPATIAL_MISS) return;
                     SpatialHit<T> h;
-                    h.collider = c; h.entity = info.x; h.distance = toi; h.normal[0] = nrm.x; h.normal[1] = nrm.y; h.normal[2] = nrm.z;
+                    sp_put<T>(h, c, info.x, toi, nrm);
                     hl[m] = h;
                 }
             } else {
                 const bool hit = KIND == SPQ_POINTS ? sp_point_exact<T>(info.z, he, pos, rot, pa) : sp_aabb_exact<T>(info.z, he, pos, rot, pa, pb);
                 if (!hit) return;
-                const uint32_t k = q.cap;
-                uint32_t m = found < k ? found : k;
-                ++found;
-                if (m == k) {
-                    if (k == 0 || c >= il[k - 1]) return;
-                    m = k - 1;
-                }
-                while (m > 0 && il[m - 1] > c) { il[m] = il[m - 1]; --m; }
-                il[m] = c;
+                const uint32_t m = sp_slot_by_collider(il, q.cap, found, c);
+                if (m != AVN_SPATIAL_MISS) il[m] = c;
             }
         };
-
-        if (!finite_query) {
-        } else if (n == 1) {
-            if (test(0) != sp_inf<T>()) leaf(0);
-        } else if (n > 1 && test(0) != sp_inf<T>()) {
-            uint32_t sp_top = 0, node = 0;
-            for (;;) {
-                const uint2 ch = sp.child[node];
-                T e0 = test(ch.x), e1 = test(ch.y);
-                const bool l0 = ch.x >= n - 1, l1 = ch.y >= n - 1;
-                if (l0 && e0 != sp_inf<T>()) { leaf(ch.x); e0 = sp_inf<T>(); }
-                if (l1 && e1 != sp_inf<T>()) { leaf(ch.y); e1 = sp_inf<T>(); }
-                const bool g0 = e0 != sp_inf<T>(), g1 = e1 != sp_inf<T>();
-                if (g0 && g1) {
-                    const bool first0 = !(e1 < e0);   // the nearer child first (ties: the left one)
-                    if (sp_top < SP_STACK) { stack[sp_top * SP_WAVE + lane] = first0 ? ch.y : ch.x; ++sp_top; }
-                    else overflow = 1;   // (cannot happen: the depth of the tree is at most 64)
-                    node = first0 ? ch.x : ch.y;
-                    continue;
-                }
-                if (g0) { node = ch.x; continue; }
-                if (g1) { node = ch.y; continue; }
-                if (sp_top == 0) break;
-                --sp_top;
-                node = stack[sp_top * SP_WAVE + lane];
-                // a node pushed before the best hit shrank: re-test its box against the current bound (closest hit only)
-                if (KIND == SPQ_CLOSEST) {
-                    for (;;) {
-                        if (test(node) != sp_inf<T>()) break;
-                        if (sp_top == 0) { node = AVN_SPATIAL_MISS; break; }
-                        --sp_top;
-                        node = stack[sp_top * SP_WAVE + lane];
-                    }
-                    if (node == AVN_SPATIAL_MISS) break;
-                }
-            }
-        }
+        if (finite_query) sp_walk<T, KIND == SPQ_CLOSEST>(sp, overflow, best, test, leaf);
 
         // write the results
         if (KIND == SPQ_CLOSEST) {
             SpatialHit<T> h;
-            h.collider = best_c;
-            h.entity = best_c == AVN_SPATIAL_MISS ? AVN_SPATIAL_MISS : sp.info[best_c].x;
-            h.distance = best_c == AVN_SPATIAL_MISS ? T(0) : best;
-            h.normal[0] = best_n.x; h.normal[1] = best_n.y; h.normal[2] = best_n.z;
+            sp_put<T>(h, best_c, best_c == AVN_SPATIAL_MISS ? AVN_SPATIAL_MISS : sp.info[best_c].x, best_c == AVN_SPATIAL_MISS ? T(0) : best, best_n);
             if (!PQ) q.hits[qi] = h;
             else {
                 // the caster's row: the hit or a miss, then misses; count 0 or 1
-                SpatialHit<T>* row = q.hits + (size_t)qi * q.cap;
-                row[0] = h;
-                h.collider = AVN_SPATIAL_MISS; h.entity = AVN_SPATIAL_MISS; h.distance = T(0); h.normal[0] = h.normal[1] = h.normal[2] = T(0);
-                for (uint32_t m = 1; m < q.cap; ++m) row[m] = h;
+                hl[0] = h;
+                sp_fill_miss(hl, 1u, q.cap);
                 q.count[qi] = best_c == AVN_SPATIAL_MISS ? 0u : 1u;
             }
-        } else if (KIND == SPQ_HITS) {
-            SpatialHit<T> miss;
-            miss.collider = AVN_SPATIAL_MISS; miss.entity = AVN_SPATIAL_MISS; miss.distance = T(0); miss.normal[0] = miss.normal[1] = miss.normal[2] = T(0);
-            for (uint32_t m = PQ ? (found < kq ? found : kq) : found; m < q.cap; ++m) hl[m] = miss;
-            q.count[qi] = found;
         } else {
-            for (uint32_t m = found; m < q.cap; ++m) il[m] = AVN_SPATIAL_MISS;
+            if (KIND == SPQ_HITS) sp_fill_miss(hl, found < kq ? found : kq, q.cap);
+            else sp_fill_miss(il, found, q.cap);
             q.count[qi] = found;
         }
     }
-    // totals of the call: one atomic per wave
-    uint32_t a = nodes_tested, b = leaves_tested, o = overflow;
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) { a += __shfl_xor(a, off); b += __shfl_xor(b, off); o |= __shfl_xor(o, off); }
-    if (lane == 0) {
-        atomicAdd(&q.stats[0], (unsigned long long)a);
-        atomicAdd(&q.stats[1], (unsigned long long)b);
-        if (o) atomicOr(&q.stats[2], 1ull);
-    }
+    sp_add_stats(q.stats, nodes_tested, leaves_tested, overflow);
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// point projection and shape intersections (kernels of their own: the four query kinds above compile as before)
+// point projection and shape intersections
 
 // the header's projection of a point onto one collider: false when the distance is not finite
 template <class T>
@@ -521,67 +606,32 @@ template <class T> __device__ __forceinline__ T sp_point_box_distance(V3<T> p, T
 
 template <class T>
 __global__ __launch_bounds__(SP_WAVE) void k_sp_project(SP<T> sp, SQ<T> q) {
-    __shared__ uint32_t stack[SP_STACK * SP_WAVE];
-    const uint32_t lane = threadIdx.x;
-    const uint32_t qi = blockIdx.x * SP_WAVE + lane;
+    const uint32_t qi = blockIdx.x * SP_WAVE + threadIdx.x;
     uint32_t nodes_tested = 0, leaves_tested = 0, overflow = 0;
-    const uint32_t n = sp.n;
     if (qi < q.n) {
         const uint32_t mask = q.mask ? q.mask[qi] : 0xFFFFFFFFu;
-        const V3<T> p{q.a[3 * (size_t)qi], q.a[3 * (size_t)qi + 1], q.a[3 * (size_t)qi + 2]};
+        const V3<T> p = sp_load3(q.a, qi);
         const bool solid = q.solid[qi] != 0;
         const T tol = T(64) * Limits<T>::eps * sp_maxabs(p);
         T best = sp_inf<T>();
         uint32_t best_c = AVN_SPATIAL_MISS, best_in = 0;
         V3<T> best_p = vzero<T>();
-        // the node's lower bound, or -1 when the node is culled: only a bound STRICTLY above the best distance culls, so a collider at the
-        // best distance with a lower index is still reached
+        // the node's lower bound, or +inf when the node is empty or culled: only a bound STRICTLY above the best distance culls, so a collider
+        // at the best distance with a lower index is still reached
         auto test = [&](uint32_t node) -> T {
             ++nodes_tested;
             const T b = sp_point_box_distance<T>(p, tol, sp.bmin[node], sp.bmax[node]);
-            return b > best ? T(-1) : b;
+            return (b >= T(0) && !(b > best)) ? b : sp_inf<T>();
         };
-        auto leaf = [&](uint32_t node) {
-            const uint32_t c = sp.leaf_col[node - (n - 1)];
+        auto leaf = [&](uint32_t c) {
             const uint4 info = sp.info[c];
-            if (!info.w || (info.y & mask) == 0u || (q.n_excluded && sp_excluded(q.excluded, q.n_excluded, info.x))) return;
+            if (!sp_leaf_ok(info, mask, AVN_SPATIAL_MISS, q.excluded, q.n_excluded)) return;
             ++leaves_tested;
             T d; V3<T> pt; bool in;
             if (!sp_project_exact<T>(info.z, xyz<T>(sp.he[c]), xyz<T>(sp.pos[c]), quat<T>(sp.rot[c]), p, solid, d, pt, in)) return;
             if (d < best || (d == best && c < best_c)) { best = d; best_c = c; best_p = pt; best_in = in ? 1u : 0u; }
         };
-        if (!is_finite(p)) {
-        } else if (n == 1) {
-            if (test(0) >= T(0)) leaf(0);
-        } else if (n > 1 && test(0) >= T(0)) {
-            uint32_t sp_top = 0, node = 0;
-            for (;;) {
-                const uint2 ch = sp.child[node];
-                T e0 = test(ch.x), e1 = test(ch.y);
-                const bool l0 = ch.x >= n - 1, l1 = ch.y >= n - 1;
-                if (l0 && e0 >= T(0)) { leaf(ch.x); e0 = T(-1); }
-                // (the first leaf may have shrunk the best distance below the second one's bound)
-                if (l1 && e1 >= T(0)) { if (!(e1 > best)) leaf(ch.y); e1 = T(-1); }
-                const bool g0 = e0 >= T(0) && !(e0 > best), g1 = e1 >= T(0) && !(e1 > best);
-                if (g0 && g1) {
-                    const bool first0 = !(e1 < e0);   // the nearer child first (ties: the left one)
-                    if (sp_top < SP_STACK) { stack[sp_top * SP_WAVE + lane] = first0 ? ch.y : ch.x; ++sp_top; }
-                    else overflow = 1;   // (cannot happen: the depth of the tree is at most 64)
-                    node = first0 ? ch.x : ch.y;
-                    continue;
-                }
-                if (g0) { node = ch.x; continue; }
-                if (g1) { node = ch.y; continue; }
-                // pop; a node pushed before the best distance shrank is re-tested against it
-                node = AVN_SPATIAL_MISS;
-                while (sp_top > 0) {
-                    --sp_top;
-                    const uint32_t cand = stack[sp_top * SP_WAVE + lane];
-                    if (test(cand) >= T(0)) { node = cand; break; }
-                }
-                if (node == AVN_SPATIAL_MISS) break;
-            }
-        }
+        if (is_finite(p)) sp_walk<T, true>(sp, overflow, best, test, leaf);
         SpatialProjection<T> r;
         r.collider = best_c;
         r.entity = best_c == AVN_SPATIAL_MISS ? AVN_SPATIAL_MISS : sp.info[best_c].x;
@@ -591,14 +641,7 @@ __global__ __launch_bounds__(SP_WAVE) void k_sp_project(SP<T> sp, SQ<T> q) {
         r.distance = best_c == AVN_SPATIAL_MISS ? T(0) : best;
         q.proj[qi] = r;
     }
-    uint32_t a = nodes_tested, b = leaves_tested, o = overflow;
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) { a += __shfl_xor(a, off); b += __shfl_xor(b, off); o |= __shfl_xor(o, off); }
-    if (lane == 0) {
-        atomicAdd(&q.stats[0], (unsigned long long)a);
-        atomicAdd(&q.stats[1], (unsigned long long)b);
-        if (o) atomicOr(&q.stats[2], 1ull);
-    }
+    sp_add_stats(q.stats, nodes_tested, leaves_tested, overflow);
 }
 
 // the header's intersection test of a query shape (shape 1, isometry iso1 = make_isometry of its pose) with one collider (shape 2)
@@ -629,307 +672,136 @@ __device__ __forceinline__ bool sp_shape_exact(uint32_t shape1, V3<T> he1, const
 
 template <class T>
 __global__ __launch_bounds__(SP_WAVE) void k_sp_shapes(SP<T> sp, SQ<T> q) {
-    __shared__ uint32_t stack[SP_STACK * SP_WAVE];
-    const uint32_t lane = threadIdx.x;
-    const uint32_t qi = blockIdx.x * SP_WAVE + lane;
+    const uint32_t qi = blockIdx.x * SP_WAVE + threadIdx.x;
     uint32_t nodes_tested = 0, leaves_tested = 0, overflow = 0;
-    const uint32_t n = sp.n;
     if (qi < q.n) {
         const uint32_t mask = q.mask ? q.mask[qi] : 0xFFFFFFFFu;
-        const uint32_t shape1 = q.shape[qi];
-        const V3<T> pos1{q.a[3 * (size_t)qi], q.a[3 * (size_t)qi + 1], q.a[3 * (size_t)qi + 2]};
-        V3<T> he1{q.he[3 * (size_t)qi], q.he[3 * (size_t)qi + 1], q.he[3 * (size_t)qi + 2]};
-        const Q4<T> rot1{q.rot[4 * (size_t)qi], q.rot[4 * (size_t)qi + 1], q.rot[4 * (size_t)qi + 2], q.rot[4 * (size_t)qi + 3]};
-        if (shape1 == AVN_SHAPE_BALL) he1 = V3<T>{he1.x, he1.x, he1.x};   // (a ball has its radius in x: y and z are not read)
-        // a shape kind other than Ball / Cuboid, a non-finite pose or half extents, a negative half extent or a non-finite box: count 0
-        bool valid = shape1 <= AVN_SHAPE_BALL && is_finite(pos1) && is_finite(V3<T>{rot1.x, rot1.y, rot1.z}) && finite_t(rot1.w) && is_finite(he1) &&
-                     he1.x >= T(0) && he1.y >= T(0) && he1.z >= T(0);
-        V3<T> qmin = vzero<T>(), qmax = vzero<T>();
-        Iso<T> iso1{Q4<T>{T(0), T(0), T(0), T(1)}, pos1};
-        if (valid) {
-            // the query shape's exact AABB at its pose, grown as the leaf boxes are
-            V3<T> a, b;
-            shape_aabb<T>(shape1, he1, pos1, rot1, a, b);
-            valid = is_finite(a) && is_finite(b);
-            const T pad = T(64) * Limits<T>::eps * smax(sp_maxabs(a), sp_maxabs(b));
-            const V3<T> pp{pad, pad, pad};
-            qmin = a - pp; qmax = b + pp;
-            iso1 = make_isometry(pos1, rot1);
-        }
+        const QShape<T> s = sp_load_shape<T>(q.shape, q.a, q.he, q.rot, qi);
+        // the query shape's exact AABB at its pose, grown as the leaf boxes are
+        V3<T> qmin, qmax;
+        sp_pad_box(s.a, s.b, qmin, qmax);
+        const Iso<T> iso1 = make_isometry(s.pos, s.rot);
         uint32_t found = 0;
         uint32_t* il = q.ids + (size_t)qi * q.cap;
-        auto test = [&](uint32_t node) -> bool {
+        auto test = [&](uint32_t node) -> T {
             ++nodes_tested;
-            return sp_box_box(qmin, qmax, sp.bmin[node], sp.bmax[node]);
+            return sp_box_box(qmin, qmax, sp.bmin[node], sp.bmax[node]) ? T(0) : sp_inf<T>();
         };
-        auto leaf = [&](uint32_t node) {
-            const uint32_t c = sp.leaf_col[node - (n - 1)];
+        auto leaf = [&](uint32_t c) {
             const uint4 info = sp.info[c];
-            if (!info.w || (info.y & mask) == 0u || (q.n_excluded && sp_excluded(q.excluded, q.n_excluded, info.x))) return;
+            if (!sp_leaf_ok(info, mask, AVN_SPATIAL_MISS, q.excluded, q.n_excluded)) return;
             ++leaves_tested;
-            if (!sp_shape_exact<T>(shape1, he1, iso1, info.z, xyz<T>(sp.he[c]), xyz<T>(sp.pos[c]), quat<T>(sp.rot[c]))) return;
-            const uint32_t k = q.cap;
-            uint32_t m = found < k ? found : k;
-            ++found;
-            if (m == k) {
-                if (k == 0 || c >= il[k - 1]) return;
-                m = k - 1;
-            }
-            while (m > 0 && il[m - 1] > c) { il[m] = il[m - 1]; --m; }
-            il[m] = c;
+            if (!sp_shape_exact<T>(s.shape, s.he, iso1, info.z, xyz<T>(sp.he[c]), xyz<T>(sp.pos[c]), quat<T>(sp.rot[c]))) return;
+            const uint32_t m = sp_slot_by_collider(il, q.cap, found, c);
+            if (m != AVN_SPATIAL_MISS) il[m] = c;
         };
-        if (!valid) {
-        } else if (n == 1) {
-            if (test(0)) leaf(0);
-        } else if (n > 1 && test(0)) {
-            uint32_t sp_top = 0, node = 0;
-            for (;;) {
-                const uint2 ch = sp.child[node];
-                bool g0 = test(ch.x), g1 = test(ch.y);
-                // one leaf call site: the SAT is emitted once
-                uint32_t pending = (ch.x >= n - 1 && g0 ? 1u : 0u) | (ch.y >= n - 1 && g1 ? 2u : 0u);
-                while (pending) {
-                    const bool first = (pending & 1u) != 0;
-                    leaf(first ? ch.x : ch.y);
-                    pending &= first ? ~1u : ~2u;
-                }
-                if (ch.x >= n - 1) g0 = false;
-                if (ch.y >= n - 1) g1 = false;
-                if (g0 && g1) {
-                    if (sp_top < SP_STACK) { stack[sp_top * SP_WAVE + lane] = ch.y; ++sp_top; }
-                    else overflow = 1;   // (cannot happen: the depth of the tree is at most 64)
-                    node = ch.x;
-                    continue;
-                }
-                if (g0) { node = ch.x; continue; }
-                if (g1) { node = ch.y; continue; }
-                if (sp_top == 0) break;
-                --sp_top;
-                node = stack[sp_top * SP_WAVE + lane];
-            }
-        }
-        for (uint32_t m = found; m < q.cap; ++m) il[m] = AVN_SPATIAL_MISS;
+        if (s.valid) sp_walk<T, false>(sp, overflow, T(0), test, leaf);
+        sp_fill_miss(il, found, q.cap);
         q.count[qi] = found;
     }
-    uint32_t a = nodes_tested, b = leaves_tested, o = overflow;
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) { a += __shfl_xor(a, off); b += __shfl_xor(b, off); o |= __shfl_xor(o, off); }
-    if (lane == 0) {
-        atomicAdd(&q.stats[0], (unsigned long long)a);
-        atomicAdd(&q.stats[1], (unsigned long long)b);
-        if (o) atomicOr(&q.stats[2], 1ull);
-    }
+    sp_add_stats(q.stats, nodes_tested, leaves_tested, overflow);
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// shape casts (a kernel of its own: the kernels above compile as before).  The header defines the per-pair tests, operation order
-// included; tests/spatial_cast_reference.py does the same operations in order.  DESIGN.md 4.4.6 has the padding argument.
+// shape casts.  The header defines the per-pair tests, operation order included; tests/spatial_cast_reference.py does the same operations in
+// order.  DESIGN.md 4.4.6 has the padding argument.
 
-
-template <class T> __device__ __forceinline__ void sp_put(SpatialShapeHit<T>& h, uint32_t c, uint32_t e, T t, V3<T> p1, V3<T> p2, V3<T> n1) {
-    h.collider = c; h.entity = e; h.distance = t;
-    h.point1[0] = p1.x; h.point1[1] = p1.y; h.point1[2] = p1.z;
-    h.point2[0] = p2.x; h.point2[1] = p2.y; h.point2[2] = p2.z;
-    h.normal1[0] = n1.x; h.normal1[1] = n1.y; h.normal1[2] = n1.z;
-    // normal2 = -normal1, a zero component staying +0 (a miss and an overlap at the start: every byte 0)
-    h.normal2[0] = n1.x == T(0) ? T(0) : -n1.x; h.normal2[1] = n1.y == T(0) ? T(0) : -n1.y; h.normal2[2] = n1.z == T(0) ? T(0) : -n1.z;
-}
-
-// one lane per cast; blocks of one wave; MANY: the nearest-k list (shape_hits), else the closest hit (cast_shapes).  PQ: a caster run, as in
-// k_sp_query
+// one lane per cast; MANY: the nearest-k list (shape_hits), else the closest hit (cast_shapes).  PQ: a caster run, as in k_sp_query
 template <class T, bool MANY, bool PQ = false>
 __global__ __launch_bounds__(SP_WAVE) void k_sp_cast(SP<T> sp, SQ<T> q) {
-    __shared__ uint32_t stack[SP_STACK * SP_WAVE];
-    const uint32_t lane = threadIdx.x;
-    const uint32_t li = blockIdx.x * SP_WAVE + lane;
+    const uint32_t li = blockIdx.x * SP_WAVE + threadIdx.x;
     uint32_t nodes_tested = 0, leaves_tested = 0, overflow = 0;
-    const uint32_t n = sp.n;
     if (li < q.n) {
         const uint32_t qi = PQ ? q.index[li] : li;
         const uint32_t mask = q.mask ? q.mask[qi] : 0xFFFFFFFFu;
         const uint32_t self = PQ ? q.self_entity[qi] : AVN_SPATIAL_MISS;
-        const uint32_t ex0 = PQ ? q.ex_offset[qi] : 0u, ex_n = PQ ? q.ex_offset[qi + 1] - ex0 : 0u;
+        const uint32_t ex0 = PQ ? q.ex_offset[qi] : 0u, ex_n = PQ ? q.ex_offset[qi + 1] - ex0 : q.n_excluded;
         const uint32_t kq = PQ ? q.kq[qi] : q.cap;   // the list length of MANY
-        const uint32_t shape2 = q.shape[qi];
-        const V3<T> pos2{q.a[3 * (size_t)qi], q.a[3 * (size_t)qi + 1], q.a[3 * (size_t)qi + 2]};
-        const V3<T> d{q.b[3 * (size_t)qi], q.b[3 * (size_t)qi + 1], q.b[3 * (size_t)qi + 2]};
-        V3<T> he2{q.he[3 * (size_t)qi], q.he[3 * (size_t)qi + 1], q.he[3 * (size_t)qi + 2]};
-        const Q4<T> rot2{q.rot[4 * (size_t)qi], q.rot[4 * (size_t)qi + 1], q.rot[4 * (size_t)qi + 2], q.rot[4 * (size_t)qi + 3]};
+        const QShape<T> s = sp_load_shape<T>(q.shape, q.a, q.he, q.rot, qi);
+        const V3<T> d = sp_load3(q.b, qi);
         const T max_distance = q.max_distance[qi];
-        if (shape2 == AVN_SHAPE_BALL) he2 = V3<T>{he2.x, he2.x, he2.x};   // (a ball has its radius in x: y and z are not read)
-        // k_sp_shapes' rule, plus a finite direction and a max_distance that is not NaN: otherwise a miss / count 0
-        bool valid = shape2 <= AVN_SHAPE_BALL && is_finite(pos2) && is_finite(V3<T>{rot2.x, rot2.y, rot2.z}) && finite_t(rot2.w) && is_finite(he2) &&
-                     he2.x >= T(0) && he2.y >= T(0) && he2.z >= T(0) && is_finite(d) && max_distance == max_distance && (!PQ || q.live[qi] != 0);
-        RayCtx<T> r;
-        r.o = r.d = r.inv = vzero<T>(); r.zero = 0; r.tol = T(0);
-        V3<T> hw = vzero<T>();
-        Iso<T> iso2{Q4<T>{T(0), T(0), T(0), T(1)}, pos2};
-        if (valid) {
-            // the cast ray: from the centre of the query shape's AABB at its pose (padded as a leaf box is) along d
-            V3<T> a, b;
-            shape_aabb<T>(shape2, he2, pos2, rot2, a, b);
-            valid = is_finite(a) && is_finite(b);
-            const T pad = T(64) * Limits<T>::eps * smax(sp_maxabs(a), sp_maxabs(b));
-            const V3<T> pp{pad, pad, pad};
-            const V3<T> qmin = a - pp, qmax = b + pp;
-            r.o = (qmin + qmax) * T(0.5);
-            hw = (qmax - qmin) * T(0.5);
-            r.d = d;
-            r.inv = V3<T>{d.x != T(0) ? T(1) / d.x : T(0), d.y != T(0) ? T(1) / d.y : T(0), d.z != T(0) ? T(1) / d.z : T(0)};
-            r.zero = (d.x == T(0) ? 1u : 0u) | (d.y == T(0) ? 2u : 0u) | (d.z == T(0) ? 4u : 0u);
-            r.tol = T(64) * Limits<T>::eps * sp_maxabs(r.o);
-            iso2 = make_isometry(pos2, rot2);
-        }
+        // a valid shape, a finite direction and a max_distance that is not NaN: otherwise a miss / count 0
+        const bool valid = s.valid && is_finite(d) && max_distance == max_distance && (!PQ || q.live[qi] != 0);
+        V3<T> hw;
+        const RayCtx<T> r = sp_cast_ray(s, d, hw);
+        const Iso<T> iso2 = make_isometry(s.pos, s.rot);
         T best = sp_inf<T>();
         uint32_t best_c = AVN_SPATIAL_MISS;
         V3<T> best_p1 = vzero<T>(), best_p2 = vzero<T>(), best_n1 = vzero<T>();
         uint32_t found = 0;
-        SpatialShapeHit<T>* hl = MANY ? q.cast + (size_t)qi * q.cap : nullptr;
-        // entry distance of the cast ray into the node box grown by the query AABB's half widths (+inf = culled: only an entry STRICTLY
-        // above the best distance culls, so a collider at the best distance with a lower index is still reached)
+        SpatialShapeHit<T>* hl = q.cast + (size_t)qi * q.cap;
+        // entry distance of the cast ray (+inf = culled: only an entry STRICTLY above the best distance culls, so a collider at the best
+        // distance with a lower index is still reached)
         auto test = [&](uint32_t node) -> T {
             ++nodes_tested;
-            const Vec4<T> lo = sp.bmin[node], hi = sp.bmax[node];
-            return sp_ray_box(r, make4<T>(lo.x - hw.x, lo.y - hw.y, lo.z - hw.z, T(0)), make4<T>(hi.x + hw.x, hi.y + hw.y, hi.z + hw.z, T(0)),
-                              MANY ? max_distance : smin(best, max_distance));
+            return sp_cast_box(r, hw, sp.bmin[node], sp.bmax[node], MANY ? max_distance : smin(best, max_distance));
         };
-        auto leaf = [&](uint32_t node) {
-            const uint32_t c = sp.leaf_col[node - (n - 1)];
+        auto leaf = [&](uint32_t c) {
             const uint4 info = sp.info[c];
-            if (!info.w || (info.y & mask) == 0u || (!PQ && q.n_excluded && sp_excluded(q.excluded, q.n_excluded, info.x))) return;
-            if (PQ && ((self != AVN_SPATIAL_MISS && info.x == self) || (ex_n && sp_excluded(q.excluded + ex0, ex_n, info.x)))) return;
+            if (!sp_leaf_ok(info, mask, self, q.excluded + ex0, ex_n)) return;
             ++leaves_tested;
             T toi; V3<T> p1, p2, n1;
-            if (!sp_cast_exact<T>(shape2, he2, iso2, d, max_distance, info.z, xyz<T>(sp.he[c]), xyz<T>(sp.pos[c]), quat<T>(sp.rot[c]), toi, p1, p2, n1)) return;
+            if (!sp_cast_exact<T>(s.shape, s.he, iso2, d, max_distance, info.z, xyz<T>(sp.he[c]), xyz<T>(sp.pos[c]), quat<T>(sp.rot[c]), toi, p1, p2, n1)) return;
             if (!MANY) {
                 if (toi < best || (toi == best && c < best_c)) { best = toi; best_c = c; best_p1 = p1; best_p2 = p2; best_n1 = n1; }
             } else {
-                const uint32_t k = kq;
-                uint32_t m = found < k ? found : k;
-                ++found;
-                if (m == k) {
-                    const T ld = hl[k - 1].distance;
-                    if (!(toi < ld || (toi == ld && c < hl[k - 1].collider))) return;
-                    m = k - 1;
-                }
-                while (m > 0 && (hl[m - 1].distance > toi || (hl[m - 1].distance == toi && hl[m - 1].collider > c))) { hl[m] = hl[m - 1]; --m; }
+                const uint32_t m = sp_slot_by_distance(hl, kq, found, toi, c);
+                if (m == AVN_SPATIAL_MISS) return;
                 SpatialShapeHit<T> h;
                 sp_put<T>(h, c, info.x, toi, p1, p2, n1);
                 hl[m] = h;
             }
         };
-        if (valid && n >= 1 && test(0) != sp_inf<T>()) {
-            uint32_t sp_top = 0, node = 0;
-            for (;;) {
-                // (a tree of one collider: its root is the leaf, handled by the same leaf call site)
-                uint2 ch = make_uint2(0u, 0u);
-                T e0 = T(0), e1 = sp_inf<T>();
-                if (n > 1) { ch = sp.child[node]; e0 = test(ch.x); e1 = test(ch.y); }
-                const bool l0 = ch.x >= n - 1, l1 = ch.y >= n - 1;
-                // one leaf call site: the pair tests are emitted once
-                uint32_t pending = (l0 && e0 != sp_inf<T>() ? 1u : 0u) | (l1 && e1 != sp_inf<T>() ? 2u : 0u);
-                while (pending) {
-                    const bool first = (pending & 1u) != 0;
-                    // (the first leaf may have shrunk the best distance below the second one's entry)
-                    if (first || MANY || !(e1 > best)) leaf(first ? ch.x : ch.y);
-                    pending &= first ? ~1u : ~2u;
-                }
-                const bool g0 = !l0 && e0 != sp_inf<T>() && (MANY || !(e0 > best)), g1 = !l1 && e1 != sp_inf<T>() && (MANY || !(e1 > best));
-                if (g0 && g1) {
-                    const bool first0 = !(e1 < e0);   // the nearer child first (ties: the left one)
-                    if (sp_top < SP_STACK) { stack[sp_top * SP_WAVE + lane] = first0 ? ch.y : ch.x; ++sp_top; }
-                    else overflow = 1;   // (cannot happen: the depth of the tree is at most 64)
-                    node = first0 ? ch.x : ch.y;
-                    continue;
-                }
-                if (g0) { node = ch.x; continue; }
-                if (g1) { node = ch.y; continue; }
-                // pop; a node pushed before the best distance shrank is re-tested against it (closest hit only)
-                node = AVN_SPATIAL_MISS;
-                while (sp_top > 0) {
-                    --sp_top;
-                    const uint32_t cand = stack[sp_top * SP_WAVE + lane];
-                    if (MANY || test(cand) != sp_inf<T>()) { node = cand; break; }
-                }
-                if (node == AVN_SPATIAL_MISS) break;
-            }
-        }
+        if (valid) sp_walk<T, !MANY>(sp, overflow, best, test, leaf);
         if (!MANY) {
             SpatialShapeHit<T> h;
             sp_put<T>(h, best_c, best_c == AVN_SPATIAL_MISS ? AVN_SPATIAL_MISS : sp.info[best_c].x, best_c == AVN_SPATIAL_MISS ? T(0) : best, best_p1, best_p2, best_n1);
             if (!PQ) q.cast[qi] = h;
             else {
-                SpatialShapeHit<T>* row = q.cast + (size_t)qi * q.cap;
-                row[0] = h;
-                sp_put<T>(h, AVN_SPATIAL_MISS, AVN_SPATIAL_MISS, T(0), vzero<T>(), vzero<T>(), vzero<T>());
-                for (uint32_t m = 1; m < q.cap; ++m) row[m] = h;
+                // the caster's row: the hit or a miss, then misses; count 0 or 1
+                hl[0] = h;
+                sp_fill_miss(hl, 1u, q.cap);
                 q.count[qi] = best_c == AVN_SPATIAL_MISS ? 0u : 1u;
             }
         } else {
-            SpatialShapeHit<T> miss;
-            sp_put<T>(miss, AVN_SPATIAL_MISS, AVN_SPATIAL_MISS, T(0), vzero<T>(), vzero<T>(), vzero<T>());
-            for (uint32_t m = PQ ? (found < kq ? found : kq) : found; m < q.cap; ++m) hl[m] = miss;
+            sp_fill_miss(hl, found < kq ? found : kq, q.cap);
             q.count[qi] = found;
         }
     }
-    uint32_t a = nodes_tested, b = leaves_tested, o = overflow;
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) { a += __shfl_xor(a, off); b += __shfl_xor(b, off); o |= __shfl_xor(o, off); }
-    if (lane == 0) {
-        atomicAdd(&q.stats[0], (unsigned long long)a);
-        atomicAdd(&q.stats[1], (unsigned long long)b);
-        if (o) atomicOr(&q.stats[2], 1ull);
-    }
+    sp_add_stats(q.stats, nodes_tested, leaves_tested, overflow);
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// shape contacts and depenetration (kernels of their own: the kernels above compile as before).  The header defines a contact; the pair
-// arithmetic is the narrow phase's contact_manifolds_pair_sink, untouched.  DESIGN.md 4.4.7.
+// shape contacts and depenetration.  The header defines a contact; the pair arithmetic is the narrow phase's contact_manifolds_pair_sink,
+// untouched.  DESIGN.md 4.4.7.
 
-
-// one lane per query shape; blocks of one wave; records inserted in ascending collider index as k_sp_shapes inserts ids
+// one lane per query shape; records inserted in ascending collider index as k_sp_shapes inserts ids
 template <class T>
 __global__ __launch_bounds__(SP_WAVE) void k_sp_contacts(SP<T> sp, SC<T> sc) {
-    __shared__ uint32_t stack[SP_STACK * SP_WAVE];
     const SQ<T>& q = sc.q;
-    const uint32_t lane = threadIdx.x;
-    const uint32_t qi = blockIdx.x * SP_WAVE + lane;
+    const uint32_t qi = blockIdx.x * SP_WAVE + threadIdx.x;
     uint32_t nodes_tested = 0, leaves_tested = 0, overflow = 0;
-    const uint32_t n = sp.n;
     if (qi < q.n) {
         const uint32_t mask = q.mask ? q.mask[qi] : 0xFFFFFFFFu;
-        const uint32_t shape1 = q.shape[qi];
-        const V3<T> pos1{q.a[3 * (size_t)qi], q.a[3 * (size_t)qi + 1], q.a[3 * (size_t)qi + 2]};
-        V3<T> he1{q.he[3 * (size_t)qi], q.he[3 * (size_t)qi + 1], q.he[3 * (size_t)qi + 2]};
-        const Q4<T> rot1{q.rot[4 * (size_t)qi], q.rot[4 * (size_t)qi + 1], q.rot[4 * (size_t)qi + 2], q.rot[4 * (size_t)qi + 3]};
+        const QShape<T> s = sp_load_shape<T>(q.shape, q.a, q.he, q.rot, qi);
         const T pred = sc.prediction ? sc.prediction[qi] : sc.prediction_all;
         const uint32_t self = sc.self_entity ? sc.self_entity[qi] : AVN_SPATIAL_MISS;
-        if (shape1 == AVN_SHAPE_BALL) he1 = V3<T>{he1.x, he1.x, he1.x};   // (a ball has its radius in x: y and z are not read)
-        // k_sp_shapes' rule, plus a prediction distance that is finite and not negative: otherwise count 0
-        bool valid = shape1 <= AVN_SHAPE_BALL && is_finite(pos1) && is_finite(V3<T>{rot1.x, rot1.y, rot1.z}) && finite_t(rot1.w) && is_finite(he1) &&
-                     he1.x >= T(0) && he1.y >= T(0) && he1.z >= T(0) && finite_t(pred) && pred >= T(0);
-        V3<T> gmin = vzero<T>(), gmax = vzero<T>(), qmin = vzero<T>(), qmax = vzero<T>();
-        if (valid) {
-            // (b)'s box: the query shape's exact AABB grown by the prediction; the node test pads it as a leaf box is padded
-            V3<T> a, b;
-            shape_aabb<T>(shape1, he1, pos1, rot1, a, b);
-            valid = is_finite(a) && is_finite(b);
-            const V3<T> pv{pred, pred, pred};
-            gmin = a - pv; gmax = b + pv;
-            const T pad = T(64) * Limits<T>::eps * smax(sp_maxabs(gmin), sp_maxabs(gmax));
-            const V3<T> pp{pad, pad, pad};
-            qmin = gmin - pp; qmax = gmax + pp;
-        }
+        // a valid shape and a prediction distance that is finite and not negative: otherwise count 0
+        const bool valid = s.valid && finite_t(pred) && pred >= T(0);
+        // (b)'s box: the query shape's exact AABB grown by the prediction; the node test pads it as a leaf box is padded
+        const V3<T> pv{pred, pred, pred};
+        const V3<T> gmin = s.a - pv, gmax = s.b + pv;
+        V3<T> qmin, qmax;
+        sp_pad_box(gmin, gmax, qmin, qmax);
         uint32_t found = 0;
         SpatialShapeContact<T>* rl = sc.rec + (size_t)qi * q.cap;
-        auto test = [&](uint32_t node) -> bool {
+        auto test = [&](uint32_t node) -> T {
             ++nodes_tested;
-            return sp_box_box(qmin, qmax, sp.bmin[node], sp.bmax[node]);
+            return sp_box_box(qmin, qmax, sp.bmin[node], sp.bmax[node]) ? T(0) : sp_inf<T>();
         };
-        auto leaf = [&](uint32_t node) {
-            const uint32_t c = sp.leaf_col[node - (n - 1)];
+        auto leaf = [&](uint32_t c) {
             const uint4 info = sp.info[c];
-            if (!info.w || (info.y & mask) == 0u || (sc.skip_sensors && (info.w & SP_INFO_SENSOR)) || (self != AVN_SPATIAL_MISS && info.x == self) || (q.n_excluded && sp_excluded(q.excluded, q.n_excluded, info.x))) return;
+            if (!sp_leaf_ok(info, mask, self, q.excluded, q.n_excluded) || (sc.skip_sensors && (info.w & SP_INFO_SENSOR))) return;
             ++leaves_tested;
             const V3<T> pos2 = xyz<T>(sp.pos[c]), he2 = xyz<T>(sp.he[c]);
             const Q4<T> rot2 = quat<T>(sp.rot[c]);
@@ -940,16 +812,10 @@ __global__ __launch_bounds__(SP_WAVE) void k_sp_contacts(SP<T> sp, SC<T> sc) {
             // (c), (d)
             SpDeepestSink<T> sink{vzero<T>(), T(0), 0};
             V3<T> nrm;
-            if (!contact_manifolds_pair_sink<T, SpDeepestSink<T>>(shape1, he1, pos1, rot1, info.z, he2, pos2, rot2, pred, sink, nrm)) return;
-            const uint32_t k = q.cap;
-            uint32_t m = found < k ? found : k;
-            ++found;
-            if (m == k) {
-                if (k == 0 || c >= rl[k - 1].collider) return;
-                m = k - 1;
-            }
-            while (m > 0 && rl[m - 1].collider > c) { rl[m] = rl[m - 1]; --m; }
-            const V3<T> a1 = sink.anchor1, a2 = a1 + (pos1 - pos2), pt = pos1 + a1;
+            if (!contact_manifolds_pair_sink<T, SpDeepestSink<T>>(s.shape, s.he, s.pos, s.rot, info.z, he2, pos2, rot2, pred, sink, nrm)) return;
+            const uint32_t m = sp_slot_by_collider(rl, q.cap, found, c);
+            if (m == AVN_SPATIAL_MISS) return;
+            const V3<T> a1 = sink.anchor1, a2 = a1 + (s.pos - pos2), pt = s.pos + a1;
             SpatialShapeContact<T> r;
             r.collider = c; r.entity = info.x; r.penetration = sink.penetration;
             r.normal[0] = -nrm.x; r.normal[1] = -nrm.y; r.normal[2] = -nrm.z;
@@ -959,53 +825,11 @@ __global__ __launch_bounds__(SP_WAVE) void k_sp_contacts(SP<T> sp, SC<T> sc) {
             sp_clear_reserved(r);
             rl[m] = r;
         };
-        if (valid && n >= 1 && test(0)) {
-            uint32_t sp_top = 0, node = 0;
-            for (;;) {
-                // (a tree of one collider: its root is the leaf, handled by the same leaf call site)
-                uint2 ch = make_uint2(0u, 0u);
-                bool g0 = true, g1 = false;
-                if (n > 1) { ch = sp.child[node]; g0 = test(ch.x); g1 = test(ch.y); }
-                const bool l0 = ch.x >= n - 1, l1 = ch.y >= n - 1;
-                // one leaf call site: the manifold test is emitted once
-                uint32_t pending = (l0 && g0 ? 1u : 0u) | (l1 && g1 ? 2u : 0u);
-                while (pending) {
-                    const bool first = (pending & 1u) != 0;
-                    leaf(first ? ch.x : ch.y);
-                    pending &= first ? ~1u : ~2u;
-                }
-                if (l0) g0 = false;
-                if (l1) g1 = false;
-                if (g0 && g1) {
-                    if (sp_top < SP_STACK) { stack[sp_top * SP_WAVE + lane] = ch.y; ++sp_top; }
-                    else overflow = 1;   // (cannot happen: the depth of the tree is at most 64)
-                    node = ch.x;
-                    continue;
-                }
-                if (g0) { node = ch.x; continue; }
-                if (g1) { node = ch.y; continue; }
-                if (sp_top == 0) break;
-                --sp_top;
-                node = stack[sp_top * SP_WAVE + lane];
-            }
-        }
-        if (sc.pad_unused && found < q.cap) {
-            SpatialShapeContact<T> miss;
-            miss.collider = AVN_SPATIAL_MISS; miss.entity = AVN_SPATIAL_MISS; miss.penetration = T(0);
-            for (int i = 0; i < 3; ++i) miss.normal[i] = miss.point[i] = miss.anchor1[i] = miss.anchor2[i] = T(0);
-            sp_clear_reserved(miss);
-            for (uint32_t m = found; m < q.cap; ++m) rl[m] = miss;
-        }
+        if (valid) sp_walk<T, false>(sp, overflow, T(0), test, leaf);
+        if (sc.pad_unused) sp_fill_miss(rl, found, q.cap);
         q.count[qi] = found;
     }
-    uint32_t a = nodes_tested, b = leaves_tested, o = overflow;
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) { a += __shfl_xor(a, off); b += __shfl_xor(b, off); o |= __shfl_xor(o, off); }
-    if (lane == 0) {
-        atomicAdd(&q.stats[0], (unsigned long long)a);
-        atomicAdd(&q.stats[1], (unsigned long long)b);
-        if (o) atomicOr(&q.stats[2], 1ull);
-    }
+    sp_add_stats(q.stats, nodes_tested, leaves_tested, overflow);
 }
 
 // Dir is f32: an f64 world rounds every normal component through float (Dir::new_unchecked(-manifold.normal.f32()), adjust_precision())
@@ -1054,8 +878,8 @@ template <class T> void launch_spatial_depenetrate(const SD<T>& d, hipStream_t s
 }
 
 // ---------------------------------------------------------------------------------------------------------
-// move and slide (kernels of their own: the kernels above compile as before).  The header defines project_velocity, cast_move and the loop,
-// operation order included; tests/spatial_move_reference.py does the same operations in order.  DESIGN.md 4.4.8.
+// move and slide.  The header defines project_velocity, cast_move and the loop, operation order included; tests/spatial_move_reference.py
+// does the same operations in order.  DESIGN.md 4.4.8.
 
 // Scalar::total_cmp as an integer key
 __device__ __forceinline__ long long sp_total_key(float x) { const int b = __float_as_int(x); return b < 0 ? (b ^ 0x7FFFFFFF) : b; }
@@ -1142,48 +966,23 @@ template <class T> __device__ __forceinline__ void sp_put_move(SpatialMoveHit<T>
 // range (fused into the leaf the kernel needed 256 VGPRs + 13 / 72 AGPRs, one wave per SIMD: profiles/spatial_moves_resource_usage.txt).
 template <class T>
 __global__ __launch_bounds__(SP_WAVE) void k_sp_cast_move(SP<T> sp, SM<T> m) {
-    __shared__ uint32_t stack[SP_STACK * SP_WAVE];
     const SQ<T>& q = m.q;
-    const uint32_t lane = threadIdx.x;
-    const uint32_t qi = blockIdx.x * SP_WAVE + lane;
+    const uint32_t qi = blockIdx.x * SP_WAVE + threadIdx.x;
     uint32_t nodes_tested = 0, leaves_tested = 0, overflow = 0;
-    const uint32_t n = sp.n;
     if (qi < q.n) {
         const uint32_t mask = q.mask ? q.mask[qi] : 0xFFFFFFFFu;
         const uint32_t self = m.self_entity ? m.self_entity[qi] : AVN_SPATIAL_MISS;
-        const uint32_t shape2 = q.shape[qi];
-        const V3<T> pos2{q.a[3 * (size_t)qi], q.a[3 * (size_t)qi + 1], q.a[3 * (size_t)qi + 2]};
-        const V3<T> mv{m.movement[3 * (size_t)qi], m.movement[3 * (size_t)qi + 1], m.movement[3 * (size_t)qi + 2]};
-        V3<T> he2{q.he[3 * (size_t)qi], q.he[3 * (size_t)qi + 1], q.he[3 * (size_t)qi + 2]};
-        const Q4<T> rot2{q.rot[4 * (size_t)qi], q.rot[4 * (size_t)qi + 1], q.rot[4 * (size_t)qi + 2], q.rot[4 * (size_t)qi + 3]};
+        const QShape<T> s = sp_load_shape<T>(q.shape, q.a, q.he, q.rot, qi);
+        const V3<T> mv = sp_load3(m.movement, qi);
         const T skin = m.skin ? m.skin[qi] : m.skin_all;
-        if (shape2 == AVN_SHAPE_BALL) he2 = V3<T>{he2.x, he2.x, he2.x};
-        // k_sp_shapes' rule, plus a finite movement and a skin width that is finite and not negative; a slide's finished character: a miss
-        bool valid = shape2 <= AVN_SHAPE_BALL && is_finite(pos2) && is_finite(V3<T>{rot2.x, rot2.y, rot2.z}) && finite_t(rot2.w) && is_finite(he2) &&
-                     he2.x >= T(0) && he2.y >= T(0) && he2.z >= T(0) && is_finite(mv) && finite_t(skin) && skin >= T(0) &&
-                     (!m.state || (m.state[qi] & SP_SLIDE_LIVE));
+        // a valid shape, a finite movement and a skin width that is finite and not negative; a slide's finished character: a miss
+        const bool valid = s.valid && is_finite(mv) && finite_t(skin) && skin >= T(0) && (!m.state || (m.state[qi] & SP_SLIDE_LIVE));
         V3<T> d{T(1), T(0), T(0)};
         T dist = T(0);
         if (valid && !sp_dir_and_length<T>(mv, d, dist)) { d = V3<T>{T(1), T(0), T(0)}; dist = T(0); }
-        RayCtx<T> r;
-        r.o = r.d = r.inv = vzero<T>(); r.zero = 0; r.tol = T(0);
-        V3<T> hw = vzero<T>();
-        Iso<T> iso2{Q4<T>{T(0), T(0), T(0), T(1)}, pos2};
-        if (valid) {
-            V3<T> a, b;
-            shape_aabb<T>(shape2, he2, pos2, rot2, a, b);
-            valid = is_finite(a) && is_finite(b);
-            const T pad = T(64) * Limits<T>::eps * smax(sp_maxabs(a), sp_maxabs(b));
-            const V3<T> pp{pad, pad, pad};
-            const V3<T> qmin = a - pp, qmax = b + pp;
-            r.o = (qmin + qmax) * T(0.5);
-            hw = (qmax - qmin) * T(0.5);
-            r.d = d;
-            r.inv = V3<T>{d.x != T(0) ? T(1) / d.x : T(0), d.y != T(0) ? T(1) / d.y : T(0), d.z != T(0) ? T(1) / d.z : T(0)};
-            r.zero = (d.x == T(0) ? 1u : 0u) | (d.y == T(0) ? 2u : 0u) | (d.z == T(0) ? 4u : 0u);
-            r.tol = T(64) * Limits<T>::eps * sp_maxabs(r.o);
-            iso2 = make_isometry(pos2, rot2);
-        }
+        V3<T> hw;
+        const RayCtx<T> r = sp_cast_ray(s, d, hw);
+        const Iso<T> iso2 = make_isometry(s.pos, s.rot);
         T best = sp_inf<T>();
         uint32_t best_c = AVN_SPATIAL_MISS;
         V3<T> best_p1 = vzero<T>(), best_p2 = vzero<T>(), best_n1 = vzero<T>();
@@ -1191,19 +990,16 @@ __global__ __launch_bounds__(SP_WAVE) void k_sp_cast_move(SP<T> sp, SM<T> m) {
         uint32_t* pend = m.pending + (size_t)qi * AVN_SPATIAL_MAX_HITS;
         auto test = [&](uint32_t node) -> T {
             ++nodes_tested;
-            const Vec4<T> lo = sp.bmin[node], hi = sp.bmax[node];
-            return sp_ray_box(r, make4<T>(lo.x - hw.x, lo.y - hw.y, lo.z - hw.z, T(0)), make4<T>(hi.x + hw.x, hi.y + hw.y, hi.z + hw.z, T(0)), smin(best, dist));
+            return sp_cast_box(r, hw, sp.bmin[node], sp.bmax[node], smin(best, dist));
         };
-        auto leaf = [&](uint32_t node) {
-            const uint32_t c = sp.leaf_col[node - (n - 1)];
+        auto leaf = [&](uint32_t c) {
             const uint4 info = sp.info[c];
-            if (!info.w || (info.w & SP_INFO_SENSOR) || (info.y & mask) == 0u || (self != AVN_SPATIAL_MISS && info.x == self) ||
-                (q.n_excluded && sp_excluded(q.excluded, q.n_excluded, info.x))) return;
+            if (!sp_leaf_ok(info, mask, self, q.excluded, q.n_excluded) || (info.w & SP_INFO_SENSOR)) return;
             ++leaves_tested;
             const V3<T> pos1 = xyz<T>(sp.pos[c]), he1 = xyz<T>(sp.he[c]);
             const Q4<T> rot1 = quat<T>(sp.rot[c]);
             T toi; V3<T> p1, p2, n1;
-            if (!sp_cast_exact<T>(shape2, he2, iso2, d, dist, info.z, he1, pos1, rot1, toi, p1, p2, n1)) return;
+            if (!sp_cast_exact<T>(s.shape, s.he, iso2, d, dist, info.z, he1, pos1, rot1, toi, p1, p2, n1)) return;
             if (toi == T(0) && n1.x == T(0) && n1.y == T(0) && n1.z == T(0)) {
                 // overlapping at the start: the pair's contact decides, in k_sp_cast_move_resolve
                 if (n_pending < AVN_SPATIAL_MAX_HITS) pend[n_pending] = c;
@@ -1213,39 +1009,7 @@ __global__ __launch_bounds__(SP_WAVE) void k_sp_cast_move(SP<T> sp, SM<T> m) {
             }
             if (toi < best || (toi == best && c < best_c)) { best = toi; best_c = c; best_p1 = p1; best_p2 = p2; best_n1 = n1; }
         };
-        if (valid && n >= 1 && test(0) != sp_inf<T>()) {
-            uint32_t sp_top = 0, node = 0;
-            for (;;) {
-                uint2 ch = make_uint2(0u, 0u);
-                T e0 = T(0), e1 = sp_inf<T>();
-                if (n > 1) { ch = sp.child[node]; e0 = test(ch.x); e1 = test(ch.y); }
-                const bool l0 = ch.x >= n - 1, l1 = ch.y >= n - 1;
-                // one leaf call site: the pair tests are emitted once
-                uint32_t pending = (l0 && e0 != sp_inf<T>() ? 1u : 0u) | (l1 && e1 != sp_inf<T>() ? 2u : 0u);
-                while (pending) {
-                    const bool first = (pending & 1u) != 0;
-                    if (first || !(e1 > best)) leaf(first ? ch.x : ch.y);
-                    pending &= first ? ~1u : ~2u;
-                }
-                const bool g0 = !l0 && e0 != sp_inf<T>() && !(e0 > best), g1 = !l1 && e1 != sp_inf<T>() && !(e1 > best);
-                if (g0 && g1) {
-                    const bool first0 = !(e1 < e0);
-                    if (sp_top < SP_STACK) { stack[sp_top * SP_WAVE + lane] = first0 ? ch.y : ch.x; ++sp_top; }
-                    else overflow = 1;   // (cannot happen: the depth of the tree is at most 64)
-                    node = first0 ? ch.x : ch.y;
-                    continue;
-                }
-                if (g0) { node = ch.x; continue; }
-                if (g1) { node = ch.y; continue; }
-                node = AVN_SPATIAL_MISS;
-                while (sp_top > 0) {
-                    --sp_top;
-                    const uint32_t cand = stack[sp_top * SP_WAVE + lane];
-                    if (test(cand) != sp_inf<T>()) { node = cand; break; }
-                }
-                if (node == AVN_SPATIAL_MISS) break;
-            }
-        }
+        if (valid) sp_walk<T, true>(sp, overflow, best, test, leaf);
         // the traversal's own answer (the hit's distance, not yet pulled back) and the pending count: k_sp_cast_move_resolve finishes the record
         SpatialMoveHit<T> h;
         if (best_c == AVN_SPATIAL_MISS) sp_put_move<T>(h, AVN_SPATIAL_MISS, AVN_SPATIAL_MISS, T(0), T(0), vzero<T>(), vzero<T>(), vzero<T>());
@@ -1253,14 +1017,7 @@ __global__ __launch_bounds__(SP_WAVE) void k_sp_cast_move(SP<T> sp, SM<T> m) {
         m.out[qi] = h;
         m.pending_count[qi] = n_pending;
     }
-    uint32_t a = nodes_tested, b = leaves_tested, o = overflow;
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) { a += __shfl_xor(a, off); b += __shfl_xor(b, off); o |= __shfl_xor(o, off); }
-    if (lane == 0) {
-        atomicAdd(&q.stats[0], (unsigned long long)a);
-        atomicAdd(&q.stats[1], (unsigned long long)b);
-        if (o) atomicOr(&q.stats[2], (unsigned long long)o);   // bit 0: stack overflow; bit 1: more than AVN_SPATIAL_MAX_HITS pending colliders
-    }
+    sp_add_stats(q.stats, nodes_tested, leaves_tested, overflow);
 }
 
 template <class T>
@@ -1272,13 +1029,9 @@ __global__ __launch_bounds__(SP_WAVE) void k_sp_cast_move_resolve(SP<T> sp, SM<T
     const uint32_t count = m.pending_count[qi];
     const uint32_t np = count < AVN_SPATIAL_MAX_HITS ? count : AVN_SPATIAL_MAX_HITS;
     if (h.collider == AVN_SPATIAL_MISS && np == 0) return;   // a miss, an invalid query, a slide's finished character: the record stands
-    const uint32_t shape2 = q.shape[qi];
-    const V3<T> pos2{q.a[3 * (size_t)qi], q.a[3 * (size_t)qi + 1], q.a[3 * (size_t)qi + 2]};
-    const V3<T> mv{m.movement[3 * (size_t)qi], m.movement[3 * (size_t)qi + 1], m.movement[3 * (size_t)qi + 2]};
-    V3<T> he2{q.he[3 * (size_t)qi], q.he[3 * (size_t)qi + 1], q.he[3 * (size_t)qi + 2]};
-    const Q4<T> rot2{q.rot[4 * (size_t)qi], q.rot[4 * (size_t)qi + 1], q.rot[4 * (size_t)qi + 2], q.rot[4 * (size_t)qi + 3]};
+    const QShape<T> s = sp_load_shape<T>(q.shape, q.a, q.he, q.rot, qi);   // (valid: k_sp_cast_move hit or noted something)
+    const V3<T> mv = sp_load3(m.movement, qi);
     const T skin = m.skin ? m.skin[qi] : m.skin_all;
-    if (shape2 == AVN_SHAPE_BALL) he2 = V3<T>{he2.x, he2.x, he2.x};
     V3<T> d{T(1), T(0), T(0)};
     T dist = T(0);
     if (!sp_dir_and_length<T>(mv, d, dist)) { d = V3<T>{T(1), T(0), T(0)}; dist = T(0); }
@@ -1297,11 +1050,11 @@ __global__ __launch_bounds__(SP_WAVE) void k_sp_cast_move_resolve(SP<T> sp, SM<T
         V3<T> p1 = vzero<T>(), p2 = vzero<T>(), n1 = vzero<T>();
         SpDeepestSink<T> sink{vzero<T>(), T(0), 0};
         V3<T> nrm;
-        if (contact_manifolds_pair_sink<T, SpDeepestSink<T>>(shape2, he2, pos2, rot2, info.z, he1, pos1, rot1, T(0), sink, nrm)) {
+        if (contact_manifolds_pair_sink<T, SpDeepestSink<T>>(s.shape, s.he, s.pos, s.rot, info.z, he1, pos1, rot1, T(0), sink, nrm)) {
             const V3<T> cn{-nrm.x, -nrm.y, -nrm.z};
             if (d.x * cn.x + d.y * cn.y + d.z * cn.z >= T(0)) continue;   // on its way out: ignored by this cast
-            const V3<T> a1 = sink.anchor1, a2 = a1 + (pos2 - pos1);
-            n1 = cn; p1 = pos1 + a2; p2 = pos2 + a1;
+            const V3<T> a1 = sink.anchor1, a2 = a1 + (s.pos - pos1);
+            n1 = cn; p1 = pos1 + a2; p2 = s.pos + a1;
         }
         best = T(0); best_c = c; best_e = info.x; best_p1 = p1; best_p2 = p2; best_n1 = n1;
     }
@@ -1339,17 +1092,7 @@ __global__ __launch_bounds__(SP_WAVE) void k_sp_slide(SL<T> l) {
     if (qi >= l.n) return;
     const size_t q3 = 3 * (size_t)qi;
     if (PHASE == SPL_BEGIN) {
-        const uint32_t shape = l.shape[qi];
-        const V3<T> pos{l.pos_in[q3], l.pos_in[q3 + 1], l.pos_in[q3 + 2]};
-        V3<T> he{l.he[q3], l.he[q3 + 1], l.he[q3 + 2]};
-        const Q4<T> rot{l.rot[4 * (size_t)qi], l.rot[4 * (size_t)qi + 1], l.rot[4 * (size_t)qi + 2], l.rot[4 * (size_t)qi + 3]};
-        if (shape == AVN_SHAPE_BALL) he = V3<T>{he.x, he.x, he.x};
-        bool valid = shape <= AVN_SHAPE_BALL && is_finite(pos) && is_finite(V3<T>{rot.x, rot.y, rot.z}) && finite_t(rot.w) && is_finite(he) && he.x >= T(0) && he.y >= T(0) && he.z >= T(0);
-        if (valid) {
-            V3<T> a, b;
-            shape_aabb<T>(shape, he, pos, rot, a, b);
-            valid = is_finite(a) && is_finite(b);
-        }
+        const bool valid = sp_load_shape<T>(l.shape, l.pos_in, l.he, l.rot, qi).valid;
         for (int i = 0; i < 3; ++i) { l.pos[q3 + i] = l.pos_in[q3 + i]; l.vel[q3 + i] = l.vel_in[q3 + i]; l.movement[q3 + i] = T(0); }
         l.time_left[qi] = l.delta_time;
         l.flags[qi] = valid ? (SP_SLIDE_VALID | SP_SLIDE_LIVE) : 0u;

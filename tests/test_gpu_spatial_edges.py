@@ -219,6 +219,20 @@ def test_query_edges(bits):
             ids, cnt = sq.aabb_intersections(p - 1, p + 1, cap)
             ri, rc = R.aabb_intersections(s, p - 1, p + 1, cap)
             assert ids.shape == (n, cap) and np.array_equal(cnt, rc) and np.array_equal(ids, ri)
+    # two identical cuboids at one pose (colliders 1 and 2) with a third (collider 0) behind them, 65 rays (a second, partial wave): the
+    # closest hit is the lower index of the two at the equal distance, whichever of them the traversal reaches first
+    pos = np.array([[3.0, 0, 0], [0, 0, 0], [0, 0, 0]])
+    cols = dict(entity_index=np.arange(3, dtype=np.uint32), body=np.arange(3, dtype=np.int32), shape=np.zeros(3, np.uint8), half_extents=np.full((3, 3), 0.5))
+    bodies = S.bodies_of(pos, np.tile(S.IDENTITY, (3, 1)))
+    w = world_of(bits, bodies, cols)
+    sq = SpatialQuery(w)
+    sq.update()
+    s = R.Snapshot(bodies, cols, None, dt)
+    o = np.c_[np.full(65, -5.0), rng.uniform(-0.4, 0.4, (65, 2))]
+    d = np.tile([1.0, 0, 0], (65, 1))
+    closest = check_queries(sq, s, o, d, np.full(65, np.inf), np.ones(65, np.uint8), o, o - 1, o + 1, ks=(1, 3))
+    assert (closest["collider"] == 1).all() and (sq.cast_rays(o, d)["collider"] == 1).all()
+    assert (sq.cast_rays(o + [10.0, 0, 0], -d)["collider"] == 0).all()
 
 
 # ---- non-finite ---------------------------------------------------------------------------------------------------------------------------
