@@ -444,8 +444,8 @@ template <class T> struct SQ {
     uint32_t* count;                 // [n]
     unsigned long long* stats;       // [3]: node boxes tested, exact tests, stack overflow flag (zeroed by the launch)
     // SPQ_PROJECT (a = points, solid) and SPQ_SHAPES (a = positions): kernels of their own, k_sp_project / k_sp_shapes
-    const uint8_t* shape;            // [n] AVN_SHAPE_CUBOID / AVN_SHAPE_BALL of the query shape
-    const T* he;                     // [3n] half extents (ball: radius in x)
+    const uint8_t* shape;            // [n] AVN_SHAPE_CUBOID / AVN_SHAPE_BALL / AVN_SHAPE_CAPSULE of the query shape
+    const T* he;                     // [3n] half extents (ball: radius in x; capsule: radius in x, half length in y)
     const T* rot;                    // [4n] xyzw
     SpatialProjection<T>* proj;      // [n]
     // SPQ_CAST / SPQ_CAST_HITS (the SPQ_SHAPES fields, b = directions, max_distance; cap = max_hits): k_sp_cast
@@ -548,14 +548,15 @@ template <class T> struct SL {
     SpatialSlideHit<T>* hits; SpatialSlide<T>* out;                      // the call's outputs
 };
 template <class T> void launch_spatial_project_velocity(const SV<T>&, hipStream_t);
-template <class T> void launch_spatial_cast_move(const SP<T>&, const SM<T>&, bool zero_stats, hipStream_t);
+// capsule (here and below): the call may hold AVN_SHAPE_CAPSULE query shapes, so the kernels' CAPSULE instantiations run behind the first launch
+template <class T> void launch_spatial_cast_move(const SP<T>&, const SM<T>&, bool zero_stats, hipStream_t, bool capsule = false);
 template <class T> void launch_spatial_slide_phase(const SL<T>&, int phase, hipStream_t);
 template <class T> void launch_spatial_build(const DW<T>&, const BP<T>&, const SP<T>&, hipStream_t);
-template <class T> void launch_spatial_query(const SP<T>&, const SQ<T>&, int kind, hipStream_t);
+template <class T> void launch_spatial_query(const SP<T>&, const SQ<T>&, int kind, hipStream_t, bool capsule = false);
 template <class T> void launch_spatial_reaim(const DW<T>&, const SP<T>&, const SCA<T>&, hipStream_t);
 // a caster group: kind SPQ_CLOSEST / SPQ_HITS / SPQ_CAST / SPQ_CAST_HITS with the per-query filter; q.stats is NOT zeroed (the run zeroes it once)
-template <class T> void launch_spatial_casters(const SP<T>&, const SQ<T>&, int kind, hipStream_t);
-template <class T> void launch_spatial_contacts(const SP<T>&, const SC<T>&, hipStream_t, bool zero_stats = true);
+template <class T> void launch_spatial_casters(const SP<T>&, const SQ<T>&, int kind, hipStream_t, bool capsule = false);
+template <class T> void launch_spatial_contacts(const SP<T>&, const SC<T>&, hipStream_t, bool zero_stats = true, bool capsule = false);
 template <class T> void launch_spatial_depenetrate(const SD<T>&, hipStream_t);
 
 // ---- k_ccd.hip: swept CCD (solve_swept_ccd, dynamics/ccd/mod.rs:523-687; include/avian_mi355x_ccd.h) as a pass over the contact rows ----

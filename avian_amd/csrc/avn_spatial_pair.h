@@ -1,6 +1,7 @@
 // avn_spatial_pair.h — the per-pair device functions of the shape casts and of the origin-penetration rule (include/avian_mi355x_spatial.h
 // "shape cast", "shape contacts"): shared by the spatial queries (k_spatial.hip) and the swept CCD pass (k_ccd.hip).  The header defines
-// the per-pair tests, operation order included; tests/spatial_cast_reference.py does the same operations in order.
+// the per-pair tests, operation order included; tests/spatial_cast_reference.py does the same operations in order.  The capsule query
+// shape's pair tests (the spatial queries only) are at the end: tests/spatial_capsule_reference.py.
 #pragma once
 #include "avn_kernels.h"
 #include "avn_narrow.h"
@@ -261,6 +262,259 @@ __device__ __forceinline__ bool sp_cast_exact(uint32_t shape2, V3<T> he2, const 
         }
     }
     p1 = w1; p2 = w2; n1 = wn;
+    return true;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// The capsule as a QUERY shape (AVN_SHAPE_CAPSULE, include/avian_mi355x_spatial.h "capsule query shapes"): parry's Capsule::new_y, the
+// segment (0, -h, 0) .. (0, +h, 0) of the shape's frame swept by a ball of radius r.  Every pair test works on the capsule's core segment
+// A + s u, s in [0, 1], in the collider's frame; a ball collider's core is its centre, a cuboid's the box.  The header defines the tests,
+// operation order included; tests/spatial_capsule_reference.py does the same operations in order.
+template <class T> __device__ __forceinline__ void sp_capsule_core(const Iso<T>& q, T h, V3<T>& A, V3<T>& u) {
+    const V3<T> hv = na_qrot(q.r, V3<T>{T(0), h, T(0)});
+    A = q.t - hv;
+    u = hv * T(2);
+}
+// segment - point: the squared distance and the parameter of the nearest point
+template <class T> __device__ __forceinline__ T sp_seg_point(V3<T> A, V3<T> u, V3<T> c, T& s_out) {
+    const T uu = na_dot(u, u);
+    T s = na_dot(c - A, u) / uu;
+    s = s < T(0) ? T(0) : (s > T(1) ? T(1) : s);
+    if (uu == T(0)) s = T(0);
+    const V3<T> e = c - (A + u * s);
+    s_out = s;
+    return na_dot(e, e);
+}
+// segment - box, exact.  f(s) = sum_i max(|x_i(s)| - he_i, 0)^2 is convex and piecewise quadratic; its breakpoints are the s = (+-he_i - A_i) / u_i
+// strictly inside (0, 1) (one that is not counts as 1).  Candidates, in this order: 0, 1, the six breakpoints ascending (a 12-comparator
+// network), then per interval between neighbours of 0 <= b_1 <= .. <= b_6 <= 1 the minimiser of the quadratic whose active faces are read at
+// the interval's midpoint, clamped to the interval (the midpoint itself when no face is active: f = 0 there; the interval's start when
+// the active axes have no slope).  The first candidate with the smallest f, evaluated in full, wins (strict <).
+template <class T> struct SegBox { T f, s; V3<T> ps, pb; };
+template <class T> __device__ __forceinline__ T sp_seg_break(T a, T u, T h) {
+    const T s = (h - a) / u;
+    return (u != T(0) && s > T(0) && s < T(1)) ? s : T(1);
+}
+template <class T> __device__ __forceinline__ void sp_seg_order(T& a, T& b) {
+    const bool sw = b < a;
+    const T lo = sw ? b : a, hi = sw ? a : b;
+    a = lo; b = hi;
+}
+template <class T> __device__ __forceinline__ void sp_seg_try(V3<T> A, V3<T> u, V3<T> he, T s, T& bf, T& bs) {
+    const V3<T> p = A + u * s;
+    const V3<T> e = p - sp_clamp3(p, he);
+    const T f = na_dot(e, e);
+    if (f < bf) { bf = f; bs = s; }
+}
+template <class T> __device__ __forceinline__ void sp_seg_interval(V3<T> A, V3<T> u, V3<T> he, T lo, T hi, T& bf, T& bs) {
+    const T mid = (lo + hi) * T(0.5);
+    const V3<T> m = A + u * mid;
+    const T sx = m.x > he.x ? T(1) : (m.x < -he.x ? T(-1) : T(0));
+    const T sy = m.y > he.y ? T(1) : (m.y < -he.y ? T(-1) : T(0));
+    const T sz = m.z > he.z ? T(1) : (m.z < -he.z ? T(-1) : T(0));
+    const T den = (sx != T(0) ? u.x * u.x : T(0)) + (sy != T(0) ? u.y * u.y : T(0)) + (sz != T(0) ? u.z * u.z : T(0));
+    const T num = (sx != T(0) ? u.x * (A.x - sx * he.x) : T(0)) + (sy != T(0) ? u.y * (A.y - sy * he.y) : T(0)) + (sz != T(0) ? u.z * (A.z - sz * he.z) : T(0));
+    T s = -num / den;
+    s = s < lo ? lo : (s > hi ? hi : s);
+    const bool none = sx == T(0) && sy == T(0) && sz == T(0);
+    sp_seg_try<T>(A, u, he, none ? mid : (den > T(0) ? s : lo), bf, bs);
+}
+template <class T> __device__ __forceinline__ SegBox<T> sp_seg_box(V3<T> A, V3<T> u, V3<T> he) {
+    T b0 = sp_seg_break<T>(A.x, u.x, -he.x), b1 = sp_seg_break<T>(A.x, u.x, he.x), b2 = sp_seg_break<T>(A.y, u.y, -he.y), b3 = sp_seg_break<T>(A.y, u.y, he.y),
+      b4 = sp_seg_break<T>(A.z, u.z, -he.z), b5 = sp_seg_break<T>(A.z, u.z, he.z);
+    sp_seg_order(b0, b5); sp_seg_order(b1, b3); sp_seg_order(b2, b4);
+    sp_seg_order(b1, b2); sp_seg_order(b3, b4);
+    sp_seg_order(b0, b3); sp_seg_order(b2, b5);
+    sp_seg_order(b0, b1); sp_seg_order(b2, b3); sp_seg_order(b4, b5);
+    sp_seg_order(b1, b2); sp_seg_order(b3, b4);
+    T bf = sp_inf<T>(), bs = T(0);
+    sp_seg_try<T>(A, u, he, T(0), bf, bs); sp_seg_try<T>(A, u, he, T(1), bf, bs);
+    sp_seg_try<T>(A, u, he, b0, bf, bs); sp_seg_try<T>(A, u, he, b1, bf, bs); sp_seg_try<T>(A, u, he, b2, bf, bs);
+    sp_seg_try<T>(A, u, he, b3, bf, bs); sp_seg_try<T>(A, u, he, b4, bf, bs); sp_seg_try<T>(A, u, he, b5, bf, bs);
+    sp_seg_interval<T>(A, u, he, T(0), b0, bf, bs); sp_seg_interval<T>(A, u, he, b0, b1, bf, bs); sp_seg_interval<T>(A, u, he, b1, b2, bf, bs);
+    sp_seg_interval<T>(A, u, he, b2, b3, bf, bs); sp_seg_interval<T>(A, u, he, b3, b4, bf, bs); sp_seg_interval<T>(A, u, he, b4, b5, bf, bs);
+    sp_seg_interval<T>(A, u, he, b5, T(1), bf, bs);
+    SegBox<T> r;
+    r.f = bf; r.s = bs;
+    r.ps = A + u * bs;
+    r.pb = sp_clamp3(r.ps, he);
+    return r;
+}
+
+// intersection of the capsule (r, h) at the relative pose q (the capsule in the collider's frame) with the collider: core distance^2 <= (r + r_c)^2
+template <class T> __device__ __forceinline__ bool sp_capsule_intersects(T r, T h, const Iso<T>& q, uint32_t shape1, V3<T> he1) {
+    V3<T> A, u;
+    sp_capsule_core<T>(q, h, A, u);
+    if (shape1 == AVN_SHAPE_BALL) {
+        T s;
+        const T d2 = sp_seg_point<T>(A, u, vzero<T>(), s);
+        const T rr = r + he1.x;
+        return d2 <= rr * rr;
+    }
+    return sp_seg_box<T>(A, u, he1).f <= r * r;
+}
+
+// The ray (o, d) of a ball's centre against the capsule (R, h) in the capsule's frame: the cylinder about y clipped to |y| <= h, then the end
+// spheres at -h and +h; the smallest entry wins (strict <), its primitive gives the normal.  pen: the origin is inside the winning primitive.
+template <class T> __device__ __forceinline__ bool sp_capsule_ray(V3<T> o, V3<T> d, T h, T R, T& t_out, V3<T>& n_out, bool& pen_out) {
+    T best = sp_inf<T>();
+    V3<T> bn = vzero<T>();
+    bool bpen = false, found = false;
+    {
+        const T a = d.x * d.x + d.z * d.z;
+        const T b = o.x * d.x + o.z * d.z, c = (o.x * o.x + o.z * o.z) - R * R;
+        const T q = b / a;
+        const T fa = o.x - d.x * q, fb = o.z - d.z * q;
+        const T delta = a * (R * R - (fa * fa + fb * fb));
+        T t = (-b - sqrt_t(delta)) / a;
+        const bool inside = t <= T(0);
+        if (inside) t = T(0);
+        const T y = o.y + d.y * t;
+        // (a ray parallel to the axis: the end spheres decide)
+        if (a > T(0) && !(c > T(0) && b > T(0)) && !(delta < T(0)) && fabs_t(y) <= h) {
+            best = t; found = true; bpen = inside;
+            const T pa = o.x + d.x * t, pb = o.z + d.z * t;
+            const T l = sqrt_t(pa * pa + pb * pb);
+            bn = (inside || !(l > T(0))) ? vzero<T>() : V3<T>{pa / l, T(0), pb / l};
+        }
+    }
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+        const V3<T> oc{o.x, e == 0 ? o.y + h : o.y - h, o.z};
+        T t; bool inside;
+        if (!sp_ball_ray<T>(oc, d, R, t, inside)) continue;
+        if (t < best) {
+            best = t; found = true; bpen = inside;
+            const V3<T> p = oc + d * t;
+            const T l = length(p);
+            bn = (inside || !(l > T(0))) ? vzero<T>() : p / l;
+        }
+    }
+    if (!found) return false;
+    t_out = best; n_out = bn; pen_out = bpen;
+    return true;
+}
+
+#define SP_CAPSULE_ROUNDS 32
+// The cast of the capsule (r, h) at pose iso2 along d against one collider.  A ball collider: its centre as a ray against the capsule grown by
+// the ball's radius, in the capsule's frame with the ray reversed.  A cuboid: Newton's iteration on g(t) = dist(segment + t dl, box) - r
+// from t = 0, which rises monotonically to the root from its left (g is convex); at most SP_CAPSULE_ROUNDS evaluations, the last t standing.
+// Same answer as sp_cast_exact: everything zero when the shapes overlap at the start.
+template <class T>
+__device__ __forceinline__ bool sp_capsule_cast_exact(T r, T h, const Iso<T>& iso2, V3<T> d, T max_distance, uint32_t shape1, V3<T> he1, V3<T> pos1, Q4<T> rot1,
+                                                      T& toi, V3<T>& p1, V3<T>& p2, V3<T>& n1) {
+    const Iso<T> q = iso_inv_mul(Iso<T>{rot1, pos1}, iso2);
+    const V3<T> dl = na_qrot(qinverse(rot1), d);
+    T t = T(0);
+    bool pen = false;
+    V3<T> w1 = vzero<T>(), w2 = vzero<T>(), wn = vzero<T>();
+    if (shape1 == AVN_SHAPE_BALL) {
+        const V3<T> o = iso_inv_point(q, vzero<T>());
+        const V3<T> dd = -iso_inv_vec(q, dl);
+        V3<T> n;
+        if (!sp_capsule_ray<T>(o, dd, h, r + he1.x, t, n, pen)) return false;
+        if (!(t <= max_distance) || !finite_t(t)) return false;
+        if (!pen) {
+            const V3<T> c2 = iso2.t + d * t;
+            const V3<T> pc = o + dd * t;   // the ball's centre at the impact, in the capsule's frame
+            const T ys = pc.y < -h ? -h : (pc.y > h ? h : pc.y);
+            const V3<T> pk = V3<T>{T(0), ys, T(0)} + n * r;
+            wn = -na_qrot(iso2.r, n);
+            w2 = na_qrot(iso2.r, pk) + c2;
+            w1 = pos1 + wn * he1.x;
+        }
+    } else {
+        V3<T> A, u;
+        sp_capsule_core<T>(q, h, A, u);
+        V3<T> n = vzero<T>(), ps = vzero<T>(), pb = vzero<T>();
+        bool hit = false;
+        for (int k = 0; k < SP_CAPSULE_ROUNDS; ++k) {
+            const SegBox<T> sb = sp_seg_box<T>(A + dl * t, u, he1);
+            const T dist = sqrt_t(sb.f);
+            if (dist > T(0)) n = (sb.ps - sb.pb) / dist;   // (dist == 0, a segment query r = 0 arriving: the round before's direction stands)
+            ps = sb.ps; pb = sb.pb;
+            if (dist <= r) { pen = k == 0; hit = true; break; }
+            const T v = -na_dot(n, dl);
+            if (!(v > T(0))) return false;
+            const T tn = t + (dist - r) / v;
+            if (tn > max_distance) return false;
+            if (!(tn > t) || k == SP_CAPSULE_ROUNDS - 1) { hit = true; break; }
+            t = tn;
+        }
+        if (!hit || !(t <= max_distance) || !finite_t(t)) return false;
+        if (!pen) {
+            wn = na_qrot(rot1, n);
+            w1 = na_qrot(rot1, pb) + pos1;
+            w2 = na_qrot(rot1, ps - n * r) + pos1;
+        }
+    }
+    toi = t; p1 = w1; p2 = w2; n1 = wn;
+    return true;
+}
+
+// The contact of the capsule (r, h) at pose iso2 with one collider within `prediction`: gap = dist - r - r_c between the cores.  Cores
+// apart: the normal from the collider's core point to the segment's; a segment crossing a cuboid: the smallest overlap over the six axes of
+// their Minkowski difference (e_0..e_2, then normalize(u x e_i)), first smallest wins; a ball's centre on the segment: no contact.
+// normal: from the collider towards the capsule (world); anchor1 / anchor2: offsets from the capsule's / the collider's position (world orientation).
+template <class T>
+__device__ __forceinline__ bool sp_capsule_contact(T r, T h, const Iso<T>& iso2, uint32_t shape1, V3<T> he1, V3<T> pos1, Q4<T> rot1, T prediction,
+                                                   T& penetration, V3<T>& normal, V3<T>& anchor1, V3<T>& anchor2) {
+    const Iso<T> q = iso_inv_mul(Iso<T>{rot1, pos1}, iso2);
+    V3<T> A, u;
+    sp_capsule_core<T>(q, h, A, u);
+    const bool ball1 = shape1 == AVN_SHAPE_BALL;
+    const T rc = ball1 ? he1.x : T(0);
+    V3<T> ps, pc;
+    T d2;
+    if (ball1) {
+        T s;
+        d2 = sp_seg_point<T>(A, u, vzero<T>(), s);
+        ps = A + u * s; pc = vzero<T>();
+    } else {
+        const SegBox<T> sb = sp_seg_box<T>(A, u, he1);
+        d2 = sb.f; ps = sb.ps; pc = sb.pb;
+    }
+    const T dist = sqrt_t(d2);
+    V3<T> n, l1, l2;
+    T pen;
+    if (dist > T(0)) {
+        const T gap = (dist - r) - rc;
+        if (gap > prediction) return false;
+        n = (ps - pc) / dist;
+        pen = -gap;
+        l1 = ps - n * r;
+        l2 = pc + n * rc;
+    } else {
+        if (ball1) return false;
+        const V3<T> hv = u * T(0.5), m = A + hv;
+        const T eps2 = Limits<T>::eps * Limits<T>::eps * na_dot(u, u);
+        T best = sp_inf<T>(), brb = T(0);
+        n = vzero<T>();
+#pragma unroll
+        for (int k = 0; k < 6; ++k) {
+            V3<T> ax;
+            if (k < 3) ax = sp_unit<T>(k, T(1));
+            else {
+                const V3<T> cx = k == 3 ? V3<T>{T(0), u.z, -u.y} : (k == 4 ? V3<T>{-u.z, T(0), u.x} : V3<T>{u.y, -u.x, T(0)});
+                const T l2c = na_dot(cx, cx);
+                if (!(l2c > eps2)) continue;
+                ax = cx / sqrt_t(l2c);
+            }
+            const T rb = fabs_t(ax.x) * he1.x + fabs_t(ax.y) * he1.y + fabs_t(ax.z) * he1.z;
+            const T rs = fabs_t(na_dot(ax, hv));
+            const T c = na_dot(ax, m);
+            const T ov = (rb + rs) - fabs_t(c);
+            if (ov < best) { best = ov; brb = rb; n = c < T(0) ? -ax : ax; }
+        }
+        pen = best + r;
+        const V3<T> pd = na_dot(n, u) < T(0) ? A + u : A;   // the segment's deepest point along -n, the lower s on a tie
+        l1 = pd - n * r;
+        l2 = pd + n * (brb - na_dot(n, pd));
+    }
+    penetration = pen;
+    normal = na_qrot(rot1, n);
+    anchor1 = na_qrot(rot1, l1 - q.t);
+    anchor2 = na_qrot(rot1, l2);
     return true;
 }
 

@@ -2,7 +2,8 @@
 // traversals for ray casts, ray hits, point and AABB intersections (k_sp_query), point projection (k_sp_project), shape intersections
 // (k_sp_shapes), shape casts (k_sp_cast), shape contacts (k_sp_contacts), the depenetration over them (k_sp_depenetrate), velocity
 // projection (k_sp_project_velocity), cast_move (k_sp_cast_move), the phases of the move-and-slide loop (k_sp_slide), and the casters: their
-// re-aiming (k_sp_reaim) and the per-caster filter of k_sp_query / k_sp_cast (PQ).
+// re-aiming (k_sp_reaim) and the per-caster filter of k_sp_query / k_sp_cast (PQ).  The kernels that take a query shape have a second,
+// CAPSULE instantiation for AVN_SHAPE_CAPSULE queries, launched behind the first (sp_lane_kind, sp_next_chunk).
 //
 // avn_spatial_update (launch_spatial_build), all on the world's stream:
 //   1. k_sp_snapshot   one thread per collider: its pose (collider_pose), the exact shape AABB (shape_aabb), padded, as the leaf box;
@@ -323,22 +324,41 @@ template <class T> __device__ __forceinline__ RayCtx<T> sp_ray_ctx(V3<T> o, V3<T
 // The query shape of lane i.  valid: a Ball or a Cuboid with a finite pose, finite half extents that are not negative and a finite AABB
 // [a, b] at its pose (shape_aabb: exact).  Every caller answers an invalid shape a miss / count 0 without traversing.
 template <class T> struct QShape { uint32_t shape; V3<T> he, pos; Q4<T> rot; V3<T> a, b; bool valid; };
-template <class T> __device__ __forceinline__ QShape<T> sp_load_shape(const uint8_t* shape, const T* pos, const T* he, const T* rot, uint32_t i) {
+// CAPSULE (the second instantiation of a query kernel, launched behind the first): valid = an AVN_SHAPE_CAPSULE with finite r (x) and h (y) that are
+// not negative; he = (r, h, 0), z is not read; [a, b] = pos +- (|qrot(rot, (0, h, 0))| + (r, r, r)).  Without it a capsule is an invalid kind.
+template <class T, bool CAPSULE = false> __device__ __forceinline__ QShape<T> sp_load_shape(const uint8_t* shape, const T* pos, const T* he, const T* rot, uint32_t i) {
     QShape<T> s;
     s.shape = shape[i];
     s.pos = sp_load3(pos, i);
     s.he = sp_load3(he, i);
     s.rot = Q4<T>{rot[4 * (size_t)i], rot[4 * (size_t)i + 1], rot[4 * (size_t)i + 2], rot[4 * (size_t)i + 3]};
     if (s.shape == AVN_SHAPE_BALL) s.he = V3<T>{s.he.x, s.he.x, s.he.x};   // (a ball has its radius in x: y and z are not read)
+    if (CAPSULE) s.he.z = T(0);
     s.a = s.b = vzero<T>();
-    s.valid = s.shape <= AVN_SHAPE_BALL && is_finite(s.pos) && is_finite(V3<T>{s.rot.x, s.rot.y, s.rot.z}) && finite_t(s.rot.w) && is_finite(s.he) &&
+    s.valid = (CAPSULE ? s.shape == AVN_SHAPE_CAPSULE : s.shape <= AVN_SHAPE_BALL) && is_finite(s.pos) && is_finite(V3<T>{s.rot.x, s.rot.y, s.rot.z}) && finite_t(s.rot.w) && is_finite(s.he) &&
               s.he.x >= T(0) && s.he.y >= T(0) && s.he.z >= T(0);
     if (s.valid) {
-        shape_aabb<T>(s.shape, s.he, s.pos, s.rot, s.a, s.b);
+        if (CAPSULE) {
+            const V3<T> hv = qrot(s.rot, V3<T>{T(0), s.he.y, T(0)});
+            const V3<T> ext = V3<T>{fabs_t(hv.x), fabs_t(hv.y), fabs_t(hv.z)} + V3<T>{s.he.x, s.he.x, s.he.x};
+            s.a = s.pos - ext; s.b = s.pos + ext;
+        } else shape_aabb<T>(s.shape, s.he, s.pos, s.rot, s.a, s.b);
         s.valid = is_finite(s.a) && is_finite(s.b);
     }
     return s;
 }
+// a lane of a CAPSULE instantiation whose query is no capsule is passed over: the first launch has answered it
+template <bool CAPSULE> __device__ __forceinline__ bool sp_lane_kind(const uint8_t* shape, uint32_t i) { return !CAPSULE || shape[i] == AVN_SHAPE_CAPSULE; }
+// The chunks of SP_WAVE queries a block answers.  The first launch has one block per chunk.  A CAPSULE launch has at most SP_CAPSULE_GRID blocks
+// that stride over the chunks: with no capsule in the call (device arrays are not read back, so the launch still goes) it costs a few
+// thousand one-wave blocks that read one byte per query, not a block -- with its 16 KB of LDS and ~200 VGPRs -- per 64 queries.
+#define SP_CAPSULE_GRID 2048u
+template <bool CAPSULE> __device__ __forceinline__ uint32_t sp_next_chunk(uint32_t base, uint32_t n) {
+    if (!CAPSULE) return n;
+    const uint32_t next = base + gridDim.x * SP_WAVE;
+    return next < base ? n : next;
+}
+static inline dim3 sp_capsule_grid(uint32_t n) { const uint32_t g = (n + SP_WAVE - 1) / SP_WAVE; return dim3(g < SP_CAPSULE_GRID ? g : SP_CAPSULE_GRID); }
 // the ray of a shape cast: from the centre of the query shape's padded AABB along d, against the node boxes grown by that AABB's half widths hw
 template <class T> __device__ __forceinline__ RayCtx<T> sp_cast_ray(const QShape<T>& s, V3<T> d, V3<T>& hw) {
     V3<T> qmin, qmax;
@@ -670,13 +690,15 @@ __device__ __forceinline__ bool sp_shape_exact(uint32_t shape1, V3<T> he1, const
     return true;
 }
 
-template <class T>
+template <class T, bool CAPSULE = false>
 __global__ __launch_bounds__(SP_WAVE) void k_sp_shapes(SP<T> sp, SQ<T> q) {
-    const uint32_t qi = blockIdx.x * SP_WAVE + threadIdx.x;
     uint32_t nodes_tested = 0, leaves_tested = 0, overflow = 0;
-    if (qi < q.n) {
+    uint32_t base = blockIdx.x * SP_WAVE;
+    do {   // (once; a CAPSULE launch: every chunk of this block's stride)
+    const uint32_t qi = base + threadIdx.x;
+    if (qi < q.n && sp_lane_kind<CAPSULE>(q.shape, qi)) {
         const uint32_t mask = q.mask ? q.mask[qi] : 0xFFFFFFFFu;
-        const QShape<T> s = sp_load_shape<T>(q.shape, q.a, q.he, q.rot, qi);
+        const QShape<T> s = sp_load_shape<T, CAPSULE>(q.shape, q.a, q.he, q.rot, qi);
         // the query shape's exact AABB at its pose, grown as the leaf boxes are
         V3<T> qmin, qmax;
         sp_pad_box(s.a, s.b, qmin, qmax);
@@ -691,7 +713,9 @@ __global__ __launch_bounds__(SP_WAVE) void k_sp_shapes(SP<T> sp, SQ<T> q) {
             const uint4 info = sp.info[c];
             if (!sp_leaf_ok(info, mask, AVN_SPATIAL_MISS, q.excluded, q.n_excluded)) return;
             ++leaves_tested;
-            if (!sp_shape_exact<T>(s.shape, s.he, iso1, info.z, xyz<T>(sp.he[c]), xyz<T>(sp.pos[c]), quat<T>(sp.rot[c]))) return;
+            if (CAPSULE) {
+                if (!sp_capsule_intersects<T>(s.he.x, s.he.y, iso_inv_mul(Iso<T>{quat<T>(sp.rot[c]), xyz<T>(sp.pos[c])}, iso1), info.z, xyz<T>(sp.he[c]))) return;
+            } else if (!sp_shape_exact<T>(s.shape, s.he, iso1, info.z, xyz<T>(sp.he[c]), xyz<T>(sp.pos[c]), quat<T>(sp.rot[c]))) return;
             const uint32_t m = sp_slot_by_collider(il, q.cap, found, c);
             if (m != AVN_SPATIAL_MISS) il[m] = c;
         };
@@ -699,6 +723,7 @@ __global__ __launch_bounds__(SP_WAVE) void k_sp_shapes(SP<T> sp, SQ<T> q) {
         sp_fill_miss(il, found, q.cap);
         q.count[qi] = found;
     }
+    } while (CAPSULE && (base = sp_next_chunk<CAPSULE>(base, q.n)) < q.n);
     sp_add_stats(q.stats, nodes_tested, leaves_tested, overflow);
 }
 
@@ -707,17 +732,19 @@ __global__ __launch_bounds__(SP_WAVE) void k_sp_shapes(SP<T> sp, SQ<T> q) {
 // order.  DESIGN.md 4.4.6 has the padding argument.
 
 // one lane per cast; MANY: the nearest-k list (shape_hits), else the closest hit (cast_shapes).  PQ: a caster run, as in k_sp_query
-template <class T, bool MANY, bool PQ = false>
+template <class T, bool MANY, bool PQ = false, bool CAPSULE = false>
 __global__ __launch_bounds__(SP_WAVE) void k_sp_cast(SP<T> sp, SQ<T> q) {
-    const uint32_t li = blockIdx.x * SP_WAVE + threadIdx.x;
     uint32_t nodes_tested = 0, leaves_tested = 0, overflow = 0;
-    if (li < q.n) {
+    uint32_t base = blockIdx.x * SP_WAVE;
+    do {   // (once; a CAPSULE launch: every chunk of this block's stride)
+    const uint32_t li = base + threadIdx.x;
+    if (li < q.n && sp_lane_kind<CAPSULE>(q.shape, PQ ? q.index[li] : li)) {
         const uint32_t qi = PQ ? q.index[li] : li;
         const uint32_t mask = q.mask ? q.mask[qi] : 0xFFFFFFFFu;
         const uint32_t self = PQ ? q.self_entity[qi] : AVN_SPATIAL_MISS;
         const uint32_t ex0 = PQ ? q.ex_offset[qi] : 0u, ex_n = PQ ? q.ex_offset[qi + 1] - ex0 : q.n_excluded;
         const uint32_t kq = PQ ? q.kq[qi] : q.cap;   // the list length of MANY
-        const QShape<T> s = sp_load_shape<T>(q.shape, q.a, q.he, q.rot, qi);
+        const QShape<T> s = sp_load_shape<T, CAPSULE>(q.shape, q.a, q.he, q.rot, qi);
         const V3<T> d = sp_load3(q.b, qi);
         const T max_distance = q.max_distance[qi];
         // a valid shape, a finite direction and a max_distance that is not NaN: otherwise a miss / count 0
@@ -741,7 +768,9 @@ __global__ __launch_bounds__(SP_WAVE) void k_sp_cast(SP<T> sp, SQ<T> q) {
             if (!sp_leaf_ok(info, mask, self, q.excluded + ex0, ex_n)) return;
             ++leaves_tested;
             T toi; V3<T> p1, p2, n1;
-            if (!sp_cast_exact<T>(s.shape, s.he, iso2, d, max_distance, info.z, xyz<T>(sp.he[c]), xyz<T>(sp.pos[c]), quat<T>(sp.rot[c]), toi, p1, p2, n1)) return;
+            if (CAPSULE) {
+                if (!sp_capsule_cast_exact<T>(s.he.x, s.he.y, iso2, d, max_distance, info.z, xyz<T>(sp.he[c]), xyz<T>(sp.pos[c]), quat<T>(sp.rot[c]), toi, p1, p2, n1)) return;
+            } else if (!sp_cast_exact<T>(s.shape, s.he, iso2, d, max_distance, info.z, xyz<T>(sp.he[c]), xyz<T>(sp.pos[c]), quat<T>(sp.rot[c]), toi, p1, p2, n1)) return;
             if (!MANY) {
                 if (toi < best || (toi == best && c < best_c)) { best = toi; best_c = c; best_p1 = p1; best_p2 = p2; best_n1 = n1; }
             } else {
@@ -768,6 +797,7 @@ __global__ __launch_bounds__(SP_WAVE) void k_sp_cast(SP<T> sp, SQ<T> q) {
             q.count[qi] = found;
         }
     }
+    } while (CAPSULE && (base = sp_next_chunk<CAPSULE>(base, q.n)) < q.n);
     sp_add_stats(q.stats, nodes_tested, leaves_tested, overflow);
 }
 
@@ -776,14 +806,17 @@ __global__ __launch_bounds__(SP_WAVE) void k_sp_cast(SP<T> sp, SQ<T> q) {
 // untouched.  DESIGN.md 4.4.7.
 
 // one lane per query shape; records inserted in ascending collider index as k_sp_shapes inserts ids
-template <class T>
+template <class T, bool CAPSULE = false>
 __global__ __launch_bounds__(SP_WAVE) void k_sp_contacts(SP<T> sp, SC<T> sc) {
     const SQ<T>& q = sc.q;
-    const uint32_t qi = blockIdx.x * SP_WAVE + threadIdx.x;
     uint32_t nodes_tested = 0, leaves_tested = 0, overflow = 0;
-    if (qi < q.n) {
+    uint32_t base = blockIdx.x * SP_WAVE;
+    do {   // (once; a CAPSULE launch: every chunk of this block's stride)
+    const uint32_t qi = base + threadIdx.x;
+    if (qi < q.n && sp_lane_kind<CAPSULE>(q.shape, qi)) {
         const uint32_t mask = q.mask ? q.mask[qi] : 0xFFFFFFFFu;
-        const QShape<T> s = sp_load_shape<T>(q.shape, q.a, q.he, q.rot, qi);
+        const QShape<T> s = sp_load_shape<T, CAPSULE>(q.shape, q.a, q.he, q.rot, qi);
+        const Iso<T> iso2 = make_isometry(s.pos, s.rot);   // (the capsule's pair test; unused otherwise)
         const T pred = sc.prediction ? sc.prediction[qi] : sc.prediction_all;
         const uint32_t self = sc.self_entity ? sc.self_entity[qi] : AVN_SPATIAL_MISS;
         // a valid shape and a prediction distance that is finite and not negative: otherwise count 0
@@ -811,11 +844,19 @@ __global__ __launch_bounds__(SP_WAVE) void k_sp_contacts(SP<T> sp, SC<T> sc) {
             if (!sp_box_box(gmin, gmax, make4<T>(mn, T(0)), make4<T>(mx, T(0)))) return;
             // (c), (d)
             SpDeepestSink<T> sink{vzero<T>(), T(0), 0};
-            V3<T> nrm;
-            if (!contact_manifolds_pair_sink<T, SpDeepestSink<T>>(s.shape, s.he, s.pos, s.rot, info.z, he2, pos2, rot2, pred, sink, nrm)) return;
+            V3<T> nrm, a1, a2;
+            if (CAPSULE) {
+                // (the capsule's own contact: the normal already points from the collider towards the query)
+                V3<T> cn;
+                if (!sp_capsule_contact<T>(s.he.x, s.he.y, iso2, info.z, he2, pos2, rot2, pred, sink.penetration, cn, a1, a2)) return;
+                nrm = -cn;
+            } else {
+                if (!contact_manifolds_pair_sink<T, SpDeepestSink<T>>(s.shape, s.he, s.pos, s.rot, info.z, he2, pos2, rot2, pred, sink, nrm)) return;
+                a1 = sink.anchor1; a2 = a1 + (s.pos - pos2);
+            }
             const uint32_t m = sp_slot_by_collider(rl, q.cap, found, c);
             if (m == AVN_SPATIAL_MISS) return;
-            const V3<T> a1 = sink.anchor1, a2 = a1 + (s.pos - pos2), pt = s.pos + a1;
+            const V3<T> pt = s.pos + a1;
             SpatialShapeContact<T> r;
             r.collider = c; r.entity = info.x; r.penetration = sink.penetration;
             r.normal[0] = -nrm.x; r.normal[1] = -nrm.y; r.normal[2] = -nrm.z;
@@ -829,6 +870,7 @@ __global__ __launch_bounds__(SP_WAVE) void k_sp_contacts(SP<T> sp, SC<T> sc) {
         if (sc.pad_unused) sp_fill_miss(rl, found, q.cap);
         q.count[qi] = found;
     }
+    } while (CAPSULE && (base = sp_next_chunk<CAPSULE>(base, q.n)) < q.n);
     sp_add_stats(q.stats, nodes_tested, leaves_tested, overflow);
 }
 
@@ -867,10 +909,11 @@ __global__ __launch_bounds__(SP_WAVE) void k_sp_depenetrate(SD<T> d) {
     d.out[qi] = r;
 }
 
-template <class T> void launch_spatial_contacts(const SP<T>& sp, const SC<T>& sc, hipStream_t s, bool zero_stats) {
+template <class T> void launch_spatial_contacts(const SP<T>& sp, const SC<T>& sc, hipStream_t s, bool zero_stats, bool capsule) {
     if (zero_stats) (void)hipMemsetAsync(sc.q.stats, 0, 4 * sizeof(unsigned long long), s);
     if (sc.q.n == 0) return;
     hipLaunchKernelGGL((k_sp_contacts<T>), dim3((sc.q.n + SP_WAVE - 1) / SP_WAVE), dim3(SP_WAVE), 0, s, sp, sc);
+    if (capsule) hipLaunchKernelGGL((k_sp_contacts<T, true>), sp_capsule_grid(sc.q.n), dim3(SP_WAVE), 0, s, sp, sc);
 }
 template <class T> void launch_spatial_depenetrate(const SD<T>& d, hipStream_t s) {
     if (d.n == 0) return;
@@ -964,15 +1007,17 @@ template <class T> __device__ __forceinline__ void sp_put_move(SpatialMoveHit<T>
 // applies the origin-penetration rule to the pending colliders with the narrow phase's contact_manifolds_pair_sink, merges them with the
 // traversal's hit by (distance, collider index) and pulls the distance back.  The contact manifold so stays out of the traversal's live
 // range (fused into the leaf the kernel needed 256 VGPRs + 13 / 72 AGPRs, one wave per SIMD: profiles/spatial_moves_resource_usage.txt).
-template <class T>
+template <class T, bool CAPSULE = false>
 __global__ __launch_bounds__(SP_WAVE) void k_sp_cast_move(SP<T> sp, SM<T> m) {
     const SQ<T>& q = m.q;
-    const uint32_t qi = blockIdx.x * SP_WAVE + threadIdx.x;
     uint32_t nodes_tested = 0, leaves_tested = 0, overflow = 0;
-    if (qi < q.n) {
+    uint32_t base = blockIdx.x * SP_WAVE;
+    do {   // (once; a CAPSULE launch: every chunk of this block's stride)
+    const uint32_t qi = base + threadIdx.x;
+    if (qi < q.n && sp_lane_kind<CAPSULE>(q.shape, qi)) {
         const uint32_t mask = q.mask ? q.mask[qi] : 0xFFFFFFFFu;
         const uint32_t self = m.self_entity ? m.self_entity[qi] : AVN_SPATIAL_MISS;
-        const QShape<T> s = sp_load_shape<T>(q.shape, q.a, q.he, q.rot, qi);
+        const QShape<T> s = sp_load_shape<T, CAPSULE>(q.shape, q.a, q.he, q.rot, qi);
         const V3<T> mv = sp_load3(m.movement, qi);
         const T skin = m.skin ? m.skin[qi] : m.skin_all;
         // a valid shape, a finite movement and a skin width that is finite and not negative; a slide's finished character: a miss
@@ -999,7 +1044,9 @@ __global__ __launch_bounds__(SP_WAVE) void k_sp_cast_move(SP<T> sp, SM<T> m) {
             const V3<T> pos1 = xyz<T>(sp.pos[c]), he1 = xyz<T>(sp.he[c]);
             const Q4<T> rot1 = quat<T>(sp.rot[c]);
             T toi; V3<T> p1, p2, n1;
-            if (!sp_cast_exact<T>(s.shape, s.he, iso2, d, dist, info.z, he1, pos1, rot1, toi, p1, p2, n1)) return;
+            if (CAPSULE) {
+                if (!sp_capsule_cast_exact<T>(s.he.x, s.he.y, iso2, d, dist, info.z, he1, pos1, rot1, toi, p1, p2, n1)) return;
+            } else if (!sp_cast_exact<T>(s.shape, s.he, iso2, d, dist, info.z, he1, pos1, rot1, toi, p1, p2, n1)) return;
             if (toi == T(0) && n1.x == T(0) && n1.y == T(0) && n1.z == T(0)) {
                 // overlapping at the start: the pair's contact decides, in k_sp_cast_move_resolve
                 if (n_pending < AVN_SPATIAL_MAX_HITS) pend[n_pending] = c;
@@ -1017,19 +1064,26 @@ __global__ __launch_bounds__(SP_WAVE) void k_sp_cast_move(SP<T> sp, SM<T> m) {
         m.out[qi] = h;
         m.pending_count[qi] = n_pending;
     }
+    } while (CAPSULE && (base = sp_next_chunk<CAPSULE>(base, q.n)) < q.n);
     sp_add_stats(q.stats, nodes_tested, leaves_tested, overflow);
 }
 
-template <class T>
+template <class T, bool CAPSULE> __device__ __forceinline__ void sp_cast_move_resolve_lane(const SP<T>& sp, const SM<T>& m, uint32_t qi);
+template <class T, bool CAPSULE = false>
 __global__ __launch_bounds__(SP_WAVE) void k_sp_cast_move_resolve(SP<T> sp, SM<T> m) {
+    uint32_t base = blockIdx.x * SP_WAVE;
+    do sp_cast_move_resolve_lane<T, CAPSULE>(sp, m, base + threadIdx.x);
+    while (CAPSULE && (base = sp_next_chunk<CAPSULE>(base, m.q.n)) < m.q.n);
+}
+template <class T, bool CAPSULE> __device__ __forceinline__ void sp_cast_move_resolve_lane(const SP<T>& sp, const SM<T>& m, uint32_t qi) {
     const SQ<T>& q = m.q;
-    const uint32_t qi = blockIdx.x * SP_WAVE + threadIdx.x;
-    if (qi >= q.n) return;
+    if (qi >= q.n || !sp_lane_kind<CAPSULE>(q.shape, qi)) return;
     SpatialMoveHit<T> h = m.out[qi];
     const uint32_t count = m.pending_count[qi];
     const uint32_t np = count < AVN_SPATIAL_MAX_HITS ? count : AVN_SPATIAL_MAX_HITS;
     if (h.collider == AVN_SPATIAL_MISS && np == 0) return;   // a miss, an invalid query, a slide's finished character: the record stands
-    const QShape<T> s = sp_load_shape<T>(q.shape, q.a, q.he, q.rot, qi);   // (valid: k_sp_cast_move hit or noted something)
+    const QShape<T> s = sp_load_shape<T, CAPSULE>(q.shape, q.a, q.he, q.rot, qi);   // (valid: k_sp_cast_move hit or noted something)
+    const Iso<T> iso2 = make_isometry(s.pos, s.rot);   // (the capsule's pair test; unused otherwise)
     const V3<T> mv = sp_load3(m.movement, qi);
     const T skin = m.skin ? m.skin[qi] : m.skin_all;
     V3<T> d{T(1), T(0), T(0)};
@@ -1049,11 +1103,19 @@ __global__ __launch_bounds__(SP_WAVE) void k_sp_cast_move_resolve(SP<T> sp, SM<T
         // the pair's contact at prediction 0, the query as shape 1
         V3<T> p1 = vzero<T>(), p2 = vzero<T>(), n1 = vzero<T>();
         SpDeepestSink<T> sink{vzero<T>(), T(0), 0};
-        V3<T> nrm;
-        if (contact_manifolds_pair_sink<T, SpDeepestSink<T>>(s.shape, s.he, s.pos, s.rot, info.z, he1, pos1, rot1, T(0), sink, nrm)) {
+        V3<T> nrm, a1, a2;
+        bool contact;
+        if (CAPSULE) {
+            V3<T> cn;
+            contact = sp_capsule_contact<T>(s.he.x, s.he.y, iso2, info.z, he1, pos1, rot1, T(0), sink.penetration, cn, a1, a2);
+            nrm = -cn;
+        } else {
+            contact = contact_manifolds_pair_sink<T, SpDeepestSink<T>>(s.shape, s.he, s.pos, s.rot, info.z, he1, pos1, rot1, T(0), sink, nrm);
+            a1 = sink.anchor1; a2 = a1 + (s.pos - pos1);
+        }
+        if (contact) {
             const V3<T> cn{-nrm.x, -nrm.y, -nrm.z};
             if (d.x * cn.x + d.y * cn.y + d.z * cn.z >= T(0)) continue;   // on its way out: ignored by this cast
-            const V3<T> a1 = sink.anchor1, a2 = a1 + (s.pos - pos1);
             n1 = cn; p1 = pos1 + a2; p2 = s.pos + a1;
         }
         best = T(0); best_c = c; best_e = info.x; best_p1 = p1; best_p2 = p2; best_n1 = n1;
@@ -1092,7 +1154,7 @@ __global__ __launch_bounds__(SP_WAVE) void k_sp_slide(SL<T> l) {
     if (qi >= l.n) return;
     const size_t q3 = 3 * (size_t)qi;
     if (PHASE == SPL_BEGIN) {
-        const bool valid = sp_load_shape<T>(l.shape, l.pos_in, l.he, l.rot, qi).valid;
+        const bool valid = sp_load_shape<T>(l.shape, l.pos_in, l.he, l.rot, qi).valid || sp_load_shape<T, true>(l.shape, l.pos_in, l.he, l.rot, qi).valid;
         for (int i = 0; i < 3; ++i) { l.pos[q3 + i] = l.pos_in[q3 + i]; l.vel[q3 + i] = l.vel_in[q3 + i]; l.movement[q3 + i] = T(0); }
         l.time_left[qi] = l.delta_time;
         l.flags[qi] = valid ? (SP_SLIDE_VALID | SP_SLIDE_LIVE) : 0u;
@@ -1217,11 +1279,14 @@ template <class T> void launch_spatial_project_velocity(const SV<T>& p, hipStrea
     if (p.n == 0) return;
     hipLaunchKernelGGL((k_sp_project_velocity<T>), dim3((p.n + SP_WAVE - 1) / SP_WAVE), dim3(SP_WAVE), 0, s, p);
 }
-template <class T> void launch_spatial_cast_move(const SP<T>& sp, const SM<T>& m, bool zero_stats, hipStream_t s) {
+template <class T> void launch_spatial_cast_move(const SP<T>& sp, const SM<T>& m, bool zero_stats, hipStream_t s, bool capsule) {
     if (zero_stats) (void)hipMemsetAsync(m.q.stats, 0, 4 * sizeof(unsigned long long), s);
     if (m.q.n == 0) return;
     hipLaunchKernelGGL((k_sp_cast_move<T>), dim3((m.q.n + SP_WAVE - 1) / SP_WAVE), dim3(SP_WAVE), 0, s, sp, m);
     hipLaunchKernelGGL((k_sp_cast_move_resolve<T>), dim3((m.q.n + SP_WAVE - 1) / SP_WAVE), dim3(SP_WAVE), 0, s, sp, m);
+    if (!capsule) return;
+    hipLaunchKernelGGL((k_sp_cast_move<T, true>), sp_capsule_grid(m.q.n), dim3(SP_WAVE), 0, s, sp, m);
+    hipLaunchKernelGGL((k_sp_cast_move_resolve<T, true>), sp_capsule_grid(m.q.n), dim3(SP_WAVE), 0, s, sp, m);
 }
 template <class T> void launch_spatial_slide_phase(const SL<T>& l, int phase, hipStream_t s) {
     if (l.n == 0) return;
@@ -1267,18 +1332,26 @@ template <class T> void launch_spatial_reaim(const DW<T>& w, const SP<T>& sp, co
     if (c.n == 0) return;
     hipLaunchKernelGGL((k_sp_reaim<T>), dim3((c.n + 255) / 256), dim3(256), 0, s, w, sp, c);
 }
-template <class T> void launch_spatial_casters(const SP<T>& sp, const SQ<T>& q, int kind, hipStream_t s) {
+template <class T> void launch_spatial_casters(const SP<T>& sp, const SQ<T>& q, int kind, hipStream_t s, bool capsule) {
     if (q.n == 0) return;
     const dim3 g((q.n + SP_WAVE - 1) / SP_WAVE), b(SP_WAVE);
     switch (kind) {
         case SPQ_CLOSEST: hipLaunchKernelGGL((k_sp_query<T, SPQ_CLOSEST, true>), g, b, 0, s, sp, q); break;
         case SPQ_HITS: hipLaunchKernelGGL((k_sp_query<T, SPQ_HITS, true>), g, b, 0, s, sp, q); break;
-        case SPQ_CAST: hipLaunchKernelGGL((k_sp_cast<T, false, true>), g, b, 0, s, sp, q); break;
-        default: hipLaunchKernelGGL((k_sp_cast<T, true, true>), g, b, 0, s, sp, q); break;
+        case SPQ_CAST:
+            hipLaunchKernelGGL((k_sp_cast<T, false, true>), g, b, 0, s, sp, q);
+            if (capsule) hipLaunchKernelGGL((k_sp_cast<T, false, true, true>), sp_capsule_grid(q.n), b, 0, s, sp, q);
+            break;
+        default:
+            hipLaunchKernelGGL((k_sp_cast<T, true, true>), g, b, 0, s, sp, q);
+            if (capsule) hipLaunchKernelGGL((k_sp_cast<T, true, true, true>), sp_capsule_grid(q.n), b, 0, s, sp, q);
+            break;
     }
 }
 
-template <class T> void launch_spatial_query(const SP<T>& sp, const SQ<T>& q, int kind, hipStream_t s) {
+// capsule (SPQ_SHAPES / SPQ_CAST / SPQ_CAST_HITS): the call may hold AVN_SHAPE_CAPSULE query shapes -- the CAPSULE instantiation runs behind the
+// first launch on the same stream and answers exactly those lanes
+template <class T> void launch_spatial_query(const SP<T>& sp, const SQ<T>& q, int kind, hipStream_t s, bool capsule) {
     (void)hipMemsetAsync(q.stats, 0, 4 * sizeof(unsigned long long), s);
     if (q.n == 0) return;
     const dim3 g((q.n + SP_WAVE - 1) / SP_WAVE), b(SP_WAVE);
@@ -1287,9 +1360,18 @@ template <class T> void launch_spatial_query(const SP<T>& sp, const SQ<T>& q, in
         case SPQ_HITS: hipLaunchKernelGGL((k_sp_query<T, SPQ_HITS>), g, b, 0, s, sp, q); break;
         case SPQ_POINTS: hipLaunchKernelGGL((k_sp_query<T, SPQ_POINTS>), g, b, 0, s, sp, q); break;
         case SPQ_PROJECT: hipLaunchKernelGGL((k_sp_project<T>), g, b, 0, s, sp, q); break;
-        case SPQ_SHAPES: hipLaunchKernelGGL((k_sp_shapes<T>), g, b, 0, s, sp, q); break;
-        case SPQ_CAST: hipLaunchKernelGGL((k_sp_cast<T, false>), g, b, 0, s, sp, q); break;
-        case SPQ_CAST_HITS: hipLaunchKernelGGL((k_sp_cast<T, true>), g, b, 0, s, sp, q); break;
+        case SPQ_SHAPES:
+            hipLaunchKernelGGL((k_sp_shapes<T>), g, b, 0, s, sp, q);
+            if (capsule) hipLaunchKernelGGL((k_sp_shapes<T, true>), sp_capsule_grid(q.n), b, 0, s, sp, q);
+            break;
+        case SPQ_CAST:
+            hipLaunchKernelGGL((k_sp_cast<T, false>), g, b, 0, s, sp, q);
+            if (capsule) hipLaunchKernelGGL((k_sp_cast<T, false, false, true>), sp_capsule_grid(q.n), b, 0, s, sp, q);
+            break;
+        case SPQ_CAST_HITS:
+            hipLaunchKernelGGL((k_sp_cast<T, true>), g, b, 0, s, sp, q);
+            if (capsule) hipLaunchKernelGGL((k_sp_cast<T, true, false, true>), sp_capsule_grid(q.n), b, 0, s, sp, q);
+            break;
         default: hipLaunchKernelGGL((k_sp_query<T, SPQ_AABBS>), g, b, 0, s, sp, q); break;
     }
 }
@@ -1334,18 +1416,18 @@ static_assert(sizeof(SpatialSlide<float>) == sizeof(avn_spatial_slide_f32) && si
 static_assert(SP_SLIDE_PLANES >= AVN_SPATIAL_MAX_PLANES + 1, "plane slots");
 template void launch_spatial_build<float>(const DW<float>&, const BP<float>&, const SP<float>&, hipStream_t);
 template void launch_spatial_build<double>(const DW<double>&, const BP<double>&, const SP<double>&, hipStream_t);
-template void launch_spatial_query<float>(const SP<float>&, const SQ<float>&, int, hipStream_t);
-template void launch_spatial_query<double>(const SP<double>&, const SQ<double>&, int, hipStream_t);
+template void launch_spatial_query<float>(const SP<float>&, const SQ<float>&, int, hipStream_t, bool);
+template void launch_spatial_query<double>(const SP<double>&, const SQ<double>&, int, hipStream_t, bool);
 template void launch_spatial_reaim<float>(const DW<float>&, const SP<float>&, const SCA<float>&, hipStream_t);
 template void launch_spatial_reaim<double>(const DW<double>&, const SP<double>&, const SCA<double>&, hipStream_t);
-template void launch_spatial_casters<float>(const SP<float>&, const SQ<float>&, int, hipStream_t);
-template void launch_spatial_casters<double>(const SP<double>&, const SQ<double>&, int, hipStream_t);
-template void launch_spatial_contacts<float>(const SP<float>&, const SC<float>&, hipStream_t, bool);
-template void launch_spatial_contacts<double>(const SP<double>&, const SC<double>&, hipStream_t, bool);
+template void launch_spatial_casters<float>(const SP<float>&, const SQ<float>&, int, hipStream_t, bool);
+template void launch_spatial_casters<double>(const SP<double>&, const SQ<double>&, int, hipStream_t, bool);
+template void launch_spatial_contacts<float>(const SP<float>&, const SC<float>&, hipStream_t, bool, bool);
+template void launch_spatial_contacts<double>(const SP<double>&, const SC<double>&, hipStream_t, bool, bool);
 template void launch_spatial_project_velocity<float>(const SV<float>&, hipStream_t);
 template void launch_spatial_project_velocity<double>(const SV<double>&, hipStream_t);
-template void launch_spatial_cast_move<float>(const SP<float>&, const SM<float>&, bool, hipStream_t);
-template void launch_spatial_cast_move<double>(const SP<double>&, const SM<double>&, bool, hipStream_t);
+template void launch_spatial_cast_move<float>(const SP<float>&, const SM<float>&, bool, hipStream_t, bool);
+template void launch_spatial_cast_move<double>(const SP<double>&, const SM<double>&, bool, hipStream_t, bool);
 template void launch_spatial_slide_phase<float>(const SL<float>&, int, hipStream_t);
 template void launch_spatial_slide_phase<double>(const SL<double>&, int, hipStream_t);
 template void launch_spatial_depenetrate<float>(const SD<float>&, hipStream_t);

@@ -77,9 +77,16 @@
     static size_t sp_stage_bytes(bool dev, size_t n, size_t in_bytes, size_t out_bytes, size_t n_excluded) {
         return al(n_excluded * 4) + (dev ? 0 : in_bytes + out_bytes + al(n * 4) * 2) + 4096;
     }
-    avn_status sp_run(SQ<T>& q, int kind) {
+    // Whether a call may hold AVN_SHAPE_CAPSULE query shapes, which the kernels' second (CAPSULE) instantiations answer: the host's kinds are
+    // scanned, a device array is not read back (the second launch always goes; its lanes leave at once unless their query is a capsule).
+    static bool sp_any_capsule(const uint8_t* shape, uint32_t n, bool dev) {
+        if (dev) return n != 0;
+        for (uint32_t i = 0; i < n; ++i) if (shape[i] == AVN_SHAPE_CAPSULE) return true;
+        return false;
+    }
+    avn_status sp_run(SQ<T>& q, int kind, bool capsule = false) {
         q.stats = b_sp_stats.as<unsigned long long>();
-        launch_spatial_query<T>(sp, q, kind, stream);
+        launch_spatial_query<T>(sp, q, kind, stream, capsule);
         HIPCHK(hipGetLastError());
         return AVN_OK;
     }
@@ -202,7 +209,7 @@
         q.n_excluded = (uint32_t)ex.size();
         q.ids = n_ids ? sp_out<uint32_t>(out->collider, n_ids, dev) : nullptr;
         q.count = sp_out<uint32_t>(out->count, n, dev);
-        if ((st = sp_run(q, SPQ_SHAPES)) != AVN_OK) return st;
+        if ((st = sp_run(q, SPQ_SHAPES, sp_any_capsule(s->shape, n, dev))) != AVN_OK) return st;
         if (!dev) {
             if ((st = stage_out<uint32_t>(out->collider, q.ids, n_ids)) != AVN_OK) return st;
             if ((st = stage_out<uint32_t>(out->count, q.count, n)) != AVN_OK) return st;
@@ -238,7 +245,7 @@
         q.n_excluded = (uint32_t)ex.size();
         q.cast = sp_out<SpatialShapeHit<T>>(out->hits, n_rec, dev);
         if (many) q.count = sp_out<uint32_t>(out->count, n, dev);
-        if ((st = sp_run(q, many ? SPQ_CAST_HITS : SPQ_CAST)) != AVN_OK) return st;
+        if ((st = sp_run(q, many ? SPQ_CAST_HITS : SPQ_CAST, sp_any_capsule(s->shape, n, dev))) != AVN_OK) return st;
         if (!dev) {
             if ((st = stage_out<SpatialShapeHit<T>>(out->hits, q.cast, n_rec)) != AVN_OK) return st;
             if (many && (st = stage_out<uint32_t>(out->count, q.count, n)) != AVN_OK) return st;
@@ -284,7 +291,7 @@
         sc.pad_unused = 1u;
         sc.rec = n_rec ? sp_out<SpatialShapeContact<T>>(out->contacts, n_rec, dev) : nullptr;
         sc.q.count = sp_out<uint32_t>(out->count, n, dev);
-        launch_spatial_contacts<T>(sp, sc, stream);
+        launch_spatial_contacts<T>(sp, sc, stream, true, sp_any_capsule(s->shape, n, dev));
         HIPCHK(hipGetLastError());
         if (!dev) {
             if ((st = stage_out<SpatialShapeContact<T>>(out->contacts, sc.rec, n_rec)) != AVN_OK) return st;
@@ -321,7 +328,7 @@
             sc.prediction_all = (T)cfg->skin_width;
             sc.pad_unused = 0u;   // (k_sp_depenetrate reads the first min(count, cap) records only)
             sc.skip_sensors = (s->flags & AVN_SPATIAL_SKIP_SENSORS) ? 1u : 0u;
-            launch_spatial_contacts<T>(sp, sc, stream);
+            launch_spatial_contacts<T>(sp, sc, stream, true, sp_any_capsule(s->shape, n, dev));
             HIPCHK(hipGetLastError());
             SD<T> d{};
             d.n = n; d.rec = sc.rec; d.count = d_count;
@@ -378,7 +385,7 @@
         bool moved = false;
         GROW(b_mv_pend, std::max<size_t>((size_t)n * AVN_SPATIAL_MAX_HITS, 1), m.pending);
         GROW(b_mv_pcount, std::max<size_t>(n, 1), m.pending_count);
-        launch_spatial_cast_move<T>(sp, m, true, stream);
+        launch_spatial_cast_move<T>(sp, m, true, stream, sp_any_capsule(s->shape, n, dev));
         HIPCHK(hipGetLastError());
         if (!dev && (st = stage_out<SpatialMoveHit<T>>(out->hits, m.out, n)) != AVN_OK) return st;
         return sp_finish();
@@ -434,8 +441,9 @@
         GROW(b_mv_pcount, nn, m.pending_count);
         m.q = sc.q; m.movement = l.movement; m.skin = nullptr; m.skin_all = l.skin; m.self_entity = self; m.state = l.flags; m.out = d_mh;
         HIPCHK(hipMemsetAsync(b_sp_stats.p, 0, 4 * sizeof(unsigned long long), stream));
+        const bool capsule = sp_any_capsule(s->shape, n, dev);   // (every traversal launch of the loop gets its CAPSULE instantiation behind it)
         auto depenetrate = [&]() {
-            if (cfg->depenetration_iterations) { sc.prediction = nullptr; sc.prediction_all = l.skin; launch_spatial_contacts<T>(sp, sc, stream, false); }
+            if (cfg->depenetration_iterations) { sc.prediction = nullptr; sc.prediction_all = l.skin; launch_spatial_contacts<T>(sp, sc, stream, false, capsule); }
             launch_spatial_slide_phase<T>(l, SPL_DEPENETRATE, stream);
         };
         launch_spatial_slide_phase<T>(l, SPL_BEGIN, stream);
@@ -443,10 +451,10 @@
         for (uint32_t it = 0; it < cfg->move_and_slide_iterations; ++it) {
             l.iteration = it;
             launch_spatial_slide_phase<T>(l, SPL_SWEEP, stream);
-            launch_spatial_cast_move<T>(sp, m, false, stream);
+            launch_spatial_cast_move<T>(sp, m, false, stream, capsule);
             launch_spatial_slide_phase<T>(l, SPL_ADVANCE, stream);
             sc.prediction = l.pred;
-            launch_spatial_contacts<T>(sp, sc, stream, false);
+            launch_spatial_contacts<T>(sp, sc, stream, false, capsule);
             launch_spatial_slide_phase<T>(l, SPL_PLANES, stream);
         }
         depenetrate();
@@ -469,7 +477,7 @@
     };
     struct CasterSet {
         uint32_t n = 0, hit_cap = 0, n_closest = 0, n_many = 0;
-        bool any_body = false, any_collider = false;
+        bool any_body = false, any_collider = false, any_capsule = false;   // any_capsule: a definition is an AVN_SHAPE_CAPSULE (the casts' second launch)
         uint32_t max_body = 0, max_collider = 0;   // the largest anchors, checked against the tables before every run
         DevBuf def, res;
         SCA<T> a{};
@@ -559,6 +567,7 @@
         cs.index_closest = (const uint32_t*)(D + o_closest); cs.index_many = (const uint32_t*)(D + o_many);
         cs.n_closest = (uint32_t)closest.size(); cs.n_many = (uint32_t)many.size();
         cs.any_body = any_body; cs.any_collider = any_collider; cs.max_body = max_body; cs.max_collider = max_collider;
+        cs.any_capsule = is_shape && sp_any_capsule(d.shape, n, false);
         cs.hit_cap = d.hit_cap;
         cs.n = n;
         return AVN_OK;
@@ -601,9 +610,9 @@
             SQ<T> q = cs->q;
             q.stats = stats;
             q.n = cs->n_closest; q.index = cs->index_closest;
-            launch_spatial_casters<T>(sp, q, is_shape ? SPQ_CAST : SPQ_CLOSEST, stream);
+            launch_spatial_casters<T>(sp, q, is_shape ? SPQ_CAST : SPQ_CLOSEST, stream, cs->any_capsule);
             q.n = cs->n_many; q.index = cs->index_many;
-            launch_spatial_casters<T>(sp, q, is_shape ? SPQ_CAST_HITS : SPQ_HITS, stream);
+            launch_spatial_casters<T>(sp, q, is_shape ? SPQ_CAST_HITS : SPQ_HITS, stream, cs->any_capsule);
         }
         HIPCHK(hipGetLastError());
         cs_ran = true;

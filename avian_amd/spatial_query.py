@@ -26,6 +26,8 @@ SLIDE_TRUNCATED = 1
 MISS = 0xFFFFFFFF
 ANCHOR_WORLD, ANCHOR_BODY, ANCHOR_COLLIDER = 0, 1, 2
 CASTER_RAY, CASTER_SHAPE = 0, 1
+# query-shape kinds: a capsule is a query shape only (half_extents = (r, h, .): the radius in x, the half length of its y segment in y)
+SHAPE_CUBOID, SHAPE_BALL, SHAPE_CAPSULE = 0, 1, 3
 
 
 class avn_spatial_filter(C.Structure):
@@ -492,7 +494,7 @@ class SpatialQuery:
 
     def shape_intersections(self, shape, half_extents, position, rotation, cap, mask=None, excluded=None, skip_host_shapes=False):
         """SpatialQueryPipeline::shape_intersections per query shape (AVN_SHAPE_CUBOID = 0 / AVN_SHAPE_BALL = 1, a ball's radius in
-        half_extents[:, 0]): (collider indices [n, cap] ascending, MISS-padded; true counts [n])."""
+        half_extents[:, 0] / SHAPE_CAPSULE = 3, ``half_extents`` = (r, h, .): the radius and the half length of the y segment): (collider indices [n, cap] ascending, MISS-padded; true counts [n])."""
         dev = self._is_tensor(position)
         n = int(position.shape[0])
         q = avn_spatial_shapes()
@@ -528,7 +530,8 @@ class SpatialQuery:
         return q, n, dev
 
     def cast_shapes(self, shape, half_extents, position, rotation, direction, max_distance=None, mask=None, excluded=None, skip_host_shapes=False):
-        """SpatialQueryPipeline::cast_shape per cast (AVN_SHAPE_CUBOID = 0 / AVN_SHAPE_BALL = 1, a ball's radius in half_extents[:, 0]): a
+        """SpatialQueryPipeline::cast_shape per cast (AVN_SHAPE_CUBOID = 0 / AVN_SHAPE_BALL = 1, a ball's radius in half_extents[:, 0] /
+        SHAPE_CAPSULE = 3, ``half_extents`` = (r, h, .)): a
         structured array of shape-hit records (``shape_hit_dtype``; collider == MISS: no hit).  Device tensors in: a uint8 tensor
         [n, itemsize] of the same records out."""
         q, n, dev = self._casts(shape, half_extents, position, rotation, direction, max_distance, mask, excluded, skip_host_shapes)
@@ -551,7 +554,8 @@ class SpatialQuery:
     def shape_contacts(self, shape, half_extents, position, rotation, prediction_distance, cap, mask=None, excluded=None, skip_host_shapes=False,
                        skip_sensors=False):
         """MoveAndSlide::intersections per query shape: (contact records [n, cap] in ascending collider index, ``shape_contact_dtype``, unused
-        slots MISS; true counts [n]).  ``prediction_distance`` is a scalar or [n].  Device tensors in: a uint8 tensor [n, cap, itemsize] out."""
+        slots MISS; true counts [n]).  ``prediction_distance`` is a scalar or [n].  Shapes as in :meth:`shape_intersections` (a capsule:
+        ``half_extents`` = (r, h, .)).  Device tensors in: a uint8 tensor [n, cap, itemsize] out."""
         dev = self._is_tensor(position)
         n = int(position.shape[0])
         q = avn_spatial_shape_contact_queries()
@@ -575,7 +579,7 @@ class SpatialQuery:
     def depenetrate(self, shape, half_extents, position, rotation, skin_width, max_depenetration_error, penetration_rejection_threshold, iterations,
                     mask=None, excluded=None, skip_host_shapes=False, skip_sensors=False):
         """MoveAndSlide::depenetrate per query shape: a structured array of ``depenetration_dtype`` records (fixup, count, iterations_run,
-        truncated).  The caller applies PhysicsLengthUnit to the configuration.  Device tensors in: a uint8 tensor [n, itemsize] out."""
+        truncated).  The caller applies PhysicsLengthUnit to the configuration.  A capsule: ``half_extents`` = (r, h, .).  Device tensors in: a uint8 tensor [n, itemsize] out."""
         dev = self._is_tensor(position)
         n = int(position.shape[0])
         q = avn_spatial_shapes()
@@ -616,7 +620,7 @@ class SpatialQuery:
 
     def cast_moves(self, shape, half_extents, position, rotation, movement, skin_width, self_entity=None, mask=None, excluded=None, skip_host_shapes=False):
         """MoveAndSlide::cast_move per move: a structured array of ``move_hit_dtype`` records (collider == MISS: the way is free).  ``skin_width``
-        is a scalar or [n]; ``self_entity`` [n] is the entity each query never hits (MISS: none).  Device tensors in: a uint8 tensor
+        is a scalar or [n]; ``self_entity`` [n] is the entity each query never hits (MISS: none).  A capsule: ``half_extents`` = (r, h, .).  Device tensors in: a uint8 tensor
         [n, itemsize] out."""
         dev = self._is_tensor(position)
         n = int(position.shape[0])
@@ -643,7 +647,8 @@ class SpatialQuery:
                        penetration_rejection_threshold, depenetration_iterations, move_and_slide_iterations=4, max_planes=20,
                        plane_similarity_dot_threshold=0.999, planes=None, hit_cap=0, self_entity=None, mask=None, excluded=None, skip_host_shapes=False):
         """MoveAndSlide::move_and_slide per character: (``slide_dtype`` records [n], ``slide_hit_dtype`` records [n, hit_cap]: what on_hit would
-        have been called with).  ``planes`` [k, 3] float32 are the configuration's initial planes, shared by the call.  The caller applies
+        have been called with).  ``planes`` [k, 3] float32 are the configuration's initial planes, shared by the call.  A capsule character
+        (Collider::capsule(radius, length)): shape SHAPE_CAPSULE, ``half_extents`` = (radius, length / 2, .).  The caller applies
         PhysicsLengthUnit to the configuration.  Device tensors in: uint8 tensors [n, itemsize] and [n, hit_cap, itemsize] out."""
         dev = self._is_tensor(position)
         n = int(position.shape[0])
@@ -714,7 +719,7 @@ class SpatialQuery:
     def shape_casters_upload(self, shape, half_extents, origin, shape_rotation, direction, anchor_kind=None, anchor=None, max_distance=None, max_hits=None,
                              hit_cap=1, enabled=None, mask=None, self_entity=None, ignore_self=None, excluded=None):
         """avn_spatial_shape_casters_upload: the world's ShapeCasters (AVN_SHAPE_CUBOID = 0 / AVN_SHAPE_BALL = 1, a ball's radius in
-        half_extents[:, 0]; ``shape_rotation`` [n, 4] xyzw, local); the other arguments as in :meth:`ray_casters_upload`."""
+        half_extents[:, 0] / SHAPE_CAPSULE = 3, ``half_extents`` = (r, h, .); ``shape_rotation`` [n, 4] xyzw, local); the other arguments as in :meth:`ray_casters_upload`."""
         n = int(np.asarray(origin).reshape(-1, 3).shape[0])
         c = avn_spatial_shape_casters()
         self._caster_common(c, n, hit_cap, anchor_kind, anchor, origin, direction, max_distance, max_hits, enabled, mask, self_entity, ignore_self, excluded)

@@ -118,7 +118,52 @@
  *      max_depenetration_error.  iterations_run counts the passes started.  Avian hands the normal over as a Dir, which is f32: in an f64
  *      world every component of n is rounded through float before use (the contact records keep the full-precision normal).  The caller
  *      applies PhysicsLengthUnit to max_depenetration_error and penetration_rejection_threshold.
- *    NOT covered: query shapes other than Ball / Cuboid, contacts against AVN_SHAPE_HOST colliders, predicates, Rust declarations.
+ *    NOT covered: query shapes other than Ball / Cuboid / Capsule (cylinders, cones, hulls), contacts against AVN_SHAPE_HOST colliders, predicates, Rust declarations.
+ *  - capsule query shapes (AVN_SHAPE_CAPSULE; parry's Capsule::new_y, the shape of Avian's character-controller examples).  A capsule is a
+ *    QUERY shape only: every entry point that takes a query shape accepts it against Ball and Cuboid colliders; colliders stay Ball /
+ *    Cuboid / Host.  half_extents = (r, h, .): x the radius (as a ball keeps its radius in x), y the half length of the segment (0, -h, 0) ..
+ *    (0, +h, 0) of the shape's frame, z not read; Collider::capsule(radius, length) is r = radius, h = length / 2.  Valid: finite r and h,
+ *    both >= 0 (h == 0 is a ball, r == 0 a segment, both 0 a point), the usual finite pose, and a finite AABB
+ *      [a, b] = position -+ (|qrot(rotation, (0, h, 0))| + (r, r, r))   per component (qrot: the function collider_pose uses),
+ *    which stands wherever a query shape's shape_aabb stands above (node tests, the AABB precondition (b) of a contact).  As for the shape
+ *    casts the pair tests are DEFINED HERE with their operation order (no FMA contraction); parity with parry is UNPINNED.  All of them
+ *    work in the collider's frame on the capsule's core, the segment A + s u, s in [0, 1]:
+ *      q = iso_inv_mul({collider rotation, collider position}, make_isometry(query position, query rotation)), hv = na_qrot(q.r, (0, h, 0)),
+ *      A = q.t - hv, u = 2 hv.  A ball collider's core is its centre (the origin) with radius r_c; a cuboid's core is the box, r_c = 0.
+ *      dot is na_dot (left to right), clamp(p) the clamp of p to the box per component.
+ *      P (segment - point c): uu = dot(u, u); s = dot(c - A, u) / uu clamped to [0, 1], 0 when uu == 0; d2 = |c - (A + u s)|^2.
+ *      X (segment - box he, exact): f(s) = |x - clamp(x)|^2 at x = A + u s is convex and piecewise quadratic.  Breakpoints: per axis i = x, y, z
+ *        and side -he_i then +he_i, b = (side - A_i) / u_i when u_i != 0 and 0 < b < 1, else 1; the six sorted ascending b_1..b_6, with b_0 = 0
+ *        and b_7 = 1.  Candidates in this order: 0, 1, b_1..b_6, then for k = 0..6 the candidate of the interval [b_k, b_k+1]: mid = (b_k +
+ *        b_k+1) / 2, m = A + u mid, sg_i = m_i > he_i ? 1 : m_i < -he_i ? -1 : 0 (the active faces); none active: mid; else den = the sum of
+ *        u_i u_i and num = the sum of u_i (A_i - sg_i he_i) over the active axes in x, y, z order, the candidate is -num / den clamped to the
+ *        interval when den > 0 and b_k otherwise.  Every candidate's f is evaluated in full; the first with the smallest f wins (strict <).
+ *        X answers f, s, p_seg = A + u s and p_box = clamp(p_seg).
+ *      intersection: P's d2 <= (r + r_c)^2 against a ball, X's f <= r * r against a cuboid (touching counts).
+ *      cast against a ball collider: the ball's centre as a ray against the capsule of radius R = r + r_c in the capsule's frame, the ray
+ *        reversed: o = iso_inv_point(q, 0), dd = -iso_inv_vec(q, d_l).  The capsule is, in this order, the cylinder about y (B on the (x, z)
+ *        components alone, left out when those components of dd are both 0, accepted when |o_y + dd_y t| <= h) and the end spheres at (0, -h, 0)
+ *        and (0, +h, 0) (B); the smallest entry wins (strict <) and gives the normal n_q ((p_x, 0, p_z) / |(p_x, p_z)| of the cylinder, p / |p|
+ *        of a sphere).  normal1 = -rot_q n_q; point1 = pos_c + normal1 r_c; point2 = rot_q ((0, clamp(o_y + dd_y t, -h, h), 0) + n_q r) +
+ *        (pos_q + d t).
+ *      cast against a cuboid collider: there is no finite SAT for a rounded segment; the cast is Newton's iteration on the convex g(t) =
+ *        sqrt(X(A + d_l t, u).f) - r from t = 0, at most 32 rounds.  A round: X at t, dist = sqrt(f), n = (p_seg - p_box) / dist (when
+ *        dist is 0 the n of the round before stands, 0 in round 0).  dist <= r: overlap at the start in round 0, else a hit at t.  v = -dot(n, d_l); !(v > 0): a miss.  t' = t + (dist - r)
+ *        / v; t' > max_distance: a miss; !(t' > t), or the 32nd round: a hit at t; else t = t'.  From the left of the root the iterates rise
+ *        monotonically and do not pass it in exact arithmetic, so a hit under-estimates the distance, never over-estimates it.  normal1 =
+ *        rot_c n; point1 = rot_c p_box + pos_c; point2 = rot_c (p_seg - n r) + pos_c.  Where the closest pair is not unique (a capsule side
+ *        parallel to a face or an edge) the witness is the one X's candidate order picks: a deterministic strengthening.
+ *      contact (the record of shape contacts, ONE point per collider, for a capsule query in place of (c) and (d); (a) and (b) unchanged):
+ *        dist = sqrt(P.d2) or sqrt(X.f).  dist > 0: gap = (dist - r) - r_c; a contact iff !(gap > p); n = (p_seg - p_core) / dist,
+ *        penetration = -gap, anchor1 = rot_c ((p_seg - n r) - q.t), anchor2 = rot_c (p_core + n r_c).  dist == 0 against a cuboid (the segment
+ *        touches or crosses the box): the smallest overlap over the six axes of the Minkowski difference, e_0..e_2 then (u x e_i) / |u x e_i|
+ *        (skipped when |u x e_i|^2 is not above eps^2 dot(u, u)), overlap = (sum |axis_i| he_i + |dot(axis, u / 2)|) - |dot(axis, A + u / 2)|,
+ *        the first smallest wins; n = the axis signed towards the segment's midpoint, penetration = overlap + r, anchor1 from p_d - n r with
+ *        p_d the segment's end deepest along -n (A on a tie), anchor2 from p_d projected onto the box's supporting plane of n.  dist == 0
+ *        against a ball (its centre on the segment): no direction, no contact.  normal = rot_c n (from the collider towards the query), point
+ *        = query position + anchor1.  cast_move's ORIGIN-PENETRATION RULE uses this contact at prediction 0 (point1 = collider position +
+ *        anchor2); depenetration, project_velocity and the slide loop read records only and are unchanged.
+ *    A capsule with h == 0 answers what the Ball query of radius r answers up to rounding (tests/test_spatial_capsule_cpu.py).
  *  - move and slide (MoveAndSlide::cast_move, project_velocity, move_and_slide; move_and_slide.rs:464-793, velocity_project.rs).  As above the
  *    definitions are written out here with their operation order (no FMA contraction); parity with glam / parry is UNPINNED.  Common rules:
  *      Sensors are never candidates (MoveAndSlide's collider query is Without<Sensor>; cast_move's predicate enforces it for the cast too).
@@ -174,8 +219,8 @@
  *  - a collider whose snapshot position, rotation or shape AABB is not finite is never a candidate (it keeps its collider index);
  *  - a query whose origin, direction, point or box corner is not finite answers a miss (ray queries, projection) or a count of 0, whatever
  *    the scene;
- *  - a query shape whose kind is neither AVN_SHAPE_CUBOID nor AVN_SHAPE_BALL, whose position, rotation, half extents (a ball: its radius) or
- *    AABB are not finite, or which has a negative half extent, answers a count of 0 (a shape cast: a miss / count 0; so does a cast whose
+ *  - a query shape whose kind is none of AVN_SHAPE_CUBOID, AVN_SHAPE_BALL and AVN_SHAPE_CAPSULE (kind 2 is not a query shape), whose position,
+ *    rotation, half extents (a ball: its radius; a capsule: r and h) or AABB are not finite, or which has a negative half extent, answers a count of 0 (a shape cast: a miss / count 0; so does a cast whose
  *    direction is not finite or whose max_distance is NaN; shape contacts: so does a prediction_distance that is NaN, infinite or
  *    negative; depenetration: a zero fixup with count 0).  This is decided per query on the device;
  *  - a hit needs a finite distance.
@@ -230,7 +275,7 @@
  *    caster order; slots past the answer are misses (both ids AVN_SPATIAL_MISS, the rest 0).  Avian's ShapeCaster loop of casts that exclude
  *    each hit in turn gives the same list; its RayCaster keeps an arbitrary subset when truncated (nearest-k: the strengthening above).
  *    NOT covered: target_distance, compute_contact_on_penetration, ignore_origin_penetration of ShapeCaster (the cast is cast_shapes': an overlap at
- *    the start answers distance 0), caster shapes other than Ball / Cuboid, ChildOf chains other than the two anchors, running the casters from
+ *    the start answers distance 0), caster shapes other than Ball / Cuboid / Capsule, ChildOf chains other than the two anchors, running the casters from
  *    avn_step, Rust declarations.
  *  - avn_despawn renumbers bodies and colliders: it drops every caster definition (a call rejected before it changed anything keeps them).  Other table uploads keep them; a run whose anchors no
  *    longer fit the tables is AVN_ERR_STATE.
@@ -243,6 +288,10 @@
 #ifdef __cplusplus
 extern "C" {
 #endif
+
+/* A query-shape kind of this header only: a capsule (the segment (0, -h, 0) .. (0, +h, 0) swept by a ball of radius r; half_extents = (r, h, .)).
+ * It is not a collider kind: avn_colliders_upload, avn_contact_manifolds and the swept CCD keep treating the value as they always have. */
+enum { AVN_SHAPE_CAPSULE = 3 };
 
 /* flags of a query */
 enum {
@@ -299,7 +348,7 @@ typedef struct avn_spatial_solid_points {
 typedef struct avn_spatial_shapes {
     uint32_t count;
     uint32_t flags;
-    const uint8_t* shape;        /* [n] AVN_SHAPE_CUBOID / AVN_SHAPE_BALL */
+    const uint8_t* shape;        /* [n] AVN_SHAPE_CUBOID / AVN_SHAPE_BALL / AVN_SHAPE_CAPSULE */
     const void* half_extents;    /* [3n] (ball: radius in x, as in the collider table) */
     const void* position;        /* [3n] */
     const void* rotation;        /* [4n] xyzw, unit (the caller normalises) */
@@ -341,7 +390,7 @@ typedef struct avn_spatial_projection_f64 {
 typedef struct avn_spatial_shape_casts {
     uint32_t count;
     uint32_t flags;
-    const uint8_t* shape;        /* [n] AVN_SHAPE_CUBOID / AVN_SHAPE_BALL */
+    const uint8_t* shape;        /* [n] AVN_SHAPE_CUBOID / AVN_SHAPE_BALL / AVN_SHAPE_CAPSULE */
     const void* half_extents;    /* [3n] (ball: radius in x) */
     const void* position;        /* [3n] the shape's position at distance 0 */
     const void* rotation;        /* [4n] xyzw, unit (the caller normalises) */
@@ -376,7 +425,7 @@ typedef struct avn_spatial_shape_hit_f64 {
 typedef struct avn_spatial_shape_contact_queries {
     uint32_t count;
     uint32_t flags;              /* AVN_SPATIAL_*, AVN_SPATIAL_SKIP_SENSORS included */
-    const uint8_t* shape;        /* [n] AVN_SHAPE_CUBOID / AVN_SHAPE_BALL */
+    const uint8_t* shape;        /* [n] AVN_SHAPE_CUBOID / AVN_SHAPE_BALL / AVN_SHAPE_CAPSULE */
     const void* half_extents;    /* [3n] (ball: radius in x) */
     const void* position;        /* [3n] */
     const void* rotation;        /* [4n] xyzw, unit (the caller normalises) */
@@ -456,7 +505,7 @@ typedef struct avn_spatial_velocities_out {
 typedef struct avn_spatial_moves {
     uint32_t count;
     uint32_t flags;
-    const uint8_t* shape;        /* [n] AVN_SHAPE_CUBOID / AVN_SHAPE_BALL */
+    const uint8_t* shape;        /* [n] AVN_SHAPE_CUBOID / AVN_SHAPE_BALL / AVN_SHAPE_CAPSULE */
     const void* half_extents;    /* [3n] (ball: radius in x) */
     const void* position;        /* [3n] */
     const void* rotation;        /* [4n] xyzw, unit */
@@ -652,7 +701,7 @@ typedef struct avn_spatial_shape_casters {
     const float* direction;          /* [3n] */
     const void* max_distance;        /* [n] */
     const uint32_t* max_hits;        /* [n] */
-    const uint8_t* shape;            /* [n] AVN_SHAPE_CUBOID / AVN_SHAPE_BALL */
+    const uint8_t* shape;            /* [n] AVN_SHAPE_CUBOID / AVN_SHAPE_BALL / AVN_SHAPE_CAPSULE */
     const void* half_extents;        /* [3n] (ball: radius in x) */
     const void* shape_rotation;      /* [4n] xyzw, local */
     const uint8_t* enabled;

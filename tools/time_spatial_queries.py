@@ -18,13 +18,17 @@
   numpy, ray_hits / shape_hits with k + 1 and the caster's own entity dropped on the host, uploads included; and the cheaper cast_rays /
   ray_hits / cast_shapes with k, which cannot ignore the own entity), the two alternating, in wall-clock windows closed by a device
   synchronisation; the host-side duration of the casters_run call alone, and the share of the run that is the LBVH build
+  capsule query shapes: shape_intersections, cast_shapes short and long, shape_contacts and move_and_slide with the reference character's capsule
+  (Collider::capsule(0.4, 1.0): r = 0.4, h = 0.5) on the poses of the legs above, each beside the same call with a Cuboid query of the capsule's
+  bounding box (0.4, 0.9, 0.4) from the same run, with the node and leaf counts; and the mean Newton rounds per capsule-cuboid pair, from the
+  numpy restatement (tests/spatial_capsule_reference.py) on a sample of the timed long casts
 
 Every figure is the median over `reps` warmed-up calls.  The queries take torch tensors on the GPU (AVN_SPATIAL_DEVICE_POINTERS: no
 staging copies), so a call is its launches plus one stream synchronisation; the update is timed with avn_synchronize behind it.  Device
 events bracket the calls on torch's stream after a synchronisation of it, which the library's own stream joins at the call's end.
 bytes_floor: the bytes each call must move at least (inputs, outputs, the snapshot records a query touches once), for a roofline fraction
 against MI355X's 8 TB/s HBM.
-usage: python tools/time_spatial_queries.py [reps] [casters]      (`casters`: that leg alone)"""
+usage: python tools/time_spatial_queries.py [reps] [casters] [nocapsule]      (`casters`: that leg alone; `nocapsule`: without the capsule legs)"""
 import json
 import os
 import sys
@@ -37,7 +41,7 @@ sys.path.insert(0, R)
 import torch  # noqa: E402
 import avian_amd  # noqa: E402
 from avian_amd import _ffi as F, scenes  # noqa: E402
-from avian_amd.spatial_query import ANCHOR_BODY, MISS, SpatialQuery  # noqa: E402
+from avian_amd.spatial_query import ANCHOR_BODY, MISS, SHAPE_CAPSULE, SpatialQuery  # noqa: E402
 
 HBM = 8.0e12
 
@@ -168,6 +172,51 @@ def casters_leg(res, w2, sq, sc, reps):
     sq.ray_casters_upload(np.zeros((0, 3)), np.zeros((0, 3), np.float32))
     sq.shape_casters_upload(np.zeros(0, np.uint8), np.zeros((0, 3)), np.zeros((0, 3)), np.zeros((0, 4)), np.zeros((0, 3), np.float32))
     sq.update()
+
+
+def capsule_legs(res, w2, sq, sc, dev, p, o, d, rot, short, long, cv, nc, mcfg, rounds, reps):
+    n = p.shape[0]
+    pred = torch.full((n,), 0.05, device=dev)
+    keys = ("shapes_1m", "cast_shapes_short", "cast_shapes_long", "contacts_1m", "move_and_slide_256k")
+    for name, kind_v, he_v in (("capsule", SHAPE_CAPSULE, (0.4, 0.5, 0.0)), ("cuboid", 0, (0.4, 0.9, 0.4))):
+        kind = torch.full((n,), kind_v, dtype=torch.uint8, device=dev)
+        he = torch.tensor(he_v, device=dev).repeat(n, 1).contiguous()
+        ck, che, cp, cr = kind[:nc].contiguous(), he[:nc].contiguous(), o[:nc].contiguous(), rot[:nc].contiguous()
+        calls = (lambda: sq.shape_intersections(kind, he, p, rot, 16), lambda: sq.cast_shapes(kind, he, o, rot, d, short), lambda: sq.cast_shapes(kind, he, o, rot, d, long),
+                 lambda: sq.shape_contacts(kind, he, p, rot, pred, 16), lambda: sq.move_and_slide(ck, che, cp, cr, cv, **mcfg, move_and_slide_iterations=rounds, hit_cap=0))
+        for key, fn in zip(keys, calls):
+            count = nc if key.startswith("move") else n
+            res[f"{name}_query_{key}_ms"] = timed(fn, reps)
+            st = sq.stats()
+            res[f"{name}_query_{key}_leaves_per_query"], res[f"{name}_query_{key}_nodes_per_query"] = st.leaves_visited / count, st.nodes_visited / count
+    for key in keys:
+        res[f"capsule_over_cuboid_{key}"] = res[f"capsule_query_{key}_ms"] / res[f"cuboid_query_{key}_ms"]
+    res.update(newton_rounds_sample(sc.collider_kwargs(), w2.bodies_download(), o[:64].cpu().numpy(), d[:64].cpu().numpy(), rot[:64].cpu().numpy()))
+
+
+def newton_rounds_sample(cols, bodies, oo, dd, rr, reach=10.0, radius=2.0):
+    """Newton rounds of the capsule-cuboid pair test, from the numpy restatement: the given casts of the reference capsule over `reach` metres against
+    the colliders whose centre lies within `radius` of a cast's path (every pair the cast can reach there, and many it merely passes)."""
+    sys.path.insert(0, os.path.join(R, "tests"))
+    import spatial_capsule_reference as CAP
+    import spatial_query_reference as REF
+    m = len(oo)
+    nc = len(cols["shape"])
+    centre = np.asarray(bodies["position"], float)[np.asarray(cols["body"], np.int64)]
+    near = np.zeros(nc, bool)
+    for i in range(m):
+        t = np.clip((centre - oo[i]) @ dd[i], 0.0, reach)
+        near |= np.linalg.norm(centre - (oo[i] + t[:, None] * dd[i]), axis=1) < radius
+    idx = np.nonzero(near)[0]
+    sub = {k: np.asarray(v)[idx] for k, v in cols.items() if isinstance(v, np.ndarray) and v.ndim >= 1 and len(v) == nc}
+    snap = REF.Snapshot(bodies, sub, None, np.float32)
+    with np.errstate(all="ignore"):
+        hit = CAP.cast_pairs(snap, np.full(m, SHAPE_CAPSULE, np.uint8), np.tile([0.4, 0.5, 0.0], (m, 1)), oo, rr, dd, np.full(m, reach))[0]
+    rounds = CAP.last_rounds
+    ran = rounds > 0
+    return {"capsule_newton_rounds_mean_per_pair": float(rounds[ran].mean()) if ran.any() else 0.0,
+            "capsule_newton_rounds_mean_per_hit_pair": float(rounds[hit & ran].mean()) if (hit & ran).any() else 0.0,
+            "capsule_newton_rounds_max": int(rounds.max()) if rounds.size else 0, "capsule_newton_rounds_pairs": int(ran.sum()), "capsule_newton_rounds_casts": m}
 
 
 def world(sc, steps):
@@ -332,6 +381,8 @@ def main():
     ms = timed(composed, reps)
     res["composed_parent_calls_256k_ms"] = ms
     res["move_and_slide_over_composed"] = res["move_and_slide_256k_ms"] / ms
+    if "nocapsule" not in sys.argv[2:]:   # (an A/B run of a library from before the capsule: the legs above alone)
+        capsule_legs(res, w2, sq, sc2, dev, p, o, d, rot, short, long, cv, nc, mcfg, rounds, reps)
     res["update_bytes_floor_per_collider"] = 4 * 16 + 16 + 8 + 4 * 16 + 2 * 16 + 2 * 2 * 16 + 8 + 12
     for k in [k for k in res if k.endswith("_bytes_floor")]:
         msk = k.replace("_bytes_floor", "_ms") if k.replace("_bytes_floor", "_ms") in res else None
