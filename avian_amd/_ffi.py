@@ -288,6 +288,7 @@ PAIR_DTYPE = np.dtype([("collider1", "<u4"), ("collider2", "<u4"), ("body1", "<i
 
 # ---- host shapes (include/avian_mi355x.h "host shapes"): the two AnyCollider callbacks -----------------------------------------------------
 SHAPE_CUBOID, SHAPE_BALL, SHAPE_HOST = 0, 1, 2
+SHAPE_CAPSULE = 3   # AVN_SHAPE_CAPSULE: half_extents = (radius, half length of the segment along local y, unused); a collider kind on the HIP backend and a query shape
 HOST_SHAPE_FN = C.CFUNCTYPE(None, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p)   # avn_host_aabb_fn == avn_host_manifolds_fn in shape
 
 

@@ -3,6 +3,7 @@
 #include <type_traits>
 
 #include "avn_device.h"
+#include "../../include/avian_mi355x_spatial.h"   // AVN_SHAPE_CAPSULE
 
 namespace avn {
 
@@ -44,9 +45,18 @@ template <class T> __device__ __forceinline__ void collider_pose(const BP<T>& bp
     rot = qnormalize(qmul(body_rot, quat<T>(bp.col_lrot[slot])));
     if (child) *child = true;
 }
-// the exact AABB of a cuboid / ball at a pose, no margins (update_aabb; the spatial queries' BVH and AABB test)
-template <class T> __device__ __forceinline__ void shape_aabb(uint32_t shape, V3<T> h, V3<T> pos, Q4<T> q, V3<T>& mn, V3<T>& mx) {
+// the exact AABB of a capsule h = (r, half length, .) at a pose: pos -+ (|qrot(q, (0, h.y, 0))| + (r, r, r)) -- ONE definition for the capsule query
+// shape (k_spatial.hip sp_load_shape) and the capsule collider (k_update_aabb): the same pose gives the same box bit for bit
+template <class T> __device__ __forceinline__ void capsule_aabb(V3<T> h, V3<T> pos, Q4<T> q, V3<T>& mn, V3<T>& mx) {
+    const V3<T> hv = qrot(q, V3<T>{T(0), h.y, T(0)});
+    const V3<T> ext = V3<T>{fabs_t(hv.x), fabs_t(hv.y), fabs_t(hv.z)} + V3<T>{h.x, h.x, h.x};
+    mn = pos - ext; mx = pos + ext;
+}
+// the exact AABB of a cuboid / ball at a pose, no margins (update_aabb; the spatial queries' BVH and AABB test).  CAP (k_update_aabb only):
+// an AVN_SHAPE_CAPSULE collider as well; without it the kinds are Ball and Cuboid as ever.
+template <class T, bool CAP = false> __device__ __forceinline__ void shape_aabb(uint32_t shape, V3<T> h, V3<T> pos, Q4<T> q, V3<T>& mn, V3<T>& mx) {
     V3<T> he;
+    if (CAP && shape == AVN_SHAPE_CAPSULE) { capsule_aabb<T>(h, pos, q, mn, mx); return; }
     if (shape == AVN_SHAPE_BALL) he = V3<T>{h.x, h.x, h.x};
     else {
         // parry3d Cuboid::aabb: centre +- |R| * half_extents, R = nalgebra UnitQuaternion::to_rotation_matrix
@@ -130,7 +140,7 @@ template <class T> void launch_joint_schedule(const DW<T>&, const StepParams<T>&
 template <class T> void launch_writeback_joint_forces(const DW<T>&, const StepParams<T>&, hipStream_t);
 // k_broadphase.hip
 // zero_words[0 .. n_zero) (n_zero <= 256) are cleared by the kernel: the step-scoped counters of what follows; returns whether a kernel ran
-template <class T> bool launch_update_aabb(const DW<T>&, const BP<T>&, const StepParams<T>&, hipStream_t, uint32_t* zero_words = nullptr, uint32_t n_zero = 0);
+template <class T> bool launch_update_aabb(const DW<T>&, const BP<T>&, const StepParams<T>&, hipStream_t, uint32_t* zero_words = nullptr, uint32_t n_zero = 0, bool capsules = false /* the world holds AVN_SHAPE_CAPSULE colliders */);
 // counters_clean: n_dropped[0..2) is known to be zero (no memset launch)
 template <class T> void launch_interval_keys(const DW<T>&, const BP<T>&, typename BP<T>::Key* keys, uint32_t* vals, uint32_t* n_dropped, hipStream_t, bool counters_clean = false);
 // partial: 6 * ceil(C / 256) scalars; returns the number of partial records written
@@ -193,8 +203,9 @@ template <class T> void launch_clear_contact_rows(const CT<T>&, const uint32_t* 
 // count == nullptr: no modify hook is registered (the plain kernels run unless the world holds host shapes).
 struct NpHookList { void* records = nullptr; uint32_t* count = nullptr; uint32_t cap = 0; uint32_t phase = 0; };
 // locals: the world holds child colliders (BP::col_lpos): their poses are computed by the HS instantiations only
-struct NpHostList { void* queries = nullptr; uint32_t* count = nullptr; uint32_t cap = 0; uint32_t host_only = 0; NpHookList hook; bool locals = false;
-                    bool any() const { return queries != nullptr || hook.count != nullptr || locals; } };
+// capsules: the world holds AVN_SHAPE_CAPSULE colliders: their manifolds are computed by the HS instantiations' heavy kernel only
+struct NpHostList { void* queries = nullptr; uint32_t* count = nullptr; uint32_t cap = 0; uint32_t host_only = 0; NpHookList hook; bool locals = false; bool capsules = false;
+                    bool any() const { return queries != nullptr || hook.count != nullptr || locals || capsules; } };
 template <class T> void launch_narrow_phase_hooked(const DW<T>&, const BP<T>&, const CT<T>&, const StepParams<T>&, bool dense, avn_contact_change* changes, uint32_t* n_changes, uint32_t* chg,
                                                    uint32_t* has, const void* records /* sorted by contact id, as the hook left them */, uint32_t n, hipStream_t);
 template <class T> void launch_narrow_phase_host(const DW<T>&, const BP<T>&, const CT<T>&, const StepParams<T>&, bool dense, avn_contact_change* changes, uint32_t* n_changes, uint32_t* chg,
@@ -334,7 +345,7 @@ template <class T> struct QueryStage {
     T *normal, *anchor1, *anchor2, *point, *penetration;
     uint32_t *feature_id1, *feature_id2;
 };
-template <class T> void launch_contact_manifolds_query(const QueryStage<T>&, uint32_t n, hipStream_t);
+template <class T> void launch_contact_manifolds_query(const QueryStage<T>&, uint32_t n, hipStream_t, bool capsules = false /* the batch holds AVN_SHAPE_CAPSULE shapes */);
 // k_transfer.hip: host-layout (interleaved xyz) <-> device Vec4 records
 template <class T> struct BodyStage {  // device staging copies of the avn_bodies arrays (nullptr = absent)
     const T *position, *rotation, *linear_velocity, *angular_velocity, *inv_mass, *inv_inertia_local, *center_of_mass, *linear_damping,

@@ -15,6 +15,7 @@
 // square roots per SAT axis); the kernel that calls this streams 2 x 80 B of collider / pose data per pair.
 #pragma once
 #include "avn_device.h"
+#include "../../include/avian_mi355x_spatial.h"   // AVN_SHAPE_CAPSULE
 
 namespace avn {
 
@@ -287,14 +288,19 @@ template <class T, class Em> __device__ void face_face_contacts(const Iso<T>& po
         }
 }
 
-// contact_query::contact_manifolds for one pair (he: cuboid half extents, ball radius in x); false = no manifold
+// the manifolds of a Capsule collider (CAP instantiations only): avn_capsule_pair.h, which a translation unit that instantiates CAP = true includes
+template <class T, class Em> __device__ bool capsule_pair_manifold(uint32_t shape1, V3<T> he1, uint32_t shape2, V3<T> he2, const Iso<T>& pos12, T prediction, Em& em);
+
+// contact_query::contact_manifolds for one pair (he: cuboid half extents, ball radius in x; CAP: a capsule's (r, h, .)); false = no manifold
+// CAP = false (every instantiation of a world without capsule colliders, the spatial queries, the swept CCD): the kinds are Ball and Cuboid,
+// anything that is not a ball is read as a cuboid.  CAP = true: a pair with an AVN_SHAPE_CAPSULE goes to capsule_pair_manifold.
 // `defer` (optional): the cuboid-cuboid path has a cheap half -- the three SAT sweeps, after which most AABB-overlapping pairs are known to be
 // apart -- and a heavy half (support faces, clipping in the plane, conversion of up to 16 raw points).  With defer != nullptr and
 // *defer == false on entry the function stops after the SAT of a pair that survives it, leaves the separating direction in *axis and sets
 // *defer = true (nothing of `out` is valid); called again with *defer == true it skips the SAT and continues from *axis.  A caller that
 // gathers the survivors of a workgroup into dense waves (k_narrow_phase) runs the heavy half at full lane occupancy; the result is the
 // one-call result bit for bit.
-template <class T, class Sink, int MODE = 0>   // MODE 1: `defer` given and false on entry (stop after the SAT), 2: given and true (continue from *axis), 0: decided at run time
+template <class T, class Sink, int MODE = 0, bool CAP = false>   // MODE 1: `defer` given and false on entry (stop after the SAT), 2: given and true (continue from *axis), 0: decided at run time
 __device__ bool contact_manifolds_pair_sink(uint32_t shape1, V3<T> he1, V3<T> position1, Q4<T> rotation1, uint32_t shape2, V3<T> he2, V3<T> position2, Q4<T> rotation2,
                                             T prediction, Sink& sink, V3<T>& normal_out, bool* defer = nullptr, V3<T>* axis = nullptr) {
     Iso<T> isometry1 = make_isometry(position1, rotation1), isometry2 = make_isometry(position2, rotation2);
@@ -302,7 +308,11 @@ __device__ bool contact_manifolds_pair_sink(uint32_t shape1, V3<T> he1, V3<T> po
     NpEmit<T, Sink> em;
     em.rotation1 = rotation1; em.sink = &sink;
     const bool ball1 = shape1 == AVN_SHAPE_BALL, ball2 = shape2 == AVN_SHAPE_BALL;
-    if (ball1 && ball2) {  // contact_manifold_ball_ball
+    bool capsule = false;
+    if constexpr (CAP) capsule = shape1 == AVN_SHAPE_CAPSULE || shape2 == AVN_SHAPE_CAPSULE;
+    if (capsule) {
+        if constexpr (CAP) { if (!capsule_pair_manifold<T, NpEmit<T, Sink>>(shape1, he1, shape2, he2, pos12, prediction, em)) return false; }
+    } else if (ball1 && ball2) {  // contact_manifold_ball_ball
         T r1 = he1.x, r2 = he2.x;
         V3<T> dcenter = pos12.t;
         T center_dist = na_norm(dcenter);

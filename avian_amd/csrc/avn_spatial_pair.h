@@ -452,6 +452,33 @@ __device__ __forceinline__ bool sp_capsule_cast_exact(T r, T h, const Iso<T>& is
     return true;
 }
 
+// The segment touches or crosses the box (X's f == 0): the smallest overlap over the six axes of their Minkowski difference, e_0..e_2 then
+// normalize(u x e_i), the first smallest wins.  n: that axis signed towards the segment's midpoint, best: the overlap, brb: the box's
+// radius along n.  Shared by the capsule query's contact (below) and the capsule collider's manifold (avn_capsule_pair.h).
+template <class T> __device__ __forceinline__ void sp_seg_box_axis(V3<T> A, V3<T> u, V3<T> he1, V3<T>& n, T& best_out, T& brb_out) {
+    const V3<T> hv = u * T(0.5), m = A + hv;
+    const T eps2 = Limits<T>::eps * Limits<T>::eps * na_dot(u, u);
+    T best = sp_inf<T>(), brb = T(0);
+    n = vzero<T>();
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+        V3<T> ax;
+        if (k < 3) ax = sp_unit<T>(k, T(1));
+        else {
+            const V3<T> cx = k == 3 ? V3<T>{T(0), u.z, -u.y} : (k == 4 ? V3<T>{-u.z, T(0), u.x} : V3<T>{u.y, -u.x, T(0)});
+            const T l2c = na_dot(cx, cx);
+            if (!(l2c > eps2)) continue;
+            ax = cx / sqrt_t(l2c);
+        }
+        const T rb = fabs_t(ax.x) * he1.x + fabs_t(ax.y) * he1.y + fabs_t(ax.z) * he1.z;
+        const T rs = fabs_t(na_dot(ax, hv));
+        const T c = na_dot(ax, m);
+        const T ov = (rb + rs) - fabs_t(c);
+        if (ov < best) { best = ov; brb = rb; n = c < T(0) ? -ax : ax; }
+    }
+    best_out = best; brb_out = brb;
+}
+
 // The contact of the capsule (r, h) at pose iso2 with one collider within `prediction`: gap = dist - r - r_c between the cores.  Cores
 // apart: the normal from the collider's core point to the segment's; a segment crossing a cuboid: the smallest overlap over the six axes of
 // their Minkowski difference (e_0..e_2, then normalize(u x e_i)), first smallest wins; a ball's centre on the segment: no contact.
@@ -486,26 +513,8 @@ __device__ __forceinline__ bool sp_capsule_contact(T r, T h, const Iso<T>& iso2,
         l2 = pc + n * rc;
     } else {
         if (ball1) return false;
-        const V3<T> hv = u * T(0.5), m = A + hv;
-        const T eps2 = Limits<T>::eps * Limits<T>::eps * na_dot(u, u);
-        T best = sp_inf<T>(), brb = T(0);
-        n = vzero<T>();
-#pragma unroll
-        for (int k = 0; k < 6; ++k) {
-            V3<T> ax;
-            if (k < 3) ax = sp_unit<T>(k, T(1));
-            else {
-                const V3<T> cx = k == 3 ? V3<T>{T(0), u.z, -u.y} : (k == 4 ? V3<T>{-u.z, T(0), u.x} : V3<T>{u.y, -u.x, T(0)});
-                const T l2c = na_dot(cx, cx);
-                if (!(l2c > eps2)) continue;
-                ax = cx / sqrt_t(l2c);
-            }
-            const T rb = fabs_t(ax.x) * he1.x + fabs_t(ax.y) * he1.y + fabs_t(ax.z) * he1.z;
-            const T rs = fabs_t(na_dot(ax, hv));
-            const T c = na_dot(ax, m);
-            const T ov = (rb + rs) - fabs_t(c);
-            if (ov < best) { best = ov; brb = rb; n = c < T(0) ? -ax : ax; }
-        }
+        T best, brb;
+        sp_seg_box_axis<T>(A, u, he1, n, best, brb);
         pen = best + r;
         const V3<T> pd = na_dot(n, u) < T(0) ? A + u : A;   // the segment's deepest point along -n, the lower s on a tie
         l1 = pd - n * r;

@@ -108,7 +108,7 @@ __device__ __forceinline__ bool ccd_pair(const DW<T>& w, const BP<T>& bp, const 
     if (!meta_has_solver_body(w.bmeta[p.b1])) return false;                    // `solver_body: Some(..)`
     if (bp.col_lpos && bp.col_lpos[c2].w != T(0)) return false;                 // a child collider (declared deviation)
     p.shape1 = i1.z & 0xFFu; p.shape2 = i2.z & 0xFFu;
-    if (p.shape1 > AVN_SHAPE_BALL || p.shape2 > AVN_SHAPE_BALL) return false;   // AVN_SHAPE_HOST (declared deviation)
+    if (p.shape1 > AVN_SHAPE_BALL || p.shape2 > AVN_SHAPE_BALL) return false;   // AVN_SHAPE_HOST, AVN_SHAPE_CAPSULE (declared deviations)
     const uint32_t bm2 = w.bmeta[p.b2];
     if (!c.include_dynamic[p.e] && meta_rb_type(bm2) == AVN_RB_DYNAMIC) return false;
     const bool has2 = meta_has_solver_body(bm2);

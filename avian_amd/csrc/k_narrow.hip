@@ -4,6 +4,7 @@
 //                               (reference collision/collider/parry/contact_query.rs:156-261)
 #include "avn_kernels.h"
 #include "avn_narrow.h"
+#include "avn_capsule_pair.h"   // capsule colliders: the CAP instantiations of contact_manifolds_pair_sink (the HS heavy kernel, the batch query)
 
 // measurement cut-offs (AVN_NP_DEBUG, tools/np_phases.sh): compiled in only by `make measure`; the default library has no switch that changes results
 #ifdef AVN_MEASURE
@@ -17,7 +18,8 @@ namespace avn {
 template <class T> __device__ __forceinline__ V3<T> ld3(const T* p, size_t i) { return {p[3 * i], p[3 * i + 1], p[3 * i + 2]}; }
 template <class T> __device__ __forceinline__ void st3(T* p, size_t i, V3<T> v) { if (p) { p[3 * i] = v.x; p[3 * i + 1] = v.y; p[3 * i + 2] = v.z; } }
 
-template <class T>
+// CAP: the batch holds AVN_SHAPE_CAPSULE shapes (the host scans the kinds); a batch without one launches the Ball / Cuboid instantiation as ever
+template <class T, bool CAP = false>
 __global__ __launch_bounds__(64) void k_contact_manifolds_query(QueryStage<T> s, uint32_t n) {
     uint32_t i = blockIdx.x * 64 + threadIdx.x;
     if (i >= n) return;
@@ -25,7 +27,13 @@ __global__ __launch_bounds__(64) void k_contact_manifolds_query(QueryStage<T> s,
     Q4<T> r1{s.rotation1[4 * i], s.rotation1[4 * i + 1], s.rotation1[4 * i + 2], s.rotation1[4 * i + 3]};
     Q4<T> r2{s.rotation2[4 * i], s.rotation2[4 * i + 1], s.rotation2[4 * i + 2], s.rotation2[4 * i + 3]};
     NpManifold<T> m;
-    bool has = contact_manifolds_pair<T>(s.shape1[i], ld3(s.half_extents1, i), p1, r1, s.shape2[i], ld3(s.half_extents2, i), p2, r2, s.prediction[i], m);
+    bool has;
+    if (CAP) {
+        m.n = 0;
+        NpArraySink<T> sink{&m, p1 - p2};
+        has = contact_manifolds_pair_sink<T, NpArraySink<T>, 0, true>(s.shape1[i], ld3(s.half_extents1, i), p1, r1, s.shape2[i], ld3(s.half_extents2, i), p2, r2, s.prediction[i], sink, m.normal);
+    } else
+    has = contact_manifolds_pair<T>(s.shape1[i], ld3(s.half_extents1, i), p1, r1, s.shape2[i], ld3(s.half_extents2, i), p2, r2, s.prediction[i], m);
     int cnt = has ? m.n : 0;
     if (s.point_count) s.point_count[i] = (uint8_t)cnt;
     st3(s.normal, i, has ? m.normal : vzero<T>());
@@ -41,11 +49,13 @@ __global__ __launch_bounds__(64) void k_contact_manifolds_query(QueryStage<T> s,
         if (s.feature_id2) s.feature_id2[slot] = live ? m.pts[k].fid2 : 0u;
     }
 }
-template <class T> void launch_contact_manifolds_query(const QueryStage<T>& s, uint32_t n, hipStream_t st) {
-    if (n) hipLaunchKernelGGL(k_contact_manifolds_query<T>, dim3((n + 63) / 64), dim3(64), 0, st, s, n);
+template <class T> void launch_contact_manifolds_query(const QueryStage<T>& s, uint32_t n, hipStream_t st, bool capsules) {
+    if (!n) return;
+    if (capsules) hipLaunchKernelGGL((k_contact_manifolds_query<T, true>), dim3((n + 63) / 64), dim3(64), 0, st, s, n);
+    else hipLaunchKernelGGL(k_contact_manifolds_query<T>, dim3((n + 63) / 64), dim3(64), 0, st, s, n);
 }
-template void launch_contact_manifolds_query<float>(const QueryStage<float>&, uint32_t, hipStream_t);
-template void launch_contact_manifolds_query<double>(const QueryStage<double>&, uint32_t, hipStream_t);
+template void launch_contact_manifolds_query<float>(const QueryStage<float>&, uint32_t, hipStream_t, bool);
+template void launch_contact_manifolds_query<double>(const QueryStage<double>&, uint32_t, hipStream_t, bool);
 
 }  // namespace avn
 
@@ -113,6 +123,9 @@ template <class T> struct NpSinkOf<T, true> { typedef NpLdsSink<T> type; };
 // One pair.  HEAVY = false: the whole update unless the pair is a cuboid-cuboid one that survives the SAT -- then nothing is written,
 // *deferred = true and *axis holds the separating direction.  HEAVY = true: the deferred pair again, from the top (every input is re-read:
 // nothing was written), with the SAT replaced by *axis.
+// Capsule colliders (include/avian_mi355x.h "capsule colliders") exist in the HS instantiations only: HEAVY = false defers every pair that holds one like a
+// surviving cuboid pair (axis unused); HEAVY = true with CAP computes its manifold (contact_manifolds_pair_sink<.., CAP = true>, avn_capsule_pair.h).  CAP is
+// k_narrow_phase_heavy's alone and set only for a world that holds a capsule: the pairs a host or a hook answered bring their manifold with them.
 // HS (host shapes, round 6: include/avian_mi355x.h "host shapes"): a pair with an AVN_SHAPE_HOST collider.  HEAVY = false: nothing is written, *deferred = true and
 // *hq holds the query contact_manifolds_with_context gets (system_param.rs:700-712); HEAVY = true: the pair again from the top with the manifold the host returned
 // (*hm) in the place of contact_query::contact_manifolds' -- margins, speculative filter, pruning, matching, status as for every other pair.
@@ -128,7 +141,7 @@ static_assert(sizeof(NpHookC<float>) == sizeof(avn_hook_contact_f32) && sizeof(N
               offsetof(NpHookC<float>, fid1) == offsetof(avn_hook_contact_f32, feature_id1), "hook record layout");
 template <class T> struct NpHookCtx { NpHookC<T>* rec; uint32_t* count; uint32_t cap, phase; const NpHookC<T>* in; };   // in != nullptr: phase 3, this pair's record
 template <class T> __host__ __device__ __forceinline__ NpHookCtx<T> np_hook_ctx(const NpHookList& l) { return NpHookCtx<T>{(NpHookC<T>*)l.records, l.count, l.cap, l.phase, nullptr}; }
-template <class T, bool DENSE, bool HEAVY, bool HS = false>
+template <class T, bool DENSE, bool HEAVY, bool HS = false, bool CAP = false>
 __device__ void np_update_pair(const DW<T>& w, const BP<T>& bp, const CT<T>& ct, const StepParams<T>& p, const uint32_t c,
                                avn_contact_change* __restrict__ changes, uint32_t* __restrict__ n_changes, uint32_t* __restrict__ chg,
                                uint32_t* __restrict__ has, bool* deferred, V3<T>* axis, T* lds_col, NpHostQ<T>* hq = nullptr, const NpHostM<T>* hm = nullptr,
@@ -248,9 +261,13 @@ __device__ void np_update_pair(const DW<T>& w, const BP<T>& bp, const CT<T>& ct,
             normal = V3<T>{hm->normal[0], hm->normal[1], hm->normal[2]};
             for (uint32_t k = 0; k < n; ++k) sink.put(V3<T>{hm->anchor1[3 * k], hm->anchor1[3 * k + 1], hm->anchor1[3 * k + 2]}, hm->penetration[k], hm->fid1[k], hm->fid2[k]);
             has_manifold = n != 0u;
+        } else if (HS && !HEAVY && ((ci1.z & 0xFFu) == AVN_SHAPE_CAPSULE || (ci2.z & 0xFFu) == AVN_SHAPE_CAPSULE)) {
+            // a capsule collider's pair: its AABB / layer / margin work is done; the manifold (sp_seg_box's candidates) is the heavy kernel's -- the row joins the
+            // survivor lists as a cuboid pair does after its SAT, the axis slot unused
+            has_manifold = false; defer = true;
         } else
         has_manifold = NP_DEBUG(p) == 1u ? false
-            : contact_manifolds_pair_sink<T, Sink, HEAVY ? 2 : 1>(ci1.z & 0xFFu, xyz<T>(he1), x1, q1, ci2.z & 0xFFu, xyz<T>(he2), x2, q2, max_contact_distance, sink, normal, &defer, axis);
+            : contact_manifolds_pair_sink<T, Sink, HEAVY ? 2 : 1, HS && HEAVY && CAP>(ci1.z & 0xFFu, xyz<T>(he1), x1, q1, ci2.z & 0xFFu, xyz<T>(he2), x2, q2, max_contact_distance, sink, normal, &defer, axis);
         if (!HEAVY && defer) { if (NP_DEBUG(p) == 2u) defer = false; else { *deferred = true; return; } }
         if (!HEAVY && has_manifold) load_manifold_inputs();
         if (HEAVY && NP_DEBUG(p) == 4u) {   // timing cut-off: the manifold's raw points are in LDS, nothing converted or written
@@ -490,7 +507,7 @@ __global__ __launch_bounds__(NP_LIGHT_THREADS) void k_narrow_phase(DW<T> w, BP<T
 // workgroup (chunk, list) = (blockIdx / NP_LISTS, blockIdx mod NP_LISTS): the populated chunks come first in the grid.  The last workgroup of
 // a list to finish clears the list's counters for the next launch (every workgroup that takes part has read the count before it reports);
 // the workgroups beyond a list's end leave without touching anything.
-template <class T, bool DENSE, bool HS = false>
+template <class T, bool DENSE, bool HS = false, bool CAP = false>
 __global__ __launch_bounds__(NP_THREADS) void k_narrow_phase_heavy(DW<T> w, BP<T> bp, CT<T> ct, StepParams<T> p, avn_contact_change* __restrict__ changes,
                                                                    uint32_t* __restrict__ n_changes, uint32_t* __restrict__ chg, uint32_t* __restrict__ has, uint32_t n_pairs,
                                                                    NpHookCtx<T> hk = NpHookCtx<T>()) {
@@ -504,7 +521,7 @@ __global__ __launch_bounds__(NP_THREADS) void k_narrow_phase_heavy(DW<T> w, BP<T
         const size_t k = (size_t)list * np_list_segment(n_pairs) + i;
         V3<T> axis{ct.np_axis[3 * k], ct.np_axis[3 * k + 1], ct.np_axis[3 * k + 2]};
         bool deferred = false;
-        if (HS) np_update_pair<T, DENSE, true, true>(w, bp, ct, p, ct.np_row[k], changes, n_changes, chg, has, &deferred, &axis, s_pts + threadIdx.x, nullptr, nullptr, &hk);
+        if (HS) np_update_pair<T, DENSE, true, true, CAP>(w, bp, ct, p, ct.np_row[k], changes, n_changes, chg, has, &deferred, &axis, s_pts + threadIdx.x, nullptr, nullptr, &hk);
         else
         np_update_pair<T, DENSE, true>(w, bp, ct, p, ct.np_row[k], changes, n_changes, chg, has, &deferred, &axis, s_pts + threadIdx.x);
     }
@@ -539,8 +556,10 @@ size_t np_survivor_list_slack() { return (size_t)NP_LISTS * NP_LIGHT_THREADS; }
 size_t np_survivor_counter_bytes() { return (size_t)NP_LISTS * NP_CTR_STRIDE * sizeof(uint32_t); }
 template <class T, bool DENSE>
 static void launch_np_heavy(const DW<T>& w, const BP<T>& bp, const CT<T>& ct, const StepParams<T>& p, avn_contact_change* changes, uint32_t* n_changes, uint32_t* chg, uint32_t* has,
-                            uint32_t n_pairs, hipStream_t st, const NpHookList& hook = NpHookList(), bool hs = false) {
+                            uint32_t n_pairs, hipStream_t st, const NpHookList& hook = NpHookList(), bool hs = false, bool caps = false) {
     const uint32_t chunks = np_list_segment(n_pairs) / NP_THREADS;
+    if (caps) hipLaunchKernelGGL((k_narrow_phase_heavy<T, DENSE, true, true>), dim3(chunks * NP_LISTS), dim3(NP_THREADS), 0, st, w, bp, ct, p, changes, n_changes, chg, has, n_pairs, np_hook_ctx<T>(hook));
+    else
     if (hook.count || hs) hipLaunchKernelGGL((k_narrow_phase_heavy<T, DENSE, true>), dim3(chunks * NP_LISTS), dim3(NP_THREADS), 0, st, w, bp, ct, p, changes, n_changes, chg, has, n_pairs, np_hook_ctx<T>(hook));
     else
     hipLaunchKernelGGL((k_narrow_phase_heavy<T, DENSE>), dim3(chunks * NP_LISTS), dim3(NP_THREADS), 0, st, w, bp, ct, p, changes, n_changes, chg, has, n_pairs, NpHookCtx<T>());
@@ -671,7 +690,7 @@ template <class T> void launch_narrow_phase(const DW<T>& w, const BP<T>& bp, con
     else
     hipLaunchKernelGGL((k_narrow_phase<T, false>), dim3((n_active + NP_LIGHT_THREADS - 1) / NP_LIGHT_THREADS), dim3(NP_LIGHT_THREADS), 0, st, w, bp, ct, p, active, n_active, changes, n_changes, nullptr, nullptr, 0u, 0u);
     if (hl.host_only) return;   // (a retry hands no cuboid pair over: nothing for the second kernel)
-    launch_np_heavy<T, false>(w, bp, ct, p, changes, n_changes, nullptr, nullptr, n_active, st, hl.hook, hl.any());
+    launch_np_heavy<T, false>(w, bp, ct, p, changes, n_changes, nullptr, nullptr, n_active, st, hl.hook, hl.any(), hl.capsules);
 }
 template <class T> void launch_narrow_phase_dense(const DW<T>& w, const BP<T>& bp, const CT<T>& ct, const StepParams<T>& p, uint32_t n_rows, uint32_t* chg, uint32_t* has,
                                                   uint32_t* n_remove, hipStream_t st, bool reset_counter, const NpHostList& hl) {
@@ -681,7 +700,7 @@ template <class T> void launch_narrow_phase_dense(const DW<T>& w, const BP<T>& b
     else
     hipLaunchKernelGGL((k_narrow_phase<T, true>), dim3((n_rows + NP_LIGHT_THREADS - 1) / NP_LIGHT_THREADS), dim3(NP_LIGHT_THREADS), 0, st, w, bp, ct, p, nullptr, n_rows, nullptr, n_remove, chg, has, 0u, 0u);
     if (hl.host_only) return;
-    launch_np_heavy<T, true>(w, bp, ct, p, nullptr, n_remove, chg, has, n_rows, st, hl.hook, hl.any());
+    launch_np_heavy<T, true>(w, bp, ct, p, nullptr, n_remove, chg, has, n_rows, st, hl.hook, hl.any(), hl.capsules);
 }
 // the rows list[0 .. n_list) followed by range_base .. range_base + n_range: same per-row work and outputs as the dense form; the
 // removal counter is NOT reset (it continues the count of the launch over the older rows)
@@ -697,7 +716,7 @@ template <class T> void launch_narrow_phase_rows(const DW<T>& w, const BP<T>& bp
     if (!n_list && !range_base) hipLaunchKernelGGL((k_narrow_phase<T, true>), dim3((n_range + NP_LIGHT_THREADS - 1) / NP_LIGHT_THREADS), dim3(NP_LIGHT_THREADS), 0, st, w, bp, ct, p, nullptr, n_range, nullptr, n_remove, chg, has, 0u, 0u);
     else hipLaunchKernelGGL((k_narrow_phase<T, true>), dim3((n + NP_LIGHT_THREADS - 1) / NP_LIGHT_THREADS), dim3(NP_LIGHT_THREADS), 0, st, w, bp, ct, p, list, n, nullptr, n_remove, chg, has, n_list, range_base);
     if (hl.host_only) return;
-    launch_np_heavy<T, true>(w, bp, ct, p, nullptr, n_remove, chg, has, n, st, hl.hook, hl.any());
+    launch_np_heavy<T, true>(w, bp, ct, p, nullptr, n_remove, chg, has, n, st, hl.hook, hl.any(), hl.capsules);
 }
 // the pairs the host answered (queries sorted by contact id on the host, manifolds in the same order): dense = the closed loop's chg / has outputs, else the change list
 template <class T> void launch_narrow_phase_host(const DW<T>& w, const BP<T>& bp, const CT<T>& ct, const StepParams<T>& p, bool dense, avn_contact_change* changes, uint32_t* n_changes,

@@ -72,11 +72,11 @@ __global__ __launch_bounds__(256) void k_sp_snapshot(DW<T> w, BP<T> bp, SP<T> sp
     sp.pos[c] = make4<T>(pos, T(0));
     sp.rot[c] = make4<T>(rot);
     sp.he[c] = make4<T>(h, T(0));
-    // a candidate has device geometry and a finite position, rotation and shape AABB; the others get an empty leaf box and never reach
-    // an exact test
+    // a candidate has device geometry for the queries (a capsule COLLIDER has none yet: it is left out as a host shape is) and a finite
+    // position, rotation and shape AABB; the others get an empty leaf box and never reach an exact test
     bool candidate = false;
     V3<T> mn{sp_inf<T>(), sp_inf<T>(), sp_inf<T>()}, mx{-sp_inf<T>(), -sp_inf<T>(), -sp_inf<T>()};
-    if (shape != AVN_SHAPE_HOST && is_finite(pos) && is_finite(V3<T>{rot.x, rot.y, rot.z}) && finite_t(rot.w)) {
+    if (shape != AVN_SHAPE_HOST && shape != AVN_SHAPE_CAPSULE && is_finite(pos) && is_finite(V3<T>{rot.x, rot.y, rot.z}) && finite_t(rot.w)) {
         V3<T> a, b;
         shape_aabb<T>(shape, h, pos, rot, a, b);
         if (is_finite(a) && is_finite(b)) {
@@ -338,11 +338,8 @@ template <class T, bool CAPSULE = false> __device__ __forceinline__ QShape<T> sp
     s.valid = (CAPSULE ? s.shape == AVN_SHAPE_CAPSULE : s.shape <= AVN_SHAPE_BALL) && is_finite(s.pos) && is_finite(V3<T>{s.rot.x, s.rot.y, s.rot.z}) && finite_t(s.rot.w) && is_finite(s.he) &&
               s.he.x >= T(0) && s.he.y >= T(0) && s.he.z >= T(0);
     if (s.valid) {
-        if (CAPSULE) {
-            const V3<T> hv = qrot(s.rot, V3<T>{T(0), s.he.y, T(0)});
-            const V3<T> ext = V3<T>{fabs_t(hv.x), fabs_t(hv.y), fabs_t(hv.z)} + V3<T>{s.he.x, s.he.x, s.he.x};
-            s.a = s.pos - ext; s.b = s.pos + ext;
-        } else shape_aabb<T>(s.shape, s.he, s.pos, s.rot, s.a, s.b);
+        if (CAPSULE) capsule_aabb<T>(s.he, s.pos, s.rot, s.a, s.b);
+        else shape_aabb<T>(s.shape, s.he, s.pos, s.rot, s.a, s.b);
         s.valid = is_finite(s.a) && is_finite(s.b);
     }
     return s;

@@ -358,8 +358,12 @@
         if (!p || !o || (p->count && (!p->shape1 || !p->shape2 || !p->half_extents1 || !p->half_extents2 || !p->position1 || !p->position2 ||
                                       !p->rotation1 || !p->rotation2 || !p->prediction_distance))) { error = "contact_manifolds: null array"; return AVN_ERR_BAD_ARG; }
         size_t n = p->count;
-        for (size_t i = 0; i < n; ++i)
-            if (p->shape1[i] > AVN_SHAPE_BALL || p->shape2[i] > AVN_SHAPE_BALL) { error = "contact_manifolds: unknown shape"; return AVN_ERR_BAD_ARG; }
+        bool capsules = false;   // (a batch with a capsule takes the kernel's CAP instantiation: avn_capsule_pair.h)
+        for (size_t i = 0; i < n; ++i) {
+            const uint8_t k1 = p->shape1[i], k2 = p->shape2[i];
+            if ((k1 > AVN_SHAPE_BALL && k1 != AVN_SHAPE_CAPSULE) || (k2 > AVN_SHAPE_BALL && k2 != AVN_SHAPE_CAPSULE)) { error = "contact_manifolds: unknown shape"; return AVN_ERR_BAD_ARG; }
+            capsules = capsules || k1 == AVN_SHAPE_CAPSULE || k2 == AVN_SHAPE_CAPSULE;
+        }
         const size_t Q = AVN_MAX_QUERY_POINTS;
         avn_status st = stage_reserve(al(n) * 3 + al(sizeof(T) * 3 * n) * 5 + al(sizeof(T) * 4 * n) * 2 + al(sizeof(T) * n) + al(sizeof(T) * 3 * Q * n) * 3 +
                                       al(sizeof(T) * Q * n) + al(4 * Q * n) * 2 + 64 * 32);
@@ -378,7 +382,7 @@
         s.penetration = o->penetration ? stage_alloc<T>(Q * n) : nullptr;
         s.feature_id1 = o->feature_id1 ? stage_alloc<uint32_t>(Q * n) : nullptr;
         s.feature_id2 = o->feature_id2 ? stage_alloc<uint32_t>(Q * n) : nullptr;
-        launch_contact_manifolds_query<T>(s, (uint32_t)n, stream);
+        launch_contact_manifolds_query<T>(s, (uint32_t)n, stream, capsules);
         HIPCHK(hipGetLastError());
         SOUT(o->point_count, s.point_count, n, uint8_t); SOUT(o->normal, s.normal, 3 * n, T);
         SOUT(o->anchor1, s.anchor1, 3 * Q * n, T); SOUT(o->anchor2, s.anchor2, 3 * Q * n, T); SOUT(o->point, s.point, 3 * Q * n, T);

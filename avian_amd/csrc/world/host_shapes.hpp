@@ -7,6 +7,7 @@
     avn_host_manifolds_fn hs_manifolds_fn = nullptr;
     void* hs_user = nullptr;
     std::vector<uint32_t> hs_slots;          // collider slots uploaded with AVN_SHAPE_HOST (upload order)
+    uint32_t cap_count = 0;                  // colliders uploaded with AVN_SHAPE_CAPSULE: the narrow phase takes its general (HS) instantiations, the spatial queries leave them out
     DevBuf b_hs_slots, b_hs_aq, b_hs_ab, b_hs_mq, b_hs_mm, b_hs_cnt;
     Pinned pin_hs, pin_hs_aabb;
     uint32_t hs_mq_cap = 0;
@@ -32,7 +33,8 @@
     // colliders_upload: which slots are the host's
     avn_status hs_on_colliders_upload(const avn_colliders* c) {
         hs_slots.clear();
-        for (uint32_t i = 0; i < c->count; ++i) if (c->shape[i] == AVN_SHAPE_HOST) hs_slots.push_back(i);
+        cap_count = 0;
+        for (uint32_t i = 0; i < c->count; ++i) { if (c->shape[i] == AVN_SHAPE_HOST) hs_slots.push_back(i); else if (c->shape[i] == AVN_SHAPE_CAPSULE) ++cap_count; }
         if (hs_slots.empty()) return AVN_OK;
         hipError_t err;
         const size_t n = hs_slots.size();
@@ -84,12 +86,14 @@
         const avn_status st = hk_begin(l, s);   // (collision hooks, world/hooks.hpp: phase 1 rides the same launches; a failure fails the step instead of skipping the hooks)
         if (st != AVN_OK) return st;
         l.locals = tf_any;                       // (child colliders: the HS instantiations compute their poses)
+        l.capsules = cap_count != 0;             // (capsule colliders: the HS heavy kernel computes their manifolds)
         *out = l;
         return AVN_OK;
     }
     NpHookList hk_phase1() const { NpHookList h; if (hk_modify_active() && b_hk_cnt.p) { h.count = b_hk_cnt.as<uint32_t>(); h.phase = 1; } return h; }
     NpHostList hs_list(uint32_t host_only = 0) const {
         NpHostList l;
+        l.capsules = cap_count != 0;
         if (!hs_any()) return l;
         l.queries = b_hs_mq.p; l.count = b_hs_cnt.as<uint32_t>(); l.cap = hs_mq_cap; l.host_only = host_only; l.locals = tf_any;
         return l;

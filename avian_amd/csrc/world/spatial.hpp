@@ -11,7 +11,7 @@
         b_mv_pend, b_mv_pcount;   // cast_move's hand-over: the colliders overlapping each query at its start [n * AVN_SPATIAL_MAX_HITS], their counts [n]
     uint32_t sp_cap = 0;
     bool sp_valid = false;      // a snapshot exists and no table changed since (bodies / colliders / collider transforms uploads and avn_despawn clear it)
-    uint32_t sp_host = 0;       // AVN_SHAPE_HOST colliders in the snapshot
+    uint32_t sp_host = 0;       // AVN_SHAPE_HOST and AVN_SHAPE_CAPSULE colliders in the snapshot: neither has device geometry for the queries
     unsigned long long sp_visits[3] = {0, 0, 0};   // last query call: node boxes tested, exact tests, stack overflow
 
     avn_status sp_grow(uint32_t C) {
@@ -43,7 +43,7 @@
         sp.n = C;
         launch_spatial_build<T>(dw, bp, sp, stream);
         HIPCHK(hipGetLastError());
-        sp_host = (uint32_t)hs_slots.size();
+        sp_host = (uint32_t)hs_slots.size() + cap_count;
         sp_valid = true;
         return AVN_OK;
     }
@@ -51,7 +51,7 @@
     avn_status sp_check(uint32_t flags) {
         if (!sp_valid) { error = "spatial query: no avn_spatial_update since the tables last changed"; return AVN_ERR_STATE; }
         if (sp_host && !(flags & AVN_SPATIAL_SKIP_HOST_SHAPES)) {
-            error = "spatial query: the snapshot holds AVN_SHAPE_HOST colliders, which have no device geometry (AVN_SPATIAL_SKIP_HOST_SHAPES leaves them out)";
+            error = "spatial query: the snapshot holds AVN_SHAPE_HOST or AVN_SHAPE_CAPSULE colliders, which the queries have no device geometry for (AVN_SPATIAL_SKIP_HOST_SHAPES leaves them out)";
             return AVN_ERR_STATE;
         }
         return AVN_OK;

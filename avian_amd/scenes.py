@@ -67,6 +67,58 @@ def cuboid_mass_properties(hx, hy, hz, density=1.0):
     return m, (ixx, iyy, izz)
 
 
+def capsule_mass_properties(radius, half_height, density=1.0):
+    """Volume-derived mass and principal inertia (about x, y, z; the axis is y) of a solid capsule: the cylinder of length 2 * half_height plus
+    the two hemispheres (each with its centre of mass 3r/8 from its flat face: 83/320 m r^2 about it, shifted to the capsule's centre)."""
+    r, h = radius, half_height
+    mc = density * np.pi * r * r * 2.0 * h
+    ms = density * 4.0 / 3.0 * np.pi * r ** 3
+    iyy = mc * r * r / 2.0 + ms * 2.0 * r * r / 5.0
+    ixx = mc * (r * r / 4.0 + (2.0 * h) ** 2 / 12.0) + ms * (2.0 * r * r / 5.0 + h * h + 3.0 * h * r / 4.0)
+    return mc + ms, (ixx, iyy, ixx)
+
+
+def capsule_drop(n: int, seed: int = 0, n_boxes: Optional[int] = None, n_balls: Optional[int] = None, radius: float = 0.25, half_height: float = 0.4,
+                 spacing: float = 0.9, layers: int = 3) -> Scene:
+    """`n` capsules (AVN_SHAPE_CAPSULE colliders, half_extents = (radius, half_height, 0)), `n_boxes` cuboids (default n // 3) and `n_balls` balls
+    (default n // 6) in shuffled order, tumbling from `layers` layers of a grid narrower than a capsule is long onto box_stack's ground slab
+    (body 0, top at y = 0): they collide with each other on the way down and end up lying on the ground.  Unit density."""
+    n_boxes = n // 3 if n_boxes is None else n_boxes
+    n_balls = n // 6 if n_balls is None else n_balls
+    rng = np.random.default_rng(seed)
+    m = n + n_boxes + n_balls
+    kind = np.concatenate([np.full(n, F.SHAPE_CAPSULE), np.full(n_boxes, F.SHAPE_CUBOID), np.full(n_balls, F.SHAPE_BALL)]).astype(np.uint8)
+    kind = kind[rng.permutation(m)]
+    per_layer = -(-m // layers)
+    side = int(np.ceil(np.sqrt(per_layer)))
+    N = m + 1
+    pos = np.zeros((N, 3)); pos[0] = (0.0, -20.0, 0.0)
+    he = np.zeros((N, 3)); he[0] = (400.0, 20.0, 400.0)
+    inv_mass = np.zeros(N); inv_i = np.zeros((N, 6))
+    box_h, ball_r = 0.15, 0.3   # (boxes lower than a lying capsule: one that ends up on a box still counts as lying on the ground, centre below r + 0.45)
+    for k in range(m):
+        layer, cell = divmod(k, per_layer)
+        pos[1 + k] = [(cell % side - (side - 1) * 0.5) * spacing + rng.uniform(-0.1, 0.1), 1.0 + 1.1 * layer + rng.uniform(0.0, 0.2),
+                      (cell // side - (side - 1) * 0.5) * spacing + rng.uniform(-0.1, 0.1)]
+        if kind[k] == F.SHAPE_CAPSULE:
+            he[1 + k] = (radius, half_height, 0.0)
+            mass, inertia = capsule_mass_properties(radius, half_height)
+        elif kind[k] == F.SHAPE_CUBOID:
+            he[1 + k] = (box_h, box_h, box_h)
+            mass, inertia = cuboid_mass_properties(box_h, box_h, box_h)
+        else:
+            he[1 + k] = (ball_r, ball_r, ball_r)
+            mass = 4.0 / 3.0 * np.pi * ball_r ** 3
+            inertia = (0.4 * mass * ball_r * ball_r,) * 3
+        inv_mass[1 + k] = 1.0 / mass
+        inv_i[1 + k, 0], inv_i[1 + k, 3], inv_i[1 + k, 5] = 1.0 / inertia[0], 1.0 / inertia[1], 1.0 / inertia[2]
+    rot = rng.normal(size=(N, 4)); rot /= np.linalg.norm(rot, axis=1, keepdims=True); rot[0] = (0.0, 0.0, 0.0, 1.0)
+    rb = np.zeros(N, np.uint8); rb[0] = F.RB_STATIC
+    dyn = (rb == 0)[:, None]
+    shape = np.concatenate([[F.SHAPE_CUBOID], kind]).astype(np.uint8)
+    return Scene(pos, rot, rng.normal(scale=0.3, size=(N, 3)) * dyn, rng.normal(scale=1.0, size=(N, 3)) * dyn, inv_mass, inv_i, rb, he, shape, friction=0.6)
+
+
 def _assemble(centers, half, ground_center, ground_half) -> Scene:
     """Static ground (body 0) + dynamic unit-density cuboids."""
     n = len(centers) + 1

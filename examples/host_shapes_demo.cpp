@@ -5,6 +5,9 @@
 // the library's closed loop, and the boxes never leave the device.  Boxes and capsules are on different collision layers (no capsule-box manifold is implemented here).
 //
 //   examples/host_shapes_demo [nx ny nz] [capsules] [steps]      prints ms per step with and without the capsules and what crossed the bus
+//   examples/host_shapes_demo nx ny nz capsules steps native     the same capsules uploaded as AVN_SHAPE_CAPSULE colliders instead: the device owns them, no
+//                                                                callback runs.  TIMING ONLY: the callbacks above are a simpler geometry than the native definition
+//                                                                (ends against the ground plane, one point between capsules), so the two worlds are not compared.
 #include <algorithm>
 #include <chrono>
 #include <cmath>
@@ -14,6 +17,7 @@
 #include <vector>
 
 #include "avian_mi355x.h"
+#include "avian_mi355x_spatial.h"   // AVN_SHAPE_CAPSULE
 
 #define CHECK(call)                                                                                         \
     do {                                                                                                    \
@@ -103,7 +107,7 @@ static avn_config config() {
 }
 
 // one world: the box stack and `n_caps` capsules lying in a grid beside it; returns ms per step over the last `timed` steps
-static int run(int nx, int ny, int nz, uint32_t n_caps, int steps, int timed, double* ms_out, avn_host_shape_stats* stats_out, float* worst_y_error) {
+static int run(int nx, int ny, int nz, uint32_t n_caps, int steps, int timed, double* ms_out, avn_host_shape_stats* stats_out, float* worst_y_error, bool native = false) {
     const uint32_t n_box = (uint32_t)(nx * ny * nz), n = 1u + n_box + n_caps;
     avn_config cfg = config();
     avn_world* world = nullptr;
@@ -128,6 +132,7 @@ static int run(int nx, int ny, int nz, uint32_t n_caps, int steps, int timed, do
         const float ang_z = 1.5707963f + 0.1f * (float)((c * 7u) % 5u) - 0.2f;   // local y (the capsule's axis) turned towards world x
         rot[4 * b + 2] = std::sin(0.5f * ang_z); rot[4 * b + 3] = std::cos(0.5f * ang_z);
         shape[b] = AVN_SHAPE_HOST; he[3 * b] = he[3 * b + 1] = he[3 * b + 2] = 0.f;
+        if (native) { shape[b] = AVN_SHAPE_CAPSULE; he[3 * b] = caps.radius; he[3 * b + 1] = caps.half_height; }   // half_extents = (r, h, .)
         member[b] = 4u; filter[b] = 1u | 4u;
         inv_m[b] = 1.f / vol;
         const float iy = 0.5f * vol * caps.radius * caps.radius, ix = vol * (3.f * caps.radius * caps.radius + 4.f * caps.half_height * caps.half_height) / 12.f + 0.3f * vol * caps.half_height * caps.half_height;
@@ -144,7 +149,7 @@ static int run(int nx, int ny, int nz, uint32_t n_caps, int steps, int timed, do
     CHECK(avn_existing_pairs_upload(world, nullptr, 0));
     avn_collider_materials mats; std::memset(&mats, 0, sizeof mats); mats.count = n;
     CHECK(avn_collider_materials_upload(world, &mats));
-    if (n_caps) CHECK(avn_host_shapes_set(world, capsule_aabbs, capsule_manifolds, &caps));
+    if (n_caps && !native) CHECK(avn_host_shapes_set(world, capsule_aabbs, capsule_manifolds, &caps));
     CHECK(avn_pipeline_enable(world, 1));
     for (int s = 0; s < steps - timed; ++s) CHECK(avn_step(world));
     CHECK(avn_synchronize(world));
@@ -169,13 +174,16 @@ int main(int argc, char** argv) {
     const int nx = argc > 3 ? std::atoi(argv[1]) : 12, ny = argc > 3 ? std::atoi(argv[2]) : 10, nz = argc > 3 ? std::atoi(argv[3]) : 12;
     const uint32_t n_caps = argc > 4 ? (uint32_t)std::atoi(argv[4]) : 400u;
     const int steps = argc > 5 ? std::atoi(argv[5]) : 120, timed = std::min(steps, 20);
+    const bool native = argc > 6 && std::strcmp(argv[6], "native") == 0;
     double ms_boxes = 0, ms_both = 0; avn_host_shape_stats s0, s1; float e0 = 0, e1 = 0;
-    std::printf("host shapes demo: capsules implemented in this file (AnyCollider callbacks), boxes in device kernels\n");
+    std::printf(native ? "host shapes demo, native: capsules as AVN_SHAPE_CAPSULE colliders, capsules and boxes in device kernels\n"
+                       : "host shapes demo: capsules implemented in this file (AnyCollider callbacks), boxes in device kernels\n");
     int rc = run(nx, ny, nz, 0u, steps, timed, &ms_boxes, &s0, &e0);
     if (rc) return rc;
-    if ((rc = run(nx, ny, nz, n_caps, steps, timed, &ms_both, &s1, &e1))) return rc;
+    if ((rc = run(nx, ny, nz, n_caps, steps, timed, &ms_both, &s1, &e1, native))) return rc;
     std::printf("  the capsules cost %.3f ms per step (%.1f us per capsule); worst |centre height - radius| of a capsule: %.4f\n", ms_both - ms_boxes, n_caps ? 1e3 * (ms_both - ms_boxes) / n_caps : 0.0, e1);
-    const bool ok = s1.host_colliders == n_caps && s1.last_aabb_queries == n_caps && s1.last_manifold_queries >= n_caps && e1 < 0.05f && s0.host_colliders == 0;
+    const bool ok = native ? (s1.host_colliders == 0 && s1.last_manifold_queries == 0 && e1 < 0.05f && s0.host_colliders == 0)
+                           : (s1.host_colliders == n_caps && s1.last_aabb_queries == n_caps && s1.last_manifold_queries >= n_caps && e1 < 0.05f && s0.host_colliders == 0);
     std::printf(ok ? "HOST_SHAPES_DEMO_OK\n" : "HOST_SHAPES_DEMO_FAILED\n");
     return ok ? 0 : 3;
 }

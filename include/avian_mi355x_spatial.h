@@ -120,8 +120,9 @@
  *      applies PhysicsLengthUnit to max_depenetration_error and penetration_rejection_threshold.
  *    NOT covered: query shapes other than Ball / Cuboid / Capsule (cylinders, cones, hulls), contacts against AVN_SHAPE_HOST colliders, predicates, Rust declarations.
  *  - capsule query shapes (AVN_SHAPE_CAPSULE; parry's Capsule::new_y, the shape of Avian's character-controller examples).  A capsule is a
- *    QUERY shape only: every entry point that takes a query shape accepts it against Ball and Cuboid colliders; colliders stay Ball /
- *    Cuboid / Host.  half_extents = (r, h, .): x the radius (as a ball keeps its radius in x), y the half length of the segment (0, -h, 0) ..
+ *    QUERY shape here: every entry point that takes a query shape accepts it against Ball and Cuboid colliders.  (A capsule COLLIDER --
+ *    avian_mi355x.h "capsule colliders" -- is to these queries what a host shape is: AVN_ERR_STATE unless AVN_SPATIAL_SKIP_HOST_SHAPES is set, then
+ *    never a candidate and counted in host_skipped.  Rays and casts against capsule colliders are not built.)  half_extents = (r, h, .): x the radius (as a ball keeps its radius in x), y the half length of the segment (0, -h, 0) ..
  *    (0, +h, 0) of the shape's frame, z not read; Collider::capsule(radius, length) is r = radius, h = length / 2.  Valid: finite r and h,
  *    both >= 0 (h == 0 is a ball, r == 0 a segment, both 0 a point), the usual finite pose, and a finite AABB
  *      [a, b] = position -+ (|qrot(rotation, (0, h, 0))| + (r, r, r))   per component (qrot: the function collider_pose uses),
@@ -289,8 +290,9 @@
 extern "C" {
 #endif
 
-/* A query-shape kind of this header only: a capsule (the segment (0, -h, 0) .. (0, +h, 0) swept by a ball of radius r; half_extents = (r, h, .)).
- * It is not a collider kind: avn_colliders_upload, avn_contact_manifolds and the swept CCD keep treating the value as they always have. */
+/* A capsule (the segment (0, -h, 0) .. (0, +h, 0) swept by a ball of radius r; half_extents = (r, h, .)): a query-shape kind of this header and, on the HIP
+ * backend, a collider kind (avian_mi355x.h "capsule colliders": avn_colliders_upload, avn_contact_manifolds).  The spatial queries of this header have no
+ * geometry for capsule COLLIDERS yet: a snapshot treats them as host shapes.  The swept CCD skips them. */
 enum { AVN_SHAPE_CAPSULE = 3 };
 
 /* flags of a query */
