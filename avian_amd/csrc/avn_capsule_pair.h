@@ -9,10 +9,8 @@
 
 namespace avn {
 
-template <class T> __device__ __forceinline__ T cp_clamp01(T x) { return x < T(0) ? T(0) : (x > T(1) ? T(1) : x); }
 template <class T> __device__ __forceinline__ V3<T> cp_set(V3<T> v, int i, T x) { return V3<T>{i == 0 ? x : v.x, i == 1 ? x : v.y, i == 2 ? x : v.z}; }
-// sin^2 of the angle under which two capsule axes count as parallel (two-point manifold): parallel to rounding, not a tuning knob
-template <class T> __device__ __forceinline__ T cp_parallel() { return Limits<T>::eps * T(64); }
+// (cp_clamp01, cp_parallel and the closest points of two segments, sp_seg_seg: avn_spatial_pair.h)
 
 // pos12: shape 2 in shape 1's frame (of the two make_isometry poses); em.rotation1 / em.sink are set.  Sets em.normal and pushes the points;
 // false = no manifold (the caller also drops a manifold without points).
@@ -25,22 +23,9 @@ __device__ bool capsule_pair_manifold(uint32_t shape1, V3<T> he1, uint32_t shape
         const V3<T> A1{T(0), -he1.y, T(0)}, u1{T(0), he1.y * T(2), T(0)};
         V3<T> A2, u2;
         sp_capsule_core<T>(pos12, he2.y, A2, u2);
-        const V3<T> w = A1 - A2;
-        const T a = na_dot(u1, u1), e = na_dot(u2, u2), f = na_dot(u2, w), c = na_dot(u1, w), b = na_dot(u1, u2);
-        T s = T(0), t = T(0);
-        bool par = false;
-        if (a == T(0) && e == T(0)) {}                       // two points
-        else if (a == T(0)) t = cp_clamp01<T>(f / e);        // segment 1 is a point
-        else if (e == T(0)) s = cp_clamp01<T>(-c / a);       // segment 2 is a point
-        else {
-            const T ae = a * e;
-            const T den = ae - b * b;
-            par = !(den > cp_parallel<T>() * ae);
-            s = par ? T(0) : cp_clamp01<T>((b * f - c * e) / den);
-            t = (b * s + f) / e;
-            if (t < T(0)) { t = T(0); s = cp_clamp01<T>(-c / a); }
-            else if (t > T(1)) { t = T(1); s = cp_clamp01<T>((b - c) / a); }
-        }
+        const SegSeg<T> ss = sp_seg_seg<T>(A1, u1, A2, u2);
+        const T a = ss.a, e = ss.e, f = ss.f, c = ss.c, b = ss.b, s = ss.s, t = ss.t;
+        const bool par = ss.par;
         if (par) {
             // parallel axes: segment 2's ends projected onto segment 1's parameter; an overlap [lo, hi] with lo < hi gives two points
             const T sa = -c / a, sb = (b - c) / a;

@@ -560,14 +560,14 @@ template <class T> struct SL {
 };
 template <class T> void launch_spatial_project_velocity(const SV<T>&, hipStream_t);
 // capsule (here and below): the call may hold AVN_SHAPE_CAPSULE query shapes, so the kernels' CAPSULE instantiations run behind the first launch
-template <class T> void launch_spatial_cast_move(const SP<T>&, const SM<T>&, bool zero_stats, hipStream_t, bool capsule = false);
+template <class T> void launch_spatial_cast_move(const SP<T>&, const SM<T>&, bool zero_stats, hipStream_t, bool capsule = false, bool ccap = false);
 template <class T> void launch_spatial_slide_phase(const SL<T>&, int phase, hipStream_t);
-template <class T> void launch_spatial_build(const DW<T>&, const BP<T>&, const SP<T>&, hipStream_t);
-template <class T> void launch_spatial_query(const SP<T>&, const SQ<T>&, int kind, hipStream_t, bool capsule = false);
+template <class T> void launch_spatial_build(const DW<T>&, const BP<T>&, const SP<T>&, hipStream_t, bool ccap = false);
+template <class T> void launch_spatial_query(const SP<T>&, const SQ<T>&, int kind, hipStream_t, bool capsule = false, bool ccap = false);
 template <class T> void launch_spatial_reaim(const DW<T>&, const SP<T>&, const SCA<T>&, hipStream_t);
 // a caster group: kind SPQ_CLOSEST / SPQ_HITS / SPQ_CAST / SPQ_CAST_HITS with the per-query filter; q.stats is NOT zeroed (the run zeroes it once)
-template <class T> void launch_spatial_casters(const SP<T>&, const SQ<T>&, int kind, hipStream_t, bool capsule = false);
-template <class T> void launch_spatial_contacts(const SP<T>&, const SC<T>&, hipStream_t, bool zero_stats = true, bool capsule = false);
+template <class T> void launch_spatial_casters(const SP<T>&, const SQ<T>&, int kind, hipStream_t, bool capsule = false, bool ccap = false);
+template <class T> void launch_spatial_contacts(const SP<T>&, const SC<T>&, hipStream_t, bool zero_stats = true, bool capsule = false, bool ccap = false);
 template <class T> void launch_spatial_depenetrate(const SD<T>&, hipStream_t);
 
 // ---- k_ccd.hip: swept CCD (solve_swept_ccd, dynamics/ccd/mod.rs:523-687; include/avian_mi355x_ccd.h) as a pass over the contact rows ----

@@ -1,7 +1,8 @@
 // avn_spatial_pair.h — the per-pair device functions of the shape casts and of the origin-penetration rule (include/avian_mi355x_spatial.h
 // "shape cast", "shape contacts"): shared by the spatial queries (k_spatial.hip) and the swept CCD pass (k_ccd.hip).  The header defines
 // the per-pair tests, operation order included; tests/spatial_cast_reference.py does the same operations in order.  The capsule query
-// shape's pair tests (the spatial queries only) are at the end: tests/spatial_capsule_reference.py.
+// shape's pair tests (the spatial queries only) follow: tests/spatial_capsule_reference.py.  The capsule COLLIDER's pair tests of the spatial
+// queries (the CCAP instantiations of k_spatial.hip) are at the end: tests/spatial_capsule_collider_reference.py.
 #pragma once
 #include "avn_kernels.h"
 #include "avn_narrow.h"
@@ -285,6 +286,67 @@ template <class T> __device__ __forceinline__ T sp_seg_point(V3<T> A, V3<T> u, V
     s_out = s;
     return na_dot(e, e);
 }
+template <class T> __device__ __forceinline__ T cp_clamp01(T x) { return x < T(0) ? T(0) : (x > T(1) ? T(1) : x); }
+// sin^2 of the angle under which two capsule axes count as parallel (two-point manifold): parallel to rounding, not a tuning knob
+template <class T> __device__ __forceinline__ T cp_parallel() { return Limits<T>::eps * T(64); }
+// segment - segment: the clamped closest points A1 + s u1, A2 + t u2 with the dot products they came from.  par: both segments have a length
+// and their axes count as parallel (s = 0 is tried first; the capsule manifold then looks for an overlap).  ONE routine for the capsule
+// collider's manifold (avn_capsule_pair.h) and the spatial queries of a capsule against a capsule collider (below).
+template <class T> struct SegSeg { T a, e, f, c, b, s, t; bool par; };
+template <class T> __device__ __forceinline__ SegSeg<T> sp_seg_seg(V3<T> A1, V3<T> u1, V3<T> A2, V3<T> u2) {
+    const V3<T> w = A1 - A2;
+    const T a = na_dot(u1, u1), e = na_dot(u2, u2), f = na_dot(u2, w), c = na_dot(u1, w), b = na_dot(u1, u2);
+    T s = T(0), t = T(0);
+    bool par = false;
+    if (a == T(0) && e == T(0)) {}                       // two points
+    else if (a == T(0)) t = cp_clamp01<T>(f / e);        // segment 1 is a point
+    else if (e == T(0)) s = cp_clamp01<T>(-c / a);       // segment 2 is a point
+    else {
+        const T ae = a * e;
+        const T den = ae - b * b;
+        par = !(den > cp_parallel<T>() * ae);
+        s = par ? T(0) : cp_clamp01<T>((b * f - c * e) / den);
+        t = (b * s + f) / e;
+        if (t < T(0)) { t = T(0); s = cp_clamp01<T>(-c / a); }
+        else if (t > T(1)) { t = T(1); s = cp_clamp01<T>((b - c) / a); }
+    }
+    return SegSeg<T>{a, e, f, c, b, s, t, par};
+}
+// The squared distance of two segments for the QUERIES, with the two points.  sp_seg_seg's quotient (b f - c e) / den cancels for nearly parallel
+// axes (its s is wrong by about eps / sin^2), and under its parallel rule s is simply 0: good enough for the manifold, which then looks for an
+// overlap, but an over-estimate of the distance of converging or crossing cores.  So six candidate pairs are evaluated in full, in this order, and
+// the first with the smallest |p2 - p1|^2 wins (strict <; a NaN candidate never wins): sp_seg_seg's (s, t); the interior point in its
+// well-conditioned form -- with u2p = u2 - u1 (b / a) and wp = w - u1 (c / a), the parts perpendicular to u1: t = clamp(dot(wp, u2p) / dot(u2p, u2p)),
+// s = clamp((b t - c) / a), t = clamp((b s + f) / e) --; and the four ends against the other segment: (0, clamp(f / e)), (1, clamp((b + f) / e)),
+// (clamp(-c / a), 0), (clamp((b - c) / a), 1).  The minimum of the convex distance over the square is the interior point or lies on an edge, so
+// this is exact up to rounding.  capsule_pair_manifold does not come here: its bits are sp_seg_seg's.
+template <class T> __device__ __forceinline__ void sp_seg_seg_try(V3<T> A1, V3<T> u1, V3<T> A2, V3<T> u2, T s, T t, T& best, V3<T>& p1, V3<T>& p2) {
+    const V3<T> q1 = A1 + u1 * s, q2 = A2 + u2 * t;
+    const V3<T> d = q2 - q1;
+    const T d2 = na_dot(d, d);
+    if (d2 < best) { best = d2; p1 = q1; p2 = q2; }
+}
+template <class T> __device__ __forceinline__ T sp_seg_seg_d2(V3<T> A1, V3<T> u1, V3<T> A2, V3<T> u2, V3<T>& p1, V3<T>& p2) {
+    const SegSeg<T> ss = sp_seg_seg<T>(A1, u1, A2, u2);
+    const T a = ss.a, e = ss.e, f = ss.f, c = ss.c, b = ss.b;
+    T best = sp_inf<T>();
+    p1 = A1 + u1 * ss.s; p2 = A2 + u2 * ss.t;   // (what stands when every candidate is NaN: non-finite inputs)
+    sp_seg_seg_try<T>(A1, u1, A2, u2, ss.s, ss.t, best, p1, p2);
+    {
+        const V3<T> w = A1 - A2;
+        const V3<T> u2p = u2 - u1 * (b / a), wp = w - u1 * (c / a);
+        T t = cp_clamp01<T>(na_dot(wp, u2p) / na_dot(u2p, u2p));
+        const T s = cp_clamp01<T>((b * t - c) / a);
+        t = cp_clamp01<T>((b * s + f) / e);
+        sp_seg_seg_try<T>(A1, u1, A2, u2, s, t, best, p1, p2);
+    }
+    sp_seg_seg_try<T>(A1, u1, A2, u2, T(0), cp_clamp01<T>(f / e), best, p1, p2);
+    sp_seg_seg_try<T>(A1, u1, A2, u2, T(1), cp_clamp01<T>((b + f) / e), best, p1, p2);
+    sp_seg_seg_try<T>(A1, u1, A2, u2, cp_clamp01<T>(-c / a), T(0), best, p1, p2);
+    sp_seg_seg_try<T>(A1, u1, A2, u2, cp_clamp01<T>((b - c) / a), T(1), best, p1, p2);
+    const V3<T> d = p2 - p1;
+    return na_dot(d, d);
+}
 // segment - box, exact.  f(s) = sum_i max(|x_i(s)| - he_i, 0)^2 is convex and piecewise quadratic; its breakpoints are the s = (+-he_i - A_i) / u_i
 // strictly inside (0, 1) (one that is not counts as 1).  Candidates, in this order: 0, 1, the six breakpoints ascending (a 12-comparator
 // network), then per interval between neighbours of 0 <= b_1 <= .. <= b_6 <= 1 the minimiser of the quadratic whose active faces are read at
@@ -396,6 +458,28 @@ template <class T> __device__ __forceinline__ bool sp_capsule_ray(V3<T> o, V3<T>
 }
 
 #define SP_CAPSULE_ROUNDS 32
+// Newton's iteration on g(t) = dist(t) - R from t = 0, which rises monotonically to the root from its left (g is convex): closest(t, a, b)
+// answers the squared distance of the moving core displaced by dl t (its point a) from the fixed one (its point b).  At most SP_CAPSULE_ROUNDS
+// evaluations, the last t standing.  n: from b towards a; pen: the cores are within R at t = 0.  false = a miss.
+template <class T, class Closest>
+__device__ __forceinline__ bool sp_newton_cast(Closest closest, V3<T> dl, T R, T max_distance, T& t, V3<T>& n, V3<T>& pm, V3<T>& pf, bool& pen) {
+    n = vzero<T>(); pm = vzero<T>(); pf = vzero<T>();
+    bool hit = false;
+    for (int k = 0; k < SP_CAPSULE_ROUNDS; ++k) {
+        V3<T> a, b;
+        const T dist = sqrt_t(closest(t, a, b));
+        if (dist > T(0)) n = (a - b) / dist;   // (dist == 0, touching cores arriving: the round before's direction stands)
+        pm = a; pf = b;
+        if (dist <= R) { pen = k == 0; hit = true; break; }
+        const T v = -na_dot(n, dl);
+        if (!(v > T(0))) return false;
+        const T tn = t + (dist - R) / v;
+        if (tn > max_distance) return false;
+        if (!(tn > t) || k == SP_CAPSULE_ROUNDS - 1) { hit = true; break; }
+        t = tn;
+    }
+    return hit;
+}
 // The cast of the capsule (r, h) at pose iso2 along d against one collider.  A ball collider: its centre as a ray against the capsule grown by
 // the ball's radius, in the capsule's frame with the ray reversed.  A cuboid: Newton's iteration on g(t) = dist(segment + t dl, box) - r
 // from t = 0, which rises monotonically to the root from its left (g is convex); at most SP_CAPSULE_ROUNDS evaluations, the last t standing.
@@ -426,21 +510,9 @@ __device__ __forceinline__ bool sp_capsule_cast_exact(T r, T h, const Iso<T>& is
     } else {
         V3<T> A, u;
         sp_capsule_core<T>(q, h, A, u);
-        V3<T> n = vzero<T>(), ps = vzero<T>(), pb = vzero<T>();
-        bool hit = false;
-        for (int k = 0; k < SP_CAPSULE_ROUNDS; ++k) {
-            const SegBox<T> sb = sp_seg_box<T>(A + dl * t, u, he1);
-            const T dist = sqrt_t(sb.f);
-            if (dist > T(0)) n = (sb.ps - sb.pb) / dist;   // (dist == 0, a segment query r = 0 arriving: the round before's direction stands)
-            ps = sb.ps; pb = sb.pb;
-            if (dist <= r) { pen = k == 0; hit = true; break; }
-            const T v = -na_dot(n, dl);
-            if (!(v > T(0))) return false;
-            const T tn = t + (dist - r) / v;
-            if (tn > max_distance) return false;
-            if (!(tn > t) || k == SP_CAPSULE_ROUNDS - 1) { hit = true; break; }
-            t = tn;
-        }
+        V3<T> n, ps, pb;
+        const bool hit = sp_newton_cast<T>([&](T tt, V3<T>& a, V3<T>& b) { const SegBox<T> sb = sp_seg_box<T>(A + dl * tt, u, he1); a = sb.ps; b = sb.pb; return sb.f; },
+                                           dl, r, max_distance, t, n, ps, pb, pen);
         if (!hit || !(t <= max_distance) || !finite_t(t)) return false;
         if (!pen) {
             wn = na_qrot(rot1, n);
@@ -539,5 +611,151 @@ template <class T> struct SpDeepestSink {
         ++count;
     }
 };
+
+// ---------------------------------------------------------------------------------------------------------
+// The capsule as a COLLIDER of the spatial queries (include/avian_mi355x_spatial.h "queries against capsule colliders"; the CCAP
+// instantiations of k_spatial.hip): (r_c, h_c) = (he.x, he.y), the core segment (0, -h_c, 0) .. (0, +h_c, 0) of its own frame.  The header
+// defines the tests, operation order included; tests/spatial_capsule_collider_reference.py does the same operations in order.
+template <class T> __device__ __forceinline__ void sp_capcol_core(T h, V3<T>& A, V3<T>& u) {
+    A = V3<T>{T(0), -h, T(0)};
+    u = V3<T>{T(0), h * T(2), T(0)};
+}
+// The exit of the ray (o, d), whose origin is inside the capsule (R, h), in the capsule's frame: the cylinder's far root where |y| <= h, then
+// the far roots of the end spheres at -h and +h; the largest wins (strict >), its primitive gives the outward normal.
+template <class T> __device__ __forceinline__ bool sp_capsule_ray_exit(V3<T> o, V3<T> d, T h, T R, T& t_out, V3<T>& n_out) {
+    T best = -sp_inf<T>();
+    V3<T> bn = vzero<T>();
+    {
+        const T a = d.x * d.x + d.z * d.z;
+        const T b = o.x * d.x + o.z * d.z;
+        const T q = b / a;
+        const T fa = o.x - d.x * q, fb = o.z - d.z * q;
+        const T delta = a * (R * R - (fa * fa + fb * fb));
+        const T t = (-b + sqrt_t(delta)) / a;
+        const T y = o.y + d.y * t;
+        if (a > T(0) && !(delta < T(0)) && fabs_t(y) <= h) {
+            best = t;
+            const T pa = o.x + d.x * t, pb = o.z + d.z * t;
+            const T l = sqrt_t(pa * pa + pb * pb);
+            bn = l > T(0) ? V3<T>{pa / l, T(0), pb / l} : vzero<T>();
+        }
+    }
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+        const V3<T> oc{o.x, e == 0 ? o.y + h : o.y - h, o.z};
+        const T a = dot(d, d), b = dot(oc, d);
+        const V3<T> f = oc - d * (b / a);
+        const T delta = a * (R * R - dot(f, f));
+        if (delta < T(0)) continue;
+        const T t = (-b + sqrt_t(delta)) / a;
+        if (t > best) {
+            best = t;
+            const V3<T> p = oc + d * t;
+            const T l = length(p);
+            bn = l > T(0) ? p / l : vzero<T>();
+        }
+    }
+    if (!(best > -sp_inf<T>())) return false;
+    t_out = best; n_out = bn;
+    return true;
+}
+// The local ray (ol, dl) against the capsule collider: the entry by sp_capsule_ray with R = r_c; an origin inside answers distance 0 and no
+// normal when solid, the exit otherwise.  nl: the outward surface normal in the capsule's frame, zero when there is none.
+template <class T> __device__ __forceinline__ bool sp_capcol_ray(V3<T> he, V3<T> ol, V3<T> dl, bool solid, T& t, V3<T>& nl) {
+    bool pen;
+    if (!sp_capsule_ray<T>(ol, dl, he.y, he.x, t, nl, pen)) return false;
+    if (pen && !solid && !sp_capsule_ray_exit<T>(ol, dl, he.y, he.x, t, nl)) return false;
+    return true;
+}
+template <class T> __device__ __forceinline__ bool sp_capcol_point(V3<T> he, V3<T> pl) {
+    V3<T> A, u;
+    sp_capcol_core<T>(he.y, A, u);
+    T s;
+    return sp_seg_point<T>(A, u, pl, s) <= he.x * he.x;
+}
+// the ball's projection rule about the nearest core point pc: inside = d^2 <= r_c^2; a point on the core goes to pc + (0, r_c, 0)
+template <class T> __device__ __forceinline__ void sp_capcol_project(V3<T> he, V3<T> pl, bool solid, V3<T>& proj, bool& inside) {
+    V3<T> A, u;
+    sp_capcol_core<T>(he.y, A, u);
+    const T r = he.x;
+    T s;
+    const T d2 = sp_seg_point<T>(A, u, pl, s);
+    const V3<T> pc = A + u * s;
+    inside = d2 <= r * r;
+    if (!(solid && inside)) proj = d2 == T(0) ? pc + V3<T>{T(0), r, T(0)} : pc + (pl - pc) * (r / sqrt_t(d2));
+}
+// Intersection of the query shape (shape2, he2, iso2) with the capsule collider.  A ball or a cuboid: sp_capsule_intersects with the roles
+// exchanged (the collider is the capsule, posed in the query's frame).  CAPSULE (a capsule query): the two cores by sp_seg_seg in the collider's
+// frame, the collider's as segment 1; d^2 <= (r_q + r_c)^2.
+template <class T, bool CAPSULE>
+__device__ __forceinline__ bool sp_capcol_intersects(uint32_t shape2, V3<T> he2, const Iso<T>& iso2, V3<T> he1, V3<T> pos1, Q4<T> rot1) {
+    if (!CAPSULE) return sp_capsule_intersects<T>(he1.x, he1.y, iso_inv_mul(iso2, Iso<T>{rot1, pos1}), shape2, he2);
+    const Iso<T> q = iso_inv_mul(Iso<T>{rot1, pos1}, iso2);
+    V3<T> A1, u1, A2, u2, p1, p2;
+    sp_capcol_core<T>(he1.y, A1, u1);
+    sp_capsule_core<T>(q, he2.y, A2, u2);
+    const T d2 = sp_seg_seg_d2<T>(A1, u1, A2, u2, p1, p2);
+    const T rr = he2.x + he1.x;
+    return d2 <= rr * rr;
+}
+// The cast of the query shape (shape2, he2, pose iso2) along d against the capsule collider (he1 = (r_c, h_c, .)).  A ball: its centre as a
+// ray against the capsule grown by the ball's radius, in the collider's frame.  A cuboid: sp_newton_cast in the QUERY's frame, the collider's
+// core moving by -d against the box.  CAPSULE: sp_newton_cast in the collider's frame on the two cores (sp_seg_seg), R = r_q + r_c.
+// Same answer as sp_cast_exact: p1 / n1 the collider's, p2 the query's at the impact pose; everything zero when the shapes overlap at the start.
+template <class T, bool CAPSULE>
+__device__ __forceinline__ bool sp_capcol_cast_exact(uint32_t shape2, V3<T> he2, const Iso<T>& iso2, V3<T> d, T max_distance, V3<T> he1, V3<T> pos1, Q4<T> rot1,
+                                                     T& toi, V3<T>& p1, V3<T>& p2, V3<T>& n1) {
+    const T rc = he1.x, hc = he1.y;
+    T t = T(0);
+    bool pen = false;
+    V3<T> w1 = vzero<T>(), w2 = vzero<T>(), wn = vzero<T>();
+    if (CAPSULE) {
+        const Iso<T> q = iso_inv_mul(Iso<T>{rot1, pos1}, iso2);
+        const V3<T> dl = na_qrot(qinverse(rot1), d);
+        V3<T> A1, u1, A2, u2;
+        sp_capcol_core<T>(hc, A1, u1);
+        sp_capsule_core<T>(q, he2.y, A2, u2);
+        V3<T> n, pq, pc;
+        const bool hit = sp_newton_cast<T>([&](T tt, V3<T>& a, V3<T>& b) { return sp_seg_seg_d2<T>(A1, u1, A2 + dl * tt, u2, b, a); }, dl, he2.x + rc, max_distance, t, n, pq, pc, pen);
+        if (!hit || !(t <= max_distance) || !finite_t(t)) return false;
+        if (!pen) {
+            wn = na_qrot(rot1, n);
+            w1 = na_qrot(rot1, pc + n * rc) + pos1;
+            w2 = na_qrot(rot1, pq - n * he2.x) + pos1;
+        }
+    } else if (shape2 == AVN_SHAPE_BALL) {
+        const Iso<T> q = iso_inv_mul(Iso<T>{rot1, pos1}, iso2);
+        const V3<T> dl = na_qrot(qinverse(rot1), d);
+        V3<T> n;
+        if (!sp_capsule_ray<T>(q.t, dl, hc, rc + he2.x, t, n, pen)) return false;
+        if (!(t <= max_distance) || !finite_t(t)) return false;
+        if (!pen) {
+            const V3<T> c2 = iso2.t + d * t;
+            const V3<T> pb = q.t + dl * t;   // the ball's centre at the impact, in the collider's frame
+            const T ys = pb.y < -hc ? -hc : (pb.y > hc ? hc : pb.y);
+            const V3<T> pk = V3<T>{T(0), ys, T(0)} + n * rc;
+            wn = na_qrot(rot1, n);
+            w1 = na_qrot(rot1, pk) + pos1;
+            w2 = c2 + (-wn) * he2.x;
+        }
+    } else {
+        const Iso<T> qc = iso_inv_mul(iso2, Iso<T>{rot1, pos1});   // the collider in the query's frame
+        const V3<T> dm = -iso_inv_vec(iso2, d);
+        V3<T> A, u;
+        sp_capsule_core<T>(qc, hc, A, u);
+        V3<T> n, ps, pb;
+        const bool hit = sp_newton_cast<T>([&](T tt, V3<T>& a, V3<T>& b) { const SegBox<T> sb = sp_seg_box<T>(A + dm * tt, u, he2); a = sb.ps; b = sb.pb; return sb.f; },
+                                           dm, rc, max_distance, t, n, ps, pb, pen);
+        if (!hit || !(t <= max_distance) || !finite_t(t)) return false;
+        if (!pen) {
+            const V3<T> c2 = iso2.t + d * t;
+            wn = -na_qrot(iso2.r, n);
+            w1 = na_qrot(iso2.r, ps - n * rc) + c2;
+            w2 = na_qrot(iso2.r, pb) + c2;
+        }
+    }
+    toi = t; p1 = w1; p2 = w2; n1 = wn;
+    return true;
+}
 
 }  // namespace avn

@@ -3,7 +3,9 @@
 // (k_sp_shapes), shape casts (k_sp_cast), shape contacts (k_sp_contacts), the depenetration over them (k_sp_depenetrate), velocity
 // projection (k_sp_project_velocity), cast_move (k_sp_cast_move), the phases of the move-and-slide loop (k_sp_slide), and the casters: their
 // re-aiming (k_sp_reaim) and the per-caster filter of k_sp_query / k_sp_cast (PQ).  The kernels that take a query shape have a second,
-// CAPSULE instantiation for AVN_SHAPE_CAPSULE queries, launched behind the first (sp_lane_kind, sp_next_chunk).
+// CAPSULE instantiation for AVN_SHAPE_CAPSULE queries, launched behind the first (sp_lane_kind, sp_next_chunk).  The kernels
+// that reach a collider's geometry have a CCAP instantiation each, whose leaf tests know the capsule COLLIDER: the host launches it when the
+// world's switch is on and the snapshot holds a capsule collider, and the ones it always has otherwise.
 //
 // avn_spatial_update (launch_spatial_build), all on the world's stream:
 //   1. k_sp_snapshot   one thread per collider: its pose (collider_pose), the exact shape AABB (shape_aabb), padded, as the leaf box;
@@ -32,6 +34,7 @@
 #include "avn_kernels.h"
 #include "avn_narrow.h"
 #include "avn_spatial_pair.h"
+#include "avn_capsule_pair.h"   // capsule colliders: the CAP instantiation of contact_manifolds_pair_sink (the CCAP contact kernels)
 #include "../../include/avian_mi355x_spatial.h"
 
 namespace avn {
@@ -59,7 +62,8 @@ template <class T> __device__ __forceinline__ void sp_pad_box(V3<T> a, V3<T> b, 
 
 // ---------------------------------------------------------------------------------------------------------
 // build
-template <class T>
+// CCAP: a capsule collider is a candidate, its leaf box shape_aabb<T, true> padded like every other
+template <class T, bool CCAP = false>
 __global__ __launch_bounds__(256) void k_sp_snapshot(DW<T> w, BP<T> bp, SP<T> sp) {
     const uint32_t c = blockIdx.x * 256 + threadIdx.x;
     if (c >= sp.n) return;
@@ -72,13 +76,13 @@ __global__ __launch_bounds__(256) void k_sp_snapshot(DW<T> w, BP<T> bp, SP<T> sp
     sp.pos[c] = make4<T>(pos, T(0));
     sp.rot[c] = make4<T>(rot);
     sp.he[c] = make4<T>(h, T(0));
-    // a candidate has device geometry for the queries (a capsule COLLIDER has none yet: it is left out as a host shape is) and a finite
+    // a candidate has device geometry for the queries (without CCAP a capsule COLLIDER is left out as a host shape is) and a finite
     // position, rotation and shape AABB; the others get an empty leaf box and never reach an exact test
     bool candidate = false;
     V3<T> mn{sp_inf<T>(), sp_inf<T>(), sp_inf<T>()}, mx{-sp_inf<T>(), -sp_inf<T>(), -sp_inf<T>()};
-    if (shape != AVN_SHAPE_HOST && shape != AVN_SHAPE_CAPSULE && is_finite(pos) && is_finite(V3<T>{rot.x, rot.y, rot.z}) && finite_t(rot.w)) {
+    if (shape != AVN_SHAPE_HOST && (CCAP || shape != AVN_SHAPE_CAPSULE) && is_finite(pos) && is_finite(V3<T>{rot.x, rot.y, rot.z}) && finite_t(rot.w)) {
         V3<T> a, b;
-        shape_aabb<T>(shape, h, pos, rot, a, b);
+        shape_aabb<T, CCAP>(shape, h, pos, rot, a, b);
         if (is_finite(a) && is_finite(b)) {
             candidate = true;
             sp_pad_box(a, b, mn, mx);
@@ -181,14 +185,15 @@ __global__ __launch_bounds__(256) void k_sp_refit(SP<T> sp) {
     }
 }
 
-template <class T> void launch_spatial_build(const DW<T>& w, const BP<T>& bp, const SP<T>& sp, hipStream_t s) {
+template <class T> void launch_spatial_build(const DW<T>& w, const BP<T>& bp, const SP<T>& sp, hipStream_t s, bool ccap) {
     const uint32_t n = sp.n;
     if (n == 0) return;
     const uint32_t nb = (n + 255) / 256;
     // bounds: min keys start at ~0, max keys at 0 (one memset each half)
     (void)hipMemsetAsync(sp.bounds, 0xFF, 3 * sizeof(uint32_t), s);
     (void)hipMemsetAsync(sp.bounds + 3, 0x00, 5 * sizeof(uint32_t), s);
-    hipLaunchKernelGGL((k_sp_snapshot<T>), dim3(nb), dim3(256), 0, s, w, bp, sp);
+    if (ccap) hipLaunchKernelGGL((k_sp_snapshot<T, true>), dim3(nb), dim3(256), 0, s, w, bp, sp);
+    else hipLaunchKernelGGL((k_sp_snapshot<T>), dim3(nb), dim3(256), 0, s, w, bp, sp);
     hipLaunchKernelGGL((k_sp_morton<T>), dim3(nb), dim3(256), 0, s, sp);
     uint32_t *ko = nullptr, *vo = nullptr;
     launch_radix_sort<uint32_t>(sp.keys_a, sp.vals_a, sp.keys_b, sp.vals_b, n, sp.hist, sp.block_sums, nullptr, &ko, &vo, s);
@@ -199,7 +204,7 @@ template <class T> void launch_spatial_build(const DW<T>& w, const BP<T>& bp, co
 
 // ---------------------------------------------------------------------------------------------------------
 // exact per-collider tests (the header's restatement of parry3d; tests/spatial_query_reference.py does the same operations in order)
-template <class T>
+template <class T, bool CCAP = false>
 __device__ __forceinline__ bool sp_ray_exact(uint32_t shape, V3<T> he, V3<T> pos, Q4<T> rot, V3<T> o, V3<T> d, T max_distance, bool solid, T& toi, V3<T>& normal) {
     const Q4<T> ci = qinverse(rot);
     const V3<T> ol = qrot(ci, o - pos);
@@ -207,7 +212,11 @@ __device__ __forceinline__ bool sp_ray_exact(uint32_t shape, V3<T> he, V3<T> pos
     T t;
     bool zero_normal = false;
     V3<T> nl = vzero<T>();
-    if (shape == AVN_SHAPE_BALL) {
+    if (CCAP && shape == AVN_SHAPE_CAPSULE) {
+        if (!sp_capcol_ray<T>(he, ol, dl, solid, t, nl)) return false;
+        if (!(t <= max_distance)) return false;
+        zero_normal = nl.x == T(0) && nl.y == T(0) && nl.z == T(0);
+    } else if (shape == AVN_SHAPE_BALL) {
         const T r = he.x;
         const T a = dot(dl, dl), b = dot(ol, dl), c = dot(ol, ol) - r * r;
         if (c > T(0) && b > T(0)) return false;
@@ -261,14 +270,15 @@ __device__ __forceinline__ bool sp_ray_exact(uint32_t shape, V3<T> he, V3<T> pos
     normal = zero_normal ? vzero<T>() : qrot(rot, nl);
     return true;
 }
-template <class T> __device__ __forceinline__ bool sp_point_exact(uint32_t shape, V3<T> he, V3<T> pos, Q4<T> rot, V3<T> p) {
+template <class T, bool CCAP = false> __device__ __forceinline__ bool sp_point_exact(uint32_t shape, V3<T> he, V3<T> pos, Q4<T> rot, V3<T> p) {
     const V3<T> pl = qrot(qinverse(rot), p - pos);
+    if (CCAP && shape == AVN_SHAPE_CAPSULE) return sp_capcol_point<T>(he, pl);
     if (shape == AVN_SHAPE_BALL) return dot(pl, pl) <= he.x * he.x;
     return fabs_t(pl.x) <= he.x && fabs_t(pl.y) <= he.y && fabs_t(pl.z) <= he.z;
 }
-template <class T> __device__ __forceinline__ bool sp_aabb_exact(uint32_t shape, V3<T> he, V3<T> pos, Q4<T> rot, V3<T> qmin, V3<T> qmax) {
+template <class T, bool CCAP = false> __device__ __forceinline__ bool sp_aabb_exact(uint32_t shape, V3<T> he, V3<T> pos, Q4<T> rot, V3<T> qmin, V3<T> qmax) {
     V3<T> mn, mx;
-    shape_aabb<T>(shape, he, pos, rot, mn, mx);
+    shape_aabb<T, CCAP>(shape, he, pos, rot, mn, mx);
     return mn.x <= qmax.x && mn.y <= qmax.y && mn.z <= qmax.z && mx.x >= qmin.x && mx.y >= qmin.y && mx.z >= qmin.z;
 }
 
@@ -489,7 +499,7 @@ __device__ __forceinline__ void sp_walk(const SP<T>& sp, uint32_t& overflow, con
 
 // one lane per query.  PQ (a caster run, SPQ_CLOSEST / SPQ_HITS only): the lane answers caster q.index[lane's query] with that caster's own
 // self_entity, excluded slice, live flag and k, into its row of q.cap record slots.
-template <class T, int KIND, bool PQ = false>
+template <class T, int KIND, bool PQ = false, bool CCAP = false>
 __global__ __launch_bounds__(SP_WAVE) void k_sp_query(SP<T> sp, SQ<T> q) {
     constexpr bool RAY = KIND == SPQ_CLOSEST || KIND == SPQ_HITS;
     const uint32_t li = blockIdx.x * SP_WAVE + threadIdx.x;
@@ -534,7 +544,7 @@ __global__ __launch_bounds__(SP_WAVE) void k_sp_query(SP<T> sp, SQ<T> q) {
             const Q4<T> rot = quat<T>(sp.rot[c]);
             if (RAY) {
                 T toi; V3<T> nrm;
-                if (!sp_ray_exact<T>(info.z, he, pos, rot, r.o, r.d, max_distance, solid, toi, nrm)) return;
+                if (!sp_ray_exact<T, CCAP>(info.z, he, pos, rot, r.o, r.d, max_distance, solid, toi, nrm)) return;
                 if (KIND == SPQ_CLOSEST) {
                     if (toi < best || (toi == best && c < best_c)) { best = toi; best_c = c; best_n = nrm; }
                 } else {
@@ -545,7 +555,7 @@ __global__ __launch_bounds__(SP_WAVE) void k_sp_query(SP<T> sp, SQ<T> q) {
                     hl[m] = h;
                 }
             } else {
-                const bool hit = KIND == SPQ_POINTS ? sp_point_exact<T>(info.z, he, pos, rot, pa) : sp_aabb_exact<T>(info.z, he, pos, rot, pa, pb);
+                const bool hit = KIND == SPQ_POINTS ? sp_point_exact<T, CCAP>(info.z, he, pos, rot, pa) : sp_aabb_exact<T, CCAP>(info.z, he, pos, rot, pa, pb);
                 if (!hit) return;
                 const uint32_t m = sp_slot_by_collider(il, q.cap, found, c);
                 if (m != AVN_SPATIAL_MISS) il[m] = c;
@@ -577,12 +587,13 @@ __global__ __launch_bounds__(SP_WAVE) void k_sp_query(SP<T> sp, SQ<T> q) {
 // point projection and shape intersections
 
 // the header's projection of a point onto one collider: false when the distance is not finite
-template <class T>
+template <class T, bool CCAP = false>
 __device__ __forceinline__ bool sp_project_exact(uint32_t shape, V3<T> he, V3<T> pos, Q4<T> rot, V3<T> p, bool solid, T& distance, V3<T>& point, bool& is_inside) {
     const V3<T> pl = qrot(qinverse(rot), p - pos);
     V3<T> proj;
     bool inside;
-    if (shape == AVN_SHAPE_BALL) {
+    if (CCAP && shape == AVN_SHAPE_CAPSULE) sp_capcol_project<T>(he, pl, solid, proj, inside);
+    else if (shape == AVN_SHAPE_BALL) {
         const T r = he.x;
         const T d2 = dot(pl, pl);
         inside = d2 <= r * r;
@@ -621,7 +632,7 @@ template <class T> __device__ __forceinline__ T sp_point_box_distance(V3<T> p, T
     return sqrt_t(dot(d, d)) * (T(1) - T(8) * Limits<T>::eps);
 }
 
-template <class T>
+template <class T, bool CCAP = false>
 __global__ __launch_bounds__(SP_WAVE) void k_sp_project(SP<T> sp, SQ<T> q) {
     const uint32_t qi = blockIdx.x * SP_WAVE + threadIdx.x;
     uint32_t nodes_tested = 0, leaves_tested = 0, overflow = 0;
@@ -645,7 +656,7 @@ __global__ __launch_bounds__(SP_WAVE) void k_sp_project(SP<T> sp, SQ<T> q) {
             if (!sp_leaf_ok(info, mask, AVN_SPATIAL_MISS, q.excluded, q.n_excluded)) return;
             ++leaves_tested;
             T d; V3<T> pt; bool in;
-            if (!sp_project_exact<T>(info.z, xyz<T>(sp.he[c]), xyz<T>(sp.pos[c]), quat<T>(sp.rot[c]), p, solid, d, pt, in)) return;
+            if (!sp_project_exact<T, CCAP>(info.z, xyz<T>(sp.he[c]), xyz<T>(sp.pos[c]), quat<T>(sp.rot[c]), p, solid, d, pt, in)) return;
             if (d < best || (d == best && c < best_c)) { best = d; best_c = c; best_p = pt; best_in = in ? 1u : 0u; }
         };
         if (is_finite(p)) sp_walk<T, true>(sp, overflow, best, test, leaf);
@@ -687,7 +698,7 @@ __device__ __forceinline__ bool sp_shape_exact(uint32_t shape1, V3<T> he1, const
     return true;
 }
 
-template <class T, bool CAPSULE = false>
+template <class T, bool CAPSULE = false, bool CCAP = false>
 __global__ __launch_bounds__(SP_WAVE) void k_sp_shapes(SP<T> sp, SQ<T> q) {
     uint32_t nodes_tested = 0, leaves_tested = 0, overflow = 0;
     uint32_t base = blockIdx.x * SP_WAVE;
@@ -710,7 +721,9 @@ __global__ __launch_bounds__(SP_WAVE) void k_sp_shapes(SP<T> sp, SQ<T> q) {
             const uint4 info = sp.info[c];
             if (!sp_leaf_ok(info, mask, AVN_SPATIAL_MISS, q.excluded, q.n_excluded)) return;
             ++leaves_tested;
-            if (CAPSULE) {
+            if (CCAP && info.z == AVN_SHAPE_CAPSULE) {
+                if (!sp_capcol_intersects<T, CAPSULE>(s.shape, s.he, iso1, xyz<T>(sp.he[c]), xyz<T>(sp.pos[c]), quat<T>(sp.rot[c]))) return;
+            } else if (CAPSULE) {
                 if (!sp_capsule_intersects<T>(s.he.x, s.he.y, iso_inv_mul(Iso<T>{quat<T>(sp.rot[c]), xyz<T>(sp.pos[c])}, iso1), info.z, xyz<T>(sp.he[c]))) return;
             } else if (!sp_shape_exact<T>(s.shape, s.he, iso1, info.z, xyz<T>(sp.he[c]), xyz<T>(sp.pos[c]), quat<T>(sp.rot[c]))) return;
             const uint32_t m = sp_slot_by_collider(il, q.cap, found, c);
@@ -729,7 +742,7 @@ __global__ __launch_bounds__(SP_WAVE) void k_sp_shapes(SP<T> sp, SQ<T> q) {
 // order.  DESIGN.md 4.4.6 has the padding argument.
 
 // one lane per cast; MANY: the nearest-k list (shape_hits), else the closest hit (cast_shapes).  PQ: a caster run, as in k_sp_query
-template <class T, bool MANY, bool PQ = false, bool CAPSULE = false>
+template <class T, bool MANY, bool PQ = false, bool CAPSULE = false, bool CCAP = false>
 __global__ __launch_bounds__(SP_WAVE) void k_sp_cast(SP<T> sp, SQ<T> q) {
     uint32_t nodes_tested = 0, leaves_tested = 0, overflow = 0;
     uint32_t base = blockIdx.x * SP_WAVE;
@@ -765,7 +778,9 @@ __global__ __launch_bounds__(SP_WAVE) void k_sp_cast(SP<T> sp, SQ<T> q) {
             if (!sp_leaf_ok(info, mask, self, q.excluded + ex0, ex_n)) return;
             ++leaves_tested;
             T toi; V3<T> p1, p2, n1;
-            if (CAPSULE) {
+            if (CCAP && info.z == AVN_SHAPE_CAPSULE) {
+                if (!sp_capcol_cast_exact<T, CAPSULE>(s.shape, s.he, iso2, d, max_distance, xyz<T>(sp.he[c]), xyz<T>(sp.pos[c]), quat<T>(sp.rot[c]), toi, p1, p2, n1)) return;
+            } else if (CAPSULE) {
                 if (!sp_capsule_cast_exact<T>(s.he.x, s.he.y, iso2, d, max_distance, info.z, xyz<T>(sp.he[c]), xyz<T>(sp.pos[c]), quat<T>(sp.rot[c]), toi, p1, p2, n1)) return;
             } else if (!sp_cast_exact<T>(s.shape, s.he, iso2, d, max_distance, info.z, xyz<T>(sp.he[c]), xyz<T>(sp.pos[c]), quat<T>(sp.rot[c]), toi, p1, p2, n1)) return;
             if (!MANY) {
@@ -803,7 +818,7 @@ __global__ __launch_bounds__(SP_WAVE) void k_sp_cast(SP<T> sp, SQ<T> q) {
 // untouched.  DESIGN.md 4.4.7.
 
 // one lane per query shape; records inserted in ascending collider index as k_sp_shapes inserts ids
-template <class T, bool CAPSULE = false>
+template <class T, bool CAPSULE = false, bool CCAP = false>
 __global__ __launch_bounds__(SP_WAVE) void k_sp_contacts(SP<T> sp, SC<T> sc) {
     const SQ<T>& q = sc.q;
     uint32_t nodes_tested = 0, leaves_tested = 0, overflow = 0;
@@ -837,18 +852,22 @@ __global__ __launch_bounds__(SP_WAVE) void k_sp_contacts(SP<T> sp, SC<T> sc) {
             const Q4<T> rot2 = quat<T>(sp.rot[c]);
             // (b) the collider's exact box, by the snapshot's own arithmetic
             V3<T> mn, mx;
-            shape_aabb<T>(info.z, he2, pos2, rot2, mn, mx);
+            shape_aabb<T, CCAP>(info.z, he2, pos2, rot2, mn, mx);
             if (!sp_box_box(gmin, gmax, make4<T>(mn, T(0)), make4<T>(mx, T(0)))) return;
             // (c), (d)
             SpDeepestSink<T> sink{vzero<T>(), T(0), 0};
             V3<T> nrm, a1, a2;
-            if (CAPSULE) {
+            if (CAPSULE && CCAP && info.z == AVN_SHAPE_CAPSULE) {
+                // (two capsules: the narrow phase's capsule-capsule manifold, the query as shape 1)
+                if (!contact_manifolds_pair_sink<T, SpDeepestSink<T>, 0, true>(AVN_SHAPE_CAPSULE, s.he, s.pos, s.rot, AVN_SHAPE_CAPSULE, he2, pos2, rot2, pred, sink, nrm)) return;
+                a1 = sink.anchor1; a2 = a1 + (s.pos - pos2);
+            } else if (CAPSULE) {
                 // (the capsule's own contact: the normal already points from the collider towards the query)
                 V3<T> cn;
                 if (!sp_capsule_contact<T>(s.he.x, s.he.y, iso2, info.z, he2, pos2, rot2, pred, sink.penetration, cn, a1, a2)) return;
                 nrm = -cn;
             } else {
-                if (!contact_manifolds_pair_sink<T, SpDeepestSink<T>>(s.shape, s.he, s.pos, s.rot, info.z, he2, pos2, rot2, pred, sink, nrm)) return;
+                if (!contact_manifolds_pair_sink<T, SpDeepestSink<T>, 0, CCAP>(s.shape, s.he, s.pos, s.rot, info.z, he2, pos2, rot2, pred, sink, nrm)) return;
                 a1 = sink.anchor1; a2 = a1 + (s.pos - pos2);
             }
             const uint32_t m = sp_slot_by_collider(rl, q.cap, found, c);
@@ -906,11 +925,16 @@ __global__ __launch_bounds__(SP_WAVE) void k_sp_depenetrate(SD<T> d) {
     d.out[qi] = r;
 }
 
-template <class T> void launch_spatial_contacts(const SP<T>& sp, const SC<T>& sc, hipStream_t s, bool zero_stats, bool capsule) {
+template <class T, bool CCAP> static void launch_spatial_contacts_as(const SP<T>& sp, const SC<T>& sc, hipStream_t s, bool capsule) {
+    hipLaunchKernelGGL((k_sp_contacts<T, false, CCAP>), dim3((sc.q.n + SP_WAVE - 1) / SP_WAVE), dim3(SP_WAVE), 0, s, sp, sc);
+    if (capsule) hipLaunchKernelGGL((k_sp_contacts<T, true, CCAP>), sp_capsule_grid(sc.q.n), dim3(SP_WAVE), 0, s, sp, sc);
+}
+// ccap (here and in every launch_spatial_* below): the snapshot holds capsule colliders as candidates -- the CCAP instantiations go
+template <class T> void launch_spatial_contacts(const SP<T>& sp, const SC<T>& sc, hipStream_t s, bool zero_stats, bool capsule, bool ccap) {
     if (zero_stats) (void)hipMemsetAsync(sc.q.stats, 0, 4 * sizeof(unsigned long long), s);
     if (sc.q.n == 0) return;
-    hipLaunchKernelGGL((k_sp_contacts<T>), dim3((sc.q.n + SP_WAVE - 1) / SP_WAVE), dim3(SP_WAVE), 0, s, sp, sc);
-    if (capsule) hipLaunchKernelGGL((k_sp_contacts<T, true>), sp_capsule_grid(sc.q.n), dim3(SP_WAVE), 0, s, sp, sc);
+    if (ccap) launch_spatial_contacts_as<T, true>(sp, sc, s, capsule);
+    else launch_spatial_contacts_as<T, false>(sp, sc, s, capsule);
 }
 template <class T> void launch_spatial_depenetrate(const SD<T>& d, hipStream_t s) {
     if (d.n == 0) return;
@@ -1004,7 +1028,7 @@ template <class T> __device__ __forceinline__ void sp_put_move(SpatialMoveHit<T>
 // applies the origin-penetration rule to the pending colliders with the narrow phase's contact_manifolds_pair_sink, merges them with the
 // traversal's hit by (distance, collider index) and pulls the distance back.  The contact manifold so stays out of the traversal's live
 // range (fused into the leaf the kernel needed 256 VGPRs + 13 / 72 AGPRs, one wave per SIMD: profiles/spatial_moves_resource_usage.txt).
-template <class T, bool CAPSULE = false>
+template <class T, bool CAPSULE = false, bool CCAP = false>
 __global__ __launch_bounds__(SP_WAVE) void k_sp_cast_move(SP<T> sp, SM<T> m) {
     const SQ<T>& q = m.q;
     uint32_t nodes_tested = 0, leaves_tested = 0, overflow = 0;
@@ -1041,7 +1065,9 @@ __global__ __launch_bounds__(SP_WAVE) void k_sp_cast_move(SP<T> sp, SM<T> m) {
             const V3<T> pos1 = xyz<T>(sp.pos[c]), he1 = xyz<T>(sp.he[c]);
             const Q4<T> rot1 = quat<T>(sp.rot[c]);
             T toi; V3<T> p1, p2, n1;
-            if (CAPSULE) {
+            if (CCAP && info.z == AVN_SHAPE_CAPSULE) {
+                if (!sp_capcol_cast_exact<T, CAPSULE>(s.shape, s.he, iso2, d, dist, he1, pos1, rot1, toi, p1, p2, n1)) return;
+            } else if (CAPSULE) {
                 if (!sp_capsule_cast_exact<T>(s.he.x, s.he.y, iso2, d, dist, info.z, he1, pos1, rot1, toi, p1, p2, n1)) return;
             } else if (!sp_cast_exact<T>(s.shape, s.he, iso2, d, dist, info.z, he1, pos1, rot1, toi, p1, p2, n1)) return;
             if (toi == T(0) && n1.x == T(0) && n1.y == T(0) && n1.z == T(0)) {
@@ -1065,14 +1091,14 @@ __global__ __launch_bounds__(SP_WAVE) void k_sp_cast_move(SP<T> sp, SM<T> m) {
     sp_add_stats(q.stats, nodes_tested, leaves_tested, overflow);
 }
 
-template <class T, bool CAPSULE> __device__ __forceinline__ void sp_cast_move_resolve_lane(const SP<T>& sp, const SM<T>& m, uint32_t qi);
-template <class T, bool CAPSULE = false>
+template <class T, bool CAPSULE, bool CCAP> __device__ __forceinline__ void sp_cast_move_resolve_lane(const SP<T>& sp, const SM<T>& m, uint32_t qi);
+template <class T, bool CAPSULE = false, bool CCAP = false>
 __global__ __launch_bounds__(SP_WAVE) void k_sp_cast_move_resolve(SP<T> sp, SM<T> m) {
     uint32_t base = blockIdx.x * SP_WAVE;
-    do sp_cast_move_resolve_lane<T, CAPSULE>(sp, m, base + threadIdx.x);
+    do sp_cast_move_resolve_lane<T, CAPSULE, CCAP>(sp, m, base + threadIdx.x);
     while (CAPSULE && (base = sp_next_chunk<CAPSULE>(base, m.q.n)) < m.q.n);
 }
-template <class T, bool CAPSULE> __device__ __forceinline__ void sp_cast_move_resolve_lane(const SP<T>& sp, const SM<T>& m, uint32_t qi) {
+template <class T, bool CAPSULE, bool CCAP> __device__ __forceinline__ void sp_cast_move_resolve_lane(const SP<T>& sp, const SM<T>& m, uint32_t qi) {
     const SQ<T>& q = m.q;
     if (qi >= q.n || !sp_lane_kind<CAPSULE>(q.shape, qi)) return;
     SpatialMoveHit<T> h = m.out[qi];
@@ -1102,12 +1128,15 @@ template <class T, bool CAPSULE> __device__ __forceinline__ void sp_cast_move_re
         SpDeepestSink<T> sink{vzero<T>(), T(0), 0};
         V3<T> nrm, a1, a2;
         bool contact;
-        if (CAPSULE) {
+        if (CAPSULE && CCAP && info.z == AVN_SHAPE_CAPSULE) {
+            contact = contact_manifolds_pair_sink<T, SpDeepestSink<T>, 0, true>(AVN_SHAPE_CAPSULE, s.he, s.pos, s.rot, AVN_SHAPE_CAPSULE, he1, pos1, rot1, T(0), sink, nrm);
+            a1 = sink.anchor1; a2 = a1 + (s.pos - pos1);
+        } else if (CAPSULE) {
             V3<T> cn;
             contact = sp_capsule_contact<T>(s.he.x, s.he.y, iso2, info.z, he1, pos1, rot1, T(0), sink.penetration, cn, a1, a2);
             nrm = -cn;
         } else {
-            contact = contact_manifolds_pair_sink<T, SpDeepestSink<T>>(s.shape, s.he, s.pos, s.rot, info.z, he1, pos1, rot1, T(0), sink, nrm);
+            contact = contact_manifolds_pair_sink<T, SpDeepestSink<T>, 0, CCAP>(s.shape, s.he, s.pos, s.rot, info.z, he1, pos1, rot1, T(0), sink, nrm);
             a1 = sink.anchor1; a2 = a1 + (s.pos - pos1);
         }
         if (contact) {
@@ -1276,14 +1305,18 @@ template <class T> void launch_spatial_project_velocity(const SV<T>& p, hipStrea
     if (p.n == 0) return;
     hipLaunchKernelGGL((k_sp_project_velocity<T>), dim3((p.n + SP_WAVE - 1) / SP_WAVE), dim3(SP_WAVE), 0, s, p);
 }
-template <class T> void launch_spatial_cast_move(const SP<T>& sp, const SM<T>& m, bool zero_stats, hipStream_t s, bool capsule) {
+template <class T, bool CCAP> static void launch_spatial_cast_move_as(const SP<T>& sp, const SM<T>& m, hipStream_t s, bool capsule) {
+    hipLaunchKernelGGL((k_sp_cast_move<T, false, CCAP>), dim3((m.q.n + SP_WAVE - 1) / SP_WAVE), dim3(SP_WAVE), 0, s, sp, m);
+    hipLaunchKernelGGL((k_sp_cast_move_resolve<T, false, CCAP>), dim3((m.q.n + SP_WAVE - 1) / SP_WAVE), dim3(SP_WAVE), 0, s, sp, m);
+    if (!capsule) return;
+    hipLaunchKernelGGL((k_sp_cast_move<T, true, CCAP>), sp_capsule_grid(m.q.n), dim3(SP_WAVE), 0, s, sp, m);
+    hipLaunchKernelGGL((k_sp_cast_move_resolve<T, true, CCAP>), sp_capsule_grid(m.q.n), dim3(SP_WAVE), 0, s, sp, m);
+}
+template <class T> void launch_spatial_cast_move(const SP<T>& sp, const SM<T>& m, bool zero_stats, hipStream_t s, bool capsule, bool ccap) {
     if (zero_stats) (void)hipMemsetAsync(m.q.stats, 0, 4 * sizeof(unsigned long long), s);
     if (m.q.n == 0) return;
-    hipLaunchKernelGGL((k_sp_cast_move<T>), dim3((m.q.n + SP_WAVE - 1) / SP_WAVE), dim3(SP_WAVE), 0, s, sp, m);
-    hipLaunchKernelGGL((k_sp_cast_move_resolve<T>), dim3((m.q.n + SP_WAVE - 1) / SP_WAVE), dim3(SP_WAVE), 0, s, sp, m);
-    if (!capsule) return;
-    hipLaunchKernelGGL((k_sp_cast_move<T, true>), sp_capsule_grid(m.q.n), dim3(SP_WAVE), 0, s, sp, m);
-    hipLaunchKernelGGL((k_sp_cast_move_resolve<T, true>), sp_capsule_grid(m.q.n), dim3(SP_WAVE), 0, s, sp, m);
+    if (ccap) launch_spatial_cast_move_as<T, true>(sp, m, s, capsule);
+    else launch_spatial_cast_move_as<T, false>(sp, m, s, capsule);
 }
 template <class T> void launch_spatial_slide_phase(const SL<T>& l, int phase, hipStream_t s) {
     if (l.n == 0) return;
@@ -1329,48 +1362,56 @@ template <class T> void launch_spatial_reaim(const DW<T>& w, const SP<T>& sp, co
     if (c.n == 0) return;
     hipLaunchKernelGGL((k_sp_reaim<T>), dim3((c.n + 255) / 256), dim3(256), 0, s, w, sp, c);
 }
-template <class T> void launch_spatial_casters(const SP<T>& sp, const SQ<T>& q, int kind, hipStream_t s, bool capsule) {
-    if (q.n == 0) return;
+template <class T, bool CCAP> static void launch_spatial_casters_as(const SP<T>& sp, const SQ<T>& q, int kind, hipStream_t s, bool capsule) {
     const dim3 g((q.n + SP_WAVE - 1) / SP_WAVE), b(SP_WAVE);
     switch (kind) {
-        case SPQ_CLOSEST: hipLaunchKernelGGL((k_sp_query<T, SPQ_CLOSEST, true>), g, b, 0, s, sp, q); break;
-        case SPQ_HITS: hipLaunchKernelGGL((k_sp_query<T, SPQ_HITS, true>), g, b, 0, s, sp, q); break;
+        case SPQ_CLOSEST: hipLaunchKernelGGL((k_sp_query<T, SPQ_CLOSEST, true, CCAP>), g, b, 0, s, sp, q); break;
+        case SPQ_HITS: hipLaunchKernelGGL((k_sp_query<T, SPQ_HITS, true, CCAP>), g, b, 0, s, sp, q); break;
         case SPQ_CAST:
-            hipLaunchKernelGGL((k_sp_cast<T, false, true>), g, b, 0, s, sp, q);
-            if (capsule) hipLaunchKernelGGL((k_sp_cast<T, false, true, true>), sp_capsule_grid(q.n), b, 0, s, sp, q);
+            hipLaunchKernelGGL((k_sp_cast<T, false, true, false, CCAP>), g, b, 0, s, sp, q);
+            if (capsule) hipLaunchKernelGGL((k_sp_cast<T, false, true, true, CCAP>), sp_capsule_grid(q.n), b, 0, s, sp, q);
             break;
         default:
-            hipLaunchKernelGGL((k_sp_cast<T, true, true>), g, b, 0, s, sp, q);
-            if (capsule) hipLaunchKernelGGL((k_sp_cast<T, true, true, true>), sp_capsule_grid(q.n), b, 0, s, sp, q);
+            hipLaunchKernelGGL((k_sp_cast<T, true, true, false, CCAP>), g, b, 0, s, sp, q);
+            if (capsule) hipLaunchKernelGGL((k_sp_cast<T, true, true, true, CCAP>), sp_capsule_grid(q.n), b, 0, s, sp, q);
             break;
     }
+}
+template <class T> void launch_spatial_casters(const SP<T>& sp, const SQ<T>& q, int kind, hipStream_t s, bool capsule, bool ccap) {
+    if (q.n == 0) return;
+    if (ccap) launch_spatial_casters_as<T, true>(sp, q, kind, s, capsule);
+    else launch_spatial_casters_as<T, false>(sp, q, kind, s, capsule);
 }
 
 // capsule (SPQ_SHAPES / SPQ_CAST / SPQ_CAST_HITS): the call may hold AVN_SHAPE_CAPSULE query shapes -- the CAPSULE instantiation runs behind the
 // first launch on the same stream and answers exactly those lanes
-template <class T> void launch_spatial_query(const SP<T>& sp, const SQ<T>& q, int kind, hipStream_t s, bool capsule) {
-    (void)hipMemsetAsync(q.stats, 0, 4 * sizeof(unsigned long long), s);
-    if (q.n == 0) return;
+template <class T, bool CCAP> static void launch_spatial_query_as(const SP<T>& sp, const SQ<T>& q, int kind, hipStream_t s, bool capsule) {
     const dim3 g((q.n + SP_WAVE - 1) / SP_WAVE), b(SP_WAVE);
     switch (kind) {
-        case SPQ_CLOSEST: hipLaunchKernelGGL((k_sp_query<T, SPQ_CLOSEST>), g, b, 0, s, sp, q); break;
-        case SPQ_HITS: hipLaunchKernelGGL((k_sp_query<T, SPQ_HITS>), g, b, 0, s, sp, q); break;
-        case SPQ_POINTS: hipLaunchKernelGGL((k_sp_query<T, SPQ_POINTS>), g, b, 0, s, sp, q); break;
-        case SPQ_PROJECT: hipLaunchKernelGGL((k_sp_project<T>), g, b, 0, s, sp, q); break;
+        case SPQ_CLOSEST: hipLaunchKernelGGL((k_sp_query<T, SPQ_CLOSEST, false, CCAP>), g, b, 0, s, sp, q); break;
+        case SPQ_HITS: hipLaunchKernelGGL((k_sp_query<T, SPQ_HITS, false, CCAP>), g, b, 0, s, sp, q); break;
+        case SPQ_POINTS: hipLaunchKernelGGL((k_sp_query<T, SPQ_POINTS, false, CCAP>), g, b, 0, s, sp, q); break;
+        case SPQ_PROJECT: hipLaunchKernelGGL((k_sp_project<T, CCAP>), g, b, 0, s, sp, q); break;
         case SPQ_SHAPES:
-            hipLaunchKernelGGL((k_sp_shapes<T>), g, b, 0, s, sp, q);
-            if (capsule) hipLaunchKernelGGL((k_sp_shapes<T, true>), sp_capsule_grid(q.n), b, 0, s, sp, q);
+            hipLaunchKernelGGL((k_sp_shapes<T, false, CCAP>), g, b, 0, s, sp, q);
+            if (capsule) hipLaunchKernelGGL((k_sp_shapes<T, true, CCAP>), sp_capsule_grid(q.n), b, 0, s, sp, q);
             break;
         case SPQ_CAST:
-            hipLaunchKernelGGL((k_sp_cast<T, false>), g, b, 0, s, sp, q);
-            if (capsule) hipLaunchKernelGGL((k_sp_cast<T, false, false, true>), sp_capsule_grid(q.n), b, 0, s, sp, q);
+            hipLaunchKernelGGL((k_sp_cast<T, false, false, false, CCAP>), g, b, 0, s, sp, q);
+            if (capsule) hipLaunchKernelGGL((k_sp_cast<T, false, false, true, CCAP>), sp_capsule_grid(q.n), b, 0, s, sp, q);
             break;
         case SPQ_CAST_HITS:
-            hipLaunchKernelGGL((k_sp_cast<T, true>), g, b, 0, s, sp, q);
-            if (capsule) hipLaunchKernelGGL((k_sp_cast<T, true, false, true>), sp_capsule_grid(q.n), b, 0, s, sp, q);
+            hipLaunchKernelGGL((k_sp_cast<T, true, false, false, CCAP>), g, b, 0, s, sp, q);
+            if (capsule) hipLaunchKernelGGL((k_sp_cast<T, true, false, true, CCAP>), sp_capsule_grid(q.n), b, 0, s, sp, q);
             break;
-        default: hipLaunchKernelGGL((k_sp_query<T, SPQ_AABBS>), g, b, 0, s, sp, q); break;
+        default: hipLaunchKernelGGL((k_sp_query<T, SPQ_AABBS, false, CCAP>), g, b, 0, s, sp, q); break;
     }
+}
+template <class T> void launch_spatial_query(const SP<T>& sp, const SQ<T>& q, int kind, hipStream_t s, bool capsule, bool ccap) {
+    (void)hipMemsetAsync(q.stats, 0, 4 * sizeof(unsigned long long), s);
+    if (q.n == 0) return;
+    if (ccap) launch_spatial_query_as<T, true>(sp, q, kind, s, capsule);
+    else launch_spatial_query_as<T, false>(sp, q, kind, s, capsule);
 }
 
 static_assert(sizeof(SpatialHit<float>) == sizeof(avn_spatial_hit_f32) && sizeof(SpatialHit<double>) == sizeof(avn_spatial_hit_f64), "hit record layout");
@@ -1411,20 +1452,20 @@ static_assert(sizeof(SpatialSlide<float>) == sizeof(avn_spatial_slide_f32) && si
               offsetof(SpatialSlide<double>, reserved) == offsetof(avn_spatial_slide_f64, reserved),
               "slide record layout");
 static_assert(SP_SLIDE_PLANES >= AVN_SPATIAL_MAX_PLANES + 1, "plane slots");
-template void launch_spatial_build<float>(const DW<float>&, const BP<float>&, const SP<float>&, hipStream_t);
-template void launch_spatial_build<double>(const DW<double>&, const BP<double>&, const SP<double>&, hipStream_t);
-template void launch_spatial_query<float>(const SP<float>&, const SQ<float>&, int, hipStream_t, bool);
-template void launch_spatial_query<double>(const SP<double>&, const SQ<double>&, int, hipStream_t, bool);
+template void launch_spatial_build<float>(const DW<float>&, const BP<float>&, const SP<float>&, hipStream_t, bool);
+template void launch_spatial_build<double>(const DW<double>&, const BP<double>&, const SP<double>&, hipStream_t, bool);
+template void launch_spatial_query<float>(const SP<float>&, const SQ<float>&, int, hipStream_t, bool, bool);
+template void launch_spatial_query<double>(const SP<double>&, const SQ<double>&, int, hipStream_t, bool, bool);
 template void launch_spatial_reaim<float>(const DW<float>&, const SP<float>&, const SCA<float>&, hipStream_t);
 template void launch_spatial_reaim<double>(const DW<double>&, const SP<double>&, const SCA<double>&, hipStream_t);
-template void launch_spatial_casters<float>(const SP<float>&, const SQ<float>&, int, hipStream_t, bool);
-template void launch_spatial_casters<double>(const SP<double>&, const SQ<double>&, int, hipStream_t, bool);
-template void launch_spatial_contacts<float>(const SP<float>&, const SC<float>&, hipStream_t, bool, bool);
-template void launch_spatial_contacts<double>(const SP<double>&, const SC<double>&, hipStream_t, bool, bool);
+template void launch_spatial_casters<float>(const SP<float>&, const SQ<float>&, int, hipStream_t, bool, bool);
+template void launch_spatial_casters<double>(const SP<double>&, const SQ<double>&, int, hipStream_t, bool, bool);
+template void launch_spatial_contacts<float>(const SP<float>&, const SC<float>&, hipStream_t, bool, bool, bool);
+template void launch_spatial_contacts<double>(const SP<double>&, const SC<double>&, hipStream_t, bool, bool, bool);
 template void launch_spatial_project_velocity<float>(const SV<float>&, hipStream_t);
 template void launch_spatial_project_velocity<double>(const SV<double>&, hipStream_t);
-template void launch_spatial_cast_move<float>(const SP<float>&, const SM<float>&, bool, hipStream_t, bool);
-template void launch_spatial_cast_move<double>(const SP<double>&, const SM<double>&, bool, hipStream_t, bool);
+template void launch_spatial_cast_move<float>(const SP<float>&, const SM<float>&, bool, hipStream_t, bool, bool);
+template void launch_spatial_cast_move<double>(const SP<double>&, const SM<double>&, bool, hipStream_t, bool, bool);
 template void launch_spatial_slide_phase<float>(const SL<float>&, int, hipStream_t);
 template void launch_spatial_slide_phase<double>(const SL<double>&, int, hipStream_t);
 template void launch_spatial_depenetrate<float>(const SD<float>&, hipStream_t);

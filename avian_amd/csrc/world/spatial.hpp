@@ -11,7 +11,9 @@
         b_mv_pend, b_mv_pcount;   // cast_move's hand-over: the colliders overlapping each query at its start [n * AVN_SPATIAL_MAX_HITS], their counts [n]
     uint32_t sp_cap = 0;
     bool sp_valid = false;      // a snapshot exists and no table changed since (bodies / colliders / collider transforms uploads and avn_despawn clear it)
-    uint32_t sp_host = 0;       // AVN_SHAPE_HOST and AVN_SHAPE_CAPSULE colliders in the snapshot: neither has device geometry for the queries
+    uint32_t sp_host = 0;       // the colliders the snapshot leaves out: AVN_SHAPE_HOST, and AVN_SHAPE_CAPSULE unless sp_capsules is set
+    bool sp_capsules = false;   // avn_spatial_capsule_colliders_set: capsule colliders are candidates of the queries (sticky, off by default)
+    bool sp_ccap = false;       // the snapshot holds capsule colliders as candidates: every traversal launch takes its CCAP instantiation
     unsigned long long sp_visits[3] = {0, 0, 0};   // last query call: node boxes tested, exact tests, stack overflow
 
     avn_status sp_grow(uint32_t C) {
@@ -41,17 +43,25 @@
         avn_status st = sp_grow(C);
         if (st != AVN_OK) return st;
         sp.n = C;
-        launch_spatial_build<T>(dw, bp, sp, stream);
+        sp_ccap = sp_capsules && cap_count != 0;   // (a world without a capsule, or with the switch off, launches what it always has)
+        launch_spatial_build<T>(dw, bp, sp, stream, sp_ccap);
         HIPCHK(hipGetLastError());
-        sp_host = (uint32_t)hs_slots.size() + cap_count;
+        sp_host = (uint32_t)hs_slots.size() + (sp_capsules ? 0u : cap_count);
         sp_valid = true;
+        return AVN_OK;
+    }
+
+    avn_status spatial_capsule_colliders_set(uint32_t enabled) override {
+        sp_capsules = enabled != 0;
+        sp_valid = false;   // (the snapshot was built under the old rule: avn_spatial_update again)
         return AVN_OK;
     }
 
     avn_status sp_check(uint32_t flags) {
         if (!sp_valid) { error = "spatial query: no avn_spatial_update since the tables last changed"; return AVN_ERR_STATE; }
         if (sp_host && !(flags & AVN_SPATIAL_SKIP_HOST_SHAPES)) {
-            error = "spatial query: the snapshot holds AVN_SHAPE_HOST or AVN_SHAPE_CAPSULE colliders, which the queries have no device geometry for (AVN_SPATIAL_SKIP_HOST_SHAPES leaves them out)";
+            error = sp_capsules ? "spatial query: the snapshot holds AVN_SHAPE_HOST colliders, which the queries have no device geometry for (AVN_SPATIAL_SKIP_HOST_SHAPES leaves them out)"
+                                : "spatial query: the snapshot holds AVN_SHAPE_HOST or AVN_SHAPE_CAPSULE colliders, which the queries have no device geometry for (AVN_SPATIAL_SKIP_HOST_SHAPES leaves them out; avn_spatial_capsule_colliders_set makes capsules candidates)";
             return AVN_ERR_STATE;
         }
         return AVN_OK;
@@ -86,7 +96,7 @@
     }
     avn_status sp_run(SQ<T>& q, int kind, bool capsule = false) {
         q.stats = b_sp_stats.as<unsigned long long>();
-        launch_spatial_query<T>(sp, q, kind, stream, capsule);
+        launch_spatial_query<T>(sp, q, kind, stream, capsule, sp_ccap);
         HIPCHK(hipGetLastError());
         return AVN_OK;
     }
@@ -291,7 +301,7 @@
         sc.pad_unused = 1u;
         sc.rec = n_rec ? sp_out<SpatialShapeContact<T>>(out->contacts, n_rec, dev) : nullptr;
         sc.q.count = sp_out<uint32_t>(out->count, n, dev);
-        launch_spatial_contacts<T>(sp, sc, stream, true, sp_any_capsule(s->shape, n, dev));
+        launch_spatial_contacts<T>(sp, sc, stream, true, sp_any_capsule(s->shape, n, dev), sp_ccap);
         HIPCHK(hipGetLastError());
         if (!dev) {
             if ((st = stage_out<SpatialShapeContact<T>>(out->contacts, sc.rec, n_rec)) != AVN_OK) return st;
@@ -328,7 +338,7 @@
             sc.prediction_all = (T)cfg->skin_width;
             sc.pad_unused = 0u;   // (k_sp_depenetrate reads the first min(count, cap) records only)
             sc.skip_sensors = (s->flags & AVN_SPATIAL_SKIP_SENSORS) ? 1u : 0u;
-            launch_spatial_contacts<T>(sp, sc, stream, true, sp_any_capsule(s->shape, n, dev));
+            launch_spatial_contacts<T>(sp, sc, stream, true, sp_any_capsule(s->shape, n, dev), sp_ccap);
             HIPCHK(hipGetLastError());
             SD<T> d{};
             d.n = n; d.rec = sc.rec; d.count = d_count;
@@ -385,7 +395,7 @@
         bool moved = false;
         GROW(b_mv_pend, std::max<size_t>((size_t)n * AVN_SPATIAL_MAX_HITS, 1), m.pending);
         GROW(b_mv_pcount, std::max<size_t>(n, 1), m.pending_count);
-        launch_spatial_cast_move<T>(sp, m, true, stream, sp_any_capsule(s->shape, n, dev));
+        launch_spatial_cast_move<T>(sp, m, true, stream, sp_any_capsule(s->shape, n, dev), sp_ccap);
         HIPCHK(hipGetLastError());
         if (!dev && (st = stage_out<SpatialMoveHit<T>>(out->hits, m.out, n)) != AVN_OK) return st;
         return sp_finish();
@@ -443,7 +453,7 @@
         HIPCHK(hipMemsetAsync(b_sp_stats.p, 0, 4 * sizeof(unsigned long long), stream));
         const bool capsule = sp_any_capsule(s->shape, n, dev);   // (every traversal launch of the loop gets its CAPSULE instantiation behind it)
         auto depenetrate = [&]() {
-            if (cfg->depenetration_iterations) { sc.prediction = nullptr; sc.prediction_all = l.skin; launch_spatial_contacts<T>(sp, sc, stream, false, capsule); }
+            if (cfg->depenetration_iterations) { sc.prediction = nullptr; sc.prediction_all = l.skin; launch_spatial_contacts<T>(sp, sc, stream, false, capsule, sp_ccap); }
             launch_spatial_slide_phase<T>(l, SPL_DEPENETRATE, stream);
         };
         launch_spatial_slide_phase<T>(l, SPL_BEGIN, stream);
@@ -451,10 +461,10 @@
         for (uint32_t it = 0; it < cfg->move_and_slide_iterations; ++it) {
             l.iteration = it;
             launch_spatial_slide_phase<T>(l, SPL_SWEEP, stream);
-            launch_spatial_cast_move<T>(sp, m, false, stream, capsule);
+            launch_spatial_cast_move<T>(sp, m, false, stream, capsule, sp_ccap);
             launch_spatial_slide_phase<T>(l, SPL_ADVANCE, stream);
             sc.prediction = l.pred;
-            launch_spatial_contacts<T>(sp, sc, stream, false, capsule);
+            launch_spatial_contacts<T>(sp, sc, stream, false, capsule, sp_ccap);
             launch_spatial_slide_phase<T>(l, SPL_PLANES, stream);
         }
         depenetrate();
@@ -610,9 +620,9 @@
             SQ<T> q = cs->q;
             q.stats = stats;
             q.n = cs->n_closest; q.index = cs->index_closest;
-            launch_spatial_casters<T>(sp, q, is_shape ? SPQ_CAST : SPQ_CLOSEST, stream, cs->any_capsule);
+            launch_spatial_casters<T>(sp, q, is_shape ? SPQ_CAST : SPQ_CLOSEST, stream, cs->any_capsule, sp_ccap);   // (sp_ccap: of the update above)
             q.n = cs->n_many; q.index = cs->index_many;
-            launch_spatial_casters<T>(sp, q, is_shape ? SPQ_CAST_HITS : SPQ_HITS, stream, cs->any_capsule);
+            launch_spatial_casters<T>(sp, q, is_shape ? SPQ_CAST_HITS : SPQ_HITS, stream, cs->any_capsule, sp_ccap);
         }
         HIPCHK(hipGetLastError());
         cs_ran = true;

@@ -8,6 +8,8 @@ library reads and writes the tensors in place).  These entry points are not part
 """
 from __future__ import annotations
 
+import os
+
 import ctypes as C
 
 import numpy as np
@@ -229,7 +231,7 @@ STRUCTS = [avn_spatial_filter, avn_spatial_rays, avn_spatial_points, avn_spatial
            avn_spatial_velocities_out, avn_spatial_moves, avn_spatial_move_hit_f32, avn_spatial_move_hit_f64, avn_spatial_move_hits_out,
            avn_spatial_characters, avn_spatial_move_and_slide_config, avn_spatial_slide_f32, avn_spatial_slide_f64, avn_spatial_slide_hit_f32,
            avn_spatial_slide_hit_f64, avn_spatial_slides_out, avn_spatial_ray_casters, avn_spatial_shape_casters, avn_spatial_caster_poses_out]
-SYMBOLS = ["avn_spatial_update", "avn_spatial_cast_rays", "avn_spatial_ray_hits", "avn_spatial_point_intersections",
+SYMBOLS = ["avn_spatial_update", "avn_spatial_capsule_colliders_set", "avn_spatial_cast_rays", "avn_spatial_ray_hits", "avn_spatial_point_intersections",
            "avn_spatial_aabb_intersections", "avn_spatial_stats_get", "avn_spatial_project_points", "avn_spatial_shape_intersections",
            "avn_spatial_cast_shapes", "avn_spatial_shape_hits", "avn_spatial_shape_contacts", "avn_spatial_depenetrate", "avn_spatial_project_velocities",
            "avn_spatial_cast_moves", "avn_spatial_move_and_slide", "avn_spatial_ray_casters_upload", "avn_spatial_shape_casters_upload",
@@ -292,9 +294,14 @@ def slide_hit_dtype(bits: int) -> np.dtype:
 
 
 def _declare(dll):
+    # (AVN_AB_OLDER_LIBRARY=1 with AVN_LIB_PATH, as in _ffi.Library: an A/B run against a build from before the switch; otherwise a missing symbol is an error)
+    switch = hasattr(dll, "avn_spatial_capsule_colliders_set") or not os.environ.get("AVN_AB_OLDER_LIBRARY")
     for name in SYMBOLS:
-        getattr(dll, name).restype = C.c_int32
+        if switch or name != "avn_spatial_capsule_colliders_set":
+            getattr(dll, name).restype = C.c_int32
     dll.avn_spatial_update.argtypes = [vp]
+    if switch:
+        dll.avn_spatial_capsule_colliders_set.argtypes = [vp, C.c_uint32]
     dll.avn_spatial_cast_rays.argtypes = [vp, vp, vp]
     dll.avn_spatial_ray_hits.argtypes = [vp, vp, C.c_uint32, vp]
     dll.avn_spatial_point_intersections.argtypes = [vp, vp, C.c_uint32, vp]
@@ -323,9 +330,12 @@ class SpatialQuery:
 
     Arguments that are torch tensors on the GPU select the device-pointer path: every array of that call must then be a contiguous tensor on
     the world's device (scalars in the world's dtype, ``solid`` uint8, masks / excluded entities int32 read as uint32), outputs come back
-    as tensors.  Otherwise everything is numpy."""
+    as tensors.  Otherwise everything is numpy.
 
-    def __init__(self, world: F.World):
+    ``capsule_colliders=True`` switches the world's capsule colliders in as candidates of every query (:meth:`set_capsule_colliders`); the
+    default leaves the world's switch as it is, which is off in a new world: capsule colliders are then left out as host shapes are."""
+
+    def __init__(self, world: F.World, capsule_colliders: bool = False):
         self.world = world
         self.dll = world.lib.dll
         if not hasattr(self.dll, "avn_spatial_update"):
@@ -343,6 +353,8 @@ class SpatialQuery:
         self.slide_hit_dtype = slide_hit_dtype(self.bits)
         self._keep = []
         self._casters = {CASTER_RAY: (0, 1), CASTER_SHAPE: (0, 1)}   # (count, hit_cap) of the last uploads
+        if capsule_colliders:
+            self.set_capsule_colliders(True)
 
     # -- plumbing ------------------------------------------------------------------------------
     def _check(self, st: int):
@@ -402,6 +414,13 @@ class SpatialQuery:
     def update(self):
         """avn_spatial_update: the LBVH of every collider at the poses the device holds now."""
         self._check(self.dll.avn_spatial_update(self.world.handle))
+
+    def set_capsule_colliders(self, enabled: bool):
+        """avn_spatial_capsule_colliders_set: whether capsule colliders are candidates of the queries.  Sticky; it invalidates the snapshot, so
+        call :meth:`update` (or :meth:`casters_run`) before the next query."""
+        if not hasattr(self.dll, "avn_spatial_capsule_colliders_set"):
+            raise ImportError(f"{self.world.lib.path} is older than avn_spatial_capsule_colliders_set")
+        self._check(self.dll.avn_spatial_capsule_colliders_set(self.world.handle, 1 if enabled else 0))
 
     def _rays(self, origin, direction, max_distance, solid, mask, excluded, skip_host_shapes):
         dev = self._is_tensor(origin)

@@ -401,8 +401,10 @@ typedef struct avn_query_manifolds_out { /* slot = AVN_MAX_QUERY_POINTS * pair +
  *      of ball_ball (dist < p, here <=).  A capsule as shape 1 against a Ball or Cuboid gives the normal and deepest penetration of the capsule query's
  *      contact (avn_spatial_shape_contacts) at the same pose up to rounding -- one P, one X, one six-axis rule serve both -- except that under a face normal
  *      with crossing cores the manifold's points are the ends of the CLIPPED segment (an end that hangs outside the face gives no support).
- *      NOT in this version: spatial queries against capsule colliders (a snapshot treats them as it treats host shapes: AVN_ERR_STATE without
- *      AVN_SPATIAL_SKIP_HOST_SHAPES, never a candidate and counted in host_skipped with it), swept CCD (avian_mi355x_ccd.h: kinds above Ball are skipped),
+ *      The spatial queries answer against capsule colliders once avn_spatial_capsule_colliders_set (avian_mi355x_spatial.h, "queries against capsule
+ *      colliders") has switched them in; by default a snapshot treats them as it treats host shapes: AVN_ERR_STATE without AVN_SPATIAL_SKIP_HOST_SHAPES,
+ *      never a candidate and counted in host_skipped with it.  The capsule-capsule manifold's closest points are sp_seg_seg, the routine those queries use.
+ *      NOT in this version: swept CCD (avian_mi355x_ccd.h: kinds above Ball are skipped),
  *      and the oracle backend (avo_colliders_upload has no capsule kind, avo_contact_manifolds rejects kind 3: there a capsule is a host shape). */
 typedef struct avn_host_aabb_query_f32 {
     uint32_t collider;          /* Entity::index() */

@@ -120,9 +120,10 @@
  *      applies PhysicsLengthUnit to max_depenetration_error and penetration_rejection_threshold.
  *    NOT covered: query shapes other than Ball / Cuboid / Capsule (cylinders, cones, hulls), contacts against AVN_SHAPE_HOST colliders, predicates, Rust declarations.
  *  - capsule query shapes (AVN_SHAPE_CAPSULE; parry's Capsule::new_y, the shape of Avian's character-controller examples).  A capsule is a
- *    QUERY shape here: every entry point that takes a query shape accepts it against Ball and Cuboid colliders.  (A capsule COLLIDER --
+ *    QUERY shape here: every entry point that takes a query shape accepts it against Ball and Cuboid colliders, and against Capsule colliders
+ *    once avn_spatial_capsule_colliders_set has switched them in ("queries against capsule colliders" below; by default a capsule COLLIDER --
  *    avian_mi355x.h "capsule colliders" -- is to these queries what a host shape is: AVN_ERR_STATE unless AVN_SPATIAL_SKIP_HOST_SHAPES is set, then
- *    never a candidate and counted in host_skipped.  Rays and casts against capsule colliders are not built.)  half_extents = (r, h, .): x the radius (as a ball keeps its radius in x), y the half length of the segment (0, -h, 0) ..
+ *    never a candidate and counted in host_skipped).  half_extents = (r, h, .): x the radius (as a ball keeps its radius in x), y the half length of the segment (0, -h, 0) ..
  *    (0, +h, 0) of the shape's frame, z not read; Collider::capsule(radius, length) is r = radius, h = length / 2.  Valid: finite r and h,
  *    both >= 0 (h == 0 is a ball, r == 0 a segment, both 0 a point), the usual finite pose, and a finite AABB
  *      [a, b] = position -+ (|qrot(rotation, (0, h, 0))| + (r, r, r))   per component (qrot: the function collider_pose uses),
@@ -165,6 +166,56 @@
  *        = query position + anchor1.  cast_move's ORIGIN-PENETRATION RULE uses this contact at prediction 0 (point1 = collider position +
  *        anchor2); depenetration, project_velocity and the slide loop read records only and are unchanged.
  *    A capsule with h == 0 answers what the Ball query of radius r answers up to rounding (tests/test_spatial_capsule_cpu.py).
+ *  - queries against capsule colliders (avn_spatial_capsule_colliders_set(w, 1); off by default, and then every answer is what it was before the
+ *    switch existed).  With the switch on a capsule collider (r_c, h_c) = (half_extents.x, half_extents.y) is a candidate of every query: its leaf
+ *    box is the capsule box [a, b] above at the collider's pose, padded like every other; host_skipped and the AVN_SPATIAL_SKIP_HOST_SHAPES rule
+ *    are about AVN_SHAPE_HOST colliders alone.  The pair tests are DEFINED HERE with their operation order (no FMA contraction); parity with
+ *    parry is UNPINNED.  The collider's core is the segment A_c + s u_c of its own frame, A_c = (0, -h_c, 0), u_c = (0, 2 h_c, 0); P, X, B and
+ *    the cylinder-and-spheres ray are the ones of "capsule query shapes" above.
+ *      S (segment - segment, A1 + s u1 against A2 + t u2, the clamped closest points; the capsule collider's manifold uses the same routine):
+ *        w = A1 - A2; a = dot(u1, u1), e = dot(u2, u2), f = dot(u2, w), c = dot(u1, w), b = dot(u1, u2); clamp = to [0, 1].  a == 0 and e == 0:
+ *        s = t = 0.  a == 0: s = 0, t = clamp(f / e).  e == 0: t = 0, s = clamp(-c / a).  Else den = a e - b b; s = 0 when !(den > 64 eps a e)
+ *        (parallel axes), else clamp((b f - c e) / den); t = (b s + f) / e; t < 0: t = 0, s = clamp(-c / a); t > 1: t = 1, s = clamp((b - c) / a).
+ *        p1 = A1 + u1 s, p2 = A2 + u2 t, d2 = |p2 - p1|^2.
+ *      ray (in the collider's frame, o_l and d_l as for the other kinds): the entry is the cylinder-and-spheres ray with R = r_c.  An origin
+ *        inside the winning primitive: solid answers distance 0 and a zero normal; not solid answers the EXIT, the largest (strict >) of, in
+ *        this order, the cylinder's far root (-b + sqrt(delta)) / a on the (x, z) components (left out when those components of d_l are both 0
+ *        or delta < 0, accepted when |o_y + d_y t| <= h_c) and the far roots of the spheres at (0, -h_c, 0) and (0, +h_c, 0) (delta = a (r_c^2 -
+ *        |f|^2) with f = o - d (b / a), left out when delta < 0).  The normal is the outward surface normal of the winning primitive at the hit
+ *        point ((p_x, 0, p_z) / |(p_x, p_z)| or p / |p|; a zero length: the zero normal), rotated by the collider's rotation.  max_distance
+ *        and the finite-distance rule as for the other kinds.
+ *      point intersection: P(A_c, u_c, point_l).d2 <= r_c^2.  AABB intersection: the capsule box against the query box.
+ *      point projection: P gives the nearest core point p_c = A_c + u_c s and d2; is_inside = d2 <= r_c^2; the projection is the ball's about
+ *        p_c: p_c + (0, r_c, 0) when d2 == 0, else p_c + (point_l - p_c) (r_c / sqrt(d2)); solid and the distance as for a ball.
+ *      S' (the DISTANCE of two segments, for the queries): S's quotient cancels for nearly parallel axes and its parallel rule sets s = 0, which
+ *        over-estimates the distance of converging or crossing cores; so six candidate (s, t) are evaluated in full, d2 = |p2 - p1|^2, and the first
+ *        with the smallest d2 wins (strict <; a NaN never wins): S's own; the interior point in its well-conditioned form, with u2p = u2 - u1 (b / a)
+ *        and wp = w - u1 (c / a): t = clamp(dot(wp, u2p) / dot(u2p, u2p)), s = clamp((b t - c) / a), t = clamp((b s + f) / e); and the four ends,
+ *        (0, clamp(f / e)), (1, clamp((b + f) / e)), (clamp(-c / a), 0), (clamp((b - c) / a), 1).  The manifold of two capsules keeps S alone.
+ *      shape intersection: a ball or a cuboid query: the capsule-query test above with the roles exchanged (the collider is the capsule, posed
+ *        in the query's frame by iso_inv_mul(make_isometry(query), {collider rotation, collider position}); the query shape is the "collider"
+ *        of that test).  A capsule query: S in the collider's frame with the collider's core as segment 1 and the query's (A, u of q above) as
+ *        segment 2, the distance by S'; they intersect iff d2 <= (r + r_c)^2.
+ *      shape cast (point1 / normal1 the collider's, point2 the query's at the impact pose; everything 0 when the shapes overlap at the start):
+ *        a ball query (radius r): its centre q.t as a ray along d_l against the capsule of radius R = r_c + r in the collider's frame (the
+ *          cylinder-and-spheres ray, not reversed), n its normal: normal1 = rot_c n; point1 = rot_c ((0, clamp(q.t_y + d_l_y t, -h_c, h_c), 0) +
+ *          n r_c) + pos_c; point2 = (pos_q + d t) + (-normal1) r.
+ *        a cuboid query: the Newton iteration of the capsule-query cast in the QUERY's frame: q' = iso_inv_mul(make_isometry(query), {collider
+ *          rotation, collider position}), the collider's core (A, u of q', h_c) moves by d' = -iso_inv_vec(make_isometry(query), d) against the
+ *          box he_q, radius r_c.  With R_q = make_isometry(query).r and c2 = pos_q + d t: normal1 = -(R_q n); point1 = R_q (p_seg - n r_c) + c2;
+ *          point2 = R_q p_box + c2.
+ *        a capsule query: the same iteration on g(t) = sqrt(S'(A_c, u_c, A + d_l t, u).d2) - (r + r_c) in the collider's frame, n = (p2 - p1) /
+ *          dist: normal1 = rot_c n; point1 = rot_c (p1 + n r_c) + pos_c; point2 = rot_c (p2 - n r) + pos_c.
+ *        The 32-round cap, the last t standing and "never an over-estimate" are those of the capsule-query cast.
+ *      contacts (shape contacts, depenetration, cast_move's origin-penetration rule, move and slide): (a), (b) with the capsule box, then the
+ *        narrow phase's capsule manifold of avian_mi355x.h "capsule colliders" with the query as shape 1 -- a ball or a cuboid query, and a
+ *        capsule query against a capsule collider alike -- and (d)'s fold: the deepest point, the later point wins a tie.  A ball's centre on the
+ *        collider's core, or two capsule cores that touch or cross, have no direction and give NO contact, as a ball's centre inside a cuboid gives
+ *        none.  A cuboid query whose box the collider's core touches or crosses DOES get the manifold's six-axis contact -- the one place where an
+ *        h_c == 0 capsule collider answers more than a Ball collider does (a Ball's centre inside a cuboid query: no contact).  A capsule query
+ *        against Ball / Cuboid colliders keeps its own contact above.
+ *    A capsule collider with h_c == 0 answers what a Ball collider of radius r_c answers up to rounding (tests/test_spatial_capsule_colliders_cpu.py).
+ *    NOT covered: swept CCD against capsule colliders, target_distance != 0, queries against AVN_SHAPE_HOST colliders.
  *  - move and slide (MoveAndSlide::cast_move, project_velocity, move_and_slide; move_and_slide.rs:464-793, velocity_project.rs).  As above the
  *    definitions are written out here with their operation order (no FMA contraction); parity with glam / parry is UNPINNED.  Common rules:
  *      Sensors are never candidates (MoveAndSlide's collider query is Without<Sensor>; cast_move's predicate enforces it for the cast too).
@@ -291,8 +342,9 @@ extern "C" {
 #endif
 
 /* A capsule (the segment (0, -h, 0) .. (0, +h, 0) swept by a ball of radius r; half_extents = (r, h, .)): a query-shape kind of this header and, on the HIP
- * backend, a collider kind (avian_mi355x.h "capsule colliders": avn_colliders_upload, avn_contact_manifolds).  The spatial queries of this header have no
- * geometry for capsule COLLIDERS yet: a snapshot treats them as host shapes.  The swept CCD skips them. */
+ * backend, a collider kind (avian_mi355x.h "capsule colliders": avn_colliders_upload, avn_contact_manifolds).  The spatial queries of this header answer
+ * against capsule COLLIDERS once avn_spatial_capsule_colliders_set has switched them in; by default a snapshot treats them as host shapes.  The swept
+ * CCD skips them. */
 enum { AVN_SHAPE_CAPSULE = 3 };
 
 /* flags of a query */
@@ -627,7 +679,7 @@ typedef struct avn_spatial_ids_out {
 typedef struct avn_spatial_stats {
     uint32_t colliders;        /* colliders in the snapshot */
     uint32_t nodes;            /* BVH nodes (2 * colliders - 1) */
-    uint32_t host_skipped;     /* AVN_SHAPE_HOST colliders in the snapshot (never candidates) */
+    uint32_t host_skipped;     /* AVN_SHAPE_HOST colliders in the snapshot (never candidates); AVN_SHAPE_CAPSULE ones too unless avn_spatial_capsule_colliders_set switched them in */
     uint32_t valid;            /* 1: the snapshot can be queried */
     uint64_t nodes_visited;    /* last query call: node boxes tested, all queries together */
     uint64_t leaves_visited;   /* last query call: exact per-collider tests run, all queries together */
@@ -636,6 +688,10 @@ typedef struct avn_spatial_stats {
 /* update_spatial_query_pipeline / SpatialQueryPipeline::update (pipeline.rs:96-133): builds the LBVH from the poses the device holds when the
  * call runs, enqueued on the world's stream after any step work.  avn_step never calls it. */
 AVN_API avn_status avn_spatial_update(avn_world* w);
+/* Capsule colliders as candidates of the queries ("queries against capsule colliders"): a sticky per-world switch, 0 (off) in a new world.  It
+ * invalidates the snapshot -- a query before the next avn_spatial_update is AVN_ERR_STATE -- and holds for every later avn_spatial_update, the
+ * one inside avn_spatial_casters_run included.  A world without a capsule collider launches the same kernels with the switch on as with it off. */
+AVN_API avn_status avn_spatial_capsule_colliders_set(avn_world* w, uint32_t enabled);
 /* SpatialQueryPipeline::cast_ray (pipeline.rs:162-231); RayCaster with max_hits = 1: per ray the closest hit within max_distance, or a miss */
 AVN_API avn_status avn_spatial_cast_rays(avn_world* w, const avn_spatial_rays* rays, const avn_spatial_hits_out* out);
 /* SpatialQueryPipeline::ray_hits (pipeline.rs:233-333); RayCaster / RayHits: per ray the max_hits nearest hits, sorted, plus the true count.

@@ -22,13 +22,20 @@
   (Collider::capsule(0.4, 1.0): r = 0.4, h = 0.5) on the poses of the legs above, each beside the same call with a Cuboid query of the capsule's
   bounding box (0.4, 0.9, 0.4) from the same run, with the node and leaf counts; and the mean Newton rounds per capsule-cuboid pair, from the
   numpy restatement (tests/spatial_capsule_reference.py) on a sample of the timed long casts
+  capsule colliders (`capcol`: this leg alone): the cfg2 poses once as they are (all cuboids) and once with every fourth collider an
+  AVN_SHAPE_CAPSULE of r = 0.3, h = 0.2 (inside the cuboid it replaces) and avn_spatial_capsule_colliders_set on, the same 262144 queries into
+  both: update, cast_rays short / long, ray_hits k = 16, point and AABB intersections, project_points, shape_intersections, shape_contacts,
+  depenetrate, cast_shapes, shape_hits k = 16, cast_moves, move_and_slide with Ball / Cuboid query shapes, and cast_shapes, shape_contacts and
+  move_and_slide with the capsule character -- per entry point the two figures side by side, the second being the CCAP instantiations' cost
 
 Every figure is the median over `reps` warmed-up calls.  The queries take torch tensors on the GPU (AVN_SPATIAL_DEVICE_POINTERS: no
 staging copies), so a call is its launches plus one stream synchronisation; the update is timed with avn_synchronize behind it.  Device
 events bracket the calls on torch's stream after a synchronisation of it, which the library's own stream joins at the call's end.
 bytes_floor: the bytes each call must move at least (inputs, outputs, the snapshot records a query touches once), for a roofline fraction
 against MI355X's 8 TB/s HBM.
-usage: python tools/time_spatial_queries.py [reps] [casters] [nocapsule]      (`casters`: that leg alone; `nocapsule`: without the capsule legs)"""
+usage: python tools/time_spatial_queries.py [reps] [casters] [capcol] [nocapsule]
+       (`casters` / `capcol`: that leg alone; `nocapsule`: without the capsule legs, for an A/B run of a library from before them;
+        AVN_LIB_PATH=path AVN_AB_OLDER_LIBRARY=1: time that (older) build of libavian_mi355x.so instead of the tree's)"""
 import json
 import os
 import sys
@@ -219,6 +226,67 @@ def newton_rounds_sample(cols, bodies, oo, dd, rr, reach=10.0, radius=2.0):
             "capsule_newton_rounds_max": int(rounds.max()) if rounds.size else 0, "capsule_newton_rounds_pairs": int(ran.sum()), "capsule_newton_rounds_casts": m}
 
 
+def capsule_colliders_leg(res, sc, w_box, reps, dev):
+    """The same queries into the all-cuboid cfg2 poses and into those poses with every fourth collider a capsule, the switch on."""
+    b = w_box.bodies_download()
+    n_col = sc.n
+    shape = np.array(sc.shape, np.uint8).copy(); he = np.array(sc.half_extents, float).copy()
+    caps = np.arange(n_col) % 4 == 1
+    shape[caps] = SHAPE_CAPSULE; he[caps] = (0.3, 0.2, 0.0)
+    w_cap = F.World(w_box.lib, F.default_config(32, substeps=4))
+    w_cap.bodies_upload(**dict(sc.body_kwargs(), **b)); w_cap.colliders_upload(**dict(sc.collider_kwargs(), shape=shape, half_extents=he))
+    g = torch.Generator(device=dev).manual_seed(3)
+    n = 262144
+    pos = torch.from_numpy(b["position"]).to(dev)
+    o = pos[torch.randint(1, n_col, (n,), device=dev, generator=g)] + torch.randn(n, 3, device=dev, generator=g) * 0.7
+    d = torch.nn.functional.normalize(torch.randn(n, 3, device=dev, generator=g), dim=1)
+    solid = (torch.arange(n, device=dev) & 1).to(torch.uint8)
+    short = torch.rand(n, device=dev, generator=g) * 2.0
+    long = torch.full((n,), 200.0, device=dev)
+    ext = torch.rand(n, 3, device=dev, generator=g)
+    small = ext * 0.25
+    kind = (torch.arange(n, device=dev) & 1).to(torch.uint8)
+    rot = torch.nn.functional.normalize(torch.randn(n, 4, device=dev, generator=g), dim=1)
+    pred = torch.full((n,), 0.05, device=dev)
+    skin = torch.full((n,), 0.01, device=dev)
+    ckind = torch.full((n,), SHAPE_CAPSULE, dtype=torch.uint8, device=dev)
+    che = torch.tensor([0.4, 0.5, 0.0], device=dev).repeat(n, 1)
+    upright = torch.tensor([0.0, 0.0, 0.0, 1.0], device=dev).repeat(n, 1)
+    cv = (d * 4.0).contiguous()
+    mcfg = dict(delta_time=0.1, skin_width=0.01, max_depenetration_error=1e-4, penetration_rejection_threshold=0.5, depenetration_iterations=4)
+    nk = 65536
+    res["capcol_queries"] = n
+    res["capcol_capsule_colliders"] = int(caps.sum())
+    for name, w in (("boxes", w_box), ("capsules", w_cap)):
+        sq = SpatialQuery(w, capsule_colliders=name == "capsules")
+
+        def upd():
+            sq.update(); w.synchronize()
+        calls = {
+            "update": upd,
+            "cast_rays_short": lambda: sq.cast_rays(o, d, short, solid), "cast_rays_long": lambda: sq.cast_rays(o, d, long, solid),
+            "ray_hits_k16_64k": lambda: sq.ray_hits(o[:nk], d[:nk], 16, long[:nk], solid[:nk]),
+            "point_intersections": lambda: sq.point_intersections(o, 8), "aabb_intersections": lambda: sq.aabb_intersections(o - ext, o + ext, 16),
+            "project_points": lambda: sq.project_points(o, solid),
+            "shape_intersections": lambda: sq.shape_intersections(kind, ext, o, rot, 16), "shape_contacts": lambda: sq.shape_contacts(kind, ext, o, rot, pred, 16),
+            "depenetrate": lambda: sq.depenetrate(kind, ext, o, rot, 0.05, 1e-4, 0.5, 4),
+            "cast_shapes_short": lambda: sq.cast_shapes(kind, small, o, rot, d, short), "shape_hits_k16_64k": lambda: sq.shape_hits(kind[:nk], small[:nk], o[:nk], rot[:nk], d[:nk], 16, long[:nk]),
+            "cast_moves": lambda: sq.cast_moves(kind, small, o, rot, cv * 0.1, skin),
+            "move_and_slide": lambda: sq.move_and_slide(kind, small, o, rot, cv, **mcfg, move_and_slide_iterations=4, hit_cap=0),
+            "capsule_query_cast_shapes_short": lambda: sq.cast_shapes(ckind, che, o, upright, d, short),
+            "capsule_query_shape_contacts": lambda: sq.shape_contacts(ckind, che, o, upright, pred, 16),
+            "capsule_query_move_and_slide": lambda: sq.move_and_slide(ckind, che, o, upright, cv, **mcfg, move_and_slide_iterations=4, hit_cap=0),
+        }
+        for key, fn in calls.items():
+            res[f"capcol_{name}_{key}_ms"] = timed(fn, reps)
+            if key != "update":
+                st = sq.stats()
+                res[f"capcol_{name}_{key}_leaves_per_query"] = st.leaves_visited / (nk if key.endswith("64k") else n)
+        res[f"capcol_{name}_host_skipped"] = sq.stats().host_skipped
+    for key in calls:
+        res[f"capcol_ratio_{key}"] = res[f"capcol_capsules_{key}_ms"] / res[f"capcol_boxes_{key}_ms"]
+
+
 def world(sc, steps):
     lib = avian_amd.load_library()
     w = F.World(lib, F.default_config(32, substeps=4))
@@ -243,6 +311,10 @@ def main():
     if "casters" in sys.argv[2:]:
         del res["timing"]          # (device events: the other legs'; this one's is res["casters_timing"])
         casters_leg(res, w2, sq, sc2, reps)
+        print(json.dumps(res))
+        return
+    if "capcol" in sys.argv[2:]:
+        capsule_colliders_leg(res, sc2, w2, reps, dev)
         print(json.dumps(res))
         return
 
@@ -389,6 +461,8 @@ def main():
         if msk:
             res[k.replace("_bytes_floor", "_hbm_fraction")] = res[k] / (res[msk] * 1e-3) / HBM
     casters_leg(res, w2, sq, sc2, reps)
+    if "nocapsule" not in sys.argv[2:]:
+        capsule_colliders_leg(res, sc2, w2, reps, dev)
     del sq, w2
     w4 = world(scenes.sparse_mixed(1_000_000), 0)
     sq4 = SpatialQuery(w4)
