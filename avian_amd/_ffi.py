@@ -211,13 +211,22 @@ class avn_swept_ccd_results_out(C.Structure):
     _fields_ = [("results", vp), ("capacity", C.c_uint32), ("count", C.c_uint32)]
 
 
+class avn_swept_ccd_stats(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("nonlinear_tested", C.c_uint32), ("rounds_max", C.c_uint32), ("exhausted", C.c_uint32)]
+
+
 SWEPT_CCD_SYMBOLS = ("avn_swept_ccd_upload", "avn_swept_ccd_results_get")
+SWEPT_CCD_NON_LINEAR_SYMBOLS = ("avn_swept_ccd_non_linear_set", "avn_swept_ccd_stats_get")   # absent from a library older than SweepMode::NonLinear
 
 
 def declare_swept_ccd(dll):
     for name in SWEPT_CCD_SYMBOLS:
         getattr(dll, name).restype = C.c_int32
         getattr(dll, name).argtypes = [vp, vp]
+    if all(hasattr(dll, name) for name in SWEPT_CCD_NON_LINEAR_SYMBOLS):
+        dll.avn_swept_ccd_non_linear_set.restype = dll.avn_swept_ccd_stats_get.restype = C.c_int32
+        dll.avn_swept_ccd_non_linear_set.argtypes = [vp, C.c_uint32]
+        dll.avn_swept_ccd_stats_get.argtypes = [vp, vp]
 
 
 class avn_slab_in(C.Structure):

@@ -582,7 +582,7 @@ template <class T> struct CCD {
     const T *lin2, *ang2;                // [n] the thresholds squared (Scalar::powi(2))
     uint32_t* own;                       // [n_bodies] the body's own collider: its lowest slot without a ColliderTransform | CCD_NONE
     uint32_t* entry;                     // [n_colliders] the entry whose own collider the slot is | CCD_NONE
-    uint32_t* ctr;                       // [1] candidates found
+    uint32_t* ctr;                       // [16] [0] candidates found, [1..3] the statistics of the last pass (CCD_CTR_*), the rest spare
     uint32_t cand_cap;
     uint2* cand;                         // [cand_cap] (row, entry << 1 | side); side 0: the CCD collider is the row's slot 1
     unsigned long long* cand_t;          // [cand_cap] bits of the candidate's time of impact | CCD_T_NONE | CCD_T_ORIGIN
@@ -590,9 +590,17 @@ template <class T> struct CCD {
     SweptCcdResult<T>* rec;              // [n]
     uint32_t *wkey_a, *wval_a, *wkey_b, *wval_b;   // [2n] the writes (target body | n_bodies = none, 2 entry + side) and the sort's second pair
     uint32_t *hist, *block_sums;         // the sort's scratch
+    // SweepMode::NonLinear: both null while the list in force has no NonLinear entry (then no _nl kernel is launched)
+    const uint32_t* mode;                // [n] AVN_SWEEP_*
+    const uint32_t* body_mode;           // [n_bodies] 1: the body is listed with AVN_SWEEP_NON_LINEAR (N0 goes by body)
 };
 #define CCD_T_NONE 0xFFFFFFFFFFFFFFFFull
 #define CCD_T_ORIGIN 0ull                // t == 0: the origin-penetration rule decides (k_ccd_origin)
+#define CCD_T_ORIGIN_NL 0xFFFFFFFFFFFFFFFEull   // t == 0 of a NonLinear pair (k_ccd_origin_nl); no accepted time has these bits (they are positive scalars)
+// CCD::ctr: [0] candidates found, then the statistics of avn_swept_ccd_stats_get (k_ccd_begin zeroes all four)
+enum { CCD_CTR_CAND = 0, CCD_CTR_NL_TESTED = 1, CCD_CTR_ROUNDS_MAX = 2, CCD_CTR_EXHAUSTED = 3 };
+// the round cap of the NonLinear pair test: the smallest power of two >= the 99.9th percentile of profiles/swept_ccd_nonlinear_rounds.txt
+#define CCD_NL_ROUNDS 64
 template <class T> void launch_ccd_tables(const DW<T>&, const BP<T>&, const CCD<T>&, hipStream_t);   // CCD::own / CCD::entry from the collider table
 // the pass: candidates, times of impact, winners, the writes in list order.  n_rows: the contact table's row high-water mark.  Returns the launches issued.
 template <class T> uint32_t launch_ccd_pass(const DW<T>&, const BP<T>&, const CT<T>&, const PG&, const CCD<T>&, const StepParams<T>&, uint32_t n_rows, hipStream_t);

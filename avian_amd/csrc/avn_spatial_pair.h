@@ -758,4 +758,55 @@ __device__ __forceinline__ bool sp_capcol_cast_exact(uint32_t shape2, V3<T> he2,
     return true;
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// swept CCD, SweepMode::NonLinear (include/avian_mi355x_ccd.h, N2): the gap of a Ball / Cuboid pair at the given poses and the unit axis n
+// (world, from collider 1 towards 2) along which it was measured.  The rotations are used as they are (no make_isometry).  Ball pairs: the
+// distance.  Cuboid - cuboid: the largest SAT separation with the narrow phase's choice among the three sweeps, a lower bound of the distance
+// that is positive exactly when the boxes are disjoint.
+template <class T>
+__device__ __forceinline__ T sp_nl_gap(uint32_t shape1, V3<T> he1, V3<T> p1, Q4<T> q1, uint32_t shape2, V3<T> he2, V3<T> p2, Q4<T> q2, V3<T>& n) {
+    const bool ball1 = shape1 == AVN_SHAPE_BALL, ball2 = shape2 == AVN_SHAPE_BALL;
+    if (ball1 && ball2) {
+        const V3<T> dv = p2 - p1;
+        const T dist = length(dv);
+        n = dist > T(0) ? dv / dist : V3<T>{T(0), T(1), T(0)};
+        return dist - (he1.x + he2.x);
+    }
+    if (ball1 || ball2) {
+        const V3<T> pc = ball1 ? p2 : p1, pb = ball1 ? p1 : p2, he = ball1 ? he2 : he1;
+        const Q4<T> qc = ball1 ? q2 : q1;
+        const T r = ball1 ? he1.x : he2.x;
+        const V3<T> l = qrot(qinverse(qc), pb - pc);   // the ball's centre in the cuboid's frame
+        const V3<T> df = l - sp_clamp3(l, he);
+        const T dist = length(df);
+        V3<T> nl;
+        T g;
+        if (dist > T(0)) { nl = df / dist; g = dist - r; }
+        else {   // the centre is inside: the nearest face (the lowest axis among equals)
+            T m = he.x - fabs_t(l.x);
+            int axis = 0;
+            const T my = he.y - fabs_t(l.y), mz = he.z - fabs_t(l.z);
+            if (my < m) { m = my; axis = 1; }
+            if (mz < m) { m = mz; axis = 2; }
+            nl = sp_unit<T>(axis, copysign_t(T(1), sp_vget(l, axis)));
+            g = -r;
+        }
+        const V3<T> nw = qrot(qc, nl);
+        n = ball1 ? -nw : nw;
+        return g;
+    }
+    const Iso<T> pos12 = iso_inv_mul(Iso<T>{q1, p1}, Iso<T>{q2, p2});
+    const Iso<T> pos21 = iso_inverse(pos12);
+    V3<T> d1, d2, d3;
+    const T sep1 = sat_normal_oneway(he1, he2, pos12, d1);
+    const T sep2 = sat_normal_oneway(he2, he1, pos21, d2);
+    const T sep3 = sat_edge_twoway(he1, he2, pos12, d3);
+    V3<T> best = d1;
+    T g = sep1;
+    if (sep2 > sep1 && sep2 > sep3) { best = iso_vec(pos12, -d2); g = sep2; }
+    else if (sep3 > sep1) { best = d3; g = sep3; }
+    n = na_qrot(q1, best);
+    return g;
+}
+
 }  // namespace avn

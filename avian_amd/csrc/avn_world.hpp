@@ -150,6 +150,8 @@ struct WorldBase {
     // swept CCD (include/avian_mi355x_ccd.h; world/ccd.hpp)
     virtual avn_status swept_ccd_upload(const avn_swept_ccd*) = 0;
     virtual avn_status swept_ccd_results_get(avn_swept_ccd_results_out*) = 0;
+    virtual avn_status swept_ccd_non_linear_set(uint32_t enabled) = 0;
+    virtual avn_status swept_ccd_stats_get(avn_swept_ccd_stats*) = 0;
 };
 
 // RCCL transport of the level-2 halo exchange (avn_comm.cpp; librccl is opened on first use)

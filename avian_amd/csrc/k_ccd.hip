@@ -1,8 +1,8 @@
-// k_ccd.hip — swept CCD (solve_swept_ccd, dynamics/ccd/mod.rs:523-687; SweepMode::Linear) as a parallel pass over the contact rows of the
+// k_ccd.hip — swept CCD (solve_swept_ccd, dynamics/ccd/mod.rs:523-687; SweepMode::Linear and NonLinear) as a parallel pass over the contact rows of the
 // device closed loop (include/avian_mi355x_ccd.h has the definition).  The reference's loop is serial (`// TODO: Parallelize.`): per SweptCcd
 // entity it walks the ContactGraph's edges of the body's collider, keeps the smallest time of impact and then rewinds both bodies.  Here:
 //
-//   k_ccd_begin        records, per-entry minima and the write list back to their empty state; the candidate counter to 0
+//   k_ccd_begin        records, per-entry minima and the write list back to their empty state; the candidate counter and the statistics to 0
 //   k_ccd_candidates   one lane per contact row: a live row with a CCD collider in slot 1 / slot 2 appends (row, entry, side), one atomic per wave
 //   k_ccd_toi          one lane per candidate, blocks of one wave (the swept SAT is register-heavy, as in k_sp_cast): the reference's filters,
 //                      the header's shape cast of the other collider against the CCD body's own along v2 - v1 with max_distance = dt; an
@@ -11,6 +11,10 @@
 //   k_ccd_origin       only with a bounded default_speculative_margin: the ORIGIN-PENETRATION RULE for the candidates that start overlapping
 //                      (the pair's contact at prediction 0, then the "small ball" fallback); a kernel of its own so that the manifold stays
 //                      out of the cast's live range, as k_sp_cast_move_resolve does it
+//   k_ccd_toi_nl       only when the list in force has a SweepMode::NonLinear entry (k_ccd_toi then skips the NonLinear pairs, rule N0): the
+//                      header's conservative advancement N1 - N3 over both bodies' linear and angular motion, at most CCD_NL_ROUNDS rounds; the
+//                      same atomicMin; the statistics of avn_swept_ccd_stats_get go into the spare words of CCD::ctr
+//   k_ccd_origin_nl    its t == 0 pairs with a bounded margin: the contact at prediction 0, then the small ball by the same advancement (N4)
 //   k_ccd_pick         among the candidates whose time equals the entry's minimum: atomicMin of (incoming << 63 | ~seq), which is the
 //                      position of the edge in the reference's `neighbors` order (outgoing edges newest first, then incoming newest first)
 //   k_ccd_resolve      the one candidate that holds both minima writes the entry's record and its two writes (target body, 2 entry + side)
@@ -54,7 +58,7 @@ __global__ __launch_bounds__(256) void k_ccd_entry(CCD<T> c) {
 template <class T>
 __global__ __launch_bounds__(256) void k_ccd_begin(CCD<T> c, uint32_t n_bodies) {
     const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-    if (i == 0) c.ctr[0] = 0u;
+    if (i == 0) { c.ctr[CCD_CTR_CAND] = 0u; c.ctr[CCD_CTR_NL_TESTED] = 0u; c.ctr[CCD_CTR_ROUNDS_MAX] = 0u; c.ctr[CCD_CTR_EXHAUSTED] = 0u; }
     if (i < c.n) {
         SweptCcdResult<T> r;
         r.toi = T(0); r.hit_collider = CCD_NONE; r.hit_body = -1; r.tested = 0u;
@@ -125,13 +129,18 @@ template <class T> __device__ __forceinline__ void ccd_accept(const CCD<T>& c, u
     if (t > T(0) && t < dt) { bits = ccd_bits(t); atomicMin(&c.min_t[e], bits); }
 }
 
-template <class T>
+// N0: the pair's mode goes by body (`body2.ccd.is_none_or(..)`): the entry's own mode, or the mode b2 is listed with
+template <class T> __device__ __forceinline__ bool ccd_pair_nl(const CCD<T>& c, const CcdPair<T>& p) { return c.mode[p.e] != 0u || c.body_mode[p.b2] != 0u; }   // (0: AVN_SWEEP_LINEAR)
+
+// MIXED: the list in force has NonLinear entries; their pairs are left to k_ccd_toi_nl (which then writes their cand_t)
+template <class T, bool MIXED>
 __global__ __launch_bounds__(CCD_WAVE) void k_ccd_toi(DW<T> w, BP<T> bp, CT<T> ct, CCD<T> c, T dt, bool origin_rule) {
     const uint32_t count = c.ctr[0] < c.cand_cap ? c.ctr[0] : c.cand_cap;
     for (uint32_t i = blockIdx.x * CCD_WAVE + threadIdx.x; i < count; i += gridDim.x * CCD_WAVE) {
         unsigned long long bits = CCD_T_NONE;
         CcdPair<T> p;
         if (ccd_pair<T>(w, bp, ct, c, c.cand[i], p)) {
+            if constexpr (MIXED) { if (ccd_pair_nl<T>(c, p)) continue; }
             atomicAdd(&c.rec[p.e].tested, 1u);
             T toi; V3<T> p1, p2, n1;
             if (sp_cast_exact<T>(p.shape2, p.he2, make_isometry(p.pos2, p.rot2), p.d, dt, p.shape1, p.he1, p.pos1, p.rot1, toi, p1, p2, n1)) {
@@ -167,6 +176,108 @@ __global__ __launch_bounds__(CCD_WAVE) void k_ccd_origin(DW<T> w, BP<T> bp, CT<T
                 T toi; V3<T> p1, p2, n1;
                 if (sp_cast_exact<T>(AVN_SHAPE_BALL, V3<T>{margin, margin, margin}, make_isometry(p.pos2, p.rot2), p.d, dt, p.shape1, p.he1, p.pos1, p.rot1, toi, p1, p2, n1))
                     ccd_accept<T>(c, p.e, toi, dt, bits);
+            }
+        }
+        c.cand_t[i] = bits;
+    }
+}
+
+// ---- SweepMode::NonLinear (the header's N1 - N4) ----
+// N1: a body's motion over the step, always evaluated from its step-start pose
+template <class T> struct CcdMotion { V3<T> c0, v, om, com; Q4<T> rot; T R; };
+template <class T> __device__ __forceinline__ T ccd_rho(uint32_t shape, V3<T> he) { return shape == AVN_SHAPE_BALL ? he.x : length(he); }
+template <class T> __device__ __forceinline__ CcdMotion<T> ccd_motion(const DW<T>& w, uint32_t b, V3<T> pos, Q4<T> rot, T rho) {
+    CcdMotion<T> m;
+    const bool has = meta_has_solver_body(w.bmeta[b]);
+    m.v = has ? xyz<T>(w.sb_lin[b]) : vzero<T>();
+    m.om = has ? xyz<T>(w.sb_ang[b]) : vzero<T>();
+    m.com = xyz<T>(w.com[b]);
+    m.rot = rot;
+    m.c0 = pos + qrot(rot, m.com);
+    m.R = length(m.com) + rho;
+    return m;
+}
+template <class T> __device__ __forceinline__ void ccd_pose(const CcdMotion<T>& m, T t, V3<T>& p, Q4<T>& q) {
+    q = qmul(from_scaled_axis(m.om * t), m.rot);
+    p = (m.c0 + t * m.v) - qrot(q, m.com);
+}
+// N3: conservative advancement from t = 0.  1: a hit at t_out, 0: a miss, 2: out of rounds (answers nothing)
+template <class T>
+__device__ __forceinline__ int ccd_nl_advance(uint32_t shape1, V3<T> he1, const CcdMotion<T>& m1, uint32_t shape2, V3<T> he2, const CcdMotion<T>& m2, V3<T> d, T dt, T tol,
+                                              T& t_out, uint32_t& rounds) {
+    T t = T(0);
+    for (uint32_t r = 0; r < CCD_NL_ROUNDS; ++r) {
+        rounds = r + 1u;
+        V3<T> p1, p2, n;
+        Q4<T> q1, q2;
+        ccd_pose<T>(m1, t, p1, q1);
+        ccd_pose<T>(m2, t, p2, q2);
+        const T g = sp_nl_gap<T>(shape1, he1, p1, q1, shape2, he2, p2, q2, n);
+        if (g <= tol) { t_out = t; return 1; }
+        const T B = (-dot(d, n) + length(cross(m1.om, n)) * m1.R) + length(cross(m2.om, n)) * m2.R;
+        if (!(B > T(0))) return 0;
+        const T tn = t + g / B;
+        if (tn > dt) return 0;
+        if (!(tn > t)) { t_out = t; return 1; }
+        t = tn;
+    }
+    return 2;
+}
+template <class T> __device__ __forceinline__ void ccd_nl_stats(const CCD<T>& c, int res, uint32_t rounds) {
+    atomicMax(&c.ctr[CCD_CTR_ROUNDS_MAX], rounds);
+    if (res == 2) atomicAdd(&c.ctr[CCD_CTR_EXHAUSTED], 1u);
+}
+
+template <class T>
+__global__ __launch_bounds__(CCD_WAVE) void k_ccd_toi_nl(DW<T> w, BP<T> bp, CT<T> ct, CCD<T> c, T dt, T tol, bool origin_rule) {
+    const uint32_t count = c.ctr[0] < c.cand_cap ? c.ctr[0] : c.cand_cap;
+    for (uint32_t i = blockIdx.x * CCD_WAVE + threadIdx.x; i < count; i += gridDim.x * CCD_WAVE) {
+        CcdPair<T> p;
+        if (!ccd_pair<T>(w, bp, ct, c, c.cand[i], p) || !ccd_pair_nl<T>(c, p)) continue;   // (k_ccd_toi wrote the candidate's cand_t)
+        atomicAdd(&c.rec[p.e].tested, 1u);
+        atomicAdd(&c.ctr[CCD_CTR_NL_TESTED], 1u);
+        const CcdMotion<T> m1 = ccd_motion<T>(w, p.b1, p.pos1, p.rot1, ccd_rho<T>(p.shape1, p.he1));
+        const CcdMotion<T> m2 = ccd_motion<T>(w, p.b2, p.pos2, p.rot2, ccd_rho<T>(p.shape2, p.he2));
+        T toi = T(0);
+        uint32_t rounds = 0u;
+        const int res = ccd_nl_advance<T>(p.shape1, p.he1, m1, p.shape2, p.he2, m2, p.d, dt, tol, toi, rounds);
+        ccd_nl_stats<T>(c, res, rounds);
+        unsigned long long bits = CCD_T_NONE;
+        if (res == 1) {
+            if (toi == T(0)) { if (origin_rule) bits = CCD_T_ORIGIN_NL; }
+            else ccd_accept<T>(c, p.e, toi, dt, bits);
+        }
+        c.cand_t[i] = bits;
+    }
+}
+
+// N4: step 4 for the NonLinear pairs that start within the tolerance.  The contact runs first and only `leaving` survives it, so the manifold
+// stays out of the advancement loop's live range.
+template <class T>
+__global__ __launch_bounds__(CCD_WAVE) void k_ccd_origin_nl(DW<T> w, BP<T> bp, CT<T> ct, CCD<T> c, T dt, T tol, T margin) {
+    const uint32_t count = c.ctr[0] < c.cand_cap ? c.ctr[0] : c.cand_cap;
+    for (uint32_t i = blockIdx.x * CCD_WAVE + threadIdx.x; i < count; i += gridDim.x * CCD_WAVE) {
+        if (c.cand_t[i] != CCD_T_ORIGIN_NL) continue;
+        unsigned long long bits = CCD_T_NONE;
+        CcdPair<T> p;
+        if (ccd_pair<T>(w, bp, ct, c, c.cand[i], p)) {
+            SpDeepestSink<T> sink{vzero<T>(), T(0), 0};
+            V3<T> nrm;
+            const V3<T> hq = p.shape2 == AVN_SHAPE_BALL ? V3<T>{p.he2.x, p.he2.x, p.he2.x} : p.he2;
+            bool leaving = false;
+            if (contact_manifolds_pair_sink<T, SpDeepestSink<T>>(p.shape2, hq, p.pos2, p.rot2, p.shape1, p.he1, p.pos1, p.rot1, T(0), sink, nrm)) {
+                const V3<T> cn{-nrm.x, -nrm.y, -nrm.z};
+                leaving = p.d.x * cn.x + p.d.y * cn.y + p.d.z * cn.z >= T(0);
+            }
+            if (!leaving) {
+                // the "small ball" rides body 2's motion: shape 2 = Ball(margin) at body 2's origin, rho = margin
+                const CcdMotion<T> m1 = ccd_motion<T>(w, p.b1, p.pos1, p.rot1, ccd_rho<T>(p.shape1, p.he1));
+                const CcdMotion<T> m2 = ccd_motion<T>(w, p.b2, p.pos2, p.rot2, margin);
+                T toi = T(0);
+                uint32_t rounds = 0u;
+                const int res = ccd_nl_advance<T>(p.shape1, p.he1, m1, AVN_SHAPE_BALL, V3<T>{margin, margin, margin}, m2, p.d, dt, tol, toi, rounds);
+                ccd_nl_stats<T>(c, res, rounds);
+                if (res == 1) ccd_accept<T>(c, p.e, toi, dt, bits);
             }
         }
         c.cand_t[i] = bits;
@@ -248,7 +359,13 @@ template <class T> uint32_t launch_ccd_pass(const DW<T>& w, const BP<T>& bp, con
     const uint32_t most = 2u * n_rows < c.cand_cap ? 2u * n_rows : c.cand_cap;
     const uint32_t wave_blocks = std::min<uint32_t>((most + CCD_WAVE - 1) / CCD_WAVE, 8192u), flat_blocks = std::min<uint32_t>((most + 255) / 256, 2048u);
     const bool origin_rule = p.default_speculative_margin < Limits<T>::max;
-    hipLaunchKernelGGL(k_ccd_toi<T>, dim3(wave_blocks), dim3(CCD_WAVE), 0, s, w, bp, ct, c, p.dt_adj, origin_rule); ++launches;
+    const bool nl = c.mode != nullptr;   // the list in force has a NonLinear entry: known since the upload
+    if (!nl) { hipLaunchKernelGGL((k_ccd_toi<T, false>), dim3(wave_blocks), dim3(CCD_WAVE), 0, s, w, bp, ct, c, p.dt_adj, origin_rule); ++launches; }
+    else {
+        hipLaunchKernelGGL((k_ccd_toi<T, true>), dim3(wave_blocks), dim3(CCD_WAVE), 0, s, w, bp, ct, c, p.dt_adj, origin_rule); ++launches;
+        hipLaunchKernelGGL(k_ccd_toi_nl<T>, dim3(wave_blocks), dim3(CCD_WAVE), 0, s, w, bp, ct, c, p.dt_adj, p.contact_tolerance, origin_rule); ++launches;
+        if (origin_rule) { hipLaunchKernelGGL(k_ccd_origin_nl<T>, dim3(wave_blocks), dim3(CCD_WAVE), 0, s, w, bp, ct, c, p.dt_adj, p.contact_tolerance, p.default_speculative_margin); ++launches; }
+    }
     if (origin_rule) { hipLaunchKernelGGL(k_ccd_origin<T>, dim3(wave_blocks), dim3(CCD_WAVE), 0, s, w, bp, ct, c, p.dt_adj, p.default_speculative_margin); ++launches; }
     hipLaunchKernelGGL(k_ccd_pick<T>, dim3(flat_blocks), dim3(256), 0, s, c, pg.seq); ++launches;
     hipLaunchKernelGGL(k_ccd_resolve<T>, dim3(flat_blocks), dim3(256), 0, s, w, bp, ct, c, pg.seq); ++launches;

@@ -1,5 +1,6 @@
 """ctypes binding of ``include/avian_mi355x_ccd.h``: the SweptCcd list of a :class:`avian_amd._ffi.World` in device closed-loop mode and
-the records its pass leaves per step (``SweepMode::Linear``, Ball / Cuboid colliders)."""
+the records its pass leaves per step (``SweepMode::Linear`` and, behind :meth:`SweptCcd.set_non_linear`, ``SweepMode::NonLinear``; Ball /
+Cuboid colliders)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -22,7 +23,7 @@ def result_dtype(bits: int) -> np.dtype:
 class SweptCcd:
     """The SweptCcd components of one world, in the order of Avian's ``Query<Entity, With<SweptCcd>>``."""
 
-    def __init__(self, world: F.World):
+    def __init__(self, world: F.World, non_linear: bool = False):
         self.world = world
         self.dll = world.lib.dll
         if not hasattr(self.dll, "avn_swept_ccd_upload"):
@@ -30,6 +31,23 @@ class SweptCcd:
         F.declare_swept_ccd(self.dll)
         self.result_dtype = result_dtype(world.cfg.scalar_bits)
         self.count = 0
+        if non_linear:
+            self.set_non_linear(True)
+
+    def set_non_linear(self, enabled: bool):
+        """avn_swept_ccd_non_linear_set: whether :meth:`upload` accepts ``SWEEP_NON_LINEAR`` (sticky, off in a new world).  Turning it off while
+        the list in force holds a NonLinear entry raises (AVN_ERR_STATE)."""
+        if not hasattr(self.dll, "avn_swept_ccd_non_linear_set"):
+            raise ImportError(f"{self.world.lib.path} is older than avn_swept_ccd_non_linear_set")
+        self.world._check(self.dll.avn_swept_ccd_non_linear_set(self.world.handle, 1 if enabled else 0))
+
+    def stats(self) -> dict:
+        """avn_swept_ccd_stats_get: nonlinear_tested, rounds_max and exhausted of the last step's pass (waits for it)."""
+        if not hasattr(self.dll, "avn_swept_ccd_stats_get"):
+            raise ImportError(f"{self.world.lib.path} is older than avn_swept_ccd_stats_get")
+        o = F.avn_swept_ccd_stats(C.sizeof(F.avn_swept_ccd_stats), 0, 0, 0)
+        self.world._check(self.dll.avn_swept_ccd_stats_get(self.world.handle, C.byref(o)))
+        return dict(nonlinear_tested=int(o.nonlinear_tested), rounds_max=int(o.rounds_max), exhausted=int(o.exhausted))
 
     def upload(self, body, mode=None, include_dynamic=None, linear_threshold=None, angular_threshold=None):
         """Replaces the list; an empty ``body`` clears it.  Defaults are SweptCcd::default(): Linear, include_dynamic, thresholds 0."""

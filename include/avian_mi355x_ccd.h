@@ -4,7 +4,8 @@
  * Mirrors `solve_swept_ccd` (ccd/mod.rs:523-687), the system of PhysicsStepSystems::Solver that the reference schedules after
  * SolverSystems::PostSubstep and before SolverSystems::Restitution (ccd/mod.rs:257-261): per SweptCcd body it finds the first time of impact
  * against the colliders whose AABBs its own collider's AABB intersects and moves both bodies back to that time, so that a fast body stops
- * at a thin wall instead of passing through it.  Only SweepMode::Linear is built, for Ball / Cuboid colliders; the pass runs on the world's
+ * at a thin wall instead of passing through it.  SweepMode::Linear and, behind avn_swept_ccd_non_linear_set, SweepMode::NonLinear (Avian's
+ * default, which also follows the bodies' rotation) are built, for Ball / Cuboid colliders; the pass runs on the world's
  * stream between the substep loop and the restitution pass of avn_step / AVN_SYS_SOLVER, and nothing is read back.  A world without a list
  * launches, stamps and allocates nothing for it.
  *
@@ -38,8 +39,43 @@
  *     delta_rotation(b1) in integrate_positions' arithmetic (the product with the FULL step's delta_rotation is the reference's behaviour);
  *     the same two writes to b2 with its own v2, w2 when b2 has a SolverBody.  When several entries write one body the result is what the
  *     serial loop leaves: the last delta_position, the delta_rotations multiplied in list order.  Velocities are never changed.
- * NOT covered: SweepMode::NonLinear (the upload refuses it), shapes other than Ball / Cuboid, child and host-shape colliders as targets,
- * level-2 / sharded worlds, the host-bookkeeping closed loop, 2D, Rust declarations.
+ *
+ * SweepMode::NonLinear (`NonlinearRigidMotion` + parry's cast_shapes_nonlinear in the reference; iterative there too, so it is DEFINED here
+ * and parity with parry stays UNPINNED; k_ccd.hip and tests/swept_ccd_nonlinear_reference.py follow it at tolerance 0).  Steps 1, 2, 5 and 6
+ * hold unchanged; steps 3 and 4 of a NonLinear pair are N1 - N4.  Every operation is in the world's scalar, without fused multiply-adds,
+ * with avn_math.h's dot / cross / length / qrot / qmul / from_scaled_axis in the association written here.
+ *  N0. the pair's mode: NonLinear iff the entry's mode is AVN_SWEEP_NON_LINEAR or b2 is itself in the list with AVN_SWEEP_NON_LINEAR
+ *      (`body2.ccd.is_none_or(..)`, ccd/mod.rs:621-627).  This goes by BODY: a listed b2 whose colliders are all children counts.
+ *  N1. the motion of body k (k = 1, 2) with step-start pos_k, rot_k, local centre of mass com_k and SolverBody v_k, w_k (0 without one):
+ *      c0_k = pos_k + qrot(rot_k, com_k);  q_k(t) = qmul(from_scaled_axis(w_k * t), rot_k) (not renormalised);
+ *      p_k(t) = (c0_k + t * v_k) - qrot(q_k(t), com_k).  Every round evaluates from the step-start pose; nothing is accumulated.
+ *  N2. the gap g and a unit axis n (world, from collider 1 towards 2) at the poses (p_1, q_1), (p_2, q_2), the rotations used as they are:
+ *      ball - ball: dv = p_2 - p_1, dist = length(dv), g = dist - (r_1 + r_2), n = dv / dist, or (0, 1, 0) when !(dist > 0).
+ *      ball - cuboid: l = qrot(conj(q_c), p_b - p_c), df = l - clamp(l, -he, he), dist = length(df).  dist > 0: g = dist - r, nl = df / dist.
+ *        Otherwise (the centre is inside) g = -r and nl = the unit axis i of the smallest he_i - |l_i| (the lowest i among equals) with the
+ *        sign of l_i.  n = qrot(q_c, nl) when the cuboid is collider 1, its negation when the ball is.
+ *      cuboid - cuboid: pos12 = iso_inv_mul((q_1, p_1), (q_2, p_2)), pos21 = iso_inverse(pos12); sep1 = sat_normal_oneway(he1, he2, pos12),
+ *        sep2 = sat_normal_oneway(he2, he1, pos21), sep3 = sat_edge_twoway(he1, he2, pos12) (avn_narrow.h, nalgebra's arithmetic); the narrow
+ *        phase's choice: (g, nl) = (sep2, iso_vec(pos12, -d2)) when sep2 > sep1 and sep2 > sep3, else (sep3, d3) when sep3 > sep1, else
+ *        (sep1, d1); n = na_qrot(q_1, nl).  g is a lower bound of the distance that is positive exactly when the boxes are disjoint, which is
+ *        all conservative advancement needs.
+ *  N3. conservative advancement.  d = v_2 - v_1; R_k = length(com_k) + rho_k with rho = r (ball) or length(half_extents) (cuboid);
+ *      tol = contact_tolerance * length_unit, the project's own number for "touching".  t = 0; at most CCD_NL_ROUNDS (64) rounds of:
+ *        evaluate (g, n) at t.  g <= tol: a hit at t.
+ *        B = (-dot(d, n) + length(cross(w_1, n)) * R_1) + length(cross(w_2, n)) * R_2: no faster can the separation along the fixed axis n
+ *        shrink, and that separation is a lower bound of the distance.  !(B > 0): a miss.
+ *        tn = t + g / B.  tn > dt: a miss.  !(tn > t): a hit at t (no progress).  Otherwise t = tn.
+ *      Out of rounds: the pair answers NOTHING and counts in avn_swept_ccd_stats::exhausted (the advancement converges from the left: "the
+ *      last t standing" of a pair that never touches would freeze its bodies in time every step).  A hit with 0 < t < dt is a candidate of
+ *      step 5.  With contact_tolerance == 0 only g <= 0 or no progress ends in a hit.  Resting bodies sit within tol, answer t == 0 and go
+ *      through N4 instead of being rewound every step.
+ *  N4. t == 0 (a hit in the first round): step 4 as it stands, the contact at prediction 0 at the step-start poses and the leaving test with
+ *      d; the small-ball fallback is the loop N3 with shape 2 = Ball(default_speculative_margin * length_unit) at body 2's origin riding body
+ *      2's motion, rho_2 = that radius.  With an unbounded margin it is not evaluated and answers nothing.
+ * `tested` counts NonLinear pair tests too.  A list without a NonLinear entry launches exactly the kernels of a Linear-only library and leaves
+ * the same bytes, whatever the switch says.
+ * NOT covered: shapes other than Ball / Cuboid (capsules are skipped in both modes), child and host-shape colliders as targets, parity with
+ * parry's nonlinear search, level-2 / sharded worlds, the host-bookkeeping closed loop, 2D, Rust declarations.
  */
 #ifndef AVIAN_MI355X_CCD_H
 #define AVIAN_MI355X_CCD_H
@@ -58,7 +94,7 @@ typedef struct avn_swept_ccd {
     uint32_t struct_size;             /* sizeof(avn_swept_ccd) */
     uint32_t count;                   /* n; 0 clears the list */
     const uint32_t* body;             /* [n] body-table index; each body at most once */
-    const uint32_t* mode;             /* [n] AVN_SWEEP_LINEAR (AVN_SWEEP_NON_LINEAR is refused) */
+    const uint32_t* mode;             /* [n] AVN_SWEEP_LINEAR; AVN_SWEEP_NON_LINEAR only after avn_swept_ccd_non_linear_set(w, 1) */
     const uint32_t* include_dynamic;  /* [n] 0: dynamic bodies are not tested */
     const double* linear_threshold;   /* [n] */
     const double* angular_threshold;  /* [n] */
@@ -85,14 +121,27 @@ typedef struct avn_swept_ccd_results_out {
     uint32_t count;         /* out: entries of the last pass; 0 if no pass has run since the list was uploaded */
 } avn_swept_ccd_results_out;
 
+/* what the last pass did under SweepMode::NonLinear; the counters live on the device and nothing is read back during a step */
+typedef struct avn_swept_ccd_stats {
+    uint32_t struct_size;       /* in: sizeof(avn_swept_ccd_stats) */
+    uint32_t nonlinear_tested;  /* pair tests that ran under N1 - N3 (the fallback of N4 is not counted, as in `tested`) */
+    uint32_t rounds_max;        /* the most rounds one advancement took (the fallback's included) */
+    uint32_t exhausted;         /* advancements that ran out of CCD_NL_ROUNDS rounds and answered nothing */
+} avn_swept_ccd_stats;
+
 /* Replaces the world's list (NULL or count 0 clears it).  AVN_ERR_BAD_ARG, with the previous list left in force: a mode other than
- * AVN_SWEEP_LINEAR, a body index outside the body table, a body named twice, a null array.  AVN_ERR_STATE: level-2 (halo plan) and
+ * AVN_SWEEP_LINEAR (with the switch below on: other than the two modes), a body index outside the body table, a body named twice, a null array.  AVN_ERR_STATE: level-2 (halo plan) and
  * avn_dshard worlds.  avn_bodies_upload with another body count and avn_despawn clear the list: its indices are stale.
  * With a non-empty list avn_step and AVN_SYS_SOLVER return AVN_ERR_STATE, before doing anything, unless the world is in device closed-loop
  * mode (avn_pipeline_enable(w, 1)): the pass reads the contact table that mode keeps. */
 AVN_API avn_status avn_swept_ccd_upload(avn_world* w, const avn_swept_ccd* list);
 /* The records of the last step's pass (waits for it).  More entries than `capacity`: AVN_ERR_CAPACITY with `count` set. */
 AVN_API avn_status avn_swept_ccd_results_get(avn_world* w, avn_swept_ccd_results_out* out);
+/* Whether avn_swept_ccd_upload accepts AVN_SWEEP_NON_LINEAR, per entry.  Sticky; off in a new world, where the upload refuses the mode as it
+ * always has.  Turning it off while the list in force holds a NonLinear entry: AVN_ERR_STATE, the switch and the list unchanged. */
+AVN_API avn_status avn_swept_ccd_non_linear_set(avn_world* w, uint32_t enabled);
+/* The statistics of the last step's pass (waits for it); zeros if no pass has run since the list was uploaded. */
+AVN_API avn_status avn_swept_ccd_stats_get(avn_world* w, avn_swept_ccd_stats* out);
 
 #ifdef __cplusplus
 }

@@ -9,9 +9,16 @@ usage: python tools/time_swept_ccd.py MODE [repeats]
   bullets         1 000 balls (r = 0.1, AVN_COLLIDER_SWEPT_CCD, SpeculativeMargin 0) parked over the pile from the start, listed, and fired
                   down at 300 units / s after the settling steps: per step the wall time, swept_ccd_ms and the number of entries with a hit.
   bullets_nolist  the same scene and shots without the list (what the steps cost when the bullets tunnel into the pile instead).
+  bullets_nl      the same 1 000 bullets, spinning at (20, 0, 35) rad / s and listed with SweepMode::NonLinear (avn_swept_ccd_non_linear_set on):
+                  per step also nonlinear_tested, rounds_max and exhausted of avn_swept_ccd_stats_get.
+  ab OLDER [repeats]
+                  a same-box A/B of `nolist` and `bullets` (1 000 Linear bullets) against an older build of the library (the parent commit's
+                  libavian_mi355x.so): child processes, alternating older / this tree, `repeats` runs a side, the side that goes first alternating too.  Per leg one summary line: the
+                  older library's min .. max over its repeats, this tree's, and whether this tree's median lies inside the older one's range.
 One JSON line per run."""
 import json
 import os
+import subprocess
 import sys
 import time
 
@@ -47,8 +54,44 @@ def tables(with_bullets):
     return bodies, cols, n, bullets
 
 
+def leg_metrics(mode, out):
+    """What one run of a leg is judged by."""
+    if mode == "nolist":
+        return dict(ms_per_step=out["median"])
+    steps = out["steps"]
+    return dict(device_step_ms=float(np.median([r["device_step_ms"] for r in steps])), swept_ccd_ms=float(np.median([r["swept_ccd_ms"] for r in steps])),
+                first_step_swept_ccd_ms=steps[0]["swept_ccd_ms"])
+
+
+def ab(older, repeats):
+    here = os.path.abspath(__file__)
+    for mode in ("nolist", "bullets"):
+        runs = {"older": [], "this": []}
+        for rep in range(repeats):
+            for side in (("older", "this") if rep % 2 == 0 else ("this", "older")):   # alternating, and the side that goes first alternates too
+                env = dict(os.environ)
+                env.pop("AVN_LIB_PATH", None); env.pop("AVN_AB_OLDER_LIBRARY", None)
+                if side == "older":
+                    env.update(AVN_LIB_PATH=os.path.abspath(older), AVN_AB_OLDER_LIBRARY="1")
+                r = subprocess.run([sys.executable, here, mode, "5"], env=env, capture_output=True, text=True, timeout=600)
+                if r.returncode != 0:
+                    print(json.dumps(dict(mode=mode, side=side, error=r.stderr[-400:])), flush=True)
+                    sys.exit(1)
+                out = json.loads(r.stdout.strip().splitlines()[-1])
+                runs[side].append(leg_metrics(mode, out))
+                print(json.dumps(dict(ab=mode, side=side, library=out["library"], **{k: round(v, 4) for k, v in runs[side][-1].items()})), flush=True)
+        for key in runs["this"][0]:
+            o, t = [r[key] for r in runs["older"]], [r[key] for r in runs["this"]]
+            med = float(np.median(t))
+            print(json.dumps(dict(ab=mode, metric=key, older_min=round(min(o), 4), older_median=round(float(np.median(o)), 4), older_max=round(max(o), 4),
+                                  this_min=round(min(t), 4), this_median=round(med, 4), this_max=round(max(t), 4), this_median_inside_older_range=bool(min(o) <= med <= max(o)),
+                                  difference_of_medians=round(med - float(np.median(o)), 4))), flush=True)
+
+
 def main():
     mode = sys.argv[1] if len(sys.argv) > 1 else "nolist"
+    if mode == "ab":
+        return ab(sys.argv[2], int(sys.argv[3]) if len(sys.argv) > 3 else 3)
     repeats = int(sys.argv[2]) if len(sys.argv) > 2 else 5
     with_bullets = mode.startswith("bullets")
     lib = avian_amd.load_library()
@@ -58,10 +101,10 @@ def main():
     w.existing_pairs_upload(np.zeros(0, np.uint64)); w.collider_materials_upload(friction=0.5)
     w.pipeline_enable()
     ccd = None
-    if mode in ("all", "bullets"):
-        from avian_amd.swept_ccd import SweptCcd
-        ccd = SweptCcd(w)
-        ccd.upload(bullets if mode == "bullets" else np.arange(n, dtype=np.uint32))
+    if mode in ("all", "bullets", "bullets_nl"):
+        from avian_amd.swept_ccd import SWEEP_LINEAR, SWEEP_NON_LINEAR, SweptCcd
+        ccd = SweptCcd(w, non_linear=mode == "bullets_nl")
+        ccd.upload(bullets if with_bullets else np.arange(n, dtype=np.uint32), mode=SWEEP_NON_LINEAR if mode == "bullets_nl" else SWEEP_LINEAR)
     for _ in range(SETTLE):
         w.step()
     w.synchronize()
@@ -84,6 +127,8 @@ def main():
         for key in ("position", "rotation", "linear_velocity", "angular_velocity"):
             kw[key] = state[key].astype(np.float64)
         kw["linear_velocity"][bullets] = [0.0, -300.0, 0.0]
+        if mode == "bullets_nl":
+            kw["angular_velocity"][bullets] = [20.0, 0.0, 35.0]
         w.bodies_upload(**kw)
         rows = []
         for s in range(repeats * 2):
@@ -92,6 +137,8 @@ def main():
             if ccd is not None:
                 rec = ccd.results()
                 row.update(swept_ccd_ms=round(w.diagnostics().swept_ccd_ms, 4), tested=int(rec["tested"].sum()), hits=int((rec["hit_body"] >= 0).sum()))
+                if mode == "bullets_nl":
+                    row.update(ccd.stats())
             rows.append(row)
         out.update(steps=rows, lowest_bullet_y=round(float(w.bodies_download()["position"][bullets, 1].min()), 3))
     print(json.dumps(out), flush=True)
