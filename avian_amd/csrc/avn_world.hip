@@ -1,6 +1,7 @@
 // avn_world.hip — host orchestration of the MI355X physics step (see avn_world.hpp).
 #include "avn_world.hpp"
 #include "avn_islands.hpp"
+#include "avn_stage.h"
 
 #include <algorithm>
 #include <array>
@@ -205,8 +206,7 @@ template <class T> struct World : WorldBase {
     uint64_t pg_dump_step = 0;
     Pinned pin_ctr;
     SweepScratch sweep_scratch{nullptr, nullptr, nullptr, nullptr, 0, nullptr};
-    DevBuf stage;  // staging arena for uploads/downloads
-    size_t stage_off = 0;
+    DevBuf stage;  // staging arena for uploads/downloads (StagePlan)
     // host state
     uint32_t color_offsets[AVN_GRAPH_COLOR_COUNT + 1];
     uint32_t grid_blocks[AVN_GRAPH_COLOR_COUNT];      // launch grids (captured into the graph with slack)
@@ -386,33 +386,50 @@ template <class T> struct World : WorldBase {
     }
 
     // ---- staging arena ---------------------------------------------------------------------------------
-    avn_status stage_reserve(size_t bytes) {
-        hipError_t err;
-        HIPCHK(hipStreamSynchronize(stream));  // arena reuse: previous users must be done
-        if (stream_bp) HIPCHK(hipStreamSynchronize(stream_bp));
-        stage.ensure(bytes + 4096, err);
-        if (err != hipSuccess) { error = "staging allocation failed"; return AVN_ERR_OOM; }
-        stage_off = 0;
-        return AVN_OK;
-    }
-    template <class U> U* stage_alloc(size_t count) {
-        stage_off = (stage_off + 63) & ~(size_t)63;
-        U* r = (U*)((char*)stage.p + stage_off);
-        stage_off += count * sizeof(U);
-        return r;
-    }
-    template <class U> avn_status stage_in(const void* host, size_t count, const U** out) {
-        if (!host || count == 0) { *out = nullptr; return AVN_OK; }
-        U* d = stage_alloc<U>(count);
-        HIPCHK(hipMemcpyAsync(d, host, count * sizeof(U), hipMemcpyHostToDevice, stream));
-        *out = d;
-        return AVN_OK;
-    }
-    template <class U> avn_status stage_out(void* host, const U* dev, size_t count) {
-        if (!host || !dev || count == 0) return AVN_OK;
-        HIPCHK(hipMemcpyAsync(host, dev, count * sizeof(U), hipMemcpyDeviceToHost, stream));
-        return AVN_OK;
-    }
+    // Every host-facing call moves its arrays through one arena by a StagePlan: it declares each array once, commit() sizes and reserves the
+    // arena from that list (avn_stage.h), hands out the device pointers and issues the uploads; after the launches finish() issues the
+    // downloads.  All copies are hipMemcpyAsync on `stream`, in declaration order.  Device pointers are valid from commit() on.
+    struct StagePlan {
+        World& w;
+        std::string& error;   // (HIPCHK's)
+        const bool direct;    // AVN_SPATIAL_DEVICE_POINTERS: in() / out() arrays are the caller's device pointers, used as they are
+        avn_stage::Layout l;
+        explicit StagePlan(World& w_, bool direct_ = false) : w(w_), error(w_.error), direct(direct_) {}
+        // an input staged from the host whatever `direct` says
+        template <class U> void staged(const void* host, size_t count, const U** dev) { l.add(avn_stage::IN, host, count, sizeof(U), (void**)dev); }
+        template <class U> void in(const void* host, size_t count, const U** dev) {
+            if (direct) *dev = host && count ? (const U*)host : nullptr; else staged(host, count, dev);
+        }
+        template <class U> void in(const void* host, size_t count, U** dev) { in(host, count, (const U**)dev); }   // (a stage struct shared with the download direction)
+        // an output: arena space, copied to `host` by finish(); a null `host` (an optional output the caller left out) gets a null pointer
+        template <class U> void out(void* host, size_t count, U** dev) {
+            if (direct) *dev = host && count ? (U*)host : nullptr; else l.add(avn_stage::OUT, host, count, sizeof(U), (void**)dev);
+        }
+        template <class U> void scratch(size_t count, U** dev) { l.add(avn_stage::SCRATCH, nullptr, count, sizeof(U), (void**)dev); }
+        size_t bytes() const { return l.total; }
+        avn_status commit() {
+            if (!l.ok) { error = "staging: more arrays than a plan holds, or a size beyond size_t"; return AVN_ERR_BAD_ARG; }
+            hipError_t err;
+            HIPCHK(hipStreamSynchronize(w.stream));  // arena reuse: previous users must be done
+            if (w.stream_bp) HIPCHK(hipStreamSynchronize(w.stream_bp));
+            w.stage.ensure(l.total + 4096, err);
+            if (err != hipSuccess) { error = "staging allocation failed"; return AVN_ERR_OOM; }
+            if (!l.assign(w.stage.p, w.stage.cap)) { error = "staging: the plan does not fit its arena"; return AVN_ERR_STATE; }
+            for (int i = 0; i < l.n; ++i)
+                if (l.item[i].dir == avn_stage::IN) HIPCHK(hipMemcpyAsync(*l.item[i].dev, l.item[i].host, l.item[i].bytes, hipMemcpyHostToDevice, w.stream));
+            return AVN_OK;
+        }
+        avn_status finish() {
+            for (int i = 0; i < l.n; ++i)
+                if (l.item[i].dir == avn_stage::OUT) HIPCHK(hipMemcpyAsync(l.item[i].host, *l.item[i].dev, l.item[i].bytes, hipMemcpyDeviceToHost, w.stream));
+            return AVN_OK;
+        }
+    };
+// declarations of a plan `plan` into the fields of a stage struct `s` (the element type is the field's)
+#define SIN(field, src, cnt) plan.in(src, cnt, &s.field)
+#define SOUT(field, dst, cnt) plan.out(dst, cnt, &s.field)
+#define COMMIT(plan) do { avn_status s_ = (plan).commit(); if (s_ != AVN_OK) return s_; } while (0)
+#define FINISH(plan) do { avn_status s_ = (plan).finish(); if (s_ != AVN_OK) return s_; } while (0)
     static size_t al(size_t b) { return (b + 63) & ~(size_t)63; }
 
     template <class U> avn_status grow(DevBuf& b, size_t count, U** field, bool& moved) {

@@ -61,22 +61,19 @@
             if (bad_c) { bp.n_colliders = 0; bp.n_intervals = 0; have_colliders = false; slot_entity.clear(); entity_slot.clear(); h_col_body.clear(); }
         }
         dw.n_bodies = n;
-        size_t total = 0;
-        total += al(sizeof(T) * 3 * n) * 7 + al(sizeof(T) * 4 * n) + al(sizeof(T) * 6 * n) + al(sizeof(T) * n) * 6 + al(n) * 4;
-        avn_status st = stage_reserve(total + 64 * 32);
-        if (st != AVN_OK) return st;
         BodyStage<T> s;
         std::memset(&s, 0, sizeof s);
-#define SIN(field, src, cnt, U) do { st = stage_in<U>(src, cnt, &s.field); if (st != AVN_OK) return st; } while (0)
-        SIN(position, b->position, 3 * (size_t)n, T); SIN(rotation, b->rotation, 4 * (size_t)n, T);
-        SIN(linear_velocity, b->linear_velocity, 3 * (size_t)n, T); SIN(angular_velocity, b->angular_velocity, 3 * (size_t)n, T);
-        SIN(inv_mass, b->inv_mass, n, T); SIN(inv_inertia_local, b->inv_inertia_local, 6 * (size_t)n, T);
-        SIN(center_of_mass, b->center_of_mass, 3 * (size_t)n, T); SIN(linear_damping, b->linear_damping, n, T);
-        SIN(angular_damping, b->angular_damping, n, T); SIN(gravity_scale, b->gravity_scale, n, T);
-        SIN(accel_linear, b->accel_linear, 3 * (size_t)n, T); SIN(accel_angular, b->accel_angular, 3 * (size_t)n, T);
-        SIN(max_linear_speed, b->max_linear_speed, n, T); SIN(max_angular_speed, b->max_angular_speed, n, T);
-        SIN(rb_type, b->rb_type, n, uint8_t); SIN(locked_axes, b->locked_axes, n, uint8_t); SIN(body_flags, b->body_flags, n, uint8_t);
-        SIN(dominance, b->dominance, n, int8_t);
+        StagePlan plan(*this);
+        SIN(position, b->position, 3 * (size_t)n); SIN(rotation, b->rotation, 4 * (size_t)n);
+        SIN(linear_velocity, b->linear_velocity, 3 * (size_t)n); SIN(angular_velocity, b->angular_velocity, 3 * (size_t)n);
+        SIN(inv_mass, b->inv_mass, n); SIN(inv_inertia_local, b->inv_inertia_local, 6 * (size_t)n);
+        SIN(center_of_mass, b->center_of_mass, 3 * (size_t)n); SIN(linear_damping, b->linear_damping, n);
+        SIN(angular_damping, b->angular_damping, n); SIN(gravity_scale, b->gravity_scale, n);
+        SIN(accel_linear, b->accel_linear, 3 * (size_t)n); SIN(accel_angular, b->accel_angular, 3 * (size_t)n);
+        SIN(max_linear_speed, b->max_linear_speed, n); SIN(max_angular_speed, b->max_angular_speed, n);
+        SIN(rb_type, b->rb_type, n); SIN(locked_axes, b->locked_axes, n); SIN(body_flags, b->body_flags, n);
+        SIN(dominance, b->dominance, n);
+        COMMIT(plan);
         launch_pack_bodies<T>(dw, s, stream);
         HIPCHK(hipGetLastError());
         // host copy of "has SolverBody" for the joint schedules
@@ -97,10 +94,11 @@
             std::vector<uint32_t> awake_list;
             for (uint32_t i = 0; i < n; ++i) if (!(h_body_flags[i] & AVN_BODY_SLEEPING) && b->body_flags && (b->body_flags[i] & AVN_BODY_SLEEPING)) awake_list.push_back(i);
             HIPCHK(hipStreamSynchronize(stream));
-            avn_status s2 = stage_reserve((asleep.size() + awake_list.size()) * 4 + 1024);
-            if (s2 != AVN_OK) return s2;
             const uint32_t *d1 = nullptr, *d2 = nullptr;
-            if ((s2 = stage_in<uint32_t>(asleep.data(), asleep.size(), &d1)) != AVN_OK || (s2 = stage_in<uint32_t>(awake_list.data(), awake_list.size(), &d2)) != AVN_OK) return s2;
+            StagePlan plan2(*this);
+            plan2.in(asleep.data(), asleep.size(), &d1); plan2.in(awake_list.data(), awake_list.size(), &d2);
+            COMMIT(plan2);
+            avn_status s2;
             launch_bodies_set_sleeping<T>(dw, d1, (uint32_t)asleep.size(), 1u, nullptr, stream);
             launch_bodies_set_sleeping<T>(dw, d2, (uint32_t)awake_list.size(), 0u, nullptr, stream);
             if ((s2 = slp_grow_bodies(n)) != AVN_OK) return s2;   // spawned bodies: SleepTimer 0, the world's thresholds
@@ -127,10 +125,10 @@
         Vec4<T>*dl = nullptr, *da = nullptr;
         HIPCHK(hipStreamSynchronize(stream));
         GROW(b_lacc_l, (size_t)cap_bodies, dl); GROW(b_lacc_a, (size_t)cap_bodies, da);
-        avn_status st = stage_reserve(al(sizeof(T) * 3 * (size_t)count) * 2 + 1024);
-        if (st != AVN_OK) return st;
         const T *sl = nullptr, *sa = nullptr;
-        if ((st = stage_in<T>(linear, 3 * (size_t)count, &sl)) != AVN_OK || (st = stage_in<T>(angular, 3 * (size_t)count, &sa)) != AVN_OK) return st;
+        StagePlan plan(*this);
+        plan.in(linear, 3 * (size_t)count, &sl); plan.in(angular, 3 * (size_t)count, &sa);
+        COMMIT(plan);
         launch_pack_local_accelerations<T>(dl, da, sl, sa, count, stream);
         HIPCHK(hipGetLastError());
         if (dw.lacc_l != dl || dw.lacc_a != da) { dw.lacc_l = dl; dw.lacc_a = da; graph_valid = false; }
@@ -140,48 +138,32 @@
     avn_status bodies_download(const avn_bodies_out* o) override {
         if (!o) return AVN_ERR_BAD_ARG;
         size_t n = dw.n_bodies;
-        avn_status st = stage_reserve(al(sizeof(T) * 3 * n) * 3 + al(sizeof(T) * 4 * n) + 1024);
-        if (st != AVN_OK) return st;
-        T* p = o->position ? stage_alloc<T>(3 * n) : nullptr;
-        T* r = o->rotation ? stage_alloc<T>(4 * n) : nullptr;
-        T* l = o->linear_velocity ? stage_alloc<T>(3 * n) : nullptr;
-        T* a = o->angular_velocity ? stage_alloc<T>(3 * n) : nullptr;
+        T *p, *r, *l, *a;
+        StagePlan plan(*this);
+        plan.out(o->position, 3 * n, &p); plan.out(o->rotation, 4 * n, &r);
+        plan.out(o->linear_velocity, 3 * n, &l); plan.out(o->angular_velocity, 3 * n, &a);
+        COMMIT(plan);
         launch_unpack_bodies<T>(dw, p, r, l, a, stream);
         HIPCHK(hipGetLastError());
-        if ((st = stage_out<T>(o->position, p, 3 * n)) != AVN_OK) return st;
-        if ((st = stage_out<T>(o->rotation, r, 4 * n)) != AVN_OK) return st;
-        if ((st = stage_out<T>(o->linear_velocity, l, 3 * n)) != AVN_OK) return st;
-        if ((st = stage_out<T>(o->angular_velocity, a, 3 * n)) != AVN_OK) return st;
+        FINISH(plan);
         HIPCHK(hipStreamSynchronize(stream));
         return AVN_OK;
     }
     avn_status solver_bodies_download(const avn_solver_bodies_out* o) override {
         if (!o) return AVN_ERR_BAD_ARG;
         size_t n = dw.n_bodies;
-        avn_status st = stage_reserve(al(sizeof(T) * 3 * n) * 5 + al(sizeof(T) * 4 * n) + al(sizeof(T) * 6 * n) + al(sizeof(T) * n) * 3 + al(4 * n) + al(2 * n) + 4096);
-        if (st != AVN_OK) return st;
         SolverBodiesStage<T> s;
-        s.linear_velocity = o->linear_velocity ? stage_alloc<T>(3 * n) : nullptr;
-        s.angular_velocity = o->angular_velocity ? stage_alloc<T>(3 * n) : nullptr;
-        s.delta_position = o->delta_position ? stage_alloc<T>(3 * n) : nullptr;
-        s.delta_rotation = o->delta_rotation ? stage_alloc<T>(4 * n) : nullptr;
-        s.flags = o->flags ? stage_alloc<uint32_t>(n) : nullptr;
-        s.inv_mass = o->inv_mass ? stage_alloc<T>(n) : nullptr;
-        s.inv_inertia_world = o->inv_inertia_world ? stage_alloc<T>(6 * n) : nullptr;
-        s.dominance = o->dominance ? stage_alloc<int16_t>(n) : nullptr;
-        s.linear_increment = o->linear_increment ? stage_alloc<T>(3 * n) : nullptr;
-        s.angular_increment = o->angular_increment ? stage_alloc<T>(3 * n) : nullptr;
-        s.linear_damping_rhs = o->linear_damping_rhs ? stage_alloc<T>(n) : nullptr;
-        s.angular_damping_rhs = o->angular_damping_rhs ? stage_alloc<T>(n) : nullptr;
+        StagePlan plan(*this);
+        SOUT(linear_velocity, o->linear_velocity, 3 * n); SOUT(angular_velocity, o->angular_velocity, 3 * n);
+        SOUT(delta_position, o->delta_position, 3 * n); SOUT(delta_rotation, o->delta_rotation, 4 * n);
+        SOUT(flags, o->flags, n); SOUT(inv_mass, o->inv_mass, n); SOUT(inv_inertia_world, o->inv_inertia_world, 6 * n);
+        SOUT(dominance, o->dominance, n); SOUT(linear_increment, o->linear_increment, 3 * n);
+        SOUT(angular_increment, o->angular_increment, 3 * n); SOUT(linear_damping_rhs, o->linear_damping_rhs, n);
+        SOUT(angular_damping_rhs, o->angular_damping_rhs, n);
+        COMMIT(plan);
         launch_unpack_solver_bodies<T>(dw, s, stream);
         HIPCHK(hipGetLastError());
-#define SOUT(dst, src, cnt, U) do { if ((st = stage_out<U>(dst, src, cnt)) != AVN_OK) return st; } while (0)
-        SOUT(o->linear_velocity, s.linear_velocity, 3 * n, T); SOUT(o->angular_velocity, s.angular_velocity, 3 * n, T);
-        SOUT(o->delta_position, s.delta_position, 3 * n, T); SOUT(o->delta_rotation, s.delta_rotation, 4 * n, T);
-        SOUT(o->flags, s.flags, n, uint32_t); SOUT(o->inv_mass, s.inv_mass, n, T); SOUT(o->inv_inertia_world, s.inv_inertia_world, 6 * n, T);
-        SOUT(o->dominance, s.dominance, n, int16_t); SOUT(o->linear_increment, s.linear_increment, 3 * n, T);
-        SOUT(o->angular_increment, s.angular_increment, 3 * n, T); SOUT(o->linear_damping_rhs, s.linear_damping_rhs, n, T);
-        SOUT(o->angular_damping_rhs, s.angular_damping_rhs, n, T);
+        FINISH(plan);
         HIPCHK(hipStreamSynchronize(stream));
         return AVN_OK;
     }

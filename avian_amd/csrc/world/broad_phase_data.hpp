@@ -11,11 +11,11 @@
         if (err != hipSuccess) { error = "hipMalloc failed"; return AVN_ERR_OOM; }
         tab = buf.as<uint64_t>();
         cap = need;
-        avn_status st = stage_reserve((size_t)n * 8 + 1024);
-        if (st != AVN_OK) return st;
-        HIPCHK(hipMemsetAsync(tab, 0xFF, (size_t)cap * 8, stream));
         const uint64_t* d;
-        if ((st = stage_in<uint64_t>(host_keys, n, &d)) != AVN_OK) return st;
+        StagePlan plan(*this);
+        plan.in(host_keys, n, &d);
+        COMMIT(plan);
+        HIPCHK(hipMemsetAsync(tab, 0xFF, (size_t)cap * 8, stream));
         launch_hs_insert(tab, cap, d, n, stream);
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(stream));
@@ -89,10 +89,10 @@
                     identity = identity && remap[s] == (uint32_t)s;
                 }
                 if (!identity) {
-                    avn_status sr = stage_reserve(al(remap.size() * 4) + 1024);
-                    if (sr != AVN_OK) return sr;
                     const uint32_t* d_map;
-                    if ((sr = stage_in<uint32_t>(remap.data(), remap.size(), &d_map)) != AVN_OK) return sr;
+                    StagePlan plan(*this);
+                    plan.in(remap.data(), remap.size(), &d_map);
+                    COMMIT(plan);
                     uint32_t* d_orphans = b_misc.as<uint32_t>() + 41;
                     HIPCHK(hipMemsetAsync(d_orphans, 0, 4, stream));
                     launch_remap_row_slots<T>(ct, d_map, (uint32_t)remap.size(), 0u, d_orphans, stream);
@@ -170,13 +170,13 @@
                 HIPCHK(hipMemcpy(bp.aabb_max, keep_max.data(), (size_t)C * sizeof(V), hipMemcpyHostToDevice));
             }
         }
-        avn_status st = stage_reserve(al(4 * (size_t)C) * 4 + al(C) * 2 + al(sizeof(T) * 3 * C) + al(sizeof(T) * C) * 2 + 4096);
-        if (st != AVN_OK) return st;
         ColliderStage<T> s;
         std::memset(&s, 0, sizeof s);
-        SIN(entity, c->entity_index, C, uint32_t); SIN(body, c->body, C, int32_t); SIN(shape, c->shape, C, uint8_t);
-        SIN(half_extents, c->half_extents, 3 * (size_t)C, T); SIN(memberships, c->memberships, C, uint32_t); SIN(filters, c->filters, C, uint32_t);
-        SIN(cflags, c->collider_flags, C, uint8_t); SIN(collision_margin, c->collision_margin, C, T); SIN(speculative_margin, c->speculative_margin, C, T);
+        StagePlan plan(*this);
+        SIN(entity, c->entity_index, C); SIN(body, c->body, C); SIN(shape, c->shape, C);
+        SIN(half_extents, c->half_extents, 3 * (size_t)C); SIN(memberships, c->memberships, C); SIN(filters, c->filters, C);
+        SIN(cflags, c->collider_flags, C); SIN(collision_margin, c->collision_margin, C); SIN(speculative_margin, c->speculative_margin, C);
+        COMMIT(plan);
         launch_pack_colliders<T>(bp, s, stream);
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(stream));

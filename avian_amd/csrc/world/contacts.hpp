@@ -77,12 +77,11 @@
             h_live_keys.insert(x < y ? ((uint64_t)x << 32) | y : ((uint64_t)y << 32) | x);
         }
         contact_keys_live = true;
-        if ((st = stage_reserve(al(4 * (size_t)n) * 4 + 1024)) != AVN_OK) return st;
         const uint32_t *d_id, *d_s1, *d_s2, *d_pf;
-        if ((st = stage_in<uint32_t>(p->contact_id, n, &d_id)) != AVN_OK) return st;
-        if ((st = stage_in<uint32_t>(s1.data(), n, &d_s1)) != AVN_OK) return st;
-        if ((st = stage_in<uint32_t>(s2.data(), n, &d_s2)) != AVN_OK) return st;
-        if ((st = stage_in<uint32_t>(p->pair_flags, n, &d_pf)) != AVN_OK) return st;
+        StagePlan plan(*this);
+        plan.in(p->contact_id, n, &d_id); plan.in(s1.data(), n, &d_s1); plan.in(s2.data(), n, &d_s2);
+        plan.in(p->pair_flags, n, &d_pf);
+        COMMIT(plan);
         launch_init_contact_rows<T>(ct, d_id, d_s1, d_s2, d_pf, n, stream);
         HIPCHK(hipGetLastError());
         HIPCHK(hipStreamSynchronize(stream));
@@ -98,11 +97,10 @@
             keys[i] = x < y ? ((uint64_t)x << 32) | y : ((uint64_t)y << 32) | x;
         }
         for (size_t i = 0; i < n; ++i) { h_ct_used[ids[i]] = 0; h_live_keys.erase(keys[i]); }
-        avn_status st = stage_reserve(al(4 * n) + al(8 * n) + 1024);
-        if (st != AVN_OK) return st;
         const uint32_t* d_id; const uint64_t* d_keys;
-        if ((st = stage_in<uint32_t>(ids, n, &d_id)) != AVN_OK) return st;
-        if ((st = stage_in<uint64_t>(keys.data(), n, &d_keys)) != AVN_OK) return st;
+        StagePlan plan(*this);
+        plan.in(ids, n, &d_id); plan.in(keys.data(), n, &d_keys);
+        COMMIT(plan);
         launch_clear_contact_rows<T>(ct, d_id, (uint32_t)n, stream);
         launch_hs_remove(bp.pair_set, bp.pair_set_cap, d_keys, (uint32_t)n, stream);
         HIPCHK(hipGetLastError());
@@ -250,25 +248,19 @@
         if (!o || (n && !ids)) return AVN_ERR_BAD_ARG;
         for (size_t i = 0; i < n; ++i)
             if (ids[i] >= ct.cap || (!pipe_dev && !h_ct_used[ids[i]])) { error = "contacts_download: no such contact"; return AVN_ERR_STATE; }   // (device closed loop: liveness is a row flag)
-        avn_status st = stage_reserve(al(4 * n) * 4 + al(n) + al(sizeof(T) * 3 * n) + al(sizeof(T) * n) * 2 + al(sizeof(T) * 12 * n) * 2 + al(sizeof(T) * 4 * n) * 4 + al(sizeof(T) * 8 * n) + al(16 * n) * 2 + 4096);
-        if (st != AVN_OK) return st;
         const uint32_t* d_id;
-        if ((st = stage_in<uint32_t>(ids, n, &d_id)) != AVN_OK) return st;
         ContactsStage<T> s;
-        s.flags = o->flags ? stage_alloc<uint32_t>(n) : nullptr; s.point_count = o->point_count ? stage_alloc<uint8_t>(n) : nullptr;
-        s.normal = o->normal ? stage_alloc<T>(3 * n) : nullptr; s.friction = o->friction ? stage_alloc<T>(n) : nullptr; s.restitution = o->restitution ? stage_alloc<T>(n) : nullptr;
-        s.anchor1 = o->anchor1 ? stage_alloc<T>(12 * n) : nullptr; s.anchor2 = o->anchor2 ? stage_alloc<T>(12 * n) : nullptr;
-        s.penetration = o->penetration ? stage_alloc<T>(4 * n) : nullptr; s.normal_speed = o->normal_speed ? stage_alloc<T>(4 * n) : nullptr;
-        s.warm_n = o->warm_start_normal_impulse ? stage_alloc<T>(4 * n) : nullptr; s.warm_t = o->warm_start_tangent_impulse ? stage_alloc<T>(8 * n) : nullptr;
-        s.normal_impulse = o->normal_impulse ? stage_alloc<T>(4 * n) : nullptr;
-        s.feature_id1 = o->feature_id1 ? stage_alloc<uint32_t>(4 * n) : nullptr; s.feature_id2 = o->feature_id2 ? stage_alloc<uint32_t>(4 * n) : nullptr;
+        StagePlan plan(*this);
+        plan.in(ids, n, &d_id);
+        SOUT(flags, o->flags, n); SOUT(point_count, o->point_count, n); SOUT(normal, o->normal, 3 * n);
+        SOUT(friction, o->friction, n); SOUT(restitution, o->restitution, n); SOUT(anchor1, o->anchor1, 12 * n); SOUT(anchor2, o->anchor2, 12 * n);
+        SOUT(penetration, o->penetration, 4 * n); SOUT(normal_speed, o->normal_speed, 4 * n); SOUT(warm_n, o->warm_start_normal_impulse, 4 * n);
+        SOUT(warm_t, o->warm_start_tangent_impulse, 8 * n); SOUT(normal_impulse, o->normal_impulse, 4 * n);
+        SOUT(feature_id1, o->feature_id1, 4 * n); SOUT(feature_id2, o->feature_id2, 4 * n);
+        COMMIT(plan);
         launch_unpack_contacts<T>(ct, d_id, (uint32_t)n, s, stream);
         HIPCHK(hipGetLastError());
-        SOUT(o->flags, s.flags, n, uint32_t); SOUT(o->point_count, s.point_count, n, uint8_t); SOUT(o->normal, s.normal, 3 * n, T);
-        SOUT(o->friction, s.friction, n, T); SOUT(o->restitution, s.restitution, n, T); SOUT(o->anchor1, s.anchor1, 12 * n, T); SOUT(o->anchor2, s.anchor2, 12 * n, T);
-        SOUT(o->penetration, s.penetration, 4 * n, T); SOUT(o->normal_speed, s.normal_speed, 4 * n, T); SOUT(o->warm_start_normal_impulse, s.warm_n, 4 * n, T);
-        SOUT(o->warm_start_tangent_impulse, s.warm_t, 8 * n, T); SOUT(o->normal_impulse, s.normal_impulse, 4 * n, T);
-        SOUT(o->feature_id1, s.feature_id1, 4 * n, uint32_t); SOUT(o->feature_id2, s.feature_id2, 4 * n, uint32_t);
+        FINISH(plan);
         HIPCHK(hipStreamSynchronize(stream));
         return AVN_OK;
     }
@@ -283,23 +275,16 @@
             if (in->point_count[i] > AVN_MAX_MANIFOLD_POINTS) { error = "contacts_upload: point_count > 4"; return AVN_ERR_BAD_ARG; }
         }
         if (!n) return AVN_OK;
-        avn_status st = stage_reserve(al(4 * n) * 2 + al(n) + al(sizeof(T) * 3 * n) + al(sizeof(T) * n) * 2 + al(sizeof(T) * 12 * n) * 2 + al(sizeof(T) * 4 * n) * 4 + al(sizeof(T) * 8 * n) + al(16 * n) * 2 + 4096);
-        if (st != AVN_OK) return st;
-        const uint32_t *d_id, *d_flags, *d_f1, *d_f2; const uint8_t* d_pc;
-        const T *d_n, *d_fr, *d_re, *d_a1, *d_a2, *d_pen, *d_ns, *d_wn, *d_wt, *d_ni;
-        if ((st = stage_in<uint32_t>(ids, n, &d_id)) != AVN_OK || (st = stage_in<uint32_t>(in->flags, n, &d_flags)) != AVN_OK || (st = stage_in<uint8_t>(in->point_count, n, &d_pc)) != AVN_OK ||
-            (st = stage_in<T>((const T*)in->normal, 3 * n, &d_n)) != AVN_OK || (st = stage_in<T>((const T*)in->friction, n, &d_fr)) != AVN_OK ||
-            (st = stage_in<T>((const T*)in->restitution, n, &d_re)) != AVN_OK || (st = stage_in<T>((const T*)in->anchor1, 12 * n, &d_a1)) != AVN_OK ||
-            (st = stage_in<T>((const T*)in->anchor2, 12 * n, &d_a2)) != AVN_OK || (st = stage_in<T>((const T*)in->penetration, 4 * n, &d_pen)) != AVN_OK ||
-            (st = stage_in<T>((const T*)in->normal_speed, 4 * n, &d_ns)) != AVN_OK || (st = stage_in<T>((const T*)in->warm_start_normal_impulse, 4 * n, &d_wn)) != AVN_OK ||
-            (st = stage_in<T>((const T*)in->warm_start_tangent_impulse, 8 * n, &d_wt)) != AVN_OK || (st = stage_in<T>((const T*)in->normal_impulse, 4 * n, &d_ni)) != AVN_OK ||
-            (st = stage_in<uint32_t>(in->feature_id1, 4 * n, &d_f1)) != AVN_OK || (st = stage_in<uint32_t>(in->feature_id2, 4 * n, &d_f2)) != AVN_OK)
-            return st;
+        const uint32_t* d_id;
         ContactsStage<T> s;   // read-only here; the struct is shared with the download direction
-        s.flags = const_cast<uint32_t*>(d_flags); s.point_count = const_cast<uint8_t*>(d_pc); s.normal = const_cast<T*>(d_n); s.friction = const_cast<T*>(d_fr);
-        s.restitution = const_cast<T*>(d_re); s.anchor1 = const_cast<T*>(d_a1); s.anchor2 = const_cast<T*>(d_a2); s.penetration = const_cast<T*>(d_pen);
-        s.normal_speed = const_cast<T*>(d_ns); s.warm_n = const_cast<T*>(d_wn); s.warm_t = const_cast<T*>(d_wt); s.normal_impulse = const_cast<T*>(d_ni);
-        s.feature_id1 = const_cast<uint32_t*>(d_f1); s.feature_id2 = const_cast<uint32_t*>(d_f2);
+        StagePlan plan(*this);
+        plan.in(ids, n, &d_id);
+        SIN(flags, in->flags, n); SIN(point_count, in->point_count, n); SIN(normal, in->normal, 3 * n);
+        SIN(friction, in->friction, n); SIN(restitution, in->restitution, n); SIN(anchor1, in->anchor1, 12 * n); SIN(anchor2, in->anchor2, 12 * n);
+        SIN(penetration, in->penetration, 4 * n); SIN(normal_speed, in->normal_speed, 4 * n); SIN(warm_n, in->warm_start_normal_impulse, 4 * n);
+        SIN(warm_t, in->warm_start_tangent_impulse, 8 * n); SIN(normal_impulse, in->normal_impulse, 4 * n);
+        SIN(feature_id1, in->feature_id1, 4 * n); SIN(feature_id2, in->feature_id2, 4 * n);
+        COMMIT(plan);
         // device closed loop: liveness is a row flag only the device knows -- the kernel skips ids without a live row and raises bit 2 of
         // the error word, read back here (the call synchronises anyway)
         uint32_t* d_err = pipe_dev ? pg.ctr + PGC_ERROR : nullptr;
@@ -323,14 +308,13 @@
     }
     avn_status aabbs_download(void* mn, void* mx, uint32_t* ents, size_t* n_iv) override {
         size_t C = bp.n_colliders, I = bp.n_intervals;
-        avn_status st = stage_reserve(al(sizeof(T) * 3 * C) * 2 + al(4 * I) + 1024);
-        if (st != AVN_OK) return st;
-        T* a = mn ? stage_alloc<T>(3 * C) : nullptr;
-        T* b = mx ? stage_alloc<T>(3 * C) : nullptr;
-        uint32_t* e = ents ? stage_alloc<uint32_t>(I) : nullptr;
+        T *a, *b; uint32_t* e;
+        StagePlan plan(*this);
+        plan.out(mn, 3 * C, &a); plan.out(mx, 3 * C, &b); plan.out(ents, I, &e);
+        COMMIT(plan);
         launch_unpack_aabbs<T>(bp, a, b, e, stream);
         HIPCHK(hipGetLastError());
-        SOUT(mn, a, 3 * C, T); SOUT(mx, b, 3 * C, T); SOUT(ents, e, I, uint32_t);
+        FINISH(plan);
         HIPCHK(hipStreamSynchronize(stream));
         if (n_iv) *n_iv = I;
         return AVN_OK;
@@ -341,13 +325,14 @@
         for (int k = 0; k < 3; ++k) { mn[k] = inf; mx[k] = -inf; }
         uint32_t nb = (bp.n_colliders + 255) / 256;
         if (!nb) return AVN_OK;
-        avn_status st = stage_reserve((size_t)nb * 6 * sizeof(T) + 1024);
-        if (st != AVN_OK) return st;
-        T* part = stage_alloc<T>((size_t)nb * 6);
+        std::vector<T> h((size_t)nb * 6);
+        T* part;
+        StagePlan plan(*this);
+        plan.out(h.data(), h.size(), &part);
+        COMMIT(plan);
         launch_dynamic_bounds<T>(dw, bp, part, stream);
         HIPCHK(hipGetLastError());
-        std::vector<T> h((size_t)nb * 6);
-        HIPCHK(hipMemcpyAsync(h.data(), part, h.size() * sizeof(T), hipMemcpyDeviceToHost, stream));
+        FINISH(plan);
         HIPCHK(hipStreamSynchronize(stream));
         for (uint32_t b = 0; b < nb; ++b)
             for (int k = 0; k < 3; ++k) { mn[k] = std::min(mn[k], (double)h[b * 6 + k]); mx[k] = std::max(mx[k], (double)h[b * 6 + 3 + k]); }
@@ -365,28 +350,20 @@
             capsules = capsules || k1 == AVN_SHAPE_CAPSULE || k2 == AVN_SHAPE_CAPSULE;
         }
         const size_t Q = AVN_MAX_QUERY_POINTS;
-        avn_status st = stage_reserve(al(n) * 3 + al(sizeof(T) * 3 * n) * 5 + al(sizeof(T) * 4 * n) * 2 + al(sizeof(T) * n) + al(sizeof(T) * 3 * Q * n) * 3 +
-                                      al(sizeof(T) * Q * n) + al(4 * Q * n) * 2 + 64 * 32);
-        if (st != AVN_OK) return st;
         QueryStage<T> s;
         std::memset(&s, 0, sizeof s);
-        SIN(shape1, p->shape1, n, uint8_t); SIN(shape2, p->shape2, n, uint8_t);
-        SIN(half_extents1, p->half_extents1, 3 * n, T); SIN(position1, p->position1, 3 * n, T); SIN(rotation1, p->rotation1, 4 * n, T);
-        SIN(half_extents2, p->half_extents2, 3 * n, T); SIN(position2, p->position2, 3 * n, T); SIN(rotation2, p->rotation2, 4 * n, T);
-        SIN(prediction, p->prediction_distance, n, T);
-        s.point_count = o->point_count ? stage_alloc<uint8_t>(n) : nullptr;
-        s.normal = o->normal ? stage_alloc<T>(3 * n) : nullptr;
-        s.anchor1 = o->anchor1 ? stage_alloc<T>(3 * Q * n) : nullptr;
-        s.anchor2 = o->anchor2 ? stage_alloc<T>(3 * Q * n) : nullptr;
-        s.point = o->point ? stage_alloc<T>(3 * Q * n) : nullptr;
-        s.penetration = o->penetration ? stage_alloc<T>(Q * n) : nullptr;
-        s.feature_id1 = o->feature_id1 ? stage_alloc<uint32_t>(Q * n) : nullptr;
-        s.feature_id2 = o->feature_id2 ? stage_alloc<uint32_t>(Q * n) : nullptr;
+        StagePlan plan(*this);
+        SIN(shape1, p->shape1, n); SIN(shape2, p->shape2, n);
+        SIN(half_extents1, p->half_extents1, 3 * n); SIN(position1, p->position1, 3 * n); SIN(rotation1, p->rotation1, 4 * n);
+        SIN(half_extents2, p->half_extents2, 3 * n); SIN(position2, p->position2, 3 * n); SIN(rotation2, p->rotation2, 4 * n);
+        SIN(prediction, p->prediction_distance, n);
+        SOUT(point_count, o->point_count, n); SOUT(normal, o->normal, 3 * n);
+        SOUT(anchor1, o->anchor1, 3 * Q * n); SOUT(anchor2, o->anchor2, 3 * Q * n); SOUT(point, o->point, 3 * Q * n);
+        SOUT(penetration, o->penetration, Q * n); SOUT(feature_id1, o->feature_id1, Q * n); SOUT(feature_id2, o->feature_id2, Q * n);
+        COMMIT(plan);
         launch_contact_manifolds_query<T>(s, (uint32_t)n, stream, capsules);
         HIPCHK(hipGetLastError());
-        SOUT(o->point_count, s.point_count, n, uint8_t); SOUT(o->normal, s.normal, 3 * n, T);
-        SOUT(o->anchor1, s.anchor1, 3 * Q * n, T); SOUT(o->anchor2, s.anchor2, 3 * Q * n, T); SOUT(o->point, s.point, 3 * Q * n, T);
-        SOUT(o->penetration, s.penetration, Q * n, T); SOUT(o->feature_id1, s.feature_id1, Q * n, uint32_t); SOUT(o->feature_id2, s.feature_id2, Q * n, uint32_t);
+        FINISH(plan);
         HIPCHK(hipStreamSynchronize(stream));
         return AVN_OK;
     }

@@ -119,12 +119,12 @@
         double host_ms = 0;
         auto flush_pops = [&]() -> avn_status {
             if (pops.empty()) return AVN_OK;
-            avn_status s2 = stage_reserve(pops.size() * 8 + 1024);
-            if (s2 != AVN_OK) return s2;
             std::vector<uint32_t> kinds(pops.size(), 2u /* PG_KIND_POP */);
             const uint32_t *d_c, *d_k;
-            if ((s2 = stage_in<uint32_t>(pops.data(), pops.size(), &d_c)) != AVN_OK || (s2 = stage_in<uint32_t>(kinds.data(), kinds.size(), &d_k)) != AVN_OK) return s2;
-            s2 = pg_apply_ops((uint32_t)pops.size(), 0u, 0u, d_c, d_k, host_ms);
+            StagePlan plan(*this);
+            plan.in(pops.data(), pops.size(), &d_c); plan.in(kinds.data(), kinds.size(), &d_k);
+            COMMIT(plan);
+            const avn_status s2 = pg_apply_ops((uint32_t)pops.size(), 0u, 0u, d_c, d_k, host_ms);
             pops.clear();
             return s2;
         };
@@ -185,9 +185,10 @@
             std::sort(ids.begin(), ids.end());
             const uint32_t n_rem = (uint32_t)ids.size();
             HIPCHK(hipStreamSynchronize(stream));
-            if ((st = stage_reserve((size_t)n_rem * 4 + 1024)) != AVN_OK) return st;
             const uint32_t* d_ids;
-            if ((st = stage_in<uint32_t>(ids.data(), n_rem, &d_ids)) != AVN_OK) return st;
+            StagePlan plan(*this);
+            plan.in(ids.data(), n_rem, &d_ids);
+            COMMIT(plan);
             launch_pg_remove_list<T>(pg, ct, bp, d_ids, n_rem, stream);
             launch_pg_merge_free(pg, pgm_head, pgm_n_free, n_rem, stream);
             std::swap(b_pg_free_a.p, b_pg_free_b.p); std::swap(b_pg_free_a.cap, b_pg_free_b.cap);

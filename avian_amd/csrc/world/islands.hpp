@@ -49,10 +49,10 @@
         k.body_lin = nullptr; k.body_ang = nullptr; k.body_disabled = nullptr;
         if (sp->body_linear_threshold || sp->body_angular_threshold || sp->body_sleeping_disabled) {
             const size_t n = dw.n_bodies;
-            if ((st = stage_reserve(al(4 * n) * 2 + al(n) + 1024)) != AVN_OK) return st;
-            if ((st = stage_in<float>(sp->body_linear_threshold, n, &k.body_lin)) != AVN_OK) return st;
-            if ((st = stage_in<float>(sp->body_angular_threshold, n, &k.body_ang)) != AVN_OK) return st;
-            if ((st = stage_in<uint8_t>(sp->body_sleeping_disabled, n, &k.body_disabled)) != AVN_OK) return st;
+            StagePlan plan(*this);
+            plan.in(sp->body_linear_threshold, n, &k.body_lin); plan.in(sp->body_angular_threshold, n, &k.body_ang);
+            plan.in(sp->body_sleeping_disabled, n, &k.body_disabled);
+            COMMIT(plan);
         }
         HIPCHK(hipMemsetAsync(b_isl_awake.p, 0, (size_t)std::max<uint32_t>(dw.n_bodies, 1) * 4, stream));
         launch_sleep_update<T>(dw, k, b_isl_label.as<uint32_t>(), b_sleep_timer.as<float>(), b_isl_awake.as<uint32_t>(), b_isl_rests.as<uint8_t>(), b_isl_wakes.as<uint8_t>(), b_isl_ctr.as<uint32_t>(), stream);
@@ -85,9 +85,10 @@
         if (st != AVN_OK) return st;
         if ((st = island_buffers()) != AVN_OK) return st;
         if (!bodies || n == 0) { launch_sleep_reset(b_sleep_timer.as<float>(), nullptr, dw.n_bodies, dw.n_bodies, stream); HIPCHK(hipStreamSynchronize(stream)); return AVN_OK; }
-        if ((st = stage_reserve(al(4 * n) + 1024)) != AVN_OK) return st;
         const uint32_t* d = nullptr;
-        if ((st = stage_in<uint32_t>(bodies, n, &d)) != AVN_OK) return st;
+        StagePlan plan(*this);
+        plan.in(bodies, n, &d);
+        COMMIT(plan);
         launch_sleep_reset(b_sleep_timer.as<float>(), d, (uint32_t)n, dw.n_bodies, stream);
         HIPCHK(hipStreamSynchronize(stream));
         return AVN_OK;

@@ -57,18 +57,18 @@
         }
         if (moved || dw.n_joints != J) graph_valid = false;
         dw.n_joints = J;
-        avn_status st = stage_reserve(al(4 * (size_t)J) * 2 + al(J) * 2 + al(sizeof(T) * 3 * J) * 4 + al(sizeof(T) * 4 * J) * 2 + al(sizeof(T) * J) * 6 + 8192);
-        if (st != AVN_OK) return st;
         JointStage<T> s;
         std::memset(&s, 0, sizeof s);
-        SIN(joint_type, j->joint_type, J, uint8_t); SIN(limit_flags, j->limit_flags, J, uint8_t);
-        SIN(body1, j->body1, J, int32_t); SIN(body2, j->body2, J, int32_t);
-        SIN(local_anchor1, j->local_anchor1, 3 * (size_t)J, T); SIN(local_anchor2, j->local_anchor2, 3 * (size_t)J, T);
-        SIN(local_basis1, j->local_basis1, 4 * (size_t)J, T); SIN(local_basis2, j->local_basis2, 4 * (size_t)J, T);
-        SIN(axis, j->axis, 3 * (size_t)J, T);
-        SIN(limit_min, j->limit_min, J, T); SIN(limit_max, j->limit_max, J, T); SIN(limit2_min, j->limit2_min, J, T); SIN(limit2_max, j->limit2_max, J, T);
-        SIN(compliance, j->compliance, 3 * (size_t)J, T);
-        SIN(damping_linear, j->damping_linear, J, T); SIN(damping_angular, j->damping_angular, J, T);
+        StagePlan plan(*this);
+        SIN(joint_type, j->joint_type, J); SIN(limit_flags, j->limit_flags, J);
+        SIN(body1, j->body1, J); SIN(body2, j->body2, J);
+        SIN(local_anchor1, j->local_anchor1, 3 * (size_t)J); SIN(local_anchor2, j->local_anchor2, 3 * (size_t)J);
+        SIN(local_basis1, j->local_basis1, 4 * (size_t)J); SIN(local_basis2, j->local_basis2, 4 * (size_t)J);
+        SIN(axis, j->axis, 3 * (size_t)J);
+        SIN(limit_min, j->limit_min, J); SIN(limit_max, j->limit_max, J); SIN(limit2_min, j->limit2_min, J); SIN(limit2_max, j->limit2_max, J);
+        SIN(compliance, j->compliance, 3 * (size_t)J);
+        SIN(damping_linear, j->damping_linear, J); SIN(damping_angular, j->damping_angular, J);
+        COMMIT(plan);
         launch_pack_joints<T>(dw, s, stream);
         HIPCHK(hipGetLastError());
         h_j_body1.assign(j->body1, j->body1 + J);
@@ -86,7 +86,7 @@
                 uint32_t a = (uint32_t)j->body1[i], b = (uint32_t)j->body2[i];
                 disabled.push_back(a < b ? ((uint64_t)a << 32) | b : ((uint64_t)b << 32) | a);
             }
-        st = build_hash_set(b_disabled_set, bp.disabled_set, bp.disabled_cap, disabled.data(), (uint32_t)disabled.size());
+        avn_status st = build_hash_set(b_disabled_set, bp.disabled_set, bp.disabled_cap, disabled.data(), (uint32_t)disabled.size());
         if (st != AVN_OK) return st;
         joint_schedule_dirty = true;
         HIPCHK(hipStreamSynchronize(stream));
@@ -97,20 +97,15 @@
         if (!o) return AVN_ERR_BAD_ARG;
         if (despawn_needs_joints) { error = "joints_download: avn_despawn removed joints: upload the remaining joints (avn_joints_upload) first"; return AVN_ERR_STATE; }
         size_t J = dw.n_joints;
-        avn_status st = stage_reserve(al(sizeof(T) * 3 * J) * 7 + 1024);
-        if (st != AVN_OK) return st;
-        T* a = o->world_r1 ? stage_alloc<T>(3 * J) : nullptr;
-        T* b = o->world_r2 ? stage_alloc<T>(3 * J) : nullptr;
-        T* c = o->center_difference ? stage_alloc<T>(3 * J) : nullptr;
-        T* d = o->total_lagrange ? stage_alloc<T>(3 * J) : nullptr;
-        T* e = o->force ? stage_alloc<T>(3 * J) : nullptr;
-        T* f = o->total_rotation_lagrange ? stage_alloc<T>(3 * J) : nullptr;
-        T* g = o->torque ? stage_alloc<T>(3 * J) : nullptr;
+        T *a, *b, *c, *d, *e, *f, *g;
+        StagePlan plan(*this);
+        plan.out(o->world_r1, 3 * J, &a); plan.out(o->world_r2, 3 * J, &b); plan.out(o->center_difference, 3 * J, &c);
+        plan.out(o->total_lagrange, 3 * J, &d); plan.out(o->force, 3 * J, &e);
+        plan.out(o->total_rotation_lagrange, 3 * J, &f); plan.out(o->torque, 3 * J, &g);
+        COMMIT(plan);
         launch_unpack_joints<T>(dw, a, b, c, d, e, f, g, stream);
         HIPCHK(hipGetLastError());
-        SOUT(o->world_r1, a, 3 * J, T); SOUT(o->world_r2, b, 3 * J, T); SOUT(o->center_difference, c, 3 * J, T);
-        SOUT(o->total_lagrange, d, 3 * J, T); SOUT(o->force, e, 3 * J, T);
-        SOUT(o->total_rotation_lagrange, f, 3 * J, T); SOUT(o->torque, g, 3 * J, T);
+        FINISH(plan);
         HIPCHK(hipStreamSynchronize(stream));
         return AVN_OK;
     }

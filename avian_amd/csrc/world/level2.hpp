@@ -214,8 +214,10 @@
         b_bounds_send.ensure(6 * sizeof(double), err); if (err != hipSuccess) { error = "hipMalloc failed"; return AVN_ERR_OOM; }
         b_bounds_recv.ensure((size_t)nr * 6 * sizeof(double), err); if (err != hipSuccess) { error = "hipMalloc failed"; return AVN_ERR_OOM; }
         const uint32_t nb = (bp.n_colliders + 255) / 256;
-        if ((st = stage_reserve((size_t)std::max(nb, 1u) * 6 * sizeof(T) + 1024)) != AVN_OK) return st;
-        T* part = stage_alloc<T>((size_t)std::max(nb, 1u) * 6);
+        T* part;
+        StagePlan plan(*this);
+        plan.scratch((size_t)std::max(nb, 1u) * 6, &part);
+        COMMIT(plan);
         launch_dynamic_bounds<T>(dw, bp, part, stream);
         launch_bounds_reduce<T>(part, nb, b_bounds_send.as<double>(), stream);
         launches += 2;

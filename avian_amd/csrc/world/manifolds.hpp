@@ -19,18 +19,17 @@
         if (dw.n_manifolds != M) graph_valid = false;
         dw.n_manifolds = M;
         set_color_offsets(m->color_offsets);
-        size_t total = al(4 * (size_t)M) * 2 + al(sizeof(T) * 3 * M) * 2 + al(sizeof(T) * M) * 2 + al(M) * 2 + al(sizeof(T) * 12 * M) * 2 + al(sizeof(T) * 4 * M) * 3 + al(sizeof(T) * 8 * M);
-        avn_status st = stage_reserve(total + 64 * 32);
-        if (st != AVN_OK) return st;
-        HIPCHK(hipMemcpyAsync(dw.color_offsets, color_offsets, sizeof color_offsets, hipMemcpyHostToDevice, stream));
         ManifoldStage<T> s;
         std::memset(&s, 0, sizeof s);
-        SIN(body1, m->body1, M, int32_t); SIN(body2, m->body2, M, int32_t); SIN(normal, m->normal, 3 * (size_t)M, T);
-        SIN(friction, m->friction, M, T); SIN(restitution, m->restitution, M, T); SIN(tangent_velocity, m->tangent_velocity, 3 * (size_t)M, T);
-        SIN(point_count, m->point_count, M, uint8_t); SIN(manifold_flags, m->manifold_flags, M, uint8_t);
-        SIN(anchor1, m->anchor1, 12 * (size_t)M, T); SIN(anchor2, m->anchor2, 12 * (size_t)M, T);
-        SIN(penetration, m->penetration, 4 * (size_t)M, T); SIN(normal_speed, m->normal_speed, 4 * (size_t)M, T);
-        SIN(warm_n, m->warm_start_normal_impulse, 4 * (size_t)M, T); SIN(warm_t, m->warm_start_tangent_impulse, 8 * (size_t)M, T);
+        StagePlan plan(*this);
+        SIN(body1, m->body1, M); SIN(body2, m->body2, M); SIN(normal, m->normal, 3 * (size_t)M);
+        SIN(friction, m->friction, M); SIN(restitution, m->restitution, M); SIN(tangent_velocity, m->tangent_velocity, 3 * (size_t)M);
+        SIN(point_count, m->point_count, M); SIN(manifold_flags, m->manifold_flags, M);
+        SIN(anchor1, m->anchor1, 12 * (size_t)M); SIN(anchor2, m->anchor2, 12 * (size_t)M);
+        SIN(penetration, m->penetration, 4 * (size_t)M); SIN(normal_speed, m->normal_speed, 4 * (size_t)M);
+        SIN(warm_n, m->warm_start_normal_impulse, 4 * (size_t)M); SIN(warm_t, m->warm_start_tangent_impulse, 8 * (size_t)M);
+        COMMIT(plan);
+        HIPCHK(hipMemcpyAsync(dw.color_offsets, color_offsets, sizeof color_offsets, hipMemcpyHostToDevice, stream));
         launch_pack_manifolds<T>(dw, s, stream);
         HIPCHK(hipGetLastError());
         // (while the copies run) one pass over the host arrays: range checks, "any restitution", and the host copy of the ContactPair bodies (incidence CSR source)
@@ -315,43 +314,33 @@
     avn_status impulses_download(const avn_impulses_out* o) override {
         if (!o) return AVN_ERR_BAD_ARG;
         size_t M = dw.n_manifolds;
-        avn_status st = stage_reserve(al(sizeof(T) * 4 * M) * 2 + al(sizeof(T) * 8 * M) + 1024);
-        if (st != AVN_OK) return st;
-        T* a = o->warm_start_normal_impulse ? stage_alloc<T>(4 * M) : nullptr;
-        T* b = o->warm_start_tangent_impulse ? stage_alloc<T>(8 * M) : nullptr;
-        T* c = o->normal_impulse ? stage_alloc<T>(4 * M) : nullptr;
+        T *a, *b, *c;
+        StagePlan plan(*this);
+        plan.out(o->warm_start_normal_impulse, 4 * M, &a); plan.out(o->warm_start_tangent_impulse, 8 * M, &b);
+        plan.out(o->normal_impulse, 4 * M, &c);
+        COMMIT(plan);
         launch_unpack_impulses<T>(dw, a, b, c, stream);
         HIPCHK(hipGetLastError());
-        SOUT(o->warm_start_normal_impulse, a, 4 * M, T); SOUT(o->warm_start_tangent_impulse, b, 8 * M, T); SOUT(o->normal_impulse, c, 4 * M, T);
+        FINISH(plan);
         HIPCHK(hipStreamSynchronize(stream));
         return AVN_OK;
     }
     avn_status constraints_download(const avn_constraints_out* o) override {
         if (!o) return AVN_ERR_BAD_ARG;
         size_t M = dw.n_manifolds;
-        avn_status st = stage_reserve(al(M) * 2 + al(2 * M) + al(sizeof(T) * 3 * M) + al(sizeof(T) * 12 * M) * 2 + al(sizeof(T) * 4 * M) * 4 + al(sizeof(T) * 8 * M) + 4096);
-        if (st != AVN_OK) return st;
         ConstraintsStage<T> s;
-        s.point_count = o->point_count ? stage_alloc<uint8_t>(M) : nullptr;
-        s.softness_non_dynamic = o->softness_non_dynamic ? stage_alloc<uint8_t>(M) : nullptr;
-        s.relative_dominance = o->relative_dominance ? stage_alloc<int16_t>(M) : nullptr;
-        s.tangent1 = o->tangent1 ? stage_alloc<T>(3 * M) : nullptr;
-        s.anchor1 = o->anchor1 ? stage_alloc<T>(12 * M) : nullptr;
-        s.initial_separation = o->initial_separation ? stage_alloc<T>(4 * M) : nullptr;
-        s.normal_impulse = o->normal_impulse ? stage_alloc<T>(4 * M) : nullptr;
-        s.total_impulse = o->total_impulse ? stage_alloc<T>(4 * M) : nullptr;
-        s.normal_effective_mass = o->normal_effective_mass ? stage_alloc<T>(4 * M) : nullptr;
-        s.tangent_impulse = o->tangent_impulse ? stage_alloc<T>(8 * M) : nullptr;
-        s.tangent_k = o->tangent_effective_inverse_mass ? stage_alloc<T>(12 * M) : nullptr;
-        if (stage_off) HIPCHK(hipMemsetAsync(stage.p, 0, stage_off, stream));  // absent constraints read back as zeros
+        StagePlan plan(*this);
+        SOUT(point_count, o->point_count, M); SOUT(softness_non_dynamic, o->softness_non_dynamic, M);
+        SOUT(relative_dominance, o->relative_dominance, M); SOUT(tangent1, o->tangent1, 3 * M);
+        SOUT(anchor1, o->anchor1, 12 * M); SOUT(initial_separation, o->initial_separation, 4 * M);
+        SOUT(normal_impulse, o->normal_impulse, 4 * M); SOUT(total_impulse, o->total_impulse, 4 * M);
+        SOUT(normal_effective_mass, o->normal_effective_mass, 4 * M); SOUT(tangent_impulse, o->tangent_impulse, 8 * M);
+        SOUT(tangent_k, o->tangent_effective_inverse_mass, 12 * M);
+        COMMIT(plan);
+        if (plan.bytes()) HIPCHK(hipMemsetAsync(stage.p, 0, plan.bytes(), stream));  // absent constraints read back as zeros
         launch_unpack_constraints<T>(dw, s, stream);
         HIPCHK(hipGetLastError());
-        SOUT(o->point_count, s.point_count, M, uint8_t); SOUT(o->softness_non_dynamic, s.softness_non_dynamic, M, uint8_t);
-        SOUT(o->relative_dominance, s.relative_dominance, M, int16_t); SOUT(o->tangent1, s.tangent1, 3 * M, T);
-        SOUT(o->anchor1, s.anchor1, 12 * M, T); SOUT(o->initial_separation, s.initial_separation, 4 * M, T);
-        SOUT(o->normal_impulse, s.normal_impulse, 4 * M, T); SOUT(o->total_impulse, s.total_impulse, 4 * M, T);
-        SOUT(o->normal_effective_mass, s.normal_effective_mass, 4 * M, T); SOUT(o->tangent_impulse, s.tangent_impulse, 8 * M, T);
-        SOUT(o->tangent_effective_inverse_mass, s.tangent_k, 12 * M, T);
+        FINISH(plan);
         HIPCHK(hipStreamSynchronize(stream));
         return AVN_OK;
     }

@@ -238,10 +238,11 @@
         const size_t o_pw = slp_list.size(); slp_list.insert(slp_list.end(), pw.begin(), pw.end());
         const size_t o_bs = slp_list.size(); slp_list.insert(slp_list.end(), bsl.begin(), bsl.end());
         const size_t o_bw = slp_list.size(); slp_list.insert(slp_list.end(), bw.begin(), bw.end());
-        avn_status st = stage_reserve(slp_list.size() * 4 + 1024);
-        if (st != AVN_OK) return st;
         const uint32_t* d;
-        if ((st = stage_in<uint32_t>(slp_list.data(), slp_list.size(), &d)) != AVN_OK) return st;
+        StagePlan plan(*this);
+        plan.in(slp_list.data(), slp_list.size(), &d);
+        COMMIT(plan);
+        avn_status st;
         launch_rows_set_sleeping<T>(ct, d + o_ps, (uint32_t)ps.size(), 1u, stream);
         launch_rows_set_sleeping<T>(ct, d + o_pw, (uint32_t)pw.size(), 0u, stream);
         launch_bodies_set_sleeping<T>(dw, d + o_bs, (uint32_t)bsl.size(), 1u, nullptr, stream);

@@ -77,15 +77,11 @@
         }
         return AVN_OK;
     }
-    template <class U> avn_status sp_in(const void* p, size_t count, bool dev, const U** out) {
-        if (!p || count == 0) { *out = nullptr; return AVN_OK; }
-        if (dev) { *out = (const U*)p; return AVN_OK; }
-        return stage_in<U>(p, count, out);
-    }
-    template <class U> U* sp_out(void* p, size_t count, bool dev) { return dev ? (U*)p : stage_alloc<U>(count); }
-    // bytes the staging arena needs for a call (host pointers: inputs and outputs; always: the excluded list)
-    static size_t sp_stage_bytes(bool dev, size_t n, size_t in_bytes, size_t out_bytes, size_t n_excluded) {
-        return al(n_excluded * 4) + (dev ? 0 : in_bytes + out_bytes + al(n * 4) * 2) + 4096;
+    // the filter of a call: the per-query masks are the caller's (host or device), the sorted excluded list is always staged
+    void sp_filter_in(StagePlan& plan, SQ<T>& q, const avn_spatial_filter& f, uint32_t n, const std::vector<uint32_t>& ex) {
+        plan.in(f.mask, n, &q.mask);
+        plan.staged(ex.data(), ex.size(), &q.excluded);
+        q.n_excluded = (uint32_t)ex.size();
     }
     // Whether a call may hold AVN_SHAPE_CAPSULE query shapes, which the kernels' second (CAPSULE) instantiations answer: the host's kinds are
     // scanned, a device array is not read back (the second launch always goes; its lanes leave at once unless their query is a capsule).
@@ -120,23 +116,17 @@
         std::vector<uint32_t> ex;
         if ((st = sp_excluded(r->filter, dev, ex)) != AVN_OK) return st;
         const size_t n_rec = (size_t)n * (many ? max_hits : 1);
-        if ((st = stage_reserve(sp_stage_bytes(dev, n, 2 * al(3 * sizeof(T) * n) + al(sizeof(T) * n) + al(n), al(n_rec * sizeof(SpatialHit<T>)), ex.size()))) != AVN_OK) return st;
         SQ<T> q{};
         q.n = n; q.cap = max_hits;
-        if ((st = sp_in<T>(r->origin, 3 * (size_t)n, dev, &q.a)) != AVN_OK) return st;
-        if ((st = sp_in<T>(r->direction, 3 * (size_t)n, dev, &q.b)) != AVN_OK) return st;
-        if ((st = sp_in<T>(r->max_distance, n, dev, &q.max_distance)) != AVN_OK) return st;
-        if ((st = sp_in<uint8_t>(r->solid, n, dev, &q.solid)) != AVN_OK) return st;
-        if ((st = sp_in<uint32_t>(r->filter.mask, n, dev, &q.mask)) != AVN_OK) return st;
-        if ((st = stage_in<uint32_t>(ex.data(), ex.size(), &q.excluded)) != AVN_OK) return st;
-        q.n_excluded = (uint32_t)ex.size();
-        q.hits = sp_out<SpatialHit<T>>(out->hits, n_rec, dev);
-        if (many) q.count = sp_out<uint32_t>(out->count, n, dev);
+        StagePlan plan(*this, dev);
+        plan.in(r->origin, 3 * (size_t)n, &q.a); plan.in(r->direction, 3 * (size_t)n, &q.b);
+        plan.in(r->max_distance, n, &q.max_distance); plan.in(r->solid, n, &q.solid);
+        sp_filter_in(plan, q, r->filter, n, ex);
+        plan.out(out->hits, n_rec, &q.hits);
+        if (many) plan.out(out->count, n, &q.count);
+        COMMIT(plan);
         if ((st = sp_run(q, many ? SPQ_HITS : SPQ_CLOSEST)) != AVN_OK) return st;
-        if (!dev) {
-            if ((st = stage_out<SpatialHit<T>>(out->hits, q.hits, n_rec)) != AVN_OK) return st;
-            if (many && (st = stage_out<uint32_t>(out->count, q.count, n)) != AVN_OK) return st;
-        }
+        FINISH(plan);
         return sp_finish();
     }
 
@@ -150,21 +140,16 @@
         std::vector<uint32_t> ex;
         if ((st = sp_excluded(f, dev, ex)) != AVN_OK) return st;
         const size_t n_ids = (size_t)n * cap;
-        if ((st = stage_reserve(sp_stage_bytes(dev, n, 2 * al(3 * sizeof(T) * n), al(n_ids * 4), ex.size()))) != AVN_OK) return st;
         SQ<T> q{};
         q.n = n; q.cap = cap;
-        if ((st = sp_in<T>(a, 3 * (size_t)n, dev, &q.a)) != AVN_OK) return st;
-        if (kind == SPQ_AABBS && (st = sp_in<T>(b, 3 * (size_t)n, dev, &q.b)) != AVN_OK) return st;
-        if ((st = sp_in<uint32_t>(f.mask, n, dev, &q.mask)) != AVN_OK) return st;
-        if ((st = stage_in<uint32_t>(ex.data(), ex.size(), &q.excluded)) != AVN_OK) return st;
-        q.n_excluded = (uint32_t)ex.size();
-        q.ids = n_ids ? sp_out<uint32_t>(out->collider, n_ids, dev) : nullptr;
-        q.count = sp_out<uint32_t>(out->count, n, dev);
+        StagePlan plan(*this, dev);
+        plan.in(a, 3 * (size_t)n, &q.a);
+        if (kind == SPQ_AABBS) plan.in(b, 3 * (size_t)n, &q.b);
+        sp_filter_in(plan, q, f, n, ex);
+        plan.out(out->collider, n_ids, &q.ids); plan.out(out->count, n, &q.count);
+        COMMIT(plan);
         if ((st = sp_run(q, kind)) != AVN_OK) return st;
-        if (!dev) {
-            if ((st = stage_out<uint32_t>(out->collider, q.ids, n_ids)) != AVN_OK) return st;
-            if ((st = stage_out<uint32_t>(out->count, q.count, n)) != AVN_OK) return st;
-        }
+        FINISH(plan);
         return sp_finish();
     }
     avn_status spatial_point_intersections(const avn_spatial_points* p, uint32_t cap, const avn_spatial_ids_out* out) override {
@@ -184,17 +169,15 @@
         const bool dev = (p->flags & AVN_SPATIAL_DEVICE_POINTERS) != 0;
         std::vector<uint32_t> ex;
         if ((st = sp_excluded(p->filter, dev, ex)) != AVN_OK) return st;
-        if ((st = stage_reserve(sp_stage_bytes(dev, n, al(3 * sizeof(T) * n) + al(n), al((size_t)n * sizeof(SpatialProjection<T>)), ex.size()))) != AVN_OK) return st;
         SQ<T> q{};
         q.n = n;
-        if ((st = sp_in<T>(p->point, 3 * (size_t)n, dev, &q.a)) != AVN_OK) return st;
-        if ((st = sp_in<uint8_t>(p->solid, n, dev, &q.solid)) != AVN_OK) return st;
-        if ((st = sp_in<uint32_t>(p->filter.mask, n, dev, &q.mask)) != AVN_OK) return st;
-        if ((st = stage_in<uint32_t>(ex.data(), ex.size(), &q.excluded)) != AVN_OK) return st;
-        q.n_excluded = (uint32_t)ex.size();
-        q.proj = sp_out<SpatialProjection<T>>(out->projection, n, dev);
+        StagePlan plan(*this, dev);
+        plan.in(p->point, 3 * (size_t)n, &q.a); plan.in(p->solid, n, &q.solid);
+        sp_filter_in(plan, q, p->filter, n, ex);
+        plan.out(out->projection, n, &q.proj);
+        COMMIT(plan);
         if ((st = sp_run(q, SPQ_PROJECT)) != AVN_OK) return st;
-        if (!dev && (st = stage_out<SpatialProjection<T>>(out->projection, q.proj, n)) != AVN_OK) return st;
+        FINISH(plan);
         return sp_finish();
     }
     avn_status spatial_shape_intersections(const avn_spatial_shapes* s, uint32_t cap, const avn_spatial_ids_out* out) override {
@@ -207,23 +190,14 @@
         std::vector<uint32_t> ex;
         if ((st = sp_excluded(s->filter, dev, ex)) != AVN_OK) return st;
         const size_t n_ids = (size_t)n * cap;
-        if ((st = stage_reserve(sp_stage_bytes(dev, n, 2 * al(3 * sizeof(T) * n) + al(4 * sizeof(T) * n) + al(n), al(n_ids * 4), ex.size()))) != AVN_OK) return st;
         SQ<T> q{};
-        q.n = n; q.cap = cap;
-        if ((st = sp_in<uint8_t>(s->shape, n, dev, &q.shape)) != AVN_OK) return st;
-        if ((st = sp_in<T>(s->half_extents, 3 * (size_t)n, dev, &q.he)) != AVN_OK) return st;
-        if ((st = sp_in<T>(s->position, 3 * (size_t)n, dev, &q.a)) != AVN_OK) return st;
-        if ((st = sp_in<T>(s->rotation, 4 * (size_t)n, dev, &q.rot)) != AVN_OK) return st;
-        if ((st = sp_in<uint32_t>(s->filter.mask, n, dev, &q.mask)) != AVN_OK) return st;
-        if ((st = stage_in<uint32_t>(ex.data(), ex.size(), &q.excluded)) != AVN_OK) return st;
-        q.n_excluded = (uint32_t)ex.size();
-        q.ids = n_ids ? sp_out<uint32_t>(out->collider, n_ids, dev) : nullptr;
-        q.count = sp_out<uint32_t>(out->count, n, dev);
+        q.cap = cap;
+        StagePlan plan(*this, dev);
+        sp_shape_inputs(plan, q, n, s->shape, s->half_extents, s->position, s->rotation, s->filter, ex);
+        plan.out(out->collider, n_ids, &q.ids); plan.out(out->count, n, &q.count);
+        COMMIT(plan);
         if ((st = sp_run(q, SPQ_SHAPES, sp_any_capsule(s->shape, n, dev))) != AVN_OK) return st;
-        if (!dev) {
-            if ((st = stage_out<uint32_t>(out->collider, q.ids, n_ids)) != AVN_OK) return st;
-            if ((st = stage_out<uint32_t>(out->count, q.count, n)) != AVN_OK) return st;
-        }
+        FINISH(plan);
         return sp_finish();
     }
     // cast_shapes (max_hits == 0: the closest hit per cast) and shape_hits (the max_hits nearest, plus the true count)
@@ -241,42 +215,27 @@
         std::vector<uint32_t> ex;
         if ((st = sp_excluded(s->filter, dev, ex)) != AVN_OK) return st;
         const size_t n_rec = (size_t)n * (many ? max_hits : 1);
-        if ((st = stage_reserve(sp_stage_bytes(dev, n, 3 * al(3 * sizeof(T) * n) + al(4 * sizeof(T) * n) + al(sizeof(T) * n) + al(n), al(n_rec * sizeof(SpatialShapeHit<T>)), ex.size()))) != AVN_OK) return st;
         SQ<T> q{};
         q.n = n; q.cap = max_hits;
-        if ((st = sp_in<uint8_t>(s->shape, n, dev, &q.shape)) != AVN_OK) return st;
-        if ((st = sp_in<T>(s->half_extents, 3 * (size_t)n, dev, &q.he)) != AVN_OK) return st;
-        if ((st = sp_in<T>(s->position, 3 * (size_t)n, dev, &q.a)) != AVN_OK) return st;
-        if ((st = sp_in<T>(s->rotation, 4 * (size_t)n, dev, &q.rot)) != AVN_OK) return st;
-        if ((st = sp_in<T>(s->direction, 3 * (size_t)n, dev, &q.b)) != AVN_OK) return st;
-        if ((st = sp_in<T>(s->max_distance, n, dev, &q.max_distance)) != AVN_OK) return st;
-        if ((st = sp_in<uint32_t>(s->filter.mask, n, dev, &q.mask)) != AVN_OK) return st;
-        if ((st = stage_in<uint32_t>(ex.data(), ex.size(), &q.excluded)) != AVN_OK) return st;
-        q.n_excluded = (uint32_t)ex.size();
-        q.cast = sp_out<SpatialShapeHit<T>>(out->hits, n_rec, dev);
-        if (many) q.count = sp_out<uint32_t>(out->count, n, dev);
+        StagePlan plan(*this, dev);
+        plan.in(s->shape, n, &q.shape); plan.in(s->half_extents, 3 * (size_t)n, &q.he);
+        plan.in(s->position, 3 * (size_t)n, &q.a); plan.in(s->rotation, 4 * (size_t)n, &q.rot);
+        plan.in(s->direction, 3 * (size_t)n, &q.b); plan.in(s->max_distance, n, &q.max_distance);
+        sp_filter_in(plan, q, s->filter, n, ex);
+        plan.out(out->hits, n_rec, &q.cast);
+        if (many) plan.out(out->count, n, &q.count);
+        COMMIT(plan);
         if ((st = sp_run(q, many ? SPQ_CAST_HITS : SPQ_CAST, sp_any_capsule(s->shape, n, dev))) != AVN_OK) return st;
-        if (!dev) {
-            if ((st = stage_out<SpatialShapeHit<T>>(out->hits, q.cast, n_rec)) != AVN_OK) return st;
-            if (many && (st = stage_out<uint32_t>(out->count, q.count, n)) != AVN_OK) return st;
-        }
+        FINISH(plan);
         return sp_finish();
     }
-    // the query-shape fields shared by shape_contacts and depenetrate, staged into sc.q (the SPQ_SHAPES fields); stage_reserve is the caller's
-    avn_status sp_contact_inputs(SC<T>& sc, uint32_t n, bool dev, const uint8_t* shape, const void* he, const void* pos, const void* rot, const avn_spatial_filter& f,
-                                 const std::vector<uint32_t>& ex) {
-        avn_status st;
-        SQ<T>& q = sc.q;
+    // the query-shape fields (the SPQ_SHAPES fields of q) shared by shape_intersections, shape_contacts, depenetrate, cast_moves and move_and_slide
+    void sp_shape_inputs(StagePlan& plan, SQ<T>& q, uint32_t n, const uint8_t* shape, const void* he, const void* pos, const void* rot, const avn_spatial_filter& f,
+                         const std::vector<uint32_t>& ex) {
         q.n = n;
-        if ((st = sp_in<uint8_t>(shape, n, dev, &q.shape)) != AVN_OK) return st;
-        if ((st = sp_in<T>(he, 3 * (size_t)n, dev, &q.he)) != AVN_OK) return st;
-        if ((st = sp_in<T>(pos, 3 * (size_t)n, dev, &q.a)) != AVN_OK) return st;
-        if ((st = sp_in<T>(rot, 4 * (size_t)n, dev, &q.rot)) != AVN_OK) return st;
-        if ((st = sp_in<uint32_t>(f.mask, n, dev, &q.mask)) != AVN_OK) return st;
-        if ((st = stage_in<uint32_t>(ex.data(), ex.size(), &q.excluded)) != AVN_OK) return st;
-        q.n_excluded = (uint32_t)ex.size();
+        plan.in(shape, n, &q.shape); plan.in(he, 3 * (size_t)n, &q.he); plan.in(pos, 3 * (size_t)n, &q.a); plan.in(rot, 4 * (size_t)n, &q.rot);
+        sp_filter_in(plan, q, f, n, ex);
         q.stats = b_sp_stats.as<unsigned long long>();
-        return AVN_OK;
     }
     // MoveAndSlide::intersections: the deepest contact per collider within the prediction distance, ascending collider index
     avn_status spatial_shape_contacts(const avn_spatial_shape_contact_queries* s, uint32_t cap, const avn_spatial_shape_contacts_out* out) override {
@@ -292,21 +251,18 @@
         std::vector<uint32_t> ex;
         if ((st = sp_excluded(s->filter, dev, ex)) != AVN_OK) return st;
         const size_t n_rec = (size_t)n * cap;
-        if ((st = stage_reserve(sp_stage_bytes(dev, n, 2 * al(3 * sizeof(T) * n) + al(4 * sizeof(T) * n) + al(sizeof(T) * n) + al(n), al(n_rec * sizeof(SpatialShapeContact<T>)), ex.size()))) != AVN_OK) return st;
         SC<T> sc{};
-        if ((st = sp_contact_inputs(sc, n, dev, s->shape, s->half_extents, s->position, s->rotation, s->filter, ex)) != AVN_OK) return st;
-        if ((st = sp_in<T>(s->prediction_distance, n, dev, &sc.prediction)) != AVN_OK) return st;
+        StagePlan plan(*this, dev);
+        sp_shape_inputs(plan, sc.q, n, s->shape, s->half_extents, s->position, s->rotation, s->filter, ex);
+        plan.in(s->prediction_distance, n, &sc.prediction);
         sc.q.cap = cap;
         sc.skip_sensors = (s->flags & AVN_SPATIAL_SKIP_SENSORS) ? 1u : 0u;
         sc.pad_unused = 1u;
-        sc.rec = n_rec ? sp_out<SpatialShapeContact<T>>(out->contacts, n_rec, dev) : nullptr;
-        sc.q.count = sp_out<uint32_t>(out->count, n, dev);
+        plan.out(out->contacts, n_rec, &sc.rec); plan.out(out->count, n, &sc.q.count);
+        COMMIT(plan);
         launch_spatial_contacts<T>(sp, sc, stream, true, sp_any_capsule(s->shape, n, dev), sp_ccap);
         HIPCHK(hipGetLastError());
-        if (!dev) {
-            if ((st = stage_out<SpatialShapeContact<T>>(out->contacts, sc.rec, n_rec)) != AVN_OK) return st;
-            if ((st = stage_out<uint32_t>(out->count, sc.q.count, n)) != AVN_OK) return st;
-        }
+        FINISH(plan);
         return sp_finish();
     }
     // MoveAndSlide::depenetrate: the contacts with prediction skin_width into a buffer the world keeps, then k_sp_depenetrate over them
@@ -319,9 +275,11 @@
         const bool dev = (s->flags & AVN_SPATIAL_DEVICE_POINTERS) != 0;
         std::vector<uint32_t> ex;
         if ((st = sp_excluded(s->filter, dev, ex)) != AVN_OK) return st;
-        if ((st = stage_reserve(sp_stage_bytes(dev, n, 2 * al(3 * sizeof(T) * n) + al(4 * sizeof(T) * n) + al(n), al((size_t)n * sizeof(SpatialDepenetration<T>)), ex.size()))) != AVN_OK) return st;
-        SpatialDepenetration<T>* d_out = sp_out<SpatialDepenetration<T>>(out->depenetration, n, dev);
+        SpatialDepenetration<T>* d_out;
+        StagePlan plan(*this, dev);
+        plan.out(out->depenetration, n, &d_out);
         if (cfg->iterations == 0) {
+            COMMIT(plan);
             // depenetration disabled: zero vectors, no traversal (every byte of a record is 0)
             if (n) HIPCHK(hipMemsetAsync(d_out, 0, (size_t)n * sizeof(SpatialDepenetration<T>), stream));
             HIPCHK(hipMemsetAsync(b_sp_stats.p, 0, 4 * sizeof(unsigned long long), stream));
@@ -331,7 +289,8 @@
             uint32_t* d_count;
             GROW(b_sp_crec, std::max<size_t>((size_t)n * AVN_SPATIAL_MAX_HITS, 1), sc.rec);
             GROW(b_sp_ccount, std::max<size_t>(n, 1), d_count);
-            if ((st = sp_contact_inputs(sc, n, dev, s->shape, s->half_extents, s->position, s->rotation, s->filter, ex)) != AVN_OK) return st;
+            sp_shape_inputs(plan, sc.q, n, s->shape, s->half_extents, s->position, s->rotation, s->filter, ex);
+            COMMIT(plan);
             sc.q.cap = AVN_SPATIAL_MAX_HITS;
             sc.q.count = d_count;
             sc.prediction = nullptr;
@@ -348,7 +307,7 @@
             launch_spatial_depenetrate<T>(d, stream);
             HIPCHK(hipGetLastError());
         }
-        if (!dev && (st = stage_out<SpatialDepenetration<T>>(out->depenetration, d_out, n)) != AVN_OK) return st;
+        FINISH(plan);
         return sp_finish();
     }
     // project_velocity per query: no snapshot, no traversal
@@ -359,17 +318,15 @@
         if (n && (!p->velocity || !p->normal_count || !out->velocity || (p->stride && !p->normals))) { error = "spatial_project_velocities: null array"; return AVN_ERR_BAD_ARG; }
         const bool dev = (p->flags & AVN_SPATIAL_DEVICE_POINTERS) != 0;
         const size_t n_nrm = (size_t)n * p->stride * 3;
-        avn_status st;
-        if ((st = stage_reserve(sp_stage_bytes(dev, n, al(3 * sizeof(T) * n) + al(n_nrm * 4), al(3 * sizeof(T) * n), 0))) != AVN_OK) return st;
         SV<T> v{};
         v.n = n; v.stride = p->stride;
-        if ((st = sp_in<T>(p->velocity, 3 * (size_t)n, dev, &v.velocity)) != AVN_OK) return st;
-        if ((st = sp_in<float>(p->normals, n_nrm, dev, &v.normals)) != AVN_OK) return st;
-        if ((st = sp_in<uint32_t>(p->normal_count, n, dev, &v.count)) != AVN_OK) return st;
-        v.out = sp_out<T>(out->velocity, 3 * (size_t)n, dev);
+        StagePlan plan(*this, dev);
+        plan.in(p->velocity, 3 * (size_t)n, &v.velocity); plan.in(p->normals, n_nrm, &v.normals); plan.in(p->normal_count, n, &v.count);
+        plan.out(out->velocity, 3 * (size_t)n, &v.out);
+        COMMIT(plan);
         launch_spatial_project_velocity<T>(v, stream);
         HIPCHK(hipGetLastError());
-        if (!dev && (st = stage_out<T>(out->velocity, v.out, 3 * (size_t)n)) != AVN_OK) return st;
+        FINISH(plan);
         HIPCHK(hipStreamSynchronize(stream));
         return AVN_OK;
     }
@@ -383,21 +340,18 @@
         const bool dev = (s->flags & AVN_SPATIAL_DEVICE_POINTERS) != 0;
         std::vector<uint32_t> ex;
         if ((st = sp_excluded(s->filter, dev, ex)) != AVN_OK) return st;
-        if ((st = stage_reserve(sp_stage_bytes(dev, n, 3 * al(3 * sizeof(T) * n) + al(4 * sizeof(T) * n) + al(sizeof(T) * n) + al(n) + al(4 * (size_t)n), al((size_t)n * sizeof(SpatialMoveHit<T>)), ex.size()))) != AVN_OK) return st;
-        SC<T> sc{};   // (the shared staging of the query-shape fields)
-        if ((st = sp_contact_inputs(sc, n, dev, s->shape, s->half_extents, s->position, s->rotation, s->filter, ex)) != AVN_OK) return st;
         SM<T> m{};
-        m.q = sc.q;
-        if ((st = sp_in<T>(s->movement, 3 * (size_t)n, dev, &m.movement)) != AVN_OK) return st;
-        if ((st = sp_in<T>(s->skin_width, n, dev, &m.skin)) != AVN_OK) return st;
-        if ((st = sp_in<uint32_t>(s->self_entity, n, dev, &m.self_entity)) != AVN_OK) return st;
-        m.out = sp_out<SpatialMoveHit<T>>(out->hits, n, dev);
+        StagePlan plan(*this, dev);
+        sp_shape_inputs(plan, m.q, n, s->shape, s->half_extents, s->position, s->rotation, s->filter, ex);
+        plan.in(s->movement, 3 * (size_t)n, &m.movement); plan.in(s->skin_width, n, &m.skin); plan.in(s->self_entity, n, &m.self_entity);
+        plan.out(out->hits, n, &m.out);
+        COMMIT(plan);
         bool moved = false;
         GROW(b_mv_pend, std::max<size_t>((size_t)n * AVN_SPATIAL_MAX_HITS, 1), m.pending);
         GROW(b_mv_pcount, std::max<size_t>(n, 1), m.pending_count);
         launch_spatial_cast_move<T>(sp, m, true, stream, sp_any_capsule(s->shape, n, dev), sp_ccap);
         HIPCHK(hipGetLastError());
-        if (!dev && (st = stage_out<SpatialMoveHit<T>>(out->hits, m.out, n)) != AVN_OK) return st;
+        FINISH(plan);
         return sp_finish();
     }
     // MoveAndSlide::move_and_slide per character: a fixed sequence of launches over the state buffers, no read-back inside the loop
@@ -416,18 +370,16 @@
         std::vector<uint32_t> ex;
         if ((st = sp_excluded(s->filter, dev, ex)) != AVN_OK) return st;
         const size_t n_hits = (size_t)n * hit_cap;
-        if ((st = stage_reserve(sp_stage_bytes(dev, n, 3 * al(3 * sizeof(T) * n) + al(4 * sizeof(T) * n) + al(n) + al(4 * (size_t)n),
-                                               al((size_t)n * sizeof(SpatialSlide<T>)) + al(n_hits * sizeof(SpatialSlideHit<T>)), ex.size()))) != AVN_OK) return st;
         SC<T> sc{};
-        if ((st = sp_contact_inputs(sc, n, dev, s->shape, s->half_extents, s->position, s->rotation, s->filter, ex)) != AVN_OK) return st;
         SL<T> l{};
+        const uint32_t* self = nullptr;
+        StagePlan plan(*this, dev);
+        sp_shape_inputs(plan, sc.q, n, s->shape, s->half_extents, s->position, s->rotation, s->filter, ex);
+        plan.in(s->velocity, 3 * (size_t)n, &l.vel_in); plan.in(s->self_entity, n, &self);
+        plan.out(out->slides, n, &l.out); plan.out(out->hits, n_hits, &l.hits);
+        COMMIT(plan);
         l.n = n; l.hit_cap = hit_cap; l.n_planes = cfg->n_planes; l.max_planes = cfg->max_planes; l.depen_iterations = cfg->depenetration_iterations;
         l.shape = sc.q.shape; l.he = sc.q.he; l.pos_in = sc.q.a; l.rot = sc.q.rot;
-        if ((st = sp_in<T>(s->velocity, 3 * (size_t)n, dev, &l.vel_in)) != AVN_OK) return st;
-        const uint32_t* self = nullptr;
-        if ((st = sp_in<uint32_t>(s->self_entity, n, dev, &self)) != AVN_OK) return st;
-        l.out = sp_out<SpatialSlide<T>>(out->slides, n, dev);
-        l.hits = n_hits ? sp_out<SpatialSlideHit<T>>(out->hits, n_hits, dev) : nullptr;
         bool moved = false;
         const size_t nn = std::max<size_t>(n, 1);
         uint32_t* d_count;
@@ -470,10 +422,7 @@
         depenetrate();
         launch_spatial_slide_phase<T>(l, SPL_END, stream);
         HIPCHK(hipGetLastError());
-        if (!dev) {
-            if ((st = stage_out<SpatialSlide<T>>(out->slides, l.out, n)) != AVN_OK) return st;
-            if ((st = stage_out<SpatialSlideHit<T>>(out->hits, l.hits, n_hits)) != AVN_OK) return st;
-        }
+        FINISH(plan);
         return sp_finish();
     }
     // ---- casters (include/avian_mi355x_spatial.h "Casters") ----
