@@ -156,7 +156,8 @@ template <class K> void launch_radix_sort(K* keys_a, uint32_t* vals_a, K* keys_b
 void launch_exclusive_scan(const uint32_t* in, uint32_t* out, uint32_t n, uint32_t* block_sums, uint32_t* total, hipStream_t, const uint32_t* enabled = nullptr);
 template <class T> void launch_gather_sorted(const DW<T>&, const BP<T>&, const uint32_t* sorted_collider, uint32_t n, hipStream_t);
 template <class T> void launch_sweep_ranges(const BP<T>&, uint32_t n, const SweepScratch&, hipStream_t, bool counters_clean = false /* SweepScratch::n_long[0..2) is known to be zero */);
-template <class T> void launch_sweep(const BP<T>&, uint32_t n, bool emit, const SweepScratch&, uint32_t* counts, const uint32_t* offsets, avn_pair* out, hipStream_t);
+template <class T> void launch_sweep(const BP<T>&, uint32_t n, bool emit, const SweepScratch&, uint32_t* counts, const uint32_t* offsets, avn_pair* out, uint32_t count_lds_pad, hipStream_t);
+hipError_t sweep_footprint_pad(int device, uint32_t resident_per_cu, uint32_t* pad_bytes);   // dynamic LDS with which exactly that many k_sweep workgroups fit a CU (0: no bound)
 size_t sweep_long_item_bytes();
 template <class T> void launch_bounds_reduce(const T* partial, uint32_t n_partials, double* out6, hipStream_t);   // k_dynamic_bounds' partials -> one (min, max)
 uint32_t sweep_pad_records();

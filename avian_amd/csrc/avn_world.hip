@@ -310,6 +310,13 @@ template <class T> struct World : WorldBase {
         HIPCHK(hipEventCreateWithFlags(&ev_bp_done, hipEventDisableTiming | EV_FLAGS));
         HIPCHK(hipEventCreateWithFlags(&ev_bp_t0, EV_FLAGS)); HIPCHK(hipEventCreateWithFlags(&ev_bp_t1, EV_FLAGS));
         if (avn_env("AVN_NO_BP_OVERLAP")) overlap_bp = false;
+        {
+            uint32_t resident = SWEEP_WG_PER_CU;
+            if (const char* e = avn_env("AVN_SWEEP_WG_PER_CU")) resident = (uint32_t)strtoul(e, nullptr, 10);   // (A/B: 0 = unbounded, the launch of before)
+            HIPCHK(sweep_footprint_pad(c->device, resident, &sweep_lds_pad));
+            if (const char* e = avn_env("AVN_SWEEP_BOUND_MIN_WORK")) sweep_bound_min_work = (uint32_t)strtoul(e, nullptr, 10);
+            if (avn_env("AVN_HOST_TRACE")) std::fprintf(stderr, "[avn] k_sweep count pass beside the solver: %u resident workgroups per CU asked, %u bytes of LDS reserved\n", resident, sweep_lds_pad);
+        }
 #ifdef AVN_MEASURE
         if (avn_env("AVN_NO_OCT")) oct_enabled = false;           // (A/B: every colour on the lane-per-manifold kernel)
         if (avn_env("AVN_NO_HANDLE_SORT")) handle_sort = false;   // (A/B: the solver's arrays in the bookkeeping's list order, as before round 5)

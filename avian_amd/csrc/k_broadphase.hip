@@ -1057,8 +1057,44 @@ template <class T> void launch_sweep_ranges(const BP<T>& bp, uint32_t n, const S
     hipLaunchKernelGGL(k_sweep_ranges<T>, dim3((n + 255) / 256), dim3(256), 0, s, n, bp.s_minx, bp.s_maxx, bp.s_end, bp.s_flags, (LongItem*)sc.long_items,
                        sc.n_long, sc.long_cap, sc.n_long + 1);
 }
+// k_sweep's footprint next to the solver (a frozen-manifold step runs the count pass on a second stream, beside the colour launches): its static LDS lets 7
+// workgroups live on a CU, and the colour kernel's waves queue behind those 28 waves.  A launch may reserve DYNAMIC LDS that the kernel never touches, sized so
+// that exactly `resident_per_cu` workgroups fit a CU's LDS: the hardware then walks the same grid of one workgroup per 64-interval tile with that many
+// resident at a time.  The kernel, its grid and the tile -> workgroup mapping do not change, so neither do counts, records, offsets or pairs.
+// (Measured against a fixed grid of resident workgroups that loop over the tiles: the loop keeps every kernel argument live across the sweep's inner loop --
+//  SGPR spills 8 -> 73 in the count pass, 129 -> 190 us -- DESIGN.md 7.0.0a.)
+hipError_t sweep_footprint_pad(int device, uint32_t resident_per_cu, uint32_t* pad_bytes) {
+    *pad_bytes = 0u;
+    if (!resident_per_cu) return hipSuccess;
+    int lds_per_cu = 0;
+    hipError_t e = hipDeviceGetAttribute(&lds_per_cu, hipDeviceAttributeMaxSharedMemoryPerMultiprocessor, device);
+    if (e != hipSuccess) return e;
+    const void* fns[2] = {(const void*)k_sweep<float, false>, (const void*)k_sweep<double, false>};
+    uint32_t st = 0;
+    for (const void* f : fns) {
+        hipFuncAttributes fa;
+        if ((e = hipFuncGetAttributes(&fa, f)) != hipSuccess) return e;
+        st = std::max<uint32_t>(st, (uint32_t)fa.sharedSizeBytes);
+    }
+    // a workgroup's LDS such that resident_per_cu of them fit and one more does not (2 KiB above the even split: more than any allocation granule)
+    const uint32_t gran = 2048u;
+    const uint32_t total = ((uint32_t)lds_per_cu / (resident_per_cu + 1u) + gran + gran - 1u) / gran * gran;
+    if (total <= st || (uint64_t)total * resident_per_cu > (uint64_t)lds_per_cu) return hipSuccess;   // already that few resident, or no such size: no reservation
+    for (const void* f : fns)
+        if ((e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(total - st))) != hipSuccess) return e;
+    // what the runtime itself makes of it: if a workgroup of that size does not come out at resident_per_cu per CU (an LDS size reported differently
+    // from what the dispatcher allocates from), the bound would silently be another one -- an error, not a quiet fall-back
+    for (const void* f : fns) {
+        int occ = 0;
+        if ((e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, f, (int)SW_THREADS, (size_t)(total - st))) != hipSuccess) return e;
+        if ((uint32_t)occ != resident_per_cu) return hipErrorInvalidConfiguration;
+    }
+    *pad_bytes = total - st;
+    return hipSuccess;
+}
+// count_lds_pad: dynamic LDS reserved by the COUNT pass's k_sweep (sweep_footprint_pad; 0 = none).  The emit pass is awaited by the host and never reserves.
 template <class T> void launch_sweep(const BP<T>& bp, uint32_t n, bool emit, const SweepScratch& sc, uint32_t* counts, const uint32_t* offsets, avn_pair* out,
-                                     hipStream_t s) {
+                                     uint32_t count_lds_pad, hipStream_t s) {
     if (!n) return;
     uint32_t nb = (n + 63u) / 64u;
     nb = ((nb + 7) / 8) * 8;
@@ -1069,7 +1105,7 @@ template <class T> void launch_sweep(const BP<T>& bp, uint32_t n, bool emit, con
         hipLaunchKernelGGL((k_sweep_long<T, true>), dim3(2048), dim3(SW_THREADS), 0, s, bp.s_yz, bp.s_info, bp.s_flags, hs, li, sc.n_long, sc.long_counts,
                            sc.long_off, offsets, out);
     } else {
-        hipLaunchKernelGGL((k_sweep<T, false>), dim3(nb), dim3(SW_THREADS), 0, s, n, bp.s_yz, bp.s_bb, bp.s_bb2, bp.s_end, bp.s_info, bp.s_flags, hs, counts, offsets, out, sc.hits);
+        hipLaunchKernelGGL((k_sweep<T, false>), dim3(nb), dim3(SW_THREADS), count_lds_pad, s, n, bp.s_yz, bp.s_bb, bp.s_bb2, bp.s_end, bp.s_info, bp.s_flags, hs, counts, offsets, out, sc.hits);
         hipLaunchKernelGGL((k_sweep_long<T, false>), dim3(2048), dim3(SW_THREADS), 0, s, bp.s_yz, bp.s_info, bp.s_flags, hs, li, sc.n_long, sc.long_counts,
                            sc.long_off, offsets, out);
         hipLaunchKernelGGL(k_long_finish, dim3(64), dim3(256), 0, s, li, sc.n_long, sc.long_counts, sc.long_off, counts);
@@ -1086,7 +1122,7 @@ uint32_t sweep_pad_records() { return 8u; }  // k_sweep reads whole candidate ba
     template void launch_gather_sorted<T>(const DW<T>&, const BP<T>&, const uint32_t*, uint32_t, hipStream_t); \
     template void launch_sweep_ranges<T>(const BP<T>&, uint32_t, const SweepScratch&, hipStream_t, bool);     \
     template uint32_t launch_dynamic_bounds<T>(const DW<T>&, const BP<T>&, T*, hipStream_t);            \
-    template void launch_sweep<T>(const BP<T>&, uint32_t, bool, const SweepScratch&, uint32_t*, const uint32_t*, avn_pair*, hipStream_t);
+    template void launch_sweep<T>(const BP<T>&, uint32_t, bool, const SweepScratch&, uint32_t*, const uint32_t*, avn_pair*, uint32_t, hipStream_t);
 INST(float)
 INST(double)
 #undef INST

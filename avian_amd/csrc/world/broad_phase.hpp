@@ -21,6 +21,21 @@
     uint32_t* h_counters = nullptr;  // pinned: [dropped, unsorted, total, long chunks, long overflow]
     hipEvent_t ev_counters = nullptr;
     uint32_t collect_n = 0;
+    // k_sweep's footprint beside the solver: in a frozen-manifold step the count pass runs on stream_bp next to the colour launches, and is bounded to
+    // SWEEP_WG_PER_CU resident workgroups per CU through an LDS reservation (k_broadphase.hip: sweep_footprint_pad; R chosen by measurement among 1, 2, 4 and
+    // unbounded, profiles/bp_early_sweep_footprint.txt).  Wherever the sweep is on the critical path -- the device closed loop, a stand-alone
+    // COLLECT_COLLISION_PAIRS, a step without the overlap -- it keeps the whole machine.
+    // The bound lengthens the chain (cfg2: it ends 0.33 -> 0.50 ms into the step), so it is taken only where the solver beside it is known to be much longer:
+    // substeps x manifolds >= SWEEP_BOUND_MIN_WORK x intervals.  cfg2 (678 200 manifolds, 100 001 intervals) has 6.8 per substep: bounded from two substeps
+    // on, not with one (0.47 ms step), and never in a collider-heavy, contact-light scene, where the sweep is the step (profiles/bp_early_bound_condition.txt).
+    static constexpr uint32_t SWEEP_WG_PER_CU = 2;
+    static constexpr uint32_t SWEEP_BOUND_MIN_WORK = 12;
+    uint32_t sweep_lds_pad = 0;   // bytes (init)
+    uint32_t sweep_bound_min_work = SWEEP_BOUND_MIN_WORK;   // (A/B in `make measure` builds: AVN_SWEEP_BOUND_MIN_WORK, 0 = wherever the chain overlaps)
+    uint32_t sweep_count_pad() const {
+        if (pipe_on || bs != stream_bp) return 0u;
+        return (uint64_t)cfg.substeps * dw.n_manifolds >= (uint64_t)sweep_bound_min_work * bp.n_intervals ? sweep_lds_pad : 0u;
+    }
     bool collect_pending = false;
     avn_status collect_launch() {
         uint32_t n = bp.n_intervals;
@@ -47,7 +62,7 @@
         launch_radix_sort<Key>(keys_a, vals_a, keys_b, vals_b, n, b_hist.as<uint32_t>(), b_block_sums.as<uint32_t>(), d_dropped + 1, &keys_sorted, &vals_sorted, bs);
         launch_gather_sorted<T>(dw, bp, vals_sorted, n, bs);
         launch_sweep_ranges<T>(bp, n, sweep_scratch, bs, clean);
-        launch_sweep<T>(bp, n, false, sweep_scratch, b_counts.as<uint32_t>(), nullptr, nullptr, bs);
+        launch_sweep<T>(bp, n, false, sweep_scratch, b_counts.as<uint32_t>(), nullptr, nullptr, sweep_count_pad(), bs);
         launch_exclusive_scan(b_counts.as<uint32_t>(), b_offsets.as<uint32_t>(), n * sweep_count_slots(), b_block_sums.as<uint32_t>(), d_total, bs);
         launches += 3 + radix_sort_launches(n, (uint32_t)sizeof(Key)) + 3 + exclusive_scan_launches(n * sweep_count_slots());
         HIPCHK(hipGetLastError());
@@ -85,7 +100,7 @@
             hipError_t err;
             b_pairs.ensure((size_t)total * sizeof(avn_pair), err);
             if (err != hipSuccess) { error = "pair buffer allocation failed"; return AVN_ERR_OOM; }
-            launch_sweep<T>(bp, n, true, sweep_scratch, b_counts.as<uint32_t>(), b_offsets.as<uint32_t>(), b_pairs.as<avn_pair>(), bs);
+            launch_sweep<T>(bp, n, true, sweep_scratch, b_counts.as<uint32_t>(), b_offsets.as<uint32_t>(), b_pairs.as<avn_pair>(), 0u, bs);
             launches += 2;
             HIPCHK(hipGetLastError());
             h_pairs.resize(total);

@@ -446,7 +446,7 @@
                 hipError_t err;
                 b_pairs.ensure((size_t)total * sizeof(avn_pair), err);
                 if (err != hipSuccess) { error = "pair buffer allocation failed"; return fail(AVN_ERR_OOM); }
-                launch_sweep<T>(bp, collect_n, true, sweep_scratch, b_counts.as<uint32_t>(), b_offsets.as<uint32_t>(), b_pairs.as<avn_pair>(), bs);
+                launch_sweep<T>(bp, collect_n, true, sweep_scratch, b_counts.as<uint32_t>(), b_offsets.as<uint32_t>(), b_pairs.as<avn_pair>(), 0u, bs);
                 launches += 2;
                 if ((st = hk_filter_device(total, bs)) != AVN_OK) return fail(st);   // CollisionHooks::filter_pairs: the pairs the hook rejects never get an id (world/hooks.hpp)
             }

@@ -15,6 +15,11 @@
             HIPCHK(hipEventElapsedTime(&e, ev[0], ev[4]));
             if (avn_env("AVN_HOST_TRACE")) std::fprintf(stderr, "[avn events] step start -> solver start %.4f ms, prepare %.4f, substeps %.4f, finalize %.4f, whole %.4f\n", a, b, c, d, e);
             // overlapped broad phase: its own duration on its own stream (it is NOT a term of step_ms then)
+            if (bp_timed && avn_env("AVN_HOST_TRACE")) {   // (debugging aid: when the second stream's chain was done, without a profiler attached.  Its START is not
+                float s1 = 0;                               //  printed: ev_bp_t0 sits right behind the wait on ev[0] and reads ev[0]'s time)
+                HIPCHK(hipEventElapsedTime(&s1, ev[0], ev_bp_t1));
+                std::fprintf(stderr, "[avn events] broad phase on its stream: done %.4f ms after the step's start\n", s1);
+            }
             if (bp_timed) HIPCHK(hipEventElapsedTime(&a, ev_bp_t0, ev_bp_t1));
             last_timers.broad_phase_ms = a; last_timers.prepare_ms = b; last_timers.substeps_ms = c; last_timers.finalize_ms = d;
             last_timers.step_ms = e;
