@@ -229,6 +229,15 @@ def declare_swept_ccd(dll):
         dll.avn_swept_ccd_stats_get.argtypes = [vp, vp]
 
 
+class avn_broad_phase_stats(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("intervals", C.c_uint32), ("dropped", C.c_uint32), ("unsorted", C.c_uint32), ("pairs", C.c_uint32),
+                ("long_chunks", C.c_uint32), ("long_retries", C.c_uint32), ("sort_form", C.c_uint32)]
+
+
+BROAD_PHASE_STATS_SYMBOLS = ("avn_broad_phase_stats_get",)   # a plain avn_ function, not part of ABI_SYMBOLS: absent from the oracle and from an older library
+SORT_FORM_NONE, SORT_FORM_ONE_WORKGROUP, SORT_FORM_TILES_MERGE, SORT_FORM_FUSED_RADIX, SORT_FORM_RADIX_SCAN = range(5)
+
+
 class avn_slab_in(C.Structure):
     _fields_ = [("n_colliders", C.c_uint32), ("aabb_min_x", vp), ("aabb_max_x", vp), ("prev_order", vp), ("n_prev", C.c_uint32),
                 ("n_ranks", C.c_uint32), ("rank", C.c_uint32)]
@@ -815,6 +824,16 @@ class World:
         n = C.c_size_t()
         self._check(self.lib.fn("aabbs_download")(self.handle, _ptr(mn), _ptr(mx), _ptr(ents), C.byref(n)))
         return mn, mx, ents[: n.value]
+
+    def broad_phase_stats(self) -> avn_broad_phase_stats:
+        """``avn_broad_phase_stats_get``: which sort form and sweep path the last collect took (the product only)."""
+        if not all(hasattr(self.lib.dll, name) for name in BROAD_PHASE_STATS_SYMBOLS):
+            raise ImportError(f"{self.lib.path} does not export avn_broad_phase_stats_get")
+        fn = self.lib.dll.avn_broad_phase_stats_get
+        fn.restype, fn.argtypes = C.c_int32, [vp, C.POINTER(avn_broad_phase_stats)]
+        o = avn_broad_phase_stats(C.sizeof(avn_broad_phase_stats))
+        self._check(fn(self.handle, C.byref(o)))
+        return o
 
     # -- narrow phase, part 2: the ContactGraph side -----------------------------------------------------------------
     def collider_materials_upload(self, friction=None, restitution=None, friction_combine=None, restitution_combine=None):

@@ -543,8 +543,11 @@ static_assert(SW_BB_GROUP == 8u && SW_BB2_GROUP == 64u, "k_gather_sorted reduces
 // ranges, so one interval that reaches much further than its 63 neighbours (a ground plate among boxes: 5 500 candidates
 // against ~200 in the reference's pyramid scenes) drags the whole wave through its range on the slow per-lane-bounds path --
 // 160 us of a 5 k-box step.  An interval with more than SW_LONG_MIN candidates and more than 4x the mean of the other lanes
-// of its wave goes to the long path too (at most 16 lanes of a wave can satisfy that, so the item capacity holds).  The
-// split only moves work between two order-exact paths: the pair list does not change.
+// of its wave goes to the long path too.  At most 16 lanes of a wave can satisfy the relative rule, but each of them may ask
+// for up to SW_CAP / SW_LCHUNK chunks, and under the absolute rule all 64 lanes can be long: the item capacity (colliders +
+// 65 536) is NOT a bound.  A request past it raises *overflow, writes no item, and the host grows the chunk arrays to the
+// requested count and runs the count pass again (collect_finish, the closed loop's step).  The split only moves work between
+// two order-exact paths: the pair list does not change.
 template <class T>
 __global__ __launch_bounds__(256) void k_sweep_ranges(uint32_t n, const T* __restrict__ s_minx, const T* __restrict__ s_maxx, uint32_t* __restrict__ s_end,
                                                        uint32_t* __restrict__ s_flags, LongItem* __restrict__ items, uint32_t* __restrict__ n_long,
@@ -997,6 +1000,10 @@ template <> bool sort_small<uint32_t>(uint32_t* keys_a, uint32_t* vals_a, uint32
     return false;
 }
 uint32_t radix_sort_launches(uint32_t n, uint32_t key_bytes) { return key_bytes == 4 && n <= SS_MAX ? 1u : key_bytes == 4 && n <= SM_TILE * SM_MAX_TILES ? 2u : key_bytes * radix_pass_launches(n); }
+// the same decisions as launch_radix_sort below, by name (avn_broad_phase_stats::sort_form): 1 one workgroup, 2 tiles + merge, 3 fused radix, 4 radix + scan
+uint32_t radix_sort_form(uint32_t n, uint32_t key_bytes) {
+    return n == 0 ? 0u : key_bytes == 4 && n <= SS_MAX ? 1u : key_bytes == 4 && n <= SM_TILE * SM_MAX_TILES ? 2u : radix_blocks(n) <= RS_FUSED_MAX_BLOCKS ? 3u : 4u;
+}
 template <class K> void launch_radix_sort(K* keys_a, uint32_t* vals_a, K* keys_b, uint32_t* vals_b, uint32_t n, uint32_t* hist, uint32_t* block_sums,
                                           const uint32_t* unsorted, K** keys_out, uint32_t** vals_out, hipStream_t s) {
     // Every kernel returns at once (or copies through) when *unsorted == 0 (the persistent interval order is still sorted: the reference's

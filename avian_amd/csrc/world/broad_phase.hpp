@@ -37,13 +37,27 @@
         return (uint64_t)cfg.substeps * dw.n_manifolds >= (uint64_t)sweep_bound_min_work * bp.n_intervals ? sweep_lds_pad : 0u;
     }
     bool collect_pending = false;
+    // avn_broad_phase_stats_get: which of the interchangeable paths the last collect took, from the counters the host has just read back.
+    // first_unsorted: the unsorted flag of the collect's FIRST count pass (a repeated pass starts from the order the first one left sorted).
+    avn_broad_phase_stats bp_stats{};
+    void bp_stats_note(uint32_t first_unsorted, uint32_t retries) {
+        bp_stats.intervals = collect_n; bp_stats.dropped = h_counters[0]; bp_stats.unsorted = first_unsorted ? 1u : 0u; bp_stats.pairs = h_counters[2];
+        bp_stats.long_chunks = h_counters[3]; bp_stats.long_retries = retries;
+        bp_stats.sort_form = first_unsorted ? radix_sort_form(collect_n, (uint32_t)sizeof(Key)) : 0u;
+    }
+    avn_status broad_phase_stats_get(avn_broad_phase_stats* out) override {
+        if (!out || out->struct_size != sizeof(avn_broad_phase_stats)) { error = "broad_phase_stats_get: null argument or struct_size"; return AVN_ERR_BAD_ARG; }
+        *out = bp_stats;
+        out->struct_size = (uint32_t)sizeof(avn_broad_phase_stats);
+        return AVN_OK;
+    }
     avn_status collect_launch() {
         uint32_t n = bp.n_intervals;
         h_pairs.clear();
         last_timers.pair_count = 0;
         collect_n = n;
         collect_pending = false;
-        if (n == 0) return AVN_OK;
+        if (n == 0) { bp_stats = avn_broad_phase_stats{}; return AVN_OK; }
         if (n > (1u << 26)) { error = "collect_collision_pairs: more than 2^26 intervals"; return AVN_ERR_CAPACITY; }
         if (!h_counters) {
             HIPCHK(hipHostMalloc((void**)&h_counters, 8 * sizeof(uint32_t), hipHostMallocDefault));
@@ -87,6 +101,8 @@
         collect_pending = false;
         uint32_t n = collect_n;
         HIPCHK(hipEventSynchronize(ev_counters));
+        const uint32_t first_unsorted = h_counters[1];
+        uint32_t retries = 0;
         if (h_counters[4]) {   // more long-interval chunks than slots: grow to the requested count and run the count pass again
             avn_status st = grow_long_chunks(h_counters[3]);
             if (st != AVN_OK) return st;
@@ -94,7 +110,9 @@
             collect_pending = false;
             HIPCHK(hipEventSynchronize(ev_counters));
             if (h_counters[4]) { error = "collect_collision_pairs: long-interval chunk capacity exceeded"; return AVN_ERR_CAPACITY; }
+            retries = 1;
         }
+        bp_stats_note(first_unsorted, retries);
         uint32_t dropped = h_counters[0], total = h_counters[2];
         if (total) {
             hipError_t err;

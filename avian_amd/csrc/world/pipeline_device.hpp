@@ -433,13 +433,17 @@
             HIPCHK(spin_event(ev_counters));
             ht("read 0 (pair count) arrived");
             t0 = std::chrono::steady_clock::now();
+            const uint32_t first_unsorted = h_counters[1];
+            uint32_t retries = 0;
             if (h_counters[4]) {   // more long-interval chunks than slots: grow to the requested count and run the count pass again
                 if ((st = grow_long_chunks(h_counters[3])) != AVN_OK) return fail(st);
                 if ((st = collect_launch()) != AVN_OK) return fail(st);
                 collect_pending = false;
                 HIPCHK(hipEventSynchronize(ev_counters));
                 if (h_counters[4]) { error = "collect_collision_pairs: long-interval chunk capacity exceeded"; return fail(AVN_ERR_CAPACITY); }
+                retries = 1;
             }
+            bp_stats_note(first_unsorted, retries);
             const uint32_t dropped = h_counters[0];
             total = h_counters[2];
             if (total) {

@@ -1235,6 +1235,23 @@ AVN_API avn_status AVN_FN(shard_stats_get)(avn_shard* s, avn_shard_stats* out);
  * Empty worlds return min = +inf, max = -inf. */
 AVN_API avn_status AVN_FN(dynamic_bounds)(avn_world* w, double aabb_min[3], double aabb_max[3]);
 
+/* ---- which path the broad phase took (inspection; the product only: the oracle has one path and does not export it) ------------------------
+ * COLLECT_COLLISION_PAIRS answers through interchangeable, order-exact paths chosen by size: four forms of the sort, the per-wave sweep or
+ * chunked "long" intervals, a repeated count pass when the chunk list was too small.  The pair list cannot tell which of them ran; this can.
+ * Filled on the host from the counters the last collect -- AVN_SYS_COLLECT_COLLISION_PAIRS, avn_step, a step of the device closed loop -- read
+ * back anyway: no kernel, launch or device buffer exists for it.  Zeros before the first collect and after one over no interval. */
+typedef struct avn_broad_phase_stats {
+    uint32_t struct_size;    /* in: sizeof(avn_broad_phase_stats) */
+    uint32_t intervals;      /* intervals the collect swept (the dropped ones included) */
+    uint32_t dropped;        /* of them: non-finite AABB, sorted last and truncated off the list */
+    uint32_t unsorted;       /* 1: the persistent order was no longer sorted by this frame's min.x and the sort ran */
+    uint32_t pairs;          /* pairs the sweep emitted (before CollisionHooks::filter_pairs) */
+    uint32_t long_chunks;    /* chunks the last count pass requested for long intervals (512 candidates each) */
+    uint32_t long_retries;   /* count passes repeated because the chunk list was too small: 0 or 1 */
+    uint32_t sort_form;      /* 0 none (unsorted == 0), 1 one workgroup, 2 tiles + merge, 3 fused radix passes, 4 radix passes + scan */
+} avn_broad_phase_stats;
+AVN_API avn_status avn_broad_phase_stats_get(avn_world* w, avn_broad_phase_stats* out);
+
 #ifdef __cplusplus
 }
 #endif

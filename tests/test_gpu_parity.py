@@ -185,8 +185,10 @@ def test_broadphase_pairs_bit_exact_over_frames(bits):
 
 
 def test_broadphase_long_interval_path():
-    """An AABB that spans the scene (ground) has > SW_CAP (8192) sweep candidates: its tail is swept by the
-    workgroup-cooperative kernel; the pair sequence must still be the reference's (i asc, j asc) order."""
+    """An AABB that spans the scene (ground) has 10 800 sweep candidates against 688 on average for the boxes of its wave: long by the RELATIVE rule of
+    k_sweep_ranges (SW_CAP is 65 536: the absolute rule is out of reach here), one interval of 22 chunks swept by the workgroup-cooperative kernel
+    (tests/test_broadphase_reference_cpu.py pins that count; tests/test_gpu_broadphase_paths.py covers the absolute rule).  The pair sequence must still be
+    the reference's (i asc, j asc) order."""
     from avian_amd import scenes
     sc = scenes.box_stack(30, 6, 60)   # 10 800 cubes on one big static ground, plus a second huge static slab
     wo, wh = make_pair(32)
@@ -257,19 +259,14 @@ def test_sweep_batch_cull_with_non_finite_yz_and_ragged_group_count(bits):
 
 
 def test_long_interval_chunk_overflow_grows_and_retries(monkeypatch):
-    """A wall of 9 600 boxes sharing one x extent: every interval has > 8 192 sweep candidates and is cut into chunks -- more chunks
-    than the (here artificially small) chunk arrays hold.  The library must grow them and run the count pass again instead of reading the
-    unwritten items: same pair list as the oracle."""
-    monkeypatch.setenv("AVN_SWEEP_LONG_CAP", "1024")
-    ny, nz = 120, 80
-    n = ny * nz
-    yy, zz = np.meshgrid(np.arange(ny) * 3.0, np.arange(nz) * 3.0, indexing="ij")
-    rng = np.random.default_rng(7)
-    pos = np.stack([rng.uniform(-0.2, 0.2, n), yy.ravel(), zz.ravel()], 1)
-    pos[::7, 1] += 2.2   # some boxes reach their neighbours
-    bodies = dict(position=pos, rotation=np.tile([0, 0, 0, 1.0], (n, 1)), linear_velocity=np.zeros((n, 3)), angular_velocity=np.zeros((n, 3)),
-                  inv_mass=np.ones(n), inv_inertia_local=np.tile([6, 0, 0, 6, 0, 6.0], (n, 1)), rb_type=np.zeros(n, np.uint8))
-    col = dict(entity_index=np.arange(n, dtype=np.uint32), body=np.arange(n, dtype=np.int32), shape=np.zeros(n, np.uint8), half_extents=np.full((n, 3), 0.5))
+    """A strip of 5 000 small boxes under two planks of 2 500 sweep candidates each: two long intervals (relative rule), cut into 5 chunks each -- more
+    chunks than the (here artificially small: 8) chunk arrays hold.  The library must grow them and run the count pass again instead of reading the
+    unwritten items: same pair list as the oracle, and avn_broad_phase_stats says the count pass WAS repeated.  (Until SW_CAP went from
+    8 192 to 65 536 this test used a wall of 9 600 boxes sharing one x extent; since then that wall has no long interval at all and the test compared two
+    ordinary sweeps: tests/test_broadphase_reference_cpu.py.  The variants -- NaN pose, second frame, closed loop -- are in tests/test_gpu_broadphase_paths.py.)"""
+    import broadphase_reference as R
+    monkeypatch.setenv("AVN_SWEEP_LONG_CAP", "8")
+    bodies, col, _ = R.world_tables(*R.strip(5000, 1 / 32, 0.05, [(100, 2500), (2400, 2500)]))
     from helpers import hip_measure_lib   # (AVN_SWEEP_LONG_CAP is a test hook of the `make measure` build)
     wo, wh = F.World(oracle_lib(), F.default_config(32)), F.World(hip_measure_lib(), F.default_config(32))
     for w in (wo, wh):
@@ -278,6 +275,8 @@ def test_long_interval_chunk_overflow_grows_and_retries(monkeypatch):
         w.run_system("UPDATE_AABB"); w.run_system("COLLECT_COLLISION_PAIRS")
     po, ph = wo.pairs_get(), wh.pairs_get()
     assert len(po) > 500 and np.array_equal(po, ph)
+    st = wh.broad_phase_stats()
+    assert st.long_chunks == 10 and st.long_retries == 1, "the chunk list overflowed and the count pass ran again"
 
 
 def test_bad_arguments_are_reported_not_crashed():

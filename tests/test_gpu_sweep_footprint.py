@@ -4,7 +4,8 @@
 oracle's COLLECT_COLLISION_PAIRS on the same colliders, in f32 and f64 --
   - seeded random unit boxes in a volume sized for ~6 overlaps each, uploaded in ascending min.x, n = 1, 63, 64, 65, 129 (the 64-interval tile's edges);
   - n = 64 * (CU count * 2) + 65: more tiles than workgroups can be resident under the bound;
-  - a ground slab spanning everything (the long-interval path) and a NaN pose (dropped intervals);
+  - a ground slab spanning everything (the long-interval path, by the RELATIVE rule of k_sweep_ranges: 1 500 candidates in 3 chunks, 288 in 1 chunk
+    on the lattice -- the absolute rule, SW_CAP = 65 536 candidates, is tests/test_gpu_broadphase_paths.py's) and a NaN pose (dropped intervals);
   - a frozen box stack over four steps with an upload that makes the third step find new pairs (the emit pass): pair count, pairs, bodies, impulses.
 The release build takes the bound only by its work rule, which these small scenes do not meet, so the bounded launches run on the `make measure`
 build with AVN_SWEEP_BOUND_MIN_WORK=0 (the bound wherever the chain overlaps) and AVN_SWEEP_WG_PER_CU = 2 (the default), 1 (a workgroup's LDS above
