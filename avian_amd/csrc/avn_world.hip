@@ -25,23 +25,11 @@ namespace avn {
             return e_ == hipErrorOutOfMemory ? AVN_ERR_OOM : AVN_ERR_HIP;                      \
         }                                                                                     \
     } while (0)
-
-DevBuf::~DevBuf() { if (p) (void)hipFree(p); }
-bool DevBuf::ensure(size_t bytes, hipError_t& err, bool keep, hipStream_t s) {
-    err = hipSuccess;
-    if (bytes <= cap) return false;
-    size_t ncap = std::max(bytes, cap + cap / 2);
-    ncap = (ncap + 255) & ~(size_t)255;
-    void* np = nullptr;
-    err = hipMalloc(&np, ncap);
-    if (err != hipSuccess) return false;
-    if (p) {
-        if (keep) { err = hipMemcpyAsync(np, p, cap, hipMemcpyDeviceToDevice, s); if (err == hipSuccess) err = hipStreamSynchronize(s); }
-        (void)hipFree(p);
-    }
-    p = np;
-    cap = ncap;
-    return true;
+// every DevBuf / Pinned ensure (avn_devbuf.h): a failure names the call and is AVN_ERR_OOM
+#define ALLOC(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) return alloc_failed(error, #call, e_); } while (0)
+__attribute__((noinline)) static avn_status alloc_failed(std::string& error, const char* call, hipError_t e) {
+    error = std::string(call) + ": " + hipGetErrorName(e);
+    return AVN_ERR_OOM;
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -175,20 +163,7 @@ template <class T> struct World : WorldBase {
     PipeColor pipe_colors[AVN_GRAPH_COLOR_COUNT];
     std::vector<uint32_t> pipe_handles;        // colour-major contact ids (GraphColor::manifold_handles)
     uint32_t pipe_offsets[AVN_GRAPH_COLOR_COUNT + 1];
-    // pinned host staging (grow-only): island block arrays on their way up, narrow-phase change list on its way down
-    struct Pinned {
-        void* p = nullptr; size_t cap = 0;
-        ~Pinned() { if (p) (void)hipHostFree(p); }
-        hipError_t ensure(size_t bytes) {
-            if (bytes <= cap) return hipSuccess;
-            if (p) (void)hipHostFree(p);
-            p = nullptr; cap = 0;
-            size_t c = (bytes + bytes / 2 + 4095) & ~(size_t)4095;
-            hipError_t e = hipHostMalloc(&p, c, hipHostMallocDefault);
-            if (e == hipSuccess) cap = c;
-            return e;
-        }
-    };
+    using Pinned = avn::Pinned;   // pinned host staging: island block arrays on their way up, narrow-phase change list on its way down
     avn_pipeline_stats pipe_stats;
     // ---- the same closed loop with the bookkeeping ON THE DEVICE (k_graph.hip): the host keeps exact mirrors of a few counters ----
     bool pipe_dev = false;               // avn_pipeline_enable(1): device bookkeeping (AVN_PIPELINE_HOST=1 or enable(2): the host structures above)
@@ -325,9 +300,7 @@ template <class T> struct World : WorldBase {
         for (auto& x : ev_dg) HIPCHK(hipEventCreateWithFlags(&x, EV_FLAGS));
         for (auto& x : ev_dgs) HIPCHK(hipEventCreateWithFlags(&x, EV_FLAGS));
         for (auto& x : ev_bias) HIPCHK(hipEventCreateWithFlags(&x, EV_FLAGS));
-        hipError_t err;
-        b_misc.ensure(4096, err);
-        if (err != hipSuccess) { error = "hipMalloc failed"; return AVN_ERR_OOM; }
+        ALLOC(b_misc.ensure(4096));
         HIPCHK(hipMemsetAsync(b_misc.p, 0, 4096, stream));
         // misc layout: [0..25) color offsets, [32] constraint count, [33] n_dropped, [34] unsorted flag, [35] pair total,
         // [36] long chunks used, [37] long chunk overflow
@@ -398,7 +371,7 @@ template <class T> struct World : WorldBase {
     // downloads.  All copies are hipMemcpyAsync on `stream`, in declaration order.  Device pointers are valid from commit() on.
     struct StagePlan {
         World& w;
-        std::string& error;   // (HIPCHK's)
+        std::string& error;   // (HIPCHK's and ALLOC's)
         const bool direct;    // AVN_SPATIAL_DEVICE_POINTERS: in() / out() arrays are the caller's device pointers, used as they are
         avn_stage::Layout l;
         explicit StagePlan(World& w_, bool direct_ = false) : w(w_), error(w_.error), direct(direct_) {}
@@ -416,11 +389,9 @@ template <class T> struct World : WorldBase {
         size_t bytes() const { return l.total; }
         avn_status commit() {
             if (!l.ok) { error = "staging: more arrays than a plan holds, or a size beyond size_t"; return AVN_ERR_BAD_ARG; }
-            hipError_t err;
             HIPCHK(hipStreamSynchronize(w.stream));  // arena reuse: previous users must be done
             if (w.stream_bp) HIPCHK(hipStreamSynchronize(w.stream_bp));
-            w.stage.ensure(l.total + 4096, err);
-            if (err != hipSuccess) { error = "staging allocation failed"; return AVN_ERR_OOM; }
+            ALLOC(w.stage.ensure(l.total + 4096));
             if (!l.assign(w.stage.p, w.stage.cap)) { error = "staging: the plan does not fit its arena"; return AVN_ERR_STATE; }
             for (int i = 0; i < l.n; ++i)
                 if (l.item[i].dir == avn_stage::IN) HIPCHK(hipMemcpyAsync(*l.item[i].dev, l.item[i].host, l.item[i].bytes, hipMemcpyHostToDevice, w.stream));
@@ -439,14 +410,9 @@ template <class T> struct World : WorldBase {
 #define FINISH(plan) do { avn_status s_ = (plan).finish(); if (s_ != AVN_OK) return s_; } while (0)
     static size_t al(size_t b) { return (b + 63) & ~(size_t)63; }
 
-    template <class U> avn_status grow(DevBuf& b, size_t count, U** field, bool& moved) {
-        hipError_t err;
-        if (b.ensure(count * sizeof(U), err)) moved = true;
-        if (err != hipSuccess) { error = std::string("hipMalloc: ") + hipGetErrorName(err); return AVN_ERR_OOM; }
-        *field = b.as<U>();
-        return AVN_OK;
-    }
-#define GROW(buf, count, field) do { avn_status s_ = grow(buf, count, &(field), moved); if (s_ != AVN_OK) return s_; } while (0)
+// a typed device array of `count` elements in `buf`, its pointer in `field`; an optional fourth argument is ensure()'s `bool* moved`
+#define GROW(buf, count, field, ...) ALLOC(buf.ensure_as(count, &(field), ##__VA_ARGS__))
+#define GROW_KEEP(buf, count, field) ALLOC(buf.ensure_as(count, &(field), nullptr, true, stream))   // ... with the old contents, copied on `stream`
 
 #include "world/bodies.hpp"
 #include "world/manifolds.hpp"

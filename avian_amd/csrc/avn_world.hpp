@@ -21,23 +21,12 @@
 #include <unordered_map>
 #include <vector>
 
+#include "avn_devbuf.h"
 #include "avn_kernels.h"
 #include "../../include/avian_mi355x_spatial.h"
 #include "../../include/avian_mi355x_ccd.h"
 
 namespace avn {
-
-struct DevBuf {
-    void* p = nullptr;
-    size_t cap = 0;
-    ~DevBuf();
-    DevBuf() = default;
-    DevBuf(const DevBuf&) = delete;
-    DevBuf& operator=(const DevBuf&) = delete;
-    // grows (never shrinks); returns true when the pointer changed; contents are NOT preserved unless keep
-    bool ensure(size_t bytes, hipError_t& err, bool keep = false, hipStream_t s = nullptr);
-    template <class U> U* as() const { return (U*)p; }
-};
 
 // Host-built execution schedule that makes a serial joint loop parallel without changing its result
 // (see k_xpbd.hip header).

@@ -25,13 +25,13 @@
         if (n + DUMMY_SLOTS > cap_bodies || !have_bodies) {
             HIPCHK(hipStreamSynchronize(stream));
             size_t c = (size_t)std::max<uint32_t>(n + DUMMY_SLOTS, cap_bodies + cap_bodies / 2);  // + the virtual DUMMY bodies of joint_damping
-            GROW(b_pos, c, dw.pos); GROW(b_rot, c, dw.rot); GROW(b_lvel, c, dw.lvel); GROW(b_avel, c, dw.avel); GROW(b_com, c, dw.com);
-            GROW(b_iloc_a, c, dw.iloc_a); GROW(b_iloc_b, c, dw.iloc_b); GROW(b_acc_l, c, dw.acc_l); GROW(b_acc_a, c, dw.acc_a); GROW(b_bmeta, c, dw.bmeta);
-            GROW(b_sb_vel, 2 * c, dw.sb_lin.p); dw.sb_ang.p = dw.sb_lin.p + 1;   // Pair2 slots (avn_device.h)
-            GROW(b_sb_delta, 2 * c, dw.sb_dp.p); dw.sb_dq.p = dw.sb_dp.p + 1;
-            GROW(b_si, 2 * c, dw.si_a.p); dw.si_b.p = dw.si_a.p + 1;
-            GROW(b_vid_l, c, dw.vid_l); GROW(b_vid_a, c, dw.vid_a);
-            GROW(b_pre_dp, c, dw.pre_dp); GROW(b_pre_dq, c, dw.pre_dq); GROW(b_sb_flags, c, dw.sb_flags);
+            GROW(b_pos, c, dw.pos, &moved); GROW(b_rot, c, dw.rot, &moved); GROW(b_lvel, c, dw.lvel, &moved); GROW(b_avel, c, dw.avel, &moved); GROW(b_com, c, dw.com, &moved);
+            GROW(b_iloc_a, c, dw.iloc_a, &moved); GROW(b_iloc_b, c, dw.iloc_b, &moved); GROW(b_acc_l, c, dw.acc_l, &moved); GROW(b_acc_a, c, dw.acc_a, &moved); GROW(b_bmeta, c, dw.bmeta, &moved);
+            GROW(b_sb_vel, 2 * c, dw.sb_lin.p, &moved); dw.sb_ang.p = dw.sb_lin.p + 1;   // Pair2 slots (avn_device.h)
+            GROW(b_sb_delta, 2 * c, dw.sb_dp.p, &moved); dw.sb_dq.p = dw.sb_dp.p + 1;
+            GROW(b_si, 2 * c, dw.si_a.p, &moved); dw.si_b.p = dw.si_a.p + 1;
+            GROW(b_vid_l, c, dw.vid_l, &moved); GROW(b_vid_a, c, dw.vid_a, &moved);
+            GROW(b_pre_dp, c, dw.pre_dp, &moved); GROW(b_pre_dq, c, dw.pre_dq, &moved); GROW(b_sb_flags, c, dw.sb_flags, &moved);
             cap_bodies = (uint32_t)c;
             if (pipe_dev) { avn_status sg = pg_bcol_grow(); if (sg != AVN_OK) return sg; }   // bodies spawned inside the closed loop: their colour masks start empty
         }
@@ -121,7 +121,6 @@
         if (!have_bodies || count != dw.n_bodies) { error = "local_accelerations_upload: count differs from the last bodies_upload"; return AVN_ERR_BAD_ARG; }
         if (despawn_needs_bodies) { error = "local_accelerations_upload: avn_despawn removed bodies: upload the remaining bodies (avn_bodies_upload) first"; return AVN_ERR_STATE; }
         slp_world_asleep = slp_world_idle = false;
-        bool moved = false;
         Vec4<T>*dl = nullptr, *da = nullptr;
         HIPCHK(hipStreamSynchronize(stream));
         GROW(b_lacc_l, (size_t)cap_bodies, dl); GROW(b_lacc_a, (size_t)cap_bodies, da);

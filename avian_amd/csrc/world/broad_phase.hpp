@@ -88,12 +88,9 @@
     avn_status grow_long_chunks(uint32_t chunks_needed) {
         HIPCHK(hipStreamSynchronize(bs));
         const size_t lcap = (size_t)chunks_needed + chunks_needed / 4 + 65536;
-        bool moved = false;
-        uint8_t* dummy_b; uint32_t* dummy_u;
-        GROW(b_long_items, lcap * sweep_long_item_bytes(), dummy_b);
-        GROW(b_long_counts, lcap, dummy_u); GROW(b_long_off, lcap, dummy_u);
-        sweep_scratch.long_items = b_long_items.p; sweep_scratch.long_counts = b_long_counts.as<uint32_t>();
-        sweep_scratch.long_off = b_long_off.as<uint32_t>(); sweep_scratch.long_cap = (uint32_t)lcap;
+        ALLOC(b_long_items.ensure(lcap * sweep_long_item_bytes()));
+        sweep_scratch.long_items = b_long_items.p; sweep_scratch.long_cap = (uint32_t)lcap;
+        GROW(b_long_counts, lcap, sweep_scratch.long_counts); GROW(b_long_off, lcap, sweep_scratch.long_off);
         return AVN_OK;
     }
     avn_status collect_finish() {
@@ -115,9 +112,7 @@
         bp_stats_note(first_unsorted, retries);
         uint32_t dropped = h_counters[0], total = h_counters[2];
         if (total) {
-            hipError_t err;
-            b_pairs.ensure((size_t)total * sizeof(avn_pair), err);
-            if (err != hipSuccess) { error = "pair buffer allocation failed"; return AVN_ERR_OOM; }
+            ALLOC(b_pairs.ensure((size_t)total * sizeof(avn_pair)));
             launch_sweep<T>(bp, n, true, sweep_scratch, b_counts.as<uint32_t>(), b_offsets.as<uint32_t>(), b_pairs.as<avn_pair>(), 0u, bs);
             launches += 2;
             HIPCHK(hipGetLastError());
@@ -130,8 +125,7 @@
             std::vector<uint64_t> nk(total);
             for (uint32_t i = 0; i < total; ++i) { uint32_t a = h_pairs[i].collider1, b = h_pairs[i].collider2; nk[i] = a < b ? ((uint64_t)a << 32) | b : ((uint64_t)b << 32) | a; }
             if (contact_keys_live) h_live_keys.insert(nk.begin(), nk.end());
-            b_pair_keys.ensure(((size_t)n_pair_keys + total) * 8, err, true, bs);
-            if (err != hipSuccess) { error = "pair key list allocation failed"; return AVN_ERR_OOM; }
+            ALLOC(b_pair_keys.ensure(((size_t)n_pair_keys + total) * 8, nullptr, true, bs));
             HIPCHK(hipMemcpyAsync(b_pair_keys.as<uint64_t>() + n_pair_keys, nk.data(), (size_t)total * 8, hipMemcpyHostToDevice, bs));
             n_pair_keys += total;
             if (bp.pair_set_cap < 2 * (n_pair_keys + 16)) { avn_status st = rebuild_pair_set(n_pair_keys + n_pair_keys / 2); if (st != AVN_OK) return st; }

@@ -6,9 +6,7 @@
         if (n == 0) { if (cap) graph_valid = false; cap = 0; return AVN_OK; }
         uint32_t need = 64;
         while (need < 2 * n + 16) need <<= 1;
-        hipError_t err;
-        buf.ensure((size_t)need * 8, err);
-        if (err != hipSuccess) { error = "hipMalloc failed"; return AVN_ERR_OOM; }
+        ALLOC(buf.ensure((size_t)need * 8));
         tab = buf.as<uint64_t>();
         cap = need;
         const uint64_t* d;
@@ -24,9 +22,7 @@
     avn_status existing_pairs_upload(const uint64_t* keys, size_t n) override {
         slp_world_asleep = slp_world_idle = false;
         if (n && !keys) return AVN_ERR_BAD_ARG;
-        hipError_t err;
-        b_pair_keys.ensure(std::max<size_t>(n, 1) * 8, err);
-        if (err != hipSuccess) { error = "hipMalloc failed"; return AVN_ERR_OOM; }
+        ALLOC(b_pair_keys.ensure(std::max<size_t>(n, 1) * 8));
         if (n) HIPCHK(hipMemcpyAsync(b_pair_keys.p, keys, n * 8, hipMemcpyHostToDevice, stream));
         n_pair_keys = (uint32_t)n;
         return rebuild_pair_set((uint32_t)n);
@@ -36,9 +32,7 @@
         if (contact_keys_live) {
             // rows have been removed since the key list was built (contact_pairs_remove): rebuild from the live keys only
             std::vector<uint64_t> keys(h_live_keys.begin(), h_live_keys.end());
-            hipError_t e2;
-            b_pair_keys.ensure(std::max<size_t>(keys.size(), 1) * 8, e2);
-            if (e2 != hipSuccess) { error = "hipMalloc failed"; return AVN_ERR_OOM; }
+            ALLOC(b_pair_keys.ensure(std::max<size_t>(keys.size(), 1) * 8));
             HIPCHK(hipStreamSynchronize(bs));
             if (!keys.empty()) HIPCHK(hipMemcpy(b_pair_keys.p, keys.data(), keys.size() * 8, hipMemcpyHostToDevice));
             n_pair_keys = (uint32_t)keys.size();
@@ -46,9 +40,7 @@
         }
         uint32_t need = 1024;
         while (need < 2 * (expect + 16)) need <<= 1;
-        hipError_t err;
-        b_pair_set.ensure((size_t)need * 8, err);
-        if (err != hipSuccess) { error = "hipMalloc failed"; return AVN_ERR_OOM; }
+        ALLOC(b_pair_set.ensure((size_t)need * 8));
         bp.pair_set = b_pair_set.as<uint64_t>();
         bp.pair_set_cap = need;
         HIPCHK(hipMemsetAsync(bp.pair_set, 0xFF, (size_t)need * 8, bs));
@@ -136,28 +128,24 @@
                 if (!known[i]) new_iv.push_back(i);  // add_new_aabb_intervals: appended at the END in upload order
             slot_entity.assign(c->entity_index, c->entity_index + C);
         }
-        bool moved = false;
         if (C > cap_colliders) {
             size_t cc = std::max<size_t>(C, cap_colliders + cap_colliders / 2);
             GROW(b_col_info, cc, bp.col_info); GROW(b_col_he, cc, bp.col_he); GROW(b_col_spec, cc, bp.col_spec); GROW(b_col_layers, cc, bp.col_layers);
             GROW(b_aabb_min, cc, bp.aabb_min); GROW(b_aabb_max, cc, bp.aabb_max); GROW(b_iv, cc, bp.iv_collider);
             GROW(b_s_minx, cc, bp.s_minx); GROW(b_s_maxx, cc, bp.s_maxx); GROW(b_s_yz, cc + sweep_pad_records(), bp.s_yz); GROW(b_s_bb, sweep_bounds_words((uint32_t)cc), bp.s_bb); bp.s_bb2 = bp.s_bb + sweep_bounds_level2_offset((uint32_t)cc); GROW(b_s_end, cc, bp.s_end);
             GROW(b_s_info, cc, bp.s_info); GROW(b_s_flags, cc, bp.s_flags);
-            Key* dummy_k; uint32_t* dummy_u;
-            GROW(b_keys_a, cc, dummy_k); GROW(b_keys_b, cc, dummy_k); GROW(b_vals_a, cc, dummy_u); GROW(b_vals_b, cc, dummy_u);
-            GROW(b_hist, (size_t)256 * radix_blocks((uint32_t)cc) + 256, dummy_u);
-            GROW(b_block_sums, std::max<size_t>(scan_block_sums_needed(256 * radix_blocks((uint32_t)cc)), scan_block_sums_needed((uint32_t)cc * sweep_count_slots())) + 16, dummy_u);
+            ALLOC(b_keys_a.ensure(cc * sizeof(Key))); ALLOC(b_keys_b.ensure(cc * sizeof(Key))); ALLOC(b_vals_a.ensure(cc * 4)); ALLOC(b_vals_b.ensure(cc * 4));
+            ALLOC(b_hist.ensure(((size_t)256 * radix_blocks((uint32_t)cc) + 256) * 4));
+            ALLOC(b_block_sums.ensure((std::max<size_t>(scan_block_sums_needed(256 * radix_blocks((uint32_t)cc)), scan_block_sums_needed((uint32_t)cc * sweep_count_slots())) + 16) * 4));
             HIPCHK(hipMemset(b_block_sums.p, 0, b_block_sums.cap));   // the one-launch scan's state: zero once, self-cleaning afterwards (avn_scan.h)
-            GROW(b_counts, cc * sweep_count_slots() + 1, dummy_u); GROW(b_offsets, cc * sweep_count_slots() + 1, dummy_u);
+            ALLOC(b_counts.ensure((cc * sweep_count_slots() + 1) * 4)); ALLOC(b_offsets.ensure((cc * sweep_count_slots() + 1) * 4));
             GROW(b_sweep_hits, sweep_hit_words((uint32_t)cc), sweep_scratch.hits);
             {   // long-interval chunks: every interval may need one slot, plus room for the chunks of scene-spanning ones
                 size_t lcap = cc + 65536;
                 if (const char* e = avn_env("AVN_SWEEP_LONG_CAP")) lcap = std::max<size_t>(8, (size_t)strtoull(e, nullptr, 10));   // (tests: force the grow-and-retry path)
-                uint8_t* dummy_b;
-                GROW(b_long_items, lcap * sweep_long_item_bytes(), dummy_b);
-                GROW(b_long_counts, lcap, dummy_u); GROW(b_long_off, lcap, dummy_u);
-                sweep_scratch.long_items = b_long_items.p; sweep_scratch.long_counts = b_long_counts.as<uint32_t>();
-                sweep_scratch.long_off = b_long_off.as<uint32_t>(); sweep_scratch.long_cap = (uint32_t)lcap;
+                ALLOC(b_long_items.ensure(lcap * sweep_long_item_bytes()));
+                sweep_scratch.long_items = b_long_items.p; sweep_scratch.long_cap = (uint32_t)lcap;
+                GROW(b_long_counts, lcap, sweep_scratch.long_counts); GROW(b_long_off, lcap, sweep_scratch.long_off);
             }
             cap_colliders = (uint32_t)cc;
         }
@@ -185,9 +173,7 @@
         h_col_body.assign(c->body, c->body + C);
         for (uint32_t i = 0; i < C; ++i) entity_slot.emplace(c->entity_index[i], i);
         {   // Friction / Restitution defaults until collider_materials_upload: DefaultFriction 0.5, DefaultRestitution 0, Average
-            hipError_t err;
-            b_col_mat.ensure(std::max<size_t>(C, 1) * sizeof(V), err);
-            if (err != hipSuccess) { error = "hipMalloc failed"; return AVN_ERR_OOM; }
+            ALLOC(b_col_mat.ensure(std::max<size_t>(C, 1) * sizeof(V)));
             ct.col_mat = b_col_mat.as<V>();
             std::vector<V> mats(C, make4<T>(T(0.5), T(0), bits_to_scalar((uint32_t)AVN_COMBINE_AVERAGE | ((uint32_t)AVN_COMBINE_AVERAGE << 8), T(0)), T(0)));
             if (C) HIPCHK(hipMemcpy(ct.col_mat, mats.data(), (size_t)C * sizeof(V), hipMemcpyHostToDevice));

@@ -14,14 +14,6 @@
     void ccd_clear() { ccd.n = 0; ccd.mode = nullptr; ccd.body_mode = nullptr; ccd_ran = false; ccd_tables_dirty = true; }
     bool ccd_closed_loop() const { return pipe_on && pipe_dev && !halo_on && !dsh_on; }
 
-    template <class U> avn_status ccd_buf(DevBuf& b, size_t count, U** field) {
-        hipError_t err;
-        b.ensure(std::max<size_t>(count, 1) * sizeof(U), err);
-        if (err != hipSuccess) { error = std::string("swept_ccd: hipMalloc: ") + hipGetErrorName(err); return AVN_ERR_OOM; }
-        *field = b.as<U>();
-        return AVN_OK;
-    }
-
     avn_status swept_ccd_upload(const avn_swept_ccd* l) override {
         if (l && l->struct_size != sizeof(avn_swept_ccd)) { error = "swept_ccd_upload: struct_size"; return AVN_ERR_BAD_ARG; }
         if (halo_on || dsh_on) { error = "swept_ccd_upload: not in a level-2 / sharded world"; return AVN_ERR_STATE; }
@@ -51,19 +43,17 @@
             lin2[i] = lt * lt; ang2[i] = at * at;
         }
         CCD<T> c = ccd;
-        avn_status st;
+        ccd_clear();   // (a failure below leaves no list: the old list's buffers may have moved)
         uint32_t *d_body = nullptr, *d_incl = nullptr; T *d_lin2 = nullptr, *d_ang2 = nullptr;
-        if ((st = ccd_buf(b_ccd_body, n, &d_body)) != AVN_OK || (st = ccd_buf(b_ccd_incl, n, &d_incl)) != AVN_OK || (st = ccd_buf(b_ccd_lin2, n, &d_lin2)) != AVN_OK ||
-            (st = ccd_buf(b_ccd_ang2, n, &d_ang2)) != AVN_OK || (st = ccd_buf(b_ccd_own, dw.n_bodies, &c.own)) != AVN_OK || (st = ccd_buf(b_ccd_ctr, 16, &c.ctr)) != AVN_OK ||
-            (st = ccd_buf(b_ccd_min_t, n, &c.min_t)) != AVN_OK || (st = ccd_buf(b_ccd_min_key, n, &c.min_key)) != AVN_OK || (st = ccd_buf(b_ccd_rec, n, &c.rec)) != AVN_OK ||
-            (st = ccd_buf(b_ccd_wkey_a, 2 * (size_t)n, &c.wkey_a)) != AVN_OK || (st = ccd_buf(b_ccd_wval_a, 2 * (size_t)n, &c.wval_a)) != AVN_OK ||
-            (st = ccd_buf(b_ccd_wkey_b, 2 * (size_t)n, &c.wkey_b)) != AVN_OK || (st = ccd_buf(b_ccd_wval_b, 2 * (size_t)n, &c.wval_b)) != AVN_OK ||
-            (st = ccd_buf(b_ccd_hist, (size_t)256 * radix_blocks(2 * n) + 256, &c.hist)) != AVN_OK ||
-            (st = ccd_buf(b_ccd_sums, scan_block_sums_needed(256 * radix_blocks(2 * n)) + 16, &c.block_sums)) != AVN_OK) { ccd_clear(); return st; }   // (the old list's buffers may have moved)
+        GROW(b_ccd_body, n, d_body); GROW(b_ccd_incl, n, d_incl); GROW(b_ccd_lin2, n, d_lin2); GROW(b_ccd_ang2, n, d_ang2);
+        GROW(b_ccd_own, dw.n_bodies, c.own); GROW(b_ccd_ctr, 16, c.ctr); GROW(b_ccd_min_t, n, c.min_t); GROW(b_ccd_min_key, n, c.min_key); GROW(b_ccd_rec, n, c.rec);
+        GROW(b_ccd_wkey_a, 2 * (size_t)n, c.wkey_a); GROW(b_ccd_wval_a, 2 * (size_t)n, c.wval_a); GROW(b_ccd_wkey_b, 2 * (size_t)n, c.wkey_b); GROW(b_ccd_wval_b, 2 * (size_t)n, c.wval_b);
+        GROW(b_ccd_hist, (size_t)256 * radix_blocks(2 * n) + 256, c.hist);
+        GROW(b_ccd_sums, scan_block_sums_needed(256 * radix_blocks(2 * n)) + 16, c.block_sums);
         // the mode tables exist only for a list with a NonLinear entry; CCD::mode == nullptr is what keeps the _nl kernels from launching
         uint32_t *d_mode = nullptr, *d_bmode = nullptr;
         if (any_nl) {
-            if ((st = ccd_buf(b_ccd_mode, n, &d_mode)) != AVN_OK || (st = ccd_buf(b_ccd_bmode, dw.n_bodies, &d_bmode)) != AVN_OK) { ccd_clear(); return st; }
+            GROW(b_ccd_mode, n, d_mode); GROW(b_ccd_bmode, dw.n_bodies, d_bmode);
             std::vector<uint32_t> bmode(dw.n_bodies, 0u);
             for (uint32_t i = 0; i < n; ++i) if (l->mode[i] == AVN_SWEEP_NON_LINEAR) bmode[l->body[i]] = 1u;
             HIPCHK(hipMemcpy(d_mode, l->mode, (size_t)n * 4, hipMemcpyHostToDevice));
@@ -83,16 +73,15 @@
 
     // between the substep loop (every island stream joined) and the restitution pass, on the world's stream
     avn_status ccd_pass() {
-        avn_status st;
         if (ccd_tables_dirty) {
-            if ((st = ccd_buf(b_ccd_entry, bp.n_colliders, &ccd.entry)) != AVN_OK) return st;
+            GROW(b_ccd_entry, std::max<size_t>(bp.n_colliders, 1), ccd.entry);
             launch_ccd_tables<T>(dw, bp, ccd, stream); launches += 4;
             ccd_tables_dirty = false;
         }
         // a row with two CCD sides yields two candidates
         if (2 * (size_t)ct.cap > ccd.cand_cap || !ccd.cand) {
             const size_t cap = std::max<size_t>(2 * (size_t)ct.cap, 64);
-            if ((st = ccd_buf(b_ccd_cand, cap, &ccd.cand)) != AVN_OK || (st = ccd_buf(b_ccd_cand_t, cap, &ccd.cand_t)) != AVN_OK) return st;
+            GROW(b_ccd_cand, cap, ccd.cand); GROW(b_ccd_cand_t, cap, ccd.cand_t);
             ccd.cand_cap = (uint32_t)std::min<size_t>(cap, 0xFFFFFFFFu);
         }
         launches += launch_ccd_pass<T>(dw, bp, ct, pg, ccd, params, pgm_next_id, stream);

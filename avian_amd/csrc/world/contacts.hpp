@@ -27,27 +27,16 @@
         size_t c = std::max<size_t>(rows, (size_t)old + old / 2);
         c = (c + 63) & ~(size_t)63;
         // grow with contents: the rows are persistent state
-        auto grow_flat = [&](DevBuf& b, size_t elem, void** field) -> avn_status {
-            hipError_t err;
-            b.ensure(c * elem, err, true, stream);
-            if (err != hipSuccess) { error = "hipMalloc failed"; return AVN_ERR_OOM; }
-            *field = b.p;
-            return AVN_OK;
-        };
-        avn_status st;
-        if ((st = grow_flat(b_ct_meta, sizeof(uint4), (void**)&ct.meta)) != AVN_OK) return st;
-        if ((st = grow_flat(b_ct_dcount, sizeof(int32_t), (void**)&ct.dcount)) != AVN_OK) return st;
-        if ((st = grow_flat(b_ct_rows, AVN_CT_ROW_V4 * sizeof(V), (void**)&ct.rows)) != AVN_OK) return st;   // one block of 16 records per row: grows like a flat array
+        GROW_KEEP(b_ct_meta, c, ct.meta);
+        GROW_KEEP(b_ct_dcount, c, ct.dcount);
+        GROW_KEEP(b_ct_rows, c * AVN_CT_ROW_V4, ct.rows);   // one block of 16 records per row: grows like a flat array
         HIPCHK(hipMemset((char*)ct.meta + (size_t)old * sizeof(uint4), 0, (c - old) * sizeof(uint4)));
         // the narrow phase's survivor list (scratch of one launch pair: nothing to keep) and its counters
         {
-            hipError_t err;
             const size_t slots = c + np_survivor_list_slack();   // 64 lists, each rounded up to whole workgroups of the first kernel (k_narrow.hip)
-            b_np_row.ensure(slots * sizeof(uint32_t), err);
-            if (err == hipSuccess) b_np_axis.ensure(3 * slots * sizeof(T), err);
-            if (err == hipSuccess && !b_np_ctr.p) { b_np_ctr.ensure(np_survivor_counter_bytes(), err); if (err == hipSuccess) HIPCHK(hipMemset(b_np_ctr.p, 0, np_survivor_counter_bytes())); }
-            if (err != hipSuccess) { error = "hipMalloc failed"; return AVN_ERR_OOM; }
-            ct.np_row = b_np_row.as<uint32_t>(); ct.np_axis = b_np_axis.as<T>(); ct.np_ctr = b_np_ctr.as<uint32_t>();
+            GROW(b_np_row, slots, ct.np_row); GROW(b_np_axis, 3 * slots, ct.np_axis);
+            if (!b_np_ctr.p) { ALLOC(b_np_ctr.ensure(np_survivor_counter_bytes())); HIPCHK(hipMemset(b_np_ctr.p, 0, np_survivor_counter_bytes())); }
+            ct.np_ctr = b_np_ctr.as<uint32_t>();
         }
         ct.cap = (uint32_t)c;
         h_ct_used.resize(c, 0); h_ct_c1.resize(c, 0); h_ct_c2.resize(c, 0); h_ct_b1.resize(c, -1); h_ct_b2.resize(c, -1);
@@ -112,11 +101,8 @@
         for (size_t i = 0; i < n; ++i)
             if (ids[i] >= ct.cap || !h_ct_used[ids[i]]) { error = "active_pairs_set: no such contact"; return AVN_ERR_STATE; }
         HIPCHK(hipStreamSynchronize(stream));
-        hipError_t err;
-        b_active.ensure(std::max<size_t>(n, 1) * 4, err);
-        if (err != hipSuccess) { error = "hipMalloc failed"; return AVN_ERR_OOM; }
-        b_changes.ensure(std::max<size_t>(n, 1) * sizeof(avn_contact_change) + 64, err);
-        if (err != hipSuccess) { error = "hipMalloc failed"; return AVN_ERR_OOM; }
+        ALLOC(b_active.ensure(std::max<size_t>(n, 1) * 4));
+        ALLOC(b_changes.ensure(std::max<size_t>(n, 1) * sizeof(avn_contact_change) + 64));
         if (n) HIPCHK(hipMemcpy(b_active.p, ids, n * 4, hipMemcpyHostToDevice));
         n_active = (uint32_t)n;
         return AVN_OK;
@@ -142,7 +128,7 @@
         // the count and the first CHANGES_PREFIX changes come back in one round trip (pinned memory, one synchronisation);
         // only a step with more changes than that pays a second copy
         const uint32_t prefix = std::min<uint32_t>(CHANGES_PREFIX, n_active);
-        HIPCHK(pin_changes.ensure(64 + (size_t)CHANGES_PREFIX * sizeof(avn_contact_change)));
+        ALLOC(pin_changes.ensure(64 + (size_t)CHANGES_PREFIX * sizeof(avn_contact_change)));
         uint32_t* h_cnt = (uint32_t*)pin_changes.p;
         avn_contact_change* h_pre = (avn_contact_change*)((char*)pin_changes.p + 64);
         HIPCHK(hipMemcpyAsync(h_cnt, d_count, 4, hipMemcpyDeviceToHost, stream));
@@ -171,10 +157,10 @@
             HIPCHK(hipStreamSynchronize(stream));
             size_t c = std::max<size_t>(M, cap_manifolds + cap_manifolds / 2);
             c = (c + 63) & ~(size_t)63;  // keep every point plane 1 KiB aligned
-            GROW(b_m_bodies, c, dw.m_bodies); GROW(b_m_n, c, dw.m_n); GROW(b_m_tv, c, dw.m_tv); GROW(b_m_meta, c, dw.m_meta);
-            GROW(b_mp_a1, 4 * c, dw.mp_a1); GROW(b_mp_a2, 4 * c, dw.mp_a2); GROW(b_mp_w, 4 * c, dw.mp_w);
-            GROW(b_c_h1, c, dw.c_h1); GROW(b_c_pa, 4 * c, dw.c_pa); GROW(b_c_pb, 4 * c, dw.c_pb); GROW(b_c_pc, 4 * c, dw.c_pc); GROW(b_c_pd, 4 * c, dw.c_pd);
-            GROW(b_c_reldom, c, dw.c_reldom);
+            GROW(b_m_bodies, c, dw.m_bodies, &moved); GROW(b_m_n, c, dw.m_n, &moved); GROW(b_m_tv, c, dw.m_tv, &moved); GROW(b_m_meta, c, dw.m_meta, &moved);
+            GROW(b_mp_a1, 4 * c, dw.mp_a1, &moved); GROW(b_mp_a2, 4 * c, dw.mp_a2, &moved); GROW(b_mp_w, 4 * c, dw.mp_w, &moved);
+            GROW(b_c_h1, c, dw.c_h1, &moved); GROW(b_c_pa, 4 * c, dw.c_pa, &moved); GROW(b_c_pb, 4 * c, dw.c_pb, &moved); GROW(b_c_pc, 4 * c, dw.c_pc, &moved); GROW(b_c_pd, 4 * c, dw.c_pd, &moved);
+            GROW(b_c_reldom, c, dw.c_reldom, &moved);
             cap_manifolds = (uint32_t)c;
             dw.m_stride = cap_manifolds;
         }
@@ -233,9 +219,9 @@
         if (dw.n_manifolds != M) graph_valid = false;
         dw.n_manifolds = M;
         set_color_offsets(offsets);
-        hipError_t err;
-        if (b_handles.ensure(std::max<size_t>(M, 1) * 4, err)) graph_valid = false;
-        if (err != hipSuccess) { error = "hipMalloc failed"; return AVN_ERR_OOM; }
+        bool moved = false;
+        ALLOC(b_handles.ensure(std::max<size_t>(M, 1) * 4, &moved));
+        if (moved) graph_valid = false;
         HIPCHK(hipMemcpy(dw.color_offsets, color_offsets, sizeof color_offsets, hipMemcpyHostToDevice));
         if (M) HIPCHK(hipMemcpy(b_handles.p, ids, (size_t)M * 4, hipMemcpyHostToDevice));
         if (!use_handles) graph_valid = false;

@@ -82,14 +82,11 @@
         const uint32_t n_rows = pgm_next_id;
         std::vector<PGEdgeRec> recs;
         if (n_rows && n_rm) {
-            hipError_t e;
-            b_dsp_a.ensure((size_t)C * 4 + 64, e);
-            if (e != hipSuccess) { error = "hipMalloc failed"; return AVN_ERR_OOM; }
+            ALLOC(b_dsp_a.ensure((size_t)C * 4 + 64));
             HIPCHK(hipMemcpy(b_dsp_a.p, rm_rank.data(), (size_t)C * 4, hipMemcpyHostToDevice));
             uint32_t cap = 4096 + 64 * n_rm;
             for (int attempt = 0; attempt < 2; ++attempt) {
-                b_dsp_b.ensure((size_t)cap * sizeof(PGEdgeRec), e);
-                if (e != hipSuccess) { error = "hipMalloc failed"; return AVN_ERR_OOM; }
+                ALLOC(b_dsp_b.ensure((size_t)cap * sizeof(PGEdgeRec)));
                 launch_pg_collect_edges<T>(pg, ct, n_rows, b_dsp_a.as<uint32_t>(), b_dsp_b.as<PGEdgeRec>(), cap, stream);
                 uint32_t found = 0;
                 HIPCHK(hipMemcpyAsync(&found, pg.ctr + PGC_COLLECT, 4, hipMemcpyDeviceToHost, stream));
@@ -204,9 +201,7 @@
             uint32_t n_new = 0;
             for (uint32_t b = 0; b < n_old; ++b) if (!gone_body[b]) new_index[b] = n_new++;
             new_index[n_old] = n_new;   // ("no body" keys of per-step scratch map to the new count)
-            hipError_t e;
-            b_dsp_a.ensure(((size_t)n_old + 1) * 4 + 64, e);
-            if (e != hipSuccess) { error = "hipMalloc failed"; return AVN_ERR_OOM; }
+            ALLOC(b_dsp_a.ensure(((size_t)n_old + 1) * 4 + 64));
             HIPCHK(hipMemcpy(b_dsp_a.p, new_index.data(), ((size_t)n_old + 1) * 4, hipMemcpyHostToDevice));
             const uint32_t* d_map = b_dsp_a.as<uint32_t>();
             launch_pg_renumber_rows<T>(pg, ct, pgm_next_id, d_map, stream);
@@ -214,8 +209,7 @@
             // per-body arrays that are STATE: the colour masks, and with sleeping on the SleepTimers and the per-body thresholds
             auto compact32 = [&](DevBuf& buf, size_t words_needed) -> avn_status {
                 if (!buf.p) return AVN_OK;
-                b_dsp_b.ensure(std::max(buf.cap, words_needed * 4), e);
-                if (e != hipSuccess) { error = "hipMalloc failed"; return AVN_ERR_OOM; }
+                ALLOC(b_dsp_b.ensure(std::max(buf.cap, words_needed * 4)));
                 HIPCHK(hipMemsetAsync(b_dsp_b.p, 0, buf.cap, stream));
                 launch_compact_u32(buf.as<uint32_t>(), b_dsp_b.as<uint32_t>(), d_map, n_old, stream);
                 HIPCHK(hipMemcpyAsync(buf.p, b_dsp_b.p, buf.cap, hipMemcpyDeviceToDevice, stream));
@@ -227,8 +221,7 @@
                 if (slp_k.body_lin && (st = compact32(b_slp_lin, n_old)) != AVN_OK) return st;
                 if (slp_k.body_ang && (st = compact32(b_slp_ang, n_old)) != AVN_OK) return st;
                 if (slp_k.body_disabled) {
-                    b_dsp_b.ensure(std::max<size_t>(b_slp_dis.cap, n_old), e);
-                    if (e != hipSuccess) { error = "hipMalloc failed"; return AVN_ERR_OOM; }
+                    ALLOC(b_dsp_b.ensure(std::max<size_t>(b_slp_dis.cap, n_old)));
                     HIPCHK(hipMemsetAsync(b_dsp_b.p, 0, b_slp_dis.cap, stream));
                     launch_compact_u8(b_slp_dis.as<uint8_t>(), b_dsp_b.as<uint8_t>(), d_map, n_old, stream);
                     HIPCHK(hipMemcpyAsync(b_slp_dis.p, b_dsp_b.p, b_slp_dis.cap, hipMemcpyDeviceToDevice, stream));

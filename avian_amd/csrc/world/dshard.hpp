@@ -48,11 +48,10 @@
         for (uint32_t r = 0; r < dsh_ranks; ++r) { dsh_max_own = std::max(dsh_max_own, dsh_off[r + 1]); dsh_off[r + 1] += dsh_off[r]; }
         dsh_list.resize(dsh_off[dsh_ranks]);
         { std::vector<uint32_t> cur(dsh_off.begin(), dsh_off.end() - 1); for (uint32_t b = 0; b < n; ++b) if (dsh_owner[b] >= 0) dsh_list[cur[dsh_owner[b]]++] = b; }
-        hipError_t err;
-        b_dsh_owner.ensure(std::max<size_t>(n, 1) * 4, err); if (err != hipSuccess) { error = "hipMalloc failed"; return AVN_ERR_OOM; }
-        b_dsh_list.ensure(std::max<size_t>(dsh_list.size(), 1) * 4, err); if (err != hipSuccess) { error = "hipMalloc failed"; return AVN_ERR_OOM; }
-        b_dsh_send.ensure(std::max<size_t>(dsh_max_own, 1) * 4 * sizeof(V), err); if (err != hipSuccess) { error = "hipMalloc failed"; return AVN_ERR_OOM; }
-        b_dsh_recv.ensure((size_t)dsh_ranks * std::max<size_t>(dsh_max_own, 1) * 4 * sizeof(V), err); if (err != hipSuccess) { error = "hipMalloc failed"; return AVN_ERR_OOM; }
+        ALLOC(b_dsh_owner.ensure(std::max<size_t>(n, 1) * 4));
+        ALLOC(b_dsh_list.ensure(std::max<size_t>(dsh_list.size(), 1) * 4));
+        ALLOC(b_dsh_send.ensure(std::max<size_t>(dsh_max_own, 1) * 4 * sizeof(V)));
+        ALLOC(b_dsh_recv.ensure((size_t)dsh_ranks * std::max<size_t>(dsh_max_own, 1) * 4 * sizeof(V)));
         HIPCHK(hipMemcpy(b_dsh_owner.p, dsh_owner.data(), (size_t)n * 4, hipMemcpyHostToDevice));
         if (!dsh_list.empty()) HIPCHK(hipMemcpy(b_dsh_list.p, dsh_list.data(), dsh_list.size() * 4, hipMemcpyHostToDevice));
         dsh_on = true; dsh_exchanges = 0;
@@ -61,15 +60,14 @@
     }
     // the local lists live next to PG::lists, same stride
     avn_status dsh_local_lists(uint32_t n_ops) {
-        hipError_t err;
-        if (b_dsh_local.ensure((size_t)AVN_GRAPH_COLOR_COUNT * pg.list_stride * 4, err)) graph_valid = false;
-        if (err != hipSuccess) { error = "hipMalloc failed"; return AVN_ERR_OOM; }
+        bool moved = false;
+        ALLOC(b_dsh_local.ensure((size_t)AVN_GRAPH_COLOR_COUNT * pg.list_stride * 4, &moved));
+        if (moved) graph_valid = false;
         // chunks of 2 048 entries: a list is at most its length before the batch + the batch's ops long (the exact lengths are read on the device)
         uint32_t longest = 0;
         for (int c = 0; c < AVN_GRAPH_COLOR_COUNT; ++c) longest = std::max(longest, pgm_len[c]);
         const uint32_t n_chunks = std::max(1u, (longest + n_ops + 2047u) / 2048u);
-        b_dsh_cnt.ensure((size_t)AVN_GRAPH_COLOR_COUNT * n_chunks * 4, err);
-        if (err != hipSuccess) { error = "hipMalloc failed"; return AVN_ERR_OOM; }
+        ALLOC(b_dsh_cnt.ensure((size_t)AVN_GRAPH_COLOR_COUNT * n_chunks * 4));
         launch_pg_local_lists(pg, ct.meta, b_dsh_owner.as<int32_t>(), dsh_rank, b_dsh_local.as<uint32_t>(), b_dsh_cnt.as<uint32_t>(), n_chunks, stream); launches += 2;
         HIPCHK(hipGetLastError());
         return AVN_OK;

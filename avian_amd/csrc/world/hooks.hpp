@@ -27,8 +27,7 @@
     bool hk_modify_active() const { return hk_modify_fn && hk_any_modify; }
     avn_status hk_counters() {
         if (b_hk_cnt.p) return AVN_OK;
-        hipError_t err;
-        b_hk_cnt.ensure(64, err); if (err != hipSuccess) { error = "hipMalloc failed"; return AVN_ERR_OOM; }
+        ALLOC(b_hk_cnt.ensure(64));
         HIPCHK(hipMemset(b_hk_cnt.p, 0, 64));
         return AVN_OK;
     }
@@ -68,9 +67,8 @@
         if (!hk_filter_active() || !total) return AVN_OK;
         avn_status st = hk_counters();
         if (st != AVN_OK) return st;
-        hipError_t err;
-        b_hk_fq.ensure((size_t)total * sizeof(avn_hook_pair), err); if (err != hipSuccess) { error = "hipMalloc failed"; return AVN_ERR_OOM; }
-        if (pin_hk.ensure(std::max<size_t>((size_t)total * sizeof(avn_hook_pair) + 64, 4096)) != hipSuccess) { error = "hipHostMalloc failed"; return AVN_ERR_OOM; }
+        ALLOC(b_hk_fq.ensure((size_t)total * sizeof(avn_hook_pair)));
+        ALLOC(pin_hk.ensure(std::max<size_t>((size_t)total * sizeof(avn_hook_pair) + 64, 4096)));
         uint32_t* d_cnt = b_hk_cnt.as<uint32_t>() + 1;
         HIPCHK(hipMemsetAsync(d_cnt, 0, 4, s));
         launch_hook_filter_collect(b_pairs.as<avn_pair>(), total, b_hk_fq.as<avn_hook_pair>(), d_cnt, s); ++launches;
@@ -86,8 +84,8 @@
         std::vector<uint32_t> rej;
         hk_ask_filter(q, n, rej);
         if (rej.empty()) return AVN_OK;
-        b_hk_rej.ensure(rej.size() * 4, err); if (err != hipSuccess) { error = "hipMalloc failed"; return AVN_ERR_OOM; }
-        b_pairs_alt.ensure((size_t)total * sizeof(avn_pair), err); if (err != hipSuccess) { error = "hipMalloc failed"; return AVN_ERR_OOM; }
+        ALLOC(b_hk_rej.ensure(rej.size() * 4));
+        ALLOC(b_pairs_alt.ensure((size_t)total * sizeof(avn_pair)));
         HIPCHK(hipMemcpyAsync(b_hk_rej.p, rej.data(), rej.size() * 4, hipMemcpyHostToDevice, s));
         launch_hook_filter_compact(b_pairs.as<avn_pair>(), b_pairs_alt.as<avn_pair>(), total, b_hk_rej.as<uint32_t>(), (uint32_t)rej.size(), s); ++launches;
         HIPCHK(hipGetLastError());
@@ -121,20 +119,19 @@
     // after the step's narrow-phase launches and the host shapes' answers (all on `s`): phase 2 collects the pending pairs' records, the hook sees them, phase 3 finishes the pairs
     avn_status hk_modify(bool dense, const StepParams<T>& np, avn_contact_change* changes, uint32_t* n_changes, uint32_t* chg, uint32_t* has, hipStream_t s) {
         if (!hk_modify_active() || !b_hk_cnt.p) return AVN_OK;
-        if (pin_hk.ensure(4096) != hipSuccess) { error = "hipHostMalloc failed"; return AVN_ERR_OOM; }
+        ALLOC(pin_hk.ensure(4096));
         uint32_t* d_cnt = b_hk_cnt.as<uint32_t>();
         HIPCHK(hipMemcpyAsync(pin_hk.p, d_cnt, 4, hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
         const uint32_t n = *(uint32_t*)pin_hk.p;
         hk_stats.last_modify_queries = n;
         if (!n) return AVN_OK;
-        hipError_t err;
         if (n > hk_rec_cap) {
             const uint32_t cap = std::max<uint32_t>(n + n / 2, 256u);
-            b_hk_rec.ensure((size_t)cap * HK_REC, err); if (err != hipSuccess) { error = "hipMalloc failed"; return AVN_ERR_OOM; }
+            ALLOC(b_hk_rec.ensure((size_t)cap * HK_REC));
             hk_rec_cap = cap;
         }
-        if (pin_hk.ensure((size_t)n * HK_REC + 64) != hipSuccess) { error = "hipHostMalloc failed"; return AVN_ERR_OOM; }
+        ALLOC(pin_hk.ensure((size_t)n * HK_REC + 64));
         HIPCHK(hipMemsetAsync(d_cnt, 0, 4, s));
         NpHostList l;
         l.hook.records = b_hk_rec.p; l.hook.count = d_cnt; l.hook.cap = hk_rec_cap; l.hook.phase = 2; l.locals = tf_any; l.capsules = cap_count != 0;
@@ -196,9 +193,8 @@
         }
         tf_any = any;
         if (!any) { bp.col_lpos = nullptr; bp.col_lrot = nullptr; return AVN_OK; }
-        hipError_t err;
-        b_col_lpos.ensure((size_t)C * sizeof(V), err); if (err != hipSuccess) { error = "hipMalloc failed"; return AVN_ERR_OOM; }
-        b_col_lrot.ensure((size_t)C * sizeof(V), err); if (err != hipSuccess) { error = "hipMalloc failed"; return AVN_ERR_OOM; }
+        ALLOC(b_col_lpos.ensure((size_t)C * sizeof(V)));
+        ALLOC(b_col_lrot.ensure((size_t)C * sizeof(V)));
         HIPCHK(hipMemcpy(b_col_lpos.p, lp.data(), (size_t)C * sizeof(V), hipMemcpyHostToDevice));
         HIPCHK(hipMemcpy(b_col_lrot.p, lr.data(), (size_t)C * sizeof(V), hipMemcpyHostToDevice));
         bp.col_lpos = b_col_lpos.as<V>(); bp.col_lrot = b_col_lrot.as<V>();

@@ -36,12 +36,11 @@
         cap_count = 0;
         for (uint32_t i = 0; i < c->count; ++i) { if (c->shape[i] == AVN_SHAPE_HOST) hs_slots.push_back(i); else if (c->shape[i] == AVN_SHAPE_CAPSULE) ++cap_count; }
         if (hs_slots.empty()) return AVN_OK;
-        hipError_t err;
         const size_t n = hs_slots.size();
-        b_hs_slots.ensure(n * 4, err); if (err != hipSuccess) { error = "hipMalloc failed"; return AVN_ERR_OOM; }
-        b_hs_aq.ensure(n * HS_AQ, err); if (err != hipSuccess) { error = "hipMalloc failed"; return AVN_ERR_OOM; }
-        b_hs_ab.ensure(n * HS_AB, err); if (err != hipSuccess) { error = "hipMalloc failed"; return AVN_ERR_OOM; }
-        b_hs_cnt.ensure(64, err); if (err != hipSuccess) { error = "hipMalloc failed"; return AVN_ERR_OOM; }
+        ALLOC(b_hs_slots.ensure(n * 4));
+        ALLOC(b_hs_aq.ensure(n * HS_AQ));
+        ALLOC(b_hs_ab.ensure(n * HS_AB));
+        ALLOC(b_hs_cnt.ensure(64));
         HIPCHK(hipMemcpy(b_hs_slots.p, hs_slots.data(), n * 4, hipMemcpyHostToDevice));
         HIPCHK(hipMemset(b_hs_cnt.p, 0, 64));
         if (const char* e = avn_env("AVN_HS_QUERY_CAP")) return hs_reserve_queries((uint32_t)std::max<long>(1, atol(e)));   // (measure build, tests: force the grow-and-retry path)
@@ -49,9 +48,8 @@
     }
     avn_status hs_reserve_queries(uint32_t cap) {
         if (cap <= hs_mq_cap) return AVN_OK;
-        hipError_t err;
-        b_hs_mq.ensure((size_t)cap * HS_MQ, err); if (err != hipSuccess) { error = "hipMalloc failed"; return AVN_ERR_OOM; }
-        b_hs_mm.ensure((size_t)cap * HS_MM, err); if (err != hipSuccess) { error = "hipMalloc failed"; return AVN_ERR_OOM; }
+        ALLOC(b_hs_mq.ensure((size_t)cap * HS_MQ));
+        ALLOC(b_hs_mm.ensure((size_t)cap * HS_MM));
         hs_mq_cap = cap;
         return AVN_OK;
     }
@@ -62,7 +60,7 @@
         avn_status st = hs_need_callbacks();
         if (st != AVN_OK) return st;
         const uint32_t n = (uint32_t)hs_slots.size();
-        if (pin_hs_aabb.ensure((size_t)n * (HS_AQ + HS_AB) + 64) != hipSuccess) { error = "hipHostMalloc failed"; return AVN_ERR_OOM; }
+        ALLOC(pin_hs_aabb.ensure((size_t)n * (HS_AQ + HS_AB) + 64));
         launch_host_aabb_queries<T>(dw, bp, params, b_hs_slots.as<uint32_t>(), n, b_hs_aq.p, s); ++launches;
         HIPCHK(hipGetLastError());
         char* hq = (char*)pin_hs_aabb.p; char* ha = hq + (size_t)n * HS_AQ;
@@ -105,7 +103,7 @@
         avn_status st = hs_need_callbacks();
         if (st != AVN_OK) return st;
         uint32_t* h_cnt = (uint32_t*)pin_hs.p;
-        if (!h_cnt) { if (pin_hs.ensure((size_t)hs_mq_cap * (HS_MQ + HS_MM) + 64) != hipSuccess) { error = "hipHostMalloc failed"; return AVN_ERR_OOM; } h_cnt = (uint32_t*)pin_hs.p; }
+        if (!h_cnt) { ALLOC(pin_hs.ensure((size_t)hs_mq_cap * (HS_MQ + HS_MM) + 64)); h_cnt = (uint32_t*)pin_hs.p; }
         HIPCHK(hipMemcpyAsync(h_cnt, b_hs_cnt.p, 4, hipMemcpyDeviceToHost, s));
         HIPCHK(hipStreamSynchronize(s));
         uint32_t n = *h_cnt;
@@ -125,7 +123,7 @@
             if (listed < n || listed > hs_mq_cap) { error = "host shapes: the retry found " + std::to_string(listed) + " pairs, the first pass " + std::to_string(n); return AVN_ERR_STATE; }
         }
         if (pin_hs.cap < (size_t)listed * (HS_MQ + HS_MM) + 64) {
-            if (pin_hs.ensure((size_t)std::max(hs_mq_cap, listed) * (HS_MQ + HS_MM) + 64) != hipSuccess) { error = "hipHostMalloc failed"; return AVN_ERR_OOM; }
+            ALLOC(pin_hs.ensure((size_t)std::max(hs_mq_cap, listed) * (HS_MQ + HS_MM) + 64));
         }
         char* hq = (char*)pin_hs.p + 64;
         HIPCHK(hipMemcpyAsync(hq, b_hs_mq.p, (size_t)listed * HS_MQ, hipMemcpyDeviceToHost, s));

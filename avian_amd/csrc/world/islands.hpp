@@ -8,12 +8,12 @@
     bool islands_fresh = false; // labels on the device describe the current constraint graph
     avn_status island_buffers() {
         const size_t n = std::max<uint32_t>(dw.n_bodies, 1);
-        hipError_t err;
-        for (DevBuf* b : {&b_isl_parent, &b_isl_label, &b_isl_awake, &b_isl_blk_label}) { b->ensure(n * 4, err); if (err != hipSuccess) { error = "hipMalloc failed"; return AVN_ERR_OOM; } }
-        b_isl_rests.ensure(n, err); if (err != hipSuccess) { error = "hipMalloc failed"; return AVN_ERR_OOM; }
-        b_isl_wakes.ensure(n, err); if (err != hipSuccess) { error = "hipMalloc failed"; return AVN_ERR_OOM; }
-        b_isl_ctr.ensure(64, err); if (err != hipSuccess) { error = "hipMalloc failed"; return AVN_ERR_OOM; }
-        const bool grown = b_sleep_timer.ensure(n * 4, err); if (err != hipSuccess) { error = "hipMalloc failed"; return AVN_ERR_OOM; }
+        for (DevBuf* b : {&b_isl_parent, &b_isl_label, &b_isl_awake, &b_isl_blk_label}) ALLOC(b->ensure(n * 4));
+        ALLOC(b_isl_rests.ensure(n));
+        ALLOC(b_isl_wakes.ensure(n));
+        ALLOC(b_isl_ctr.ensure(64));
+        bool grown = false;
+        ALLOC(b_sleep_timer.ensure(n * 4, &grown));
         if (grown || sleep_n != dw.n_bodies) { HIPCHK(hipMemsetAsync(b_sleep_timer.p, 0, n * 4, stream)); sleep_n = dw.n_bodies; }
         return AVN_OK;
     }

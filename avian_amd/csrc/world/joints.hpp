@@ -48,11 +48,11 @@
         if (J > cap_joints) {
             HIPCHK(hipStreamSynchronize(stream));
             size_t c = std::max<size_t>(J, cap_joints + cap_joints / 2);
-            GROW(b_j_bodies, c, dw.j_bodies); GROW(b_j_a1, c, dw.j_a1); GROW(b_j_a2, c, dw.j_a2); GROW(b_j_par, c, dw.j_par);
-            GROW(b_j_b1, c, dw.j_b1); GROW(b_j_b2, c, dw.j_b2); GROW(b_j_ax, c, dw.j_ax); GROW(b_j_l2, c, dw.j_l2);
-            GROW(b_j_r1, c, dw.j_r1); GROW(b_j_r2, c, dw.j_r2); GROW(b_j_cd, c, dw.j_cd); GROW(b_j_lag, c, dw.j_lag);
-            GROW(b_j_s0, c, dw.j_s0); GROW(b_j_s1, c, dw.j_s1); GROW(b_j_s2, c, dw.j_s2); GROW(b_j_s3, c, dw.j_s3);
-            GROW(b_j_rl0, c, dw.j_rl0); GROW(b_j_rl1, c, dw.j_rl1); GROW(b_j_force, c, dw.j_force); GROW(b_j_torque, c, dw.j_torque);
+            GROW(b_j_bodies, c, dw.j_bodies, &moved); GROW(b_j_a1, c, dw.j_a1, &moved); GROW(b_j_a2, c, dw.j_a2, &moved); GROW(b_j_par, c, dw.j_par, &moved);
+            GROW(b_j_b1, c, dw.j_b1, &moved); GROW(b_j_b2, c, dw.j_b2, &moved); GROW(b_j_ax, c, dw.j_ax, &moved); GROW(b_j_l2, c, dw.j_l2, &moved);
+            GROW(b_j_r1, c, dw.j_r1, &moved); GROW(b_j_r2, c, dw.j_r2, &moved); GROW(b_j_cd, c, dw.j_cd, &moved); GROW(b_j_lag, c, dw.j_lag, &moved);
+            GROW(b_j_s0, c, dw.j_s0, &moved); GROW(b_j_s1, c, dw.j_s1, &moved); GROW(b_j_s2, c, dw.j_s2, &moved); GROW(b_j_s3, c, dw.j_s3, &moved);
+            GROW(b_j_rl0, c, dw.j_rl0, &moved); GROW(b_j_rl1, c, dw.j_rl1, &moved); GROW(b_j_force, c, dw.j_force, &moved); GROW(b_j_torque, c, dw.j_torque, &moved);
             cap_joints = (uint32_t)c;
         }
         if (moved || dw.n_joints != J) graph_valid = false;
@@ -110,9 +110,7 @@
         return AVN_OK;
     }
     avn_status upload_u32(DevBuf& b, const std::vector<uint32_t>& v) {
-        hipError_t err;
-        b.ensure(std::max<size_t>(v.size(), 1) * 4, err);
-        if (err != hipSuccess) { error = "hipMalloc failed"; return AVN_ERR_OOM; }
+        ALLOC(b.ensure(std::max<size_t>(v.size(), 1) * 4));
         if (!v.empty()) HIPCHK(hipMemcpyAsync(b.p, v.data(), v.size() * 4, hipMemcpyHostToDevice, stream));
         return AVN_OK;
     }
@@ -264,9 +262,7 @@
             avn_status st;
             if ((st = upload_schedule(so)) != AVN_OK || (st = upload_schedule(da)) != AVN_OK) return st;
         }
-        hipError_t err;
-        b_side_group.ensure(std::max<size_t>(N, 1), err);
-        if (err != hipSuccess) { error = "hipMalloc failed"; return AVN_ERR_OOM; }
+        ALLOC(b_side_group.ensure(std::max<size_t>(N, 1)));
         HIPCHK(hipMemcpyAsync(b_side_group.p, side.data(), N, hipMemcpyHostToDevice, stream));
         HIPCHK(hipStreamSynchronize(stream));
         if (!stream_side) {

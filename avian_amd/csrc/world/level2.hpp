@@ -47,9 +47,7 @@
         l2_order.resize(n23);
         std::vector<uint32_t> cur(l2_off.begin(), l2_off.end() - 1);
         for (uint32_t i = 0; i < n23; ++i) l2_order[cur[l2_level_of[i]]++] = o0 + i;
-        hipError_t err;
-        b_l2_order.ensure(std::max<size_t>(n23, 1) * 4, err);
-        if (err != hipSuccess) { error = "hipMalloc failed"; return AVN_ERR_OOM; }
+        ALLOC(b_l2_order.ensure(std::max<size_t>(n23, 1) * 4));
         if (n23) HIPCHK(hipMemcpy(b_l2_order.p, l2_order.data(), (size_t)n23 * 4, hipMemcpyHostToDevice));
         l2_built_for = dw.n_manifolds;
         return AVN_OK;
@@ -87,12 +85,11 @@
         groups_dirty = true;
         drop_graph();
         if (!halo_on) return AVN_OK;
-        hipError_t err;
-        b_halo_send.ensure(std::max<size_t>(halo.send.size(), 1) * 4, err); if (err != hipSuccess) { error = "hipMalloc failed"; return AVN_ERR_OOM; }
-        b_halo_recv.ensure(std::max<size_t>(halo.recv.size(), 1) * 4, err); if (err != hipSuccess) { error = "hipMalloc failed"; return AVN_ERR_OOM; }
-        b_halo_out.ensure(std::max<size_t>(halo.send.size(), 1) * 4 * sizeof(V), err); if (err != hipSuccess) { error = "hipMalloc failed"; return AVN_ERR_OOM; }
+        ALLOC(b_halo_send.ensure(std::max<size_t>(halo.send.size(), 1) * 4));
+        ALLOC(b_halo_recv.ensure(std::max<size_t>(halo.recv.size(), 1) * 4));
+        ALLOC(b_halo_out.ensure(std::max<size_t>(halo.send.size(), 1) * 4 * sizeof(V)));
         // (record k of list entry i at 2 i: the joint slot, the LAST slot, spills into the doubled tail)
-        b_halo_in.ensure(std::max<size_t>(halo.recv.size(), 1) * 4 * sizeof(V), err); if (err != hipSuccess) { error = "hipMalloc failed"; return AVN_ERR_OOM; }
+        ALLOC(b_halo_in.ensure(std::max<size_t>(halo.recv.size(), 1) * 4 * sizeof(V)));
         if (!halo.send.empty()) HIPCHK(hipMemcpyAsync(b_halo_send.p, halo.send.data(), halo.send.size() * 4, hipMemcpyHostToDevice, stream));
         if (!halo.recv.empty()) HIPCHK(hipMemcpyAsync(b_halo_recv.p, halo.recv.data(), halo.recv.size() * 4, hipMemcpyHostToDevice, stream));
         HIPCHK(hipStreamSynchronize(stream));
@@ -210,9 +207,8 @@
         if (!bounds || cap_ranks < nr) { error = "bounds_exchange: the bounds array must hold n_ranks x 6 doubles"; return AVN_ERR_BAD_ARG; }
         avn_status st = need_bodies();
         if (st != AVN_OK) return st;
-        hipError_t err;
-        b_bounds_send.ensure(6 * sizeof(double), err); if (err != hipSuccess) { error = "hipMalloc failed"; return AVN_ERR_OOM; }
-        b_bounds_recv.ensure((size_t)nr * 6 * sizeof(double), err); if (err != hipSuccess) { error = "hipMalloc failed"; return AVN_ERR_OOM; }
+        ALLOC(b_bounds_send.ensure(6 * sizeof(double)));
+        ALLOC(b_bounds_recv.ensure((size_t)nr * 6 * sizeof(double)));
         const uint32_t nb = (bp.n_colliders + 255) / 256;
         T* part;
         StagePlan plan(*this);

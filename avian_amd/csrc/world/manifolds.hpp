@@ -77,10 +77,9 @@
         if (M == 0) { incidence_dirty = false; island_mode = false; islands_dirty = false; return AVN_OK; }
         if (h_body_has_sb.size() != N || h_m_body1.size() != M) { error = "incidence: bodies / manifolds out of sync"; return AVN_ERR_STATE; }
         HIPCHK(hipStreamSynchronize(stream));
-        hipError_t err;
         {   // slot table storage: 23 colour planes of cap_bodies entries
-            bool moved = b_inc_slot.ensure((size_t)AVN_COLOR_OVERFLOW_INDEX * cap_bodies * sizeof(uint32_t), err);
-            if (err != hipSuccess) { error = "hipMalloc failed"; return AVN_ERR_OOM; }
+            bool moved = false;
+            ALLOC(b_inc_slot.ensure((size_t)AVN_COLOR_OVERFLOW_INDEX * cap_bodies * sizeof(uint32_t), &moved));
             if (moved || dw.inc_stride != cap_bodies) graph_valid = false;
             dw.inc_slot = b_inc_slot.as<uint32_t>();
             dw.inc_stride = cap_bodies;
@@ -101,10 +100,9 @@
             if (h_body_has_sb[a]) ent[cursor[a]++] = m;
             if (h_body_has_sb[b]) ent[cursor[b]++] = m | 0x80000000u;
         }
-        bool moved = b_inc_off.ensure(((size_t)N + 1) * 4, err);
-        if (err != hipSuccess) { error = "hipMalloc failed"; return AVN_ERR_OOM; }
-        moved |= b_inc_ent.ensure(std::max<size_t>(ent.size(), 1) * sizeof(uint32_t), err);
-        if (err != hipSuccess) { error = "hipMalloc failed"; return AVN_ERR_OOM; }
+        bool moved = false;
+        ALLOC(b_inc_off.ensure(((size_t)N + 1) * 4, &moved));
+        ALLOC(b_inc_ent.ensure(std::max<size_t>(ent.size(), 1) * sizeof(uint32_t), &moved));
         if (moved || !dw.inc_off) graph_valid = false;
         dw.inc_off = b_inc_off.as<uint32_t>();
         dw.inc_ent = b_inc_ent.as<uint32_t>();
@@ -297,14 +295,12 @@
         // was idle when the previous block went up (rebuild_incidence / the narrow-phase read-back synchronise it every step)
         const size_t w0 = body_off.size(), w1 = bodies.size(), w2 = col_off.size(), w3 = ent.size();
         const size_t o1 = (w0 + 63) & ~(size_t)63, o2 = o1 + ((w1 + 63) & ~(size_t)63), o3 = o2 + ((w2 + 63) & ~(size_t)63), words = o3 + w3;
-        if (pin_islands.ensure(words * 4) != hipSuccess) { error = "hipHostMalloc failed"; return AVN_ERR_OOM; }
+        ALLOC(pin_islands.ensure(words * 4));
         uint32_t* h = (uint32_t*)pin_islands.p;
         std::memcpy(h, body_off.data(), w0 * 4); std::memcpy(h + o1, bodies.data(), w1 * 4);
         std::memcpy(h + o2, col_off.data(), w2 * 4); std::memcpy(h + o3, ent.data(), w3 * 4);
         if (words * 4 > b_isl_bodies.cap) HIPCHK(hipStreamSynchronize(stream));   // growing frees the old block: nothing may still read it
-        hipError_t err;
-        b_isl_bodies.ensure(words * 4, err);
-        if (err != hipSuccess) { error = "hipMalloc failed"; return AVN_ERR_OOM; }
+        ALLOC(b_isl_bodies.ensure(words * 4));
         HIPCHK(hipMemcpyAsync(b_isl_bodies.p, h, words * 4, hipMemcpyHostToDevice, stream));
         uint32_t* d = b_isl_bodies.as<uint32_t>();
         islands = IslandBlocks{d, d + o1, d + o2, (const uint2*)(d + o3), n_blocks, max_bodies, lm_pad, cache_records ? 1u : 0u};

@@ -2,46 +2,36 @@
 // closed loop with the bookkeeping on the device (k_graph.hip).
 
     // ---- closed loop, bookkeeping on the device -------------------------------------------------------------------------------
-    template <class U> avn_status pg_buf(DevBuf& b, size_t count, U** field, bool keep = false) {
-        hipError_t err;
-        b.ensure(std::max<size_t>(count, 1) * sizeof(U), err, keep, stream);
-        if (err != hipSuccess) { error = "hipMalloc failed"; return AVN_ERR_OOM; }
-        *field = b.as<U>();
-        return AVN_OK;
-    }
     // per-row arrays follow CT::cap (contents kept: they are persistent state); per-op scratch is sized for one op per row
     avn_status pg_ensure_rows(uint32_t rows) {
         if (rows <= pg_rows) return AVN_OK;
         HIPCHK(hipStreamSynchronize(stream));
         const uint32_t old = pg_rows;
-        avn_status st;
-#define PGB(buf, cnt, field, keep) do { if ((st = pg_buf(buf, cnt, &(field), keep)) != AVN_OK) return st; } while (0)
-        PGB(b_pg_bodies, rows, pg.bodies, true); PGB(b_pg_color, rows, pg.color, true); PGB(b_pg_lpos, rows, pg.lpos, true);
-        PGB(b_pg_free_a, rows, pg.free_ids, true); PGB(b_pg_free_b, rows, pg.free_alt, true);
-        PGB(b_pg_seq, rows, pg.seq, true);
+        // (rows >= 1 here: no array below is empty)
+        GROW_KEEP(b_pg_bodies, rows, pg.bodies); GROW_KEEP(b_pg_color, rows, pg.color); GROW_KEEP(b_pg_lpos, rows, pg.lpos);
+        GROW_KEEP(b_pg_free_a, rows, pg.free_ids); GROW_KEEP(b_pg_free_b, rows, pg.free_alt);
+        GROW_KEEP(b_pg_seq, rows, pg.seq);
         {   // colour lists: [24][stride] re-laid out for the new stride
             uint32_t* nl = nullptr;
-            if (hipMalloc((void**)&nl, (size_t)AVN_GRAPH_COLOR_COUNT * rows * 4) != hipSuccess) { error = "hipMalloc failed"; return AVN_ERR_OOM; }
+            ALLOC(hipMalloc((void**)&nl, (size_t)AVN_GRAPH_COLOR_COUNT * rows * 4));
             for (int c = 0; c < AVN_GRAPH_COLOR_COUNT && old; ++c)
                 if (pgm_len[c]) HIPCHK(hipMemcpy(nl + (size_t)c * rows, pg.lists + (size_t)c * old, (size_t)pgm_len[c] * 4, hipMemcpyDeviceToDevice));
             if (b_pg_lists.p) (void)hipFree(b_pg_lists.p);
             b_pg_lists.p = nl; b_pg_lists.cap = (size_t)AVN_GRAPH_COLOR_COUNT * rows * 4;
             pg.lists = nl; pg.list_stride = rows;
         }
-        PGB(b_pg_chg, rows, pg.chg, true); PGB(b_pg_has, rows, pg.has, true);   // (kept: the overlapped narrow phase has written the old rows' changes when a step's new pairs grow the table)
-        PGB(b_pg_off, rows + 1, pg.off, false);
-        PGB(b_pg_op_cid, rows, pg.op_cid, false); PGB(b_pg_op_chg, rows, pg.op_chg, false); PGB(b_pg_op_info, rows, pg.op_info, false); PGB(b_pg_op_bodies, rows, pg.op_bodies, false);
-        PGB(b_pg_ekey_a, 2 * (size_t)rows, pg.ekey_a, false); PGB(b_pg_eval_a, 2 * (size_t)rows, pg.eval_a, false);
-        PGB(b_pg_ekey_b, 2 * (size_t)rows, pg.ekey_b, false); PGB(b_pg_eval_b, 2 * (size_t)rows, pg.eval_b, false);
-        PGB(b_pg_epos, 2 * (size_t)rows, pg.epos, false); PGB(b_pg_popbefore, 2 * (size_t)rows, pg.popbefore, false);
-        PGB(b_pg_prevpush, 2 * (size_t)rows, pg.prevpush, false); PGB(b_pg_est, 2 * (size_t)rows, pg.est, false);
-        PGB(b_pg_tile_agg, 5 * (size_t)pg_scan_tiles(2 * rows) + 8, pg.tile_agg, false);
-        PGB(b_pg_ckey_a, rows, pg.ckey_a, false); PGB(b_pg_cval_a, rows, pg.cval_a, false); PGB(b_pg_ckey_b, rows, pg.ckey_b, false); PGB(b_pg_cval_b, rows, pg.cval_b, false);
-        PGB(b_pg_rem_flag, rows, pg.rem_flag, false); PGB(b_pg_rem_off, rows + 1, pg.rem_off, false); PGB(b_pg_rem_ids, rows, pg.rem_ids, false);
-        uint32_t* dummy;
-        PGB(b_pg_hist, (size_t)256 * radix_blocks(2 * rows) + 256, dummy, false);
-        PGB(b_pg_sums, std::max<size_t>(scan_block_sums_needed(256 * radix_blocks(2 * rows)), scan_block_sums_needed(2 * rows)) + 16, dummy, false);
-#undef PGB
+        GROW_KEEP(b_pg_chg, rows, pg.chg); GROW_KEEP(b_pg_has, rows, pg.has);   // (kept: the overlapped narrow phase has written the old rows' changes when a step's new pairs grow the table)
+        GROW(b_pg_off, rows + 1, pg.off);
+        GROW(b_pg_op_cid, rows, pg.op_cid); GROW(b_pg_op_chg, rows, pg.op_chg); GROW(b_pg_op_info, rows, pg.op_info); GROW(b_pg_op_bodies, rows, pg.op_bodies);
+        GROW(b_pg_ekey_a, 2 * (size_t)rows, pg.ekey_a); GROW(b_pg_eval_a, 2 * (size_t)rows, pg.eval_a);
+        GROW(b_pg_ekey_b, 2 * (size_t)rows, pg.ekey_b); GROW(b_pg_eval_b, 2 * (size_t)rows, pg.eval_b);
+        GROW(b_pg_epos, 2 * (size_t)rows, pg.epos); GROW(b_pg_popbefore, 2 * (size_t)rows, pg.popbefore);
+        GROW(b_pg_prevpush, 2 * (size_t)rows, pg.prevpush); GROW(b_pg_est, 2 * (size_t)rows, pg.est);
+        GROW(b_pg_tile_agg, 5 * (size_t)pg_scan_tiles(2 * rows) + 8, pg.tile_agg);
+        GROW(b_pg_ckey_a, rows, pg.ckey_a); GROW(b_pg_cval_a, rows, pg.cval_a); GROW(b_pg_ckey_b, rows, pg.ckey_b); GROW(b_pg_cval_b, rows, pg.cval_b);
+        GROW(b_pg_rem_flag, rows, pg.rem_flag); GROW(b_pg_rem_off, rows + 1, pg.rem_off); GROW(b_pg_rem_ids, rows, pg.rem_ids);
+        ALLOC(b_pg_hist.ensure(((size_t)256 * radix_blocks(2 * rows) + 256) * 4));
+        ALLOC(b_pg_sums.ensure((std::max<size_t>(scan_block_sums_needed(256 * radix_blocks(2 * rows)), scan_block_sums_needed(2 * rows)) + 16) * 4));
         HIPCHK(hipMemset(b_pg_sums.p, 0, b_pg_sums.cap));   // the one-launch scan's state: zero once, self-cleaning afterwards (avn_scan.h)
         pg.rows = rows; pg_rows = rows;
         graph_valid = false;
@@ -53,8 +43,7 @@
         const uint32_t want = cap_bodies + 1;
         if (want <= pg_bcol_words) return AVN_OK;
         HIPCHK(hipStreamSynchronize(stream));
-        avn_status st = pg_buf(b_pg_bcol, want, &pg.bcol, true);
-        if (st != AVN_OK) return st;
+        GROW_KEEP(b_pg_bcol, want, pg.bcol);
         HIPCHK(hipMemsetAsync(pg.bcol + pg_bcol_words, 0, (size_t)(want - pg_bcol_words) * 4, stream));
         pg_bcol_words = want;
         graph_valid = false;
@@ -69,8 +58,7 @@
         for (uint32_t i = 0; i < slot_entity.size(); ++i) e2s[slot_entity[i]] = i;
         HIPCHK(hipStreamSynchronize(stream)); HIPCHK(hipStreamSynchronize(stream_bp));
         uint32_t* d;
-        avn_status st = pg_buf(b_pg_ent2slot, e2s.size(), &d);
-        if (st != AVN_OK) return st;
+        GROW(b_pg_ent2slot, e2s.size(), d);
         HIPCHK(hipMemcpy(d, e2s.data(), e2s.size() * 4, hipMemcpyHostToDevice));
         pg.ent2slot = d;
         return AVN_OK;
@@ -80,9 +68,7 @@
         HIPCHK(hipStreamSynchronize(stream));
         HIPCHK(hipStreamSynchronize(stream_bp));
         avn_status st;
-        hipError_t err;
-        b_pg_ctr.ensure(PGC_WORDS * 4, err);
-        if (err != hipSuccess) { error = "hipMalloc failed"; return AVN_ERR_OOM; }
+        ALLOC(b_pg_ctr.ensure(PGC_WORDS * 4));
         pg.ctr = b_pg_ctr.as<uint32_t>();
         HIPCHK(hipMemset(pg.ctr, 0, PGC_WORDS * 4));
         pg_bcol_words = 0;
@@ -110,7 +96,7 @@
         HIPCHK(hipMemcpy(dw.color_offsets, zero, sizeof zero, hipMemcpyHostToDevice));
         use_handles = true; any_restitution = materials_restitution || hk_restitution;
         incidence_dirty = true; graph_valid = false;
-        if (pin_ctr.ensure(4096) != hipSuccess) { error = "hipHostMalloc failed"; return AVN_ERR_OOM; }
+        ALLOC(pin_ctr.ensure(4096));
         return AVN_OK;
     }
     static uint32_t bits_for(uint32_t max_value) { uint32_t b = 1; while (b < 32 && (max_value >> b)) ++b; return b; }
@@ -121,9 +107,7 @@
         uint32_t need = 1024;
         while ((uint64_t)need < 4 * ((uint64_t)n_pair_keys + pgm_live + incoming + 16)) need <<= 1;
         HIPCHK(hipStreamSynchronize(bs));
-        hipError_t err;
-        b_pair_set.ensure((size_t)need * 8, err);
-        if (err != hipSuccess) { error = "hipMalloc failed"; return AVN_ERR_OOM; }
+        ALLOC(b_pair_set.ensure((size_t)need * 8));
         bp.pair_set = b_pair_set.as<uint64_t>();
         bp.pair_set_cap = need;
         HIPCHK(hipMemsetAsync(bp.pair_set, 0xFF, (size_t)need * 8, bs));
@@ -236,12 +220,10 @@
     }
     avn_status pg_sort_ensure() {   // [23][stride] words, all EMPTY between batches (k_pg_sort_emit cleans what k_pg_build_handles wrote)
         const size_t stride = pg_sort_stride(dw.n_bodies);
-        hipError_t err;
-        const bool fresh = b_pg_sort_tab.ensure((size_t)AVN_COLOR_OVERFLOW_INDEX * stride * 4, err);
-        if (err != hipSuccess) { error = "hipMalloc failed"; return AVN_ERR_OOM; }
+        bool fresh = false;
+        ALLOC(b_pg_sort_tab.ensure((size_t)AVN_COLOR_OVERFLOW_INDEX * stride * 4, &fresh));
         if (fresh) HIPCHK(hipMemsetAsync(b_pg_sort_tab.p, 0xFF, b_pg_sort_tab.cap, stream));
-        b_pg_sort_cnt.ensure((size_t)AVN_COLOR_OVERFLOW_INDEX * (stride / 2048u) * 4 + 64, err);
-        if (err != hipSuccess) { error = "hipMalloc failed"; return AVN_ERR_OOM; }
+        ALLOC(b_pg_sort_cnt.ensure((size_t)AVN_COLOR_OVERFLOW_INDEX * (stride / 2048u) * 4 + 64));
         return AVN_OK;
     }
     avn_status pg_apply_ops(uint32_t n_ops, uint32_t n_rem, uint32_t n_rows, const uint32_t* list_cids, const uint32_t* list_kinds, double& host_ms) {
@@ -255,7 +237,7 @@
             //  loop's ops were classified by k_pg_scan_classify, the scan that counted them)
             if (list_cids) launch_pg_ops_from_list<T>(pg, ct, list_cids, list_kinds, n_ops, dw.n_bodies, stream);
             if (slp_on && !list_cids) {   // the island manager reads the loop's changes: (contact id, packed change) per op, in ascending id
-                if (pin_slp_ops.ensure((size_t)n_ops * 8 + 64) != hipSuccess) { error = "hipHostMalloc failed"; return AVN_ERR_OOM; }
+                ALLOC(pin_slp_ops.ensure((size_t)n_ops * 8 + 64));
                 HIPCHK(hipMemcpyAsync(pin_slp_ops.p, pg.op_cid, (size_t)n_ops * 4, hipMemcpyDeviceToHost, stream));
                 HIPCHK(hipMemcpyAsync((uint32_t*)pin_slp_ops.p + n_ops, pg.op_chg, (size_t)n_ops * 4, hipMemcpyDeviceToHost, stream));
             }
@@ -294,9 +276,9 @@
             if (early) {
                 M_ub = dw.n_manifolds + n_ops;
                 if ((st = ensure_manifold_capacity(M_ub)) != AVN_OK) return st;
-                hipError_t e2;
-                if (b_handles.ensure(std::max<size_t>(M_ub, 1) * 4, e2)) graph_valid = false;
-                if (e2 != hipSuccess) { error = "hipMalloc failed"; return AVN_ERR_OOM; }
+                bool moved = false;
+                ALLOC(b_handles.ensure(std::max<size_t>(M_ub, 1) * 4, &moved));
+                if (moved) graph_valid = false;
                 const bool sorted_ub = handle_sort && M_ub >= 4096u && (uint64_t)AVN_COLOR_OVERFLOW_INDEX * dw.n_bodies <= 32ull * M_ub;
                 if (sorted_ub && (st = pg_sort_ensure()) != AVN_OK) return st;
                 launch_pg_build_handles(dsh_on ? dsh_pg() : pg, b_handles.as<uint32_t>(), dw.color_offsets, M_ub, ct.meta, sorted_ub ? b_pg_sort_tab.as<uint32_t>() : nullptr, b_pg_sort_cnt.as<uint32_t>(), dw.n_bodies, stream, dsh_on ? (uint32_t)PGC_LLEN : (uint32_t)PGC_LEN);
@@ -350,9 +332,9 @@
             if ((dw.n_manifolds == 0) != (M == 0)) graph_valid = false;   // (no captured kernel reads DW::n_manifolds; only "any manifolds at all" shapes the substep)
             dw.n_manifolds = M;
             set_color_offsets(offs);
-            hipError_t err;
-            if (b_handles.ensure(std::max<size_t>(M, 1) * 4, err)) graph_valid = false;
-            if (err != hipSuccess) { error = "hipMalloc failed"; return AVN_ERR_OOM; }
+            bool moved = false;
+            ALLOC(b_handles.ensure(std::max<size_t>(M, 1) * 4, &moved));
+            if (moved) graph_valid = false;
             // the solver's order inside colours 0..22: by key body (k_graph.hip, round 5) when the manifolds are dense enough in the bodies for the
             // 23 x n_bodies table walk to be cheaper than what the locality saves (a sparse scene's colour launches are tiny either way)
             if (!early) {
@@ -447,9 +429,7 @@
             const uint32_t dropped = h_counters[0];
             total = h_counters[2];
             if (total) {
-                hipError_t err;
-                b_pairs.ensure((size_t)total * sizeof(avn_pair), err);
-                if (err != hipSuccess) { error = "pair buffer allocation failed"; return fail(AVN_ERR_OOM); }
+                if (b_pairs.ensure((size_t)total * sizeof(avn_pair)) != hipSuccess) { error = "pair buffer allocation failed"; return fail(AVN_ERR_OOM); }
                 launch_sweep<T>(bp, collect_n, true, sweep_scratch, b_counts.as<uint32_t>(), b_offsets.as<uint32_t>(), b_pairs.as<avn_pair>(), 0u, bs);
                 launches += 2;
                 if ((st = hk_filter_device(total, bs)) != AVN_OK) return fail(st);   // CollisionHooks::filter_pairs: the pairs the hook rejects never get an id (world/hooks.hpp)
@@ -460,14 +440,12 @@
                 if (np_overlap) HIPCHK(hipStreamWaitEvent(stream_bp, ev_np_old, 0));               // nothing below may touch a row while that launch runs
                 if ((st = pg_pair_set_reserve(pgm_next_id, total)) != AVN_OK) return fail(st);
                 {   // the ids of the new pairs in emission order: the island manager's edge lists (sleeping on), avn_pipeline_new_pair_ids_get (a host's events)
-                    hipError_t e2;
-                    b_pg_new_ids.ensure((size_t)total * 4, e2);
-                    if (e2 != hipSuccess) { error = "hipMalloc failed"; return fail(AVN_ERR_OOM); }
+                    if (b_pg_new_ids.ensure((size_t)total * 4) != hipSuccess) { error = "new pair id list allocation failed"; return fail(AVN_ERR_OOM); }
                     pg.new_ids = b_pg_new_ids.as<uint32_t>();
                 }
                 launch_pg_add_pairs<T>(pg, ct, b_pairs.as<avn_pair>(), total, bp.pair_set, bp.pair_set_cap, bs);   // ids, rows, PairKeys (add_edge_and_key_with), IdPool counters
                 if (slp_on) {
-                    if (pin_slp_pairs.ensure((size_t)total * (sizeof(avn_pair) + 4) + 64) != hipSuccess) { error = "hipHostMalloc failed"; return fail(AVN_ERR_OOM); }
+                    if (pin_slp_pairs.ensure((size_t)total * (sizeof(avn_pair) + 4) + 64) != hipSuccess) { error = "pinned pair list allocation failed"; return fail(AVN_ERR_OOM); }
                     HIPCHK(hipMemcpyAsync(pin_slp_pairs.p, b_pairs.p, (size_t)total * sizeof(avn_pair), hipMemcpyDeviceToHost, bs));
                     HIPCHK(hipMemcpyAsync((char*)pin_slp_pairs.p + (size_t)total * sizeof(avn_pair), pg.new_ids, (size_t)total * 4, hipMemcpyDeviceToHost, bs));
                 }
@@ -570,28 +548,22 @@
         incidence_dirty = false;
         island_mode = false; islands_dirty = false;
         if (M == 0) return AVN_OK;
-        hipError_t err;
-        bool moved = b_inc_slot.ensure((size_t)AVN_COLOR_OVERFLOW_INDEX * cap_bodies * sizeof(uint32_t), err);
-        if (err != hipSuccess) { error = "hipMalloc failed"; return AVN_ERR_OOM; }
-        if (moved || dw.inc_stride != cap_bodies) { graph_valid = false; slot_clear_pending = false; }   // (a new table: the early clear hit the old one)
+        bool slot_moved = false, moved = false;
+        ALLOC(b_inc_slot.ensure((size_t)AVN_COLOR_OVERFLOW_INDEX * cap_bodies * sizeof(uint32_t), &slot_moved));
+        if (slot_moved || dw.inc_stride != cap_bodies) { graph_valid = false; slot_clear_pending = false; }   // (a new table: the early clear hit the old one)
         dw.inc_slot = b_inc_slot.as<uint32_t>(); dw.inc_stride = cap_bodies;
         slots_dirty = true;
         const uint32_t o0 = color_offsets[AVN_COLOR_OVERFLOW_INDEX], n23 = color_offsets[AVN_COLOR_OVERFLOW_INDEX + 1] - o0;
-        moved = b_inc_off.ensure(((size_t)N + 2) * 4, err);
-        if (err != hipSuccess) { error = "hipMalloc failed"; return AVN_ERR_OOM; }
+        ALLOC(b_inc_off.ensure(((size_t)N + 2) * 4, &moved));
         if (n23 > pg_ovf_cap) {
             HIPCHK(hipStreamSynchronize(stream));
             const size_t c = std::max<size_t>(2 * (size_t)n23 + 1024, (size_t)pg_ovf_cap * 3);
-            for (DevBuf* b : {&b_inc_ent, &b_ovf_keys_a, &b_ovf_vals_a, &b_ovf_keys_b, &b_ovf_vals_b, &b_ovf_rank}) {
-                b->ensure(c * 4, err);
-                if (err != hipSuccess) { error = "hipMalloc failed"; return AVN_ERR_OOM; }
-            }
+            for (DevBuf* b : {&b_inc_ent, &b_ovf_keys_a, &b_ovf_vals_a, &b_ovf_keys_b, &b_ovf_vals_b, &b_ovf_rank}) ALLOC(b->ensure(c * 4));
             pg_ovf_cap = (uint32_t)(c / 2);
             moved = true;
         }
-        if (b_inc_ent.cap == 0) { b_inc_ent.ensure(1024, err); b_ovf_rank.ensure(1024, err); moved = true; }
-        if (b_ovf_ticket.ensure(((size_t)cap_bodies + 1) * 4, err)) moved = true;
-        if (err != hipSuccess) { error = "hipMalloc failed"; return AVN_ERR_OOM; }
+        if (b_inc_ent.cap == 0) { ALLOC(b_inc_ent.ensure(1024)); ALLOC(b_ovf_rank.ensure(1024)); moved = true; }
+        ALLOC(b_ovf_ticket.ensure(((size_t)cap_bodies + 1) * 4, &moved));
         if (moved || !dw.inc_off) graph_valid = false;
         dw.inc_off = b_inc_off.as<uint32_t>(); dw.inc_ent = b_inc_ent.as<uint32_t>();
         islands_dirty = island_candidate(M) && dw.n_joints == 0;

@@ -54,13 +54,11 @@
         adj_pending = false;
         const uint32_t N = dw.n_bodies, n_slots = (uint32_t)slot_entity.size(), n = 2u * dw.n_manifolds;
         if (!slp_adj_enabled || !N || pipe_stats.pairs_added >= (1ull << 32) || n_slots >= (1u << 30) || dw.n_manifolds >= (1u << 30)) return AVN_OK;   // (the manager's own edge lists serve)
-        hipError_t err = hipSuccess;
         if (adj_rank_epoch != isl.collider_epoch() || adj_rank_slots != n_slots) {
             adj_rank_host.resize(std::max<size_t>(n_slots, 1));
             isl.collider_ranks(slot_entity.data(), n_slots, adj_rank_host.data());
             HIPCHK(hipStreamSynchronize(stream_bp));
-            b_adj_rank.ensure(adj_rank_host.size() * 4, err);
-            if (err != hipSuccess) { error = "hipMalloc failed (collider ranks)"; return AVN_ERR_OOM; }
+            ALLOC(b_adj_rank.ensure(adj_rank_host.size() * 4));
             HIPCHK(hipMemcpy(b_adj_rank.p, adj_rank_host.data(), (size_t)n_slots * 4, hipMemcpyHostToDevice));
             adj_rank_epoch = isl.collider_epoch(); adj_rank_slots = n_slots;
         }
@@ -68,21 +66,19 @@
         if (b_adj_ka.cap < cap * 4) {
             HIPCHK(hipStreamSynchronize(stream_bp));
             const size_t c = cap + cap / 2;
-            for (DevBuf* b : {&b_adj_key2, &b_adj_other, &b_adj_body, &b_adj_ka, &b_adj_va, &b_adj_kb, &b_adj_vb, &b_adj_out}) { b->ensure(c * 4, err); if (err != hipSuccess) { error = "hipMalloc failed (island adjacency)"; return AVN_ERR_OOM; } }
-            b_adj_hist.ensure(((size_t)256 * radix_blocks((uint32_t)c) + 256) * 4, err);
-            if (err != hipSuccess) { error = "hipMalloc failed (island adjacency)"; return AVN_ERR_OOM; }
-            b_adj_sums.ensure((std::max<size_t>(scan_block_sums_needed(256 * radix_blocks((uint32_t)c)), scan_block_sums_needed((uint32_t)c)) + 16) * 4, err);
-            if (err != hipSuccess) { error = "hipMalloc failed (island adjacency)"; return AVN_ERR_OOM; }
+            for (DevBuf* b : {&b_adj_key2, &b_adj_other, &b_adj_body, &b_adj_ka, &b_adj_va, &b_adj_kb, &b_adj_vb, &b_adj_out}) ALLOC(b->ensure(c * 4));
+            ALLOC(b_adj_hist.ensure(((size_t)256 * radix_blocks((uint32_t)c) + 256) * 4));
+            ALLOC(b_adj_sums.ensure((std::max<size_t>(scan_block_sums_needed(256 * radix_blocks((uint32_t)c)), scan_block_sums_needed((uint32_t)c)) + 16) * 4));
             HIPCHK(hipMemset(b_adj_sums.p, 0, b_adj_sums.cap));   // (the one-launch scan's state: zero once, self-cleaning afterwards)
         }
-        b_adj_off.ensure(((size_t)N + 2) * 4, err); if (err != hipSuccess) { error = "hipMalloc failed (island adjacency)"; return AVN_ERR_OOM; }
-        b_adj_parent.ensure((size_t)N * 4, err); if (err != hipSuccess) { error = "hipMalloc failed (island adjacency)"; return AVN_ERR_OOM; }
-        b_adj_label.ensure((size_t)N * 4, err); if (err != hipSuccess) { error = "hipMalloc failed (island adjacency)"; return AVN_ERR_OOM; }
-        b_adj_ccctr.ensure(64, err); if (err != hipSuccess) { error = "hipMalloc failed (island adjacency)"; return AVN_ERR_OOM; }
+        ALLOC(b_adj_off.ensure(((size_t)N + 2) * 4));
+        ALLOC(b_adj_parent.ensure((size_t)N * 4));
+        ALLOC(b_adj_label.ensure((size_t)N * 4));
+        ALLOC(b_adj_ccctr.ensure(64));
         if (pin_adj2[adj_flip].cap < ((size_t)2 * N + 2 + n) * 4 + 64) {
             avn_status js = isl.split_join();   // (growing frees the old block)
             if (js != AVN_OK) return slp_fail(js);
-            if (pin_adj2[adj_flip].ensure(((size_t)2 * N + 2 + n) * 4 + 64) != hipSuccess) { error = "hipHostMalloc failed"; return AVN_ERR_OOM; }
+            ALLOC(pin_adj2[adj_flip].ensure(((size_t)2 * N + 2 + n) * 4 + 64));
         }
         adj_used = adj_flip;
         if (!ev_adj) { HIPCHK(hipEventCreateWithFlags(&ev_adj, hipEventDisableTiming)); HIPCHK(hipEventCreateWithFlags(&ev_adj_go, hipEventDisableTiming | EV_FLAGS)); }
@@ -138,16 +134,12 @@
         if (n <= slp_bodies) return AVN_OK;
         HIPCHK(hipStreamSynchronize(stream));
         const uint32_t old = slp_bodies;
-        hipError_t e;
-        b_slp_timer.ensure((size_t)n * 4, e, true, stream);
-        if (e != hipSuccess) { error = "hipMalloc failed (sleep timers)"; return AVN_ERR_OOM; }
-        b_slp_flags.ensure((size_t)n, e);
-        if (e != hipSuccess) { error = "hipMalloc failed (sleep flags)"; return AVN_ERR_OOM; }
+        ALLOC(b_slp_timer.ensure((size_t)n * 4, nullptr, true, stream));
+        ALLOC(b_slp_flags.ensure((size_t)n));
         HIPCHK(hipMemsetAsync((float*)b_slp_timer.p + old, 0, (size_t)(n - old) * 4, stream));
         auto grow_f = [&](DevBuf& b, const float*& field, float fill) -> avn_status {
             if (!field) return AVN_OK;
-            b.ensure((size_t)n * 4, e, true, stream);
-            if (e != hipSuccess) { error = "hipMalloc failed (per-body sleep thresholds)"; return AVN_ERR_OOM; }
+            ALLOC(b.ensure((size_t)n * 4, nullptr, true, stream));
             std::vector<float> tail(n - old, fill);
             HIPCHK(hipMemcpy((float*)b.p + old, tail.data(), tail.size() * 4, hipMemcpyHostToDevice));
             field = (const float*)b.p;
@@ -156,8 +148,7 @@
         avn_status st;
         if ((st = grow_f(b_slp_lin, slp_k.body_lin, slp_lin_default)) != AVN_OK || (st = grow_f(b_slp_ang, slp_k.body_ang, slp_ang_default)) != AVN_OK) return st;
         if (slp_k.body_disabled) {
-            b_slp_dis.ensure((size_t)n, e, true, stream);
-            if (e != hipSuccess) { error = "hipMalloc failed (SleepingDisabled flags)"; return AVN_ERR_OOM; }
+            ALLOC(b_slp_dis.ensure((size_t)n, nullptr, true, stream));
             HIPCHK(hipMemsetAsync((uint8_t*)b_slp_dis.p + old, 0, n - old, stream));
             slp_k.body_disabled = (const uint8_t*)b_slp_dis.p;
         }
@@ -203,21 +194,20 @@
         slp_time_to_sleep = p->time_to_sleep;
         slp_lin_default = p->linear_threshold; slp_ang_default = p->angular_threshold; slp_bodies = n;
         HIPCHK(hipStreamSynchronize(stream));
-        hipError_t err;
-        auto up = [&](DevBuf& b, const void* src, size_t bytes) -> const void* {
-            if (!src) return nullptr;
-            b.ensure(std::max<size_t>(bytes, 1), err);
-            if (err != hipSuccess) return nullptr;
-            if (hipMemcpy(b.p, src, bytes, hipMemcpyHostToDevice) != hipSuccess) { err = hipErrorUnknown; return nullptr; }
-            return b.p;
-        };
-        err = hipSuccess;
-        slp_k.body_lin = (const float*)up(b_slp_lin, p->body_linear_threshold, (size_t)n * 4);
-        slp_k.body_ang = (const float*)up(b_slp_ang, p->body_angular_threshold, (size_t)n * 4);
-        slp_k.body_disabled = (const uint8_t*)up(b_slp_dis, p->body_sleeping_disabled, n);
-        if (err != hipSuccess) { error = "sleeping_enable: device allocation / copy failed"; return AVN_ERR_OOM; }
-        b_slp_timer.ensure(std::max<size_t>(n, 1) * 4, err); if (err != hipSuccess) { error = "hipMalloc failed"; return AVN_ERR_OOM; }
-        b_slp_flags.ensure(std::max<size_t>(n, 1), err); if (err != hipSuccess) { error = "hipMalloc failed"; return AVN_ERR_OOM; }
+        if (p->body_linear_threshold) {
+            ALLOC(b_slp_lin.ensure_as(std::max<size_t>(n, 1), &slp_k.body_lin));
+            HIPCHK(hipMemcpy(b_slp_lin.p, p->body_linear_threshold, (size_t)n * 4, hipMemcpyHostToDevice));
+        }
+        if (p->body_angular_threshold) {
+            ALLOC(b_slp_ang.ensure_as(std::max<size_t>(n, 1), &slp_k.body_ang));
+            HIPCHK(hipMemcpy(b_slp_ang.p, p->body_angular_threshold, (size_t)n * 4, hipMemcpyHostToDevice));
+        }
+        if (p->body_sleeping_disabled) {
+            ALLOC(b_slp_dis.ensure_as(std::max<size_t>(n, 1), &slp_k.body_disabled));
+            HIPCHK(hipMemcpy(b_slp_dis.p, p->body_sleeping_disabled, n, hipMemcpyHostToDevice));
+        }
+        ALLOC(b_slp_timer.ensure(std::max<size_t>(n, 1) * 4));
+        ALLOC(b_slp_flags.ensure(std::max<size_t>(n, 1)));
         HIPCHK(hipMemset(b_slp_timer.p, 0, std::max<size_t>(n, 1) * 4));
         slp_n_awake = slp_last_slept = slp_last_woken = slp_last_popped = slp_last_pushed = 0;
         slp_on = true;
@@ -310,7 +300,7 @@
         double m0 = slp_now();
         launch_sleep_timers_flags<T>(dw, slp_k, b_slp_timer.as<float>(), b_slp_flags.as<uint8_t>(), stream); ++launches;   // behind the write-back: SolverBody velocities of this step
         HIPCHK(hipGetLastError());
-        if (pin_slp_timers.ensure((size_t)n * 5 + 64) != hipSuccess) { error = "hipHostMalloc failed"; return AVN_ERR_OOM; }
+        ALLOC(pin_slp_timers.ensure((size_t)n * 5 + 64));
         float* h_timer = (float*)pin_slp_timers.p; uint8_t* h_flags = (uint8_t*)(h_timer + n);
         HIPCHK(hipMemcpyAsync(h_timer, b_slp_timer.p, (size_t)n * 4, hipMemcpyDeviceToHost, stream));
         HIPCHK(hipMemcpyAsync(h_flags, b_slp_flags.p, n, hipMemcpyDeviceToHost, stream));

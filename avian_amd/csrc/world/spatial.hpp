@@ -20,7 +20,6 @@
         if (sp_cap && C <= sp_cap) return AVN_OK;
         HIPCHK(hipStreamSynchronize(stream));   // (the old buffers may still be read by an update in flight)
         const size_t cc = std::max<size_t>({(size_t)C, (size_t)sp_cap + sp_cap / 2, 64});
-        bool moved = false;
         GROW(b_sp_pos, cc, sp.pos); GROW(b_sp_rot, cc, sp.rot); GROW(b_sp_he, cc, sp.he); GROW(b_sp_info, cc, sp.info);
         GROW(b_sp_smin, cc, sp.smin); GROW(b_sp_smax, cc, sp.smax);
         GROW(b_sp_bmin, 2 * cc, sp.bmin); GROW(b_sp_bmax, 2 * cc, sp.bmax); GROW(b_sp_child, cc, sp.child); GROW(b_sp_parent, 2 * cc, sp.parent);
@@ -29,8 +28,7 @@
         GROW(b_sp_hist, (size_t)256 * radix_blocks((uint32_t)cc) + 256, sp.hist);
         GROW(b_sp_block_sums, scan_block_sums_needed(256 * radix_blocks((uint32_t)cc)) + 16, sp.block_sums);
         HIPCHK(hipMemset(b_sp_block_sums.p, 0, b_sp_block_sums.cap));   // the one-launch scan's state: zero once, self-cleaning afterwards (avn_scan.h)
-        unsigned long long* dummy_s;
-        GROW(b_sp_stats, 4, dummy_s);
+        ALLOC(b_sp_stats.ensure(4 * sizeof(unsigned long long)));
         sp_cap = (uint32_t)cc;
         return AVN_OK;
     }
@@ -284,7 +282,6 @@
             if (n) HIPCHK(hipMemsetAsync(d_out, 0, (size_t)n * sizeof(SpatialDepenetration<T>), stream));
             HIPCHK(hipMemsetAsync(b_sp_stats.p, 0, 4 * sizeof(unsigned long long), stream));
         } else {
-            bool moved = false;
             SC<T> sc{};
             uint32_t* d_count;
             GROW(b_sp_crec, std::max<size_t>((size_t)n * AVN_SPATIAL_MAX_HITS, 1), sc.rec);
@@ -346,7 +343,6 @@
         plan.in(s->movement, 3 * (size_t)n, &m.movement); plan.in(s->skin_width, n, &m.skin); plan.in(s->self_entity, n, &m.self_entity);
         plan.out(out->hits, n, &m.out);
         COMMIT(plan);
-        bool moved = false;
         GROW(b_mv_pend, std::max<size_t>((size_t)n * AVN_SPATIAL_MAX_HITS, 1), m.pending);
         GROW(b_mv_pcount, std::max<size_t>(n, 1), m.pending_count);
         launch_spatial_cast_move<T>(sp, m, true, stream, sp_any_capsule(s->shape, n, dev), sp_ccap);
@@ -380,7 +376,6 @@
         COMMIT(plan);
         l.n = n; l.hit_cap = hit_cap; l.n_planes = cfg->n_planes; l.max_planes = cfg->max_planes; l.depen_iterations = cfg->depenetration_iterations;
         l.shape = sc.q.shape; l.he = sc.q.he; l.pos_in = sc.q.a; l.rot = sc.q.rot;
-        bool moved = false;
         const size_t nn = std::max<size_t>(n, 1);
         uint32_t* d_count;
         SpatialMoveHit<T>* d_mh;
@@ -499,11 +494,9 @@
         const size_t r_origin = 0, r_dir = r_origin + al(3 * sizeof(T) * n), r_dir_t = r_dir + al(12 * (size_t)n), r_rot = r_dir_t + al(3 * sizeof(T) * n),
                      r_rec = r_rot + al(4 * sizeof(T) * n), r_count = r_rec + al(rec * n * d.hit_cap), r_end = r_count + al(4 * (size_t)n);
         HIPCHK(hipStreamSynchronize(stream));   // (a run in flight may still read the old tables)
-        hipError_t err;
         cs.n = 0;
-        cs.def.ensure(al(img.size()) + 64, err);
-        if (err == hipSuccess) cs.res.ensure(r_end, err);
-        if (err != hipSuccess) { error = std::string(who) + ": hipMalloc: " + hipGetErrorName(err); return AVN_ERR_OOM; }
+        ALLOC(cs.def.ensure(al(img.size()) + 64));
+        ALLOC(cs.res.ensure(r_end));
         HIPCHK(hipMemcpy(cs.def.p, img.data(), img.size(), hipMemcpyHostToDevice));
         const char* D = (const char*)cs.def.p;
         char* R = (char*)cs.res.p;
@@ -556,9 +549,7 @@
         }
         if ((cs_ray.n || cs_shape.n) && (st = sp_check(flags)) != AVN_OK) return st;   // (no casters: the run is the update)
         if (!b_cs_stats.p) {
-            hipError_t err;
-            b_cs_stats.ensure(4 * sizeof(unsigned long long), err);
-            if (err != hipSuccess) { error = std::string("spatial_casters_run: hipMalloc: ") + hipGetErrorName(err); return AVN_ERR_OOM; }
+            ALLOC(b_cs_stats.ensure(4 * sizeof(unsigned long long)));
         }
         unsigned long long* stats = b_cs_stats.as<unsigned long long>();
         HIPCHK(hipMemsetAsync(stats, 0, 4 * sizeof(unsigned long long), stream));
