@@ -217,6 +217,7 @@ class avn_swept_ccd_stats(C.Structure):
 
 SWEPT_CCD_SYMBOLS = ("avn_swept_ccd_upload", "avn_swept_ccd_results_get")
 SWEPT_CCD_NON_LINEAR_SYMBOLS = ("avn_swept_ccd_non_linear_set", "avn_swept_ccd_stats_get")   # absent from a library older than SweepMode::NonLinear
+SWEPT_CCD_CAPSULES_SYMBOLS = ("avn_swept_ccd_capsules_set",)   # absent from a library older than swept CCD against Capsule colliders
 
 
 def declare_swept_ccd(dll):
@@ -227,6 +228,9 @@ def declare_swept_ccd(dll):
         dll.avn_swept_ccd_non_linear_set.restype = dll.avn_swept_ccd_stats_get.restype = C.c_int32
         dll.avn_swept_ccd_non_linear_set.argtypes = [vp, C.c_uint32]
         dll.avn_swept_ccd_stats_get.argtypes = [vp, vp]
+    if all(hasattr(dll, name) for name in SWEPT_CCD_CAPSULES_SYMBOLS):
+        dll.avn_swept_ccd_capsules_set.restype = C.c_int32
+        dll.avn_swept_ccd_capsules_set.argtypes = [vp, C.c_uint32]
 
 
 class avn_broad_phase_stats(C.Structure):

@@ -605,6 +605,7 @@ enum { CCD_CTR_CAND = 0, CCD_CTR_NL_TESTED = 1, CCD_CTR_ROUNDS_MAX = 2, CCD_CTR_
 #define CCD_NL_ROUNDS 64
 template <class T> void launch_ccd_tables(const DW<T>&, const BP<T>&, const CCD<T>&, hipStream_t);   // CCD::own / CCD::entry from the collider table
 // the pass: candidates, times of impact, winners, the writes in list order.  n_rows: the contact table's row high-water mark.  Returns the launches issued.
-template <class T> uint32_t launch_ccd_pass(const DW<T>&, const BP<T>&, const CT<T>&, const PG&, const CCD<T>&, const StepParams<T>&, uint32_t n_rows, hipStream_t);
+// capsules: avn_swept_ccd_capsules_set is on and the collider table holds an AVN_SHAPE_CAPSULE: the _cap kernels run behind the Ball / Cuboid ones
+template <class T> uint32_t launch_ccd_pass(const DW<T>&, const BP<T>&, const CT<T>&, const PG&, const CCD<T>&, const StepParams<T>&, uint32_t n_rows, hipStream_t, bool capsules = false);
 
 }  // namespace avn

@@ -48,6 +48,7 @@ AVN_API avn_status avn_spatial_stats_get(avn_world* w, avn_spatial_stats* o) { S
 AVN_API avn_status avn_swept_ccd_upload(avn_world* w, const avn_swept_ccd* l) { if (w && w->impl) w->impl->touched(); SP_GUARD(swept_ccd_upload(l)); }
 AVN_API avn_status avn_swept_ccd_results_get(avn_world* w, avn_swept_ccd_results_out* o) { SP_GUARD(swept_ccd_results_get(o)); }
 AVN_API avn_status avn_swept_ccd_non_linear_set(avn_world* w, uint32_t enabled) { SP_GUARD(swept_ccd_non_linear_set(enabled)); }
+AVN_API avn_status avn_swept_ccd_capsules_set(avn_world* w, uint32_t enabled) { SP_GUARD(swept_ccd_capsules_set(enabled)); }
 AVN_API avn_status avn_swept_ccd_stats_get(avn_world* w, avn_swept_ccd_stats* o) { SP_GUARD(swept_ccd_stats_get(o)); }
 
 }  // extern "C"

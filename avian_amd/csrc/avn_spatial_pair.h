@@ -809,4 +809,52 @@ __device__ __forceinline__ T sp_nl_gap(uint32_t shape1, V3<T> he1, V3<T> p1, Q4<
     return g;
 }
 
+// N2 with Capsule colliders (avn_swept_ccd_capsules_set; the _cap kernels of k_ccd.hip only, so that no instantiation of sp_nl_gap changes): the
+// exact distance of the cores minus the radii.  A capsule's he = (r, h, .).  capsule - ball in the capsule's frame by sp_seg_point; capsule -
+// capsule in collider 1's frame by sp_seg_seg_d2 with collider 1's core as segment 1; capsule - cuboid in the cuboid's frame by sp_seg_box.
+// !(dist > 0): g as computed (minus the radius or radii), n = (0, 1, 0).  A pair without a capsule (the small ball of N4 against a Ball /
+// Cuboid collider 1; never two cuboids) goes to sp_nl_gap.
+template <class T>
+__device__ __forceinline__ T sp_nl_gap_cap(uint32_t shape1, V3<T> he1, V3<T> p1, Q4<T> q1, uint32_t shape2, V3<T> he2, V3<T> p2, Q4<T> q2, V3<T>& n) {
+    const bool cap1 = shape1 == AVN_SHAPE_CAPSULE, cap2 = shape2 == AVN_SHAPE_CAPSULE;
+    const V3<T> up{T(0), T(1), T(0)};
+    if (cap1 && cap2) {
+        const Iso<T> pos12 = iso_inv_mul(Iso<T>{q1, p1}, Iso<T>{q2, p2});
+        V3<T> A1, u1, A2, u2, pa, pb;
+        sp_capcol_core<T>(he1.y, A1, u1);
+        sp_capsule_core<T>(pos12, he2.y, A2, u2);
+        const T dist = sqrt_t(sp_seg_seg_d2<T>(A1, u1, A2, u2, pa, pb));
+        n = dist > T(0) ? na_qrot(q1, (pb - pa) / dist) : up;
+        return dist - (he1.x + he2.x);
+    }
+    if (cap1 || cap2) {
+        const V3<T> pc = cap1 ? p1 : p2, po = cap1 ? p2 : p1, hc = cap1 ? he1 : he2, ho = cap1 ? he2 : he1;
+        const Q4<T> qc = cap1 ? q1 : q2, qo = cap1 ? q2 : q1;
+        if ((cap1 ? shape2 : shape1) == AVN_SHAPE_BALL) {
+            const V3<T> l = qrot(qinverse(qc), po - pc);   // the ball's centre in the capsule's frame
+            V3<T> A, u;
+            sp_capcol_core<T>(hc.y, A, u);
+            T s;
+            (void)sp_seg_point<T>(A, u, l, s);
+            const V3<T> df = l - (A + u * s);
+            const T dist = length(df);
+            const V3<T> nw = qrot(qc, df / dist);             // from the capsule towards the ball
+            n = dist > T(0) ? (cap1 ? nw : -nw) : up;
+            return dist - (hc.x + ho.x);
+        }
+        const Iso<T> pos = iso_inv_mul(Iso<T>{qo, po}, Iso<T>{qc, pc});   // the capsule in the cuboid's frame
+        V3<T> A, u;
+        sp_capsule_core<T>(pos, hc.y, A, u);
+        const SegBox<T> sb = sp_seg_box<T>(A, u, ho);
+        const T dist = sqrt_t(sb.f);
+        const V3<T> nw = qrot(qo, (sb.ps - sb.pb) / dist);   // from the box towards the capsule
+        n = dist > T(0) ? (cap1 ? -nw : nw) : up;
+        return dist - hc.x;
+    }
+    // (no caller brings two cuboids: said here so that the SAT sweeps stay out of the _cap kernels)
+    if (shape1 == AVN_SHAPE_BALL || shape2 == AVN_SHAPE_BALL) return sp_nl_gap<T>(shape1, he1, p1, q1, shape2, he2, p2, q2, n);
+    n = up;
+    return sp_inf<T>();
+}
+
 }  // namespace avn

@@ -141,6 +141,7 @@ struct WorldBase {
     virtual avn_status swept_ccd_upload(const avn_swept_ccd*) = 0;
     virtual avn_status swept_ccd_results_get(avn_swept_ccd_results_out*) = 0;
     virtual avn_status swept_ccd_non_linear_set(uint32_t enabled) = 0;
+    virtual avn_status swept_ccd_capsules_set(uint32_t enabled) = 0;
     virtual avn_status swept_ccd_stats_get(avn_swept_ccd_stats*) = 0;
 };
 

@@ -15,6 +15,9 @@
 //                      header's conservative advancement N1 - N3 over both bodies' linear and angular motion, at most CCD_NL_ROUNDS rounds; the
 //                      same atomicMin; the statistics of avn_swept_ccd_stats_get go into the spare words of CCD::ctr
 //   k_ccd_origin_nl    its t == 0 pairs with a bounded margin: the contact at prediction 0, then the small ball by the same advancement (N4)
+//   k_ccd_toi_cap, k_ccd_toi_nl_cap, k_ccd_origin_nl_cap, k_ccd_origin_cap
+//                      only with avn_swept_ccd_capsules_set on and a capsule in the collider table, behind the four above: the same for the pairs
+//                      with an AVN_SHAPE_CAPSULE collider (the casts of the capsule query / the capsule collider, sp_nl_gap_cap, the capsule manifold)
 //   k_ccd_pick         among the candidates whose time equals the entry's minimum: atomicMin of (incoming << 63 | ~seq), which is the
 //                      position of the edge in the reference's `neighbors` order (outgoing edges newest first, then incoming newest first)
 //   k_ccd_resolve      the one candidate that holds both minima writes the entry's record and its two writes (target body, 2 entry + side)
@@ -26,6 +29,7 @@
 #include <algorithm>
 
 #include "avn_spatial_pair.h"
+#include "avn_capsule_pair.h"   // capsule colliders: the CAP instantiation of contact_manifolds_pair_sink (k_ccd_origin_cap, k_ccd_origin_nl_cap)
 
 namespace avn {
 
@@ -99,8 +103,8 @@ template <class T> struct CcdPair {
     V3<T> he1, he2, pos1, pos2, d;
     Q4<T> rot1, rot2;
 };
-// the reference's filters, in its order; false: the pair is not tested
-template <class T>
+// the reference's filters, in its order; false: the pair is not tested.  CAP (the _cap kernels): AVN_SHAPE_CAPSULE passes, AVN_SHAPE_HOST does not
+template <class T, bool CAP = false>
 __device__ __forceinline__ bool ccd_pair(const DW<T>& w, const BP<T>& bp, const CT<T>& ct, const CCD<T>& c, uint2 cd, CcdPair<T>& p) {
     const uint4 m = ct.meta[cd.x];
     const uint32_t side = cd.y & 1u;
@@ -112,7 +116,8 @@ __device__ __forceinline__ bool ccd_pair(const DW<T>& w, const BP<T>& bp, const 
     if (!meta_has_solver_body(w.bmeta[p.b1])) return false;                    // `solver_body: Some(..)`
     if (bp.col_lpos && bp.col_lpos[c2].w != T(0)) return false;                 // a child collider (declared deviation)
     p.shape1 = i1.z & 0xFFu; p.shape2 = i2.z & 0xFFu;
-    if (p.shape1 > AVN_SHAPE_BALL || p.shape2 > AVN_SHAPE_BALL) return false;   // AVN_SHAPE_HOST, AVN_SHAPE_CAPSULE (declared deviations)
+    if constexpr (CAP) { if (p.shape1 == AVN_SHAPE_HOST || p.shape2 == AVN_SHAPE_HOST || p.shape1 > AVN_SHAPE_CAPSULE || p.shape2 > AVN_SHAPE_CAPSULE) return false; }
+    else if (p.shape1 > AVN_SHAPE_BALL || p.shape2 > AVN_SHAPE_BALL) return false;   // AVN_SHAPE_HOST, AVN_SHAPE_CAPSULE (declared deviations)
     const uint32_t bm2 = w.bmeta[p.b2];
     if (!c.include_dynamic[p.e] && meta_rb_type(bm2) == AVN_RB_DYNAMIC) return false;
     const bool has2 = meta_has_solver_body(bm2);
@@ -202,7 +207,7 @@ template <class T> __device__ __forceinline__ void ccd_pose(const CcdMotion<T>& 
     p = (m.c0 + t * m.v) - qrot(q, m.com);
 }
 // N3: conservative advancement from t = 0.  1: a hit at t_out, 0: a miss, 2: out of rounds (answers nothing)
-template <class T>
+template <class T, bool CAP = false>
 __device__ __forceinline__ int ccd_nl_advance(uint32_t shape1, V3<T> he1, const CcdMotion<T>& m1, uint32_t shape2, V3<T> he2, const CcdMotion<T>& m2, V3<T> d, T dt, T tol,
                                               T& t_out, uint32_t& rounds) {
     T t = T(0);
@@ -212,7 +217,9 @@ __device__ __forceinline__ int ccd_nl_advance(uint32_t shape1, V3<T> he1, const 
         Q4<T> q1, q2;
         ccd_pose<T>(m1, t, p1, q1);
         ccd_pose<T>(m2, t, p2, q2);
-        const T g = sp_nl_gap<T>(shape1, he1, p1, q1, shape2, he2, p2, q2, n);
+        T g;
+        if constexpr (CAP) g = sp_nl_gap_cap<T>(shape1, he1, p1, q1, shape2, he2, p2, q2, n);
+        else g = sp_nl_gap<T>(shape1, he1, p1, q1, shape2, he2, p2, q2, n);
         if (g <= tol) { t_out = t; return 1; }
         const T B = (-dot(d, n) + length(cross(m1.om, n)) * m1.R) + length(cross(m2.om, n)) * m2.R;
         if (!(B > T(0))) return 0;
@@ -284,6 +291,113 @@ __global__ __launch_bounds__(CCD_WAVE) void k_ccd_origin_nl(DW<T> w, BP<T> bp, C
     }
 }
 
+// ---- Capsule colliders (avn_swept_ccd_capsules_set; the header's "capsule colliders") ----
+// Kernels of their own behind the ones above, launched only when the switch is on and the collider table holds a capsule: the segment - box
+// routine and the Newton casts stay out of the Ball / Cuboid kernels, which have written CCD_T_NONE for every pair with a capsule.  Each passes
+// over the candidates without one and overwrites cand_t of the others.
+template <class T> __device__ __forceinline__ bool ccd_has_capsule(const CcdPair<T>& p) { return p.shape1 == AVN_SHAPE_CAPSULE || p.shape2 == AVN_SHAPE_CAPSULE; }
+template <class T> __device__ __forceinline__ T ccd_rho_cap(uint32_t shape, V3<T> he) { return shape == AVN_SHAPE_CAPSULE ? he.y + he.x : ccd_rho<T>(shape, he); }
+// step 3 by role: collider = c1, cast shape = c2
+template <class T>
+__device__ __forceinline__ bool ccd_cast_cap(const CcdPair<T>& p, T dt, T& toi) {
+    V3<T> p1, p2, n1;
+    const Iso<T> iso2 = make_isometry(p.pos2, p.rot2);
+    if (p.shape1 != AVN_SHAPE_CAPSULE) return sp_capsule_cast_exact<T>(p.he2.x, p.he2.y, iso2, p.d, dt, p.shape1, p.he1, p.pos1, p.rot1, toi, p1, p2, n1);
+    if (p.shape2 != AVN_SHAPE_CAPSULE) return sp_capcol_cast_exact<T, false>(p.shape2, p.he2, iso2, p.d, dt, p.he1, p.pos1, p.rot1, toi, p1, p2, n1);
+    return sp_capcol_cast_exact<T, true>(p.shape2, p.he2, iso2, p.d, dt, p.he1, p.pos1, p.rot1, toi, p1, p2, n1);
+}
+// step 4's contact at prediction 0 with the cast shape (2) as shape 1: true when the pair is leaving
+template <class T>
+__device__ __forceinline__ bool ccd_leaving_cap(const CcdPair<T>& p) {
+    SpDeepestSink<T> sink{vzero<T>(), T(0), 0};
+    V3<T> nrm;
+    const V3<T> hq = p.shape2 == AVN_SHAPE_BALL ? V3<T>{p.he2.x, p.he2.x, p.he2.x} : p.he2;
+    if (!contact_manifolds_pair_sink<T, SpDeepestSink<T>, 0, true>(p.shape2, hq, p.pos2, p.rot2, p.shape1, p.he1, p.pos1, p.rot1, T(0), sink, nrm)) return false;
+    const V3<T> cn{-nrm.x, -nrm.y, -nrm.z};
+    return p.d.x * cn.x + p.d.y * cn.y + p.d.z * cn.z >= T(0);
+}
+
+template <class T, bool MIXED>
+__global__ __launch_bounds__(CCD_WAVE) void k_ccd_toi_cap(DW<T> w, BP<T> bp, CT<T> ct, CCD<T> c, T dt, bool origin_rule) {
+    const uint32_t count = c.ctr[0] < c.cand_cap ? c.ctr[0] : c.cand_cap;
+    for (uint32_t i = blockIdx.x * CCD_WAVE + threadIdx.x; i < count; i += gridDim.x * CCD_WAVE) {
+        CcdPair<T> p;
+        if (!ccd_pair<T, true>(w, bp, ct, c, c.cand[i], p) || !ccd_has_capsule<T>(p)) continue;   // (k_ccd_toi wrote the candidate's cand_t)
+        if constexpr (MIXED) { if (ccd_pair_nl<T>(c, p)) continue; }
+        atomicAdd(&c.rec[p.e].tested, 1u);
+        unsigned long long bits = CCD_T_NONE;
+        T toi;
+        if (ccd_cast_cap<T>(p, dt, toi)) {
+            if (toi == T(0)) { if (origin_rule) bits = CCD_T_ORIGIN; }
+            else ccd_accept<T>(c, p.e, toi, dt, bits);
+        }
+        c.cand_t[i] = bits;
+    }
+}
+
+template <class T>
+__global__ __launch_bounds__(CCD_WAVE) void k_ccd_origin_cap(DW<T> w, BP<T> bp, CT<T> ct, CCD<T> c, T dt, T margin) {
+    const uint32_t count = c.ctr[0] < c.cand_cap ? c.ctr[0] : c.cand_cap;
+    for (uint32_t i = blockIdx.x * CCD_WAVE + threadIdx.x; i < count; i += gridDim.x * CCD_WAVE) {
+        if (c.cand_t[i] != CCD_T_ORIGIN) continue;   // (k_ccd_origin has resolved its own: only k_ccd_toi_cap's marks are left)
+        unsigned long long bits = CCD_T_NONE;
+        CcdPair<T> p;
+        if (ccd_pair<T, true>(w, bp, ct, c, c.cand[i], p) && ccd_has_capsule<T>(p) && !ccd_leaving_cap<T>(p)) {
+            // the "small ball" against c1: a capsule collider by sp_capcol_cast_exact, a Ball / Cuboid one (the capsule is the cast shape) as ever
+            T toi; V3<T> p1, p2, n1;
+            const V3<T> hb{margin, margin, margin};
+            const Iso<T> iso2 = make_isometry(p.pos2, p.rot2);
+            const bool hit = p.shape1 == AVN_SHAPE_CAPSULE ? sp_capcol_cast_exact<T, false>(AVN_SHAPE_BALL, hb, iso2, p.d, dt, p.he1, p.pos1, p.rot1, toi, p1, p2, n1)
+                                                           : sp_cast_exact<T>(AVN_SHAPE_BALL, hb, iso2, p.d, dt, p.shape1, p.he1, p.pos1, p.rot1, toi, p1, p2, n1);
+            if (hit) ccd_accept<T>(c, p.e, toi, dt, bits);
+        }
+        c.cand_t[i] = bits;
+    }
+}
+
+template <class T>
+__global__ __launch_bounds__(CCD_WAVE) void k_ccd_toi_nl_cap(DW<T> w, BP<T> bp, CT<T> ct, CCD<T> c, T dt, T tol, bool origin_rule) {
+    const uint32_t count = c.ctr[0] < c.cand_cap ? c.ctr[0] : c.cand_cap;
+    for (uint32_t i = blockIdx.x * CCD_WAVE + threadIdx.x; i < count; i += gridDim.x * CCD_WAVE) {
+        CcdPair<T> p;
+        if (!ccd_pair<T, true>(w, bp, ct, c, c.cand[i], p) || !ccd_has_capsule<T>(p) || !ccd_pair_nl<T>(c, p)) continue;
+        atomicAdd(&c.rec[p.e].tested, 1u);
+        atomicAdd(&c.ctr[CCD_CTR_NL_TESTED], 1u);
+        const CcdMotion<T> m1 = ccd_motion<T>(w, p.b1, p.pos1, p.rot1, ccd_rho_cap<T>(p.shape1, p.he1));
+        const CcdMotion<T> m2 = ccd_motion<T>(w, p.b2, p.pos2, p.rot2, ccd_rho_cap<T>(p.shape2, p.he2));
+        T toi = T(0);
+        uint32_t rounds = 0u;
+        const int res = ccd_nl_advance<T, true>(p.shape1, p.he1, m1, p.shape2, p.he2, m2, p.d, dt, tol, toi, rounds);
+        ccd_nl_stats<T>(c, res, rounds);
+        unsigned long long bits = CCD_T_NONE;
+        if (res == 1) {
+            if (toi == T(0)) { if (origin_rule) bits = CCD_T_ORIGIN_NL; }
+            else ccd_accept<T>(c, p.e, toi, dt, bits);
+        }
+        c.cand_t[i] = bits;
+    }
+}
+
+template <class T>
+__global__ __launch_bounds__(CCD_WAVE) void k_ccd_origin_nl_cap(DW<T> w, BP<T> bp, CT<T> ct, CCD<T> c, T dt, T tol, T margin) {
+    const uint32_t count = c.ctr[0] < c.cand_cap ? c.ctr[0] : c.cand_cap;
+    for (uint32_t i = blockIdx.x * CCD_WAVE + threadIdx.x; i < count; i += gridDim.x * CCD_WAVE) {
+        if (c.cand_t[i] != CCD_T_ORIGIN_NL) continue;   // (k_ccd_origin_nl has resolved its own)
+        unsigned long long bits = CCD_T_NONE;
+        CcdPair<T> p;
+        if (ccd_pair<T, true>(w, bp, ct, c, c.cand[i], p) && ccd_has_capsule<T>(p) && !ccd_leaving_cap<T>(p)) {
+            const CcdMotion<T> m1 = ccd_motion<T>(w, p.b1, p.pos1, p.rot1, ccd_rho_cap<T>(p.shape1, p.he1));
+            const CcdMotion<T> m2 = ccd_motion<T>(w, p.b2, p.pos2, p.rot2, margin);
+            T toi = T(0);
+            uint32_t rounds = 0u;
+            const int res = ccd_nl_advance<T, true>(p.shape1, p.he1, m1, AVN_SHAPE_BALL, V3<T>{margin, margin, margin}, m2, p.d, dt, tol, toi, rounds);
+            ccd_nl_stats<T>(c, res, rounds);
+            if (res == 1) ccd_accept<T>(c, p.e, toi, dt, bits);
+        }
+        c.cand_t[i] = bits;
+    }
+}
+
 __device__ __forceinline__ unsigned long long ccd_edge_key(uint32_t side, unsigned long long seq) { return ((unsigned long long)side << 63) | (~seq & CCD_KEY_MASK); }
 
 template <class T>
@@ -348,7 +462,7 @@ template <class T> void launch_ccd_tables(const DW<T>& w, const BP<T>& bp, const
 
 static uint32_t ccd_bits_for(uint32_t max_value) { uint32_t b = 1; while (b < 32 && (max_value >> b)) ++b; return b; }
 
-template <class T> uint32_t launch_ccd_pass(const DW<T>& w, const BP<T>& bp, const CT<T>& ct, const PG& pg, const CCD<T>& c, const StepParams<T>& p, uint32_t n_rows, hipStream_t s) {
+template <class T> uint32_t launch_ccd_pass(const DW<T>& w, const BP<T>& bp, const CT<T>& ct, const PG& pg, const CCD<T>& c, const StepParams<T>& p, uint32_t n_rows, hipStream_t s, bool capsules) {
     if (!c.n) return 0;
     uint32_t launches = 0;
     const uint32_t n2 = 2u * c.n;
@@ -367,6 +481,15 @@ template <class T> uint32_t launch_ccd_pass(const DW<T>& w, const BP<T>& bp, con
         if (origin_rule) { hipLaunchKernelGGL(k_ccd_origin_nl<T>, dim3(wave_blocks), dim3(CCD_WAVE), 0, s, w, bp, ct, c, p.dt_adj, p.contact_tolerance, p.default_speculative_margin); ++launches; }
     }
     if (origin_rule) { hipLaunchKernelGGL(k_ccd_origin<T>, dim3(wave_blocks), dim3(CCD_WAVE), 0, s, w, bp, ct, c, p.dt_adj, p.default_speculative_margin); ++launches; }
+    if (capsules) {   // the switch is on and the collider table holds a capsule: each origin kernel behind the _cap kernel that marks for it
+        if (!nl) { hipLaunchKernelGGL((k_ccd_toi_cap<T, false>), dim3(wave_blocks), dim3(CCD_WAVE), 0, s, w, bp, ct, c, p.dt_adj, origin_rule); ++launches; }
+        else {
+            hipLaunchKernelGGL((k_ccd_toi_cap<T, true>), dim3(wave_blocks), dim3(CCD_WAVE), 0, s, w, bp, ct, c, p.dt_adj, origin_rule); ++launches;
+            hipLaunchKernelGGL(k_ccd_toi_nl_cap<T>, dim3(wave_blocks), dim3(CCD_WAVE), 0, s, w, bp, ct, c, p.dt_adj, p.contact_tolerance, origin_rule); ++launches;
+            if (origin_rule) { hipLaunchKernelGGL(k_ccd_origin_nl_cap<T>, dim3(wave_blocks), dim3(CCD_WAVE), 0, s, w, bp, ct, c, p.dt_adj, p.contact_tolerance, p.default_speculative_margin); ++launches; }
+        }
+        if (origin_rule) { hipLaunchKernelGGL(k_ccd_origin_cap<T>, dim3(wave_blocks), dim3(CCD_WAVE), 0, s, w, bp, ct, c, p.dt_adj, p.default_speculative_margin); ++launches; }
+    }
     hipLaunchKernelGGL(k_ccd_pick<T>, dim3(flat_blocks), dim3(256), 0, s, c, pg.seq); ++launches;
     hipLaunchKernelGGL(k_ccd_resolve<T>, dim3(flat_blocks), dim3(256), 0, s, w, bp, ct, c, pg.seq); ++launches;
     uint32_t *keys = c.wkey_a, *vals = c.wval_a;
@@ -380,7 +503,7 @@ template <class T> uint32_t launch_ccd_pass(const DW<T>& w, const BP<T>& bp, con
 static_assert(sizeof(SweptCcdResult<float>) == 16 && sizeof(SweptCcdResult<double>) == 24, "swept CCD record layout");
 template void launch_ccd_tables<float>(const DW<float>&, const BP<float>&, const CCD<float>&, hipStream_t);
 template void launch_ccd_tables<double>(const DW<double>&, const BP<double>&, const CCD<double>&, hipStream_t);
-template uint32_t launch_ccd_pass<float>(const DW<float>&, const BP<float>&, const CT<float>&, const PG&, const CCD<float>&, const StepParams<float>&, uint32_t, hipStream_t);
-template uint32_t launch_ccd_pass<double>(const DW<double>&, const BP<double>&, const CT<double>&, const PG&, const CCD<double>&, const StepParams<double>&, uint32_t, hipStream_t);
+template uint32_t launch_ccd_pass<float>(const DW<float>&, const BP<float>&, const CT<float>&, const PG&, const CCD<float>&, const StepParams<float>&, uint32_t, hipStream_t, bool);
+template uint32_t launch_ccd_pass<double>(const DW<double>&, const BP<double>&, const CT<double>&, const PG&, const CCD<double>&, const StepParams<double>&, uint32_t, hipStream_t, bool);
 
 }  // namespace avn

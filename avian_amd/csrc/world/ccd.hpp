@@ -6,6 +6,7 @@
     DevBuf b_ccd_body, b_ccd_incl, b_ccd_lin2, b_ccd_ang2, b_ccd_own, b_ccd_entry, b_ccd_ctr, b_ccd_cand, b_ccd_cand_t, b_ccd_min_t, b_ccd_min_key, b_ccd_rec,
         b_ccd_wkey_a, b_ccd_wval_a, b_ccd_wkey_b, b_ccd_wval_b, b_ccd_hist, b_ccd_sums, b_ccd_mode, b_ccd_bmode;
     bool ccd_nl_on = false;         // avn_swept_ccd_non_linear_set: AVN_SWEEP_NON_LINEAR is accepted (sticky, off in a new world)
+    bool ccd_caps_on = false;       // avn_swept_ccd_capsules_set: pairs with an AVN_SHAPE_CAPSULE collider are tested (sticky, off in a new world)
     bool ccd_tables_dirty = true;   // CCD::own / CCD::entry name the collider table of an earlier upload (colliders / collider transforms / the list itself)
     bool ccd_ran = false;           // a pass has run since the list was uploaded
     bool ccd_stamped = false;       // this step's pass recorded ev_ccd
@@ -84,7 +85,7 @@
             GROW(b_ccd_cand, cap, ccd.cand); GROW(b_ccd_cand_t, cap, ccd.cand_t);
             ccd.cand_cap = (uint32_t)std::min<size_t>(cap, 0xFFFFFFFFu);
         }
-        launches += launch_ccd_pass<T>(dw, bp, ct, pg, ccd, params, pgm_next_id, stream);
+        launches += launch_ccd_pass<T>(dw, bp, ct, pg, ccd, params, pgm_next_id, stream, ccd_caps_on && cap_count != 0);   // (a world without a capsule, or with the switch off, launches what it always has)
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventRecord(ev_ccd, stream));
         ccd_stamped = true; ccd_ran = true;
@@ -106,6 +107,8 @@
         ccd_nl_on = enabled != 0;
         return AVN_OK;
     }
+
+    avn_status swept_ccd_capsules_set(uint32_t enabled) override { ccd_caps_on = enabled != 0; return AVN_OK; }   // (read per pass: nothing to strand)
 
     avn_status swept_ccd_stats_get(avn_swept_ccd_stats* out) override {
         if (!out || out->struct_size != sizeof(avn_swept_ccd_stats)) { error = "swept_ccd_stats_get: null argument or struct_size"; return AVN_ERR_BAD_ARG; }

@@ -1,6 +1,6 @@
 """ctypes binding of ``include/avian_mi355x_ccd.h``: the SweptCcd list of a :class:`avian_amd._ffi.World` in device closed-loop mode and
 the records its pass leaves per step (``SweepMode::Linear`` and, behind :meth:`SweptCcd.set_non_linear`, ``SweepMode::NonLinear``; Ball /
-Cuboid colliders)."""
+Cuboid colliders and, behind :meth:`SweptCcd.set_capsules`, Capsule colliders)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -23,7 +23,7 @@ def result_dtype(bits: int) -> np.dtype:
 class SweptCcd:
     """The SweptCcd components of one world, in the order of Avian's ``Query<Entity, With<SweptCcd>>``."""
 
-    def __init__(self, world: F.World, non_linear: bool = False):
+    def __init__(self, world: F.World, non_linear: bool = False, capsules: bool = False):
         self.world = world
         self.dll = world.lib.dll
         if not hasattr(self.dll, "avn_swept_ccd_upload"):
@@ -33,6 +33,8 @@ class SweptCcd:
         self.count = 0
         if non_linear:
             self.set_non_linear(True)
+        if capsules:
+            self.set_capsules(True)
 
     def set_non_linear(self, enabled: bool):
         """avn_swept_ccd_non_linear_set: whether :meth:`upload` accepts ``SWEEP_NON_LINEAR`` (sticky, off in a new world).  Turning it off while
@@ -40,6 +42,13 @@ class SweptCcd:
         if not hasattr(self.dll, "avn_swept_ccd_non_linear_set"):
             raise ImportError(f"{self.world.lib.path} is older than avn_swept_ccd_non_linear_set")
         self.world._check(self.dll.avn_swept_ccd_non_linear_set(self.world.handle, 1 if enabled else 0))
+
+    def set_capsules(self, enabled: bool):
+        """avn_swept_ccd_capsules_set: whether pairs with a Capsule collider on either side are tested (sticky, off in a new world; may be
+        toggled between steps, it takes effect from the next pass)."""
+        if not hasattr(self.dll, "avn_swept_ccd_capsules_set"):
+            raise ImportError(f"{self.world.lib.path} is older than avn_swept_ccd_capsules_set")
+        self.world._check(self.dll.avn_swept_ccd_capsules_set(self.world.handle, 1 if enabled else 0))
 
     def stats(self) -> dict:
         """avn_swept_ccd_stats_get: nonlinear_tested, rounds_max and exhausted of the last step's pass (waits for it)."""

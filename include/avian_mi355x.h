@@ -404,8 +404,8 @@ typedef struct avn_query_manifolds_out { /* slot = AVN_MAX_QUERY_POINTS * pair +
  *      The spatial queries answer against capsule colliders once avn_spatial_capsule_colliders_set (avian_mi355x_spatial.h, "queries against capsule
  *      colliders") has switched them in; by default a snapshot treats them as it treats host shapes: AVN_ERR_STATE without AVN_SPATIAL_SKIP_HOST_SHAPES,
  *      never a candidate and counted in host_skipped with it.  The capsule-capsule manifold's closest points are sp_seg_seg, the routine those queries use.
- *      NOT in this version: swept CCD (avian_mi355x_ccd.h: kinds above Ball are skipped),
- *      and the oracle backend (avo_colliders_upload has no capsule kind, avo_contact_manifolds rejects kind 3: there a capsule is a host shape). */
+ *      Swept CCD tests pairs with a capsule once avn_swept_ccd_capsules_set has switched them in (avian_mi355x_ccd.h "capsule colliders"; skipped by default).
+ *      NOT in this version: the oracle backend (avo_colliders_upload has no capsule kind, avo_contact_manifolds rejects kind 3: there a capsule is a host shape). */
 typedef struct avn_host_aabb_query_f32 {
     uint32_t collider;          /* Entity::index() */
     uint32_t swept;             /* 0: aabb_with_context(start); 1: swept_aabb_with_context(start, end) */

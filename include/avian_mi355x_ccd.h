@@ -5,7 +5,8 @@
  * SolverSystems::PostSubstep and before SolverSystems::Restitution (ccd/mod.rs:257-261): per SweptCcd body it finds the first time of impact
  * against the colliders whose AABBs its own collider's AABB intersects and moves both bodies back to that time, so that a fast body stops
  * at a thin wall instead of passing through it.  SweepMode::Linear and, behind avn_swept_ccd_non_linear_set, SweepMode::NonLinear (Avian's
- * default, which also follows the bodies' rotation) are built, for Ball / Cuboid colliders; the pass runs on the world's
+ * default, which also follows the bodies' rotation) are built, for Ball / Cuboid colliders and, behind avn_swept_ccd_capsules_set, Capsule
+ * colliders (AVN_SHAPE_CAPSULE, both modes); the pass runs on the world's
  * stream between the substep loop and the restitution pass of avn_step / AVN_SYS_SOLVER, and nothing is read back.  A world without a list
  * launches, stamps and allocates nothing for it.
  *
@@ -21,7 +22,8 @@
  *     body's entity).
  *  2. candidates: the live contact rows (one per AABB-overlapping pair) with c1 in either slot; c2 is the other slot, b2 its body.  A row is
  *     not tested when c2 is a child collider (the reference would cast it at the body's pose, `TODO: Support child colliders`: a declared
- *     deviation); when either collider is AVN_SHAPE_HOST or AVN_SHAPE_CAPSULE (every kind above Ball is skipped: a declared deviation; capsule colliders have no cast here yet); when include_dynamic == 0 and b2 is dynamic, awake or
+ *     deviation); when either collider is AVN_SHAPE_HOST (a declared deviation: the device has no geometry for it), or AVN_SHAPE_CAPSULE
+ *     unless avn_swept_ccd_capsules_set is on ("capsule colliders" below); when include_dynamic == 0 and b2 is dynamic, awake or
  *     asleep; when |w1 - w2|^2 < angular_threshold^2 and |v1 - v2|^2 < linear_threshold^2 (the thresholds cast to the world's scalar, then
  *     squared; v2, w2 = b2's SolverBody velocities, 0 when it has none).  Sensors ARE tested: the reference does not filter them.
  *  3. time of impact: the "shape cast" of avian_mi355x_spatial.h with the collider = c1 at b1's step-start Position / Rotation, the cast
@@ -74,8 +76,35 @@
  *      2's motion, rho_2 = that radius.  With an unbounded margin it is not evaluated and answers nothing.
  * `tested` counts NonLinear pair tests too.  A list without a NonLinear entry launches exactly the kernels of a Linear-only library and leaves
  * the same bytes, whatever the switch says.
- * NOT covered: shapes other than Ball / Cuboid (capsules are skipped in both modes), child and host-shape colliders as targets, parity with
- * parry's nonlinear search, level-2 / sharded worlds, the host-bookkeeping closed loop, 2D, Rust declarations.
+ *
+ * CAPSULE COLLIDERS (avn_swept_ccd_capsules_set; DEFINED like the rest, parity with parry UNPINNED; k_ccd.hip's _cap kernels and
+ * tests/swept_ccd_capsule_reference.py follow it at tolerance 0).  With the switch off a pair with a capsule on either side is skipped, as it
+ * always was.  With it on the pair is tested, in both modes; steps 1, 2, 5 and 6 and N0, N1 and N3 stand as written.  A capsule's
+ * half_extents are (r, h, .): parry's Capsule::new_y, the core segment (0, -h, 0) .. (0, +h, 0) of its frame swept by a ball of radius r.
+ *  Step 3 is unchanged: the shape cast of avian_mi355x_spatial.h, which defines the capsule cases ("capsule query shapes", "queries against
+ *     capsule colliders"), round cap included (at most 32 Newton evaluations, the last t standing).  By role: c1 a Ball or a Cuboid and c2 a
+ *     capsule: the capsule query's cast against that collider; c1 a capsule and c2 a Ball or a Cuboid: that query shape's cast against the
+ *     capsule collider; both capsules: the capsule query's cast against the capsule collider (Newton's iteration on the two cores).
+ *  Step 4 / N4: the contact at prediction 0 is the narrow phase's capsule manifold (avian_mi355x.h, "capsule colliders") with the cast shape as
+ *     shape 1.  The small ball against a capsule c1 is the Ball query's cast against the capsule collider in Linear mode, the advancement N3
+ *     with the capsule - ball gap below in NonLinear mode; against a Ball / Cuboid c1 (the capsule is c2) it is what it always was.
+ *  N2 for a pair with a capsule: the exact distance of the cores minus the radii, so the bound B of N3 is valid as written with
+ *     rho(capsule) = h + r (that sum, in this order).  Arithmetic as in N2 above; `core` of a capsule in its own frame: A = (0, -h, 0),
+ *     u = (0, h * 2, 0); of a capsule at the relative pose (q, t): hv = na_qrot(q, (0, h, 0)), A = t - hv, u = hv * 2.
+ *      capsule - ball: l = qrot(conj(q_c), p_b - p_c); s = clamp(na_dot(l - A, u) / na_dot(u, u), 0, 1) (0 when na_dot(u, u) == 0);
+ *        pc = A + u * s; df = l - pc; dist = length(df); g = dist - (r_c + r_b); nl = df / dist; n = qrot(q_c, nl) when the capsule is
+ *        collider 1, its negation when the ball is.
+ *      capsule - capsule: pos12 = iso_inv_mul((q_1, p_1), (q_2, p_2)); collider 1's core in its own frame as segment 1, collider 2's at pos12 as
+ *        segment 2; (d2, p1, p2) = the segment - segment distance of the spatial queries (six candidate pairs evaluated in full, the first
+ *        smallest wins); dist = sqrt(d2); g = dist - (r_1 + r_2); nl = (p2 - p1) / dist; n = na_qrot(q_1, nl).
+ *      capsule - cuboid: pos = iso_inv_mul((q_x, p_x), (q_c, p_c)) (the capsule in the cuboid's frame), its core at pos; (f, ps, pb) = the
+ *        segment - box routine of the spatial queries (ps on the core, pb = clamp(ps, -he, he)); dist = sqrt(f); g = dist - r;
+ *        nl = (ps - pb) / dist (box towards capsule); n = qrot(q_x, nl) when the cuboid is collider 1, its negation otherwise.
+ *      !(dist > 0) in any arm (a core point on the other core, in the ball's centre or in the box): g is as computed, minus the radius or
+ *        radii, and n = (0, 1, 0).  With tol >= 0 the round ends in a hit before n is used.
+ * A world whose collider table holds no capsule launches exactly the kernels it launches with the switch off and leaves the same bytes.
+ * NOT covered: shapes other than Ball / Cuboid / Capsule, child and host-shape colliders as targets, parity with parry's searches,
+ * level-2 / sharded worlds, the host-bookkeeping closed loop, 2D, Rust declarations.
  */
 #ifndef AVIAN_MI355X_CCD_H
 #define AVIAN_MI355X_CCD_H
@@ -140,6 +169,10 @@ AVN_API avn_status avn_swept_ccd_results_get(avn_world* w, avn_swept_ccd_results
 /* Whether avn_swept_ccd_upload accepts AVN_SWEEP_NON_LINEAR, per entry.  Sticky; off in a new world, where the upload refuses the mode as it
  * always has.  Turning it off while the list in force holds a NonLinear entry: AVN_ERR_STATE, the switch and the list unchanged. */
 AVN_API avn_status avn_swept_ccd_non_linear_set(avn_world* w, uint32_t enabled);
+/* Whether a pair with an AVN_SHAPE_CAPSULE collider on either side is tested ("capsule colliders" above), in both sweep modes.  Sticky; off in
+ * a new world, where such a pair is skipped as it always was.  May be toggled between steps at any time: it strands no state and takes effect
+ * from the next pass.  AVN_SHAPE_HOST and child colliders as targets stay declared deviations. */
+AVN_API avn_status avn_swept_ccd_capsules_set(avn_world* w, uint32_t enabled);
 /* The statistics of the last step's pass (waits for it); zeros if no pass has run since the list was uploaded. */
 AVN_API avn_status avn_swept_ccd_stats_get(avn_world* w, avn_swept_ccd_stats* out);
 

@@ -215,7 +215,7 @@
  *        h_c == 0 capsule collider answers more than a Ball collider does (a Ball's centre inside a cuboid query: no contact).  A capsule query
  *        against Ball / Cuboid colliders keeps its own contact above.
  *    A capsule collider with h_c == 0 answers what a Ball collider of radius r_c answers up to rounding (tests/test_spatial_capsule_colliders_cpu.py).
- *    NOT covered: swept CCD against capsule colliders, target_distance != 0, queries against AVN_SHAPE_HOST colliders.
+ *    NOT covered: target_distance != 0, queries against AVN_SHAPE_HOST colliders.
  *  - move and slide (MoveAndSlide::cast_move, project_velocity, move_and_slide; move_and_slide.rs:464-793, velocity_project.rs).  As above the
  *    definitions are written out here with their operation order (no FMA contraction); parity with glam / parry is UNPINNED.  Common rules:
  *      Sensors are never candidates (MoveAndSlide's collider query is Without<Sensor>; cast_move's predicate enforces it for the cast too).
@@ -344,7 +344,7 @@ extern "C" {
 /* A capsule (the segment (0, -h, 0) .. (0, +h, 0) swept by a ball of radius r; half_extents = (r, h, .)): a query-shape kind of this header and, on the HIP
  * backend, a collider kind (avian_mi355x.h "capsule colliders": avn_colliders_upload, avn_contact_manifolds).  The spatial queries of this header answer
  * against capsule COLLIDERS once avn_spatial_capsule_colliders_set has switched them in; by default a snapshot treats them as host shapes.  The swept
- * CCD skips them. */
+ * CCD tests them behind avn_swept_ccd_capsules_set (avian_mi355x_ccd.h) and skips them by default. */
 enum { AVN_SHAPE_CAPSULE = 3 };
 
 /* flags of a query */

@@ -11,6 +11,9 @@ usage: python tools/time_swept_ccd.py MODE [repeats]
   bullets_nolist  the same scene and shots without the list (what the steps cost when the bullets tunnel into the pile instead).
   bullets_nl      the same 1 000 bullets, spinning at (20, 0, 35) rad / s and listed with SweepMode::NonLinear (avn_swept_ccd_non_linear_set on):
                   per step also nonlinear_tested, rounds_max and exhausted of avn_swept_ccd_stats_get.
+  capsules        the same shots with 1 000 capsule bullets (AVN_SHAPE_CAPSULE, r = 0.1, h = 0.3, upright) and avn_swept_ccd_capsules_set on,
+                  SweepMode::Linear: the figures of `bullets`.
+  capsules_nl     the capsule bullets spinning at (20, 0, 35) rad / s, SweepMode::NonLinear: the figures of `bullets_nl`.
   ab OLDER [repeats]
                   a same-box A/B of `nolist` and `bullets` (1 000 Linear bullets) against an older build of the library (the parent commit's
                   libavian_mi355x.so): child processes, alternating older / this tree, `repeats` runs a side, the side that goes first alternating too.  Per leg one summary line: the
@@ -31,7 +34,7 @@ from avian_amd import _ffi as F, scenes
 SETTLE, WINDOW, N_BULLETS = 100, 100, 1000
 
 
-def tables(with_bullets):
+def tables(with_bullets, capsules=False):
     sc = scenes.box_stack(50, 40, 50)
     bodies, cols = sc.body_kwargs(), sc.collider_kwargs()
     n = sc.n
@@ -47,7 +50,10 @@ def tables(with_bullets):
         bodies = {key: np.concatenate([np.asarray(v), add[key]]) for key, v in bodies.items()}
         bodies["gravity_scale"] = np.concatenate([np.ones(n), np.zeros(k)])   # parked until they are fired
         he = np.zeros((k, 3)); he[:, 0] = 0.1
-        cols = dict(entity_index=np.arange(n + k, dtype=np.uint32), body=np.arange(n + k, dtype=np.int32), shape=np.concatenate([cols["shape"], np.full(k, F.SHAPE_BALL, np.uint8)]),
+        if capsules:
+            he[:, 1] = 0.3
+        cols = dict(entity_index=np.arange(n + k, dtype=np.uint32), body=np.arange(n + k, dtype=np.int32),
+                    shape=np.concatenate([cols["shape"], np.full(k, F.SHAPE_CAPSULE if capsules else F.SHAPE_BALL, np.uint8)]),
                     half_extents=np.concatenate([cols["half_extents"], he]), collider_flags=np.concatenate([np.zeros(n, np.uint8), np.full(k, F.COLLIDER_SWEPT_CCD, np.uint8)]),
                     speculative_margin=np.concatenate([np.full(n, -1.0), np.zeros(k)]))
         bullets = np.arange(n, n + k, dtype=np.uint32)
@@ -93,18 +99,20 @@ def main():
     if mode == "ab":
         return ab(sys.argv[2], int(sys.argv[3]) if len(sys.argv) > 3 else 3)
     repeats = int(sys.argv[2]) if len(sys.argv) > 2 else 5
-    with_bullets = mode.startswith("bullets")
+    capsules = mode.startswith("capsules")
+    with_bullets = mode.startswith("bullets") or capsules
+    non_linear = mode in ("bullets_nl", "capsules_nl")
     lib = avian_amd.load_library()
-    bodies, cols, n, bullets = tables(with_bullets)
+    bodies, cols, n, bullets = tables(with_bullets, capsules)
     w = F.World(lib, F.default_config(32, substeps=4))
     w.bodies_upload(**bodies); w.colliders_upload(**cols)
     w.existing_pairs_upload(np.zeros(0, np.uint64)); w.collider_materials_upload(friction=0.5)
     w.pipeline_enable()
     ccd = None
-    if mode in ("all", "bullets", "bullets_nl"):
+    if mode in ("all", "bullets", "bullets_nl", "capsules", "capsules_nl"):
         from avian_amd.swept_ccd import SWEEP_LINEAR, SWEEP_NON_LINEAR, SweptCcd
-        ccd = SweptCcd(w, non_linear=mode == "bullets_nl")
-        ccd.upload(bullets if with_bullets else np.arange(n, dtype=np.uint32), mode=SWEEP_NON_LINEAR if mode == "bullets_nl" else SWEEP_LINEAR)
+        ccd = SweptCcd(w, non_linear=non_linear, capsules=capsules)
+        ccd.upload(bullets if with_bullets else np.arange(n, dtype=np.uint32), mode=SWEEP_NON_LINEAR if non_linear else SWEEP_LINEAR)
     for _ in range(SETTLE):
         w.step()
     w.synchronize()
@@ -127,7 +135,7 @@ def main():
         for key in ("position", "rotation", "linear_velocity", "angular_velocity"):
             kw[key] = state[key].astype(np.float64)
         kw["linear_velocity"][bullets] = [0.0, -300.0, 0.0]
-        if mode == "bullets_nl":
+        if non_linear:
             kw["angular_velocity"][bullets] = [20.0, 0.0, 35.0]
         w.bodies_upload(**kw)
         rows = []
@@ -137,7 +145,7 @@ def main():
             if ccd is not None:
                 rec = ccd.results()
                 row.update(swept_ccd_ms=round(w.diagnostics().swept_ccd_ms, 4), tested=int(rec["tested"].sum()), hits=int((rec["hit_body"] >= 0).sum()))
-                if mode == "bullets_nl":
+                if non_linear:
                     row.update(ccd.stats())
             rows.append(row)
         out.update(steps=rows, lowest_bullet_y=round(float(w.bodies_download()["position"][bullets, 1].min()), 3))
