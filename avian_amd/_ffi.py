@@ -242,6 +242,16 @@ BROAD_PHASE_STATS_SYMBOLS = ("avn_broad_phase_stats_get",)   # a plain avn_ func
 SORT_FORM_NONE, SORT_FORM_ONE_WORKGROUP, SORT_FORM_TILES_MERGE, SORT_FORM_FUSED_RADIX, SORT_FORM_RADIX_SCAN = range(5)
 
 
+class avn_level_compaction_stats(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("state", C.c_uint32), ("why_off", C.c_uint32), ("colours", C.c_uint32), ("levels", C.c_uint32),
+                ("max_degree", C.c_uint32), ("moved", C.c_uint32), ("sizes", C.c_uint32 * 23),
+                ("overflow_first", C.c_uint32), ("overflow_count", C.c_uint32)]
+
+
+LEVELS_OFF, LEVELS_EARLY_OUT, LEVELS_COMPACTED = range(3)
+LEVELS_WHY_NONE, LEVELS_WHY_SWITCH, LEVELS_WHY_CLOSED_LOOP, LEVELS_WHY_LEVEL2, LEVELS_WHY_EMPTY = range(5)
+
+
 class avn_slab_in(C.Structure):
     _fields_ = [("n_colliders", C.c_uint32), ("aabb_min_x", vp), ("aabb_max_x", vp), ("prev_order", vp), ("n_prev", C.c_uint32),
                 ("n_ranks", C.c_uint32), ("rank", C.c_uint32)]
@@ -836,6 +846,16 @@ class World:
         fn = self.lib.dll.avn_broad_phase_stats_get
         fn.restype, fn.argtypes = C.c_int32, [vp, C.POINTER(avn_broad_phase_stats)]
         o = avn_broad_phase_stats(C.sizeof(avn_broad_phase_stats))
+        self._check(fn(self.handle, C.byref(o)))
+        return o
+
+    def level_compaction_stats(self) -> avn_level_compaction_stats:
+        """``avn_level_compaction_stats_get``: what the last manifolds_upload did with the colours (the product only)."""
+        if not hasattr(self.lib.dll, "avn_level_compaction_stats_get"):
+            raise ImportError(f"{self.lib.path} does not export avn_level_compaction_stats_get")
+        fn = self.lib.dll.avn_level_compaction_stats_get
+        fn.restype, fn.argtypes = C.c_int32, [vp, C.POINTER(avn_level_compaction_stats)]
+        o = avn_level_compaction_stats(C.sizeof(avn_level_compaction_stats))
         self._check(fn(self.handle, C.byref(o)))
         return o
 

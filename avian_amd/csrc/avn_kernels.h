@@ -381,7 +381,22 @@ template <class T> struct ManifoldStage {
     const T *normal, *friction, *restitution, *tangent_velocity, *anchor1, *anchor2, *penetration, *normal_speed, *warm_n, *warm_t;
     const uint8_t *point_count, *manifold_flags;
 };
-template <class T> void launch_pack_manifolds(const DW<T>&, const ManifoldStage<T>&, hipStream_t);
+// perm (nullable = identity): upload position -> position in the device arrays (level compaction, k_levels.hip); the unpack kernels take the same map
+template <class T> void launch_pack_manifolds(const DW<T>&, const ManifoldStage<T>&, const uint32_t* perm, hipStream_t);
+// k_levels.hip -- level compaction of an uploaded manifold set (world/manifolds.hpp: manifolds_upload)
+#define LVL_TILE 256   // manifolds per workgroup of the rank pass
+struct LevelOffsets { uint32_t o[AVN_GRAPH_COLOR_COUNT + 1]; };   // the uploaded colour offsets, by value
+uint32_t level_tiles(uint32_t n_manifolds);
+// result words behind the per-body arrays: [0..23) the offsets the solver runs, [23] moved, [24] the most colours on one ordering body
+#define LVL_RES_WORDS 32u
+#define LVL_RES_MOVED 23u
+#define LVL_RES_MAX_DEGREE 24u
+uint32_t level_zeroed_words(uint32_t n_bodies, uint32_t n_manifolds);   // `zeroed`: [mask n_bodies | next n_bodies | res LVL_RES_WORDS | scan state], zeroed by the caller on the same stream
+// every kernel of the compaction on one stream: masks, degree, one launch per populated colour, histogram, scan, ranks.  level[n_manifolds], hist[23 * level_tiles]: scratch;
+// perm[n_manifolds] and the res words: results (the early out -- degree == populated -- leaves the identity and the uploaded offsets).  Returns the launches made.
+uint32_t launch_level_build(const int32_t* body1, const int32_t* body2, uint32_t n_bodies, const LevelOffsets&, uint32_t populated,
+                            uint32_t* zeroed, uint8_t* level, uint32_t* hist, uint32_t* perm, hipStream_t);
+bool launch_level_unpermute(void* dst, const void* src, size_t elem_bytes, const uint32_t* perm, uint32_t n, hipStream_t);   // dst[m] = src[perm[m]]
 template <class T> struct JointStage {  // device staging copies of the avn_joints arrays (nullptr = absent)
     const uint8_t *joint_type, *limit_flags;
     const int32_t *body1, *body2;
@@ -406,13 +421,13 @@ template <class T> struct SolverBodiesStage {
     int16_t* dominance;
 };
 template <class T> void launch_unpack_solver_bodies(const DW<T>&, const SolverBodiesStage<T>&, hipStream_t);
-template <class T> void launch_unpack_impulses(const DW<T>&, T* warm_n, T* warm_t, T* normal_impulse, hipStream_t);
+template <class T> void launch_unpack_impulses(const DW<T>&, T* warm_n, T* warm_t, T* normal_impulse, const uint32_t* perm, hipStream_t);
 template <class T> struct ConstraintsStage {
     uint8_t *point_count, *softness_non_dynamic;
     int16_t* relative_dominance;
     T *tangent1, *anchor1, *initial_separation, *normal_impulse, *total_impulse, *normal_effective_mass, *tangent_impulse, *tangent_k;
 };
-template <class T> void launch_unpack_constraints(const DW<T>&, const ConstraintsStage<T>&, hipStream_t);
+template <class T> void launch_unpack_constraints(const DW<T>&, const ConstraintsStage<T>&, const uint32_t* perm, hipStream_t);
 template <class T> void launch_unpack_joints(const DW<T>&, T* r1, T* r2, T* cd, T* lag, T* force, T* rot_lag, T* torque, hipStream_t);
 template <class T> void launch_unpack_aabbs(const BP<T>&, T* mn, T* mx, uint32_t* interval_entities, hipStream_t);
 

@@ -9,6 +9,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <limits>
 #include <numeric>
 #include <chrono>
@@ -247,6 +248,7 @@ template <class T> struct World : WorldBase {
         if (h_pg_error) (void)hipHostFree(h_pg_error);
         for (hipEvent_t e : {ev_np_fork, ev_np_old, ev_slot_clear}) if (e) (void)hipEventDestroy(e);
         for (hipEvent_t e : {ev_side_fork, ev_side_done}) if (e) (void)hipEventDestroy(e);
+        for (hipEvent_t e : {ev_lvl_go, ev_lvl_done}) if (e) (void)hipEventDestroy(e);
         for (hipEvent_t e : {ev_adj, ev_adj_go}) if (e) (void)hipEventDestroy(e);
         if (stream_side) { (void)hipStreamSynchronize(stream_side); (void)hipStreamDestroy(stream_side); }
         if (stream) (void)hipStreamDestroy(stream);
@@ -374,6 +376,9 @@ template <class T> struct World : WorldBase {
         std::string& error;   // (HIPCHK's and ALLOC's)
         const bool direct;    // AVN_SPATIAL_DEVICE_POINTERS: in() / out() arrays are the caller's device pointers, used as they are
         avn_stage::Layout l;
+        // work that needs only the first arrays of an upload: run by commit() right after the copy of item `hook_after` is issued, in front of the remaining copies
+        int hook_after = -1;
+        std::function<avn_status()> hook;
         explicit StagePlan(World& w_, bool direct_ = false) : w(w_), error(w_.error), direct(direct_) {}
         // an input staged from the host whatever `direct` says
         template <class U> void staged(const void* host, size_t count, const U** dev) { l.add(avn_stage::IN, host, count, sizeof(U), (void**)dev); }
@@ -393,8 +398,10 @@ template <class T> struct World : WorldBase {
             if (w.stream_bp) HIPCHK(hipStreamSynchronize(w.stream_bp));
             ALLOC(w.stage.ensure(l.total + 4096));
             if (!l.assign(w.stage.p, w.stage.cap)) { error = "staging: the plan does not fit its arena"; return AVN_ERR_STATE; }
-            for (int i = 0; i < l.n; ++i)
+            for (int i = 0; i < l.n; ++i) {
                 if (l.item[i].dir == avn_stage::IN) HIPCHK(hipMemcpyAsync(*l.item[i].dev, l.item[i].host, l.item[i].bytes, hipMemcpyHostToDevice, w.stream));
+                if (i == hook_after && hook) { const avn_status sh = hook(); if (sh != AVN_OK) return sh; }
+            }
             return AVN_OK;
         }
         avn_status finish() {

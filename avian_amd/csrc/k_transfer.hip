@@ -51,24 +51,25 @@ __global__ __launch_bounds__(256) void k_pack_local_accelerations(Vec4<T>* lin, 
 }
 
 template <class T>
-__global__ __launch_bounds__(256) void k_pack_manifolds(DW<T> w, ManifoldStage<T> s) {
+__global__ __launch_bounds__(256) void k_pack_manifolds(DW<T> w, ManifoldStage<T> s, const uint32_t* __restrict__ perm) {
     uint32_t m = blockIdx.x * 256 + threadIdx.x;
     if (m >= w.n_manifolds) return;
-    w.m_bodies[m] = make_int2(s.body1[m], s.body2[m]);
-    w.m_n[m] = make4<T>(ld3(s.normal, m), s.friction[m]);
-    w.m_tv[m] = make4<T>(ld3(s.tangent_velocity, m), s.restitution[m]);
+    const uint32_t d = perm ? perm[m] : m;   // (level compaction: the staged arrays are in upload order, the device arrays level-major)
+    w.m_bodies[d] = make_int2(s.body1[m], s.body2[m]);
+    w.m_n[d] = make4<T>(ld3(s.normal, m), s.friction[m]);
+    w.m_tv[d] = make4<T>(ld3(s.tangent_velocity, m), s.restitution[m]);
     uint32_t np = s.point_count[m];
     uint32_t fl = s.manifold_flags ? s.manifold_flags[m] : (uint32_t)AVN_MANIFOLD_GENERATES_CONSTRAINTS;
-    w.m_meta[m] = np | (fl << 8);
+    w.m_meta[d] = np | (fl << 8);
     for (uint32_t k = 0; k < AVN_MAX_MANIFOLD_POINTS; ++k) {
         size_t src = 4 * (size_t)m + k;
-        size_t dst = (size_t)k * w.m_stride + m;
+        size_t dst = (size_t)k * w.m_stride + d;
         w.mp_a1[dst] = make4<T>(ld3(s.anchor1, src), s.penetration[src]);
         w.mp_a2[dst] = make4<T>(ld3(s.anchor2, src), s.normal_speed[src]);
         w.mp_w[dst] = make4<T>(s.warm_n ? s.warm_n[src] : T(0), s.warm_t ? s.warm_t[2 * src] : T(0), s.warm_t ? s.warm_t[2 * src + 1] : T(0), T(0));
     }
-    w.c_h1[m] = make4<T>(0, 0, 0, bits_to_scalar(0u, T(0)));  // no constraint until prepare runs
-    w.c_reldom[m] = 0;
+    w.c_h1[d] = make4<T>(0, 0, 0, bits_to_scalar(0u, T(0)));  // no constraint until prepare runs
+    w.c_reldom[d] = 0;
 }
 
 template <class T>
@@ -136,12 +137,13 @@ __global__ __launch_bounds__(256) void k_unpack_solver_bodies(DW<T> w, SolverBod
 }
 
 template <class T>
-__global__ __launch_bounds__(256) void k_unpack_impulses(DW<T> w, T* warm_n, T* warm_t, T* normal_impulse) {
+__global__ __launch_bounds__(256) void k_unpack_impulses(DW<T> w, T* warm_n, T* warm_t, T* normal_impulse, const uint32_t* __restrict__ perm) {
     uint32_t m = blockIdx.x * 256 + threadIdx.x;
     if (m >= w.n_manifolds) return;
+    const uint32_t d = perm ? perm[m] : m;   // rows come back in upload order
     for (uint32_t k = 0; k < AVN_MAX_MANIFOLD_POINTS; ++k) {
         size_t dst = 4 * (size_t)m + k;
-        Vec4<T> v = w.mp_w[(size_t)k * w.m_stride + m];
+        Vec4<T> v = w.mp_w[(size_t)k * w.m_stride + d];
         if (warm_n) warm_n[dst] = v.x;
         if (warm_t) { warm_t[2 * dst] = v.y; warm_t[2 * dst + 1] = v.z; }
         if (normal_impulse) normal_impulse[dst] = v.w;
@@ -149,18 +151,19 @@ __global__ __launch_bounds__(256) void k_unpack_impulses(DW<T> w, T* warm_n, T* 
 }
 
 template <class T>
-__global__ __launch_bounds__(256) void k_unpack_constraints(DW<T> w, ConstraintsStage<T> o) {
+__global__ __launch_bounds__(256) void k_unpack_constraints(DW<T> w, ConstraintsStage<T> o, const uint32_t* __restrict__ perm) {
     uint32_t m = blockIdx.x * 256 + threadIdx.x;
     if (m >= w.n_manifolds) return;
-    Vec4<T> h1 = w.c_h1[m];
+    const uint32_t d = perm ? perm[m] : m;   // rows come back in upload order
+    Vec4<T> h1 = w.c_h1[d];
     uint32_t cm = scalar_to_bits(h1.w), np = cm & 7u;
     if (o.point_count) o.point_count[m] = (uint8_t)np;
     if (np == 0) return;
-    if (o.relative_dominance) o.relative_dominance[m] = w.c_reldom[m];
+    if (o.relative_dominance) o.relative_dominance[m] = w.c_reldom[d];
     if (o.softness_non_dynamic) o.softness_non_dynamic[m] = (cm & AVN_CM_SOFT_ND) ? 1 : 0;
     st3(o.tangent1, m, xyz<T>(h1));
     for (uint32_t k = 0; k < np; ++k) {
-        size_t src = (size_t)k * w.m_stride + m, dst = 4 * (size_t)m + k;
+        size_t src = (size_t)k * w.m_stride + d, dst = 4 * (size_t)m + k;
         Vec4<T> a = w.c_pa[src], b = w.c_pb[src], c = w.c_pc[src], d = w.c_pd[src];
         st3(o.anchor1, dst, xyz<T>(a));
         if (o.initial_separation) o.initial_separation[dst] = a.w;
@@ -194,14 +197,14 @@ __global__ __launch_bounds__(256) void k_unpack_aabbs(BP<T> bp, T* mn, T* mx, ui
 
 static inline dim3 g256(uint32_t n) { return dim3((n + 255) / 256); }
 template <class T> void launch_pack_bodies(const DW<T>& w, const BodyStage<T>& s, hipStream_t st) { if (w.n_bodies) hipLaunchKernelGGL(k_pack_bodies<T>, g256(w.n_bodies), dim3(256), 0, st, w, s); }
-template <class T> void launch_pack_manifolds(const DW<T>& w, const ManifoldStage<T>& s, hipStream_t st) { if (w.n_manifolds) hipLaunchKernelGGL(k_pack_manifolds<T>, g256(w.n_manifolds), dim3(256), 0, st, w, s); }
+template <class T> void launch_pack_manifolds(const DW<T>& w, const ManifoldStage<T>& s, const uint32_t* perm, hipStream_t st) { if (w.n_manifolds) hipLaunchKernelGGL(k_pack_manifolds<T>, g256(w.n_manifolds), dim3(256), 0, st, w, s, perm); }
 template <class T> void launch_pack_joints(const DW<T>& w, const JointStage<T>& s, hipStream_t st) { if (w.n_joints) hipLaunchKernelGGL(k_pack_joints<T>, g256(w.n_joints), dim3(256), 0, st, w, s); }
 template <class T> void launch_pack_colliders(const BP<T>& bp, const ColliderStage<T>& s, hipStream_t st) { if (bp.n_colliders) hipLaunchKernelGGL(k_pack_colliders<T>, g256(bp.n_colliders), dim3(256), 0, st, bp, s); }
 template <class T> void launch_pack_local_accelerations(Vec4<T>* lin, Vec4<T>* ang, const T* s_lin, const T* s_ang, uint32_t n, hipStream_t st) { if (n) hipLaunchKernelGGL(k_pack_local_accelerations<T>, g256(n), dim3(256), 0, st, lin, ang, s_lin, s_ang, n); }
 template <class T> void launch_unpack_bodies(const DW<T>& w, T* p, T* r, T* l, T* a, hipStream_t st) { if (w.n_bodies) hipLaunchKernelGGL(k_unpack_bodies<T>, g256(w.n_bodies), dim3(256), 0, st, w, p, r, l, a); }
 template <class T> void launch_unpack_solver_bodies(const DW<T>& w, const SolverBodiesStage<T>& o, hipStream_t st) { if (w.n_bodies) hipLaunchKernelGGL(k_unpack_solver_bodies<T>, g256(w.n_bodies), dim3(256), 0, st, w, o); }
-template <class T> void launch_unpack_impulses(const DW<T>& w, T* a, T* b, T* c, hipStream_t st) { if (w.n_manifolds) hipLaunchKernelGGL(k_unpack_impulses<T>, g256(w.n_manifolds), dim3(256), 0, st, w, a, b, c); }
-template <class T> void launch_unpack_constraints(const DW<T>& w, const ConstraintsStage<T>& o, hipStream_t st) { if (w.n_manifolds) hipLaunchKernelGGL(k_unpack_constraints<T>, g256(w.n_manifolds), dim3(256), 0, st, w, o); }
+template <class T> void launch_unpack_impulses(const DW<T>& w, T* a, T* b, T* c, const uint32_t* perm, hipStream_t st) { if (w.n_manifolds) hipLaunchKernelGGL(k_unpack_impulses<T>, g256(w.n_manifolds), dim3(256), 0, st, w, a, b, c, perm); }
+template <class T> void launch_unpack_constraints(const DW<T>& w, const ConstraintsStage<T>& o, const uint32_t* perm, hipStream_t st) { if (w.n_manifolds) hipLaunchKernelGGL(k_unpack_constraints<T>, g256(w.n_manifolds), dim3(256), 0, st, w, o, perm); }
 template <class T> void launch_unpack_joints(const DW<T>& w, T* a, T* b, T* c, T* d, T* e, T* f, T* g, hipStream_t st) { if (w.n_joints) hipLaunchKernelGGL(k_unpack_joints<T>, g256(w.n_joints), dim3(256), 0, st, w, a, b, c, d, e, f, g); }
 template <class T> void launch_unpack_aabbs(const BP<T>& bp, T* mn, T* mx, uint32_t* ents, hipStream_t st) {
     uint32_t n = bp.n_colliders > bp.n_intervals ? bp.n_colliders : bp.n_intervals;
@@ -295,14 +298,14 @@ template <class T> void launch_dsh_unpack(const DW<T>& w, const uint32_t* bodies
 
 #define INST(T)                                                                                     \
     template void launch_pack_bodies<T>(const DW<T>&, const BodyStage<T>&, hipStream_t);            \
-    template void launch_pack_manifolds<T>(const DW<T>&, const ManifoldStage<T>&, hipStream_t);     \
+    template void launch_pack_manifolds<T>(const DW<T>&, const ManifoldStage<T>&, const uint32_t*, hipStream_t); \
     template void launch_pack_joints<T>(const DW<T>&, const JointStage<T>&, hipStream_t);           \
     template void launch_pack_colliders<T>(const BP<T>&, const ColliderStage<T>&, hipStream_t);     \
     template void launch_unpack_bodies<T>(const DW<T>&, T*, T*, T*, T*, hipStream_t);               \
     template void launch_pack_local_accelerations<T>(Vec4<T>*, Vec4<T>*, const T*, const T*, uint32_t, hipStream_t); \
     template void launch_unpack_solver_bodies<T>(const DW<T>&, const SolverBodiesStage<T>&, hipStream_t); \
-    template void launch_unpack_impulses<T>(const DW<T>&, T*, T*, T*, hipStream_t);                 \
-    template void launch_unpack_constraints<T>(const DW<T>&, const ConstraintsStage<T>&, hipStream_t); \
+    template void launch_unpack_impulses<T>(const DW<T>&, T*, T*, T*, const uint32_t*, hipStream_t); \
+    template void launch_unpack_constraints<T>(const DW<T>&, const ConstraintsStage<T>&, const uint32_t*, hipStream_t); \
     template void launch_unpack_joints<T>(const DW<T>&, T*, T*, T*, T*, T*, T*, T*, hipStream_t);           \
     template void launch_unpack_aabbs<T>(const BP<T>&, T*, T*, uint32_t*, hipStream_t);           \
     template void launch_dsh_set_foreign<T>(const DW<T>&, const int32_t*, uint32_t, hipStream_t);  \

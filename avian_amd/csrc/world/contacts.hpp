@@ -176,6 +176,7 @@
     void set_color_offsets(const uint32_t* offsets) {
         if (!use_handles && std::memcmp(color_offsets, offsets, sizeof color_offsets) != 0) graph_valid = false;  // (ranges captured as kernel arguments; handle mode reads them from the device)
         std::memcpy(color_offsets, offsets, sizeof color_offsets);
+        lvl_active = false;   // (whoever sets new ranges has new lists; manifolds_upload raises it again after a compaction)
         l2_built_for = 0xFFFFFFFFu;   // (level 2: the overflow colour's manifolds or its start may have changed under the same total count -- regroup by level)
         {
             const uint32_t n23 = color_offsets[AVN_COLOR_OVERFLOW_INDEX + 1] - color_offsets[AVN_COLOR_OVERFLOW_INDEX];

@@ -20,6 +20,7 @@
     uint32_t joint_slot_index() const { return (uint32_t)AVN_COLOR_OVERFLOW_INDEX + l2_levels; }
     bool is_joint_slot(uint32_t slot) const { return l2_joint_slot && slot == joint_slot_index(); }
     avn_status halo_joint_slot_set(uint32_t joint_slot, uint32_t global_joints) override {
+        { const avn_status sl = level_uncompact(); if (sl != AVN_OK) return sl; }   // (a level-2 world: colour order, world/manifolds.hpp)
         HIPCHK(hipStreamSynchronize(stream));
         l2_joint_slot = joint_slot != 0; l2_global_joints = global_joints != 0;
         halo = HaloPlan(); halo_on = false;   // (a plan uploaded before counted other slots)
@@ -29,6 +30,7 @@
     avn_status halo_overflow_levels_upload(uint32_t n_levels, const uint32_t* level_of, size_t count) override {
         if (count && !level_of) { error = "halo_overflow_levels_upload: null array"; return AVN_ERR_BAD_ARG; }
         for (size_t i = 0; i < count; ++i) if (level_of[i] >= std::max(n_levels, 1u)) { error = "halo_overflow_levels_upload: level out of range"; return AVN_ERR_BAD_ARG; }
+        { const avn_status sl = level_uncompact(); if (sl != AVN_OK) return sl; }
         HIPCHK(hipStreamSynchronize(stream));
         l2_levels = std::max(n_levels, 1u);
         l2_level_of.assign(level_of, level_of + count);
@@ -64,6 +66,7 @@
     std::vector<CommXfer> xf_send, xf_recv;
     avn_status halo_plan_upload(const avn_halo_plan* p) override {
         if (!p) { error = "halo_plan_upload: null plan"; return AVN_ERR_BAD_ARG; }
+        { const avn_status sl = level_uncompact(); if (sl != AVN_OK) return sl; }   // (also a plan without peers: a single rank of a level-2 plan addresses colours all the same)
         const size_t n = (size_t)halo_slots() * p->n_peers;
         if (p->n_peers && (!p->peer_rank || !p->send_offsets || !p->recv_offsets)) { error = "halo_plan_upload: null array"; return AVN_ERR_BAD_ARG; }
         HaloPlan h;
@@ -142,6 +145,7 @@
         if (pass < 0) { error = "run_color_pass: not a contact pass"; return AVN_ERR_BAD_ARG; }
         avn_status st = need_bodies();
         if (st != AVN_OK) return st;
+        if ((st = level_uncompact()) != AVN_OK) return st;   // `color` names one of the host's colours
         if ((st = rebuild_incidence()) != AVN_OK) return st;
         if (pass == PASS_RESTITUTION_ && !any_restitution) return AVN_OK;
         if ((st = color_pass_enqueue(pass, color)) != AVN_OK) return st;
@@ -196,6 +200,7 @@
         return AVN_OK;
     }
     avn_status comm_init(const uint8_t* unique_id, int n_ranks, int rank) override {
+        { const avn_status sl = level_uncompact(); if (sl != AVN_OK) return sl; }   // (a rank of several exchanges colour by colour)
         HIPCHK(hipStreamSynchronize(stream));
         return comm.init(unique_id, n_ranks, rank, error);
     }

@@ -2,6 +2,88 @@
 // host-uploaded manifolds, the warm start's incidence, island blocks, impulse / constraint read-back.
 
     // ---- manifolds ---------------------------------------------------------------------------------------
+    // Level compaction (k_levels.hip): the upload regroups colours 0..22 into the levels of the per-body order the colouring
+    // fixes.  The device arrays and color_offsets are then level-major; lvl_perm maps an upload position to its device position, and every
+    // reader of manifold-indexed data behind the ABI goes through it (the unpack kernels) or sees host copies already translated (h_m_body1/2).
+    DevBuf b_lvl_perm;
+    bool lvl_active = false;                 // the manifolds on the device are level-major (lvl_perm valid); cleared by every set_color_offsets
+    bool lvl_level2 = false;                 // the level-2 / per-colour API was used on this world: ranks must agree on the colours -- never compact again
+#ifdef AVN_MEASURE
+    bool lvl_enabled = avn_env("AVN_NO_LEVEL_COMPACTION") == nullptr;   // (A/B, and the tests' second reference: colour launches as before)
+#else
+    static constexpr bool lvl_enabled = true;
+#endif
+    uint32_t lvl_uploaded_offsets[AVN_GRAPH_COLOR_COUNT + 1] = {0};     // the colour offsets of the last manifolds_upload, as the host sent them
+    Pinned pin_lvl;                          // the result words of an upload's compaction (LVL_RES_*), read back with the synchronisation the upload ends with
+    hipEvent_t ev_lvl_go = nullptr, ev_lvl_done = nullptr;   // body1 / body2 are on the device -> the level kernels on the second stream -> k_pack_manifolds
+    avn_level_compaction_stats lvl_stats{};
+    const uint32_t* lvl_perm() const { return lvl_active ? b_lvl_perm.as<uint32_t>() : nullptr; }
+    void lvl_note(uint32_t state, uint32_t why, const uint32_t* uploaded, const uint32_t* now, uint32_t max_degree, uint32_t moved) {
+        lvl_stats = avn_level_compaction_stats{};
+        lvl_stats.state = state; lvl_stats.why_off = why; lvl_stats.max_degree = max_degree; lvl_stats.moved = moved;
+        for (int c = 0; c < AVN_COLOR_OVERFLOW_INDEX; ++c) {
+            lvl_stats.colours += uploaded[c + 1] > uploaded[c] ? 1u : 0u;
+            lvl_stats.sizes[c] = now[c + 1] - now[c];
+            lvl_stats.levels += lvl_stats.sizes[c] ? 1u : 0u;
+        }
+    }
+    avn_status level_compaction_stats_get(avn_level_compaction_stats* out) override {
+        if (!out || out->struct_size != sizeof(avn_level_compaction_stats)) { error = "level_compaction_stats_get: null argument or struct_size"; return AVN_ERR_BAD_ARG; }
+        *out = lvl_stats;
+        if (pipe_on || use_handles) {   // the lists are the bookkeeping's, not an upload's: answered from the ranges as they are, nothing is stored
+            *out = avn_level_compaction_stats{};
+            out->why_off = AVN_LEVELS_WHY_CLOSED_LOOP;
+            for (int c = 0; c < AVN_COLOR_OVERFLOW_INDEX; ++c) { out->sizes[c] = color_offsets[c + 1] - color_offsets[c]; out->colours += out->sizes[c] ? 1u : 0u; }
+            out->levels = out->colours;
+        }
+        out->overflow_first = color_offsets[AVN_COLOR_OVERFLOW_INDEX]; out->overflow_count = color_offsets[AVN_COLOR_OVERFLOW_INDEX + 1] - color_offsets[AVN_COLOR_OVERFLOW_INDEX];
+        out->struct_size = (uint32_t)sizeof(avn_level_compaction_stats);
+        return AVN_OK;
+    }
+    // The level-2 / per-colour API (halo plan, overflow levels, joint slot, run_color_pass, comm_init) addresses the host's COLOURS: from its first
+    // use on the world stays in colour order, and a set that was compacted before is put back (every manifold-indexed array, upload order).
+    avn_status level_uncompact() {
+        lvl_level2 = true;
+        if (!lvl_active) {
+            if (lvl_stats.state != AVN_LEVELS_OFF) lvl_note(AVN_LEVELS_OFF, AVN_LEVELS_WHY_LEVEL2, color_offsets, color_offsets, 0u, 0u);   // (an early-out set is in colour order already)
+            return AVN_OK;
+        }
+        const uint32_t M = dw.n_manifolds;
+        const uint32_t* perm = b_lvl_perm.as<uint32_t>();
+        HIPCHK(hipStreamSynchronize(stream));
+        if (stream_bp) HIPCHK(hipStreamSynchronize(stream_bp));
+        DevBuf tmp;
+        ALLOC(tmp.ensure((size_t)M * sizeof(V)));
+        auto put_back = [&](void* arr, size_t elem, uint32_t planes) -> hipError_t {
+            for (uint32_t k = 0; k < planes; ++k) {
+                char* a = (char*)arr + (size_t)k * dw.m_stride * elem;
+                if (!launch_level_unpermute(tmp.p, a, elem, perm, M, stream)) return hipErrorInvalidValue;
+                hipError_t e = hipMemcpyAsync(a, tmp.p, (size_t)M * elem, hipMemcpyDeviceToDevice, stream);
+                if (e != hipSuccess) return e;
+            }
+            return hipSuccess;
+        };
+        HIPCHK(put_back(dw.m_bodies, sizeof(int2), 1)); HIPCHK(put_back(dw.m_n, sizeof(V), 1)); HIPCHK(put_back(dw.m_tv, sizeof(V), 1)); HIPCHK(put_back(dw.m_meta, 4, 1));
+        HIPCHK(put_back(dw.mp_a1, sizeof(V), 4)); HIPCHK(put_back(dw.mp_a2, sizeof(V), 4)); HIPCHK(put_back(dw.mp_w, sizeof(V), 4));
+        HIPCHK(put_back(dw.c_h1, sizeof(V), 1)); HIPCHK(put_back(dw.c_pa, sizeof(V), 4)); HIPCHK(put_back(dw.c_pb, sizeof(V), 4)); HIPCHK(put_back(dw.c_pc, sizeof(V), 4));
+        HIPCHK(put_back(dw.c_pd, sizeof(V), 4)); HIPCHK(put_back(dw.c_reldom, sizeof(int16_t), 1));
+        HIPCHK(hipMemcpyAsync(dw.color_offsets, lvl_uploaded_offsets, sizeof lvl_uploaded_offsets, hipMemcpyHostToDevice, stream));
+        if (h_m_body1.size() == M && lvl_host_translated) {   // the host copies back into upload order as well
+            std::vector<uint32_t> hp(M);
+            HIPCHK(hipMemcpyAsync(hp.data(), perm, (size_t)M * 4, hipMemcpyDeviceToHost, stream));
+            HIPCHK(hipStreamSynchronize(stream));
+            std::vector<int32_t> a(M), b(M);
+            for (uint32_t i = 0; i < M; ++i) { a[i] = h_m_body1[hp[i]]; b[i] = h_m_body2[hp[i]]; }
+            h_m_body1.swap(a); h_m_body2.swap(b);
+        }
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipStreamSynchronize(stream));
+        set_color_offsets(lvl_uploaded_offsets);   // (clears lvl_active; the captured ranges differ: re-capture)
+        lvl_note(AVN_LEVELS_OFF, AVN_LEVELS_WHY_LEVEL2, color_offsets, color_offsets, 0u, 0u);
+        graph_valid = false; incidence_dirty = true;
+        return AVN_OK;
+    }
+    bool lvl_host_translated = false;   // h_m_body1 / h_m_body2 are in device order (sets small enough for the island blocks, whose entry lists are host-built)
     avn_status manifolds_upload(const avn_manifolds* m) override {
         if (!have_bodies) { error = "manifolds_upload before bodies_upload"; return AVN_ERR_STATE; }
         if (!m || !m->color_offsets || (m->count && (!m->body1 || !m->body2 || !m->normal || !m->friction || !m->restitution || !m->point_count ||
@@ -14,23 +96,67 @@
             if (m->color_offsets[c] > m->color_offsets[c + 1]) { error = "manifolds_upload: color_offsets not monotone"; return AVN_ERR_BAD_ARG; }
         if (use_handles) graph_valid = false;
         use_handles = false;  // the manifolds come from the host again
+        lvl_active = false;   // (the permutation describes the previous set: an upload that fails half way must not leave it in force)
         avn_status st0 = ensure_manifold_capacity(M);
         if (st0 != AVN_OK) return st0;
         if (dw.n_manifolds != M) graph_valid = false;
         dw.n_manifolds = M;
-        set_color_offsets(m->color_offsets);
+        // level compaction: wanted unless the world's lists are not host manifolds, it is a level-2 rank, or there is nothing to regroup
+        uint32_t populated = 0;
+        for (int c = 0; c < AVN_COLOR_OVERFLOW_INDEX; ++c) populated += m->color_offsets[c + 1] > m->color_offsets[c] ? 1u : 0u;
+        const uint32_t why_off = !lvl_enabled ? AVN_LEVELS_WHY_SWITCH : (pipe_on || pipe_dev) ? AVN_LEVELS_WHY_CLOSED_LOOP : (lvl_level2 || halo_on) ? AVN_LEVELS_WHY_LEVEL2
+                                 : populated == 0 ? AVN_LEVELS_WHY_EMPTY : AVN_LEVELS_WHY_NONE;
+        const bool lvl_try = why_off == AVN_LEVELS_WHY_NONE && populated >= 2;   // (one colour: one launch either way -- the early out, known without a reduction)
+        std::memcpy(lvl_uploaded_offsets, m->color_offsets, sizeof lvl_uploaded_offsets);
+        lvl_host_translated = false;
+        // (one set_color_offsets per upload, with the offsets the solver will run: a host that re-sends a settled pile's manifolds every step keeps its captured graph)
+        if (!lvl_try) {
+            set_color_offsets(m->color_offsets);
+            lvl_note(why_off == AVN_LEVELS_WHY_NONE ? AVN_LEVELS_EARLY_OUT : AVN_LEVELS_OFF, why_off, m->color_offsets, m->color_offsets, 0u, 0u);
+        }
         ManifoldStage<T> s;
         std::memset(&s, 0, sizeof s);
         StagePlan plan(*this);
-        SIN(body1, m->body1, M); SIN(body2, m->body2, M); SIN(normal, m->normal, 3 * (size_t)M);
+        // The level kernels need body1 / body2 only, the first two of the fourteen arrays: they run on the second stream behind an event recorded after those two copies,
+        // under the remaining copies and the host's pass below; k_pack_manifolds waits for their event, and the early out is decided on the device (k_level_scatter).  No
+        // host synchronisation but the one the upload ends with.
+        uint32_t *lvl_zeroed = nullptr, *lvl_hist = nullptr; uint8_t* lvl_level = nullptr;
+        const uint32_t nb_ = dw.n_bodies;
+        LevelOffsets lo;
+        std::memcpy(lo.o, lvl_uploaded_offsets, sizeof lo.o);
+        if (lvl_try) {
+            plan.scratch((size_t)level_zeroed_words(nb_, M), &lvl_zeroed); plan.scratch((size_t)AVN_COLOR_OVERFLOW_INDEX * level_tiles(M), &lvl_hist); plan.scratch((size_t)M, &lvl_level);
+            ALLOC(b_lvl_perm.ensure((size_t)M * 4));
+            ALLOC(pin_lvl.ensure(LVL_RES_WORDS * 4));
+            if (!ev_lvl_go) { HIPCHK(hipEventCreateWithFlags(&ev_lvl_go, hipEventDisableTiming | EV_FLAGS)); HIPCHK(hipEventCreateWithFlags(&ev_lvl_done, hipEventDisableTiming | EV_FLAGS)); }
+        }
+        SIN(body1, m->body1, M); SIN(body2, m->body2, M);
+        if (lvl_try) {
+            plan.hook_after = plan.l.n - 1;
+            // (the hook only marks the place in the stream: the chain's two dozen launches are enqueued once every copy is on its way -- enqueued here they held the
+            //  remaining copies back by their host time, 0.1 ms of a 1 ms upload)
+            plan.hook = [&]() -> avn_status { HIPCHK(hipEventRecord(ev_lvl_go, stream)); return AVN_OK; };
+        }
+        SIN(normal, m->normal, 3 * (size_t)M);
         SIN(friction, m->friction, M); SIN(restitution, m->restitution, M); SIN(tangent_velocity, m->tangent_velocity, 3 * (size_t)M);
         SIN(point_count, m->point_count, M); SIN(manifold_flags, m->manifold_flags, M);
         SIN(anchor1, m->anchor1, 12 * (size_t)M); SIN(anchor2, m->anchor2, 12 * (size_t)M);
         SIN(penetration, m->penetration, 4 * (size_t)M); SIN(normal_speed, m->normal_speed, 4 * (size_t)M);
         SIN(warm_n, m->warm_start_normal_impulse, 4 * (size_t)M); SIN(warm_t, m->warm_start_tangent_impulse, 8 * (size_t)M);
         COMMIT(plan);
-        HIPCHK(hipMemcpyAsync(dw.color_offsets, color_offsets, sizeof color_offsets, hipMemcpyHostToDevice, stream));
-        launch_pack_manifolds<T>(dw, s, stream);
+        HIPCHK(hipMemcpyAsync(dw.color_offsets, lvl_uploaded_offsets, sizeof lvl_uploaded_offsets, hipMemcpyHostToDevice, stream));
+        uint32_t* lvl_res = lvl_try ? lvl_zeroed + 2 * (size_t)nb_ : nullptr;
+        if (lvl_try) {
+            HIPCHK(hipStreamWaitEvent(stream_bp, ev_lvl_go, 0));
+            HIPCHK(hipMemsetAsync(lvl_zeroed, 0, (size_t)level_zeroed_words(nb_, M) * 4, stream_bp));
+            launches += launch_level_build(s.body1, s.body2, nb_, lo, populated, lvl_zeroed, lvl_level, lvl_hist, b_lvl_perm.as<uint32_t>(), stream_bp);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipEventRecord(ev_lvl_done, stream_bp));
+            HIPCHK(hipStreamWaitEvent(stream, ev_lvl_done, 0));
+            HIPCHK(hipMemcpyAsync(dw.color_offsets, lvl_res, AVN_COLOR_OVERFLOW_INDEX * 4, hipMemcpyDeviceToDevice, stream));   // (the ranges of colours 0..22 as the device decided them)
+            HIPCHK(hipMemcpyAsync(pin_lvl.p, lvl_res, LVL_RES_WORDS * 4, hipMemcpyDeviceToHost, stream));
+        }
+        launch_pack_manifolds<T>(dw, s, lvl_try ? b_lvl_perm.as<uint32_t>() : nullptr, stream);
         HIPCHK(hipGetLastError());
         // (while the copies run) one pass over the host arrays: range checks, "any restitution", and the host copy of the ContactPair bodies (incidence CSR source)
         {
@@ -51,12 +177,32 @@
                 uint32_t zero[AVN_GRAPH_COLOR_COUNT + 1] = {0};
                 dw.n_manifolds = 0; h_m_body1.clear(); h_m_body2.clear();
                 set_color_offsets(zero);
+                lvl_note(AVN_LEVELS_OFF, AVN_LEVELS_WHY_EMPTY, zero, zero, 0u, 0u);
                 HIPCHK(hipMemcpyAsync(dw.color_offsets, zero, sizeof zero, hipMemcpyHostToDevice, stream));
                 HIPCHK(hipStreamSynchronize(stream));
                 graph_valid = false; incidence_dirty = true;
                 error = bad_body ? "manifolds_upload: body index out of range" : "manifolds_upload: point_count > 4";
                 return AVN_ERR_BAD_ARG;
             }
+        }
+        if (lvl_try) {
+            std::vector<uint32_t> hp;
+            if (M <= island_max_manifolds) {   // (island_candidate's bound on the set, whatever bodies are uploaded later: the island-block builder reads the host copies by device position)
+                hp.resize(M);
+                HIPCHK(hipMemcpyAsync(hp.data(), b_lvl_perm.p, (size_t)M * 4, hipMemcpyDeviceToHost, stream));
+            }
+            HIPCHK(hipStreamSynchronize(stream));   // the synchronisation every upload ends with
+            const uint32_t* r = (const uint32_t*)pin_lvl.p;
+            uint32_t now[AVN_GRAPH_COLOR_COUNT + 1];
+            std::memcpy(now, lvl_uploaded_offsets, sizeof now);
+            std::memcpy(now, r, AVN_COLOR_OVERFLOW_INDEX * 4);
+            const uint32_t max_degree = r[LVL_RES_MAX_DEGREE], moved = r[LVL_RES_MOVED];
+            const bool early = max_degree == populated;   // (k_level_scatter's own test: it left the identity and the uploaded offsets)
+            set_color_offsets(now);
+            lvl_active = !early;
+            lvl_note(early ? AVN_LEVELS_EARLY_OUT : AVN_LEVELS_COMPACTED, AVN_LEVELS_WHY_NONE, lvl_uploaded_offsets, now, max_degree, moved);
+            lvl_host_translated = !early && !hp.empty();
+            if (lvl_host_translated) for (uint32_t i = 0; i < M; ++i) { h_m_body1[hp[i]] = m->body1[i]; h_m_body2[hp[i]] = m->body2[i]; }
         }
         incidence_dirty = true;
         HIPCHK(hipStreamSynchronize(stream));
@@ -315,7 +461,7 @@
         plan.out(o->warm_start_normal_impulse, 4 * M, &a); plan.out(o->warm_start_tangent_impulse, 8 * M, &b);
         plan.out(o->normal_impulse, 4 * M, &c);
         COMMIT(plan);
-        launch_unpack_impulses<T>(dw, a, b, c, stream);
+        launch_unpack_impulses<T>(dw, a, b, c, lvl_perm(), stream);
         HIPCHK(hipGetLastError());
         FINISH(plan);
         HIPCHK(hipStreamSynchronize(stream));
@@ -334,7 +480,7 @@
         SOUT(tangent_k, o->tangent_effective_inverse_mass, 12 * M);
         COMMIT(plan);
         if (plan.bytes()) HIPCHK(hipMemsetAsync(stage.p, 0, plan.bytes(), stream));  // absent constraints read back as zeros
-        launch_unpack_constraints<T>(dw, s, stream);
+        launch_unpack_constraints<T>(dw, s, lvl_perm(), stream);
         HIPCHK(hipGetLastError());
         FINISH(plan);
         HIPCHK(hipStreamSynchronize(stream));

@@ -1252,6 +1252,36 @@ typedef struct avn_broad_phase_stats {
 } avn_broad_phase_stats;
 AVN_API avn_status avn_broad_phase_stats_get(avn_world* w, avn_broad_phase_stats* out);
 
+/* ---- what the last avn_manifolds_upload did with the colours (inspection; the product only) -------------------------------------------------
+ * The solver launches once per populated range of colour_offsets[0..23).  The upload regroups colours 0..22 into the LEVELS of the order the
+ * colouring fixes per body (overflow list first, then colours in order): level(m) = max over m's ordering bodies of next[body], then
+ * next[body] = level(m) + 1.  Every body sees the same sequence of manifolds, so results are bit-identical, in as few launches as the deepest
+ * body allows.  A body orders unless two manifolds of one colour 0..22 name it (the host coloured it as static).  Rows of avn_impulses_download and
+ * avn_constraints_download stay in upload order.  Off (state 0) for the closed loop, for a world that uses the level-2 / per-colour API
+ * (avn_halo_*, avn_run_color_pass, avn_comm_init: ranks must agree on the colours -- a set compacted before such a call is put back into colour
+ * order by it) and with AVN_NO_LEVEL_COMPACTION in the measure build. */
+#define AVN_LEVELS_OFF 0u          /* colour launches, as uploaded */
+#define AVN_LEVELS_EARLY_OUT 1u    /* populated colours == the most colours on one ordering body: nothing to gain, set left as uploaded */
+#define AVN_LEVELS_COMPACTED 2u
+#define AVN_LEVELS_WHY_NONE 0u
+#define AVN_LEVELS_WHY_SWITCH 1u       /* AVN_NO_LEVEL_COMPACTION (measure build) */
+#define AVN_LEVELS_WHY_CLOSED_LOOP 2u  /* avn_pipeline_enable / manifold handles: the lists are not host-uploaded manifolds */
+#define AVN_LEVELS_WHY_LEVEL2 3u       /* level-2 / per-colour API in use */
+#define AVN_LEVELS_WHY_EMPTY 4u        /* no manifold in colours 0..22 */
+typedef struct avn_level_compaction_stats {
+    uint32_t struct_size;      /* in: sizeof(avn_level_compaction_stats) */
+    uint32_t state;            /* AVN_LEVELS_* */
+    uint32_t why_off;          /* AVN_LEVELS_WHY_* (state == AVN_LEVELS_OFF) */
+    uint32_t colours;          /* populated colours among 0..22 of the uploaded set */
+    uint32_t levels;           /* populated launch ranges among 0..22 the solver now runs (== colours unless compacted) */
+    uint32_t max_degree;       /* most colours on one ordering body (0 when not computed: state off) */
+    uint32_t moved;            /* 1: some manifold sits at another position than it was uploaded at */
+    uint32_t sizes[23];        /* manifolds per launch range 0..22 */
+    uint32_t overflow_first;   /* where the overflow list starts in the device arrays, and how many it holds: never moved by the upload */
+    uint32_t overflow_count;
+} avn_level_compaction_stats;
+AVN_API avn_status avn_level_compaction_stats_get(avn_world* w, avn_level_compaction_stats* out);
+
 #ifdef __cplusplus
 }
 #endif
