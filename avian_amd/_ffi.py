@@ -252,6 +252,20 @@ LEVELS_OFF, LEVELS_EARLY_OUT, LEVELS_COMPACTED = range(3)
 LEVELS_WHY_NONE, LEVELS_WHY_SWITCH, LEVELS_WHY_CLOSED_LOOP, LEVELS_WHY_LEVEL2, LEVELS_WHY_EMPTY = range(5)
 
 
+class avn_solver_forms(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("colour_form", C.c_uint32 * 23), ("colour_grid_blocks", C.c_uint32 * 23), ("restitution_colour_form", C.c_uint32 * 23),
+                ("colour_ranges_from", C.c_uint32), ("overflow_form", C.c_uint32), ("overflow_components", C.c_uint32), ("overflow_levels", C.c_uint32),
+                ("overflow_grid_blocks", C.c_uint32), ("island_blocks", C.c_uint32), ("island_cache_records", C.c_uint32), ("warm_start_form", C.c_uint32),
+                ("graph_captures", C.c_uint32), ("graph_replays", C.c_uint32)]
+
+
+FORM_NONE, COLOUR_FORM_LANE, COLOUR_FORM_OCT = range(3)
+RANGES_FROM_ARGUMENTS, RANGES_FROM_DEVICE = 1, 2
+OVERFLOW_FORM_COMPONENT, OVERFLOW_FORM_LEVEL, OVERFLOW_FORM_DATAFLOW, OVERFLOW_FORM_DATAFLOW_TAG = 1, 2, 3, 4
+WARM_START_FORM_LANE, WARM_START_FORM_QUADS, WARM_START_FORM_COLOURS = 1, 2, 3
+SOLVER_FORMS_SYMBOLS = ("solver_forms_get",)   # prefixed like the ABI (the oracle answers it too) but not part of ABI_SYMBOLS: a library built before it existed still loads
+
+
 class avn_slab_in(C.Structure):
     _fields_ = [("n_colliders", C.c_uint32), ("aabb_min_x", vp), ("aabb_max_x", vp), ("prev_order", vp), ("n_prev", C.c_uint32),
                 ("n_ranks", C.c_uint32), ("rank", C.c_uint32)]
@@ -856,6 +870,17 @@ class World:
         fn = self.lib.dll.avn_level_compaction_stats_get
         fn.restype, fn.argtypes = C.c_int32, [vp, C.POINTER(avn_level_compaction_stats)]
         o = avn_level_compaction_stats(C.sizeof(avn_level_compaction_stats))
+        self._check(fn(self.handle, C.byref(o)))
+        return o
+
+    def solver_forms(self) -> avn_solver_forms:
+        """``avn_solver_forms_get``: which form of the contact solve the last enqueued or captured substep loop holds (the oracle: all "none")."""
+        name = self.lib.prefix + SOLVER_FORMS_SYMBOLS[0]
+        if not hasattr(self.lib.dll, name):
+            raise ImportError(f"{self.lib.path} does not export {name}")
+        fn = getattr(self.lib.dll, name)
+        fn.restype, fn.argtypes = C.c_int32, [vp, C.POINTER(avn_solver_forms)]
+        o = avn_solver_forms(C.sizeof(avn_solver_forms))
         self._check(fn(self.handle, C.byref(o)))
         return o
 

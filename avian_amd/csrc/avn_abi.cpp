@@ -67,6 +67,7 @@ AVN_API avn_status avn_pairs_get(avn_world* w, const avn_pair** o, size_t* n) { 
 AVN_API avn_status avn_aabbs_download(avn_world* w, void* mn, void* mx, uint32_t* e, size_t* n) { GUARD(aabbs_download(mn, mx, e, n)); }
 AVN_API avn_status avn_broad_phase_stats_get(avn_world* w, avn_broad_phase_stats* out) { GUARD(broad_phase_stats_get(out)); }
 AVN_API avn_status avn_level_compaction_stats_get(avn_world* w, avn_level_compaction_stats* out) { GUARD(level_compaction_stats_get(out)); }
+AVN_API avn_status avn_solver_forms_get(avn_world* w, avn_solver_forms* out) { GUARD(solver_forms_get(out)); }
 AVN_API avn_status avn_run_system(avn_world* w, avn_system s) { GUARD_MUT(run_system(s)); }
 AVN_API avn_status avn_step(avn_world* w) { GUARD(step()); }
 AVN_API avn_status avn_synchronize(avn_world* w) { GUARD(synchronize()); }

@@ -105,7 +105,8 @@ template <class T> void launch_prepare_contact_constraints(const DW<T>&, const S
                                                            const RowsView<T>* rows = nullptr /* handle mode: read the ContactGraph side from the table (no k_gather_manifolds) */);
 template <class T> void launch_store_contact_impulses(const DW<T>&, hipStream_t);
 // body-centric warm start over the incidence CSR (DW::inc_off / inc_ent), optionally preceded by integrate_velocities
-template <class T> void launch_body_warm_start(const DW<T>&, const StepParams<T>&, bool fuse_integrate_velocities, bool quads /* four lanes per body: the device closed loop */, hipStream_t);
+// returns the form it launched (AVN_WARM_START_FORM_*; AVN_FORM_NONE without bodies): avn_solver_forms::warm_start_form
+template <class T> uint32_t launch_body_warm_start(const DW<T>&, const StepParams<T>&, bool fuse_integrate_velocities, bool quads /* four lanes per body: the device closed loop */, hipStream_t);
 // (re)build DW::inc_slot from DW::m_bodies / color_offsets (memset + one kernel)
 template <class T> void launch_build_incidence_slots(const DW<T>&, hipStream_t, bool cleared = false /* the table has been set to EMPTY already */);
 uint32_t color_grid_blocks(uint32_t count);
@@ -117,7 +118,9 @@ struct OverflowSchedule {
 // grid_blocks[c] = captured grid of colour c (0 = colour skipped); arg_offsets: the 25 colour offsets to pass in the kernel
 // arguments, or nullptr = the kernels read the live ranges from DW::color_offsets; returns the number of launches issued
 // oct_mask: bit c = colour c runs the eight-lanes-per-manifold kernel (f32 biased solve / relax only; bit-identical: a scheduling choice)
-template <class T> uint32_t launch_contact_pass(const DW<T>&, const StepParams<T>&, int pass, const uint32_t* grid_blocks, const uint32_t* arg_offsets, const OverflowSchedule&, hipStream_t, uint32_t oct_mask = 0u);
+// forms: where to write down what was launched (avn_solver_forms_get: the colour forms and grids, where the ranges come from, the overflow form), or nullptr
+template <class T> uint32_t launch_contact_pass(const DW<T>&, const StepParams<T>&, int pass, const uint32_t* grid_blocks, const uint32_t* arg_offsets, const OverflowSchedule&, hipStream_t, uint32_t oct_mask = 0u,
+                                                avn_solver_forms* forms = nullptr);
 // Island blocks (k_island_substeps): block b owns bodies[body_off[b] .. body_off[b+1]) (world body indices; LDS slot = position in
 // the range) and, per colour slot (0 = the overflow colour, 1 + c = colour c: solve order), the entries
 // ent[col_off[24 b + slot] .. col_off[24 b + slot + 1]) = (manifold index, LDS slot of body1 | LDS slot of body2 << 16); a side
@@ -335,7 +338,8 @@ struct OverflowFlow { const uint32_t* rank; /* [2 n23] rank of the manifold amon
 template <class T> void launch_ovf_entries(const DW<T>&, uint32_t o0, uint32_t n23, uint32_t* keys, uint32_t* vals, hipStream_t);
 template <class T> void launch_ovf_csr(const DW<T>&, uint32_t o0, uint32_t n23, const uint32_t* keys, const uint32_t* vals, uint32_t* inc_off, uint32_t* inc_ent, uint32_t* rank, hipStream_t);
 void launch_overflow_reset(uint32_t* ticket, uint32_t n_ticket, uint32_t* tiles, uint32_t n_tiles, hipStream_t);
-template <class T> void launch_overflow_flow(const DW<T>&, const StepParams<T>&, int pass, const OverflowFlow&, uint32_t epoch, uint32_t grid_blocks, hipStream_t);
+// returns the form it launched (AVN_OVERFLOW_FORM_DATAFLOW / _DATAFLOW_TAG; AVN_FORM_NONE for an empty grid)
+template <class T> uint32_t launch_overflow_flow(const DW<T>&, const StepParams<T>&, int pass, const OverflowFlow&, uint32_t epoch, uint32_t grid_blocks, hipStream_t);
 // radix sort on the low `bits` bits of the keys (stable LSD, 8 bits per pass); the result is in (*keys_out, *vals_out)
 void launch_radix_sort_bits(uint32_t* keys_a, uint32_t* vals_a, uint32_t* keys_b, uint32_t* vals_b, uint32_t n, uint32_t bits, uint32_t* hist, uint32_t* block_sums,
                             uint32_t** keys_out, uint32_t** vals_out, hipStream_t);

@@ -296,6 +296,8 @@ template <class T> struct World : WorldBase {
         }
 #ifdef AVN_MEASURE
         if (avn_env("AVN_NO_OCT")) oct_enabled = false;           // (A/B: every colour on the lane-per-manifold kernel)
+        if (const char* e = avn_env("AVN_OCT_ON")) oct_on = (uint32_t)strtoul(e, nullptr, 10);     // (the tests' way across the hysteresis band with dozens of manifolds)
+        if (const char* e = avn_env("AVN_OCT_OFF")) oct_off = (uint32_t)strtoul(e, nullptr, 10);
         if (avn_env("AVN_NO_HANDLE_SORT")) handle_sort = false;   // (A/B: the solver's arrays in the bookkeeping's list order, as before round 5)
 #endif
         for (auto& x : ev) HIPCHK(hipEventCreateWithFlags(&x, EV_FLAGS));

@@ -92,6 +92,7 @@ struct WorldBase {
     virtual avn_status pipeline_new_pair_ids_get(const uint32_t**, size_t*) = 0;
     virtual avn_status broad_phase_stats_get(avn_broad_phase_stats*) = 0;
     virtual avn_status level_compaction_stats_get(avn_level_compaction_stats*) = 0;
+    virtual avn_status solver_forms_get(avn_solver_forms*) = 0;
     virtual avn_status host_shapes_set(avn_host_aabb_fn, avn_host_manifolds_fn, void*) = 0;
     virtual avn_status host_shape_stats_get(avn_host_shape_stats*) = 0;
     virtual avn_status collision_hooks_set(avn_filter_pairs_fn, avn_modify_contacts_fn, void*) = 0;

@@ -1279,12 +1279,13 @@ template <> struct OverflowFlowLaunch<float> {
         return true;
     }
 };
-template <class T> void launch_overflow_flow(const DW<T>& w, const StepParams<T>& p, int pass, const OverflowFlow& of, uint32_t epoch, uint32_t grid_blocks, hipStream_t s) {
-    if (!grid_blocks) return;
-    if (OverflowFlowLaunch<T>::run(w, p, pass, of, epoch, grid_blocks, s)) return;   // f32: tags in the velocity records; f64 (two accesses per record): tickets
+template <class T> uint32_t launch_overflow_flow(const DW<T>& w, const StepParams<T>& p, int pass, const OverflowFlow& of, uint32_t epoch, uint32_t grid_blocks, hipStream_t s) {
+    if (!grid_blocks) return AVN_FORM_NONE;
+    if (OverflowFlowLaunch<T>::run(w, p, pass, of, epoch, grid_blocks, s)) return AVN_OVERFLOW_FORM_DATAFLOW_TAG;   // f32: tags in the velocity records; f64 (two accesses per record): tickets
     if (pass == PASS_BIAS) hipLaunchKernelGGL((k_overflow_flow<T, PASS_BIAS>), dim3(grid_blocks), dim3(CONTACT_THREADS), 0, s, w, p, of, epoch);
     else if (pass == PASS_RELAX) hipLaunchKernelGGL((k_overflow_flow<T, PASS_RELAX>), dim3(grid_blocks), dim3(CONTACT_THREADS), 0, s, w, p, of, epoch);
     else hipLaunchKernelGGL((k_overflow_flow<T, PASS_RESTITUTION>), dim3(grid_blocks), dim3(CONTACT_THREADS), 0, s, w, p, of, epoch);
+    return AVN_OVERFLOW_FORM_DATAFLOW;
 }
 
 template <class T>
@@ -1338,26 +1339,39 @@ template <int PASS> struct OctLaunch<float, PASS> {
         return false;
     }
 };
-template <class T, int PASS> static uint32_t launch_pass(const DW<T>& w, const StepParams<T>& p, const uint32_t* grid_blocks, const uint32_t* arg_offsets, const OverflowSchedule& ovf, hipStream_t s, uint32_t oct_mask) {
+// forms (avn_solver_forms_get): what this pass launched, written down next to the launch itself.  The restitution pass fills restitution_colour_form
+// only; every other pass the colour forms, their grids, where the ranges come from and the overflow form.  Host words: nothing reaches the device.
+template <class T, int PASS> static uint32_t launch_pass(const DW<T>& w, const StepParams<T>& p, const uint32_t* grid_blocks, const uint32_t* arg_offsets, const OverflowSchedule& ovf, hipStream_t s, uint32_t oct_mask,
+                                                         avn_solver_forms* forms) {
     uint32_t launches = 0;
+    constexpr bool loop_pass = PASS != PASS_RESTITUTION;
     if (grid_blocks[AVN_COLOR_OVERFLOW_INDEX] && ovf.n_glevels) {
+        uint32_t largest = 0;
         for (uint32_t l = 0; l < ovf.n_glevels; ++l) {
             uint32_t first = ovf.glevel_offsets[l], count = ovf.glevel_offsets[l + 1] - first;
             if (!count) continue;
             hipLaunchKernelGGL((k_overflow_level<T, PASS>), dim3(color_grid_blocks(count)), dim3(CONTACT_THREADS), 0, s, w, p, ovf.gorder, first, count);
             ++launches;
+            if (color_grid_blocks(count) > largest) largest = color_grid_blocks(count);
         }
+        if (forms && loop_pass) { forms->overflow_form = AVN_OVERFLOW_FORM_LEVEL; forms->overflow_components = 0; forms->overflow_levels = launches; forms->overflow_grid_blocks = largest; }
     } else if (grid_blocks[AVN_COLOR_OVERFLOW_INDEX] && ovf.n_components) {
         hipLaunchKernelGGL((k_overflow_pass<T, PASS>), dim3(ovf.n_components), dim3(OVERFLOW_THREADS), 0, s, w, p, ovf.comp_level_begin, ovf.level_offsets, ovf.order);
         ++launches;
+        if (forms && loop_pass) { forms->overflow_form = AVN_OVERFLOW_FORM_COMPONENT; forms->overflow_components = ovf.n_components; forms->overflow_levels = 0; forms->overflow_grid_blocks = ovf.n_components; }
     }
     for (uint32_t c = 0; c < AVN_COLOR_OVERFLOW_INDEX; ++c)
         if (grid_blocks[c]) {
             uint32_t b = arg_offsets ? arg_offsets[c] : 0u, e = arg_offsets ? arg_offsets[c + 1] : 0u;
             if (arg_offsets && e == b) continue;  // (a captured range is exact: an empty colour needs no launch)
-            if (!((oct_mask >> c) & 1u) || !OctLaunch<T, PASS>::run(w, p, c, grid_blocks[c], b, e, s))
+            uint32_t form = AVN_COLOUR_FORM_OCT;
+            if (!((oct_mask >> c) & 1u) || !OctLaunch<T, PASS>::run(w, p, c, grid_blocks[c], b, e, s)) {
                 hipLaunchKernelGGL((k_color_pass<T, PASS>), dim3(grid_blocks[c]), dim3(CONTACT_THREADS), 0, s, w, p, c, b, e);
+                form = AVN_COLOUR_FORM_LANE;
+            }
             ++launches;
+            if (forms && loop_pass) { forms->colour_form[c] = form; forms->colour_grid_blocks[c] = grid_blocks[c]; forms->colour_ranges_from = arg_offsets ? AVN_RANGES_FROM_ARGUMENTS : AVN_RANGES_FROM_DEVICE; }
+            else if (forms) forms->restitution_colour_form[c] = form;
         }
     return launches;
 }
@@ -1489,8 +1503,8 @@ void launch_island_substeps(const DW<float>& w, const StepParams<float>& p, cons
     if (ib.cache_records) hipLaunchKernelGGL((k_island_substeps<float, true>), dim3(ib.n_blocks), dim3(ISLAND_THREADS), 0, s, w, p, ib, substeps, iterations);
     else hipLaunchKernelGGL((k_island_substeps<float, false>), dim3(ib.n_blocks), dim3(ISLAND_THREADS), 0, s, w, p, ib, substeps, iterations);
 }
-template <class T> void launch_body_warm_start(const DW<T>& w, const StepParams<T>& p, bool fuse_integrate_velocities, bool quads, hipStream_t s) {
-    if (!w.n_bodies) return;
+template <class T> uint32_t launch_body_warm_start(const DW<T>& w, const StepParams<T>& p, bool fuse_integrate_velocities, bool quads, hipStream_t s) {
+    if (!w.n_bodies) return AVN_FORM_NONE;
     uint32_t nb = (w.n_bodies + WS_THREADS - 1) / WS_THREADS;
     nb = ((nb + 7u) / 8u) * 8u;
     // quads: four lanes per body (k_body_warm_start_quad) -- the device closed loop, whose handle lists are in history order (2.78 -> 2.72 ms per settled cfg2
@@ -1502,31 +1516,32 @@ template <class T> void launch_body_warm_start(const DW<T>& w, const StepParams<
         nq = ((nq + 7u) / 8u) * 8u;
         if (fuse_integrate_velocities) hipLaunchKernelGGL((k_body_warm_start_quad<T, true>), dim3(nq), dim3(WSQ_THREADS), 0, s, w, p);
         else hipLaunchKernelGGL((k_body_warm_start_quad<T, false>), dim3(nq), dim3(WSQ_THREADS), 0, s, w, p);
-        return;
+        return AVN_WARM_START_FORM_QUADS;
     }
     if (fuse_integrate_velocities) hipLaunchKernelGGL((k_body_warm_start<T, true>), dim3(nb), dim3(WS_THREADS), 0, s, w, p);
     else hipLaunchKernelGGL((k_body_warm_start<T, false>), dim3(nb), dim3(WS_THREADS), 0, s, w, p);
+    return AVN_WARM_START_FORM_LANE;
 }
-template <class T> uint32_t launch_contact_pass(const DW<T>& w, const StepParams<T>& p, int pass, const uint32_t* grid_blocks, const uint32_t* arg_offsets, const OverflowSchedule& ovf, hipStream_t s, uint32_t oct_mask) {
+template <class T> uint32_t launch_contact_pass(const DW<T>& w, const StepParams<T>& p, int pass, const uint32_t* grid_blocks, const uint32_t* arg_offsets, const OverflowSchedule& ovf, hipStream_t s, uint32_t oct_mask, avn_solver_forms* forms) {
     switch (pass) {
         case PASS_WARM: return 0;  // warm start is body-centric: launch_body_warm_start
-        case 4: return launch_pass<T, PASS_WARM>(w, p, grid_blocks, arg_offsets, ovf, s, 0u);   // PASS_WARM_START_COLORS: colour by colour
+        case 4: return launch_pass<T, PASS_WARM>(w, p, grid_blocks, arg_offsets, ovf, s, 0u, forms);   // PASS_WARM_START_COLORS: colour by colour
 #ifdef AVN_MEASURE
-        case 5: return launch_pass<T, PASS_SKELETON>(w, p, grid_blocks, arg_offsets, ovf, s, 0u);   // PASS_MEMORY_SKELETON (measurement aid, `make measure` only)
+        case 5: return launch_pass<T, PASS_SKELETON>(w, p, grid_blocks, arg_offsets, ovf, s, 0u, forms);   // PASS_MEMORY_SKELETON (measurement aid, `make measure` only)
 #endif
-        case PASS_BIAS: return launch_pass<T, PASS_BIAS>(w, p, grid_blocks, arg_offsets, ovf, s, oct_mask);
-        case PASS_RELAX: return launch_pass<T, PASS_RELAX>(w, p, grid_blocks, arg_offsets, ovf, s, oct_mask);
-        default: return launch_pass<T, PASS_RESTITUTION>(w, p, grid_blocks, arg_offsets, ovf, s, 0u);
+        case PASS_BIAS: return launch_pass<T, PASS_BIAS>(w, p, grid_blocks, arg_offsets, ovf, s, oct_mask, forms);
+        case PASS_RELAX: return launch_pass<T, PASS_RELAX>(w, p, grid_blocks, arg_offsets, ovf, s, oct_mask, forms);
+        default: return launch_pass<T, PASS_RESTITUTION>(w, p, grid_blocks, arg_offsets, ovf, s, 0u, forms);
     }
 }
 
 #define INST(T)                                                                                             \
     template void launch_prepare_contact_constraints<T>(const DW<T>&, const StepParams<T>&, hipStream_t, bool, const RowsView<T>*);   \
     template void launch_store_contact_impulses<T>(const DW<T>&, hipStream_t);                              \
-    template void launch_body_warm_start<T>(const DW<T>&, const StepParams<T>&, bool, bool, hipStream_t);   \
+    template uint32_t launch_body_warm_start<T>(const DW<T>&, const StepParams<T>&, bool, bool, hipStream_t);   \
     template void launch_build_incidence_slots<T>(const DW<T>&, hipStream_t, bool);                               \
-    template uint32_t launch_contact_pass<T>(const DW<T>&, const StepParams<T>&, int, const uint32_t*, const uint32_t*, const OverflowSchedule&, hipStream_t, uint32_t); \
-    template void launch_overflow_flow<T>(const DW<T>&, const StepParams<T>&, int, const OverflowFlow&, uint32_t, uint32_t, hipStream_t);
+    template uint32_t launch_contact_pass<T>(const DW<T>&, const StepParams<T>&, int, const uint32_t*, const uint32_t*, const OverflowSchedule&, hipStream_t, uint32_t, avn_solver_forms*); \
+    template uint32_t launch_overflow_flow<T>(const DW<T>&, const StepParams<T>&, int, const OverflowFlow&, uint32_t, uint32_t, hipStream_t);
 INST(float)
 INST(double)
 #undef INST

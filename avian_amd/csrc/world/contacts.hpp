@@ -170,9 +170,15 @@
     uint32_t ovf_grid_blocks = 0;   // device closed loop: captured grid of the overflow colour's dataflow pass (with slack, like the colours')
     // Colours small enough to leave most SIMDs idle run the eight-lanes-per-manifold solve (k_color_pass_oct, f32): chosen per colour with hysteresis, and only
     // ever changed together with a re-capture of the substep graph.  Bit-identical either way.  (AVN_NO_OCT=1 in `make measure` builds: A/B.)
+    // A colour takes the oct form at <= OCT_ON manifolds and keeps it up to OCT_OFF (AVN_OCT_ON / AVN_OCT_OFF, read at world creation, replace the two in `make measure` builds).
     uint32_t oct_mask = 0;
     bool oct_enabled = sizeof(T) == 4;
     static constexpr uint32_t OCT_ON = 12288, OCT_OFF = 20480;
+#ifdef AVN_MEASURE
+    uint32_t oct_on = OCT_ON, oct_off = OCT_OFF;
+#else
+    static constexpr uint32_t oct_on = OCT_ON, oct_off = OCT_OFF;
+#endif
     void set_color_offsets(const uint32_t* offsets) {
         if (!use_handles && std::memcmp(color_offsets, offsets, sizeof color_offsets) != 0) graph_valid = false;  // (ranges captured as kernel arguments; handle mode reads them from the device)
         std::memcpy(color_offsets, offsets, sizeof color_offsets);
@@ -197,7 +203,7 @@
                 graph_valid = false;
             }
             const bool was = (oct_mask >> c) & 1u;
-            const bool now = oct_enabled && !halo_on && cnt != 0 && (was ? cnt <= OCT_OFF : cnt <= OCT_ON);
+            const bool now = oct_enabled && !halo_on && cnt != 0 && (was ? cnt <= oct_off : cnt <= oct_on);
             if (now != was) { oct_mask ^= 1u << c; graph_valid = false; }
         }
     }

@@ -461,6 +461,15 @@
         plan.out(o->warm_start_normal_impulse, 4 * M, &a); plan.out(o->warm_start_tangent_impulse, 8 * M, &b);
         plan.out(o->normal_impulse, 4 * M, &c);
         COMMIT(plan);
+        if (use_handles && !pipe_dev) {
+            // handle lists (host bookkeeping): store_contact_impulses scattered the impulses into the contact table, and DW::mp_w holds only what k_store_contact_impulses
+            // wrote -- the points of manifolds that generated a constraint; every other slot was never written by anyone.  Answer from the rows the handles name: points
+            // beyond a row's count read as zero, as avn_contacts_download gives them.  (The device closed loop keeps the arrays: its n_manifolds is an upper bound of the list.)
+            ContactsStage<T> rows;
+            std::memset(&rows, 0, sizeof rows);
+            rows.warm_n = a; rows.warm_t = b; rows.normal_impulse = c;
+            if (M) launch_unpack_contacts<T>(ct, b_handles.as<uint32_t>(), (uint32_t)M, rows, stream);
+        } else
         launch_unpack_impulses<T>(dw, a, b, c, lvl_perm(), stream);
         HIPCHK(hipGetLastError());
         FINISH(plan);

@@ -32,7 +32,8 @@
     void warm_start(bool fused) {
         if (dw.n_manifolds) {
             if (slots_dirty && dw.inc_slot) { launch_build_incidence_slots<T>(dw, stream); launches += 2; slots_dirty = false; }  // (normally done by prepare)
-            launch_body_warm_start<T>(dw, params, fused, pipe_dev, stream); ++launches;
+            const uint32_t form = launch_body_warm_start<T>(dw, params, fused, pipe_dev, stream); ++launches;
+            if (forms_rec) forms_rec->warm_start_form = form;
         }
         else if (fused) integrate_velocities();
     }
@@ -46,14 +47,15 @@
             if (ovf_grid_blocks && ovf_epoch < PGC_OVF_TILES) {
                 OverflowFlow of{b_ovf_rank.as<uint32_t>(), b_ovf_ticket.as<uint32_t>(), pg.ctr + PGC_OVF_TILE, pg.ctr + PGC_ERROR};
                 if (const char* e = avn_env("AVN_OVF_POLL_SLEEP")) of.poll_sleep = (uint32_t)std::atoi(e);
-                launch_overflow_flow<T>(dw, params, pass, of, ovf_epoch, ovf_grid_blocks, stream);
+                const uint32_t form = launch_overflow_flow<T>(dw, params, pass, of, ovf_epoch, ovf_grid_blocks, stream);
                 ++ovf_epoch; ++launches;
+                if (forms_rec && pass != PASS_RESTITUTION_) { forms_rec->overflow_form = form; forms_rec->overflow_grid_blocks = ovf_grid_blocks; }
             }
             uint32_t gb[AVN_GRAPH_COLOR_COUNT];
             std::memcpy(gb, grid_blocks, sizeof gb);
             gb[AVN_COLOR_OVERFLOW_INDEX] = 0;
             OverflowSchedule none{0, nullptr, nullptr, nullptr, nullptr, nullptr, 0};
-            launches += launch_contact_pass<T>(dw, params, pass, gb, nullptr, none, stream, oct_mask);
+            launches += launch_contact_pass<T>(dw, params, pass, gb, nullptr, none, stream, oct_mask, forms_rec);
             return;
         }
         OverflowSchedule ovf{sched_overflow.n_components, sched_overflow.d_comp_level_begin.as<uint32_t>(), sched_overflow.d_level_offsets.as<uint32_t>(),
@@ -63,7 +65,7 @@
             ovf.glevel_offsets = sched_overflow.glevel_offsets.data();
             ovf.n_glevels = (uint32_t)sched_overflow.glevel_offsets.size() - 1;
         }
-        launches += launch_contact_pass<T>(dw, params, pass, grid_blocks, use_handles ? nullptr : color_offsets, ovf, stream, oct_mask);
+        launches += launch_contact_pass<T>(dw, params, pass, grid_blocks, use_handles ? nullptr : color_offsets, ovf, stream, oct_mask, forms_rec);
     }
     // The reference runs the snapshot and the velocity projection over ALL active bodies whenever XpbdSolverPlugin is
     // installed (xpbd/plugin.rs:61-76,192-240).  With no joints the projection adds 2 * (dq * conj(dq)).xyz / h:
@@ -162,12 +164,15 @@
         bias_timed = 0;
         dg_substeps = 0;
         if (halo_on) {   // level-2 sharding: direct launches, the exchanges are RCCL calls on the same stream
+            forms_begin(forms_direct);   // (the level-2 passes are not written down: every form reads "none")
             if (!comm.handle) { error = "a halo plan is set but no communicator: call avn_comm_init, or drive the colours through avn_run_color_pass"; return AVN_ERR_STATE; }
             return level2_substeps();
         }
         if constexpr (sizeof(T) == 4) {
             if (islands_active()) {   // every substep of every island block in ONE launch (k_island_substeps)
                 launch_island_substeps(dw, params, islands, cfg.substeps, cfg.solver_iterations, stream); ++launches;
+                forms_begin(forms_direct);
+                if (islands.n_blocks) { forms_direct.island_blocks = islands.n_blocks; forms_direct.island_cache_records = islands.cache_records; forms_direct.warm_start_form = AVN_WARM_START_FORM_COLOURS; }
                 slot_clear_pending = false;   // (the island blocks do not use the slot table: a later colour-launch step clears it itself)
                 // (device closed loop: the restitution pass after the loop still runs colour by colour; its overflow pass starts a fresh epoch count)
                 if (pipe_dev && ovf_grid_blocks) { launch_overflow_reset(b_ovf_ticket.as<uint32_t>(), dw.n_bodies + 1, pg.ctr + PGC_OVF_TILE, PGC_OVF_TILES, stream); ++launches; }
@@ -186,7 +191,9 @@
         if (!cfg.use_graph) {
             if (flow) { launch_overflow_reset(b_ovf_ticket.as<uint32_t>(), dw.n_bodies + 1, pg.ctr + PGC_OVF_TILE, PGC_OVF_TILES, stream); ++launches; }
             ovf_epoch = 0;
+            forms_rec = forms_begin(forms_direct);
             avn_status sl = substep_loop();
+            forms_rec = nullptr;
             ovf_epoch_after_substeps = ovf_epoch;
             return sl;
         }
@@ -209,6 +216,7 @@
             uint32_t before = launches;
             HIPCHK(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));
             avn_status sl = AVN_OK;
+            forms_rec = forms_begin(forms_graph);   // (the first substep of a split step is launched directly every step and is NOT written down: the read-out says what the graph holds)
             if (split) {   // substeps 1 .. S-1, continuing the first one's epochs
                 ovf_epoch = epoch_after_first; substep_index = 1;
                 for (uint32_t s = 1; s < cfg.substeps; ++s) substep();
@@ -223,6 +231,7 @@
             ovf_epoch_after_substeps = ovf_epoch;
             // whatever went wrong inside the capture, the stream must leave capture mode and the partial graph must not survive
             hipError_t ce = hipStreamEndCapture(stream, &graph);
+            forms_rec = nullptr;
             if (ce == hipSuccess && sl != AVN_OK) ce = hipErrorUnknown;
             graph_launches = launches - before;
             launches = before;
@@ -234,15 +243,32 @@
                 return AVN_ERR_HIP;
             }
             graph_valid = true;
+            ++forms_captures;
         }
         ht("substep graph: hipGraphLaunch called");
         // (Round 5, measured and removed: the replay on a stream of its own behind an event, so that its packets would already sit in a queue when the
         //  front finishes -- the device idles 43 us between k_build_incidence_slots and the graph's first kernel although hipGraphLaunch has returned
         //  40 us earlier (AVN_PIPE_HOST_TRACE).  Settled step 2.42 -> 2.62 / 2.64 ms on one box: the start gap grows to 52 us and the join costs more.)
         HIPCHK(hipGraphLaunch(graph_exec, stream));
+        forms_last = &forms_graph; ++forms_replays;
         ht("hipGraphLaunch returned");
         launches += graph_launches;
         ovf_epoch = ovf_epoch_after_substeps;   // (the restitution pass after the loop continues the step's epochs)
+        return AVN_OK;
+    }
+    // avn_solver_forms_get: the forms of the substep loop, written down by the launchers while a loop is enqueued (forms_direct) or captured (forms_graph).  A replay
+    // writes nothing: it only says that the graph's record is the current one, so a graph that should have been captured again shows as a stale read-out.
+    avn_solver_forms forms_direct{}, forms_graph{}, forms_rest{};
+    const avn_solver_forms* forms_last = &forms_direct;
+    avn_solver_forms* forms_rec = nullptr;   // where the launchers write; null outside run_substeps and the restitution pass (single systems through avn_run_system / avn_profile_system are not written down)
+    uint32_t forms_captures = 0, forms_replays = 0;
+    avn_solver_forms* forms_begin(avn_solver_forms& f) { f = avn_solver_forms{}; forms_last = &f; return &f; }
+    avn_status solver_forms_get(avn_solver_forms* out) override {
+        if (!out || out->struct_size != sizeof(avn_solver_forms)) { error = "solver_forms_get: null argument or struct_size"; return AVN_ERR_BAD_ARG; }
+        *out = *forms_last;
+        std::memcpy(out->restitution_colour_form, forms_rest.restitution_colour_form, sizeof out->restitution_colour_form);
+        out->graph_captures = forms_captures; out->graph_replays = forms_replays;
+        out->struct_size = (uint32_t)sizeof(avn_solver_forms);
         return AVN_OK;
     }
     uint32_t graph_launches = 0;
@@ -287,6 +313,7 @@
         ht("constraints / overflow CSR enqueued");
         HIPCHK(hipEventRecord(ev[2], stream));
         if ((st = run_substeps()) != AVN_OK) return st;
+        forms_rest = avn_solver_forms{};
         HIPCHK(hipEventRecord(ev[3], stream));
         stamp(DG_SUB1);
         if (ccd.n && (st = ccd_pass()) != AVN_OK) return st;   // solve_swept_ccd: after PostSubstep, before Restitution (ccd/mod.rs:257-261)
@@ -294,7 +321,7 @@
         // restitution == 0 everywhere: every manifold would early-out.  (Level 2: the exchanges are collective and `any_restitution` is a
         // per-rank fact, so the pass always runs there; a rank without restitution launches kernels whose lanes all early-out.)
         if (halo_on) { if ((st = level2_pass(PASS_RESTITUTION_)) != AVN_OK) return st; }
-        else if (any_restitution) contact_pass(PASS_RESTITUTION_);
+        else if (any_restitution) { forms_rec = &forms_rest; contact_pass(PASS_RESTITUTION_); forms_rec = nullptr; }
         stamp(DG_REST1);
         HIPCHK(hipGetLastError());
         return AVN_OK;

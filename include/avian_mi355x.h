@@ -1282,6 +1282,45 @@ typedef struct avn_level_compaction_stats {
 } avn_level_compaction_stats;
 AVN_API avn_status avn_level_compaction_stats_get(avn_world* w, avn_level_compaction_stats* out);
 
+/* ---- which form of the contact solve the substep loop holds (inspection) --------------------------------------------------------------------
+ * The host picks a kernel per launch range of colour_offsets[0..23) and for the overflow list, from sizes, thresholds with hysteresis and
+ * grids kept with slack; every form is bit-identical, so no result can tell which of them ran.  This can.  It reports what the LAST ENQUEUED
+ * OR CAPTURED substep loop contained, written down where the launches are issued -- not what the thresholds would pick now: a world that
+ * replays a captured graph reports the capture's forms until it captures again.  Filled on the host: no kernel, launch, copy or
+ * synchronisation exists for it.  Launch ranges are colours, or levels after a level compaction (avn_level_compaction_stats).
+ * The oracle has one form: it answers AVN_OK with every form "none" and every count zero. */
+#define AVN_FORM_NONE 0u                  /* every *_form: nothing of the kind was launched */
+#define AVN_COLOUR_FORM_LANE 1u           /* k_color_pass: one lane per manifold */
+#define AVN_COLOUR_FORM_OCT 2u            /* k_color_pass_oct: eight lanes per manifold (f32, biased solve and relax only) */
+#define AVN_RANGES_FROM_ARGUMENTS 1u      /* the ranges are (captured) kernel arguments: host-uploaded manifolds */
+#define AVN_RANGES_FROM_DEVICE 2u         /* the kernels read DW::color_offsets: manifold handles, the closed loop */
+#define AVN_OVERFLOW_FORM_COMPONENT 1u    /* k_overflow_pass: one workgroup per component */
+#define AVN_OVERFLOW_FORM_LEVEL 2u        /* k_overflow_level: one device-wide launch per level */
+#define AVN_OVERFLOW_FORM_DATAFLOW 3u     /* k_overflow_flow: tickets (device closed loop, f64) */
+#define AVN_OVERFLOW_FORM_DATAFLOW_TAG 4u /* k_overflow_flow_tag: tags in the velocity records (device closed loop, f32) */
+#define AVN_WARM_START_FORM_LANE 1u       /* k_body_warm_start: one lane per body */
+#define AVN_WARM_START_FORM_QUADS 2u      /* k_body_warm_start_quad: four lanes per body */
+#define AVN_WARM_START_FORM_COLOURS 3u    /* colour by colour: inside the island blocks */
+typedef struct avn_solver_forms {
+    uint32_t struct_size;                 /* in: sizeof(avn_solver_forms) */
+    uint32_t colour_form[23];             /* AVN_COLOUR_FORM_* of the biased solve and relax launches, per launch range 0..22 */
+    uint32_t colour_grid_blocks[23];      /* the grid behind each of them, in workgroups of the lane form (64 manifolds each; the oct form launches 8 per one) */
+    uint32_t restitution_colour_form[23]; /* AVN_COLOUR_FORM_* of the last restitution pass (never captured: it follows the loop); none when it did not run */
+    uint32_t colour_ranges_from;          /* AVN_RANGES_FROM_* (none: no launch over a range 0..22) */
+    uint32_t overflow_form;               /* AVN_OVERFLOW_FORM_* of the biased solve and relax passes */
+    uint32_t overflow_components;         /* per component: workgroups = components of the overflow list */
+    uint32_t overflow_levels;             /* per level: launches per pass */
+    uint32_t overflow_grid_blocks;        /* workgroups of the (largest) overflow launch of a pass */
+    uint32_t island_blocks;               /* workgroups of k_island_substeps; 0 when the device-wide path ran */
+    uint32_t island_cache_records;        /* 1: its variant that stages the constraint records in LDS */
+    uint32_t warm_start_form;             /* AVN_WARM_START_FORM_* */
+    uint32_t graph_captures;              /* substep graphs captured and instantiated since the world was created (0 with use_graph = 0) */
+    uint32_t graph_replays;               /* hipGraphLaunch calls since then (the launch that follows a capture included) */
+} avn_solver_forms;
+/* A plain avn_ function outside AVN_FN, like the two read-outs above, so that a library built before it existed still loads; the oracle exports its
+ * all-none answer as avo_solver_forms_get. */
+AVN_API avn_status avn_solver_forms_get(avn_world* w, avn_solver_forms* out);
+
 #ifdef __cplusplus
 }
 #endif

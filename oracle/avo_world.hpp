@@ -1940,6 +1940,7 @@ template <class S> struct World : WorldBase {
                 const CtPoint& c = r.pts[k];
                 m.points[k] = {c.anchor1, c.anchor2, c.penetration, c.normal_speed, c.warm_start_normal_impulse, c.normal_impulse, c.warm_start_tangent_impulse};
             }
+            for (int k = m.point_count; k < AVN_MAX_MANIFOLD_POINTS; ++k) m.points[k] = {};   // (impulses_download: points the row does not hold read as zero, not as the slot's previous tenant)
         }
         });
     }

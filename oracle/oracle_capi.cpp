@@ -50,6 +50,14 @@ avn_status avo_step(avn_world* w) { FWD(step()); }
 avn_status avo_synchronize(avn_world* w) { return w ? AVN_OK : AVN_ERR_BAD_ARG; }
 avn_status avo_timers_get(avn_world* w, avn_timers* t) { FWD(timers(t)); }
 avn_status avo_diagnostics_get(avn_world* w, avn_diagnostics* d) { FWD(diagnostics(d)); }
+// the checker solves colour by colour on the host, in one form: every form reads "none" and every count zero
+avn_status avo_solver_forms_get(avn_world* w, avn_solver_forms* out) {
+    if (!w) return AVN_ERR_BAD_ARG;
+    if (!out || out->struct_size != sizeof(avn_solver_forms)) { w->impl->error = "solver_forms_get: null argument or struct_size"; return AVN_ERR_BAD_ARG; }
+    *out = avn_solver_forms{};
+    out->struct_size = (uint32_t)sizeof(avn_solver_forms);
+    return AVN_OK;
+}
 avn_status avo_islands_get(avn_world* w, uint32_t* island_of_body, uint32_t* n_islands) { FWD(islands_get(island_of_body, n_islands)); }
 avn_status avo_sleep_update(avn_world* w, const avn_sleep_params* p, avn_sleep_stats* st) { FWD(sleep_update(p, st)); }
 avn_status avo_sleep_get(avn_world* w, const avn_sleep_out* o) { FWD(sleep_get(o)); }

@@ -112,9 +112,10 @@ def fresh_twin_step(lib, bits, use_graph, w, tab, cfg_kw):
     return out
 
 
-def run_script(lib, bits, script: List[Op], use_graph, twin=False, skip: Optional[int] = None, until_checkpoint: Optional[int] = None, base_cfg=None):
+def run_script(lib, bits, script: List[Op], use_graph, twin=False, skip: Optional[int] = None, until_checkpoint: Optional[int] = None, base_cfg=None, probe=None):
     """Executes `script` on a new world of `lib`; returns one dict per checkpoint: {"seq": downloads of the sequenced world, "twin": downloads of the fresh twin
-    (twin=True) or None}.  skip: the index of ONE operation to leave out (the mutation control); until_checkpoint: stop after that many checkpoints."""
+    (twin=True) or None}.  skip: the index of ONE operation to leave out (the mutation control); until_checkpoint: stop after that many checkpoints;
+    probe: called with the sequenced world at every checkpoint, its result kept under "probe" (read-outs such as avn_solver_forms)."""
     cfg_kw = dict(base_cfg or {})
     w = F.World(lib, make_cfg(bits, use_graph, cfg_kw))
     tab = Tables()
@@ -127,7 +128,7 @@ def run_script(lib, bits, script: List[Op], use_graph, twin=False, skip: Optiona
             tw = fresh_twin_step(lib, bits, use_graph, w, tab, cfg_kw)
         apply(w, op, bits, use_graph, tab, cfg_kw)
         if op.kind == "step" and op.checkpoint:
-            out.append({"seq": downloads(w), "twin": tw, "twin_rows": enabled_rows(tab)})
+            out.append({"seq": downloads(w), "twin": tw, "twin_rows": enabled_rows(tab), "probe": probe(w) if probe else None})
             if until_checkpoint is not None and len(out) >= until_checkpoint:
                 break
     w.close()

@@ -17,9 +17,13 @@ def declared_symbols():
 def test_header_symbols_all_exported_by_both_libraries():
     syms = declared_symbols()
     assert len(syms) >= 26 and set(syms) == set(F.ABI_SYMBOLS)
+    # avn_solver_forms_get is a plain avn_ function outside AVN_FN (a library built before it existed must still load), but BOTH libraries export it
+    assert "solver_forms_get" not in syms and F.SOLVER_FORMS_SYMBOLS == ("solver_forms_get",)
+    assert "AVN_API avn_status avn_solver_forms_get(avn_world* w, avn_solver_forms* out);" in open(os.path.join(REPO, "include", "avian_mi355x.h")).read()
     import ctypes
     for lib in (hip_lib(), oracle_lib()):
         dll = ctypes.CDLL(lib.path)
+        assert hasattr(dll, lib.prefix + "solver_forms_get"), f"{lib.path} does not export {lib.prefix}solver_forms_get"
         for s in syms:
             assert hasattr(dll, lib.prefix + s), f"{lib.path} does not export {lib.prefix}{s}"
 
@@ -98,6 +102,27 @@ def test_every_ctypes_struct_has_the_size_the_c_compiler_gives_the_header_struct
         assert int(got[n]) == ctypes.sizeof(getattr(F, n)), f"{n}: header {got[n]} B, binding {ctypes.sizeof(getattr(F, n))} B"
 
 
+def test_oracle_answers_the_solver_forms_read_out_with_no_forms():
+    """avn_solver_forms_get on the CPU checker: AVN_OK, every form "none", every count zero (it has one way of solving), and a wrong struct_size is refused."""
+    import ctypes
+    lib = oracle_lib()
+    w = F.World(lib, F.default_config(32, substeps=2))
+    w.bodies_upload(position=np.zeros((2, 3)), rotation=np.tile([0.0, 0, 0, 1], (2, 1)), linear_velocity=np.zeros((2, 3)), angular_velocity=np.zeros((2, 3)),
+                    inv_mass=np.ones(2), inv_inertia_local=np.tile([1.0, 0, 0, 1, 0, 1], (2, 1)), rb_type=np.zeros(2, np.uint8), center_of_mass=np.zeros((2, 3)))
+    for stepped in (False, True):
+        if stepped:
+            w.step()
+        f = w.solver_forms()
+        assert f.struct_size == ctypes.sizeof(F.avn_solver_forms) == 4 * (1 + 3 * 23 + 10)
+        assert all(getattr(f, name) == 0 for name, t in F.avn_solver_forms._fields_[1:] if t is ctypes.c_uint32)
+        assert not any(f.colour_form) and not any(f.colour_grid_blocks) and not any(f.restitution_colour_form)
+    for size in (0, 4, ctypes.sizeof(F.avn_solver_forms) - 4, ctypes.sizeof(F.avn_solver_forms) + 4):
+        bad = F.avn_solver_forms(size)
+        assert lib.dll.avo_solver_forms_get(w.handle, ctypes.byref(bad)) == 1, "AVN_ERR_BAD_ARG on a struct_size mismatch"
+    assert lib.dll.avo_solver_forms_get(w.handle, None) == 1
+    assert (F.FORM_NONE, F.COLOUR_FORM_LANE, F.COLOUR_FORM_OCT, F.OVERFLOW_FORM_DATAFLOW_TAG, F.WARM_START_FORM_COLOURS) == (0, 1, 2, 4, 3)
+
+
 def test_generated_rust_bindings_are_current_and_complete():
     """integration/rust/avian_mi355x-sys/src/lib.rs (what a maintainer's Rust shim links against) is generated from the header:
     it must be up to date, declare every exported symbol, and give every struct exactly the fields of the ctypes mirror, in order."""
@@ -111,6 +136,7 @@ def test_generated_rust_bindings_are_current_and_complete():
     for sym in declared_symbols():
         assert re.search(rf"pub fn avn_{sym}\(", rs), f"avn_{sym} missing from the Rust declarations"
     assert len(re.findall(r"pub fn avn_", rs)) == len(declared_symbols())
+    assert "pub struct avn_solver_forms {" in rs and "pub const AVN_COLOUR_FORM_OCT: u32 = 2;" in rs   # (the function is a plain avn_ one: the crate carries its struct and constants)
     structs = {n: c for n, c in inspect.getmembers(F, inspect.isclass) if issubclass(c, ctypes.Structure) and n.startswith("avn_")}
     checked = 0
     for n, c in structs.items():

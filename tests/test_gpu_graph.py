@@ -117,6 +117,10 @@ def test_overflow_colour_dataflow_pass_matches_the_serial_reference_loop():
             compare_step(s, wo, wh)
             seen = max(seen, wh.pipeline_stats().last_overflow_manifolds)
         assert seen > 300, "the scene must actually use colour 23"
+        f = wh.solver_forms()
+        assert f.overflow_form == F.OVERFLOW_FORM_DATAFLOW_TAG and f.overflow_grid_blocks > 0, "f32: the dataflow pass with tags in the velocity records"
+        assert f.warm_start_form == F.WARM_START_FORM_QUADS and f.colour_ranges_from == F.RANGES_FROM_DEVICE and f.island_blocks == 0
+        assert (f.graph_captures > 0) == bool(use_graph) and (0 < f.graph_replays <= 10) == bool(use_graph)
 
 
 def test_restitution_pass_continues_the_overflow_epochs():

@@ -39,7 +39,7 @@ def clustered(wd, cluster):
     return wd
 
 
-@pytest.mark.parametrize("case", ["one_island_with_overflow", "clusters", "clusters_small_blocks", "two_iterations"])
+@pytest.mark.parametrize("case", ["one_island_with_overflow", "clusters", "clusters_small_blocks", "two_iterations", "small_set"])
 def test_island_blocks_match_oracle_and_device_wide_path(case, monkeypatch):
     kw = dict(substeps=4)
     if case == "one_island_with_overflow":
@@ -47,6 +47,8 @@ def test_island_blocks_match_oracle_and_device_wide_path(case, monkeypatch):
     elif case == "two_iterations":
         wd = random_world(seed=12, n_bodies=200, n_manifolds=500, n_joints=0, hub_degree=30)
         kw["solver_iterations"] = 2
+    elif case == "small_set":   # 6 records per body + 20 per manifold of the WHOLE set fit the 4088 of a block's LDS: the CACHE variant, however the islands are packed
+        wd = random_world(seed=18, n_bodies=60, n_manifolds=120, n_joints=0, hub_degree=0)
     else:
         wd = clustered(random_world(seed=13, n_bodies=900, n_manifolds=2400, n_joints=0, hub_degree=0), 24)
         if case == "clusters_small_blocks":
@@ -66,6 +68,30 @@ def test_island_blocks_match_oracle_and_device_wide_path(case, monkeypatch):
         compare_all(wo, wd_, f"{case}: device-wide vs oracle, step {s}")
     ti, td = wi.timers(), wd_.timers()
     assert ti.island_blocks > 0 and td.island_blocks == 0
+    fi, fd = wi.solver_forms(), wd_.solver_forms()
+    assert fi.island_blocks == ti.island_blocks and fi.warm_start_form == F.WARM_START_FORM_COLOURS and not any(fi.colour_form) and fi.overflow_form == F.FORM_NONE
+    assert fd.island_blocks == 0 and fd.island_cache_records == 0 and any(fd.colour_form) and fd.warm_start_form == F.WARM_START_FORM_LANE
+    overflow = wd_.level_compaction_stats().overflow_count
+    assert overflow > 0 or case not in ("one_island_with_overflow", "two_iterations"), "the hub must fill the overflow list"
+    assert (fd.overflow_form == F.OVERFLOW_FORM_COMPONENT) == (overflow > 0) and fd.overflow_components <= overflow, "an overflow list runs one workgroup per component"
+    # the CACHE variant stages 20 records per manifold next to 6 per body in 4088: no block may hold more than 204 manifolds, so fewer blocks than M / 204 rule it out
+    m_total = wi.n_manifolds
+    print(f"{case}: {fi.island_blocks} island blocks, CACHE {fi.island_cache_records}, {m_total} manifolds")
+    if fi.island_blocks * 204 < m_total:
+        assert fi.island_cache_records == 0
+    if 6 * len(wd["bodies"]["rb_type"]) + 20 * (m_total + 1) <= 4088:   # ... and a set that fits as a whole rules it in; the switch takes it out again
+        assert case == "small_set" and fi.island_cache_records == 1
+        monkeypatch.setenv("AVN_ISLAND_CACHE_RECORDS", "0")
+        wn = F.World(hip_measure_lib(), F.default_config(32, **kw))
+        monkeypatch.delenv("AVN_ISLAND_CACHE_RECORDS")
+        color_and_upload(wn, oracle_lib(), wd)
+        for s in range(5):
+            wn.step()
+        fn = wn.solver_forms()
+        assert fn.island_blocks == fi.island_blocks and fn.island_cache_records == 0
+        compare_all(wo, wn, f"{case}: island blocks without the CACHE variant vs oracle")
+    else:
+        assert case != "small_set"
     if case == "clusters":
         assert ti.island_blocks >= 3
     if case == "clusters_small_blocks":

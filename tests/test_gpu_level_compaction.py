@@ -135,6 +135,9 @@ def test_box_stack_1k(bits, use_graph):
     w, got = run(hip_lib(), bits, case, 3, use_graph)
     st = check_readout(w, case)
     assert (st.colours, st.levels) == (15, 14) and st.moved == 1
+    f = w.solver_forms()
+    assert f.island_blocks == 0, "one island of a thousand bodies: the device-wide path"
+    assert [x for x in f.colour_form if x] == [F.COLOUR_FORM_OCT if bits == 32 else F.COLOUR_FORM_LANE] * 14, "one launch per level: oct in f32 (every level is small), lane in f64"
     ms, launches = w.profile_system("SOLVE_CONTACTS_BIAS", 1)
     print("SOLVE_CONTACTS_BIAS launches:", launches)
     assert launches == 14
@@ -172,6 +175,8 @@ def make_case(seed, n_bodies, colours, n_static=1, n_kinematic=0, overflow=(), p
 def judge(case, bits=32, steps=2, compacted=True, use_graph=1):
     w, got = run(hip_lib(), bits, case, steps, use_graph)
     st = check_readout(w, case, compacted)
+    if bits == 32 and len(case["mf"]["body1"]):   # (f32, no joints, small islands: these sets never reach the level LAUNCHES -- tests/test_gpu_solver_forms.py runs them there)
+        assert w.solver_forms().island_blocks > 0 and not any(w.solver_forms().colour_form), "the hand-made f32 sets solve through the island blocks"
     same(got, run(oracle_lib(), bits, case, steps)[1], "vs the oracle")
     same(got, run(hip_measure_lib(), bits, case, steps, switched_off=True)[1], "vs colour launches (rows in upload order)")
     return w, st

@@ -51,14 +51,30 @@ def oracle_checkpoints(name, bits):
     return _oracle_runs[(name, bits)]
 
 
-def judge(name, bits, use_graph, lib):
-    got = S.run_script(lib, bits, S.host_script(name), use_graph, twin=True)
+def judge(name, bits, use_graph, lib, probe=None):
+    got = S.run_script(lib, bits, S.host_script(name), use_graph, twin=True, probe=probe)
     want = oracle_checkpoints(name, bits)
     assert len(got) == len(want) >= 3
     for k, (g, o) in enumerate(zip(got, want)):
         what = f"{name} f{bits} use_graph={use_graph} checkpoint {k}"
         S.assert_twin(g, what + ": the sequence left stale state (sequenced device world vs fresh device world)")
         S.assert_equal_downloads(o["seq"], g["seq"], what + ": the device world equals its fresh twin but not the oracle (a kernel is wrong)")
+    return got
+
+
+def overflow_levels(m, bodies):
+    """levels of the overflow list, restated: in list order, level = 1 + the highest level so far on either body that has a SolverBody"""
+    offs = np.asarray(m["offs"]).astype(np.int64)
+    fl = np.asarray(bodies.get("body_flags", np.zeros(len(bodies["rb_type"]), np.uint8)))
+    sb = (np.asarray(bodies["rb_type"]) != S.F.RB_STATIC) & ((fl & (S.F.BODY_SLEEPING | S.F.BODY_DISABLED)) == 0)
+    last, top = {}, 0
+    for i in range(offs[S.F.COLOR_OVERFLOW_INDEX], offs[S.F.COLOR_OVERFLOW_INDEX + 1]):
+        keys = [int(b) for b in (m["mf"]["body1"][i], m["mf"]["body2"][i]) if sb[b]]
+        lv = 1 + max([last.get(b, 0) for b in keys], default=0)
+        for b in keys:
+            last[b] = lv
+        top = max(top, lv)
+    return top
 
 
 @pytest.mark.parametrize("use_graph", [0, 1])
@@ -72,7 +88,17 @@ def test_overflow_reversed_in_the_per_level_form(use_graph, monkeypatch):
     """the same script with the overflow colour above AVN_OVERFLOW_LEVEL_THRESHOLD (measure build): one launch per level, the level sizes are launch parameters
     (sched_overflow.gorder / glevel_offsets, graph_valid when they change)"""
     monkeypatch.setenv("AVN_OVERFLOW_LEVEL_THRESHOLD", "16")
-    judge("overflow_reversed", 32, use_graph, hip_measure_lib())
+    monkeypatch.setenv("AVN_ISLAND_BLOCKS", "0")   # (f32, no joints, 260 bodies: without it the island blocks solve the set and no overflow launch of either form is ever made)
+    got = judge("overflow_reversed", 32, use_graph, hip_measure_lib(), probe=lambda w: w.solver_forms())
+    script = S.host_script("overflow_reversed")
+    sets = [op.args for op in script if op.kind == "manifolds"]
+    bodies = [op.args for op in script if op.kind == "bodies"][0]
+    want = [overflow_levels(m, bodies) for m in sets]
+    print("overflow levels per upload:", want, "read out:", [(g["probe"].overflow_form, g["probe"].overflow_levels, g["probe"].island_blocks) for g in got])
+    assert len(set(want)) > 1 or want[0] > 1, "the reversed list must have a schedule of its own"
+    for g, levels in zip(got, want):
+        f = g["probe"]
+        assert f.island_blocks == 0 and f.overflow_form == S.F.OVERFLOW_FORM_LEVEL and f.overflow_levels == levels and f.overflow_components == 0
 
 
 # ---- the closed loop: the contact table lives on the device, so the reference is the oracle in lock step after EVERY step (test_gpu_graph.compare_step: colour lists

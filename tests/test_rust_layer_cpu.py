@@ -26,6 +26,7 @@ def test_every_ffi_name_the_layer_uses_is_in_the_generated_bindings():
     structs = set(re.findall(r"pub struct (avn_\w+)", sys_src)) | set(re.findall(r"pub type (avn_\w+)", sys_src))
     consts = set(re.findall(r"pub const (AVN_\w+)", sys_src))
     assert len(fns) > 80 and len(structs) > 20 and len(consts) > 60
+    assert "avn_solver_forms" in structs and {"AVN_FORM_NONE", "AVN_COLOUR_FORM_LANE", "AVN_OVERFLOW_FORM_LEVEL", "AVN_WARM_START_FORM_QUADS"} <= consts
     used = set()
     for name, src in sources().items():
         for ident in re.findall(r"(?<![\w:])ffi::(\w+)", src):
