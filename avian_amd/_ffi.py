@@ -343,6 +343,12 @@ class avn_host_shape_stats(C.Structure):
                 ("bytes_to_host", C.c_uint64), ("bytes_from_host", C.c_uint64), ("last_callback_ms", C.c_double)]
 
 
+# A triangle of a static mesh (parry's Triangle): the kind scenes.MeshScene keeps for its faces (col_shape).  No backend holds it as a collider kind yet:
+# World.colliders_upload refuses it, MeshScene.collider_kwargs() uploads the faces as SHAPE_HOST.  Edge flags: bit k = edge k (ab, bc, ca) is real.
+SHAPE_TRIANGLE = 4
+TRIANGLE_ALL_EDGES = 7
+
+
 class avn_collider_transforms(C.Structure):
     _fields_ = [("count", C.c_uint32), ("is_child", C.c_void_p), ("translation", C.c_void_p), ("rotation", C.c_void_p)]
 
@@ -805,6 +811,8 @@ class World:
     def colliders_upload(self, entity_index, body, shape, half_extents, memberships=None, filters=None,
                          collider_flags=None, collision_margin=None, speculative_margin=None):
         c = len(np.asarray(entity_index).reshape(-1))
+        if c and (np.asarray(shape).reshape(-1) == SHAPE_TRIANGLE).any():   # (the device would read kind 4 as a cuboid)
+            raise ValueError("colliders_upload: SHAPE_TRIANGLE is no collider kind of any backend yet: upload triangles as SHAPE_HOST and answer them through host_shapes_set")
         keep = [self._i(entity_index, np.uint32), self._i(body, np.int32), self._i(shape, np.uint8),
                 self._s(half_extents, (c, 3)), self._i(memberships, np.uint32), self._i(filters, np.uint32),
                 self._i(collider_flags, np.uint8), self._s(collision_margin), self._s(speculative_margin)]

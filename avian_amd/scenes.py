@@ -437,3 +437,109 @@ def stack_with_chains(nx: int = 50, ny: int = 20, nz: int = 50, n_chains: int = 
                   local_anchor2=np.zeros((J, 3)), limit_min=np.full(J, spacing), limit_max=np.full(J, spacing),
                   compliance=np.full(J, 1e-5))
     return sc, joints
+
+
+# ---- static triangle-mesh ground: one triangle collider (SHAPE_TRIANGLE, held as a host shape) per face, all on the static body 0 ---------------------
+@dataclass
+class MeshScene(Scene):
+    """A Scene whose body 0 carries the faces of a triangle mesh as colliders: the collider tables are explicit (several colliders on one body).
+    `half_extents` / `shape` stay per BODY (body 0's are unused); collider slot f < n_faces is face f, slot n_faces + k - 1 the collider of body k."""
+    col_entity: Optional[np.ndarray] = None
+    col_body: Optional[np.ndarray] = None
+    col_shape: Optional[np.ndarray] = None
+    col_half_extents: Optional[np.ndarray] = None
+    vertices: Optional[np.ndarray] = None      # [C, 3, 3] a, b, c in the collider's frame (zeros where the collider is no triangle)
+    edge_flags: Optional[np.ndarray] = None    # [C]
+    grid: Optional[tuple] = None               # (nx, nz, spacing, heights [nx + 1, nz + 1]) of trimesh_ground
+
+    @property
+    def n_faces(self) -> int:
+        return int((self.col_shape == F.SHAPE_TRIANGLE).sum())
+
+    def collider_kwargs(self, host_capsules: bool = False):
+        """What a world uploads: no backend has the triangle as a kind of its own, so the faces go up as SHAPE_HOST (the world answers them through its
+        host-shape callbacks, e.g. tests/triangle_collider_reference.py: TriangleHost); `col_shape` keeps the real kinds for those callbacks.
+        `host_capsules`: the capsules too, for a backend without the capsule kind (the oracle)."""
+        hosted = (self.col_shape == F.SHAPE_TRIANGLE) | (host_capsules & (self.col_shape == F.SHAPE_CAPSULE))
+        return dict(entity_index=self.col_entity, body=self.col_body, shape=np.where(hosted, F.SHAPE_HOST, self.col_shape).astype(np.uint8),
+                    half_extents=self.col_half_extents)
+
+    def surface_height(self, x, z):
+        """The height of the triangulated ground under (x, z) (clamped to the grid's extent)."""
+        nx, nz, spacing, h = self.grid
+        u = np.clip(np.asarray(x, np.float64) / spacing + nx * 0.5, 0.0, nx - 1e-12); w = np.clip(np.asarray(z, np.float64) / spacing + nz * 0.5, 0.0, nz - 1e-12)
+        i, j = np.floor(u).astype(int), np.floor(w).astype(int)
+        fu, fw = u - i, w - j
+        h00, h10, h01, h11 = h[i, j], h[i + 1, j], h[i, j + 1], h[i + 1, j + 1]
+        # the quad's diagonal runs from (i, j) to (i + 1, j + 1): the face (00, 01, 11) where fw >= fu, the face (00, 11, 10) otherwise
+        return np.where(fw >= fu, h00 + (h01 - h00) * fw + (h11 - h01) * fu, h00 + (h10 - h00) * fu + (h11 - h10) * fw)
+
+
+def trimesh_ground(nx: int, nz: int, spacing: float = 1.0, height_fn=None):
+    """A grid of nx x nz quads centred on the origin, two faces per quad (counter-clockwise seen from above), y = height_fn(x, z) (default: flat at 0):
+    (vertices [(nx + 1)(nz + 1), 3], indices [2 nx nz, 3]).  Quad (i, j) gives faces 2 (i nz + j) and 2 (i nz + j) + 1."""
+    xs = (np.arange(nx + 1) - nx * 0.5) * spacing
+    zs = (np.arange(nz + 1) - nz * 0.5) * spacing
+    X, Z = np.meshgrid(xs, zs, indexing="ij")
+    Y = np.zeros_like(X) if height_fn is None else np.asarray(height_fn(X, Z), np.float64)
+    vertices = np.stack([X, Y, Z], axis=-1).reshape(-1, 3)
+    vid = lambda i, j: i * (nz + 1) + j
+    faces = []
+    for i in range(nx):
+        for j in range(nz):
+            faces.append((vid(i, j), vid(i, j + 1), vid(i + 1, j + 1)))
+            faces.append((vid(i, j), vid(i + 1, j + 1), vid(i + 1, j)))
+    return vertices, np.array(faces, np.int64)
+
+
+def trimesh_drop(n_boxes: int = 8, n_balls: int = 8, n_capsules: int = 8, nx: int = 8, nz: int = 8, spacing: float = 1.0, height_fn=None, seed: int = 0,
+                 drop_height: float = 0.8, layers: int = 1, all_edges: bool = False) -> MeshScene:
+    """Boxes, balls and capsules in shuffled order dropped from a grid over a trimesh_ground (body 0, static, at the origin): they land on the faces, roll and
+    slide over the interior edges and come to rest.  `all_edges`: every edge flagged (a bag of isolated triangles) instead of the adjacency's flags."""
+    from .trimesh import triangle_colliders
+    rng = np.random.default_rng(seed)
+    gv, gi = trimesh_ground(nx, nz, spacing, height_fn)
+    tri, flags = triangle_colliders(gv, gi)
+    if all_edges:
+        flags = np.full(len(tri), F.TRIANGLE_ALL_EDGES, np.uint8)
+    nf = len(tri)
+    m = n_boxes + n_balls + n_capsules
+    kind = np.concatenate([np.full(n_boxes, F.SHAPE_CUBOID), np.full(n_balls, F.SHAPE_BALL), np.full(n_capsules, F.SHAPE_CAPSULE)]).astype(np.uint8)
+    kind = kind[rng.permutation(m)]
+    per_layer = -(-m // layers)
+    side = int(np.ceil(np.sqrt(per_layer)))
+    pitch = min(nx, nz) * spacing * 0.8 / max(side, 1)
+    N = m + 1
+    pos = np.zeros((N, 3)); he = np.zeros((N, 3)); inv_mass = np.zeros(N); inv_i = np.zeros((N, 6))
+    box_h, ball_r, cap_r, cap_h = 0.2, 0.25, 0.15, 0.25
+    top = float(gv[:, 1].max())
+    for k in range(m):
+        layer, cell = divmod(k, per_layer)
+        pos[1 + k] = [(cell % side - (side - 1) * 0.5) * pitch + rng.uniform(-0.05, 0.05), top + drop_height + 0.9 * layer + rng.uniform(0.0, 0.2),
+                      (cell // side - (side - 1) * 0.5) * pitch + rng.uniform(-0.05, 0.05)]
+        if kind[k] == F.SHAPE_CAPSULE:
+            he[1 + k] = (cap_r, cap_h, 0.0)
+            mass, inertia = capsule_mass_properties(cap_r, cap_h)
+        elif kind[k] == F.SHAPE_CUBOID:
+            he[1 + k] = (box_h, box_h, box_h)
+            mass, inertia = cuboid_mass_properties(box_h, box_h, box_h)
+        else:
+            he[1 + k] = (ball_r, ball_r, ball_r)
+            mass = 4.0 / 3.0 * np.pi * ball_r ** 3
+            inertia = (0.4 * mass * ball_r * ball_r,) * 3
+        inv_mass[1 + k] = 1.0 / mass
+        inv_i[1 + k, 0], inv_i[1 + k, 3], inv_i[1 + k, 5] = 1.0 / inertia[0], 1.0 / inertia[1], 1.0 / inertia[2]
+    rot = rng.normal(size=(N, 4)); rot /= np.linalg.norm(rot, axis=1, keepdims=True); rot[0] = (0.0, 0.0, 0.0, 1.0)
+    rb = np.zeros(N, np.uint8); rb[0] = F.RB_STATIC
+    dyn = (rb == 0)[:, None]
+    shape = np.concatenate([[F.SHAPE_TRIANGLE], kind]).astype(np.uint8)
+    C = nf + m
+    col_shape = np.concatenate([np.full(nf, F.SHAPE_TRIANGLE, np.uint8), kind])
+    col_body = np.concatenate([np.zeros(nf, np.int32), np.arange(1, N, dtype=np.int32)])
+    col_he = np.concatenate([np.zeros((nf, 3)), he[1:]])
+    verts = np.zeros((C, 3, 3)); verts[:nf] = tri
+    ef = np.full(C, F.TRIANGLE_ALL_EDGES, np.uint8); ef[:nf] = flags
+    heights = gv[:, 1].reshape(nx + 1, nz + 1)
+    return MeshScene(pos, rot, rng.normal(scale=0.2, size=(N, 3)) * dyn, rng.normal(scale=0.5, size=(N, 3)) * dyn, inv_mass, inv_i, rb, he, shape, friction=0.6,
+                     col_entity=np.arange(C, dtype=np.uint32), col_body=col_body, col_shape=col_shape, col_half_extents=col_he, vertices=verts, edge_flags=ef,
+                     grid=(nx, nz, spacing, heights))
