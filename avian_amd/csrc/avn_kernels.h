@@ -102,7 +102,8 @@ template <class T> struct RowsView {
     const uint32_t* handles; const uint4* meta; const uint4* col_info; const Vec4<T>* rows;   // CT<T>::rows: 16 records per row (n | tv | a1[4] | a2[4] | w[4] | fid)
 };
 template <class T> void launch_prepare_contact_constraints(const DW<T>&, const StepParams<T>&, hipStream_t, bool count_clean = false /* *DW::constraint_count is known to be zero */,
-                                                           const RowsView<T>* rows = nullptr /* handle mode: read the ContactGraph side from the table (no k_gather_manifolds) */);
+                                                           const RowsView<T>* rows = nullptr /* handle mode: read the ContactGraph side from the table (no k_gather_manifolds) */,
+                                                           bool lazy = false /* array mode: the impulses of the previous step are still in c_pd (World::imp_in_rows) */);
 template <class T> void launch_store_contact_impulses(const DW<T>&, hipStream_t);
 // body-centric warm start over the incidence CSR (DW::inc_off / inc_ent), optionally preceded by integrate_velocities
 // returns the form it launched (AVN_WARM_START_FORM_*; AVN_FORM_NONE without bodies): avn_solver_forms::warm_start_form

@@ -127,10 +127,28 @@ template <class T> __device__ __forceinline__ V3<T> velocity_at_point(const Body
 // PREP_TILES_PER_BLOCK tiles of 256 manifolds (stride = the grid: the resident workgroups sweep the arrays side by side), keeps its waves' counts in
 // scalar registers and issues ONE atomic at its end: 663 at cfg2, 72 us, 5.8 TB/s.  (With the counter out of the way the four-lane form reaches 80 us --
 // twice the load instructions for the same bytes -- and was not kept.)
+//
+// IMPULSES IN THE ROWS (LAZY; array mode, World::imp_in_rows): the previous step left its impulses in c_pd and did not copy them into mp_w.  The current
+// value of point k of manifold m is then stored_impulse(c_pd[s], cm_prev) for k < (cm_prev & 7) -- cm_prev = the word the PREVIOUS prepare left in c_h1[m].w, read before
+// this one stores to c_h1[m] -- and mp_w[s] for every other slot: the lane takes its warm-start values from there, and writes a slot the invariant is about to stop
+// covering (the manifold is skipped this step, or k >= this step's count) into mp_w first.  k_store_contact_impulses, unchanged, is the materialisation of all of it.
+// C_PA ONCE (PA_ONCE; array mode): c_pa[s] = (r1, -penetration - dot(r2 - r1, normal)) depends on mp_a1, mp_a2 and m_n only, which change with k_pack_manifolds alone
+// (the level permutation moves them WITH c_pa and m_meta).  Bit 31 of m_meta[m] says "c_pa of this manifold is current": k_pack_manifolds writes m_meta whole and so
+// clears it; the first lane that generates the manifold's constraint writes the rows and sets it; every later one stores 16 B per point less.
+// REGISTERS: the f32 <false, LAZY, PA_ONCE> instantiation sits at 168 VGPRs, the last count with three waves per SIMD (the parent's code: 148).  A first form chose the slot's
+// home by a pointer select in front of the loads and kept the flushed slots in registers: 174 VGPRs, two waves, 74.6 us at cfg2 against the parent's 69.3 although it wrote
+// 43 MB less.  Hence c_pd is loaded unconditionally with the other eleven records, the rare mp_w slots are fetched where they are used, the flush reads the rows on its own
+// before the loads, and bit 31 is set before the point loop (63.5 us).  Check -Rpass-analysis=kernel-resource-usage after touching this kernel.
 #define PREP_TILE 256
 #define PREP_TILES_PER_BLOCK 4
-template <class T, bool ROWS>
+#define AVN_META_PA_CURRENT 0x80000000u
+template <class T> __device__ __forceinline__ Vec4<T> stored_impulse(Vec4<T> d, uint32_t cm) {   // a c_pd record as store_contact_impulses hands it to the ContactGraph
+    const bool t = cm & AVN_CM_TANGENT;
+    return make4<T>(d.x, t ? d.z : T(0), t ? d.w : T(0), d.y);
+}
+template <class T, bool ROWS, bool LAZY = false, bool PA_ONCE = false>
 __global__ __launch_bounds__(PREP_TILE) void k_prepare_contact_constraints(DW<T> w, StepParams<T> p, RowsView<T> rv) {
+    static_assert(!ROWS || (!LAZY && !PA_ONCE), "handle mode: the rows are rebuilt every step");
     uint32_t count = 0;   // wave-uniform: the constraints this wave generated
     // handle mode: the live manifold count is the device's (the colour offsets k_pg_build_handles / the upload left); DW::n_manifolds may be the
     // host's UPPER BOUND of it -- the device closed loop launches this kernel before it has read the step's counts back
@@ -152,11 +170,22 @@ __global__ __launch_bounds__(PREP_TILE) void k_prepare_contact_constraints(DW<T>
                 w.m_meta[m] = npr | (((meta.z & AVN_CP_GENERATE_CONSTRAINTS) ? (uint32_t)AVN_MANIFOLD_GENERATES_CONSTRAINTS : 0u) << 8);
             }
             uint32_t mm = w.m_meta[m];
-            uint32_t np = mm & 7u, mflags = mm >> 8;
+            uint32_t np = mm & 7u, mflags = PA_ONCE ? (mm & ~AVN_META_PA_CURRENT) >> 8 : mm >> 8;
+            uint32_t cm_prev = 0;
+            if (LAZY) cm_prev = scalar_to_bits(w.c_h1[m].w);   // (before anything is stored to c_h1[m])
+            const uint32_t np_prev = cm_prev & 7u;
             int2 b = w.m_bodies[m];
             uint32_t meta1 = w.bmeta[b.x], meta2 = w.bmeta[b.y];
             bool skip = !(mflags & AVN_MANIFOLD_GENERATES_CONSTRAINTS) || !meta_active(meta1) || !meta_active(meta2) ||
                         (meta_rb_type(meta1) != AVN_RB_DYNAMIC && meta_rb_type(meta2) != AVN_RB_DYNAMIC) || np == 0;
+            if (LAZY) {   // slots the previous constraint covered and this step's will not (no constraint at all, or fewer points): home to mp_w, from the rows as they are
+                const uint32_t np_now = skip ? 0u : np;
+                if (np_now < np_prev) {
+#pragma unroll
+                    for (uint32_t k = 0; k < AVN_MAX_MANIFOLD_POINTS; ++k)
+                        if (k >= np_now && k < np_prev) { uint32_t s = k * w.m_stride + m; w.mp_w[s] = stored_impulse<T>(w.c_pd[s], cm_prev); }
+                }
+            }
             if (skip) {
                 w.c_h1[m] = make4<T>(0, 0, 0, bits_to_scalar(0u, T(0)));
                 w.c_reldom[m] = 0;
@@ -193,13 +222,21 @@ __global__ __launch_bounds__(PREP_TILE) void k_prepare_contact_constraints(DW<T>
 #pragma unroll
                 for (uint32_t k = 0; k < AVN_MAX_MANIFOLD_POINTS; ++k) {
                     if (ROWS) { const Vec4<T>* __restrict__ r = rv.rows + (size_t)row * AVN_CT_ROW_V4; pa1[k] = r[2 + k]; pa2[k] = r[6 + k]; pww[k] = r[10 + k]; }
-                    else { uint32_t s = k * S + m; pa1[k] = w.mp_a1[s]; pa2[k] = w.mp_a2[s]; pww[k] = w.mp_w[s]; }
+                    else { uint32_t s = k * S + m; pa1[k] = w.mp_a1[s]; pa2[k] = w.mp_a2[s]; pww[k] = LAZY ? w.c_pd[s] : w.mp_w[s]; }   // (LAZY: the rows, with the other loads; see below)
                 }
+                const bool pa_current = PA_ONCE && (mm & AVN_META_PA_CURRENT);
+                if (PA_ONCE && !pa_current) w.m_meta[m] = mm | AVN_META_PA_CURRENT;   // (this lane writes the rows below)
 #pragma unroll
                 for (uint32_t k = 0; k < AVN_MAX_MANIFOLD_POINTS; ++k) {
                     if (k >= np) break;
                     uint32_t s = k * S + m;
                     Vec4<T> a1 = pa1[k], a2 = pa2[k], ww = pww[k];
+                    if (LAZY) {
+                        // a slot the previous constraint covered lives in the row loaded above; any other one in mp_w -- only a manifold that was skipped in the
+                        // previous step (or had fewer points then) uses such a slot, so this second memory level is rare, and nothing is kept in registers for it
+                        ww = stored_impulse<T>(ww, cm_prev);
+                        if (k >= np_prev) ww = w.mp_w[s];
+                    }
                     V3<T> r1 = xyz<T>(a1), r2 = xyz<T>(a2);
                     T penetration = a1.w, normal_speed = a2.w;
                     // ContactNormalPart::generate
@@ -219,8 +256,10 @@ __global__ __launch_bounds__(PREP_TILE) void k_prepare_contact_constraints(DW<T>
                         k2 = T(2) * (dot(rt11, i1_rt21) + dot(rt12, i2_rt22));
                         if (warm) { tx = ww.y; ty = ww.z; }
                     }
-                    T initial_separation = -penetration - dot(r2 - r1, normal);
-                    w.c_pa[s] = make4<T>(r1, initial_separation);
+                    if (!pa_current) {
+                        T initial_separation = -penetration - dot(r2 - r1, normal);
+                        w.c_pa[s] = make4<T>(r1, initial_separation);
+                    }
                     w.c_pb[s] = make4<T>(r2, eff_mass);
                     w.c_pc[s] = make4<T>(k0, k1, k2, normal_speed);
                     w.c_pd[s] = make4<T>(ni, T(0), tx, ty);
@@ -1297,9 +1336,7 @@ __global__ __launch_bounds__(256) void k_store_contact_impulses(DW<T> w) {
     uint32_t S = w.m_stride;
     for (uint32_t k = 0; k < np; ++k) {
         uint32_t s = k * S + m;
-        Vec4<T> d = w.c_pd[s];
-        bool t = cm & AVN_CM_TANGENT;
-        w.mp_w[s] = make4<T>(d.x, t ? d.z : T(0), t ? d.w : T(0), d.y);
+        w.mp_w[s] = stored_impulse<T>(w.c_pd[s], cm);
     }
 }
 
@@ -1308,10 +1345,15 @@ static uint32_t prepare_grid_blocks(uint32_t n_manifolds) {   // (handle mode: n
     const uint32_t tiles = (n_manifolds + PREP_TILE - 1u) / PREP_TILE;
     return (tiles + PREP_TILES_PER_BLOCK - 1u) / PREP_TILES_PER_BLOCK;
 }
-template <class T> void launch_prepare_contact_constraints(const DW<T>& w, const StepParams<T>& p, hipStream_t s, bool count_clean, const RowsView<T>* rows) {
+template <class T> void launch_prepare_contact_constraints(const DW<T>& w, const StepParams<T>& p, hipStream_t s, bool count_clean, const RowsView<T>* rows, bool lazy) {
     if (!count_clean) (void)hipMemsetAsync(w.constraint_count, 0, sizeof(uint32_t), s);
     if (!w.n_manifolds) return;
+    static const bool pa_always = avn_env("AVN_PREP_WRITE_PA") != nullptr;   // (A/B in `make measure` builds: c_pa written every step, bit 31 of m_meta never set)
+    const dim3 grid(prepare_grid_blocks(w.n_manifolds));
     if (rows) hipLaunchKernelGGL((k_prepare_contact_constraints<T, true>), dim3(prepare_grid_blocks(w.n_manifolds)), dim3(PREP_TILE), 0, s, w, p, *rows);
+    else if (lazy && !pa_always) hipLaunchKernelGGL((k_prepare_contact_constraints<T, false, true, true>), grid, dim3(PREP_TILE), 0, s, w, p, RowsView<T>{});
+    else if (lazy) hipLaunchKernelGGL((k_prepare_contact_constraints<T, false, true, false>), grid, dim3(PREP_TILE), 0, s, w, p, RowsView<T>{});
+    else if (!pa_always) hipLaunchKernelGGL((k_prepare_contact_constraints<T, false, false, true>), grid, dim3(PREP_TILE), 0, s, w, p, RowsView<T>{});
     else hipLaunchKernelGGL((k_prepare_contact_constraints<T, false>), dim3(prepare_grid_blocks(w.n_manifolds)), dim3(PREP_TILE), 0, s, w, p, RowsView<T>{});
 }
 template <class T> void launch_store_contact_impulses(const DW<T>& w, hipStream_t s) {
@@ -1536,7 +1578,7 @@ template <class T> uint32_t launch_contact_pass(const DW<T>& w, const StepParams
 }
 
 #define INST(T)                                                                                             \
-    template void launch_prepare_contact_constraints<T>(const DW<T>&, const StepParams<T>&, hipStream_t, bool, const RowsView<T>*);   \
+    template void launch_prepare_contact_constraints<T>(const DW<T>&, const StepParams<T>&, hipStream_t, bool, const RowsView<T>*, bool);   \
     template void launch_store_contact_impulses<T>(const DW<T>&, hipStream_t);                              \
     template uint32_t launch_body_warm_start<T>(const DW<T>&, const StepParams<T>&, bool, bool, hipStream_t);   \
     template void launch_build_incidence_slots<T>(const DW<T>&, hipStream_t, bool);                               \

@@ -213,6 +213,7 @@
         for (int c = 0; c < AVN_GRAPH_COLOR_COUNT; ++c) if (offsets[c] > offsets[c + 1]) { error = "manifold_handles_upload: offsets not monotone"; return AVN_ERR_BAD_ARG; }
         uint32_t M = offsets[AVN_GRAPH_COLOR_COUNT];
         if (M && !ids) return AVN_ERR_BAD_ARG;
+        { const avn_status sm = materialize_impulses(); if (sm != AVN_OK) return sm; }   // (the host arrays' impulses go home before the lists replace them)
         h_m_body1.resize(M); h_m_body2.resize(M);
         for (uint32_t i = 0; i < M; ++i)
             if (ids[i] >= ct.cap || !h_ct_used[ids[i]]) { error = "manifold_handles_upload: no such contact"; return AVN_ERR_STATE; }

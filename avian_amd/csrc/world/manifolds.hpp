@@ -43,6 +43,7 @@
     // The level-2 / per-colour API (halo plan, overflow levels, joint slot, run_color_pass, comm_init) addresses the host's COLOURS: from its first
     // use on the world stays in colour order, and a set that was compacted before is put back (every manifold-indexed array, upload order).
     avn_status level_uncompact() {
+        { const avn_status sm = materialize_impulses(); if (sm != AVN_OK) return sm; }   // (mp_w moves below; the level-2 calls behind this one run passes of their own on c_pd)
         lvl_level2 = true;
         if (!lvl_active) {
             if (lvl_stats.state != AVN_LEVELS_OFF) lvl_note(AVN_LEVELS_OFF, AVN_LEVELS_WHY_LEVEL2, color_offsets, color_offsets, 0u, 0u);   // (an early-out set is in colour order already)
@@ -94,6 +95,7 @@
         if (m->color_offsets[0] != 0 || m->color_offsets[AVN_GRAPH_COLOR_COUNT] != M) { error = "manifolds_upload: bad color_offsets"; return AVN_ERR_BAD_ARG; }
         for (int c = 0; c < AVN_GRAPH_COLOR_COUNT; ++c)
             if (m->color_offsets[c] > m->color_offsets[c + 1]) { error = "manifolds_upload: color_offsets not monotone"; return AVN_ERR_BAD_ARG; }
+        { const avn_status sm = materialize_impulses(); if (sm != AVN_OK) return sm; }   // (with the OLD count: an upload that is rejected below leaves mp_w as a step with its store would have)
         if (use_handles) graph_valid = false;
         use_handles = false;  // the manifolds come from the host again
         lvl_active = false;   // (the permutation describes the previous set: an upload that fails half way must not leave it in force)
@@ -455,6 +457,7 @@
     }
     avn_status impulses_download(const avn_impulses_out* o) override {
         if (!o) return AVN_ERR_BAD_ARG;
+        { const avn_status sm = materialize_impulses(); if (sm != AVN_OK) return sm; }
         size_t M = dw.n_manifolds;
         T *a, *b, *c;
         StagePlan plan(*this);

@@ -6,6 +6,7 @@
         slp_world_asleep = slp_world_idle = false;
         if (on && !have_colliders) { error = "pipeline_enable: upload bodies and colliders first"; return AVN_ERR_STATE; }
         if (on && pipe_on) return AVN_OK;
+        { const avn_status sm = materialize_impulses(); if (sm != AVN_OK) return sm; }   // (the closed loop takes the arrays over: mp_w first says what the host's steps left)
         if (pipe_on && pipe_dev) {   // leaving the device closed loop: its rows and keys go with it
             if (slp_on) { avn_status sw = sleeping_enable(nullptr); if (sw != AVN_OK) return sw; }   // the island manager goes too: no body may stay flagged Sleeping without it
             HIPCHK(hipStreamSynchronize(stream));

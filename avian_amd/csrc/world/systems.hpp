@@ -16,14 +16,29 @@
         //  against 0.1873 / 0.1772.  Neither kept.)
         if (!constraints_prepared_early) {   // (device closed loop: normally enqueued by pg_apply_ops, in front of its read-back)
             RowsView<T> rv{b_handles.as<uint32_t>(), ct.meta, bp.col_info, ct.rows};
-            launch_prepare_contact_constraints<T>(dw, params, stream, constraint_count_clean, use_handles ? &rv : nullptr); ++launches;
+            launch_prepare_contact_constraints<T>(dw, params, stream, constraint_count_clean, use_handles ? &rv : nullptr, imp_in_rows && !use_handles); ++launches;
             constraint_count_clean = false;
         }
         constraints_prepared_early = false;
         if (pipe_dev && ovf_csr_dirty && dw.n_manifolds) { overflow_csr_device(); ovf_csr_dirty = false; }
     }
+    // The impulses have ONE home.  imp_in_rows == false: mp_w is current for every point -- the state after every upload and every step that stored.
+    // true (array mode only, set by a step that skipped its store): for manifold m and slot k, with cm = bits(c_h1[m].w) and s = k * m_stride + m, the current value is
+    // (d.x, cm & TANGENT ? d.z : 0, cm & TANGENT ? d.w : 0, d.y) of d = c_pd[s] if k < (cm & 7), and mp_w[s] otherwise.  That is what k_store_contact_impulses writes,
+    // so that kernel is the materialisation; the next step's k_prepare_contact_constraints reads the same thing from the same place.  Between two uploads nobody
+    // else looks: whoever reads or writes mp_w, moves the arrays, treats c_pd as scratch (single systems) or changes the mode calls materialize_impulses() first.
+    bool imp_in_rows = false;
+    bool imp_lazy_enabled = avn_env("AVN_EAGER_STORE") == nullptr;   // (A/B in `make measure` builds: store after every step, as before)
+    avn_status materialize_impulses() {
+        if (!imp_in_rows) return AVN_OK;
+        launch_store_contact_impulses<T>(dw, stream);
+        HIPCHK(hipGetLastError());
+        imp_in_rows = false;
+        return AVN_OK;
+    }
     void store_contact_impulses() {
         launch_store_contact_impulses<T>(dw, stream); ++launches;
+        imp_in_rows = false;
         if (use_handles && dw.n_manifolds) { launch_scatter_impulses<T>(dw, ct, b_handles.as<uint32_t>(), stream); ++launches; }
     }
     void pre_process_velocity_increments() { launch_pre_process_increments<T>(dw, params, stream); ++launches; }
@@ -326,13 +341,15 @@
         HIPCHK(hipGetLastError());
         return AVN_OK;
     }
-    avn_status solver_back() {    // the write-back into Position / Rotation / velocities and the ContactGraph
+    // keep_in_rows (avn_step on host-uploaded manifolds): the impulses stay in c_pd; the flag is raised once everything is enqueued without error
+    avn_status solver_back(bool keep_in_rows = false) {    // the write-back into Position / Rotation / velocities and the ContactGraph
         launch_writeback_solver_bodies<T>(dw, stream); ++launches;
         if (dw.n_joints) { launch_writeback_joint_forces<T>(dw, params, stream); ++launches; }
         stamp(DG_FIN1);
-        store_contact_impulses();
+        if (!keep_in_rows) store_contact_impulses();
         stamp(DG_STORE1);
         HIPCHK(hipGetLastError());
+        if (keep_in_rows) imp_in_rows = true;
         return AVN_OK;
     }
     avn_status solver() {
@@ -392,6 +409,7 @@
         if (sys == AVN_SYS_SOLVER && ccd.n && !ccd_closed_loop()) { error = "run_system: a SweptCcd list needs the device closed loop (avn_pipeline_enable(1)); avn_swept_ccd_upload(NULL) clears it"; return AVN_ERR_STATE; }
         if (despawn_needs_joints) { error = "run_system: avn_despawn removed joints: upload the remaining joints (avn_joints_upload) first"; return AVN_ERR_STATE; }
         if (despawn_broken) { error = "run_system: an avn_despawn failed half-way; restart the closed loop"; return AVN_ERR_STATE; }
+        if ((st = materialize_impulses()) != AVN_OK) return st;   // (single systems use c_pd as they please, and the next prepare would read it)
         if ((st = rebuild_joint_schedules()) != AVN_OK) return st;
         if ((st = rebuild_incidence()) != AVN_OK) return st;
         if (sys != AVN_SYS_SOLVER && (st = flow_begin_standalone()) != AVN_OK) return st;
@@ -402,6 +420,7 @@
     avn_status profile_system(avn_system sys, uint32_t repeats, double* total_ms, uint32_t* n_launches) override {
         avn_status st = need_bodies();
         if (st != AVN_OK) return st;
+        if ((st = materialize_impulses()) != AVN_OK) return st;
         if ((st = rebuild_joint_schedules()) != AVN_OK) return st;
         if ((st = rebuild_incidence()) != AVN_OK) return st;
         if ((st = flow_begin_standalone()) != AVN_OK) return st;
@@ -427,6 +446,9 @@
         if (ccd.n && !ccd_closed_loop()) { error = "avn_step: a SweptCcd list needs the device closed loop (avn_pipeline_enable(1)); avn_swept_ccd_upload(NULL) clears it"; return AVN_ERR_STATE; }
         for (bool& b : dg_stamped) b = false;
         dg_np = false; ccd_stamped = false;
+        // the impulses stay in the rows only where the manifolds are the host's arrays and nothing but the next prepare reads them
+        const bool keep_in_rows = imp_lazy_enabled && !pipe_on && !use_handles && !halo_on && dw.n_manifolds != 0;
+        if (!keep_in_rows && (st = materialize_impulses()) != AVN_OK) return st;
         if (pipe_on) return pipe_dev ? pipeline_step_device() : pipeline_step();
         launches = 0;
         static const bool host_trace = avn_env("AVN_HOST_TRACE") != nullptr;   // debugging aid: where the HOST spends a step (us since the call)
@@ -475,7 +497,7 @@
             bs = stream;
         }
         if (st != AVN_OK) return st;
-        if ((st = solver_back()) != AVN_OK) return st;
+        if ((st = solver_back(keep_in_rows)) != AVN_OK) return st;
         HIPCHK(hipEventRecord(ev[4], stream));
         if (host_trace) { HIPCHK(hipEventRecord(trace_ev[2 * (trace_n % TRACE_STEPS) + 1], stream)); ++trace_n; }
         ev_valid = true;
