@@ -343,10 +343,35 @@ class avn_host_shape_stats(C.Structure):
                 ("bytes_to_host", C.c_uint64), ("bytes_from_host", C.c_uint64), ("last_callback_ms", C.c_double)]
 
 
-# A triangle of a static mesh (parry's Triangle): the kind scenes.MeshScene keeps for its faces (col_shape).  No backend holds it as a collider kind yet:
-# World.colliders_upload refuses it, MeshScene.collider_kwargs() uploads the faces as SHAPE_HOST.  Edge flags: bit k = edge k (ab, bc, ca) is real.
+# A triangle of a static mesh (parry's Triangle): the kind scenes.MeshScene keeps for its faces (col_shape).  A collider kind of the HIP backend
+# (include/avian_mi355x_trimesh.h): World.colliders_upload(..., triangles=dict(vertices=, edge_flags=)) uploads the colliders and then their table; without
+# `triangles` the upload refuses kind 4 and MeshScene.collider_kwargs() uploads the faces as SHAPE_HOST.  Edge flags: bit k = edge k (ab, bc, ca) is real.
 SHAPE_TRIANGLE = 4
 TRIANGLE_ALL_EDGES = 7
+
+
+# include/avian_mi355x_trimesh.h (plain avn_* functions: not part of ABI_SYMBOLS; the CPU oracle does not export them)
+class avn_collider_triangles(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("count", C.c_uint32), ("vertices", C.c_void_p), ("edge_flags", C.c_void_p)]
+
+
+class avn_triangle_pairs(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("count", C.c_uint32)] + [(n, C.c_void_p) for n in (
+        "shape1", "half_extents1", "position1", "rotation1", "shape2", "half_extents2", "position2", "rotation2", "prediction_distance",
+        "vertices1", "vertices2", "edge_flags1", "edge_flags2")]
+
+
+TRIMESH_SYMBOLS = ("avn_collider_triangles_upload", "avn_triangle_manifolds")   # absent from the oracle and from a library older than triangle colliders
+
+
+def declare_trimesh(dll):
+    """Declares the triangle collider's entry points where the library has them; False where it has not."""
+    if not all(hasattr(dll, name) for name in TRIMESH_SYMBOLS):
+        return False
+    dll.avn_collider_triangles_upload.restype = dll.avn_triangle_manifolds.restype = C.c_int32
+    dll.avn_collider_triangles_upload.argtypes = [C.c_void_p, C.c_void_p]
+    dll.avn_triangle_manifolds.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    return True
 
 
 class avn_collider_transforms(C.Structure):
@@ -809,16 +834,32 @@ class World:
 
     # -- broad phase -----------------------------------------------------------------------------------
     def colliders_upload(self, entity_index, body, shape, half_extents, memberships=None, filters=None,
-                         collider_flags=None, collision_margin=None, speculative_margin=None):
+                         collider_flags=None, collision_margin=None, speculative_margin=None, triangles=None):
+        """``avn_colliders_upload``.  ``triangles=dict(vertices=[C, 9] or [C, 3, 3], edge_flags=[C] or None)``: the colliders of kind SHAPE_TRIANGLE are device
+        colliders (include/avian_mi355x_trimesh.h; the HIP backend only) and their table is uploaded right behind the colliders."""
         c = len(np.asarray(entity_index).reshape(-1))
-        if c and (np.asarray(shape).reshape(-1) == SHAPE_TRIANGLE).any():   # (the device would read kind 4 as a cuboid)
-            raise ValueError("colliders_upload: SHAPE_TRIANGLE is no collider kind of any backend yet: upload triangles as SHAPE_HOST and answer them through host_shapes_set")
+        if triangles is None and c and (np.asarray(shape).reshape(-1) == SHAPE_TRIANGLE).any():   # (without their table the device would read kind 4 as a cuboid)
+            raise ValueError("colliders_upload: SHAPE_TRIANGLE needs triangles=dict(vertices=, edge_flags=) (the HIP backend), or upload the triangles as SHAPE_HOST "
+                             "and answer them through host_shapes_set")
+        if triangles is not None and not declare_trimesh(self.lib.dll):
+            raise ValueError(f"colliders_upload: {self.lib.path} has no triangle collider kind (include/avian_mi355x_trimesh.h): upload the triangles as SHAPE_HOST")
         keep = [self._i(entity_index, np.uint32), self._i(body, np.int32), self._i(shape, np.uint8),
                 self._s(half_extents, (c, 3)), self._i(memberships, np.uint32), self._i(filters, np.uint32),
                 self._i(collider_flags, np.uint8), self._s(collision_margin), self._s(speculative_margin)]
         s = avn_colliders(c, *[_ptr(a) for a in keep])
         self._check(self.lib.fn("colliders_upload")(self.handle, C.byref(s)))
         self.n_colliders = c
+        if triangles is not None:
+            self.collider_triangles_upload(**triangles)
+
+    def collider_triangles_upload(self, vertices, edge_flags=None):
+        """``avn_collider_triangles_upload``: one entry per collider of the last colliders_upload (read only where the collider is a SHAPE_TRIANGLE)."""
+        if not declare_trimesh(self.lib.dll):
+            raise ValueError(f"{self.lib.path} has no triangle collider kind (include/avian_mi355x_trimesh.h)")
+        c = self.n_colliders
+        keep = [np.ascontiguousarray(np.asarray(vertices, self.dtype).reshape(c, 9)), None if edge_flags is None else np.ascontiguousarray(edge_flags, np.uint8).reshape(c)]
+        s = avn_collider_triangles(C.sizeof(avn_collider_triangles), c, _ptr(keep[0]), _ptr(keep[1]))
+        self._check(self.lib.dll.avn_collider_triangles_upload(self.handle, C.byref(s)))
 
     def existing_pairs_upload(self, keys):
         keys = np.ascontiguousarray(keys, dtype=np.uint64)
@@ -1002,6 +1043,28 @@ class World:
         pout = avn_query_manifolds_out(*[_ptr(out[k]) for k in ("point_count", "normal", "anchor1", "anchor2", "point", "penetration",
                                                                "feature_id1", "feature_id2")])
         self._check(self.lib.fn("contact_manifolds")(self.handle, C.byref(pin), C.byref(pout)))
+        return out
+
+    def triangle_manifolds(self, shape1, half_extents1, position1, rotation1, shape2, half_extents2, position2, rotation2, prediction_distance,
+                           vertices1=None, vertices2=None, edge_flags1=None, edge_flags2=None):
+        """``avn_triangle_manifolds``: :meth:`contact_manifolds` for pairs that may hold a SHAPE_TRIANGLE (vertices [n, 9] per side, read only where that side is a
+        triangle; edge flags [n], None = every edge real).  The same dict."""
+        if not declare_trimesh(self.lib.dll):
+            raise ValueError(f"{self.lib.path} has no triangle collider kind (include/avian_mi355x_trimesh.h)")
+        dt = self.dtype
+        n = len(shape1)
+        a = lambda x, w: None if x is None else np.ascontiguousarray(np.asarray(x, dt).reshape(n, w))
+        u8 = lambda x: None if x is None else np.ascontiguousarray(x, np.uint8).reshape(n)
+        keep = [u8(shape1), a(half_extents1, 3), a(position1, 3), a(rotation1, 4), u8(shape2), a(half_extents2, 3), a(position2, 3), a(rotation2, 4),
+                np.ascontiguousarray(np.broadcast_to(np.asarray(prediction_distance, dt), (n,))), a(vertices1, 9), a(vertices2, 9), u8(edge_flags1), u8(edge_flags2)]
+        out = dict(point_count=np.zeros(n, np.uint8), normal=np.zeros((n, 3), dt), anchor1=np.zeros((n, MAX_QUERY_POINTS, 3), dt),
+                   anchor2=np.zeros((n, MAX_QUERY_POINTS, 3), dt), point=np.zeros((n, MAX_QUERY_POINTS, 3), dt),
+                   penetration=np.zeros((n, MAX_QUERY_POINTS), dt), feature_id1=np.zeros((n, MAX_QUERY_POINTS), np.uint32),
+                   feature_id2=np.zeros((n, MAX_QUERY_POINTS), np.uint32))
+        pin = avn_triangle_pairs(C.sizeof(avn_triangle_pairs), n, *[_ptr(x) for x in keep])
+        pout = avn_query_manifolds_out(*[_ptr(out[k]) for k in ("point_count", "normal", "anchor1", "anchor2", "point", "penetration",
+                                                               "feature_id1", "feature_id2")])
+        self._check(self.lib.dll.avn_triangle_manifolds(self.handle, C.byref(pin), C.byref(pout)))
         return out
 
     # -- running -----------------------------------------------------------------------------------------

@@ -4,6 +4,7 @@
 
 #include "avn_device.h"
 #include "../../include/avian_mi355x_spatial.h"   // AVN_SHAPE_CAPSULE
+#include "../../include/avian_mi355x_trimesh.h"   // AVN_SHAPE_TRIANGLE
 
 namespace avn {
 
@@ -33,7 +34,23 @@ template <class T> struct BP {
     // child colliders (avn_collider_transforms_upload): ColliderTransform per collider slot; nullptr = every collider sits on its body's entity
     Vec4<T>* col_lpos;     // (translation.xyz, 1 = child | 0)
     Vec4<T>* col_lrot;     // rotation xyzw
+    // triangle colliders (avn_collider_triangles_upload): three records per collider SLOT, (a, bits(edge flags)), (b, 0), (c, 0) in the collider's frame,
+    // read only where the slot's shape is AVN_SHAPE_TRIANGLE; nullptr = the world holds no triangle.  Slot-indexed on purpose: there is no second index
+    // that could go stale across despawn, re-upload or sleeping.  Allocated with the capacity of col_he (col_tri_bytes).
+    Vec4<T>* col_tri;
 };
+// the ONE size of BP::col_tri, for every allocation and copy, in both scalars
+static_assert(sizeof(Vec4<float>) == 16 && sizeof(Vec4<double>) == 32, "BP::col_tri records are 16 / 32 bytes");
+template <class T> __host__ __device__ __forceinline__ size_t col_tri_bytes(size_t count) { return count * 3 * sizeof(Vec4<T>); }
+// the exact AABB of a triangle collider at a pose: the component-wise min / max of pos + qrot(q, v) over its three vertices (include/avian_mi355x_trimesh.h)
+template <class T> __device__ __forceinline__ void triangle_aabb(const Vec4<T>* tri, V3<T> pos, Q4<T> q, V3<T>& mn, V3<T>& mx) {
+    const V3<T> p0 = pos + qrot(q, xyz<T>(tri[0])), p1 = pos + qrot(q, xyz<T>(tri[1])), p2 = pos + qrot(q, xyz<T>(tri[2]));
+    mn = p0; mx = p0;
+    if (p1.x < mn.x) mn.x = p1.x; if (p1.y < mn.y) mn.y = p1.y; if (p1.z < mn.z) mn.z = p1.z;
+    if (p2.x < mn.x) mn.x = p2.x; if (p2.y < mn.y) mn.y = p2.y; if (p2.z < mn.z) mn.z = p2.z;
+    if (p1.x > mx.x) mx.x = p1.x; if (p1.y > mx.y) mx.y = p1.y; if (p1.z > mx.z) mx.z = p1.z;
+    if (p2.x > mx.x) mx.x = p2.x; if (p2.y > mx.y) mx.y = p2.y; if (p2.z > mx.z) mx.z = p2.z;
+}
 // update_child_collider_position (collision/collider/collider_transform/plugin.rs:62-91): a collider's Position / Rotation from its body's
 template <class T> __device__ __forceinline__ void collider_pose(const BP<T>& bp, uint32_t slot, V3<T> body_pos, Q4<T> body_rot, V3<T>& pos, Q4<T>& rot, bool* child = nullptr) {
     pos = body_pos; rot = body_rot;
@@ -53,9 +70,11 @@ template <class T> __device__ __forceinline__ void capsule_aabb(V3<T> h, V3<T> p
     mn = pos - ext; mx = pos + ext;
 }
 // the exact AABB of a cuboid / ball at a pose, no margins (update_aabb; the spatial queries' BVH and AABB test).  CAP (k_update_aabb only):
-// an AVN_SHAPE_CAPSULE collider as well; without it the kinds are Ball and Cuboid as ever.
-template <class T, bool CAP = false> __device__ __forceinline__ void shape_aabb(uint32_t shape, V3<T> h, V3<T> pos, Q4<T> q, V3<T>& mn, V3<T>& mx) {
+// an AVN_SHAPE_CAPSULE collider as well; without it the kinds are Ball and Cuboid as ever.  TRI (k_update_aabb of a world that holds a triangle):
+// an AVN_SHAPE_TRIANGLE collider as well, `tri` its three records of BP::col_tri.
+template <class T, bool CAP = false, bool TRI = false> __device__ __forceinline__ void shape_aabb(uint32_t shape, V3<T> h, V3<T> pos, Q4<T> q, V3<T>& mn, V3<T>& mx, const Vec4<T>* tri = nullptr) {
     V3<T> he;
+    if (TRI && shape == AVN_SHAPE_TRIANGLE) { triangle_aabb<T>(tri, pos, q, mn, mx); return; }
     if (CAP && shape == AVN_SHAPE_CAPSULE) { capsule_aabb<T>(h, pos, q, mn, mx); return; }
     if (shape == AVN_SHAPE_BALL) he = V3<T>{h.x, h.x, h.x};
     else {
@@ -144,7 +163,8 @@ template <class T> void launch_joint_schedule(const DW<T>&, const StepParams<T>&
 template <class T> void launch_writeback_joint_forces(const DW<T>&, const StepParams<T>&, hipStream_t);
 // k_broadphase.hip
 // zero_words[0 .. n_zero) (n_zero <= 256) are cleared by the kernel: the step-scoped counters of what follows; returns whether a kernel ran
-template <class T> bool launch_update_aabb(const DW<T>&, const BP<T>&, const StepParams<T>&, hipStream_t, uint32_t* zero_words = nullptr, uint32_t n_zero = 0, bool capsules = false /* the world holds AVN_SHAPE_CAPSULE colliders */);
+template <class T> bool launch_update_aabb(const DW<T>&, const BP<T>&, const StepParams<T>&, hipStream_t, uint32_t* zero_words = nullptr, uint32_t n_zero = 0, bool capsules = false /* the world holds AVN_SHAPE_CAPSULE colliders */,
+                                          bool triangles = false /* the world holds AVN_SHAPE_TRIANGLE colliders (BP::col_tri is set) */);
 // counters_clean: n_dropped[0..2) is known to be zero (no memset launch)
 template <class T> void launch_interval_keys(const DW<T>&, const BP<T>&, typename BP<T>::Key* keys, uint32_t* vals, uint32_t* n_dropped, hipStream_t, bool counters_clean = false);
 // partial: 6 * ceil(C / 256) scalars; returns the number of partial records written
@@ -210,8 +230,9 @@ template <class T> void launch_clear_contact_rows(const CT<T>&, const uint32_t* 
 struct NpHookList { void* records = nullptr; uint32_t* count = nullptr; uint32_t cap = 0; uint32_t phase = 0; };
 // locals: the world holds child colliders (BP::col_lpos): their poses are computed by the HS instantiations only
 // capsules: the world holds AVN_SHAPE_CAPSULE colliders: their manifolds are computed by the HS instantiations' heavy kernel only
-struct NpHostList { void* queries = nullptr; uint32_t* count = nullptr; uint32_t cap = 0; uint32_t host_only = 0; NpHookList hook; bool locals = false; bool capsules = false;
-                    bool any() const { return queries != nullptr || hook.count != nullptr || locals || capsules; } };
+// triangles: the world holds AVN_SHAPE_TRIANGLE colliders (BP::col_tri is set): likewise, by the heavy kernel's CAP + TRI instantiation
+struct NpHostList { void* queries = nullptr; uint32_t* count = nullptr; uint32_t cap = 0; uint32_t host_only = 0; NpHookList hook; bool locals = false; bool capsules = false; bool triangles = false;
+                    bool any() const { return queries != nullptr || hook.count != nullptr || locals || capsules || triangles; } };
 template <class T> void launch_narrow_phase_hooked(const DW<T>&, const BP<T>&, const CT<T>&, const StepParams<T>&, bool dense, avn_contact_change* changes, uint32_t* n_changes, uint32_t* chg,
                                                    uint32_t* has, const void* records /* sorted by contact id, as the hook left them */, uint32_t n, hipStream_t);
 template <class T> void launch_narrow_phase_host(const DW<T>&, const BP<T>&, const CT<T>&, const StepParams<T>&, bool dense, avn_contact_change* changes, uint32_t* n_changes, uint32_t* chg,
@@ -353,6 +374,13 @@ template <class T> struct QueryStage {
     uint32_t *feature_id1, *feature_id2;
 };
 template <class T> void launch_contact_manifolds_query(const QueryStage<T>&, uint32_t n, hipStream_t, bool capsules = false /* the batch holds AVN_SHAPE_CAPSULE shapes */);
+// avn_triangle_manifolds: the batch query for pairs that may hold a triangle (k_triangle_manifolds_query: contact_manifolds_pair_sink<.., CAP = true, TRI = true>)
+template <class T> struct TriQueryStage {
+    QueryStage<T> q;
+    const T *vertices1, *vertices2;          // [9n] (a side without a triangle in the batch: nullptr)
+    const uint8_t *edge_flags1, *edge_flags2; // [n] (nullptr: AVN_TRIANGLE_ALL_EDGES)
+};
+template <class T> void launch_triangle_manifolds_query(const TriQueryStage<T>&, uint32_t n, hipStream_t);
 // k_transfer.hip: host-layout (interleaved xyz) <-> device Vec4 records
 template <class T> struct BodyStage {  // device staging copies of the avn_bodies arrays (nullptr = absent)
     const T *position, *rotation, *linear_velocity, *angular_velocity, *inv_mass, *inv_inertia_local, *center_of_mass, *linear_damping,
@@ -584,7 +612,7 @@ template <class T> void launch_spatial_project_velocity(const SV<T>&, hipStream_
 // capsule (here and below): the call may hold AVN_SHAPE_CAPSULE query shapes, so the kernels' CAPSULE instantiations run behind the first launch
 template <class T> void launch_spatial_cast_move(const SP<T>&, const SM<T>&, bool zero_stats, hipStream_t, bool capsule = false, bool ccap = false);
 template <class T> void launch_spatial_slide_phase(const SL<T>&, int phase, hipStream_t);
-template <class T> void launch_spatial_build(const DW<T>&, const BP<T>&, const SP<T>&, hipStream_t, bool ccap = false);
+template <class T> void launch_spatial_build(const DW<T>&, const BP<T>&, const SP<T>&, hipStream_t, bool ccap = false, bool triangles = false /* the world holds AVN_SHAPE_TRIANGLE colliders: never candidates */);
 template <class T> void launch_spatial_query(const SP<T>&, const SQ<T>&, int kind, hipStream_t, bool capsule = false, bool ccap = false);
 template <class T> void launch_spatial_reaim(const DW<T>&, const SP<T>&, const SCA<T>&, hipStream_t);
 // a caster group: kind SPQ_CLOSEST / SPQ_HITS / SPQ_CAST / SPQ_CAST_HITS with the per-query filter; q.stats is NOT zeroed (the run zeroes it once)

@@ -16,8 +16,17 @@
 #pragma once
 #include "avn_device.h"
 #include "../../include/avian_mi355x_spatial.h"   // AVN_SHAPE_CAPSULE
+#include "../../include/avian_mi355x_trimesh.h"   // AVN_SHAPE_TRIANGLE
 
 namespace avn {
+
+// a call that is inlined whatever the inliner's budget says: the TRI instantiations use it on the calls that pass the emitter, the sink and the faces by
+// reference -- out of line those objects would live in scratch memory (the instantiations without TRI leave the decision to the compiler, as ever)
+#if defined(__clang__)
+#define AVN_INLINE_CALL [[clang::always_inline]]
+#else
+#define AVN_INLINE_CALL
+#endif
 
 #define AVN_NP_MAX_RAW 16  // 4 + 4 vertex contacts + up to 8 edge/edge crossings of two quads
 
@@ -291,18 +300,25 @@ template <class T, class Em> __device__ void face_face_contacts(const Iso<T>& po
 // the manifolds of a Capsule collider (CAP instantiations only): avn_capsule_pair.h, which a translation unit that instantiates CAP = true includes
 template <class T, class Em> __device__ bool capsule_pair_manifold(uint32_t shape1, V3<T> he1, uint32_t shape2, V3<T> he2, const Iso<T>& pos12, T prediction, Em& em);
 
+// the manifolds of a Triangle collider (TRI instantiations only): avn_triangle_pair.h, which a translation unit that instantiates TRI = true includes
+template <class T> struct NpTri { V3<T> a, b, c; uint32_t flags; };   // the triangle in its collider's frame, its edge flags (include/avian_mi355x_trimesh.h)
+template <class T, class Em> __device__ bool triangle_pair_manifold(uint32_t shape1, V3<T> he1, uint32_t shape2, V3<T> he2, const Iso<T>& pos12, T prediction, const NpTri<T>& tri, Em& em);
+
 // contact_query::contact_manifolds for one pair (he: cuboid half extents, ball radius in x; CAP: a capsule's (r, h, .)); false = no manifold
 // CAP = false (every instantiation of a world without capsule colliders, the spatial queries, the swept CCD): the kinds are Ball and Cuboid,
 // anything that is not a ball is read as a cuboid.  CAP = true: a pair with an AVN_SHAPE_CAPSULE goes to capsule_pair_manifold.
+// TRI = true (a world that holds a triangle collider, avn_triangle_manifolds): a pair with an AVN_SHAPE_TRIANGLE goes to triangle_pair_manifold with
+// the triangle of that side (tri1 / tri2: read for a side whose shape is a triangle).
 // `defer` (optional): the cuboid-cuboid path has a cheap half -- the three SAT sweeps, after which most AABB-overlapping pairs are known to be
 // apart -- and a heavy half (support faces, clipping in the plane, conversion of up to 16 raw points).  With defer != nullptr and
 // *defer == false on entry the function stops after the SAT of a pair that survives it, leaves the separating direction in *axis and sets
 // *defer = true (nothing of `out` is valid); called again with *defer == true it skips the SAT and continues from *axis.  A caller that
 // gathers the survivors of a workgroup into dense waves (k_narrow_phase) runs the heavy half at full lane occupancy; the result is the
 // one-call result bit for bit.
-template <class T, class Sink, int MODE = 0, bool CAP = false>   // MODE 1: `defer` given and false on entry (stop after the SAT), 2: given and true (continue from *axis), 0: decided at run time
+template <class T, class Sink, int MODE = 0, bool CAP = false, bool TRI = false>   // MODE 1: `defer` given and false on entry (stop after the SAT), 2: given and true (continue from *axis), 0: decided at run time
 __device__ bool contact_manifolds_pair_sink(uint32_t shape1, V3<T> he1, V3<T> position1, Q4<T> rotation1, uint32_t shape2, V3<T> he2, V3<T> position2, Q4<T> rotation2,
-                                            T prediction, Sink& sink, V3<T>& normal_out, bool* defer = nullptr, V3<T>* axis = nullptr) {
+                                            T prediction, Sink& sink, V3<T>& normal_out, bool* defer = nullptr, V3<T>* axis = nullptr,
+                                            NpTri<T> tri1 = NpTri<T>(), NpTri<T> tri2 = NpTri<T>()) {
     Iso<T> isometry1 = make_isometry(position1, rotation1), isometry2 = make_isometry(position2, rotation2);
     Iso<T> pos12 = iso_inv_mul(isometry1, isometry2);
     NpEmit<T, Sink> em;
@@ -310,8 +326,17 @@ __device__ bool contact_manifolds_pair_sink(uint32_t shape1, V3<T> he1, V3<T> po
     const bool ball1 = shape1 == AVN_SHAPE_BALL, ball2 = shape2 == AVN_SHAPE_BALL;
     bool capsule = false;
     if constexpr (CAP) capsule = shape1 == AVN_SHAPE_CAPSULE || shape2 == AVN_SHAPE_CAPSULE;
-    if (capsule) {
-        if constexpr (CAP) { if (!capsule_pair_manifold<T, NpEmit<T, Sink>>(shape1, he1, shape2, he2, pos12, prediction, em)) return false; }
+    bool triangle = false;
+    if constexpr (TRI) triangle = shape1 == AVN_SHAPE_TRIANGLE || shape2 == AVN_SHAPE_TRIANGLE;
+    if (triangle) {
+        if constexpr (TRI) {
+            const bool first = shape1 == AVN_SHAPE_TRIANGLE;   // (selected value by value: a pointer to one of two locals would put both in memory)
+            const NpTri<T> tri{first ? tri1.a : tri2.a, first ? tri1.b : tri2.b, first ? tri1.c : tri2.c, first ? tri1.flags : tri2.flags};
+            if (!triangle_pair_manifold<T, NpEmit<T, Sink>>(shape1, he1, shape2, he2, pos12, prediction, tri, em)) return false;
+        }
+    } else if (capsule) {
+        if constexpr (CAP && TRI) { bool ok; AVN_INLINE_CALL ok = capsule_pair_manifold<T, NpEmit<T, Sink>>(shape1, he1, shape2, he2, pos12, prediction, em); if (!ok) return false; }
+        else if constexpr (CAP) { if (!capsule_pair_manifold<T, NpEmit<T, Sink>>(shape1, he1, shape2, he2, pos12, prediction, em)) return false; }
     } else if (ball1 && ball2) {  // contact_manifold_ball_ball
         T r1 = he1.x, r2 = he2.x;
         V3<T> dcenter = pos12.t;
@@ -367,7 +392,8 @@ __device__ bool contact_manifolds_pair_sink(uint32_t shape1, V3<T> he1, V3<T> po
         Face<T> f1, f2;
         cuboid_support_face(he1, best, f1);
         cuboid_support_face(he2, local_n2, f2);
-        face_face_contacts(pos12, f1, best, f2, em);
+        if constexpr (TRI) { AVN_INLINE_CALL face_face_contacts(pos12, f1, best, f2, em); }
+        else face_face_contacts(pos12, f1, best, f2, em);
     }
     normal_out = em.normal;
     return sink.n() > 0;

@@ -50,5 +50,8 @@ AVN_API avn_status avn_swept_ccd_results_get(avn_world* w, avn_swept_ccd_results
 AVN_API avn_status avn_swept_ccd_non_linear_set(avn_world* w, uint32_t enabled) { SP_GUARD(swept_ccd_non_linear_set(enabled)); }
 AVN_API avn_status avn_swept_ccd_capsules_set(avn_world* w, uint32_t enabled) { SP_GUARD(swept_ccd_capsules_set(enabled)); }
 AVN_API avn_status avn_swept_ccd_stats_get(avn_world* w, avn_swept_ccd_stats* o) { SP_GUARD(swept_ccd_stats_get(o)); }
+// include/avian_mi355x_trimesh.h (world/triangles.hpp)
+AVN_API avn_status avn_collider_triangles_upload(avn_world* w, const avn_collider_triangles* t) { if (w && w->impl) w->impl->touched(); SP_GUARD(collider_triangles_upload(t)); }
+AVN_API avn_status avn_triangle_manifolds(avn_world* w, const avn_triangle_pairs* q, const avn_query_manifolds_out* o) { SP_GUARD(triangle_manifolds(q, o)); }
 
 }  // extern "C"

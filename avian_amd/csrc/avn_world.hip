@@ -442,6 +442,7 @@ template <class T> struct World : WorldBase {
 #include "world/timers.hpp"
 #include "world/spatial.hpp"
 #include "world/ccd.hpp"
+#include "world/triangles.hpp"
 };
 
 template <class T> avn_status World<T>::diagnostics(avn_diagnostics* d) {

@@ -25,6 +25,7 @@
 #include "avn_kernels.h"
 #include "../../include/avian_mi355x_spatial.h"
 #include "../../include/avian_mi355x_ccd.h"
+#include "../../include/avian_mi355x_trimesh.h"
 
 namespace avn {
 
@@ -145,6 +146,9 @@ struct WorldBase {
     virtual avn_status swept_ccd_non_linear_set(uint32_t enabled) = 0;
     virtual avn_status swept_ccd_capsules_set(uint32_t enabled) = 0;
     virtual avn_status swept_ccd_stats_get(avn_swept_ccd_stats*) = 0;
+    // triangle colliders (include/avian_mi355x_trimesh.h; world/triangles.hpp)
+    virtual avn_status collider_triangles_upload(const avn_collider_triangles*) = 0;
+    virtual avn_status triangle_manifolds(const avn_triangle_pairs*, const avn_query_manifolds_out*) = 0;
 };
 
 // RCCL transport of the level-2 halo exchange (avn_comm.cpp; librccl is opened on first use)

@@ -27,7 +27,8 @@ namespace avn {
 // ---------------------------------------------------------------------------------------------------------
 // AABB (shape_aabb: avn_kernels.h)
 // CAP: the world holds AVN_SHAPE_CAPSULE colliders (shape_aabb's capsule case); a world without one launches the instantiation it always has
-template <class T, bool CAP = false>
+// TRI: the world holds AVN_SHAPE_TRIANGLE colliders (BP::col_tri is set; always with CAP, to bound the instantiations): min / max of the three posed vertices
+template <class T, bool CAP = false, bool TRI = false>
 __global__ __launch_bounds__(256) void k_update_aabb(DW<T> w, BP<T> bp, StepParams<T> p, uint32_t* __restrict__ zero_words, uint32_t n_zero) {
     uint32_t c = blockIdx.x * 256 + threadIdx.x;
     // the first kernel of a step also clears the step-scoped counters of the kernels behind it (constraint count, dropped / unsorted,
@@ -54,14 +55,16 @@ __global__ __launch_bounds__(256) void k_update_aabb(DW<T> w, BP<T> bp, StepPara
     T g = p.contact_tolerance + he4.w;
     V3<T> mn, mx;
     V3<T> h = xyz<T>(he4);
+    Vec4<T> tri[3] = {make4<T>(0, 0, 0, 0), make4<T>(0, 0, 0, 0), make4<T>(0, 0, 0, 0)};   // (constant indices only: registers)
+    if (TRI && shape == AVN_SHAPE_TRIANGLE) { tri[0] = bp.col_tri[3 * (size_t)c]; tri[1] = bp.col_tri[3 * (size_t)c + 1]; tri[2] = bp.col_tri[3 * (size_t)c + 2]; }
     if (speculative_margin <= T(0)) {
-        shape_aabb<T, CAP>(shape, h, pos, rot, mn, mx);
+        shape_aabb<T, CAP, TRI>(shape, h, pos, rot, mn, mx, tri);
     } else {
         Q4<T> end_rot = fast_renormalize(qmul(from_scaled_axis(av * delta_secs), rot));
         V3<T> end_pos = pos + clamp_length_max(lv * delta_secs, smax(speculative_margin, p.contact_tolerance));
         V3<T> mn0, mx0, mn1, mx1;
-        shape_aabb<T, CAP>(shape, h, pos, rot, mn0, mx0);
-        shape_aabb<T, CAP>(shape, h, end_pos, end_rot, mn1, mx1);
+        shape_aabb<T, CAP, TRI>(shape, h, pos, rot, mn0, mx0, tri);
+        shape_aabb<T, CAP, TRI>(shape, h, end_pos, end_rot, mn1, mx1, tri);
         mn = vmin(mn0, mn1);
         mx = vmax(mx0, mx1);
     }
@@ -831,7 +834,9 @@ __global__ __launch_bounds__(256) void k_long_finish(const LongItem* __restrict_
 
 // ---------------------------------------------------------------------------------------------------------
 // launchers
-template <class T> bool launch_update_aabb(const DW<T>& w, const BP<T>& bp, const StepParams<T>& p, hipStream_t s, uint32_t* zero_words, uint32_t n_zero, bool capsules) {
+template <class T> bool launch_update_aabb(const DW<T>& w, const BP<T>& bp, const StepParams<T>& p, hipStream_t s, uint32_t* zero_words, uint32_t n_zero, bool capsules, bool triangles) {
+    if (bp.n_colliders && triangles && bp.col_tri) hipLaunchKernelGGL((k_update_aabb<T, true, true>), dim3((bp.n_colliders + 255) / 256), dim3(256), 0, s, w, bp, p, zero_words, n_zero < 256u ? n_zero : 256u);
+    else
     if (bp.n_colliders && capsules) hipLaunchKernelGGL((k_update_aabb<T, true>), dim3((bp.n_colliders + 255) / 256), dim3(256), 0, s, w, bp, p, zero_words, n_zero < 256u ? n_zero : 256u);
     else
     if (bp.n_colliders) hipLaunchKernelGGL(k_update_aabb<T>, dim3((bp.n_colliders + 255) / 256), dim3(256), 0, s, w, bp, p, zero_words, n_zero < 256u ? n_zero : 256u);
@@ -1124,7 +1129,7 @@ uint32_t sweep_count_slots() { return SW_WAVES; }
 uint32_t sweep_pad_records() { return 8u; }  // k_sweep reads whole candidate batches: s_yz needs this many records past n
 
 #define INST(T)                                                                                          \
-    template bool launch_update_aabb<T>(const DW<T>&, const BP<T>&, const StepParams<T>&, hipStream_t, uint32_t*, uint32_t, bool);  \
+    template bool launch_update_aabb<T>(const DW<T>&, const BP<T>&, const StepParams<T>&, hipStream_t, uint32_t*, uint32_t, bool, bool);  \
     template void launch_interval_keys<T>(const DW<T>&, const BP<T>&, typename BP<T>::Key*, uint32_t*, uint32_t*, hipStream_t, bool); \
     template void launch_gather_sorted<T>(const DW<T>&, const BP<T>&, const uint32_t*, uint32_t, hipStream_t); \
     template void launch_sweep_ranges<T>(const BP<T>&, uint32_t, const SweepScratch&, hipStream_t, bool);     \

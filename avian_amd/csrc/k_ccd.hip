@@ -117,7 +117,7 @@ __device__ __forceinline__ bool ccd_pair(const DW<T>& w, const BP<T>& bp, const 
     if (bp.col_lpos && bp.col_lpos[c2].w != T(0)) return false;                 // a child collider (declared deviation)
     p.shape1 = i1.z & 0xFFu; p.shape2 = i2.z & 0xFFu;
     if constexpr (CAP) { if (p.shape1 == AVN_SHAPE_HOST || p.shape2 == AVN_SHAPE_HOST || p.shape1 > AVN_SHAPE_CAPSULE || p.shape2 > AVN_SHAPE_CAPSULE) return false; }
-    else if (p.shape1 > AVN_SHAPE_BALL || p.shape2 > AVN_SHAPE_BALL) return false;   // AVN_SHAPE_HOST, AVN_SHAPE_CAPSULE (declared deviations)
+    else if (p.shape1 > AVN_SHAPE_BALL || p.shape2 > AVN_SHAPE_BALL) return false;   // AVN_SHAPE_HOST, AVN_SHAPE_CAPSULE, AVN_SHAPE_TRIANGLE (declared deviations; kind 4 is above AVN_SHAPE_CAPSULE: the CAP form skips it too)
     const uint32_t bm2 = w.bmeta[p.b2];
     if (!c.include_dynamic[p.e] && meta_rb_type(bm2) == AVN_RB_DYNAMIC) return false;
     const bool has2 = meta_has_solver_body(bm2);

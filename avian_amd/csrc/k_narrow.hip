@@ -5,6 +5,7 @@
 #include "avn_kernels.h"
 #include "avn_narrow.h"
 #include "avn_capsule_pair.h"   // capsule colliders: the CAP instantiations of contact_manifolds_pair_sink (the HS heavy kernel, the batch query)
+#include "avn_triangle_pair.h"  // triangle colliders: the TRI instantiations (the HS heavy kernel of a world that holds a triangle, avn_triangle_manifolds)
 
 // measurement cut-offs (AVN_NP_DEBUG, tools/np_phases.sh): compiled in only by `make measure`; the default library has no switch that changes results
 #ifdef AVN_MEASURE
@@ -56,6 +57,47 @@ template <class T> void launch_contact_manifolds_query(const QueryStage<T>& s, u
 }
 template void launch_contact_manifolds_query<float>(const QueryStage<float>&, uint32_t, hipStream_t, bool);
 template void launch_contact_manifolds_query<double>(const QueryStage<double>&, uint32_t, hipStream_t, bool);
+
+// avn_triangle_manifolds (include/avian_mi355x_trimesh.h): the batch query for pairs that may hold a triangle; a row without one takes the same path as in
+// k_contact_manifolds_query<T, true>.  Like that kernel it keeps the NpManifold of its lane in a per-lane array (scratch): a query tool, not the step's path.
+template <class T>
+__global__ __launch_bounds__(64) void k_triangle_manifolds_query(TriQueryStage<T> ts, uint32_t n) {
+    const QueryStage<T>& s = ts.q;
+    uint32_t i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    V3<T> p1 = ld3(s.position1, i), p2 = ld3(s.position2, i);
+    Q4<T> r1{s.rotation1[4 * i], s.rotation1[4 * i + 1], s.rotation1[4 * i + 2], s.rotation1[4 * i + 3]};
+    Q4<T> r2{s.rotation2[4 * i], s.rotation2[4 * i + 1], s.rotation2[4 * i + 2], s.rotation2[4 * i + 3]};
+    const uint32_t k1 = s.shape1[i], k2 = s.shape2[i];
+    NpTri<T> t1{vzero<T>(), vzero<T>(), vzero<T>(), (uint32_t)AVN_TRIANGLE_ALL_EDGES}, t2 = t1;
+    if (k1 == AVN_SHAPE_TRIANGLE && ts.vertices1) { t1.a = ld3(ts.vertices1, 3 * (size_t)i); t1.b = ld3(ts.vertices1, 3 * (size_t)i + 1); t1.c = ld3(ts.vertices1, 3 * (size_t)i + 2); if (ts.edge_flags1) t1.flags = ts.edge_flags1[i]; }
+    if (k2 == AVN_SHAPE_TRIANGLE && ts.vertices2) { t2.a = ld3(ts.vertices2, 3 * (size_t)i); t2.b = ld3(ts.vertices2, 3 * (size_t)i + 1); t2.c = ld3(ts.vertices2, 3 * (size_t)i + 2); if (ts.edge_flags2) t2.flags = ts.edge_flags2[i]; }
+    NpManifold<T> m;
+    m.n = 0;
+    NpArraySink<T> sink{&m, p1 - p2};
+    bool has;
+    AVN_INLINE_CALL has = contact_manifolds_pair_sink<T, NpArraySink<T>, 0, true, true>(k1, ld3(s.half_extents1, i), p1, r1, k2, ld3(s.half_extents2, i), p2, r2, s.prediction[i], sink, m.normal,
+                                                                              nullptr, nullptr, t1, t2);
+    int cnt = has ? m.n : 0;
+    if (s.point_count) s.point_count[i] = (uint8_t)cnt;
+    st3(s.normal, i, has ? m.normal : vzero<T>());
+    for (int k = 0; k < AVN_MAX_QUERY_POINTS; ++k) {
+        size_t slot = (size_t)AVN_MAX_QUERY_POINTS * i + k;
+        bool live = k < cnt;
+        V3<T> a1 = live ? m.pts[k].anchor1 : vzero<T>();
+        st3(s.anchor1, slot, a1);
+        st3(s.anchor2, slot, live ? m.pts[k].anchor2 : vzero<T>());
+        st3(s.point, slot, live ? p1 + a1 : vzero<T>());
+        if (s.penetration) s.penetration[slot] = live ? m.pts[k].penetration : T(0);
+        if (s.feature_id1) s.feature_id1[slot] = live ? m.pts[k].fid1 : 0u;
+        if (s.feature_id2) s.feature_id2[slot] = live ? m.pts[k].fid2 : 0u;
+    }
+}
+template <class T> void launch_triangle_manifolds_query(const TriQueryStage<T>& s, uint32_t n, hipStream_t st) {
+    if (n) hipLaunchKernelGGL(k_triangle_manifolds_query<T>, dim3((n + 63) / 64), dim3(64), 0, st, s, n);
+}
+template void launch_triangle_manifolds_query<float>(const TriQueryStage<float>&, uint32_t, hipStream_t);
+template void launch_triangle_manifolds_query<double>(const TriQueryStage<double>&, uint32_t, hipStream_t);
 
 }  // namespace avn
 
@@ -141,7 +183,11 @@ static_assert(sizeof(NpHookC<float>) == sizeof(avn_hook_contact_f32) && sizeof(N
               offsetof(NpHookC<float>, fid1) == offsetof(avn_hook_contact_f32, feature_id1), "hook record layout");
 template <class T> struct NpHookCtx { NpHookC<T>* rec; uint32_t* count; uint32_t cap, phase; const NpHookC<T>* in; };   // in != nullptr: phase 3, this pair's record
 template <class T> __host__ __device__ __forceinline__ NpHookCtx<T> np_hook_ctx(const NpHookList& l) { return NpHookCtx<T>{(NpHookC<T>*)l.records, l.count, l.cap, l.phase, nullptr}; }
-template <class T, bool DENSE, bool HEAVY, bool HS = false, bool CAP = false>
+// Triangle colliders (include/avian_mi355x_trimesh.h) likewise: HEAVY = false defers every pair that holds one; HEAVY = true with TRI (k_narrow_phase_heavy's alone, set only for a
+// world that holds a triangle, always together with CAP) reads the triangle of the slot from BP::col_tri and computes the manifold (avn_triangle_pair.h).  A pair of a
+// triangle and an AVN_SHAPE_HOST collider has left for the host before.
+__device__ __forceinline__ bool np_heavy_kind(uint32_t shape) { return shape == AVN_SHAPE_CAPSULE || shape == AVN_SHAPE_TRIANGLE; }   // the kinds whose every pair is the heavy kernel's
+template <class T, bool DENSE, bool HEAVY, bool HS = false, bool CAP = false, bool TRI = false>
 __device__ void np_update_pair(const DW<T>& w, const BP<T>& bp, const CT<T>& ct, const StepParams<T>& p, const uint32_t c,
                                avn_contact_change* __restrict__ changes, uint32_t* __restrict__ n_changes, uint32_t* __restrict__ chg,
                                uint32_t* __restrict__ has, bool* deferred, V3<T>* axis, T* lds_col, NpHostQ<T>* hq = nullptr, const NpHostM<T>* hm = nullptr,
@@ -196,7 +242,9 @@ __device__ void np_update_pair(const DW<T>& w, const BP<T>& bp, const CT<T>& ct,
             friction = np_combine<T>(m1.x, r1 & 0xFFu, m2.x, r2 & 0xFFu);
             restitution = np_combine<T>(m1.y, (r1 >> 8) & 0xFFu, m2.y, (r2 >> 8) & 0xFFu);
         };
-        if (HEAVY) load_manifold_inputs();
+        // (TRI: the clip polygons of a triangle - cuboid pair live in registers, so this instantiation fetches what only the conversion needs AFTER the manifold.
+        //  The measurement cut-offs NP_DEBUG 1 and 3 of `make measure` are not meaningful in the TRI form: 1 is not honoured, 3 returns before these loads.)
+        if (HEAVY && !TRI) load_manifold_inputs();
         V3<T> lin_vel1 = have1 ? xyz<T>(w.lvel[body1]) : vzero<T>(), lin_vel2 = have2 ? xyz<T>(w.lvel[body2]) : vzero<T>();
         flags = (flags & ~(uint32_t)(AVN_CP_STATIC1 | AVN_CP_STATIC2)) | (is_static1 ? (uint32_t)AVN_CP_STATIC1 : 0u) | (is_static2 ? (uint32_t)AVN_CP_STATIC2 : 0u);
         const uint32_t cf1 = (ci1.z >> 8) & 0xFFu, cf2 = (ci2.z >> 8) & 0xFFu;
@@ -241,7 +289,7 @@ __device__ void np_update_pair(const DW<T>& w, const BP<T>& bp, const CT<T>& ct,
                 }
             }
         };
-        if (HEAVY) load_old_points();
+        if (HEAVY && !TRI) load_old_points();
         if (HEAVY && NP_DEBUG(p) == 3u) {   // timing cut-off: every input loaded, nothing computed or written
             T acc = ((x1.x + x2.y) + (q1.w + q2.x)) + ((world_com1.x + world_com2.y) + (lin_vel1.z + lin_vel2.x)) + ((ang_vel1.x + ang_vel2.y) + (friction + restitution)) + (sp1 + sp2);
 #pragma unroll
@@ -261,15 +309,24 @@ __device__ void np_update_pair(const DW<T>& w, const BP<T>& bp, const CT<T>& ct,
             normal = V3<T>{hm->normal[0], hm->normal[1], hm->normal[2]};
             for (uint32_t k = 0; k < n; ++k) sink.put(V3<T>{hm->anchor1[3 * k], hm->anchor1[3 * k + 1], hm->anchor1[3 * k + 2]}, hm->penetration[k], hm->fid1[k], hm->fid2[k]);
             has_manifold = n != 0u;
-        } else if (HS && !HEAVY && ((ci1.z & 0xFFu) == AVN_SHAPE_CAPSULE || (ci2.z & 0xFFu) == AVN_SHAPE_CAPSULE)) {
+        } else if (HS && !HEAVY && (np_heavy_kind(ci1.z & 0xFFu) || np_heavy_kind(ci2.z & 0xFFu))) {
             // a capsule collider's pair: its AABB / layer / margin work is done; the manifold (sp_seg_box's candidates) is the heavy kernel's -- the row joins the
-            // survivor lists as a cuboid pair does after its SAT, the axis slot unused
+            // survivor lists as a cuboid pair does after its SAT, the axis slot unused.  A triangle collider's pair does the same.
             has_manifold = false; defer = true;
+        } else if constexpr (HS && HEAVY && TRI) {
+            // (a world that holds a triangle: the slot's three records of BP::col_tri, read only where the slot's shape says triangle)
+            const uint32_t k1 = ci1.z & 0xFFu, k2 = ci2.z & 0xFFu;
+            NpTri<T> t1{vzero<T>(), vzero<T>(), vzero<T>(), 0u}, t2 = t1;
+            if (k1 == AVN_SHAPE_TRIANGLE) { const Vec4<T> a = bp.col_tri[3 * (size_t)slot1], b = bp.col_tri[3 * (size_t)slot1 + 1], cc = bp.col_tri[3 * (size_t)slot1 + 2]; t1 = NpTri<T>{xyz<T>(a), xyz<T>(b), xyz<T>(cc), scalar_to_bits(a.w) & 7u}; }
+            if (k2 == AVN_SHAPE_TRIANGLE) { const Vec4<T> a = bp.col_tri[3 * (size_t)slot2], b = bp.col_tri[3 * (size_t)slot2 + 1], cc = bp.col_tri[3 * (size_t)slot2 + 2]; t2 = NpTri<T>{xyz<T>(a), xyz<T>(b), xyz<T>(cc), scalar_to_bits(a.w) & 7u}; }
+            // (inlined here: as a call it would pass the emitter, the sink and the triangles through scratch memory)
+            AVN_INLINE_CALL has_manifold = contact_manifolds_pair_sink<T, Sink, 2, CAP, true>(k1, xyz<T>(he1), x1, q1, k2, xyz<T>(he2), x2, q2, max_contact_distance, sink, normal, &defer, axis, t1, t2);
         } else
         has_manifold = NP_DEBUG(p) == 1u ? false
             : contact_manifolds_pair_sink<T, Sink, HEAVY ? 2 : 1, HS && HEAVY && CAP>(ci1.z & 0xFFu, xyz<T>(he1), x1, q1, ci2.z & 0xFFu, xyz<T>(he2), x2, q2, max_contact_distance, sink, normal, &defer, axis);
         if (!HEAVY && defer) { if (NP_DEBUG(p) == 2u) defer = false; else { *deferred = true; return; } }
         if (!HEAVY && has_manifold) load_manifold_inputs();
+        if (HEAVY && TRI) { load_manifold_inputs(); load_old_points(); }
         if (HEAVY && NP_DEBUG(p) == 4u) {   // timing cut-off: the manifold's raw points are in LDS, nothing converted or written
             if (has_manifold && normal.x + T(sink.cnt) == T(123456.75)) chg[c] = 7u;
             return;
@@ -507,7 +564,7 @@ __global__ __launch_bounds__(NP_LIGHT_THREADS) void k_narrow_phase(DW<T> w, BP<T
 // workgroup (chunk, list) = (blockIdx / NP_LISTS, blockIdx mod NP_LISTS): the populated chunks come first in the grid.  The last workgroup of
 // a list to finish clears the list's counters for the next launch (every workgroup that takes part has read the count before it reports);
 // the workgroups beyond a list's end leave without touching anything.
-template <class T, bool DENSE, bool HS = false, bool CAP = false>
+template <class T, bool DENSE, bool HS = false, bool CAP = false, bool TRI = false>
 __global__ __launch_bounds__(NP_THREADS) void k_narrow_phase_heavy(DW<T> w, BP<T> bp, CT<T> ct, StepParams<T> p, avn_contact_change* __restrict__ changes,
                                                                    uint32_t* __restrict__ n_changes, uint32_t* __restrict__ chg, uint32_t* __restrict__ has, uint32_t n_pairs,
                                                                    NpHookCtx<T> hk = NpHookCtx<T>()) {
@@ -521,7 +578,8 @@ __global__ __launch_bounds__(NP_THREADS) void k_narrow_phase_heavy(DW<T> w, BP<T
         const size_t k = (size_t)list * np_list_segment(n_pairs) + i;
         V3<T> axis{ct.np_axis[3 * k], ct.np_axis[3 * k + 1], ct.np_axis[3 * k + 2]};
         bool deferred = false;
-        if (HS) np_update_pair<T, DENSE, true, true, CAP>(w, bp, ct, p, ct.np_row[k], changes, n_changes, chg, has, &deferred, &axis, s_pts + threadIdx.x, nullptr, nullptr, &hk);
+        if constexpr (HS && TRI) { AVN_INLINE_CALL np_update_pair<T, DENSE, true, true, CAP, true>(w, bp, ct, p, ct.np_row[k], changes, n_changes, chg, has, &deferred, &axis, s_pts + threadIdx.x, nullptr, nullptr, &hk); }
+        else if (HS) np_update_pair<T, DENSE, true, true, CAP, TRI>(w, bp, ct, p, ct.np_row[k], changes, n_changes, chg, has, &deferred, &axis, s_pts + threadIdx.x, nullptr, nullptr, &hk);
         else
         np_update_pair<T, DENSE, true>(w, bp, ct, p, ct.np_row[k], changes, n_changes, chg, has, &deferred, &axis, s_pts + threadIdx.x);
     }
@@ -556,8 +614,11 @@ size_t np_survivor_list_slack() { return (size_t)NP_LISTS * NP_LIGHT_THREADS; }
 size_t np_survivor_counter_bytes() { return (size_t)NP_LISTS * NP_CTR_STRIDE * sizeof(uint32_t); }
 template <class T, bool DENSE>
 static void launch_np_heavy(const DW<T>& w, const BP<T>& bp, const CT<T>& ct, const StepParams<T>& p, avn_contact_change* changes, uint32_t* n_changes, uint32_t* chg, uint32_t* has,
-                            uint32_t n_pairs, hipStream_t st, const NpHookList& hook = NpHookList(), bool hs = false, bool caps = false) {
+                            uint32_t n_pairs, hipStream_t st, const NpHookList& hook = NpHookList(), bool hs = false, bool caps = false, bool tris = false) {
     const uint32_t chunks = np_list_segment(n_pairs) / NP_THREADS;
+    // (a world with a triangle always takes CAP = true, TRI = true: one instantiation more per scalar and form, not two)
+    if (tris && bp.col_tri) hipLaunchKernelGGL((k_narrow_phase_heavy<T, DENSE, true, true, true>), dim3(chunks * NP_LISTS), dim3(NP_THREADS), 0, st, w, bp, ct, p, changes, n_changes, chg, has, n_pairs, np_hook_ctx<T>(hook));
+    else
     if (caps) hipLaunchKernelGGL((k_narrow_phase_heavy<T, DENSE, true, true>), dim3(chunks * NP_LISTS), dim3(NP_THREADS), 0, st, w, bp, ct, p, changes, n_changes, chg, has, n_pairs, np_hook_ctx<T>(hook));
     else
     if (hook.count || hs) hipLaunchKernelGGL((k_narrow_phase_heavy<T, DENSE, true>), dim3(chunks * NP_LISTS), dim3(NP_THREADS), 0, st, w, bp, ct, p, changes, n_changes, chg, has, n_pairs, np_hook_ctx<T>(hook));
@@ -690,7 +751,7 @@ template <class T> void launch_narrow_phase(const DW<T>& w, const BP<T>& bp, con
     else
     hipLaunchKernelGGL((k_narrow_phase<T, false>), dim3((n_active + NP_LIGHT_THREADS - 1) / NP_LIGHT_THREADS), dim3(NP_LIGHT_THREADS), 0, st, w, bp, ct, p, active, n_active, changes, n_changes, nullptr, nullptr, 0u, 0u);
     if (hl.host_only) return;   // (a retry hands no cuboid pair over: nothing for the second kernel)
-    launch_np_heavy<T, false>(w, bp, ct, p, changes, n_changes, nullptr, nullptr, n_active, st, hl.hook, hl.any(), hl.capsules);
+    launch_np_heavy<T, false>(w, bp, ct, p, changes, n_changes, nullptr, nullptr, n_active, st, hl.hook, hl.any(), hl.capsules, hl.triangles);
 }
 template <class T> void launch_narrow_phase_dense(const DW<T>& w, const BP<T>& bp, const CT<T>& ct, const StepParams<T>& p, uint32_t n_rows, uint32_t* chg, uint32_t* has,
                                                   uint32_t* n_remove, hipStream_t st, bool reset_counter, const NpHostList& hl) {
@@ -700,7 +761,7 @@ template <class T> void launch_narrow_phase_dense(const DW<T>& w, const BP<T>& b
     else
     hipLaunchKernelGGL((k_narrow_phase<T, true>), dim3((n_rows + NP_LIGHT_THREADS - 1) / NP_LIGHT_THREADS), dim3(NP_LIGHT_THREADS), 0, st, w, bp, ct, p, nullptr, n_rows, nullptr, n_remove, chg, has, 0u, 0u);
     if (hl.host_only) return;
-    launch_np_heavy<T, true>(w, bp, ct, p, nullptr, n_remove, chg, has, n_rows, st, hl.hook, hl.any(), hl.capsules);
+    launch_np_heavy<T, true>(w, bp, ct, p, nullptr, n_remove, chg, has, n_rows, st, hl.hook, hl.any(), hl.capsules, hl.triangles);
 }
 // the rows list[0 .. n_list) followed by range_base .. range_base + n_range: same per-row work and outputs as the dense form; the
 // removal counter is NOT reset (it continues the count of the launch over the older rows)
@@ -716,7 +777,7 @@ template <class T> void launch_narrow_phase_rows(const DW<T>& w, const BP<T>& bp
     if (!n_list && !range_base) hipLaunchKernelGGL((k_narrow_phase<T, true>), dim3((n_range + NP_LIGHT_THREADS - 1) / NP_LIGHT_THREADS), dim3(NP_LIGHT_THREADS), 0, st, w, bp, ct, p, nullptr, n_range, nullptr, n_remove, chg, has, 0u, 0u);
     else hipLaunchKernelGGL((k_narrow_phase<T, true>), dim3((n + NP_LIGHT_THREADS - 1) / NP_LIGHT_THREADS), dim3(NP_LIGHT_THREADS), 0, st, w, bp, ct, p, list, n, nullptr, n_remove, chg, has, n_list, range_base);
     if (hl.host_only) return;
-    launch_np_heavy<T, true>(w, bp, ct, p, nullptr, n_remove, chg, has, n, st, hl.hook, hl.any(), hl.capsules);
+    launch_np_heavy<T, true>(w, bp, ct, p, nullptr, n_remove, chg, has, n, st, hl.hook, hl.any(), hl.capsules, hl.triangles);
 }
 // the pairs the host answered (queries sorted by contact id on the host, manifolds in the same order): dense = the closed loop's chg / has outputs, else the change list
 template <class T> void launch_narrow_phase_host(const DW<T>& w, const BP<T>& bp, const CT<T>& ct, const StepParams<T>& p, bool dense, avn_contact_change* changes, uint32_t* n_changes,

@@ -63,7 +63,9 @@ template <class T> __device__ __forceinline__ void sp_pad_box(V3<T> a, V3<T> b, 
 // ---------------------------------------------------------------------------------------------------------
 // build
 // CCAP: a capsule collider is a candidate, its leaf box shape_aabb<T, true> padded like every other
-template <class T, bool CCAP = false>
+// TRI: the world holds AVN_SHAPE_TRIANGLE colliders (include/avian_mi355x_trimesh.h): left out exactly as a host shape is (no device geometry for the queries);
+// a world without one launches the instantiations it always has
+template <class T, bool CCAP = false, bool TRI = false>
 __global__ __launch_bounds__(256) void k_sp_snapshot(DW<T> w, BP<T> bp, SP<T> sp) {
     const uint32_t c = blockIdx.x * 256 + threadIdx.x;
     if (c >= sp.n) return;
@@ -80,7 +82,7 @@ __global__ __launch_bounds__(256) void k_sp_snapshot(DW<T> w, BP<T> bp, SP<T> sp
     // position, rotation and shape AABB; the others get an empty leaf box and never reach an exact test
     bool candidate = false;
     V3<T> mn{sp_inf<T>(), sp_inf<T>(), sp_inf<T>()}, mx{-sp_inf<T>(), -sp_inf<T>(), -sp_inf<T>()};
-    if (shape != AVN_SHAPE_HOST && (CCAP || shape != AVN_SHAPE_CAPSULE) && is_finite(pos) && is_finite(V3<T>{rot.x, rot.y, rot.z}) && finite_t(rot.w)) {
+    if (shape != AVN_SHAPE_HOST && (CCAP || shape != AVN_SHAPE_CAPSULE) && (!TRI || shape != AVN_SHAPE_TRIANGLE) && is_finite(pos) && is_finite(V3<T>{rot.x, rot.y, rot.z}) && finite_t(rot.w)) {
         V3<T> a, b;
         shape_aabb<T, CCAP>(shape, h, pos, rot, a, b);
         if (is_finite(a) && is_finite(b)) {
@@ -185,13 +187,15 @@ __global__ __launch_bounds__(256) void k_sp_refit(SP<T> sp) {
     }
 }
 
-template <class T> void launch_spatial_build(const DW<T>& w, const BP<T>& bp, const SP<T>& sp, hipStream_t s, bool ccap) {
+template <class T> void launch_spatial_build(const DW<T>& w, const BP<T>& bp, const SP<T>& sp, hipStream_t s, bool ccap, bool triangles) {
     const uint32_t n = sp.n;
     if (n == 0) return;
     const uint32_t nb = (n + 255) / 256;
     // bounds: min keys start at ~0, max keys at 0 (one memset each half)
     (void)hipMemsetAsync(sp.bounds, 0xFF, 3 * sizeof(uint32_t), s);
     (void)hipMemsetAsync(sp.bounds + 3, 0x00, 5 * sizeof(uint32_t), s);
+    if (triangles) { if (ccap) hipLaunchKernelGGL((k_sp_snapshot<T, true, true>), dim3(nb), dim3(256), 0, s, w, bp, sp); else hipLaunchKernelGGL((k_sp_snapshot<T, false, true>), dim3(nb), dim3(256), 0, s, w, bp, sp); }
+    else
     if (ccap) hipLaunchKernelGGL((k_sp_snapshot<T, true>), dim3(nb), dim3(256), 0, s, w, bp, sp);
     else hipLaunchKernelGGL((k_sp_snapshot<T>), dim3(nb), dim3(256), 0, s, w, bp, sp);
     hipLaunchKernelGGL((k_sp_morton<T>), dim3(nb), dim3(256), 0, s, sp);
@@ -1452,8 +1456,8 @@ static_assert(sizeof(SpatialSlide<float>) == sizeof(avn_spatial_slide_f32) && si
               offsetof(SpatialSlide<double>, reserved) == offsetof(avn_spatial_slide_f64, reserved),
               "slide record layout");
 static_assert(SP_SLIDE_PLANES >= AVN_SPATIAL_MAX_PLANES + 1, "plane slots");
-template void launch_spatial_build<float>(const DW<float>&, const BP<float>&, const SP<float>&, hipStream_t, bool);
-template void launch_spatial_build<double>(const DW<double>&, const BP<double>&, const SP<double>&, hipStream_t, bool);
+template void launch_spatial_build<float>(const DW<float>&, const BP<float>&, const SP<float>&, hipStream_t, bool, bool);
+template void launch_spatial_build<double>(const DW<double>&, const BP<double>&, const SP<double>&, hipStream_t, bool, bool);
 template void launch_spatial_query<float>(const SP<float>&, const SQ<float>&, int, hipStream_t, bool, bool);
 template void launch_spatial_query<double>(const SP<double>&, const SQ<double>&, int, hipStream_t, bool, bool);
 template void launch_spatial_reaim<float>(const DW<float>&, const SP<float>&, const SCA<float>&, hipStream_t);

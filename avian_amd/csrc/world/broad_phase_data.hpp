@@ -134,6 +134,7 @@
             GROW(b_aabb_min, cc, bp.aabb_min); GROW(b_aabb_max, cc, bp.aabb_max); GROW(b_iv, cc, bp.iv_collider);
             GROW(b_s_minx, cc, bp.s_minx); GROW(b_s_maxx, cc, bp.s_maxx); GROW(b_s_yz, cc + sweep_pad_records(), bp.s_yz); GROW(b_s_bb, sweep_bounds_words((uint32_t)cc), bp.s_bb); bp.s_bb2 = bp.s_bb + sweep_bounds_level2_offset((uint32_t)cc); GROW(b_s_end, cc, bp.s_end);
             GROW(b_s_info, cc, bp.s_info); GROW(b_s_flags, cc, bp.s_flags);
+            if (b_col_tri.p) { bp.col_tri = nullptr; ALLOC(b_col_tri.ensure(col_tri_bytes<T>(cc))); }   // (triangle colliders: the capacity of col_he; the table itself is cleared below)
             ALLOC(b_keys_a.ensure(cc * sizeof(Key))); ALLOC(b_keys_b.ensure(cc * sizeof(Key))); ALLOC(b_vals_a.ensure(cc * 4)); ALLOC(b_vals_b.ensure(cc * 4));
             ALLOC(b_hist.ensure(((size_t)256 * radix_blocks((uint32_t)cc) + 256) * 4));
             ALLOC(b_block_sums.ensure((std::max<size_t>(scan_block_sums_needed(256 * radix_blocks((uint32_t)cc)), scan_block_sums_needed((uint32_t)cc * sweep_count_slots())) + 16) * 4));
@@ -184,6 +185,7 @@
         { avn_status sh = hs_on_colliders_upload(c); if (sh != AVN_OK) return sh; }
         { avn_status sh = hk_on_colliders_upload(c); if (sh != AVN_OK) return sh; }
         bp.col_lpos = nullptr; bp.col_lrot = nullptr; tf_any = false;   // (every collider sits on its body again until avn_collider_transforms_upload says otherwise)
+        bp.col_tri = nullptr;   // (and no triangle has vertices until avn_collider_triangles_upload says otherwise: hs_on_colliders_upload counted the kind)
         if (slp_on) {   // colliders spawned inside the loop join the island manager's RigidBodyColliders lists (upload order = Add order)
             for (uint32_t i = 0; i < C; ++i) {
                 if (isl.has_collider(c->entity_index[i])) continue;

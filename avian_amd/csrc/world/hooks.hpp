@@ -134,7 +134,7 @@
         ALLOC(pin_hk.ensure((size_t)n * HK_REC + 64));
         HIPCHK(hipMemsetAsync(d_cnt, 0, 4, s));
         NpHostList l;
-        l.hook.records = b_hk_rec.p; l.hook.count = d_cnt; l.hook.cap = hk_rec_cap; l.hook.phase = 2; l.locals = tf_any; l.capsules = cap_count != 0;
+        l.hook.records = b_hk_rec.p; l.hook.count = d_cnt; l.hook.cap = hk_rec_cap; l.hook.phase = 2; l.locals = tf_any; l.capsules = cap_count != 0; l.triangles = tri_count != 0;
         hs_rerun(l, dense, np, changes, n_changes, chg, has, s);
         if (hs_any() && hs_stats.last_manifold_queries)   // (pending pairs with a host-shaped collider: their manifolds are still in the answer list)
             { launch_narrow_phase_host<T>(dw, bp, ct, np, dense, changes, n_changes, chg, has, b_hs_mq.p, b_hs_mm.p, hs_stats.last_manifold_queries, s, l.hook); ++launches; }

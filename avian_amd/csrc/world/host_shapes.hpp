@@ -34,6 +34,7 @@
     avn_status hs_on_colliders_upload(const avn_colliders* c) {
         hs_slots.clear();
         cap_count = 0;
+        tri_on_colliders_upload(c);   // (triangle colliders, world/triangles.hpp: counted; their table names the old upload)
         for (uint32_t i = 0; i < c->count; ++i) { if (c->shape[i] == AVN_SHAPE_HOST) hs_slots.push_back(i); else if (c->shape[i] == AVN_SHAPE_CAPSULE) ++cap_count; }
         if (hs_slots.empty()) return AVN_OK;
         const size_t n = hs_slots.size();
@@ -85,13 +86,14 @@
         if (st != AVN_OK) return st;
         l.locals = tf_any;                       // (child colliders: the HS instantiations compute their poses)
         l.capsules = cap_count != 0;             // (capsule colliders: the HS heavy kernel computes their manifolds)
+        l.triangles = tri_count != 0;            // (triangle colliders: likewise, its CAP + TRI instantiation)
         *out = l;
         return AVN_OK;
     }
     NpHookList hk_phase1() const { NpHookList h; if (hk_modify_active() && b_hk_cnt.p) { h.count = b_hk_cnt.as<uint32_t>(); h.phase = 1; } return h; }
     NpHostList hs_list(uint32_t host_only = 0) const {
         NpHostList l;
-        l.capsules = cap_count != 0;
+        l.capsules = cap_count != 0; l.triangles = tri_count != 0;
         if (!hs_any()) return l;
         l.queries = b_hs_mq.p; l.count = b_hs_cnt.as<uint32_t>(); l.cap = hs_mq_cap; l.host_only = host_only; l.locals = tf_any;
         return l;

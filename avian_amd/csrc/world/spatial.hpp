@@ -11,7 +11,7 @@
         b_mv_pend, b_mv_pcount;   // cast_move's hand-over: the colliders overlapping each query at its start [n * AVN_SPATIAL_MAX_HITS], their counts [n]
     uint32_t sp_cap = 0;
     bool sp_valid = false;      // a snapshot exists and no table changed since (bodies / colliders / collider transforms uploads and avn_despawn clear it)
-    uint32_t sp_host = 0;       // the colliders the snapshot leaves out: AVN_SHAPE_HOST, and AVN_SHAPE_CAPSULE unless sp_capsules is set
+    uint32_t sp_host = 0;       // the colliders the snapshot leaves out: AVN_SHAPE_HOST, AVN_SHAPE_TRIANGLE, and AVN_SHAPE_CAPSULE unless sp_capsules is set
     bool sp_capsules = false;   // avn_spatial_capsule_colliders_set: capsule colliders are candidates of the queries (sticky, off by default)
     bool sp_ccap = false;       // the snapshot holds capsule colliders as candidates: every traversal launch takes its CCAP instantiation
     unsigned long long sp_visits[3] = {0, 0, 0};   // last query call: node boxes tested, exact tests, stack overflow
@@ -42,9 +42,9 @@
         if (st != AVN_OK) return st;
         sp.n = C;
         sp_ccap = sp_capsules && cap_count != 0;   // (a world without a capsule, or with the switch off, launches what it always has)
-        launch_spatial_build<T>(dw, bp, sp, stream, sp_ccap);
+        launch_spatial_build<T>(dw, bp, sp, stream, sp_ccap, tri_count != 0);
         HIPCHK(hipGetLastError());
-        sp_host = (uint32_t)hs_slots.size() + (sp_capsules ? 0u : cap_count);
+        sp_host = (uint32_t)hs_slots.size() + (sp_capsules ? 0u : cap_count) + tri_count;   // (triangle colliders: left out exactly as host shapes are)
         sp_valid = true;
         return AVN_OK;
     }
@@ -57,6 +57,10 @@
 
     avn_status sp_check(uint32_t flags) {
         if (!sp_valid) { error = "spatial query: no avn_spatial_update since the tables last changed"; return AVN_ERR_STATE; }
+        if (sp_host && tri_count && !(flags & AVN_SPATIAL_SKIP_HOST_SHAPES)) {
+            error = "spatial query: the snapshot holds AVN_SHAPE_TRIANGLE colliders (and possibly AVN_SHAPE_HOST / AVN_SHAPE_CAPSULE ones), which the queries have no device geometry for (AVN_SPATIAL_SKIP_HOST_SHAPES leaves them out)";
+            return AVN_ERR_STATE;
+        }
         if (sp_host && !(flags & AVN_SPATIAL_SKIP_HOST_SHAPES)) {
             error = sp_capsules ? "spatial query: the snapshot holds AVN_SHAPE_HOST colliders, which the queries have no device geometry for (AVN_SPATIAL_SKIP_HOST_SHAPES leaves them out)"
                                 : "spatial query: the snapshot holds AVN_SHAPE_HOST or AVN_SHAPE_CAPSULE colliders, which the queries have no device geometry for (AVN_SPATIAL_SKIP_HOST_SHAPES leaves them out; avn_spatial_capsule_colliders_set makes capsules candidates)";

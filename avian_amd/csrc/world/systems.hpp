@@ -406,6 +406,7 @@
     avn_status run_system(avn_system sys) override {
         avn_status st = need_bodies();
         if (st != AVN_OK) return st;
+        if ((st = tri_need_table()) != AVN_OK) return st;
         if (sys == AVN_SYS_SOLVER && ccd.n && !ccd_closed_loop()) { error = "run_system: a SweptCcd list needs the device closed loop (avn_pipeline_enable(1)); avn_swept_ccd_upload(NULL) clears it"; return AVN_ERR_STATE; }
         if (despawn_needs_joints) { error = "run_system: avn_despawn removed joints: upload the remaining joints (avn_joints_upload) first"; return AVN_ERR_STATE; }
         if (despawn_broken) { error = "run_system: an avn_despawn failed half-way; restart the closed loop"; return AVN_ERR_STATE; }
@@ -420,6 +421,7 @@
     avn_status profile_system(avn_system sys, uint32_t repeats, double* total_ms, uint32_t* n_launches) override {
         avn_status st = need_bodies();
         if (st != AVN_OK) return st;
+        if ((st = tri_need_table()) != AVN_OK) return st;
         if ((st = materialize_impulses()) != AVN_OK) return st;
         if ((st = rebuild_joint_schedules()) != AVN_OK) return st;
         if ((st = rebuild_incidence()) != AVN_OK) return st;
@@ -443,6 +445,7 @@
     avn_status step() override {
         avn_status st = need_bodies();
         if (st != AVN_OK) return st;
+        if ((st = tri_need_table()) != AVN_OK) return st;
         if (ccd.n && !ccd_closed_loop()) { error = "avn_step: a SweptCcd list needs the device closed loop (avn_pipeline_enable(1)); avn_swept_ccd_upload(NULL) clears it"; return AVN_ERR_STATE; }
         for (bool& b : dg_stamped) b = false;
         dg_np = false; ccd_stamped = false;

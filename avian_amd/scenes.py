@@ -456,13 +456,18 @@ class MeshScene(Scene):
     def n_faces(self) -> int:
         return int((self.col_shape == F.SHAPE_TRIANGLE).sum())
 
-    def collider_kwargs(self, host_capsules: bool = False):
-        """What a world uploads: no backend has the triangle as a kind of its own, so the faces go up as SHAPE_HOST (the world answers them through its
-        host-shape callbacks, e.g. tests/triangle_collider_reference.py: TriangleHost); `col_shape` keeps the real kinds for those callbacks.
-        `host_capsules`: the capsules too, for a backend without the capsule kind (the oracle)."""
-        hosted = (self.col_shape == F.SHAPE_TRIANGLE) | (host_capsules & (self.col_shape == F.SHAPE_CAPSULE))
-        return dict(entity_index=self.col_entity, body=self.col_body, shape=np.where(hosted, F.SHAPE_HOST, self.col_shape).astype(np.uint8),
-                    half_extents=self.col_half_extents)
+    def collider_kwargs(self, host_capsules: bool = False, native_triangles: bool = False):
+        """What a world uploads.  By default the faces go up as SHAPE_HOST (the world answers them through its host-shape callbacks, e.g.
+        tests/triangle_collider_reference.py: TriangleHost); `col_shape` keeps the real kinds for those callbacks.
+        `host_capsules`: the capsules too, for a backend without the capsule kind (the oracle).
+        `native_triangles` (the HIP backend, include/avian_mi355x_trimesh.h): the real kinds plus `triangles=`, the table World.colliders_upload sends
+        behind the colliders."""
+        hosted = ((not native_triangles) & (self.col_shape == F.SHAPE_TRIANGLE)) | (host_capsules & (self.col_shape == F.SHAPE_CAPSULE))
+        kw = dict(entity_index=self.col_entity, body=self.col_body, shape=np.where(hosted, F.SHAPE_HOST, self.col_shape).astype(np.uint8),
+                  half_extents=self.col_half_extents)
+        if native_triangles:
+            kw["triangles"] = dict(vertices=np.asarray(self.vertices, np.float64).reshape(len(self.col_shape), 9), edge_flags=np.asarray(self.edge_flags, np.uint8))
+        return kw
 
     def surface_height(self, x, z):
         """The height of the triangulated ground under (x, z) (clamped to the grid's extent)."""

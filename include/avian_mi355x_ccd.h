@@ -22,7 +22,7 @@
  *     body's entity).
  *  2. candidates: the live contact rows (one per AABB-overlapping pair) with c1 in either slot; c2 is the other slot, b2 its body.  A row is
  *     not tested when c2 is a child collider (the reference would cast it at the body's pose, `TODO: Support child colliders`: a declared
- *     deviation); when either collider is AVN_SHAPE_HOST (a declared deviation: the device has no geometry for it), or AVN_SHAPE_CAPSULE
+ *     deviation); when either collider is AVN_SHAPE_HOST or AVN_SHAPE_TRIANGLE (avian_mi355x_trimesh.h) (declared deviations: the pass has no geometry for them), or AVN_SHAPE_CAPSULE
  *     unless avn_swept_ccd_capsules_set is on ("capsule colliders" below); when include_dynamic == 0 and b2 is dynamic, awake or
  *     asleep; when |w1 - w2|^2 < angular_threshold^2 and |v1 - v2|^2 < linear_threshold^2 (the thresholds cast to the world's scalar, then
  *     squared; v2, w2 = b2's SolverBody velocities, 0 when it has none).  Sensors ARE tested: the reference does not filter them.
