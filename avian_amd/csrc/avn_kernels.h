@@ -233,21 +233,47 @@ struct NpHookList { void* records = nullptr; uint32_t* count = nullptr; uint32_t
 // triangles: the world holds AVN_SHAPE_TRIANGLE colliders (BP::col_tri is set): likewise, by the heavy kernel's CAP + TRI instantiation
 struct NpHostList { void* queries = nullptr; uint32_t* count = nullptr; uint32_t cap = 0; uint32_t host_only = 0; NpHookList hook; bool locals = false; bool capsules = false; bool triangles = false;
                     bool any() const { return queries != nullptr || hook.count != nullptr || locals || capsules || triangles; } };
-template <class T> void launch_narrow_phase_hooked(const DW<T>&, const BP<T>&, const CT<T>&, const StepParams<T>&, bool dense, avn_contact_change* changes, uint32_t* n_changes, uint32_t* chg,
-                                                   uint32_t* has, const void* records /* sorted by contact id, as the hook left them */, uint32_t n, hipStream_t);
-template <class T> void launch_narrow_phase_host(const DW<T>&, const BP<T>&, const CT<T>&, const StepParams<T>&, bool dense, avn_contact_change* changes, uint32_t* n_changes, uint32_t* chg,
-                                                 uint32_t* has, const void* queries /* sorted by contact id */, const void* manifolds, uint32_t n, hipStream_t, const NpHookList& hook = NpHookList());
+// which rows a launch of the narrow phase visits.  The form is explicit: a launch is recorded as this struct and replayed from it (World::np_launch)
+struct NpRows {
+    enum Form : uint32_t { ACTIVE, DENSE, ADDED } form;
+    const uint32_t* list; uint32_t n_list, range_base, n_range;
+    // NarrowPhase::update_contacts over the active pairs list[0 .. n): the sparse form, changes[0 .. *counter) in arbitrary order (the host sorts by id)
+    static NpRows active(const uint32_t* list, uint32_t n) { return NpRows{ACTIVE, list, n, 0u, 0u}; }
+    // dense form (device closed loop): every row id < n_rows with AVN_CP_ROW_USED is a pair; the row's status change goes to chg[id] / has[id]
+    // (id order = the order NarrowPhase::update walks the status bits)
+    static NpRows dense(uint32_t n_rows) { return NpRows{DENSE, nullptr, 0u, 0u, n_rows}; }
+    // the rows a step added, list[0 .. n_list) followed by range_base .. range_base + n_range: same per-row work and outputs as the dense form
+    static NpRows added(const uint32_t* list, uint32_t n_list, uint32_t range_base, uint32_t n_range) { return NpRows{ADDED, list, n_list, range_base, n_range}; }
+    uint32_t count() const { return n_list + n_range; }
+};
+// k_narrow_phase's (active, n_active, n_list, range_base) for a set of rows, and the row id of lane a < n from them
+struct NpRowArgs { const uint32_t* list; uint32_t n, n_list, range_base; };
+inline NpRowArgs np_row_args(const NpRows& r) {
+    // (the kernel reads "no list, n_list = 0, range_base = 0" as the plain dense form.  An added launch with an empty list and base 0 -- a world's first
+    //  pairs -- visits exactly those rows, so it is passed as that form, without the list pointer the kernel would otherwise take for a row list)
+    if (r.form == NpRows::ADDED && (r.n_list || r.range_base)) return NpRowArgs{r.list, r.count(), r.n_list, r.range_base};
+    return NpRowArgs{r.form == NpRows::ACTIVE ? r.list : nullptr, r.count(), 0u, 0u};
+}
+// DENSE with a row list: ids list[0 .. n_list), then the contiguous fresh ids range_base ..; DENSE without one: every row id; sparse: the active list
+template <bool DENSE> __host__ __device__ __forceinline__ uint32_t np_row_id(const uint32_t* list, uint32_t n_list, uint32_t range_base, uint32_t a) {
+    return !DENSE ? list[a] : (list || n_list || range_base) ? (a < n_list ? list[a] : range_base + (a - n_list)) : a;
+}
+// where a launch leaves its results: the sparse form appends to changes[], the dense form writes chg[id] / has[id]
+struct NpOut {
+    avn_contact_change* changes;
+    uint32_t* counter;   // sparse form: the number of changes appended; dense form: the number of rows to REMOVE (never reset by a launch: it runs on through a step's launches)
+    uint32_t *chg, *has;
+    bool dense() const { return chg != nullptr; }
+};
+// the pairs a hook answered (records sorted by contact id, as the hook left them) / the host answered (queries sorted by contact id, manifolds in the same order)
+template <class T> void launch_narrow_phase_hooked(const DW<T>&, const BP<T>&, const CT<T>&, const StepParams<T>&, const NpOut&, const void* records, uint32_t n, hipStream_t);
+template <class T> void launch_narrow_phase_host(const DW<T>&, const BP<T>&, const CT<T>&, const StepParams<T>&, const NpOut&, const void* queries, const void* manifolds, uint32_t n, hipStream_t,
+                                                 const NpHookList& hook = NpHookList());
 template <class T> void launch_host_aabb_queries(const DW<T>&, const BP<T>&, const StepParams<T>&, const uint32_t* slots, uint32_t n, void* out, hipStream_t);
 template <class T> void launch_host_aabb_apply(const BP<T>&, const StepParams<T>&, const uint32_t* slots, uint32_t n, const void* in, hipStream_t);
-// NarrowPhase::update_contacts over the active pairs; changes[0..*n_changes) in arbitrary order (the host sorts by id)
-template <class T> void launch_narrow_phase(const DW<T>&, const BP<T>&, const CT<T>&, const StepParams<T>&, const uint32_t* active, uint32_t n_active,
-                                            avn_contact_change* changes, uint32_t* n_changes, hipStream_t, const NpHostList& hl = NpHostList());
-// dense form (device closed loop): every row id < n_rows with AVN_CP_ROW_USED is a pair; the row's status change goes to chg[id] / has[id]
-// (id order = the order NarrowPhase::update walks the status bits) and rows that must be removed are counted in *n_remove
-template <class T> void launch_narrow_phase_dense(const DW<T>&, const BP<T>&, const CT<T>&, const StepParams<T>&, uint32_t n_rows, uint32_t* chg, uint32_t* has,
-                                                  uint32_t* n_remove, hipStream_t, bool reset_counter = true /* false: *n_remove is known to be zero (no memset launch) */, const NpHostList& hl = NpHostList());
-template <class T> void launch_narrow_phase_rows(const DW<T>&, const BP<T>&, const CT<T>&, const StepParams<T>&, const uint32_t* list, uint32_t n_list, uint32_t range_base, uint32_t n_range,
-                                                 uint32_t* chg, uint32_t* has, uint32_t* n_remove, hipStream_t, const NpHostList& hl = NpHostList());   // rows added this step (counter not reset)
+// the light kernel over `rows`, then the heavy one over its survivors.  The sparse form zeroes *out.counter first, unless the launch is a second pass over the same rows
+// (a host-only retry, hooks phase 2)
+template <class T> void launch_narrow_phase(const DW<T>&, const BP<T>&, const CT<T>&, const StepParams<T>&, const NpRows& rows, const NpOut& out, hipStream_t, const NpHostList& hl = NpHostList());
 // manifold m of the solver-side arrays <- row handles[m] of the contact table (GraphColor::manifold_handles indirection)
 // store_contact_impulses' write into the ContactGraph (plugin.rs:744-749): table row <- DW::mp_w
 template <class T> void launch_scatter_impulses(const DW<T>&, const CT<T>&, const uint32_t* handles, hipStream_t);

@@ -19,22 +19,13 @@ namespace avn {
 template <class T> __device__ __forceinline__ V3<T> ld3(const T* p, size_t i) { return {p[3 * i], p[3 * i + 1], p[3 * i + 2]}; }
 template <class T> __device__ __forceinline__ void st3(T* p, size_t i, V3<T> v) { if (p) { p[3 * i] = v.x; p[3 * i + 1] = v.y; p[3 * i + 2] = v.z; } }
 
-// CAP: the batch holds AVN_SHAPE_CAPSULE shapes (the host scans the kinds); a batch without one launches the Ball / Cuboid instantiation as ever
-template <class T, bool CAP = false>
-__global__ __launch_bounds__(64) void k_contact_manifolds_query(QueryStage<T> s, uint32_t n) {
-    uint32_t i = blockIdx.x * 64 + threadIdx.x;
-    if (i >= n) return;
-    V3<T> p1 = ld3(s.position1, i), p2 = ld3(s.position2, i);
-    Q4<T> r1{s.rotation1[4 * i], s.rotation1[4 * i + 1], s.rotation1[4 * i + 2], s.rotation1[4 * i + 3]};
-    Q4<T> r2{s.rotation2[4 * i], s.rotation2[4 * i + 1], s.rotation2[4 * i + 2], s.rotation2[4 * i + 3]};
-    NpManifold<T> m;
-    bool has;
-    if (CAP) {
-        m.n = 0;
-        NpArraySink<T> sink{&m, p1 - p2};
-        has = contact_manifolds_pair_sink<T, NpArraySink<T>, 0, true>(s.shape1[i], ld3(s.half_extents1, i), p1, r1, s.shape2[i], ld3(s.half_extents2, i), p2, r2, s.prediction[i], sink, m.normal);
-    } else
-    has = contact_manifolds_pair<T>(s.shape1[i], ld3(s.half_extents1, i), p1, r1, s.shape2[i], ld3(s.half_extents2, i), p2, r2, s.prediction[i], m);
+// what the two batch query kernels share: row i's poses in, its manifold out
+template <class T> __device__ __forceinline__ void np_query_poses(const QueryStage<T>& s, uint32_t i, V3<T>& p1, Q4<T>& r1, V3<T>& p2, Q4<T>& r2) {
+    p1 = ld3(s.position1, i); p2 = ld3(s.position2, i);
+    r1 = Q4<T>{s.rotation1[4 * i], s.rotation1[4 * i + 1], s.rotation1[4 * i + 2], s.rotation1[4 * i + 3]};
+    r2 = Q4<T>{s.rotation2[4 * i], s.rotation2[4 * i + 1], s.rotation2[4 * i + 2], s.rotation2[4 * i + 3]};
+}
+template <class T> __device__ __forceinline__ void np_query_store(const QueryStage<T>& s, uint32_t i, bool has, const NpManifold<T>& m, V3<T> p1) {
     int cnt = has ? m.n : 0;
     if (s.point_count) s.point_count[i] = (uint8_t)cnt;
     st3(s.normal, i, has ? m.normal : vzero<T>());
@@ -49,6 +40,23 @@ __global__ __launch_bounds__(64) void k_contact_manifolds_query(QueryStage<T> s,
         if (s.feature_id1) s.feature_id1[slot] = live ? m.pts[k].fid1 : 0u;
         if (s.feature_id2) s.feature_id2[slot] = live ? m.pts[k].fid2 : 0u;
     }
+}
+// CAP: the batch holds AVN_SHAPE_CAPSULE shapes (the host scans the kinds); a batch without one launches the Ball / Cuboid instantiation as ever
+template <class T, bool CAP = false>
+__global__ __launch_bounds__(64) void k_contact_manifolds_query(QueryStage<T> s, uint32_t n) {
+    uint32_t i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= n) return;
+    V3<T> p1, p2; Q4<T> r1, r2;
+    np_query_poses(s, i, p1, r1, p2, r2);
+    NpManifold<T> m;
+    bool has;
+    if (CAP) {
+        m.n = 0;
+        NpArraySink<T> sink{&m, p1 - p2};
+        has = contact_manifolds_pair_sink<T, NpArraySink<T>, 0, true>(s.shape1[i], ld3(s.half_extents1, i), p1, r1, s.shape2[i], ld3(s.half_extents2, i), p2, r2, s.prediction[i], sink, m.normal);
+    } else
+    has = contact_manifolds_pair<T>(s.shape1[i], ld3(s.half_extents1, i), p1, r1, s.shape2[i], ld3(s.half_extents2, i), p2, r2, s.prediction[i], m);
+    np_query_store(s, i, has, m, p1);
 }
 template <class T> void launch_contact_manifolds_query(const QueryStage<T>& s, uint32_t n, hipStream_t st, bool capsules) {
     if (!n) return;
@@ -65,9 +73,8 @@ __global__ __launch_bounds__(64) void k_triangle_manifolds_query(TriQueryStage<T
     const QueryStage<T>& s = ts.q;
     uint32_t i = blockIdx.x * 64 + threadIdx.x;
     if (i >= n) return;
-    V3<T> p1 = ld3(s.position1, i), p2 = ld3(s.position2, i);
-    Q4<T> r1{s.rotation1[4 * i], s.rotation1[4 * i + 1], s.rotation1[4 * i + 2], s.rotation1[4 * i + 3]};
-    Q4<T> r2{s.rotation2[4 * i], s.rotation2[4 * i + 1], s.rotation2[4 * i + 2], s.rotation2[4 * i + 3]};
+    V3<T> p1, p2; Q4<T> r1, r2;
+    np_query_poses(s, i, p1, r1, p2, r2);
     const uint32_t k1 = s.shape1[i], k2 = s.shape2[i];
     NpTri<T> t1{vzero<T>(), vzero<T>(), vzero<T>(), (uint32_t)AVN_TRIANGLE_ALL_EDGES}, t2 = t1;
     if (k1 == AVN_SHAPE_TRIANGLE && ts.vertices1) { t1.a = ld3(ts.vertices1, 3 * (size_t)i); t1.b = ld3(ts.vertices1, 3 * (size_t)i + 1); t1.c = ld3(ts.vertices1, 3 * (size_t)i + 2); if (ts.edge_flags1) t1.flags = ts.edge_flags1[i]; }
@@ -78,20 +85,7 @@ __global__ __launch_bounds__(64) void k_triangle_manifolds_query(TriQueryStage<T
     bool has;
     AVN_INLINE_CALL has = contact_manifolds_pair_sink<T, NpArraySink<T>, 0, true, true>(k1, ld3(s.half_extents1, i), p1, r1, k2, ld3(s.half_extents2, i), p2, r2, s.prediction[i], sink, m.normal,
                                                                               nullptr, nullptr, t1, t2);
-    int cnt = has ? m.n : 0;
-    if (s.point_count) s.point_count[i] = (uint8_t)cnt;
-    st3(s.normal, i, has ? m.normal : vzero<T>());
-    for (int k = 0; k < AVN_MAX_QUERY_POINTS; ++k) {
-        size_t slot = (size_t)AVN_MAX_QUERY_POINTS * i + k;
-        bool live = k < cnt;
-        V3<T> a1 = live ? m.pts[k].anchor1 : vzero<T>();
-        st3(s.anchor1, slot, a1);
-        st3(s.anchor2, slot, live ? m.pts[k].anchor2 : vzero<T>());
-        st3(s.point, slot, live ? p1 + a1 : vzero<T>());
-        if (s.penetration) s.penetration[slot] = live ? m.pts[k].penetration : T(0);
-        if (s.feature_id1) s.feature_id1[slot] = live ? m.pts[k].fid1 : 0u;
-        if (s.feature_id2) s.feature_id2[slot] = live ? m.pts[k].fid2 : 0u;
-    }
+    np_query_store(s, i, has, m, p1);
 }
 template <class T> void launch_triangle_manifolds_query(const TriQueryStage<T>& s, uint32_t n, hipStream_t st) {
     if (n) hipLaunchKernelGGL(k_triangle_manifolds_query<T>, dim3((n + 63) / 64), dim3(64), 0, st, s, n);
@@ -188,10 +182,8 @@ template <class T> __host__ __device__ __forceinline__ NpHookCtx<T> np_hook_ctx(
 // triangle and an AVN_SHAPE_HOST collider has left for the host before.
 __device__ __forceinline__ bool np_heavy_kind(uint32_t shape) { return shape == AVN_SHAPE_CAPSULE || shape == AVN_SHAPE_TRIANGLE; }   // the kinds whose every pair is the heavy kernel's
 template <class T, bool DENSE, bool HEAVY, bool HS = false, bool CAP = false, bool TRI = false>
-__device__ void np_update_pair(const DW<T>& w, const BP<T>& bp, const CT<T>& ct, const StepParams<T>& p, const uint32_t c,
-                               avn_contact_change* __restrict__ changes, uint32_t* __restrict__ n_changes, uint32_t* __restrict__ chg,
-                               uint32_t* __restrict__ has, bool* deferred, V3<T>* axis, T* lds_col, NpHostQ<T>* hq = nullptr, const NpHostM<T>* hm = nullptr,
-                               const NpHookCtx<T>* hk = nullptr) {
+__device__ void np_update_pair(const DW<T>& w, const BP<T>& bp, const CT<T>& ct, const StepParams<T>& p, const uint32_t c, const NpOut& out, bool* deferred, V3<T>* axis,
+                               T* lds_col, NpHostQ<T>* hq = nullptr, const NpHostM<T>* hm = nullptr, const NpHookCtx<T>* hk = nullptr) {
     uint4 meta = ct.meta[c];
     // (collision hooks: phase 2 visits only the rows phase 1 left pending; the bit itself is not a flag of the pair)
     const bool hk_on = HS && hk != nullptr && hk->count != nullptr;
@@ -199,7 +191,7 @@ __device__ void np_update_pair(const DW<T>& w, const BP<T>& bp, const CT<T>& ct,
     if (hk_on && hk->phase == 2u && !(meta.z & AVN_CP_ROW_HOOK_PENDING)) return;
     if (HS) meta.z &= ~(uint32_t)AVN_CP_ROW_HOOK_PENDING;
     // (a free id; or a pair of ContactGraph::sleeping_pairs: update_contacts walks the ACTIVE pairs only, system_param.rs:437-475)
-    if (DENSE && (!(meta.z & AVN_CP_ROW_USED) || (meta.z & AVN_CP_ROW_SLEEPING))) { chg[c] = 0u; has[c] = 0u; return; }
+    if (DENSE && (!(meta.z & AVN_CP_ROW_USED) || (meta.z & AVN_CP_ROW_SLEEPING))) { out.chg[c] = 0u; out.has[c] = 0u; return; }
     const uint32_t slot1 = meta.x, slot2 = meta.y;
     uint32_t flags = meta.z;
     const uint32_t old_nman = meta.w & 0xFFu, old_pc = (meta.w >> 8) & 0xFFu;
@@ -294,7 +286,7 @@ __device__ void np_update_pair(const DW<T>& w, const BP<T>& bp, const CT<T>& ct,
             T acc = ((x1.x + x2.y) + (q1.w + q2.x)) + ((world_com1.x + world_com2.y) + (lin_vel1.z + lin_vel2.x)) + ((ang_vel1.x + ang_vel2.y) + (friction + restitution)) + (sp1 + sp2);
 #pragma unroll
             for (uint32_t k = 0; k < AVN_MAX_MANIFOLD_POINTS; ++k) acc += (old_a1[k].x + old_a2[k].y) + (old_wn[k] + bits_to_scalar(old_fid[k].x ^ old_fid[k].y, T(0)));
-            if (acc == T(123456.75)) chg[c] = 7u;
+            if (acc == T(123456.75)) out.chg[c] = 7u;
             return;
         }
         // the raw points of the manifold go to this lane's LDS column (NpLdsSink): the only dynamically indexed storage of the update
@@ -328,7 +320,7 @@ __device__ void np_update_pair(const DW<T>& w, const BP<T>& bp, const CT<T>& ct,
         if (!HEAVY && has_manifold) load_manifold_inputs();
         if (HEAVY && TRI) { load_manifold_inputs(); load_old_points(); }
         if (HEAVY && NP_DEBUG(p) == 4u) {   // timing cut-off: the manifold's raw points are in LDS, nothing converted or written
-            if (has_manifold && normal.x + T(sink.cnt) == T(123456.75)) chg[c] = 7u;
+            if (has_manifold && normal.x + T(sink.cnt) == T(123456.75)) out.chg[c] = 7u;
             return;
         }
         const V3<T> d12 = x1 - x2;
@@ -398,7 +390,7 @@ __device__ void np_update_pair(const DW<T>& w, const BP<T>& bp, const CT<T>& ct,
             n_manifolds = 1;
         }
         if (HEAVY && NP_DEBUG(p) == 5u) {   // timing cut-off: points kept / pruned, nothing matched or written
-            if (T(o0 + o1 + o2 + o3) + T(point_count) == T(123456.75)) chg[c] = 7u;
+            if (T(o0 + o1 + o2 + o3) + T(point_count) == T(123456.75)) out.chg[c] = 7u;
             return;
         }
         bool touching = n_manifolds != 0;
@@ -481,14 +473,14 @@ __device__ void np_update_pair(const DW<T>& w, const BP<T>& bp, const CT<T>& ct,
         else if (dcount != 0) status = true;
     }
     if (DENSE) {
-        chg[c] = status ? ((flags & 0xFFFFu) | (n_manifolds << 16) | (((uint32_t)(dcount + 128) & 0xFFu) << 24)) : 0u;
-        has[c] = status ? 1u : 0u;
-        if (flags & AVN_CP_DISJOINT_AABB) atomicAdd(n_changes, 1u);   // rows to remove (here `n_changes` is the removal counter)
+        out.chg[c] = status ? ((flags & 0xFFFFu) | (n_manifolds << 16) | (((uint32_t)(dcount + 128) & 0xFFu) << 24)) : 0u;
+        out.has[c] = status ? 1u : 0u;
+        if (flags & AVN_CP_DISJOINT_AABB) atomicAdd(out.counter, 1u);   // rows to remove
     } else if (status) {
-        uint32_t slot = atomicAdd(n_changes, 1u);
+        uint32_t slot = atomicAdd(out.counter, 1u);
         avn_contact_change ch;
         ch.contact_id = c; ch.flags = flags & ~(uint32_t)AVN_CP_ROW_USED; ch.manifold_count_change = dcount; ch.manifold_count = n_manifolds;
-        changes[slot] = ch;
+        out.changes[slot] = ch;
     }
     // the transient status flags are handled (and cleared) by the host's status processing, system_param.rs:141-389
     const uint32_t kept_flags = flags & ~(uint32_t)(AVN_CP_STARTED_TOUCHING | AVN_CP_STOPPED_TOUCHING | AVN_CP_STARTED_GENERATING_CONSTRAINTS);
@@ -525,6 +517,7 @@ __global__ __launch_bounds__(NP_LIGHT_THREADS) void k_narrow_phase(DW<T> w, BP<T
                                                                    uint32_t* __restrict__ has, uint32_t n_list, uint32_t range_base, NpHostQ<T>* __restrict__ hostq = nullptr,
                                                                    uint32_t* __restrict__ hostq_n = nullptr, uint32_t hostq_cap = 0u, uint32_t host_only = 0u, NpHookCtx<T> hk = NpHookCtx<T>()) {
     const uint32_t a = blockIdx.x * NP_LIGHT_THREADS + threadIdx.x;
+    const NpOut out{changes, n_changes, chg, has};
     bool deferred = false;
     V3<T> axis = vzero<T>();
     uint32_t c = 0;
@@ -532,8 +525,8 @@ __global__ __launch_bounds__(NP_LIGHT_THREADS) void k_narrow_phase(DW<T> w, BP<T
         NpHostQ<T> q;
         q.contact_id = 0xFFFFFFFFu; q.reserved = host_only;
         if (a < n_active) {
-            c = !DENSE ? active[a] : (active || n_list || range_base) ? (a < n_list ? active[a] : range_base + (a - n_list)) : a;
-            np_update_pair<T, DENSE, false, true>(w, bp, ct, p, c, changes, n_changes, chg, has, &deferred, &axis, nullptr, &q, nullptr, &hk);
+            c = np_row_id<DENSE>(active, n_list, range_base, a);
+            np_update_pair<T, DENSE, false, true>(w, bp, ct, p, c, out, &deferred, &axis, nullptr, &q, nullptr, &hk);
         }
         if (deferred && q.contact_id != 0xFFFFFFFFu && hostq_n) {   // a host pair (few of them: one atomic each); past the capacity only the count grows and the host retries larger
             const uint32_t k = atomicAdd(hostq_n, 1u);
@@ -542,10 +535,8 @@ __global__ __launch_bounds__(NP_LIGHT_THREADS) void k_narrow_phase(DW<T> w, BP<T
         }
     } else
     if (a < n_active) {
-        // DENSE with a row list (the rows a step ADDED, narrow phase overlapped with the broad phase): ids list[0 .. n_list), then the
-        // contiguous fresh ids range_base ..; DENSE without one: every row id; sparse: the active list
-        c = !DENSE ? active[a] : (active || n_list || range_base) ? (a < n_list ? active[a] : range_base + (a - n_list)) : a;
-        np_update_pair<T, DENSE, false>(w, bp, ct, p, c, changes, n_changes, chg, has, &deferred, &axis, nullptr);
+        c = np_row_id<DENSE>(active, n_list, range_base, a);
+        np_update_pair<T, DENSE, false>(w, bp, ct, p, c, out, &deferred, &axis, nullptr);
     }
     const uint64_t m = __ballot(deferred);
     if (m) {
@@ -578,10 +569,9 @@ __global__ __launch_bounds__(NP_THREADS) void k_narrow_phase_heavy(DW<T> w, BP<T
         const size_t k = (size_t)list * np_list_segment(n_pairs) + i;
         V3<T> axis{ct.np_axis[3 * k], ct.np_axis[3 * k + 1], ct.np_axis[3 * k + 2]};
         bool deferred = false;
-        if constexpr (HS && TRI) { AVN_INLINE_CALL np_update_pair<T, DENSE, true, true, CAP, true>(w, bp, ct, p, ct.np_row[k], changes, n_changes, chg, has, &deferred, &axis, s_pts + threadIdx.x, nullptr, nullptr, &hk); }
-        else if (HS) np_update_pair<T, DENSE, true, true, CAP, TRI>(w, bp, ct, p, ct.np_row[k], changes, n_changes, chg, has, &deferred, &axis, s_pts + threadIdx.x, nullptr, nullptr, &hk);
-        else
-        np_update_pair<T, DENSE, true>(w, bp, ct, p, ct.np_row[k], changes, n_changes, chg, has, &deferred, &axis, s_pts + threadIdx.x);
+        const NpOut out{changes, n_changes, chg, has};
+        if constexpr (HS && TRI) { AVN_INLINE_CALL np_update_pair<T, DENSE, true, true, CAP, true>(w, bp, ct, p, ct.np_row[k], out, &deferred, &axis, s_pts + threadIdx.x, nullptr, nullptr, &hk); }
+        else np_update_pair<T, DENSE, true, HS, CAP, TRI>(w, bp, ct, p, ct.np_row[k], out, &deferred, &axis, s_pts + threadIdx.x, nullptr, nullptr, &hk);
     }
     __syncthreads();
     if (threadIdx.x == 0 && atomicAdd(ctr + 1, 1u) == (n + NP_THREADS - 1) / NP_THREADS - 1u) { atomicExch(ctr, 0u); atomicExch(ctr + 1, 0u); }
@@ -596,7 +586,7 @@ __global__ __launch_bounds__(NP_THREADS) void k_narrow_phase_host(DW<T> w, BP<T>
     if (i >= n) return;
     bool deferred = false;
     V3<T> axis = vzero<T>();
-    np_update_pair<T, DENSE, true, true>(w, bp, ct, p, q[i].contact_id, changes, n_changes, chg, has, &deferred, &axis, s_pts + threadIdx.x, nullptr, m + i, &hk);
+    np_update_pair<T, DENSE, true, true>(w, bp, ct, p, q[i].contact_id, NpOut{changes, n_changes, chg, has}, &deferred, &axis, s_pts + threadIdx.x, nullptr, m + i, &hk);
 }
 // collision hooks, phase 3: the pairs CollisionHooks::modify_contacts answered, one lane each -- the remainder of update_contacts from the returned record
 template <class T, bool DENSE>
@@ -608,22 +598,28 @@ __global__ __launch_bounds__(NP_THREADS) void k_narrow_phase_hooked(DW<T> w, BP<
     bool deferred = false;
     V3<T> axis = vzero<T>();
     const NpHookCtx<T> hk{nullptr, nullptr, 0u, 3u, rec + i};
-    np_update_pair<T, DENSE, true, true>(w, bp, ct, p, rec[i].contact_id, changes, n_changes, chg, has, &deferred, &axis, s_pts + threadIdx.x, nullptr, nullptr, &hk);
+    np_update_pair<T, DENSE, true, true>(w, bp, ct, p, rec[i].contact_id, NpOut{changes, n_changes, chg, has}, &deferred, &axis, s_pts + threadIdx.x, nullptr, nullptr, &hk);
 }
 size_t np_survivor_list_slack() { return (size_t)NP_LISTS * NP_LIGHT_THREADS; }
 size_t np_survivor_counter_bytes() { return (size_t)NP_LISTS * NP_CTR_STRIDE * sizeof(uint32_t); }
 template <class T, bool DENSE>
-static void launch_np_heavy(const DW<T>& w, const BP<T>& bp, const CT<T>& ct, const StepParams<T>& p, avn_contact_change* changes, uint32_t* n_changes, uint32_t* chg, uint32_t* has,
-                            uint32_t n_pairs, hipStream_t st, const NpHookList& hook = NpHookList(), bool hs = false, bool caps = false, bool tris = false) {
-    const uint32_t chunks = np_list_segment(n_pairs) / NP_THREADS;
+static void launch_np_heavy(const DW<T>& w, const BP<T>& bp, const CT<T>& ct, const StepParams<T>& p, const NpOut& o, uint32_t n_pairs, hipStream_t st, const NpHostList& hl) {
+    const dim3 grid(np_list_segment(n_pairs) / NP_THREADS * NP_LISTS), block(NP_THREADS);
+    const NpHookCtx<T> hk = np_hook_ctx<T>(hl.hook);
     // (a world with a triangle always takes CAP = true, TRI = true: one instantiation more per scalar and form, not two)
-    if (tris && bp.col_tri) hipLaunchKernelGGL((k_narrow_phase_heavy<T, DENSE, true, true, true>), dim3(chunks * NP_LISTS), dim3(NP_THREADS), 0, st, w, bp, ct, p, changes, n_changes, chg, has, n_pairs, np_hook_ctx<T>(hook));
-    else
-    if (caps) hipLaunchKernelGGL((k_narrow_phase_heavy<T, DENSE, true, true>), dim3(chunks * NP_LISTS), dim3(NP_THREADS), 0, st, w, bp, ct, p, changes, n_changes, chg, has, n_pairs, np_hook_ctx<T>(hook));
-    else
-    if (hook.count || hs) hipLaunchKernelGGL((k_narrow_phase_heavy<T, DENSE, true>), dim3(chunks * NP_LISTS), dim3(NP_THREADS), 0, st, w, bp, ct, p, changes, n_changes, chg, has, n_pairs, np_hook_ctx<T>(hook));
-    else
-    hipLaunchKernelGGL((k_narrow_phase_heavy<T, DENSE>), dim3(chunks * NP_LISTS), dim3(NP_THREADS), 0, st, w, bp, ct, p, changes, n_changes, chg, has, n_pairs, NpHookCtx<T>());
+    if (hl.triangles && bp.col_tri) hipLaunchKernelGGL((k_narrow_phase_heavy<T, DENSE, true, true, true>), grid, block, 0, st, w, bp, ct, p, o.changes, o.counter, o.chg, o.has, n_pairs, hk);
+    else if (hl.capsules) hipLaunchKernelGGL((k_narrow_phase_heavy<T, DENSE, true, true>), grid, block, 0, st, w, bp, ct, p, o.changes, o.counter, o.chg, o.has, n_pairs, hk);
+    else if (hl.any()) hipLaunchKernelGGL((k_narrow_phase_heavy<T, DENSE, true>), grid, block, 0, st, w, bp, ct, p, o.changes, o.counter, o.chg, o.has, n_pairs, hk);
+    else hipLaunchKernelGGL((k_narrow_phase_heavy<T, DENSE>), grid, block, 0, st, w, bp, ct, p, o.changes, o.counter, o.chg, o.has, n_pairs, hk);
+}
+// the light kernel over the rows `r` names (HS: any of the general cases of NpHostList), then the heavy one over its survivors
+template <class T, bool DENSE>
+static void launch_np(const DW<T>& w, const BP<T>& bp, const CT<T>& ct, const StepParams<T>& p, const NpRowArgs& r, const NpOut& o, hipStream_t st, const NpHostList& hl) {
+    const dim3 grid((r.n + NP_LIGHT_THREADS - 1) / NP_LIGHT_THREADS), block(NP_LIGHT_THREADS);
+    if (hl.any()) hipLaunchKernelGGL((k_narrow_phase<T, DENSE, true>), grid, block, 0, st, w, bp, ct, p, r.list, r.n, o.changes, o.counter, o.chg, o.has, r.n_list, r.range_base, (NpHostQ<T>*)hl.queries, hl.count, hl.cap, hl.host_only, np_hook_ctx<T>(hl.hook));
+    else hipLaunchKernelGGL((k_narrow_phase<T, DENSE>), grid, block, 0, st, w, bp, ct, p, r.list, r.n, o.changes, o.counter, o.chg, o.has, r.n_list, r.range_base);
+    if (hl.host_only) return;   // (a retry hands no cuboid pair over: nothing for the second kernel)
+    launch_np_heavy<T, DENSE>(w, bp, ct, p, o, r.n, st, hl);
 }
 
 template <class T>
@@ -743,54 +739,25 @@ template <class T> void launch_init_contact_rows(const CT<T>& ct, const uint32_t
 template <class T> void launch_clear_contact_rows(const CT<T>& ct, const uint32_t* ids, uint32_t n, hipStream_t st) {
     if (n) hipLaunchKernelGGL(k_clear_contact_rows<T>, dim3((n + 255) / 256), dim3(256), 0, st, ct, ids, n);
 }
-template <class T> void launch_narrow_phase(const DW<T>& w, const BP<T>& bp, const CT<T>& ct, const StepParams<T>& p, const uint32_t* active, uint32_t n_active,
-                                            avn_contact_change* changes, uint32_t* n_changes, hipStream_t st, const NpHostList& hl) {
-    if (!hl.host_only && hl.hook.phase != 2u) (void)hipMemsetAsync(n_changes, 0, sizeof(uint32_t), st);
-    if (!n_active) return;
-    if (hl.any()) hipLaunchKernelGGL((k_narrow_phase<T, false, true>), dim3((n_active + NP_LIGHT_THREADS - 1) / NP_LIGHT_THREADS), dim3(NP_LIGHT_THREADS), 0, st, w, bp, ct, p, active, n_active, changes, n_changes, nullptr, nullptr, 0u, 0u, (NpHostQ<T>*)hl.queries, hl.count, hl.cap, hl.host_only, np_hook_ctx<T>(hl.hook));
-    else
-    hipLaunchKernelGGL((k_narrow_phase<T, false>), dim3((n_active + NP_LIGHT_THREADS - 1) / NP_LIGHT_THREADS), dim3(NP_LIGHT_THREADS), 0, st, w, bp, ct, p, active, n_active, changes, n_changes, nullptr, nullptr, 0u, 0u);
-    if (hl.host_only) return;   // (a retry hands no cuboid pair over: nothing for the second kernel)
-    launch_np_heavy<T, false>(w, bp, ct, p, changes, n_changes, nullptr, nullptr, n_active, st, hl.hook, hl.any(), hl.capsules, hl.triangles);
+template <class T> void launch_narrow_phase(const DW<T>& w, const BP<T>& bp, const CT<T>& ct, const StepParams<T>& p, const NpRows& rows, const NpOut& out, hipStream_t st, const NpHostList& hl) {
+    if (!out.dense() && !hl.host_only && hl.hook.phase != 2u) (void)hipMemsetAsync(out.counter, 0, sizeof(uint32_t), st);
+    const NpRowArgs r = np_row_args(rows);
+    if (!r.n) return;
+    if (out.dense()) launch_np<T, true>(w, bp, ct, p, r, out, st, hl);
+    else launch_np<T, false>(w, bp, ct, p, r, out, st, hl);
 }
-template <class T> void launch_narrow_phase_dense(const DW<T>& w, const BP<T>& bp, const CT<T>& ct, const StepParams<T>& p, uint32_t n_rows, uint32_t* chg, uint32_t* has,
-                                                  uint32_t* n_remove, hipStream_t st, bool reset_counter, const NpHostList& hl) {
-    if (reset_counter) (void)hipMemsetAsync(n_remove, 0, sizeof(uint32_t), st);
-    if (!n_rows) return;
-    if (hl.any()) hipLaunchKernelGGL((k_narrow_phase<T, true, true>), dim3((n_rows + NP_LIGHT_THREADS - 1) / NP_LIGHT_THREADS), dim3(NP_LIGHT_THREADS), 0, st, w, bp, ct, p, nullptr, n_rows, nullptr, n_remove, chg, has, 0u, 0u, (NpHostQ<T>*)hl.queries, hl.count, hl.cap, hl.host_only, np_hook_ctx<T>(hl.hook));
-    else
-    hipLaunchKernelGGL((k_narrow_phase<T, true>), dim3((n_rows + NP_LIGHT_THREADS - 1) / NP_LIGHT_THREADS), dim3(NP_LIGHT_THREADS), 0, st, w, bp, ct, p, nullptr, n_rows, nullptr, n_remove, chg, has, 0u, 0u);
-    if (hl.host_only) return;
-    launch_np_heavy<T, true>(w, bp, ct, p, nullptr, n_remove, chg, has, n_rows, st, hl.hook, hl.any(), hl.capsules, hl.triangles);
-}
-// the rows list[0 .. n_list) followed by range_base .. range_base + n_range: same per-row work and outputs as the dense form; the
-// removal counter is NOT reset (it continues the count of the launch over the older rows)
-template <class T> void launch_narrow_phase_rows(const DW<T>& w, const BP<T>& bp, const CT<T>& ct, const StepParams<T>& p, const uint32_t* list, uint32_t n_list, uint32_t range_base,
-                                                 uint32_t n_range, uint32_t* chg, uint32_t* has, uint32_t* n_remove, hipStream_t st, const NpHostList& hl) {
-    const uint32_t n = n_list + n_range;
+template <class T> void launch_narrow_phase_host(const DW<T>& w, const BP<T>& bp, const CT<T>& ct, const StepParams<T>& p, const NpOut& o, const void* queries, const void* manifolds, uint32_t n,
+                                                 hipStream_t st, const NpHookList& hook) {
     if (!n) return;
-    // (range_base = 0 with an empty list would read as the plain dense form: a world's first pairs take the dense launch instead)
-    if (hl.any()) {
-        if (!n_list && !range_base) hipLaunchKernelGGL((k_narrow_phase<T, true, true>), dim3((n_range + NP_LIGHT_THREADS - 1) / NP_LIGHT_THREADS), dim3(NP_LIGHT_THREADS), 0, st, w, bp, ct, p, nullptr, n_range, nullptr, n_remove, chg, has, 0u, 0u, (NpHostQ<T>*)hl.queries, hl.count, hl.cap, hl.host_only, np_hook_ctx<T>(hl.hook));
-        else hipLaunchKernelGGL((k_narrow_phase<T, true, true>), dim3((n + NP_LIGHT_THREADS - 1) / NP_LIGHT_THREADS), dim3(NP_LIGHT_THREADS), 0, st, w, bp, ct, p, list, n, nullptr, n_remove, chg, has, n_list, range_base, (NpHostQ<T>*)hl.queries, hl.count, hl.cap, hl.host_only, np_hook_ctx<T>(hl.hook));
-    } else
-    if (!n_list && !range_base) hipLaunchKernelGGL((k_narrow_phase<T, true>), dim3((n_range + NP_LIGHT_THREADS - 1) / NP_LIGHT_THREADS), dim3(NP_LIGHT_THREADS), 0, st, w, bp, ct, p, nullptr, n_range, nullptr, n_remove, chg, has, 0u, 0u);
-    else hipLaunchKernelGGL((k_narrow_phase<T, true>), dim3((n + NP_LIGHT_THREADS - 1) / NP_LIGHT_THREADS), dim3(NP_LIGHT_THREADS), 0, st, w, bp, ct, p, list, n, nullptr, n_remove, chg, has, n_list, range_base);
-    if (hl.host_only) return;
-    launch_np_heavy<T, true>(w, bp, ct, p, nullptr, n_remove, chg, has, n, st, hl.hook, hl.any(), hl.capsules, hl.triangles);
+    const dim3 grid((n + NP_THREADS - 1) / NP_THREADS), block(NP_THREADS);
+    if (o.dense()) hipLaunchKernelGGL((k_narrow_phase_host<T, true>), grid, block, 0, st, w, bp, ct, p, o.changes, o.counter, o.chg, o.has, (const NpHostQ<T>*)queries, (const NpHostM<T>*)manifolds, n, np_hook_ctx<T>(hook));
+    else hipLaunchKernelGGL((k_narrow_phase_host<T, false>), grid, block, 0, st, w, bp, ct, p, o.changes, o.counter, o.chg, o.has, (const NpHostQ<T>*)queries, (const NpHostM<T>*)manifolds, n, np_hook_ctx<T>(hook));
 }
-// the pairs the host answered (queries sorted by contact id on the host, manifolds in the same order): dense = the closed loop's chg / has outputs, else the change list
-template <class T> void launch_narrow_phase_host(const DW<T>& w, const BP<T>& bp, const CT<T>& ct, const StepParams<T>& p, bool dense, avn_contact_change* changes, uint32_t* n_changes,
-                                                 uint32_t* chg, uint32_t* has, const void* queries, const void* manifolds, uint32_t n, hipStream_t st, const NpHookList& hook) {
+template <class T> void launch_narrow_phase_hooked(const DW<T>& w, const BP<T>& bp, const CT<T>& ct, const StepParams<T>& p, const NpOut& o, const void* records, uint32_t n, hipStream_t st) {
     if (!n) return;
-    if (dense) hipLaunchKernelGGL((k_narrow_phase_host<T, true>), dim3((n + NP_THREADS - 1) / NP_THREADS), dim3(NP_THREADS), 0, st, w, bp, ct, p, nullptr, n_changes, chg, has, (const NpHostQ<T>*)queries, (const NpHostM<T>*)manifolds, n, np_hook_ctx<T>(hook));
-    else hipLaunchKernelGGL((k_narrow_phase_host<T, false>), dim3((n + NP_THREADS - 1) / NP_THREADS), dim3(NP_THREADS), 0, st, w, bp, ct, p, changes, n_changes, nullptr, nullptr, (const NpHostQ<T>*)queries, (const NpHostM<T>*)manifolds, n, np_hook_ctx<T>(hook));
-}
-template <class T> void launch_narrow_phase_hooked(const DW<T>& w, const BP<T>& bp, const CT<T>& ct, const StepParams<T>& p, bool dense, avn_contact_change* changes, uint32_t* n_changes,
-                                                   uint32_t* chg, uint32_t* has, const void* records, uint32_t n, hipStream_t st) {
-    if (!n) return;
-    if (dense) hipLaunchKernelGGL((k_narrow_phase_hooked<T, true>), dim3((n + NP_THREADS - 1) / NP_THREADS), dim3(NP_THREADS), 0, st, w, bp, ct, p, nullptr, n_changes, chg, has, (const NpHookC<T>*)records, n);
-    else hipLaunchKernelGGL((k_narrow_phase_hooked<T, false>), dim3((n + NP_THREADS - 1) / NP_THREADS), dim3(NP_THREADS), 0, st, w, bp, ct, p, changes, n_changes, nullptr, nullptr, (const NpHookC<T>*)records, n);
+    const dim3 grid((n + NP_THREADS - 1) / NP_THREADS), block(NP_THREADS);
+    if (o.dense()) hipLaunchKernelGGL((k_narrow_phase_hooked<T, true>), grid, block, 0, st, w, bp, ct, p, o.changes, o.counter, o.chg, o.has, (const NpHookC<T>*)records, n);
+    else hipLaunchKernelGGL((k_narrow_phase_hooked<T, false>), grid, block, 0, st, w, bp, ct, p, o.changes, o.counter, o.chg, o.has, (const NpHookC<T>*)records, n);
 }
 template <class T> void launch_scatter_impulses(const DW<T>& w, const CT<T>& ct, const uint32_t* handles, hipStream_t st) {
     if (w.n_manifolds) hipLaunchKernelGGL(k_scatter_impulses<T>, dim3((w.n_manifolds + 255) / 256), dim3(256), 0, st, w, ct, handles);
@@ -807,11 +774,9 @@ template <class T> void launch_pack_contacts(const CT<T>& ct, const uint32_t* id
     template void launch_pack_contacts<T>(const CT<T>&, const uint32_t*, uint32_t, const ContactsStage<T>&, uint32_t*, hipStream_t);                              \
     template void launch_init_contact_rows<T>(const CT<T>&, const uint32_t*, const uint32_t*, const uint32_t*, const uint32_t*, uint32_t, hipStream_t); \
     template void launch_clear_contact_rows<T>(const CT<T>&, const uint32_t*, uint32_t, hipStream_t);                                                \
-    template void launch_narrow_phase<T>(const DW<T>&, const BP<T>&, const CT<T>&, const StepParams<T>&, const uint32_t*, uint32_t, avn_contact_change*, uint32_t*, hipStream_t, const NpHostList&); \
-    template void launch_narrow_phase_dense<T>(const DW<T>&, const BP<T>&, const CT<T>&, const StepParams<T>&, uint32_t, uint32_t*, uint32_t*, uint32_t*, hipStream_t, bool, const NpHostList&); \
-    template void launch_narrow_phase_rows<T>(const DW<T>&, const BP<T>&, const CT<T>&, const StepParams<T>&, const uint32_t*, uint32_t, uint32_t, uint32_t, uint32_t*, uint32_t*, uint32_t*, hipStream_t, const NpHostList&); \
-    template void launch_narrow_phase_host<T>(const DW<T>&, const BP<T>&, const CT<T>&, const StepParams<T>&, bool, avn_contact_change*, uint32_t*, uint32_t*, uint32_t*, const void*, const void*, uint32_t, hipStream_t, const NpHookList&); \
-    template void launch_narrow_phase_hooked<T>(const DW<T>&, const BP<T>&, const CT<T>&, const StepParams<T>&, bool, avn_contact_change*, uint32_t*, uint32_t*, uint32_t*, const void*, uint32_t, hipStream_t); \
+    template void launch_narrow_phase<T>(const DW<T>&, const BP<T>&, const CT<T>&, const StepParams<T>&, const NpRows&, const NpOut&, hipStream_t, const NpHostList&); \
+    template void launch_narrow_phase_host<T>(const DW<T>&, const BP<T>&, const CT<T>&, const StepParams<T>&, const NpOut&, const void*, const void*, uint32_t, hipStream_t, const NpHookList&); \
+    template void launch_narrow_phase_hooked<T>(const DW<T>&, const BP<T>&, const CT<T>&, const StepParams<T>&, const NpOut&, const void*, uint32_t, hipStream_t); \
     template void launch_scatter_impulses<T>(const DW<T>&, const CT<T>&, const uint32_t*, hipStream_t);                                               \
     template void launch_unpack_contacts<T>(const CT<T>&, const uint32_t*, uint32_t, const ContactsStage<T>&, hipStream_t);
 INST(float)

@@ -113,16 +113,15 @@
         uint32_t* d_count = b_misc.as<uint32_t>() + 40;
         NpHostList hl;
         { const avn_status sb = hs_begin(stream, &hl); if (sb != AVN_OK) return sb; }
-        launch_narrow_phase<T>(dw, bp, ct, params, b_active.as<uint32_t>(), n_active, b_changes.as<avn_contact_change>(), d_count, stream, hl);
-        ++launches;
+        const NpOut out{b_changes.as<avn_contact_change>(), d_count, nullptr, nullptr};
+        np_launch(NpRows::active(b_active.as<uint32_t>(), n_active), out, hl, params);
         HIPCHK(hipGetLastError());
-        if (hl.any()) hs_launches.push_back(HsLaunch{0, n_active, 0, 0, 0, b_active.as<uint32_t>()});
         if (hl.queries) {   // pairs with a host-shaped collider: contact_manifolds_with_context on the host, the rest of update_contacts here (world/host_shapes.hpp)
-            avn_status sh = hs_manifolds(false, params, b_changes.as<avn_contact_change>(), d_count, nullptr, nullptr, stream);
+            avn_status sh = hs_manifolds(out, params, stream);
             if (sh != AVN_OK) return sh;
         }
         if (hl.hook.count) {   // pairs waiting for CollisionHooks::modify_contacts (world/hooks.hpp)
-            avn_status sh = hk_modify(false, params, b_changes.as<avn_contact_change>(), d_count, nullptr, nullptr, stream);
+            avn_status sh = hk_modify(out, params, stream);
             if (sh != AVN_OK) return sh;
         }
         // the count and the first CHANGES_PREFIX changes come back in one round trip (pinned memory, one synchronisation);

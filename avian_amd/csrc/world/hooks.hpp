@@ -96,28 +96,17 @@
     }
     // ---- modify_contacts ----
     // the step's narrow-phase launches carry this list: phase 1 (count + pending bit) when a hook is registered and a collider asks for it
-    avn_status hk_begin(NpHostList& l, hipStream_t s) {
+    avn_status hk_begin(hipStream_t s) {
         hk_stats.last_modify_queries = hk_stats.last_modify_rejected = 0;
         if (!hk_filter_active()) hk_stats.last_callback_ms = 0;
         if (!hk_modify_active()) return AVN_OK;
         avn_status st = hk_counters();
         if (st != AVN_OK) return st;
         HIPCHK(hipMemsetAsync(b_hk_cnt.p, 0, 4, s));
-        l.hook.records = nullptr; l.hook.count = b_hk_cnt.as<uint32_t>(); l.hook.cap = 0; l.hook.phase = 1;
         return AVN_OK;
     }
-    // the launches of one narrow phase again, for a second pass that visits only some rows (host shapes: the retry after the query list grew; hooks: phase 2)
-    void hs_rerun(const NpHostList& l, bool dense, const StepParams<T>& np, avn_contact_change* changes, uint32_t* n_changes, uint32_t* chg, uint32_t* has, hipStream_t s) {
-        (void)dense;
-        for (const HsLaunch& k : hs_launches) {
-            if (k.form == 0) launch_narrow_phase<T>(dw, bp, ct, np, k.list, k.a, changes, n_changes, s, l);
-            else if (k.form == 1) launch_narrow_phase_dense<T>(dw, bp, ct, np, k.a, chg, has, n_changes, s, false, l);
-            else launch_narrow_phase_rows<T>(dw, bp, ct, np, k.list, k.a, k.b, k.c, chg, has, n_changes, s, l);
-            ++launches;
-        }
-    }
     // after the step's narrow-phase launches and the host shapes' answers (all on `s`): phase 2 collects the pending pairs' records, the hook sees them, phase 3 finishes the pairs
-    avn_status hk_modify(bool dense, const StepParams<T>& np, avn_contact_change* changes, uint32_t* n_changes, uint32_t* chg, uint32_t* has, hipStream_t s) {
+    avn_status hk_modify(const NpOut& out, const StepParams<T>& np, hipStream_t s) {
         if (!hk_modify_active() || !b_hk_cnt.p) return AVN_OK;
         ALLOC(pin_hk.ensure(4096));
         uint32_t* d_cnt = b_hk_cnt.as<uint32_t>();
@@ -133,11 +122,10 @@
         }
         ALLOC(pin_hk.ensure((size_t)n * HK_REC + 64));
         HIPCHK(hipMemsetAsync(d_cnt, 0, 4, s));
-        NpHostList l;
-        l.hook.records = b_hk_rec.p; l.hook.count = d_cnt; l.hook.cap = hk_rec_cap; l.hook.phase = 2; l.locals = tf_any; l.capsules = cap_count != 0; l.triangles = tri_count != 0;
-        hs_rerun(l, dense, np, changes, n_changes, chg, has, s);
+        const NpHostList l = np_host_list(0, 2);
+        hs_rerun(l, out, np, s);
         if (hs_any() && hs_stats.last_manifold_queries)   // (pending pairs with a host-shaped collider: their manifolds are still in the answer list)
-            { launch_narrow_phase_host<T>(dw, bp, ct, np, dense, changes, n_changes, chg, has, b_hs_mq.p, b_hs_mm.p, hs_stats.last_manifold_queries, s, l.hook); ++launches; }
+            { launch_narrow_phase_host<T>(dw, bp, ct, np, out, b_hs_mq.p, b_hs_mm.p, hs_stats.last_manifold_queries, s, l.hook); ++launches; }
         HIPCHK(hipGetLastError());
         uint32_t* h_cnt = (uint32_t*)pin_hk.p;
         char* rec = (char*)pin_hk.p + 64;
@@ -165,7 +153,7 @@
         }
         if (hk_restitution) any_restitution = true;
         HIPCHK(hipMemcpyAsync(b_hk_rec.p, rec, (size_t)n * HK_REC, hipMemcpyHostToDevice, s));
-        launch_narrow_phase_hooked<T>(dw, bp, ct, np, dense, changes, n_changes, chg, has, b_hk_rec.p, n, s); ++launches;
+        launch_narrow_phase_hooked<T>(dw, bp, ct, np, out, b_hk_rec.p, n, s); ++launches;
         HIPCHK(hipGetLastError());
         hk_stats.bytes_to_host += (uint64_t)n * HK_REC; hk_stats.bytes_from_host += (uint64_t)n * HK_REC;
         return AVN_OK;

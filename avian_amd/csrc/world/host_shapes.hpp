@@ -12,8 +12,7 @@
     Pinned pin_hs, pin_hs_aabb;
     uint32_t hs_mq_cap = 0;
     avn_host_shape_stats hs_stats{};
-    struct HsLaunch { int form; uint32_t a, b, c, d; const uint32_t* list; };   // the light launches of the step's narrow phase (a retry repeats them host-only)
-    std::vector<HsLaunch> hs_launches;
+    std::vector<NpRows> hs_launches;         // the step's narrow-phase launches (np_launch): a host-only retry and the hooks' phase 2 repeat them
     static constexpr size_t HS_AQ = sizeof(T) == 4 ? sizeof(avn_host_aabb_query_f32) : sizeof(avn_host_aabb_query_f64);
     static constexpr size_t HS_AB = sizeof(T) == 4 ? sizeof(avn_host_aabb_f32) : sizeof(avn_host_aabb_f64);
     static constexpr size_t HS_MQ = sizeof(T) == 4 ? sizeof(avn_host_manifold_query_f32) : sizeof(avn_host_manifold_query_f64);
@@ -80,27 +79,38 @@
     // before the step's first narrow-phase launch: the list is empty
     avn_status hs_begin(hipStream_t s, NpHostList* out) {
         hs_launches.clear();
-        NpHostList l;
-        if (hs_any()) { HIPCHK(hipMemsetAsync(b_hs_cnt.p, 0, 4, s)); l = hs_list(); }
-        const avn_status st = hk_begin(l, s);   // (collision hooks, world/hooks.hpp: phase 1 rides the same launches; a failure fails the step instead of skipping the hooks)
+        if (hs_any()) HIPCHK(hipMemsetAsync(b_hs_cnt.p, 0, 4, s));
+        const avn_status st = hk_begin(s);   // (collision hooks, world/hooks.hpp: phase 1 rides the same launches; a failure fails the step instead of skipping the hooks)
         if (st != AVN_OK) return st;
-        l.locals = tf_any;                       // (child colliders: the HS instantiations compute their poses)
-        l.capsules = cap_count != 0;             // (capsule colliders: the HS heavy kernel computes their manifolds)
-        l.triangles = tri_count != 0;            // (triangle colliders: likewise, its CAP + TRI instantiation)
-        *out = l;
+        *out = np_host_list(0, 1);
         return AVN_OK;
     }
     NpHookList hk_phase1() const { NpHookList h; if (hk_modify_active() && b_hk_cnt.p) { h.count = b_hk_cnt.as<uint32_t>(); h.phase = 1; } return h; }
-    NpHostList hs_list(uint32_t host_only = 0) const {
+    // what the narrow phase's launches carry for this world.  host_only: the retry after the query list grew; hook_phase 1: the step's own launches (count + pending bit,
+    // when a hook is registered), 2: the pass that collects the pending pairs' records (no host queries: k_narrow_phase_host's second pass collects those pairs), 0: no hook
+    NpHostList np_host_list(uint32_t host_only, uint32_t hook_phase) const {
         NpHostList l;
-        l.capsules = cap_count != 0; l.triangles = tri_count != 0;
-        if (!hs_any()) return l;
-        l.queries = b_hs_mq.p; l.count = b_hs_cnt.as<uint32_t>(); l.cap = hs_mq_cap; l.host_only = host_only; l.locals = tf_any;
+        l.locals = tf_any;               // (child colliders: the HS instantiations compute their poses)
+        l.capsules = cap_count != 0;     // (capsule colliders: the HS heavy kernel computes their manifolds)
+        l.triangles = tri_count != 0;    // (triangle colliders: likewise, its CAP + TRI instantiation)
+        if (hs_any() && hook_phase != 2) { l.queries = b_hs_mq.p; l.count = b_hs_cnt.as<uint32_t>(); l.cap = hs_mq_cap; l.host_only = host_only; }
+        if (hook_phase == 1) l.hook = hk_phase1();
+        else if (hook_phase == 2) l.hook = NpHookList{b_hk_rec.p, b_hk_cnt.as<uint32_t>(), hk_rec_cap, 2};
         return l;
     }
+    // The ONLY way a world issues the narrow phase's light + heavy launch: it is counted and recorded, so that a retry or phase 2 can repeat the step's launches.
+    // A launch that does not come through here does not exist for them.
+    void np_launch(const NpRows& rows, const NpOut& out, const NpHostList& hl, const StepParams<T>& np) {
+        launch_narrow_phase<T>(dw, bp, ct, np, rows, out, stream, hl); ++launches;
+        hs_launches.push_back(rows);
+    }
+    // the step's launches again, for a second pass that visits only some rows (host shapes: the retry after the query list grew; hooks: phase 2)
+    void hs_rerun(const NpHostList& l, const NpOut& out, const StepParams<T>& np, hipStream_t s) {
+        for (const NpRows& r : hs_launches) { launch_narrow_phase<T>(dw, bp, ct, np, r, out, s, l); ++launches; }
+    }
     // after the step's light + heavy launches (all on `s`): the pairs with a host collider have left their queries; ask the host, then run update_contacts' remainder
-    // for them.  dense: the closed loop's outputs (chg / has per row, *n_changes = the removal counter); else the change list.
-    avn_status hs_manifolds(bool dense, const StepParams<T>& np, avn_contact_change* changes, uint32_t* n_changes, uint32_t* chg, uint32_t* has, hipStream_t s) {
+    // for them, into the same `out` as those launches.
+    avn_status hs_manifolds(const NpOut& out, const StepParams<T>& np, hipStream_t s) {
         if (!hs_any()) return AVN_OK;
         avn_status st = hs_need_callbacks();
         if (st != AVN_OK) return st;
@@ -117,7 +127,7 @@
             // NEW ones: the retry's relaunch of both meets it twice.  The list is sized for that (every pair twice at worst) and the duplicates leave below.
             if ((st = hs_reserve_queries(2 * n + 16)) != AVN_OK) return st;
             HIPCHK(hipMemsetAsync(b_hs_cnt.p, 0, 4, s));
-            hs_rerun(hs_list(1), dense, np, changes, n_changes, chg, has, s);
+            hs_rerun(np_host_list(1, 0), out, np, s);
             HIPCHK(hipGetLastError());
             HIPCHK(hipMemcpyAsync(h_cnt, b_hs_cnt.p, 4, hipMemcpyDeviceToHost, s));
             HIPCHK(hipStreamSynchronize(s));
@@ -153,7 +163,7 @@
         }
         HIPCHK(hipMemcpyAsync(b_hs_mq.p, hq, (size_t)n * HS_MQ, hipMemcpyHostToDevice, s));
         HIPCHK(hipMemcpyAsync(b_hs_mm.p, hm, (size_t)n * HS_MM, hipMemcpyHostToDevice, s));
-        launch_narrow_phase_host<T>(dw, bp, ct, np, dense, changes, n_changes, chg, has, b_hs_mq.p, b_hs_mm.p, n, s, hk_phase1()); ++launches;
+        launch_narrow_phase_host<T>(dw, bp, ct, np, out, b_hs_mq.p, b_hs_mm.p, n, s, hk_phase1()); ++launches;
         HIPCHK(hipGetLastError());
         hs_stats.bytes_to_host += (uint64_t)n * HS_MQ; hs_stats.bytes_from_host += (uint64_t)n * (HS_MQ + HS_MM);
         return AVN_OK;

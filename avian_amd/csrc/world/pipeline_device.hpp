@@ -385,15 +385,14 @@
         ++pipe_step_no;
         const bool np_overlap = np_overlap_enabled && n_rows_old != 0 && bp.n_intervals != 0;
         NpHostList hs_hl;
+        auto np_out = [&]() { return NpOut{nullptr, pg.ctr + PGC_N_REM, pg.chg, pg.has}; };   // (read at every use: a step's new pairs may grow chg / has)
         if ((st = hs_begin(stream, &hs_hl)) != AVN_OK) return st;   // (host shapes: the list of this step's pairs whose manifold the host computes -- empty world/host_shapes.hpp when there are none)
         if (np_overlap) {
             if (!ev_np_fork) { HIPCHK(hipEventCreateWithFlags(&ev_np_fork, hipEventDisableTiming | EV_FLAGS)); HIPCHK(hipEventCreateWithFlags(&ev_np_old, hipEventDisableTiming | EV_FLAGS)); }
             HIPCHK(hipEventRecord(ev_np_fork, stream));
             HIPCHK(hipStreamWaitEvent(stream_bp, ev_np_fork, 0));
             // (issued BEFORE the broad phase's ~20 launches: the host needs ~150 us to enqueue those, and the narrow phase would start that late)
-            launch_narrow_phase_dense<T>(dw, bp, ct, np_params, n_rows_old, pg.chg, pg.has, pg.ctr + PGC_N_REM, stream, false, hs_hl);
-            hs_launches.push_back(HsLaunch{1, n_rows_old, 0, 0, 0, nullptr});
-            ++launches;
+            np_launch(NpRows::dense(n_rows_old), np_out(), hs_hl, np_params);
             HIPCHK(hipEventRecord(ev_np_old, stream));
             bs = stream_bp;
         }
@@ -470,14 +469,11 @@
         const uint32_t n_rows = pgm_next_id;
         uint32_t n_ops = 0, n_rem = 0, n_sleep_ops = 0;
         if (n_rows) {
-            if (!np_overlap) { launch_narrow_phase_dense<T>(dw, bp, ct, np_params, n_rows, pg.chg, pg.has, pg.ctr + PGC_N_REM, stream, false, hs_hl); hs_launches.push_back(HsLaunch{1, n_rows, 0, 0, 0, nullptr}); ++launches; }
-            else if (total) {   // the rows this step added: the lowest free ids first (k_pg_add_pairs), then the fresh ones
-                launch_narrow_phase_rows<T>(dw, bp, ct, np_params, pg.free_ids + head_old, used_ids, n_rows_old, total - used_ids, pg.chg, pg.has, pg.ctr + PGC_N_REM, stream, hs_hl);
-                hs_launches.push_back(HsLaunch{2, used_ids, n_rows_old, total - used_ids, 0, pg.free_ids + head_old});
-                ++launches;
-            }
-            if (hs_hl.queries && (st = hs_manifolds(true, np_params, nullptr, pg.ctr + PGC_N_REM, pg.chg, pg.has, stream)) != AVN_OK) return fail(st);
-            if (hs_hl.hook.count && (st = hk_modify(true, np_params, nullptr, pg.ctr + PGC_N_REM, pg.chg, pg.has, stream)) != AVN_OK) return fail(st);   // CollisionHooks::modify_contacts
+            if (!np_overlap) np_launch(NpRows::dense(n_rows), np_out(), hs_hl, np_params);
+            else if (total)   // the rows this step added: the lowest free ids first (k_pg_add_pairs), then the fresh ones
+                np_launch(NpRows::added(pg.free_ids + head_old, used_ids, n_rows_old, total - used_ids), np_out(), hs_hl, np_params);
+            if (hs_hl.queries && (st = hs_manifolds(np_out(), np_params, stream)) != AVN_OK) return fail(st);
+            if (hs_hl.hook.count && (st = hk_modify(np_out(), np_params, stream)) != AVN_OK) return fail(st);   // CollisionHooks::modify_contacts
             if ((st = pg_batch_begin()) != AVN_OK) return fail(st);
             launch_pg_scan_classify(pg, n_rows, dw.n_bodies, b_pg_sums.as<uint32_t>(), stream, slp_on ? dw.bmeta : nullptr);   // ops numbered in ascending ContactId AND classified
             ++launches;

@@ -105,6 +105,44 @@ def test_hooks_on_pairs_whose_manifold_is_the_hosts():
     assert both > 20, "pairs with a host-shaped collider must have reached the hook"
 
 
+def test_phase_two_replays_an_added_launch_with_a_list_part():
+    """The hooks' phase 2 repeats the step's recorded launches.  Bodies fly apart while others keep colliding (the scene of
+    tests/test_gpu_graph.py::test_pairs_removed_and_ids_reused_like_the_oracle), so ids are freed and taken again and the launch over a step's added rows visits them
+    through its list; half the colliders are host-shaped and every collider asks for the hooks.  The test proves its own path: it counts the steps in which a new pair
+    took an id below the highest one issued before AND a record with that contact id reached modify_contacts in the same step.  The reference alone gives 28 such
+    steps of 90 (84 with a reused id at all), so the floor of 10 has a wide margin."""
+    hip, orc = hip_lib(), oracle_lib()
+    bodies, colliders = dropped_boxes(seed=5, n=48, balls=True)
+    bodies["linear_velocity"][1:25] = [[5.0, 1.0, 0.0]] * 24
+    bodies["linear_velocity"][25:] = [[-4.0, 0.5, 1.0]] * 24
+    n = len(colliders["shape"])
+    host, flagged = np.random.default_rng(5).random(n) < 0.5, np.ones(n, bool)
+    worlds, hooks = [], []
+    for lib in (hip, orc):
+        h = Hooks(identity=True)
+        cols = dict(colliders, shape=np.where(host, F.SHAPE_HOST, colliders["shape"]).astype(np.uint8))
+        w = hooked_world(lib, 32, bodies, cols, flagged, h)
+        hs = HostShapes(F.World(orc, F.default_config(32)), colliders["entity_index"], colliders["shape"], colliders["half_extents"])
+        w.host_shapes_set(hs.aabb, hs.manifolds)
+        w._hs_obj = hs
+        w.pipeline_enable()
+        worlds.append(w); hooks.append(h)
+    dev, ref = worlds
+    dt = F.hook_contact_dtype(32)
+    issued, replayed = -1, 0
+    for step in range(90):
+        shown = len(hooks[0].modify_log)
+        dev.step(); ref.step()
+        assert_same_hooked_step(dev, ref, step)
+        new = dev.pipeline_new_pair_ids().astype(np.int64)
+        reused = set(new[new < issued].tolist())
+        replayed += bool(reused & set(int(np.frombuffer(raw, dt)[0]["contact_id"]) for raw in hooks[0].modify_log[shown:]))
+        issued = max(issued, int(new.max()) if len(new) else -1)
+    assert hooks[0].filter_log == hooks[1].filter_log and hooks[0].modify_log == hooks[1].modify_log
+    print(f"\n[collision hooks] steps in which a reused row reached modify_contacts: {replayed}")
+    assert replayed >= 10
+
+
 def test_hooks_with_sleeping_enabled():
     hip, orc = hip_lib(), oracle_lib()
     bodies, colliders = dropped_boxes(seed=14, n=40)
