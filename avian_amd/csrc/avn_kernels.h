@@ -509,6 +509,11 @@ template <class T> struct SP {
     uint32_t* bounds;        // [8] order-preserving keys of the centroid bounds (min xyz, max xyz)
     uint32_t *keys_a, *vals_a, *keys_b, *vals_b, *hist, *block_sums;   // the Morton sort's buffers
 };
+// The first argument of a CTRI traversal kernel (triangle colliders are candidates, avn_spatial_triangle_colliders_set): the snapshot plus the world's
+// slot-indexed triangle table BP::col_tri, which the leaf reads where a candidate's shape is AVN_SHAPE_TRIANGLE.  The kernels without CTRI keep SP<T>.
+template <class T> struct SPT : SP<T> { const Vec4<T>* tri; };
+template <class T, bool CTRI> struct SpArg { using type = SP<T>; };
+template <class T> struct SpArg<T, true> { using type = SPT<T>; };
 template <class T> struct SpatialHit { uint32_t collider, entity; T distance; T normal[3]; };   // == avn_spatial_hit_fNN
 template <class T> struct SpatialProjection { uint32_t collider, entity, is_inside; T point[3]; T distance; };   // == avn_spatial_projection_fNN
 template <> struct SpatialProjection<double> { uint32_t collider, entity, is_inside, reserved; double point[3]; double distance; };   // (no implicit padding: every byte of a record is written)
@@ -636,14 +641,16 @@ template <class T> struct SL {
 };
 template <class T> void launch_spatial_project_velocity(const SV<T>&, hipStream_t);
 // capsule (here and below): the call may hold AVN_SHAPE_CAPSULE query shapes, so the kernels' CAPSULE instantiations run behind the first launch
-template <class T> void launch_spatial_cast_move(const SP<T>&, const SM<T>&, bool zero_stats, hipStream_t, bool capsule = false, bool ccap = false);
+// tri (here and below): the world's triangle table when the snapshot holds triangle colliders as candidates (the CTRI instantiations go), else nullptr
+template <class T> void launch_spatial_cast_move(const SP<T>&, const SM<T>&, bool zero_stats, hipStream_t, bool capsule = false, bool ccap = false, const Vec4<T>* tri = nullptr);
 template <class T> void launch_spatial_slide_phase(const SL<T>&, int phase, hipStream_t);
-template <class T> void launch_spatial_build(const DW<T>&, const BP<T>&, const SP<T>&, hipStream_t, bool ccap = false, bool triangles = false /* the world holds AVN_SHAPE_TRIANGLE colliders: never candidates */);
-template <class T> void launch_spatial_query(const SP<T>&, const SQ<T>&, int kind, hipStream_t, bool capsule = false, bool ccap = false);
+template <class T> void launch_spatial_build(const DW<T>&, const BP<T>&, const SP<T>&, hipStream_t, bool ccap = false, bool triangles = false /* the world holds AVN_SHAPE_TRIANGLE colliders */,
+                                             bool ctri = false /* and they are candidates (BP::col_tri is set); otherwise they are left out */);
+template <class T> void launch_spatial_query(const SP<T>&, const SQ<T>&, int kind, hipStream_t, bool capsule = false, bool ccap = false, const Vec4<T>* tri = nullptr);
 template <class T> void launch_spatial_reaim(const DW<T>&, const SP<T>&, const SCA<T>&, hipStream_t);
 // a caster group: kind SPQ_CLOSEST / SPQ_HITS / SPQ_CAST / SPQ_CAST_HITS with the per-query filter; q.stats is NOT zeroed (the run zeroes it once)
-template <class T> void launch_spatial_casters(const SP<T>&, const SQ<T>&, int kind, hipStream_t, bool capsule = false, bool ccap = false);
-template <class T> void launch_spatial_contacts(const SP<T>&, const SC<T>&, hipStream_t, bool zero_stats = true, bool capsule = false, bool ccap = false);
+template <class T> void launch_spatial_casters(const SP<T>&, const SQ<T>&, int kind, hipStream_t, bool capsule = false, bool ccap = false, const Vec4<T>* tri = nullptr);
+template <class T> void launch_spatial_contacts(const SP<T>&, const SC<T>&, hipStream_t, bool zero_stats = true, bool capsule = false, bool ccap = false, const Vec4<T>* tri = nullptr);
 template <class T> void launch_spatial_depenetrate(const SD<T>&, hipStream_t);
 
 // ---- k_ccd.hip: swept CCD (solve_swept_ccd, dynamics/ccd/mod.rs:523-687; include/avian_mi355x_ccd.h) as a pass over the contact rows ----

@@ -16,6 +16,7 @@ extern "C" {
 
 AVN_API avn_status avn_spatial_update(avn_world* w) { SP_GUARD(spatial_update()); }
 AVN_API avn_status avn_spatial_capsule_colliders_set(avn_world* w, uint32_t enabled) { SP_GUARD(spatial_capsule_colliders_set(enabled)); }
+AVN_API avn_status avn_spatial_triangle_colliders_set(avn_world* w, uint32_t enabled) { SP_GUARD(spatial_triangle_colliders_set(enabled)); }
 AVN_API avn_status avn_spatial_cast_rays(avn_world* w, const avn_spatial_rays* r, const avn_spatial_hits_out* o) { SP_GUARD(spatial_cast_rays(r, 0u, o)); }
 AVN_API avn_status avn_spatial_ray_hits(avn_world* w, const avn_spatial_rays* r, uint32_t max_hits, const avn_spatial_hits_out* o) {
     if (w && w->impl && (max_hits == 0 || max_hits > AVN_SPATIAL_MAX_HITS)) { w->impl->error = "spatial_ray_hits: max_hits must be 1 .. AVN_SPATIAL_MAX_HITS"; return AVN_ERR_BAD_ARG; }

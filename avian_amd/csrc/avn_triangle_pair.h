@@ -92,6 +92,28 @@ template <class T> __device__ __forceinline__ void tri_attempt(TriBest<T>& best,
     const T d2 = na_dot(d, d);
     if (d2 < best.d2) { best.d2 = d2; best.ps = ps; best.pt = pt; best.region = region; }
 }
+// The closest points of the segment A + s u, s in [0, 1], and the triangle when the segment does not cross the face: the first smallest of five
+// candidate pairs -- the two ends against the triangle (tri_closest_point), then the segment against edge k = 0, 1, 2 (sp_seg_seg).  ONE routine for the
+// narrow phase (tri_capsule) and the spatial queries (sp_seg_tri_d2, avn_spatial_triangle_pair.h).
+template <class T> __device__ __forceinline__ TriBest<T> tri_seg_closest(V3<T> a, V3<T> b, V3<T> c, V3<T> A, V3<T> u) {
+    const V3<T> B = A + u;
+    TriBest<T> best{sp_inf<T>(), A, a, 4};
+    {
+        int rg;
+        const V3<T> q0 = tri_closest_point<T>(a, b, c, A, rg);
+        tri_attempt<T>(best, A, q0, rg);
+        const V3<T> q1 = tri_closest_point<T>(a, b, c, B, rg);
+        tri_attempt<T>(best, B, q1, rg);
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const V3<T> vk = k == 0 ? a : (k == 1 ? b : c), vn = k == 0 ? b : (k == 1 ? c : a);
+        const V3<T> ek = vn - vk;
+        const SegSeg<T> ss = sp_seg_seg<T>(A, u, vk, ek);
+        tri_attempt<T>(best, A + u * ss.s, vk + ek * ss.t, ss.t == T(0) ? 4 + k : (ss.t == T(1) ? 4 + (k + 1) % 3 : 1 + k));
+    }
+    return best;
+}
 template <class T, class Em>
 __device__ __forceinline__ bool tri_capsule(V3<T> a, V3<T> b, V3<T> c, uint32_t flags, bool flipped, T r, T h, const Iso<T>& p, T pred, Em& em) {
     const V3<T> hv = na_qrot(p.r, V3<T>{T(0), h, T(0)});
@@ -117,21 +139,7 @@ __device__ __forceinline__ bool tri_capsule(V3<T> a, V3<T> b, V3<T> c, uint32_t 
             return true;
         }
     }
-    TriBest<T> best{sp_inf<T>(), A, a, 4};
-    {
-        int rg;
-        const V3<T> q0 = tri_closest_point<T>(a, b, c, A, rg);
-        tri_attempt<T>(best, A, q0, rg);
-        const V3<T> q1 = tri_closest_point<T>(a, b, c, B, rg);
-        tri_attempt<T>(best, B, q1, rg);
-    }
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const V3<T> vk = k == 0 ? a : (k == 1 ? b : c), vn = k == 0 ? b : (k == 1 ? c : a);
-        const V3<T> ek = vn - vk;
-        const SegSeg<T> ss = sp_seg_seg<T>(A, u, vk, ek);
-        tri_attempt<T>(best, A + u * ss.s, vk + ek * ss.t, ss.t == T(0) ? 4 + k : (ss.t == T(1) ? 4 + (k + 1) % 3 : 1 + k));
-    }
+    const TriBest<T> best = tri_seg_closest<T>(a, b, c, A, u);
     const T dist = sqrt_t(best.d2);
     if (!(dist > T(0)) || !(dist <= r + pred)) return false;
     const V3<T> d = best.ps - best.pt;

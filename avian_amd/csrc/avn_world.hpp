@@ -122,6 +122,7 @@ struct WorldBase {
     // spatial queries (include/avian_mi355x_spatial.h; world/spatial.hpp)
     virtual avn_status spatial_update() = 0;
     virtual avn_status spatial_capsule_colliders_set(uint32_t enabled) = 0;
+    virtual avn_status spatial_triangle_colliders_set(uint32_t enabled) = 0;
     virtual avn_status spatial_cast_rays(const avn_spatial_rays*, uint32_t max_hits, const avn_spatial_hits_out*) = 0;   // max_hits 0: the closest hit only
     virtual avn_status spatial_point_intersections(const avn_spatial_points*, uint32_t, const avn_spatial_ids_out*) = 0;
     virtual avn_status spatial_aabb_intersections(const avn_spatial_aabbs*, uint32_t, const avn_spatial_ids_out*) = 0;

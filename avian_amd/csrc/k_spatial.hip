@@ -5,7 +5,9 @@
 // re-aiming (k_sp_reaim) and the per-caster filter of k_sp_query / k_sp_cast (PQ).  The kernels that take a query shape have a second,
 // CAPSULE instantiation for AVN_SHAPE_CAPSULE queries, launched behind the first (sp_lane_kind, sp_next_chunk).  The kernels
 // that reach a collider's geometry have a CCAP instantiation each, whose leaf tests know the capsule COLLIDER: the host launches it when the
-// world's switch is on and the snapshot holds a capsule collider, and the ones it always has otherwise.
+// world's switch is on and the snapshot holds a capsule collider, and the ones it always has otherwise.  Likewise a CTRI
+// instantiation each for the triangle COLLIDER (avn_spatial_triangle_colliders_set): its first argument carries the world's triangle
+// table, which the leaf reads by value where a candidate's shape is AVN_SHAPE_TRIANGLE; a CTRI launch always takes CCAP as well.
 //
 // avn_spatial_update (launch_spatial_build), all on the world's stream:
 //   1. k_sp_snapshot   one thread per collider: its pose (collider_pose), the exact shape AABB (shape_aabb), padded, as the leaf box;
@@ -35,6 +37,7 @@
 #include "avn_narrow.h"
 #include "avn_spatial_pair.h"
 #include "avn_capsule_pair.h"   // capsule colliders: the CAP instantiation of contact_manifolds_pair_sink (the CCAP contact kernels)
+#include "avn_spatial_triangle_pair.h"   // triangle colliders: the pair tests of the CTRI instantiations (and avn_triangle_pair.h: their contacts)
 #include "../../include/avian_mi355x_spatial.h"
 
 namespace avn {
@@ -65,7 +68,9 @@ template <class T> __device__ __forceinline__ void sp_pad_box(V3<T> a, V3<T> b, 
 // CCAP: a capsule collider is a candidate, its leaf box shape_aabb<T, true> padded like every other
 // TRI: the world holds AVN_SHAPE_TRIANGLE colliders (include/avian_mi355x_trimesh.h): left out exactly as a host shape is (no device geometry for the queries);
 // a world without one launches the instantiations it always has
-template <class T, bool CCAP = false, bool TRI = false>
+// CTRI (avn_spatial_triangle_colliders_set is on and the world holds a triangle; BP::col_tri is set): a triangle collider is a candidate, its leaf box
+// shape_aabb's TRI case (the min / max of its three posed vertices) padded like every other
+template <class T, bool CCAP = false, bool TRI = false, bool CTRI = false>
 __global__ __launch_bounds__(256) void k_sp_snapshot(DW<T> w, BP<T> bp, SP<T> sp) {
     const uint32_t c = blockIdx.x * 256 + threadIdx.x;
     if (c >= sp.n) return;
@@ -82,9 +87,10 @@ __global__ __launch_bounds__(256) void k_sp_snapshot(DW<T> w, BP<T> bp, SP<T> sp
     // position, rotation and shape AABB; the others get an empty leaf box and never reach an exact test
     bool candidate = false;
     V3<T> mn{sp_inf<T>(), sp_inf<T>(), sp_inf<T>()}, mx{-sp_inf<T>(), -sp_inf<T>(), -sp_inf<T>()};
-    if (shape != AVN_SHAPE_HOST && (CCAP || shape != AVN_SHAPE_CAPSULE) && (!TRI || shape != AVN_SHAPE_TRIANGLE) && is_finite(pos) && is_finite(V3<T>{rot.x, rot.y, rot.z}) && finite_t(rot.w)) {
+    if (shape != AVN_SHAPE_HOST && (CCAP || shape != AVN_SHAPE_CAPSULE) && (!TRI || CTRI || shape != AVN_SHAPE_TRIANGLE) && is_finite(pos) && is_finite(V3<T>{rot.x, rot.y, rot.z}) && finite_t(rot.w)) {
         V3<T> a, b;
-        shape_aabb<T, CCAP>(shape, h, pos, rot, a, b);
+        if (CTRI) shape_aabb<T, CCAP, true>(shape, h, pos, rot, a, b, bp.col_tri + 3 * (size_t)c);
+        else shape_aabb<T, CCAP>(shape, h, pos, rot, a, b);
         if (is_finite(a) && is_finite(b)) {
             candidate = true;
             sp_pad_box(a, b, mn, mx);
@@ -187,13 +193,16 @@ __global__ __launch_bounds__(256) void k_sp_refit(SP<T> sp) {
     }
 }
 
-template <class T> void launch_spatial_build(const DW<T>& w, const BP<T>& bp, const SP<T>& sp, hipStream_t s, bool ccap, bool triangles) {
+template <class T> void launch_spatial_build(const DW<T>& w, const BP<T>& bp, const SP<T>& sp, hipStream_t s, bool ccap, bool triangles, bool ctri) {
     const uint32_t n = sp.n;
     if (n == 0) return;
     const uint32_t nb = (n + 255) / 256;
     // bounds: min keys start at ~0, max keys at 0 (one memset each half)
     (void)hipMemsetAsync(sp.bounds, 0xFF, 3 * sizeof(uint32_t), s);
     (void)hipMemsetAsync(sp.bounds + 3, 0x00, 5 * sizeof(uint32_t), s);
+    // (the snapshot keeps both CCAP forms under CTRI: it is the one kernel in which CCAP decides whether a capsule is a candidate at all)
+    if (ctri) { if (ccap) hipLaunchKernelGGL((k_sp_snapshot<T, true, true, true>), dim3(nb), dim3(256), 0, s, w, bp, sp); else hipLaunchKernelGGL((k_sp_snapshot<T, false, true, true>), dim3(nb), dim3(256), 0, s, w, bp, sp); }
+    else
     if (triangles) { if (ccap) hipLaunchKernelGGL((k_sp_snapshot<T, true, true>), dim3(nb), dim3(256), 0, s, w, bp, sp); else hipLaunchKernelGGL((k_sp_snapshot<T, false, true>), dim3(nb), dim3(256), 0, s, w, bp, sp); }
     else
     if (ccap) hipLaunchKernelGGL((k_sp_snapshot<T, true>), dim3(nb), dim3(256), 0, s, w, bp, sp);
@@ -208,15 +217,27 @@ template <class T> void launch_spatial_build(const DW<T>& w, const BP<T>& bp, co
 
 // ---------------------------------------------------------------------------------------------------------
 // exact per-collider tests (the header's restatement of parry3d; tests/spatial_query_reference.py does the same operations in order)
-template <class T, bool CCAP = false>
-__device__ __forceinline__ bool sp_ray_exact(uint32_t shape, V3<T> he, V3<T> pos, Q4<T> rot, V3<T> o, V3<T> d, T max_distance, bool solid, T& toi, V3<T>& normal) {
+// The triangle of collider c (CTRI): the three records of its slot in the world's table BP::col_tri, which SPT::tri names.  The snapshot does not copy the
+// table: avn_colliders_upload and avn_collider_triangles_upload both clear sp_valid, so no query reads a table newer than its snapshot.
+template <class T> __device__ __forceinline__ const Vec4<T>* sp_tri(const SP<T>&) { return nullptr; }
+template <class T> __device__ __forceinline__ const Vec4<T>* sp_tri(const SPT<T>& sp) { return sp.tri; }
+template <class T> __device__ __forceinline__ NpTri<T> sp_load_tri(const Vec4<T>* tri, uint32_t c) {
+    const Vec4<T> a = tri[3 * (size_t)c], b = tri[3 * (size_t)c + 1], cc = tri[3 * (size_t)c + 2];
+    return NpTri<T>{xyz<T>(a), xyz<T>(b), xyz<T>(cc), scalar_to_bits(a.w) & 7u};
+}
+// CTRI: `tri` is the triangle of a collider whose shape is AVN_SHAPE_TRIANGLE (by value; not read otherwise)
+template <class T, bool CCAP = false, bool CTRI = false>
+__device__ __forceinline__ bool sp_ray_exact(uint32_t shape, V3<T> he, V3<T> pos, Q4<T> rot, V3<T> o, V3<T> d, T max_distance, bool solid, T& toi, V3<T>& normal, NpTri<T> tri = NpTri<T>()) {
     const Q4<T> ci = qinverse(rot);
     const V3<T> ol = qrot(ci, o - pos);
     const V3<T> dl = qrot(ci, d);
     T t;
     bool zero_normal = false;
     V3<T> nl = vzero<T>();
-    if (CCAP && shape == AVN_SHAPE_CAPSULE) {
+    if (CTRI && shape == AVN_SHAPE_TRIANGLE) {
+        if (!sp_tri_ray<T>(tri.a, tri.b, tri.c, ol, dl, t, nl)) return false;
+        if (!(t <= max_distance)) return false;
+    } else if (CCAP && shape == AVN_SHAPE_CAPSULE) {
         if (!sp_capcol_ray<T>(he, ol, dl, solid, t, nl)) return false;
         if (!(t <= max_distance)) return false;
         zero_normal = nl.x == T(0) && nl.y == T(0) && nl.z == T(0);
@@ -274,15 +295,17 @@ __device__ __forceinline__ bool sp_ray_exact(uint32_t shape, V3<T> he, V3<T> pos
     normal = zero_normal ? vzero<T>() : qrot(rot, nl);
     return true;
 }
-template <class T, bool CCAP = false> __device__ __forceinline__ bool sp_point_exact(uint32_t shape, V3<T> he, V3<T> pos, Q4<T> rot, V3<T> p) {
+template <class T, bool CCAP = false, bool CTRI = false> __device__ __forceinline__ bool sp_point_exact(uint32_t shape, V3<T> he, V3<T> pos, Q4<T> rot, V3<T> p, NpTri<T> tri = NpTri<T>()) {
     const V3<T> pl = qrot(qinverse(rot), p - pos);
+    if (CTRI && shape == AVN_SHAPE_TRIANGLE) return sp_tri_point<T>(tri.a, tri.b, tri.c, pl);
     if (CCAP && shape == AVN_SHAPE_CAPSULE) return sp_capcol_point<T>(he, pl);
     if (shape == AVN_SHAPE_BALL) return dot(pl, pl) <= he.x * he.x;
     return fabs_t(pl.x) <= he.x && fabs_t(pl.y) <= he.y && fabs_t(pl.z) <= he.z;
 }
-template <class T, bool CCAP = false> __device__ __forceinline__ bool sp_aabb_exact(uint32_t shape, V3<T> he, V3<T> pos, Q4<T> rot, V3<T> qmin, V3<T> qmax) {
+// tri3 (CTRI): the three table records of the collider (read only where its shape is AVN_SHAPE_TRIANGLE)
+template <class T, bool CCAP = false, bool CTRI = false> __device__ __forceinline__ bool sp_aabb_exact(uint32_t shape, V3<T> he, V3<T> pos, Q4<T> rot, V3<T> qmin, V3<T> qmax, const Vec4<T>* tri3 = nullptr) {
     V3<T> mn, mx;
-    shape_aabb<T, CCAP>(shape, he, pos, rot, mn, mx);
+    shape_aabb<T, CCAP, CTRI>(shape, he, pos, rot, mn, mx, tri3);
     return mn.x <= qmax.x && mn.y <= qmax.y && mn.z <= qmax.z && mx.x >= qmin.x && mx.y >= qmin.y && mx.z >= qmin.z;
 }
 
@@ -358,6 +381,9 @@ template <class T, bool CAPSULE = false> __device__ __forceinline__ QShape<T> sp
     }
     return s;
 }
+// the kind of a valid query shape as the instantiation knows it (a CAPSULE one: a capsule; the first: a ball or a cuboid): the triangle manifold of the
+// contacts then compiles the one or two pair tests the instantiation can reach, not all three
+template <bool CAPSULE> __device__ __forceinline__ uint32_t sp_query_kind(uint32_t shape) { return CAPSULE ? (uint32_t)AVN_SHAPE_CAPSULE : (shape == AVN_SHAPE_BALL ? (uint32_t)AVN_SHAPE_BALL : (uint32_t)AVN_SHAPE_CUBOID); }
 // a lane of a CAPSULE instantiation whose query is no capsule is passed over: the first launch has answered it
 template <bool CAPSULE> __device__ __forceinline__ bool sp_lane_kind(const uint8_t* shape, uint32_t i) { return !CAPSULE || shape[i] == AVN_SHAPE_CAPSULE; }
 // The chunks of SP_WAVE queries a block answers.  The first launch has one block per chunk.  A CAPSULE launch has at most SP_CAPSULE_GRID blocks
@@ -503,8 +529,10 @@ __device__ __forceinline__ void sp_walk(const SP<T>& sp, uint32_t& overflow, con
 
 // one lane per query.  PQ (a caster run, SPQ_CLOSEST / SPQ_HITS only): the lane answers caster q.index[lane's query] with that caster's own
 // self_entity, excluded slice, live flag and k, into its row of q.cap record slots.
-template <class T, int KIND, bool PQ = false, bool CCAP = false>
-__global__ __launch_bounds__(SP_WAVE) void k_sp_query(SP<T> sp, SQ<T> q) {
+// CTRI (here and in every traversal kernel below): a triangle collider is a candidate; the kernel's first argument then carries the world's triangle
+// table (SPT), and the leaf reads the collider's triangle from it BY VALUE where the collider's shape says triangle
+template <class T, int KIND, bool PQ = false, bool CCAP = false, bool CTRI = false>
+__global__ __launch_bounds__(SP_WAVE) void k_sp_query(typename SpArg<T, CTRI>::type sp, SQ<T> q) {
     constexpr bool RAY = KIND == SPQ_CLOSEST || KIND == SPQ_HITS;
     const uint32_t li = blockIdx.x * SP_WAVE + threadIdx.x;
     uint32_t nodes_tested = 0, leaves_tested = 0, overflow = 0;
@@ -546,9 +574,11 @@ __global__ __launch_bounds__(SP_WAVE) void k_sp_query(SP<T> sp, SQ<T> q) {
             ++leaves_tested;
             const V3<T> pos = xyz<T>(sp.pos[c]), he = xyz<T>(sp.he[c]);
             const Q4<T> rot = quat<T>(sp.rot[c]);
+            NpTri<T> tri = NpTri<T>();
+            if (CTRI && KIND != SPQ_AABBS && info.z == AVN_SHAPE_TRIANGLE) tri = sp_load_tri<T>(sp_tri(sp), c);
             if (RAY) {
                 T toi; V3<T> nrm;
-                if (!sp_ray_exact<T, CCAP>(info.z, he, pos, rot, r.o, r.d, max_distance, solid, toi, nrm)) return;
+                if (!sp_ray_exact<T, CCAP, CTRI>(info.z, he, pos, rot, r.o, r.d, max_distance, solid, toi, nrm, tri)) return;
                 if (KIND == SPQ_CLOSEST) {
                     if (toi < best || (toi == best && c < best_c)) { best = toi; best_c = c; best_n = nrm; }
                 } else {
@@ -559,7 +589,8 @@ __global__ __launch_bounds__(SP_WAVE) void k_sp_query(SP<T> sp, SQ<T> q) {
                     hl[m] = h;
                 }
             } else {
-                const bool hit = KIND == SPQ_POINTS ? sp_point_exact<T, CCAP>(info.z, he, pos, rot, pa) : sp_aabb_exact<T, CCAP>(info.z, he, pos, rot, pa, pb);
+                const bool hit = KIND == SPQ_POINTS ? sp_point_exact<T, CCAP, CTRI>(info.z, he, pos, rot, pa, tri)
+                                                    : sp_aabb_exact<T, CCAP, CTRI>(info.z, he, pos, rot, pa, pb, CTRI ? sp_tri(sp) + 3 * (size_t)c : nullptr);
                 if (!hit) return;
                 const uint32_t m = sp_slot_by_collider(il, q.cap, found, c);
                 if (m != AVN_SPATIAL_MISS) il[m] = c;
@@ -591,12 +622,19 @@ __global__ __launch_bounds__(SP_WAVE) void k_sp_query(SP<T> sp, SQ<T> q) {
 // point projection and shape intersections
 
 // the header's projection of a point onto one collider: false when the distance is not finite
-template <class T, bool CCAP = false>
-__device__ __forceinline__ bool sp_project_exact(uint32_t shape, V3<T> he, V3<T> pos, Q4<T> rot, V3<T> p, bool solid, T& distance, V3<T>& point, bool& is_inside) {
+// CTRI, a triangle collider: tri_closest_point; is_inside iff that is the point itself (sp_tri_point's test); `solid` has no effect (a triangle has no
+// interior: the point answered is always the projection carried back to the world)
+template <class T, bool CCAP = false, bool CTRI = false>
+__device__ __forceinline__ bool sp_project_exact(uint32_t shape, V3<T> he, V3<T> pos, Q4<T> rot, V3<T> p, bool solid, T& distance, V3<T>& point, bool& is_inside, NpTri<T> tri = NpTri<T>()) {
     const V3<T> pl = qrot(qinverse(rot), p - pos);
     V3<T> proj;
     bool inside;
-    if (CCAP && shape == AVN_SHAPE_CAPSULE) sp_capcol_project<T>(he, pl, solid, proj, inside);
+    if (CTRI && shape == AVN_SHAPE_TRIANGLE) {
+        int rg;
+        proj = tri_closest_point<T>(tri.a, tri.b, tri.c, pl, rg);
+        inside = proj.x == pl.x && proj.y == pl.y && proj.z == pl.z;
+        solid = false;
+    } else if (CCAP && shape == AVN_SHAPE_CAPSULE) sp_capcol_project<T>(he, pl, solid, proj, inside);
     else if (shape == AVN_SHAPE_BALL) {
         const T r = he.x;
         const T d2 = dot(pl, pl);
@@ -636,8 +674,8 @@ template <class T> __device__ __forceinline__ T sp_point_box_distance(V3<T> p, T
     return sqrt_t(dot(d, d)) * (T(1) - T(8) * Limits<T>::eps);
 }
 
-template <class T, bool CCAP = false>
-__global__ __launch_bounds__(SP_WAVE) void k_sp_project(SP<T> sp, SQ<T> q) {
+template <class T, bool CCAP = false, bool CTRI = false>
+__global__ __launch_bounds__(SP_WAVE) void k_sp_project(typename SpArg<T, CTRI>::type sp, SQ<T> q) {
     const uint32_t qi = blockIdx.x * SP_WAVE + threadIdx.x;
     uint32_t nodes_tested = 0, leaves_tested = 0, overflow = 0;
     if (qi < q.n) {
@@ -660,7 +698,9 @@ __global__ __launch_bounds__(SP_WAVE) void k_sp_project(SP<T> sp, SQ<T> q) {
             if (!sp_leaf_ok(info, mask, AVN_SPATIAL_MISS, q.excluded, q.n_excluded)) return;
             ++leaves_tested;
             T d; V3<T> pt; bool in;
-            if (!sp_project_exact<T, CCAP>(info.z, xyz<T>(sp.he[c]), xyz<T>(sp.pos[c]), quat<T>(sp.rot[c]), p, solid, d, pt, in)) return;
+            NpTri<T> tri = NpTri<T>();
+            if (CTRI && info.z == AVN_SHAPE_TRIANGLE) tri = sp_load_tri<T>(sp_tri(sp), c);
+            if (!sp_project_exact<T, CCAP, CTRI>(info.z, xyz<T>(sp.he[c]), xyz<T>(sp.pos[c]), quat<T>(sp.rot[c]), p, solid, d, pt, in, tri)) return;
             if (d < best || (d == best && c < best_c)) { best = d; best_c = c; best_p = pt; best_in = in ? 1u : 0u; }
         };
         if (is_finite(p)) sp_walk<T, true>(sp, overflow, best, test, leaf);
@@ -702,8 +742,8 @@ __device__ __forceinline__ bool sp_shape_exact(uint32_t shape1, V3<T> he1, const
     return true;
 }
 
-template <class T, bool CAPSULE = false, bool CCAP = false>
-__global__ __launch_bounds__(SP_WAVE) void k_sp_shapes(SP<T> sp, SQ<T> q) {
+template <class T, bool CAPSULE = false, bool CCAP = false, bool CTRI = false>
+__global__ __launch_bounds__(SP_WAVE) void k_sp_shapes(typename SpArg<T, CTRI>::type sp, SQ<T> q) {
     uint32_t nodes_tested = 0, leaves_tested = 0, overflow = 0;
     uint32_t base = blockIdx.x * SP_WAVE;
     do {   // (once; a CAPSULE launch: every chunk of this block's stride)
@@ -725,7 +765,9 @@ __global__ __launch_bounds__(SP_WAVE) void k_sp_shapes(SP<T> sp, SQ<T> q) {
             const uint4 info = sp.info[c];
             if (!sp_leaf_ok(info, mask, AVN_SPATIAL_MISS, q.excluded, q.n_excluded)) return;
             ++leaves_tested;
-            if (CCAP && info.z == AVN_SHAPE_CAPSULE) {
+            if (CTRI && info.z == AVN_SHAPE_TRIANGLE) {
+                if (!sp_tricol_intersects<T, CAPSULE>(s.shape, s.he, iso1, sp_load_tri<T>(sp_tri(sp), c), xyz<T>(sp.pos[c]), quat<T>(sp.rot[c]))) return;
+            } else if (CCAP && info.z == AVN_SHAPE_CAPSULE) {
                 if (!sp_capcol_intersects<T, CAPSULE>(s.shape, s.he, iso1, xyz<T>(sp.he[c]), xyz<T>(sp.pos[c]), quat<T>(sp.rot[c]))) return;
             } else if (CAPSULE) {
                 if (!sp_capsule_intersects<T>(s.he.x, s.he.y, iso_inv_mul(Iso<T>{quat<T>(sp.rot[c]), xyz<T>(sp.pos[c])}, iso1), info.z, xyz<T>(sp.he[c]))) return;
@@ -746,8 +788,8 @@ __global__ __launch_bounds__(SP_WAVE) void k_sp_shapes(SP<T> sp, SQ<T> q) {
 // order.  DESIGN.md 4.4.6 has the padding argument.
 
 // one lane per cast; MANY: the nearest-k list (shape_hits), else the closest hit (cast_shapes).  PQ: a caster run, as in k_sp_query
-template <class T, bool MANY, bool PQ = false, bool CAPSULE = false, bool CCAP = false>
-__global__ __launch_bounds__(SP_WAVE) void k_sp_cast(SP<T> sp, SQ<T> q) {
+template <class T, bool MANY, bool PQ = false, bool CAPSULE = false, bool CCAP = false, bool CTRI = false>
+__global__ __launch_bounds__(SP_WAVE) void k_sp_cast(typename SpArg<T, CTRI>::type sp, SQ<T> q) {
     uint32_t nodes_tested = 0, leaves_tested = 0, overflow = 0;
     uint32_t base = blockIdx.x * SP_WAVE;
     do {   // (once; a CAPSULE launch: every chunk of this block's stride)
@@ -782,7 +824,9 @@ __global__ __launch_bounds__(SP_WAVE) void k_sp_cast(SP<T> sp, SQ<T> q) {
             if (!sp_leaf_ok(info, mask, self, q.excluded + ex0, ex_n)) return;
             ++leaves_tested;
             T toi; V3<T> p1, p2, n1;
-            if (CCAP && info.z == AVN_SHAPE_CAPSULE) {
+            if (CTRI && info.z == AVN_SHAPE_TRIANGLE) {
+                if (!sp_tricol_cast_exact<T, CAPSULE>(s.shape, s.he, iso2, d, max_distance, sp_load_tri<T>(sp_tri(sp), c), xyz<T>(sp.pos[c]), quat<T>(sp.rot[c]), toi, p1, p2, n1)) return;
+            } else if (CCAP && info.z == AVN_SHAPE_CAPSULE) {
                 if (!sp_capcol_cast_exact<T, CAPSULE>(s.shape, s.he, iso2, d, max_distance, xyz<T>(sp.he[c]), xyz<T>(sp.pos[c]), quat<T>(sp.rot[c]), toi, p1, p2, n1)) return;
             } else if (CAPSULE) {
                 if (!sp_capsule_cast_exact<T>(s.he.x, s.he.y, iso2, d, max_distance, info.z, xyz<T>(sp.he[c]), xyz<T>(sp.pos[c]), quat<T>(sp.rot[c]), toi, p1, p2, n1)) return;
@@ -822,8 +866,10 @@ __global__ __launch_bounds__(SP_WAVE) void k_sp_cast(SP<T> sp, SQ<T> q) {
 // untouched.  DESIGN.md 4.4.7.
 
 // one lane per query shape; records inserted in ascending collider index as k_sp_shapes inserts ids
-template <class T, bool CAPSULE = false, bool CCAP = false>
-__global__ __launch_bounds__(SP_WAVE) void k_sp_contacts(SP<T> sp, SC<T> sc) {
+// CTRI, a triangle collider: the narrow phase's triangle manifold (contact_manifolds_pair_sink<.., CAP, TRI>, avn_triangle_pair.h) with the query as shape 1
+// -- a Ball, a Cuboid or a Capsule alike -- and the collider's triangle, edge flags included, as tri2; the deepest point is kept
+template <class T, bool CAPSULE = false, bool CCAP = false, bool CTRI = false>
+__global__ __launch_bounds__(SP_WAVE) void k_sp_contacts(typename SpArg<T, CTRI>::type sp, SC<T> sc) {
     const SQ<T>& q = sc.q;
     uint32_t nodes_tested = 0, leaves_tested = 0, overflow = 0;
     uint32_t base = blockIdx.x * SP_WAVE;
@@ -856,12 +902,18 @@ __global__ __launch_bounds__(SP_WAVE) void k_sp_contacts(SP<T> sp, SC<T> sc) {
             const Q4<T> rot2 = quat<T>(sp.rot[c]);
             // (b) the collider's exact box, by the snapshot's own arithmetic
             V3<T> mn, mx;
-            shape_aabb<T, CCAP>(info.z, he2, pos2, rot2, mn, mx);
+            shape_aabb<T, CCAP, CTRI>(info.z, he2, pos2, rot2, mn, mx, CTRI ? sp_tri(sp) + 3 * (size_t)c : nullptr);
             if (!sp_box_box(gmin, gmax, make4<T>(mn, T(0)), make4<T>(mx, T(0)))) return;
             // (c), (d)
             SpDeepestSink<T> sink{vzero<T>(), T(0), 0};
             V3<T> nrm, a1, a2;
-            if (CAPSULE && CCAP && info.z == AVN_SHAPE_CAPSULE) {
+            if (CTRI && info.z == AVN_SHAPE_TRIANGLE) {
+                const NpTri<T> tri = sp_load_tri<T>(sp_tri(sp), c);
+                bool ok;
+                AVN_INLINE_CALL ok = contact_manifolds_pair_sink<T, SpDeepestSink<T>, 0, true, true>(sp_query_kind<CAPSULE>(s.shape), s.he, s.pos, s.rot, AVN_SHAPE_TRIANGLE, he2, pos2, rot2, pred, sink, nrm, nullptr, nullptr, NpTri<T>(), tri);
+                if (!ok) return;
+                a1 = sink.anchor1; a2 = a1 + (s.pos - pos2);
+            } else if (CAPSULE && CCAP && info.z == AVN_SHAPE_CAPSULE) {
                 // (two capsules: the narrow phase's capsule-capsule manifold, the query as shape 1)
                 if (!contact_manifolds_pair_sink<T, SpDeepestSink<T>, 0, true>(AVN_SHAPE_CAPSULE, s.he, s.pos, s.rot, AVN_SHAPE_CAPSULE, he2, pos2, rot2, pred, sink, nrm)) return;
                 a1 = sink.anchor1; a2 = a1 + (s.pos - pos2);
@@ -871,7 +923,11 @@ __global__ __launch_bounds__(SP_WAVE) void k_sp_contacts(SP<T> sp, SC<T> sc) {
                 if (!sp_capsule_contact<T>(s.he.x, s.he.y, iso2, info.z, he2, pos2, rot2, pred, sink.penetration, cn, a1, a2)) return;
                 nrm = -cn;
             } else {
-                if (!contact_manifolds_pair_sink<T, SpDeepestSink<T>, 0, CCAP>(s.shape, s.he, s.pos, s.rot, info.z, he2, pos2, rot2, pred, sink, nrm)) return;
+                // (CTRI: inlined by statement attribute like the triangle manifold above -- left to the inliner this call stayed a real call in the CTRI
+                // instantiations, with the sink and the normal in 64 / 192 bytes of scratch memory.  Nothing but the compiler's figures pins this: after a ROCm
+                // update re-run the recipe at the head of profiles/spatial_triangle_colliders_resource_usage.txt and look for scratch 0 in every CTRI kernel)
+                if constexpr (CTRI) { bool ok; AVN_INLINE_CALL ok = contact_manifolds_pair_sink<T, SpDeepestSink<T>, 0, CCAP>(s.shape, s.he, s.pos, s.rot, info.z, he2, pos2, rot2, pred, sink, nrm); if (!ok) return; }
+                else if (!contact_manifolds_pair_sink<T, SpDeepestSink<T>, 0, CCAP>(s.shape, s.he, s.pos, s.rot, info.z, he2, pos2, rot2, pred, sink, nrm)) return;
                 a1 = sink.anchor1; a2 = a1 + (s.pos - pos2);
             }
             const uint32_t m = sp_slot_by_collider(rl, q.cap, found, c);
@@ -929,15 +985,20 @@ __global__ __launch_bounds__(SP_WAVE) void k_sp_depenetrate(SD<T> d) {
     d.out[qi] = r;
 }
 
-template <class T, bool CCAP> static void launch_spatial_contacts_as(const SP<T>& sp, const SC<T>& sc, hipStream_t s, bool capsule) {
-    hipLaunchKernelGGL((k_sp_contacts<T, false, CCAP>), dim3((sc.q.n + SP_WAVE - 1) / SP_WAVE), dim3(SP_WAVE), 0, s, sp, sc);
-    if (capsule) hipLaunchKernelGGL((k_sp_contacts<T, true, CCAP>), sp_capsule_grid(sc.q.n), dim3(SP_WAVE), 0, s, sp, sc);
+// CTRI (the `_as` helpers of every launcher): sp is the snapshot with the world's triangle table (SPT), made by the launcher from its `tri` argument
+template <class T, bool CCAP, bool CTRI = false> static void launch_spatial_contacts_as(const typename SpArg<T, CTRI>::type& sp, const SC<T>& sc, hipStream_t s, bool capsule) {
+    hipLaunchKernelGGL((k_sp_contacts<T, false, CCAP, CTRI>), dim3((sc.q.n + SP_WAVE - 1) / SP_WAVE), dim3(SP_WAVE), 0, s, sp, sc);
+    if (capsule) hipLaunchKernelGGL((k_sp_contacts<T, true, CCAP, CTRI>), sp_capsule_grid(sc.q.n), dim3(SP_WAVE), 0, s, sp, sc);
 }
 // ccap (here and in every launch_spatial_* below): the snapshot holds capsule colliders as candidates -- the CCAP instantiations go
-template <class T> void launch_spatial_contacts(const SP<T>& sp, const SC<T>& sc, hipStream_t s, bool zero_stats, bool capsule, bool ccap) {
+// tri (here and in every launch_spatial_* below): the world's triangle table when the snapshot holds triangle colliders as candidates -- the CTRI
+// instantiations go, always with CCAP (a snapshot built with the capsule switch off holds no capsule candidate, so the branch is never taken); nullptr: the
+// launches of a world without the triangle switch, exactly as before
+template <class T> void launch_spatial_contacts(const SP<T>& sp, const SC<T>& sc, hipStream_t s, bool zero_stats, bool capsule, bool ccap, const Vec4<T>* tri) {
     if (zero_stats) (void)hipMemsetAsync(sc.q.stats, 0, 4 * sizeof(unsigned long long), s);
     if (sc.q.n == 0) return;
-    if (ccap) launch_spatial_contacts_as<T, true>(sp, sc, s, capsule);
+    if (tri) launch_spatial_contacts_as<T, true, true>(SPT<T>{sp, tri}, sc, s, capsule);
+    else if (ccap) launch_spatial_contacts_as<T, true>(sp, sc, s, capsule);
     else launch_spatial_contacts_as<T, false>(sp, sc, s, capsule);
 }
 template <class T> void launch_spatial_depenetrate(const SD<T>& d, hipStream_t s) {
@@ -1032,8 +1093,8 @@ template <class T> __device__ __forceinline__ void sp_put_move(SpatialMoveHit<T>
 // applies the origin-penetration rule to the pending colliders with the narrow phase's contact_manifolds_pair_sink, merges them with the
 // traversal's hit by (distance, collider index) and pulls the distance back.  The contact manifold so stays out of the traversal's live
 // range (fused into the leaf the kernel needed 256 VGPRs + 13 / 72 AGPRs, one wave per SIMD: profiles/spatial_moves_resource_usage.txt).
-template <class T, bool CAPSULE = false, bool CCAP = false>
-__global__ __launch_bounds__(SP_WAVE) void k_sp_cast_move(SP<T> sp, SM<T> m) {
+template <class T, bool CAPSULE = false, bool CCAP = false, bool CTRI = false>
+__global__ __launch_bounds__(SP_WAVE) void k_sp_cast_move(typename SpArg<T, CTRI>::type sp, SM<T> m) {
     const SQ<T>& q = m.q;
     uint32_t nodes_tested = 0, leaves_tested = 0, overflow = 0;
     uint32_t base = blockIdx.x * SP_WAVE;
@@ -1069,7 +1130,9 @@ __global__ __launch_bounds__(SP_WAVE) void k_sp_cast_move(SP<T> sp, SM<T> m) {
             const V3<T> pos1 = xyz<T>(sp.pos[c]), he1 = xyz<T>(sp.he[c]);
             const Q4<T> rot1 = quat<T>(sp.rot[c]);
             T toi; V3<T> p1, p2, n1;
-            if (CCAP && info.z == AVN_SHAPE_CAPSULE) {
+            if (CTRI && info.z == AVN_SHAPE_TRIANGLE) {
+                if (!sp_tricol_cast_exact<T, CAPSULE>(s.shape, s.he, iso2, d, dist, sp_load_tri<T>(sp_tri(sp), c), pos1, rot1, toi, p1, p2, n1)) return;
+            } else if (CCAP && info.z == AVN_SHAPE_CAPSULE) {
                 if (!sp_capcol_cast_exact<T, CAPSULE>(s.shape, s.he, iso2, d, dist, he1, pos1, rot1, toi, p1, p2, n1)) return;
             } else if (CAPSULE) {
                 if (!sp_capsule_cast_exact<T>(s.he.x, s.he.y, iso2, d, dist, info.z, he1, pos1, rot1, toi, p1, p2, n1)) return;
@@ -1095,14 +1158,14 @@ __global__ __launch_bounds__(SP_WAVE) void k_sp_cast_move(SP<T> sp, SM<T> m) {
     sp_add_stats(q.stats, nodes_tested, leaves_tested, overflow);
 }
 
-template <class T, bool CAPSULE, bool CCAP> __device__ __forceinline__ void sp_cast_move_resolve_lane(const SP<T>& sp, const SM<T>& m, uint32_t qi);
-template <class T, bool CAPSULE = false, bool CCAP = false>
-__global__ __launch_bounds__(SP_WAVE) void k_sp_cast_move_resolve(SP<T> sp, SM<T> m) {
+template <class T, bool CAPSULE, bool CCAP, bool CTRI> __device__ __forceinline__ void sp_cast_move_resolve_lane(const typename SpArg<T, CTRI>::type& sp, const SM<T>& m, uint32_t qi);
+template <class T, bool CAPSULE = false, bool CCAP = false, bool CTRI = false>
+__global__ __launch_bounds__(SP_WAVE) void k_sp_cast_move_resolve(typename SpArg<T, CTRI>::type sp, SM<T> m) {
     uint32_t base = blockIdx.x * SP_WAVE;
-    do sp_cast_move_resolve_lane<T, CAPSULE, CCAP>(sp, m, base + threadIdx.x);
+    do sp_cast_move_resolve_lane<T, CAPSULE, CCAP, CTRI>(sp, m, base + threadIdx.x);
     while (CAPSULE && (base = sp_next_chunk<CAPSULE>(base, m.q.n)) < m.q.n);
 }
-template <class T, bool CAPSULE, bool CCAP> __device__ __forceinline__ void sp_cast_move_resolve_lane(const SP<T>& sp, const SM<T>& m, uint32_t qi) {
+template <class T, bool CAPSULE, bool CCAP, bool CTRI> __device__ __forceinline__ void sp_cast_move_resolve_lane(const typename SpArg<T, CTRI>::type& sp, const SM<T>& m, uint32_t qi) {
     const SQ<T>& q = m.q;
     if (qi >= q.n || !sp_lane_kind<CAPSULE>(q.shape, qi)) return;
     SpatialMoveHit<T> h = m.out[qi];
@@ -1132,7 +1195,11 @@ template <class T, bool CAPSULE, bool CCAP> __device__ __forceinline__ void sp_c
         SpDeepestSink<T> sink{vzero<T>(), T(0), 0};
         V3<T> nrm, a1, a2;
         bool contact;
-        if (CAPSULE && CCAP && info.z == AVN_SHAPE_CAPSULE) {
+        if (CTRI && info.z == AVN_SHAPE_TRIANGLE) {
+            const NpTri<T> tri = sp_load_tri<T>(sp_tri(sp), c);
+            AVN_INLINE_CALL contact = contact_manifolds_pair_sink<T, SpDeepestSink<T>, 0, true, true>(sp_query_kind<CAPSULE>(s.shape), s.he, s.pos, s.rot, AVN_SHAPE_TRIANGLE, he1, pos1, rot1, T(0), sink, nrm, nullptr, nullptr, NpTri<T>(), tri);
+            a1 = sink.anchor1; a2 = a1 + (s.pos - pos1);
+        } else if (CAPSULE && CCAP && info.z == AVN_SHAPE_CAPSULE) {
             contact = contact_manifolds_pair_sink<T, SpDeepestSink<T>, 0, true>(AVN_SHAPE_CAPSULE, s.he, s.pos, s.rot, AVN_SHAPE_CAPSULE, he1, pos1, rot1, T(0), sink, nrm);
             a1 = sink.anchor1; a2 = a1 + (s.pos - pos1);
         } else if (CAPSULE) {
@@ -1140,7 +1207,9 @@ template <class T, bool CAPSULE, bool CCAP> __device__ __forceinline__ void sp_c
             contact = sp_capsule_contact<T>(s.he.x, s.he.y, iso2, info.z, he1, pos1, rot1, T(0), sink.penetration, cn, a1, a2);
             nrm = -cn;
         } else {
-            contact = contact_manifolds_pair_sink<T, SpDeepestSink<T>, 0, CCAP>(s.shape, s.he, s.pos, s.rot, info.z, he1, pos1, rot1, T(0), sink, nrm);
+            // (inlined by statement attribute in the CTRI instantiations, as in k_sp_contacts: see the note there and the recipe it names)
+            if constexpr (CTRI) { AVN_INLINE_CALL contact = contact_manifolds_pair_sink<T, SpDeepestSink<T>, 0, CCAP>(s.shape, s.he, s.pos, s.rot, info.z, he1, pos1, rot1, T(0), sink, nrm); }
+            else contact = contact_manifolds_pair_sink<T, SpDeepestSink<T>, 0, CCAP>(s.shape, s.he, s.pos, s.rot, info.z, he1, pos1, rot1, T(0), sink, nrm);
             a1 = sink.anchor1; a2 = a1 + (s.pos - pos1);
         }
         if (contact) {
@@ -1309,17 +1378,18 @@ template <class T> void launch_spatial_project_velocity(const SV<T>& p, hipStrea
     if (p.n == 0) return;
     hipLaunchKernelGGL((k_sp_project_velocity<T>), dim3((p.n + SP_WAVE - 1) / SP_WAVE), dim3(SP_WAVE), 0, s, p);
 }
-template <class T, bool CCAP> static void launch_spatial_cast_move_as(const SP<T>& sp, const SM<T>& m, hipStream_t s, bool capsule) {
-    hipLaunchKernelGGL((k_sp_cast_move<T, false, CCAP>), dim3((m.q.n + SP_WAVE - 1) / SP_WAVE), dim3(SP_WAVE), 0, s, sp, m);
-    hipLaunchKernelGGL((k_sp_cast_move_resolve<T, false, CCAP>), dim3((m.q.n + SP_WAVE - 1) / SP_WAVE), dim3(SP_WAVE), 0, s, sp, m);
+template <class T, bool CCAP, bool CTRI = false> static void launch_spatial_cast_move_as(const typename SpArg<T, CTRI>::type& sp, const SM<T>& m, hipStream_t s, bool capsule) {
+    hipLaunchKernelGGL((k_sp_cast_move<T, false, CCAP, CTRI>), dim3((m.q.n + SP_WAVE - 1) / SP_WAVE), dim3(SP_WAVE), 0, s, sp, m);
+    hipLaunchKernelGGL((k_sp_cast_move_resolve<T, false, CCAP, CTRI>), dim3((m.q.n + SP_WAVE - 1) / SP_WAVE), dim3(SP_WAVE), 0, s, sp, m);
     if (!capsule) return;
-    hipLaunchKernelGGL((k_sp_cast_move<T, true, CCAP>), sp_capsule_grid(m.q.n), dim3(SP_WAVE), 0, s, sp, m);
-    hipLaunchKernelGGL((k_sp_cast_move_resolve<T, true, CCAP>), sp_capsule_grid(m.q.n), dim3(SP_WAVE), 0, s, sp, m);
+    hipLaunchKernelGGL((k_sp_cast_move<T, true, CCAP, CTRI>), sp_capsule_grid(m.q.n), dim3(SP_WAVE), 0, s, sp, m);
+    hipLaunchKernelGGL((k_sp_cast_move_resolve<T, true, CCAP, CTRI>), sp_capsule_grid(m.q.n), dim3(SP_WAVE), 0, s, sp, m);
 }
-template <class T> void launch_spatial_cast_move(const SP<T>& sp, const SM<T>& m, bool zero_stats, hipStream_t s, bool capsule, bool ccap) {
+template <class T> void launch_spatial_cast_move(const SP<T>& sp, const SM<T>& m, bool zero_stats, hipStream_t s, bool capsule, bool ccap, const Vec4<T>* tri) {
     if (zero_stats) (void)hipMemsetAsync(m.q.stats, 0, 4 * sizeof(unsigned long long), s);
     if (m.q.n == 0) return;
-    if (ccap) launch_spatial_cast_move_as<T, true>(sp, m, s, capsule);
+    if (tri) launch_spatial_cast_move_as<T, true, true>(SPT<T>{sp, tri}, m, s, capsule);
+    else if (ccap) launch_spatial_cast_move_as<T, true>(sp, m, s, capsule);
     else launch_spatial_cast_move_as<T, false>(sp, m, s, capsule);
 }
 template <class T> void launch_spatial_slide_phase(const SL<T>& l, int phase, hipStream_t s) {
@@ -1366,55 +1436,57 @@ template <class T> void launch_spatial_reaim(const DW<T>& w, const SP<T>& sp, co
     if (c.n == 0) return;
     hipLaunchKernelGGL((k_sp_reaim<T>), dim3((c.n + 255) / 256), dim3(256), 0, s, w, sp, c);
 }
-template <class T, bool CCAP> static void launch_spatial_casters_as(const SP<T>& sp, const SQ<T>& q, int kind, hipStream_t s, bool capsule) {
+template <class T, bool CCAP, bool CTRI = false> static void launch_spatial_casters_as(const typename SpArg<T, CTRI>::type& sp, const SQ<T>& q, int kind, hipStream_t s, bool capsule) {
     const dim3 g((q.n + SP_WAVE - 1) / SP_WAVE), b(SP_WAVE);
     switch (kind) {
-        case SPQ_CLOSEST: hipLaunchKernelGGL((k_sp_query<T, SPQ_CLOSEST, true, CCAP>), g, b, 0, s, sp, q); break;
-        case SPQ_HITS: hipLaunchKernelGGL((k_sp_query<T, SPQ_HITS, true, CCAP>), g, b, 0, s, sp, q); break;
+        case SPQ_CLOSEST: hipLaunchKernelGGL((k_sp_query<T, SPQ_CLOSEST, true, CCAP, CTRI>), g, b, 0, s, sp, q); break;
+        case SPQ_HITS: hipLaunchKernelGGL((k_sp_query<T, SPQ_HITS, true, CCAP, CTRI>), g, b, 0, s, sp, q); break;
         case SPQ_CAST:
-            hipLaunchKernelGGL((k_sp_cast<T, false, true, false, CCAP>), g, b, 0, s, sp, q);
-            if (capsule) hipLaunchKernelGGL((k_sp_cast<T, false, true, true, CCAP>), sp_capsule_grid(q.n), b, 0, s, sp, q);
+            hipLaunchKernelGGL((k_sp_cast<T, false, true, false, CCAP, CTRI>), g, b, 0, s, sp, q);
+            if (capsule) hipLaunchKernelGGL((k_sp_cast<T, false, true, true, CCAP, CTRI>), sp_capsule_grid(q.n), b, 0, s, sp, q);
             break;
         default:
-            hipLaunchKernelGGL((k_sp_cast<T, true, true, false, CCAP>), g, b, 0, s, sp, q);
-            if (capsule) hipLaunchKernelGGL((k_sp_cast<T, true, true, true, CCAP>), sp_capsule_grid(q.n), b, 0, s, sp, q);
+            hipLaunchKernelGGL((k_sp_cast<T, true, true, false, CCAP, CTRI>), g, b, 0, s, sp, q);
+            if (capsule) hipLaunchKernelGGL((k_sp_cast<T, true, true, true, CCAP, CTRI>), sp_capsule_grid(q.n), b, 0, s, sp, q);
             break;
     }
 }
-template <class T> void launch_spatial_casters(const SP<T>& sp, const SQ<T>& q, int kind, hipStream_t s, bool capsule, bool ccap) {
+template <class T> void launch_spatial_casters(const SP<T>& sp, const SQ<T>& q, int kind, hipStream_t s, bool capsule, bool ccap, const Vec4<T>* tri) {
     if (q.n == 0) return;
-    if (ccap) launch_spatial_casters_as<T, true>(sp, q, kind, s, capsule);
+    if (tri) launch_spatial_casters_as<T, true, true>(SPT<T>{sp, tri}, q, kind, s, capsule);
+    else if (ccap) launch_spatial_casters_as<T, true>(sp, q, kind, s, capsule);
     else launch_spatial_casters_as<T, false>(sp, q, kind, s, capsule);
 }
 
 // capsule (SPQ_SHAPES / SPQ_CAST / SPQ_CAST_HITS): the call may hold AVN_SHAPE_CAPSULE query shapes -- the CAPSULE instantiation runs behind the
 // first launch on the same stream and answers exactly those lanes
-template <class T, bool CCAP> static void launch_spatial_query_as(const SP<T>& sp, const SQ<T>& q, int kind, hipStream_t s, bool capsule) {
+template <class T, bool CCAP, bool CTRI = false> static void launch_spatial_query_as(const typename SpArg<T, CTRI>::type& sp, const SQ<T>& q, int kind, hipStream_t s, bool capsule) {
     const dim3 g((q.n + SP_WAVE - 1) / SP_WAVE), b(SP_WAVE);
     switch (kind) {
-        case SPQ_CLOSEST: hipLaunchKernelGGL((k_sp_query<T, SPQ_CLOSEST, false, CCAP>), g, b, 0, s, sp, q); break;
-        case SPQ_HITS: hipLaunchKernelGGL((k_sp_query<T, SPQ_HITS, false, CCAP>), g, b, 0, s, sp, q); break;
-        case SPQ_POINTS: hipLaunchKernelGGL((k_sp_query<T, SPQ_POINTS, false, CCAP>), g, b, 0, s, sp, q); break;
-        case SPQ_PROJECT: hipLaunchKernelGGL((k_sp_project<T, CCAP>), g, b, 0, s, sp, q); break;
+        case SPQ_CLOSEST: hipLaunchKernelGGL((k_sp_query<T, SPQ_CLOSEST, false, CCAP, CTRI>), g, b, 0, s, sp, q); break;
+        case SPQ_HITS: hipLaunchKernelGGL((k_sp_query<T, SPQ_HITS, false, CCAP, CTRI>), g, b, 0, s, sp, q); break;
+        case SPQ_POINTS: hipLaunchKernelGGL((k_sp_query<T, SPQ_POINTS, false, CCAP, CTRI>), g, b, 0, s, sp, q); break;
+        case SPQ_PROJECT: hipLaunchKernelGGL((k_sp_project<T, CCAP, CTRI>), g, b, 0, s, sp, q); break;
         case SPQ_SHAPES:
-            hipLaunchKernelGGL((k_sp_shapes<T, false, CCAP>), g, b, 0, s, sp, q);
-            if (capsule) hipLaunchKernelGGL((k_sp_shapes<T, true, CCAP>), sp_capsule_grid(q.n), b, 0, s, sp, q);
+            hipLaunchKernelGGL((k_sp_shapes<T, false, CCAP, CTRI>), g, b, 0, s, sp, q);
+            if (capsule) hipLaunchKernelGGL((k_sp_shapes<T, true, CCAP, CTRI>), sp_capsule_grid(q.n), b, 0, s, sp, q);
             break;
         case SPQ_CAST:
-            hipLaunchKernelGGL((k_sp_cast<T, false, false, false, CCAP>), g, b, 0, s, sp, q);
-            if (capsule) hipLaunchKernelGGL((k_sp_cast<T, false, false, true, CCAP>), sp_capsule_grid(q.n), b, 0, s, sp, q);
+            hipLaunchKernelGGL((k_sp_cast<T, false, false, false, CCAP, CTRI>), g, b, 0, s, sp, q);
+            if (capsule) hipLaunchKernelGGL((k_sp_cast<T, false, false, true, CCAP, CTRI>), sp_capsule_grid(q.n), b, 0, s, sp, q);
             break;
         case SPQ_CAST_HITS:
-            hipLaunchKernelGGL((k_sp_cast<T, true, false, false, CCAP>), g, b, 0, s, sp, q);
-            if (capsule) hipLaunchKernelGGL((k_sp_cast<T, true, false, true, CCAP>), sp_capsule_grid(q.n), b, 0, s, sp, q);
+            hipLaunchKernelGGL((k_sp_cast<T, true, false, false, CCAP, CTRI>), g, b, 0, s, sp, q);
+            if (capsule) hipLaunchKernelGGL((k_sp_cast<T, true, false, true, CCAP, CTRI>), sp_capsule_grid(q.n), b, 0, s, sp, q);
             break;
-        default: hipLaunchKernelGGL((k_sp_query<T, SPQ_AABBS, false, CCAP>), g, b, 0, s, sp, q); break;
+        default: hipLaunchKernelGGL((k_sp_query<T, SPQ_AABBS, false, CCAP, CTRI>), g, b, 0, s, sp, q); break;
     }
 }
-template <class T> void launch_spatial_query(const SP<T>& sp, const SQ<T>& q, int kind, hipStream_t s, bool capsule, bool ccap) {
+template <class T> void launch_spatial_query(const SP<T>& sp, const SQ<T>& q, int kind, hipStream_t s, bool capsule, bool ccap, const Vec4<T>* tri) {
     (void)hipMemsetAsync(q.stats, 0, 4 * sizeof(unsigned long long), s);
     if (q.n == 0) return;
-    if (ccap) launch_spatial_query_as<T, true>(sp, q, kind, s, capsule);
+    if (tri) launch_spatial_query_as<T, true, true>(SPT<T>{sp, tri}, q, kind, s, capsule);
+    else if (ccap) launch_spatial_query_as<T, true>(sp, q, kind, s, capsule);
     else launch_spatial_query_as<T, false>(sp, q, kind, s, capsule);
 }
 
@@ -1456,20 +1528,20 @@ static_assert(sizeof(SpatialSlide<float>) == sizeof(avn_spatial_slide_f32) && si
               offsetof(SpatialSlide<double>, reserved) == offsetof(avn_spatial_slide_f64, reserved),
               "slide record layout");
 static_assert(SP_SLIDE_PLANES >= AVN_SPATIAL_MAX_PLANES + 1, "plane slots");
-template void launch_spatial_build<float>(const DW<float>&, const BP<float>&, const SP<float>&, hipStream_t, bool, bool);
-template void launch_spatial_build<double>(const DW<double>&, const BP<double>&, const SP<double>&, hipStream_t, bool, bool);
-template void launch_spatial_query<float>(const SP<float>&, const SQ<float>&, int, hipStream_t, bool, bool);
-template void launch_spatial_query<double>(const SP<double>&, const SQ<double>&, int, hipStream_t, bool, bool);
+template void launch_spatial_build<float>(const DW<float>&, const BP<float>&, const SP<float>&, hipStream_t, bool, bool, bool);
+template void launch_spatial_build<double>(const DW<double>&, const BP<double>&, const SP<double>&, hipStream_t, bool, bool, bool);
+template void launch_spatial_query<float>(const SP<float>&, const SQ<float>&, int, hipStream_t, bool, bool, const Vec4<float>*);
+template void launch_spatial_query<double>(const SP<double>&, const SQ<double>&, int, hipStream_t, bool, bool, const Vec4<double>*);
 template void launch_spatial_reaim<float>(const DW<float>&, const SP<float>&, const SCA<float>&, hipStream_t);
 template void launch_spatial_reaim<double>(const DW<double>&, const SP<double>&, const SCA<double>&, hipStream_t);
-template void launch_spatial_casters<float>(const SP<float>&, const SQ<float>&, int, hipStream_t, bool, bool);
-template void launch_spatial_casters<double>(const SP<double>&, const SQ<double>&, int, hipStream_t, bool, bool);
-template void launch_spatial_contacts<float>(const SP<float>&, const SC<float>&, hipStream_t, bool, bool, bool);
-template void launch_spatial_contacts<double>(const SP<double>&, const SC<double>&, hipStream_t, bool, bool, bool);
+template void launch_spatial_casters<float>(const SP<float>&, const SQ<float>&, int, hipStream_t, bool, bool, const Vec4<float>*);
+template void launch_spatial_casters<double>(const SP<double>&, const SQ<double>&, int, hipStream_t, bool, bool, const Vec4<double>*);
+template void launch_spatial_contacts<float>(const SP<float>&, const SC<float>&, hipStream_t, bool, bool, bool, const Vec4<float>*);
+template void launch_spatial_contacts<double>(const SP<double>&, const SC<double>&, hipStream_t, bool, bool, bool, const Vec4<double>*);
 template void launch_spatial_project_velocity<float>(const SV<float>&, hipStream_t);
 template void launch_spatial_project_velocity<double>(const SV<double>&, hipStream_t);
-template void launch_spatial_cast_move<float>(const SP<float>&, const SM<float>&, bool, hipStream_t, bool, bool);
-template void launch_spatial_cast_move<double>(const SP<double>&, const SM<double>&, bool, hipStream_t, bool, bool);
+template void launch_spatial_cast_move<float>(const SP<float>&, const SM<float>&, bool, hipStream_t, bool, bool, const Vec4<float>*);
+template void launch_spatial_cast_move<double>(const SP<double>&, const SM<double>&, bool, hipStream_t, bool, bool, const Vec4<double>*);
 template void launch_spatial_slide_phase<float>(const SL<float>&, int, hipStream_t);
 template void launch_spatial_slide_phase<double>(const SL<double>&, int, hipStream_t);
 template void launch_spatial_depenetrate<float>(const SD<float>&, hipStream_t);

@@ -11,9 +11,14 @@
         b_mv_pend, b_mv_pcount;   // cast_move's hand-over: the colliders overlapping each query at its start [n * AVN_SPATIAL_MAX_HITS], their counts [n]
     uint32_t sp_cap = 0;
     bool sp_valid = false;      // a snapshot exists and no table changed since (bodies / colliders / collider transforms uploads and avn_despawn clear it)
-    uint32_t sp_host = 0;       // the colliders the snapshot leaves out: AVN_SHAPE_HOST, AVN_SHAPE_TRIANGLE, and AVN_SHAPE_CAPSULE unless sp_capsules is set
+    uint32_t sp_host = 0;       // the colliders the snapshot leaves out: AVN_SHAPE_HOST; AVN_SHAPE_CAPSULE unless sp_capsules is set; AVN_SHAPE_TRIANGLE unless sp_triangles is
     bool sp_capsules = false;   // avn_spatial_capsule_colliders_set: capsule colliders are candidates of the queries (sticky, off by default)
     bool sp_ccap = false;       // the snapshot holds capsule colliders as candidates: every traversal launch takes its CCAP instantiation
+    bool sp_triangles = false;  // avn_spatial_triangle_colliders_set: triangle colliders are candidates of the queries (sticky, off by default)
+    bool sp_ctri = false;       // the snapshot holds triangle colliders as candidates: every traversal launch takes its CTRI instantiation
+    // the triangle table the CTRI launches read (the world's, not a copy: avn_colliders_upload and avn_collider_triangles_upload clear sp_valid, and sp_check
+    // lets no query through until the next update has taken the new pointer)
+    const V* sp_tri_table() const { return sp_ctri ? bp.col_tri : nullptr; }
     unsigned long long sp_visits[3] = {0, 0, 0};   // last query call: node boxes tested, exact tests, stack overflow
 
     avn_status sp_grow(uint32_t C) {
@@ -40,12 +45,20 @@
         const uint32_t C = bp.n_colliders;
         avn_status st = sp_grow(C);
         if (st != AVN_OK) return st;
+        if (sp_triangles && (st = tri_need_table()) != AVN_OK) return st;   // (the CTRI snapshot reads BP::col_tri)
         sp.n = C;
         sp_ccap = sp_capsules && cap_count != 0;   // (a world without a capsule, or with the switch off, launches what it always has)
-        launch_spatial_build<T>(dw, bp, sp, stream, sp_ccap, tri_count != 0);
+        sp_ctri = sp_triangles && tri_count != 0 && bp.col_tri != nullptr;   // (likewise for triangles)
+        launch_spatial_build<T>(dw, bp, sp, stream, sp_ccap, tri_count != 0, sp_ctri);
         HIPCHK(hipGetLastError());
-        sp_host = (uint32_t)hs_slots.size() + (sp_capsules ? 0u : cap_count) + tri_count;   // (triangle colliders: left out exactly as host shapes are)
+        sp_host = (uint32_t)hs_slots.size() + (sp_capsules ? 0u : cap_count) + (sp_triangles ? 0u : tri_count);   // (with their switch off triangle colliders are left out exactly as host shapes are)
         sp_valid = true;
+        return AVN_OK;
+    }
+
+    avn_status spatial_triangle_colliders_set(uint32_t enabled) override {
+        sp_triangles = enabled != 0;
+        sp_valid = false;   // (the snapshot was built under the old rule: avn_spatial_update again)
         return AVN_OK;
     }
 
@@ -57,7 +70,7 @@
 
     avn_status sp_check(uint32_t flags) {
         if (!sp_valid) { error = "spatial query: no avn_spatial_update since the tables last changed"; return AVN_ERR_STATE; }
-        if (sp_host && tri_count && !(flags & AVN_SPATIAL_SKIP_HOST_SHAPES)) {
+        if (sp_host && tri_count && !sp_triangles && !(flags & AVN_SPATIAL_SKIP_HOST_SHAPES)) {
             error = "spatial query: the snapshot holds AVN_SHAPE_TRIANGLE colliders (and possibly AVN_SHAPE_HOST / AVN_SHAPE_CAPSULE ones), which the queries have no device geometry for (AVN_SPATIAL_SKIP_HOST_SHAPES leaves them out)";
             return AVN_ERR_STATE;
         }
@@ -94,7 +107,7 @@
     }
     avn_status sp_run(SQ<T>& q, int kind, bool capsule = false) {
         q.stats = b_sp_stats.as<unsigned long long>();
-        launch_spatial_query<T>(sp, q, kind, stream, capsule, sp_ccap);
+        launch_spatial_query<T>(sp, q, kind, stream, capsule, sp_ccap, sp_tri_table());
         HIPCHK(hipGetLastError());
         return AVN_OK;
     }
@@ -262,7 +275,7 @@
         sc.pad_unused = 1u;
         plan.out(out->contacts, n_rec, &sc.rec); plan.out(out->count, n, &sc.q.count);
         COMMIT(plan);
-        launch_spatial_contacts<T>(sp, sc, stream, true, sp_any_capsule(s->shape, n, dev), sp_ccap);
+        launch_spatial_contacts<T>(sp, sc, stream, true, sp_any_capsule(s->shape, n, dev), sp_ccap, sp_tri_table());
         HIPCHK(hipGetLastError());
         FINISH(plan);
         return sp_finish();
@@ -298,7 +311,7 @@
             sc.prediction_all = (T)cfg->skin_width;
             sc.pad_unused = 0u;   // (k_sp_depenetrate reads the first min(count, cap) records only)
             sc.skip_sensors = (s->flags & AVN_SPATIAL_SKIP_SENSORS) ? 1u : 0u;
-            launch_spatial_contacts<T>(sp, sc, stream, true, sp_any_capsule(s->shape, n, dev), sp_ccap);
+            launch_spatial_contacts<T>(sp, sc, stream, true, sp_any_capsule(s->shape, n, dev), sp_ccap, sp_tri_table());
             HIPCHK(hipGetLastError());
             SD<T> d{};
             d.n = n; d.rec = sc.rec; d.count = d_count;
@@ -349,7 +362,7 @@
         COMMIT(plan);
         GROW(b_mv_pend, std::max<size_t>((size_t)n * AVN_SPATIAL_MAX_HITS, 1), m.pending);
         GROW(b_mv_pcount, std::max<size_t>(n, 1), m.pending_count);
-        launch_spatial_cast_move<T>(sp, m, true, stream, sp_any_capsule(s->shape, n, dev), sp_ccap);
+        launch_spatial_cast_move<T>(sp, m, true, stream, sp_any_capsule(s->shape, n, dev), sp_ccap, sp_tri_table());
         HIPCHK(hipGetLastError());
         FINISH(plan);
         return sp_finish();
@@ -404,7 +417,7 @@
         HIPCHK(hipMemsetAsync(b_sp_stats.p, 0, 4 * sizeof(unsigned long long), stream));
         const bool capsule = sp_any_capsule(s->shape, n, dev);   // (every traversal launch of the loop gets its CAPSULE instantiation behind it)
         auto depenetrate = [&]() {
-            if (cfg->depenetration_iterations) { sc.prediction = nullptr; sc.prediction_all = l.skin; launch_spatial_contacts<T>(sp, sc, stream, false, capsule, sp_ccap); }
+            if (cfg->depenetration_iterations) { sc.prediction = nullptr; sc.prediction_all = l.skin; launch_spatial_contacts<T>(sp, sc, stream, false, capsule, sp_ccap, sp_tri_table()); }
             launch_spatial_slide_phase<T>(l, SPL_DEPENETRATE, stream);
         };
         launch_spatial_slide_phase<T>(l, SPL_BEGIN, stream);
@@ -412,10 +425,10 @@
         for (uint32_t it = 0; it < cfg->move_and_slide_iterations; ++it) {
             l.iteration = it;
             launch_spatial_slide_phase<T>(l, SPL_SWEEP, stream);
-            launch_spatial_cast_move<T>(sp, m, false, stream, capsule, sp_ccap);
+            launch_spatial_cast_move<T>(sp, m, false, stream, capsule, sp_ccap, sp_tri_table());
             launch_spatial_slide_phase<T>(l, SPL_ADVANCE, stream);
             sc.prediction = l.pred;
-            launch_spatial_contacts<T>(sp, sc, stream, false, capsule, sp_ccap);
+            launch_spatial_contacts<T>(sp, sc, stream, false, capsule, sp_ccap, sp_tri_table());
             launch_spatial_slide_phase<T>(l, SPL_PLANES, stream);
         }
         depenetrate();
@@ -564,9 +577,9 @@
             SQ<T> q = cs->q;
             q.stats = stats;
             q.n = cs->n_closest; q.index = cs->index_closest;
-            launch_spatial_casters<T>(sp, q, is_shape ? SPQ_CAST : SPQ_CLOSEST, stream, cs->any_capsule, sp_ccap);   // (sp_ccap: of the update above)
+            launch_spatial_casters<T>(sp, q, is_shape ? SPQ_CAST : SPQ_CLOSEST, stream, cs->any_capsule, sp_ccap, sp_tri_table());   // (sp_ccap, sp_ctri: of the update above)
             q.n = cs->n_many; q.index = cs->index_many;
-            launch_spatial_casters<T>(sp, q, is_shape ? SPQ_CAST_HITS : SPQ_HITS, stream, cs->any_capsule, sp_ccap);
+            launch_spatial_casters<T>(sp, q, is_shape ? SPQ_CAST_HITS : SPQ_HITS, stream, cs->any_capsule, sp_ccap, sp_tri_table());
         }
         HIPCHK(hipGetLastError());
         cs_ran = true;

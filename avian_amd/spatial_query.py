@@ -231,7 +231,7 @@ STRUCTS = [avn_spatial_filter, avn_spatial_rays, avn_spatial_points, avn_spatial
            avn_spatial_velocities_out, avn_spatial_moves, avn_spatial_move_hit_f32, avn_spatial_move_hit_f64, avn_spatial_move_hits_out,
            avn_spatial_characters, avn_spatial_move_and_slide_config, avn_spatial_slide_f32, avn_spatial_slide_f64, avn_spatial_slide_hit_f32,
            avn_spatial_slide_hit_f64, avn_spatial_slides_out, avn_spatial_ray_casters, avn_spatial_shape_casters, avn_spatial_caster_poses_out]
-SYMBOLS = ["avn_spatial_update", "avn_spatial_capsule_colliders_set", "avn_spatial_cast_rays", "avn_spatial_ray_hits", "avn_spatial_point_intersections",
+SYMBOLS = ["avn_spatial_update", "avn_spatial_capsule_colliders_set", "avn_spatial_triangle_colliders_set", "avn_spatial_cast_rays", "avn_spatial_ray_hits", "avn_spatial_point_intersections",
            "avn_spatial_aabb_intersections", "avn_spatial_stats_get", "avn_spatial_project_points", "avn_spatial_shape_intersections",
            "avn_spatial_cast_shapes", "avn_spatial_shape_hits", "avn_spatial_shape_contacts", "avn_spatial_depenetrate", "avn_spatial_project_velocities",
            "avn_spatial_cast_moves", "avn_spatial_move_and_slide", "avn_spatial_ray_casters_upload", "avn_spatial_shape_casters_upload",
@@ -295,13 +295,17 @@ def slide_hit_dtype(bits: int) -> np.dtype:
 
 def _declare(dll):
     # (AVN_AB_OLDER_LIBRARY=1 with AVN_LIB_PATH, as in _ffi.Library: an A/B run against a build from before the switch; otherwise a missing symbol is an error)
-    switch = hasattr(dll, "avn_spatial_capsule_colliders_set") or not os.environ.get("AVN_AB_OLDER_LIBRARY")
+    older = bool(os.environ.get("AVN_AB_OLDER_LIBRARY"))
+    switch = hasattr(dll, "avn_spatial_capsule_colliders_set") or not older
+    tri_switch = hasattr(dll, "avn_spatial_triangle_colliders_set") or not older
     for name in SYMBOLS:
-        if switch or name != "avn_spatial_capsule_colliders_set":
+        if (switch or name != "avn_spatial_capsule_colliders_set") and (tri_switch or name != "avn_spatial_triangle_colliders_set"):
             getattr(dll, name).restype = C.c_int32
     dll.avn_spatial_update.argtypes = [vp]
     if switch:
         dll.avn_spatial_capsule_colliders_set.argtypes = [vp, C.c_uint32]
+    if tri_switch:
+        dll.avn_spatial_triangle_colliders_set.argtypes = [vp, C.c_uint32]
     dll.avn_spatial_cast_rays.argtypes = [vp, vp, vp]
     dll.avn_spatial_ray_hits.argtypes = [vp, vp, C.c_uint32, vp]
     dll.avn_spatial_point_intersections.argtypes = [vp, vp, C.c_uint32, vp]
@@ -333,9 +337,10 @@ class SpatialQuery:
     as tensors.  Otherwise everything is numpy.
 
     ``capsule_colliders=True`` switches the world's capsule colliders in as candidates of every query (:meth:`set_capsule_colliders`); the
-    default leaves the world's switch as it is, which is off in a new world: capsule colliders are then left out as host shapes are."""
+    default leaves the world's switch as it is, which is off in a new world: capsule colliders are then left out as host shapes are.
+    ``triangle_colliders=True`` does the same for the world's triangle colliders (:meth:`set_triangle_colliders`); the two switches are independent."""
 
-    def __init__(self, world: F.World, capsule_colliders: bool = False):
+    def __init__(self, world: F.World, capsule_colliders: bool = False, triangle_colliders: bool = False):
         self.world = world
         self.dll = world.lib.dll
         if not hasattr(self.dll, "avn_spatial_update"):
@@ -355,6 +360,8 @@ class SpatialQuery:
         self._casters = {CASTER_RAY: (0, 1), CASTER_SHAPE: (0, 1)}   # (count, hit_cap) of the last uploads
         if capsule_colliders:
             self.set_capsule_colliders(True)
+        if triangle_colliders:
+            self.set_triangle_colliders(True)
 
     # -- plumbing ------------------------------------------------------------------------------
     def _check(self, st: int):
@@ -421,6 +428,14 @@ class SpatialQuery:
         if not hasattr(self.dll, "avn_spatial_capsule_colliders_set"):
             raise ImportError(f"{self.world.lib.path} is older than avn_spatial_capsule_colliders_set")
         self._check(self.dll.avn_spatial_capsule_colliders_set(self.world.handle, 1 if enabled else 0))
+
+    def set_triangle_colliders(self, enabled: bool):
+        """avn_spatial_triangle_colliders_set: whether triangle colliders (``World.colliders_upload(triangles=...)``) are candidates of the queries.
+        Sticky and independent of :meth:`set_capsule_colliders`; it invalidates the snapshot, so call :meth:`update` (or :meth:`casters_run`)
+        before the next query."""
+        if not hasattr(self.dll, "avn_spatial_triangle_colliders_set"):
+            raise ImportError(f"{self.world.lib.path} is older than avn_spatial_triangle_colliders_set")
+        self._check(self.dll.avn_spatial_triangle_colliders_set(self.world.handle, 1 if enabled else 0))
 
     def _rays(self, origin, direction, max_distance, solid, mask, excluded, skip_host_shapes):
         dev = self._is_tensor(origin)

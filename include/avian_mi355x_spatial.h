@@ -216,6 +216,57 @@
  *        against Ball / Cuboid colliders keeps its own contact above.
  *    A capsule collider with h_c == 0 answers what a Ball collider of radius r_c answers up to rounding (tests/test_spatial_capsule_colliders_cpu.py).
  *    NOT covered: target_distance != 0, queries against AVN_SHAPE_HOST colliders.
+ *  - queries against triangle colliders (avn_spatial_triangle_colliders_set(w, 1); off by default, and then every answer is what it was before the
+ *    switch existed: a triangle collider -- avian_mi355x_trimesh.h -- is left out and counted like a host shape).  With the switch on a triangle
+ *    collider is a candidate of every query, caster and move-and-slide call, for the three query shapes; host_skipped, the AVN_SPATIAL_SKIP_HOST_SHAPES
+ *    rule and the state error stop counting and naming triangles.  The switch and avn_spatial_capsule_colliders_set are independent.  The collider is
+ *    the triangle (a, b, c) of its table record in the collider's frame, two-sided and without interior; every test works in that frame (o_l, d_l, q as
+ *    for the capsule collider).  The leaf reads the triangle from the WORLD's table at query time, not from a copy in the snapshot:
+ *    avn_colliders_upload and avn_collider_triangles_upload both invalidate the snapshot, so no query reads a table newer than its snapshot.  The
+ *    pair tests are DEFINED HERE with their operation order (no FMA contraction, dot = na_dot, cross = na_cross); parity with parry is UNPINNED.
+ *    EDGE FLAGS matter only to the contacts; rays, projection, intersections and casts are pure geometry.  N = cross(b - a, c - a) / |.| (tri_unit_normal);
+ *    C(p) = the closest point of the triangle to p by Ericson 5.1.5 in its order of tests with its region (the narrow phase's tri_closest_point).
+ *      ray: den = dot(N, d_l); !(den != 0) (a parallel or coplanar ray, a zero direction, a NaN): a miss.  t = dot(N, a - o_l) / den; !(t >= 0): a
+ *        miss (t == 0, the origin on the plane, is a hit).  Inside test, per edge k = 0, 1, 2 with v = v_k, v' = v_k+1: m = (v + v') * 0.5; o = o_l + d_l
+ *        (dot(d_l, m - o_l) / dot(d_l, d_l)) (the ray's point nearest the edge's midpoint); s_k = dot(d_l, cross(v - o, v' - o)).  The ray is inside when
+ *        no s_k is negative or no s_k is positive (a NaN is both).  m and the cross product are exactly symmetric / antisymmetric in (v, v'), so the two
+ *        faces sharing an edge compute s_k of opposite sign bit for bit: a ray through a shared edge is never missed by both faces (both may hit; the
+ *        traversal's tie rule, lower collider index, picks).  The normal is N turned against d_l (-N when den > 0) rotated by the collider's
+ *        rotation; `solid` has no effect; hits from either side count; max_distance and the finite-distance rule as for the other kinds.
+ *      point intersection: C(point_l) == point_l, component for component.  AABB intersection: the triangle's shape AABB (the min / max of the three
+ *        posed vertices) against the query box.  The leaf box is that AABB padded like every kind's.
+ *      point projection: C(point_l) carried back to the world; distance = |point_l - C(point_l)|; is_inside iff C(point_l) == point_l; `solid` has no effect.
+ *      D (segment A + s u - triangle, squared distance with the closest points p_seg, p_tri; the narrow phase's triangle-capsule manifold uses the same
+ *        candidates routine): B = A + u, da = dot(N, A - a), db = dot(N, B - a).  The ends strictly on opposite sides (da > 0 and db < 0, or the
+ *        reverse) and X = A + u (da / (da - db)) with C(X) in the face region: 0, p_seg = X, p_tri = C(X).  Otherwise the first smallest (strict <) of
+ *        five candidates: (A, C(A)), (B, C(B)), then for k = 0, 1, 2 the S of the segment against edge k (v_k, v_k+1 - v_k).
+ *      shape intersection: a ball: |q.t - C(q.t)|^2 <= r^2.  A capsule: D(A, u of q).d2 <= r^2.  A cuboid: in the QUERY's frame (the vertices through
+ *        iso_inv_mul(make_isometry(query), {collider rotation, collider position})) no axis of the 13 separates (separation > 0): e_0..e_2, N of the posed
+ *        vertices, then edge_k x e_i / |.| with k outer and i inner, skipped when the norm is not above eps |edge_k|; per axis L the separation is
+ *        max(min_k dot(L, v_k) - rb, -max_k dot(L, v_k) - rb), rb = (|L_x| he_x + |L_y| he_y) + |L_z| he_z (the narrow phase's tri_box_axis).
+ *      shape cast (point1 / normal1 the collider's, point2 the query's at the impact pose; everything 0 when the shapes overlap at the start):
+ *        a ball query: the Newton iteration of the capsule-query cast on g(t) = |c - C(c)| - r, c = q.t + d_l t, n = (c - C(c)) / dist: normal1 =
+ *          rot_c n; point1 = rot_c C(c) + pos_c; point2 = rot_c (c - n r) + pos_c.
+ *        a capsule query: the same iteration on g(t) = sqrt(D(A + d_l t, u).d2) - r, n = (p_seg - p_tri) / dist: normal1 = rot_c n; point1 = rot_c
+ *          p_tri + pos_c; point2 = rot_c (p_seg - n r) + pos_c.  The 32-round cap, the last t standing and "never an over-estimate" are unchanged.
+ *        a cuboid query: a swept SAT in the collider's frame over 13 axes in this order: N; u_0..u_2 (the query's face axes, iso_vec(q, e_b)); cross(edge_k,
+ *          u_b) / |.| with b outer and k inner (edge_0 = b - a, edge_1 = c - b, edge_2 = a - c), skipped when the norm is not above eps.  Per axis:
+ *          [lo, hi] = min / max of dot(axis, a), dot(axis, b), dot(axis, c); s0 = dot(axis, q.t), v = dot(axis, d_l), r2 = the sum of |dot(axis, u_i)|
+ *          he_i; v != 0: t1 = ((lo - r2) - s0) / v, t2 = ((hi + r2) - s0) / v by inv = 1 / v, exchanged when inv < 0; the largest t1 (strict >) is the
+ *          entry with its axis, oriented from the triangle towards the query (-axis, or +axis when inv < 0), the smallest t2 the exit; v == 0: a miss
+ *          when s0 + r2 < lo or s0 - r2 > hi.  !(entry <= exit) or exit < 0: a miss; entry < 0: overlap at the start.  Witnesses by the entering axis,
+ *          n its orientation, tp = q.t + d_l t, s2 = the query's support vertex along -n: N: p2 = s2, p1 = s2 - N dot(N, s2 - a), inside when C(p1) is
+ *          in the face region.  u_b: p1 = the triangle's vertex of the largest dot(n, v) (the first), p2 = p1 - n (dot(p1 - tp, n) + he_b), inside when
+ *          p1 lies within the query's face on the other two axes.  An edge pair: the closest points of the lines v_k + lambda edge_k and s2 + mu u_b
+ *          (aa = |edge_k|^2, bc = dot(edge_k, u_b), cc = |u_b|^2, w = v_k - s2, dd = dot(edge_k, w), ee = dot(u_b, w), den = aa cc - bc bc, lambda = (bc ee -
+ *          cc dd) / den, mu = (aa ee - bc dd) / den; den not above eps aa cc: p1 = the edge's middle and not inside), inside when 0 <= lambda <= 1 and p2 lies
+ *          on the query's edge.  Not inside: p1 = C(p1), p2 = the box's closest point to p1 (clamp in the query's frame), p1 = C(p2), p2 = the box's closest
+ *          point to p1.  normal1 = rot_c n; point1 = rot_c p1 + pos_c; point2 = rot_c p2 + pos_c.
+ *      contacts (shape contacts, depenetration, cast_move's origin-penetration rule, move and slide): (a), (b) with the triangle's AABB, then the
+ *        narrow phase's triangle manifold of avian_mi355x_trimesh.h with the query as shape 1 -- a ball, a cuboid or a capsule query alike -- the
+ *        collider's triangle WITH ITS EDGE FLAGS as shape 2, and (d)'s fold: the deepest point, the later point wins a tie.  A character sliding over
+ *        the interior edges of a flat mesh therefore gets the face normal there.
+ *    NOT covered: swept CCD against triangles, a triangle as a query shape, triangle-triangle, target_distance != 0, level-2 and sharded worlds.
  *  - move and slide (MoveAndSlide::cast_move, project_velocity, move_and_slide; move_and_slide.rs:464-793, velocity_project.rs).  As above the
  *    definitions are written out here with their operation order (no FMA contraction); parity with glam / parry is UNPINNED.  Common rules:
  *      Sensors are never candidates (MoveAndSlide's collider query is Without<Sensor>; cast_move's predicate enforces it for the cast too).
@@ -679,7 +730,7 @@ typedef struct avn_spatial_ids_out {
 typedef struct avn_spatial_stats {
     uint32_t colliders;        /* colliders in the snapshot */
     uint32_t nodes;            /* BVH nodes (2 * colliders - 1) */
-    uint32_t host_skipped;     /* AVN_SHAPE_HOST colliders in the snapshot (never candidates); AVN_SHAPE_CAPSULE ones too unless avn_spatial_capsule_colliders_set switched them in */
+    uint32_t host_skipped;     /* AVN_SHAPE_HOST colliders in the snapshot (never candidates); AVN_SHAPE_CAPSULE ones too unless avn_spatial_capsule_colliders_set switched them in, AVN_SHAPE_TRIANGLE ones unless avn_spatial_triangle_colliders_set did */
     uint32_t valid;            /* 1: the snapshot can be queried */
     uint64_t nodes_visited;    /* last query call: node boxes tested, all queries together */
     uint64_t leaves_visited;   /* last query call: exact per-collider tests run, all queries together */
@@ -692,6 +743,11 @@ AVN_API avn_status avn_spatial_update(avn_world* w);
  * invalidates the snapshot -- a query before the next avn_spatial_update is AVN_ERR_STATE -- and holds for every later avn_spatial_update, the
  * one inside avn_spatial_casters_run included.  A world without a capsule collider launches the same kernels with the switch on as with it off. */
 AVN_API avn_status avn_spatial_capsule_colliders_set(avn_world* w, uint32_t enabled);
+/* Triangle colliders (avian_mi355x_trimesh.h) as candidates of the queries ("queries against triangle colliders"): a sticky per-world switch, 0 (off) in
+ * a new world, independent of the capsule switch.  It invalidates the snapshot as that one does and holds for every later avn_spatial_update, the one
+ * inside avn_spatial_casters_run included.  With it on avn_spatial_update needs the triangle table (AVN_ERR_STATE while AVN_SHAPE_TRIANGLE colliders
+ * exist without avn_collider_triangles_upload).  A world without a triangle collider launches the same kernels with the switch on as with it off. */
+AVN_API avn_status avn_spatial_triangle_colliders_set(avn_world* w, uint32_t enabled);
 /* SpatialQueryPipeline::cast_ray (pipeline.rs:162-231); RayCaster with max_hits = 1: per ray the closest hit within max_distance, or a miss */
 AVN_API avn_status avn_spatial_cast_rays(avn_world* w, const avn_spatial_rays* rays, const avn_spatial_hits_out* out);
 /* SpatialQueryPipeline::ray_hits (pipeline.rs:233-333); RayCaster / RayHits: per ray the max_hits nearest hits, sorted, plus the true count.

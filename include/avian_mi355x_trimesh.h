@@ -56,10 +56,11 @@
  * device closed loop), collision hooks (which see triangle pairs like any other pair) and sleeping treat the collider like every other device
  * kind; a pair of a triangle and an AVN_SHAPE_HOST collider stays the host's.  A world without a triangle launches exactly the kernels it
  * launches without this header and leaves the same bytes.
- * DECLARED DEVIATIONS: the spatial queries, the casters and move-and-slide have no device geometry for triangles and leave them out exactly
- * as they leave AVN_SHAPE_HOST colliders out (AVN_ERR_STATE unless AVN_SPATIAL_SKIP_HOST_SHAPES; avn_spatial_stats.host_skipped counts them);
- * swept CCD skips a pair with a triangle on either side, as it skips host shapes (avian_mi355x_ccd.h says the same).
- * NOT BUILT: queries and CCD against triangles, triangle - triangle, the oracle backend, Rust declarations, level-2 (halo plan) and
+ * SPATIAL QUERIES: by default the spatial queries, the casters and move-and-slide leave triangles out exactly as they leave AVN_SHAPE_HOST
+ * colliders out (AVN_ERR_STATE unless AVN_SPATIAL_SKIP_HOST_SHAPES; avn_spatial_stats.host_skipped counts them).  avn_spatial_triangle_colliders_set
+ * (avian_mi355x_spatial.h, "queries against triangle colliders") switches them in as candidates of every query, for the three query shapes.
+ * DECLARED DEVIATION: swept CCD skips a pair with a triangle on either side, as it skips host shapes (avian_mi355x_ccd.h says the same).
+ * NOT BUILT: CCD against triangles, a triangle as a query shape, triangle - triangle, the oracle backend, Rust declarations, level-2 (halo plan) and
  * avn_dshard worlds.  avn_query_manifolds (AVN_FN(contact_manifolds)) still answers kind 4 with AVN_ERR_BAD_ARG: its struct has nowhere to
  * put vertices; avn_triangle_manifolds below is the batch query for pairs that may hold a triangle.
  */

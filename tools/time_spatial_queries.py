@@ -28,13 +28,17 @@
   depenetrate, cast_shapes, shape_hits k = 16, cast_moves, move_and_slide with Ball / Cuboid query shapes, and cast_shapes, shape_contacts and
   move_and_slide with the capsule character -- per entry point the two figures side by side, the second being the CCAP instantiations' cost
 
+  triangle colliders (`tricol`: this leg alone): cfg2's boxes at their poses once on their single cuboid ground (the existing scene, the yardstick) and
+  once on the flat 8 192-face mesh of tools/time_trimesh.py with avn_spatial_triangle_colliders_set on, the same 262144 queries into both, the entry
+  points of `capcol` -- per entry point the two figures and their ratio, the CTRI instantiations' cost with a mesh under the pile
+
 Every figure is the median over `reps` warmed-up calls.  The queries take torch tensors on the GPU (AVN_SPATIAL_DEVICE_POINTERS: no
 staging copies), so a call is its launches plus one stream synchronisation; the update is timed with avn_synchronize behind it.  Device
 events bracket the calls on torch's stream after a synchronisation of it, which the library's own stream joins at the call's end.
 bytes_floor: the bytes each call must move at least (inputs, outputs, the snapshot records a query touches once), for a roofline fraction
 against MI355X's 8 TB/s HBM.
-usage: python tools/time_spatial_queries.py [reps] [casters] [capcol] [nocapsule]
-       (`casters` / `capcol`: that leg alone; `nocapsule`: without the capsule legs, for an A/B run of a library from before them;
+usage: python tools/time_spatial_queries.py [reps] [casters] [capcol] [tricol] [nocapsule]
+       (`casters` / `capcol` / `tricol`: that leg alone; `nocapsule`: without the capsule legs, for an A/B run of a library from before them;
         AVN_LIB_PATH=path AVN_AB_OLDER_LIBRARY=1: time that (older) build of libavian_mi355x.so instead of the tree's)"""
 import json
 import os
@@ -287,6 +291,76 @@ def capsule_colliders_leg(res, sc, w_box, reps, dev):
         res[f"capcol_ratio_{key}"] = res[f"capcol_capsules_{key}_ms"] / res[f"capcol_boxes_{key}_ms"]
 
 
+def triangle_colliders_leg(res, sc, w_box, reps, dev):
+    """The same queries into cfg2's boxes standing on their single cuboid ground (the existing scene: the yardstick) and into the same boxes at the same
+    poses on the flat 8 192-face mesh of tools/time_trimesh.py (its top where the slab's top is), the triangle switch on."""
+    sys.path.insert(0, os.path.join(R, "tools"))
+    import time_trimesh
+    b = w_box.bodies_download()
+    msc = time_trimesh.build_scene(time_trimesh.CONFIGS["cfg2"])
+    nf = msc.n_faces
+    bm = {k: np.array(v).copy() for k, v in b.items()}
+    bm["position"][0] = 0.0                                  # (body 0 carries the mesh: its frame's y = 0 is the slab's top)
+    w_tri = F.World(w_box.lib, F.default_config(32, substeps=4))
+    w_tri.bodies_upload(**dict(msc.body_kwargs(), **bm)); w_tri.colliders_upload(**msc.collider_kwargs(native_triangles=True))
+    n_col = sc.n
+    g = torch.Generator(device=dev).manual_seed(3)
+    n = 262144
+    pos = torch.from_numpy(b["position"]).to(dev)
+    o = pos[torch.randint(1, n_col, (n,), device=dev, generator=g)] + torch.randn(n, 3, device=dev, generator=g) * 0.7
+    d = torch.nn.functional.normalize(torch.randn(n, 3, device=dev, generator=g), dim=1)
+    solid = (torch.arange(n, device=dev) & 1).to(torch.uint8)
+    short = torch.rand(n, device=dev, generator=g) * 2.0
+    long = torch.full((n,), 200.0, device=dev)
+    ext = torch.rand(n, 3, device=dev, generator=g)
+    small = ext * 0.25
+    kind = (torch.arange(n, device=dev) & 1).to(torch.uint8)
+    rot = torch.nn.functional.normalize(torch.randn(n, 4, device=dev, generator=g), dim=1)
+    pred = torch.full((n,), 0.05, device=dev)
+    skin = torch.full((n,), 0.01, device=dev)
+    ckind = torch.full((n,), SHAPE_CAPSULE, dtype=torch.uint8, device=dev)
+    che = torch.tensor([0.4, 0.5, 0.0], device=dev).repeat(n, 1)
+    upright = torch.tensor([0.0, 0.0, 0.0, 1.0], device=dev).repeat(n, 1)
+    cv = (d * 4.0).contiguous()
+    mcfg = dict(delta_time=0.1, skin_width=0.01, max_depenetration_error=1e-4, penetration_rejection_threshold=0.5, depenetration_iterations=4)
+    nk = 65536
+    res["tricol_queries"] = n
+    res["tricol_faces"] = nf
+    keep = {}
+    for name, w in (("ground", w_box), ("mesh", w_tri)):
+        sq = SpatialQuery(w, triangle_colliders=name == "mesh")
+
+        def upd():
+            sq.update(); w.synchronize()
+        calls = {
+            "update": upd,
+            "cast_rays_short": lambda: sq.cast_rays(o, d, short, solid), "cast_rays_long": lambda: keep.__setitem__(name, sq.cast_rays(o, d, long, solid)),
+            "ray_hits_k16_64k": lambda: sq.ray_hits(o[:nk], d[:nk], 16, long[:nk], solid[:nk]),
+            "point_intersections": lambda: sq.point_intersections(o, 8), "aabb_intersections": lambda: sq.aabb_intersections(o - ext, o + ext, 16),
+            "project_points": lambda: sq.project_points(o, solid),
+            "shape_intersections": lambda: sq.shape_intersections(kind, ext, o, rot, 16), "shape_contacts": lambda: sq.shape_contacts(kind, ext, o, rot, pred, 16),
+            "depenetrate": lambda: sq.depenetrate(kind, ext, o, rot, 0.05, 1e-4, 0.5, 4),
+            "cast_shapes_short": lambda: sq.cast_shapes(kind, small, o, rot, d, short), "shape_hits_k16_64k": lambda: sq.shape_hits(kind[:nk], small[:nk], o[:nk], rot[:nk], d[:nk], 16, long[:nk]),
+            "cast_moves": lambda: sq.cast_moves(kind, small, o, rot, cv * 0.1, skin),
+            "move_and_slide": lambda: sq.move_and_slide(kind, small, o, rot, cv, **mcfg, move_and_slide_iterations=4, hit_cap=0),
+            "capsule_query_cast_shapes_short": lambda: sq.cast_shapes(ckind, che, o, upright, d, short),
+            "capsule_query_shape_contacts": lambda: sq.shape_contacts(ckind, che, o, upright, pred, 16),
+            "capsule_query_move_and_slide": lambda: sq.move_and_slide(ckind, che, o, upright, cv, **mcfg, move_and_slide_iterations=4, hit_cap=0),
+        }
+        for key, fn in calls.items():
+            res[f"tricol_{name}_{key}_ms"] = timed(fn, reps)
+            if key != "update":
+                st = sq.stats()
+                res[f"tricol_{name}_{key}_leaves_per_query"] = st.leaves_visited / (nk if key.endswith("64k") else n)
+        res[f"tricol_{name}_host_skipped"] = sq.stats().host_skipped
+        hits = keep[name].cpu().numpy().reshape(-1).view(sq.hit_dtype)
+        ground = hits["collider"] < nf if name == "mesh" else hits["collider"] == 0
+        res[f"tricol_{name}_long_rays_answered_by_the_ground_share"] = float(((hits["collider"] != MISS) & ground).mean())
+        res[f"tricol_{name}_long_rays_hit_share"] = float((hits["collider"] != MISS).mean())
+    for key in calls:
+        res[f"tricol_ratio_{key}"] = res[f"tricol_mesh_{key}_ms"] / res[f"tricol_ground_{key}_ms"]
+
+
 def world(sc, steps):
     lib = avian_amd.load_library()
     w = F.World(lib, F.default_config(32, substeps=4))
@@ -315,6 +389,10 @@ def main():
         return
     if "capcol" in sys.argv[2:]:
         capsule_colliders_leg(res, sc2, w2, reps, dev)
+        print(json.dumps(res))
+        return
+    if "tricol" in sys.argv[2:]:
+        triangle_colliders_leg(res, sc2, w2, reps, dev)
         print(json.dumps(res))
         return
 
