@@ -41,6 +41,26 @@ template <class T> struct BodyRef {
 template <class T> struct BodyView { Vec4<T> *lin, *ang, *dp, *dq, *sia, *sib; };
 template <class T> __device__ __forceinline__ BodyView<T> global_bodies(const DW<T>& w) { return {w.sb_lin.p, w.sb_ang.p, w.sb_dp.p, w.sb_dq.p, w.si_a.p, w.si_b.p}; }
 
+// What a biased solve / relax launch of k_color_pass reads of DW<T> and StepParams<T>, and nothing else: 15 pointers, the point stride and eight scalars in
+// three cache lines of kernel arguments instead of the ten of the whole DW<T> + StepParams<T>.  The members carry the names they have there, so the solve
+// templates below take it in the place of both (`w` and `p`).  launch_pass fills it on the host, once per pass.
+template <class T> struct SolveArgs {
+    using V = Vec4<T>;
+    int2* m_bodies;
+    V *c_h1, *m_n, *m_tv, *c_pa, *c_pb, *c_pc, *c_pd;
+    Pair2<V> sb_lin, sb_ang, sb_dp, sb_dq, si_a, si_b;
+    uint32_t* color_offsets;
+    uint32_t m_stride;
+    SoftCoef<T> soft_dynamic, soft_non_dynamic;
+    T h_adj, max_overlap_solve_speed;
+    SolveArgs() = default;
+    SolveArgs(const DW<T>& w, const StepParams<T>& p)
+        : m_bodies(w.m_bodies), c_h1(w.c_h1), m_n(w.m_n), m_tv(w.m_tv), c_pa(w.c_pa), c_pb(w.c_pb), c_pc(w.c_pc), c_pd(w.c_pd), sb_lin(w.sb_lin), sb_ang(w.sb_ang), sb_dp(w.sb_dp),
+          sb_dq(w.sb_dq), si_a(w.si_a), si_b(w.si_b), color_offsets(w.color_offsets), m_stride(w.m_stride), soft_dynamic(p.soft_dynamic), soft_non_dynamic(p.soft_non_dynamic), h_adj(p.h_adj),
+          max_overlap_solve_speed(p.max_overlap_solve_speed) {}
+};
+template <class T> __device__ __forceinline__ BodyView<T> global_bodies(const SolveArgs<T>& w) { return {w.sb_lin.p, w.sb_ang.p, w.sb_dp.p, w.sb_dq.p, w.si_a.p, w.si_b.p}; }
+
 // Fetch SolverBody + SolverBodyInertia, substituting DUMMY for a missing body and a DUMMY inertia for a
 // dominant one (solver/plugin.rs:491-512).
 // Agent-scope accesses of one record (k_overflow_flow: lanes of different workgroups hand a body's velocities to each other inside
@@ -90,8 +110,11 @@ template <class T, bool WITH_DELTA> __device__ __forceinline__ void body_from_re
 template <class T, bool WITH_DELTA, int STRIDE, bool COH = false>
 __device__ __forceinline__ void load_body(const BodyView<T>& bv, int idx, bool no_body, bool dummy_inertia, BodyRef<T>& b) {
     // The six records are fetched UNCONDITIONALLY (every body index is a valid row; rows of bodies without a SolverBody
-    // hold DUMMY values) and the DUMMY substitution is a select afterwards: no load waits on the constraint's flag word,
-    // so the kernel has two dependent memory levels (headers + point records | body gathers) instead of three.
+    // hold DUMMY values) and the DUMMY substitution is a select afterwards: no load waits on the constraint's flag word.
+    // (In source order that is two dependent memory levels, headers + point records | body gathers.  The compiler makes three of it where the caller
+    // leaves early on the point count: it hoists that exit above the other loads, so c_h1 is waited for alone, then m_bodies, then everything else
+    // with the gathers issued last -- profiles/colour_schedule_wait_structure_parent.txt.  k_color_pass's solve passes do not come through here:
+    // lane_pass issues their loads in two levels with the gathers first.)
     const size_t o = (size_t)idx * STRIDE;
     Vec4<T> l, a;
     if (COH) { l = ld_rec_agent(bv.lin, o); a = ld_rec_agent(bv.ang, o); }   // (the velocities are the only records a contact pass writes)
@@ -534,26 +557,49 @@ __device__ __forceinline__ void warm_core(const DW<T>& w, const StepParams<T>& p
     store_body<T, STRIDE>(bv, i2, cm & AVN_CM_NOBODY2, b2);
 }
 
-template <class T, bool USE_BIAS, int STRIDE, bool COH = false>
-__device__ __forceinline__ void solve_core(const DW<T>& w, const StepParams<T>& p, uint32_t m, const BodyView<T>& bv, int i1, int i2) {
+// Who loads the records of a solve.  NoPre: solve_core / solve_core_packed fetch everything themselves, in source order and in whatever schedule the compiler
+// makes of it (island blocks, overflow kernels, every pass but the two below).  LanePre: k_color_pass's biased solve and relax hand over the records of the
+// manifold and of its two bodies as lane_pass issued them (its comment has the order and why).  FlowPre (f32, further down): k_overflow_flow_tag's.
+struct NoPre { static constexpr bool on = false, flow = false; };
+template <class T> struct LanePre {
+    static constexpr bool on = true, flow = false;
+    Vec4<T> h0, h1, h2, pa[AVN_MAX_MANIFOLD_POINTS], pb[AVN_MAX_MANIFOLD_POINTS], pc[AVN_MAX_MANIFOLD_POINTS], pd[AVN_MAX_MANIFOLD_POINTS];
+    Vec4<T> l1, a1, dp1, dq1, sa1, sb1, l2, a2, dp2, dq2, sa2, sb2;
+};
+
+// W, P: DW<T> and StepParams<T>, or SolveArgs<T> for both (k_color_pass)
+template <class T, bool USE_BIAS, int STRIDE, bool COH = false, class PRE = NoPre, class W = DW<T>, class P = StepParams<T>>
+__device__ __forceinline__ void solve_core(const W& w, const P& p, uint32_t m, const BodyView<T>& bv, int i1, int i2, const PRE& pre = PRE()) {
     // level 1: every load that only depends on m, issued up front and unconditionally (memory-level parallelism: the
     // kernel is latency-bound at one manifold per lane; the point planes hold 4 slots per manifold, so unused points
     // are in bounds and ignored); level 2: the body gathers; then the sequential impulse iteration out of registers
-    Vec4<T> h1 = w.c_h1[m];
-    Vec4<T> h0 = w.m_n[m];
-    Vec4<T> h2 = w.m_tv[m];
+    Vec4<T> h1, h0, h2;
     uint32_t S = w.m_stride;
     Vec4<T> pa[AVN_MAX_MANIFOLD_POINTS], pb[AVN_MAX_MANIFOLD_POINTS], pc[AVN_MAX_MANIFOLD_POINTS], pd[AVN_MAX_MANIFOLD_POINTS];
+    if constexpr (PRE::on) {
+        h1 = pre.h1; h0 = pre.h0; h2 = pre.h2;
 #pragma unroll
-    for (uint32_t k = 0; k < AVN_MAX_MANIFOLD_POINTS; ++k) {
-        uint32_t s = k * S + m;
-        pa[k] = w.c_pa[s]; pb[k] = w.c_pb[s]; pc[k] = w.c_pc[s]; pd[k] = w.c_pd[s];
+        for (uint32_t k = 0; k < AVN_MAX_MANIFOLD_POINTS; ++k) { pa[k] = pre.pa[k]; pb[k] = pre.pb[k]; pc[k] = pre.pc[k]; pd[k] = pre.pd[k]; }
+    } else {
+        h1 = w.c_h1[m];
+        h0 = w.m_n[m];
+        h2 = w.m_tv[m];
+#pragma unroll
+        for (uint32_t k = 0; k < AVN_MAX_MANIFOLD_POINTS; ++k) {
+            uint32_t s = k * S + m;
+            pa[k] = w.c_pa[s]; pb[k] = w.c_pb[s]; pc[k] = w.c_pc[s]; pd[k] = w.c_pd[s];
+        }
     }
     uint32_t cm = scalar_to_bits(h1.w);
     uint32_t np = cm & 7u;
     BodyRef<T> b1, b2;
-    load_body<T, true, STRIDE, COH>(bv, i1, cm & AVN_CM_NOBODY1, cm & AVN_CM_DOM1, b1);
-    load_body<T, true, STRIDE, COH>(bv, i2, cm & AVN_CM_NOBODY2, cm & AVN_CM_DOM2, b2);
+    if constexpr (PRE::on) {
+        body_from_recs<T, true>(pre.l1, pre.a1, pre.dp1, pre.dq1, pre.sa1, pre.sb1, cm & AVN_CM_NOBODY1, cm & AVN_CM_DOM1, b1);
+        body_from_recs<T, true>(pre.l2, pre.a2, pre.dp2, pre.dq2, pre.sa2, pre.sb2, cm & AVN_CM_NOBODY2, cm & AVN_CM_DOM2, b2);
+    } else {
+        load_body<T, true, STRIDE, COH>(bv, i1, cm & AVN_CM_NOBODY1, cm & AVN_CM_DOM1, b1);
+        load_body<T, true, STRIDE, COH>(bv, i2, cm & AVN_CM_NOBODY2, cm & AVN_CM_DOM2, b2);
+    }
     if (np == 0) return;
     V3<T> normal = xyz<T>(h0);
     T friction = h0.w;
@@ -697,16 +743,15 @@ __device__ __forceinline__ void apply_impulse(BodyPair& b, V3<float> imp, V3<F2>
 //  (the body-centric warm start reads ONE side per entry and would otherwise fetch both): not built.)
 // What k_overflow_flow_tag hands to solve_core_packed: the records of the manifold and of its two bodies already in registers (loaded before
 // / by the tag wait) and the tags the velocity records leave with.  NoPre: the pass fetches everything itself (every other caller).
-struct NoPre { static constexpr bool on = false; };
 struct FlowPre {
-    static constexpr bool on = true;
+    static constexpr bool on = true, flow = true;
     Vec4<float> h0, h1, h2, pa[AVN_MAX_MANIFOLD_POINTS], pb[AVN_MAX_MANIFOLD_POINTS], pc[AVN_MAX_MANIFOLD_POINTS], pd[AVN_MAX_MANIFOLD_POINTS];
     Vec4<float> l1, a1, dp1, dq1, sa1, sb1, l2, a2, dp2, dq2, sa2, sb2;
     bool no1, no2;          // no SolverBody on that side (rank PG_NONE)
     uint32_t tag1, tag2;    // next tags
 };
-template <bool USE_BIAS, int STRIDE, bool COH = false, class PRE = NoPre>
-__device__ __forceinline__ void solve_core_packed(const DW<float>& w, const StepParams<float>& p, uint32_t m, const BodyView<float>& bv, int i1, int i2, const PRE& pre = PRE()) {
+template <bool USE_BIAS, int STRIDE, bool COH = false, class PRE = NoPre, class W = DW<float>, class P = StepParams<float>>
+__device__ __forceinline__ void solve_core_packed(const W& w, const P& p, uint32_t m, const BodyView<float>& bv, int i1, int i2, const PRE& pre = PRE()) {
     typedef float T;
     // memory levels exactly as solve_one: (headers + point records) | body gathers
     Vec4<T> h1, h0, h2;
@@ -730,7 +775,7 @@ __device__ __forceinline__ void solve_core_packed(const DW<float>& w, const Step
     uint32_t np = cm & 7u;
     BodyRef<T> b1, b2;
     bool no1 = cm & AVN_CM_NOBODY1, no2 = cm & AVN_CM_NOBODY2;
-    if constexpr (PRE::on) {
+    if constexpr (PRE::flow) {
         no1 = pre.no1; no2 = pre.no2;
         body_from_recs<T, true>(pre.l1, pre.a1, pre.dp1, pre.dq1, pre.sa1, pre.sb1, no1, cm & AVN_CM_DOM1, b1);
         body_from_recs<T, true>(pre.l2, pre.a2, pre.dp2, pre.dq2, pre.sa2, pre.sb2, no2, cm & AVN_CM_DOM2, b2);
@@ -740,6 +785,10 @@ __device__ __forceinline__ void solve_core_packed(const DW<float>& w, const Step
             store_body<T, STRIDE, COH>(bv, i2, no2, b2);
             return;
         }
+    } else if constexpr (PRE::on) {
+        body_from_recs<T, true>(pre.l1, pre.a1, pre.dp1, pre.dq1, pre.sa1, pre.sb1, no1, cm & AVN_CM_DOM1, b1);
+        body_from_recs<T, true>(pre.l2, pre.a2, pre.dp2, pre.dq2, pre.sa2, pre.sb2, no2, cm & AVN_CM_DOM2, b2);
+        if (np == 0) return;
     } else {
         load_body<T, true, STRIDE, COH>(bv, i1, no1, cm & AVN_CM_DOM1, b1);
         load_body<T, true, STRIDE, COH>(bv, i2, no2, cm & AVN_CM_DOM2, b2);
@@ -823,10 +872,14 @@ __device__ __forceinline__ void solve_core_packed(const DW<float>& w, const Step
     store_body<T, STRIDE, COH>(bv, i2, no2, b2);
 }
 template <class T, bool USE_BIAS, int STRIDE, bool COH = false> struct SolveDispatch {
-    static __device__ __forceinline__ void run(const DW<T>& w, const StepParams<T>& p, uint32_t m, const BodyView<T>& bv, int i1, int i2) { solve_core<T, USE_BIAS, STRIDE, COH>(w, p, m, bv, i1, i2); }
+    template <class W, class P, class PRE = NoPre> static __device__ __forceinline__ void run(const W& w, const P& p, uint32_t m, const BodyView<T>& bv, int i1, int i2, const PRE& pre = PRE()) {
+        solve_core<T, USE_BIAS, STRIDE, COH, PRE>(w, p, m, bv, i1, i2, pre);
+    }
 };
 template <bool USE_BIAS, int STRIDE, bool COH> struct SolveDispatch<float, USE_BIAS, STRIDE, COH> {
-    static __device__ __forceinline__ void run(const DW<float>& w, const StepParams<float>& p, uint32_t m, const BodyView<float>& bv, int i1, int i2) { solve_core_packed<USE_BIAS, STRIDE, COH>(w, p, m, bv, i1, i2); }
+    template <class W, class P, class PRE = NoPre> static __device__ __forceinline__ void run(const W& w, const P& p, uint32_t m, const BodyView<float>& bv, int i1, int i2, const PRE& pre = PRE()) {
+        solve_core_packed<USE_BIAS, STRIDE, COH, PRE>(w, p, m, bv, i1, i2, pre);
+    }
 };
 
 // ---- f32, EIGHT LANES PER MANIFOLD (round 5) ---------------------------------------------------------------------------------
@@ -1102,13 +1155,75 @@ template <class T, int PASS, bool COH = false> __device__ __forceinline__ void p
 //  meant to remove.  The in-kernel-barrier idea survives where the barrier is a workgroup one: k_island_substeps.)
 // One colour: manifolds [offsets[c], offsets[c+1]) read from device memory so that a captured graph stays
 // valid while the colour populations drift; the grid is a multiple of 8 blocks and remapped per XCD.
+//
+// The biased solve and the relax pass of a colour launch (one manifold per lane) issue their loads themselves, in the order the wave consumes them, and hand the
+// records to the solve as a LanePre.  A launch runs less than one wave per SIMD, so nothing hides a wave's round trips but the wave itself:
+//   level 1  m_bodies, c_h1, m_n, m_tv together; the wave waits for the first two (body indices, point count) and leaves if it has nothing to solve --
+//            a lane with np == 0 loads nothing further and stores nothing;
+//   level 2  the twelve body gathers FIRST (unconditional: every body index is a valid row, load_body), then per point c_pa, c_pb, c_pd in the order of use,
+//            then the four c_pc, which only the friction loop reads.  Loads return in order: the chain starts behind a counted wait on the gathers and point
+//            0 while the other records are still on their way, and the wave reaches vmcnt(0) only where the friction loop wants its last c_pc.
+// The compiler fences keep the groups in this order (the scheduler otherwise issues the gathers LAST, behind a vmcnt(0) on everything); they cost no instruction.
+// The four point slots of a manifold are loaded whatever np is, as before (in bounds: the planes hold four slots per manifold).
+#define AVN_LOAD_FENCE() asm volatile("" ::: "memory")
+template <class T, int PASS> __device__ __forceinline__ void lane_pass(const SolveArgs<T>& a, uint32_t m) {
+    LanePre<T> r;
+    const int2 b = a.m_bodies[m];
+    r.h1 = a.c_h1[m];
+    r.h0 = a.m_n[m];
+    r.h2 = a.m_tv[m];
+    AVN_LOAD_FENCE();
+    if ((scalar_to_bits(r.h1.w) & 7u) == 0u) return;
+    const size_t o1 = (size_t)b.x, o2 = (size_t)b.y;   // (Pair2::operator[]: record i at base[2 i])
+    r.dq1 = a.sb_dq[o1]; r.dq2 = a.sb_dq[o2]; r.dp1 = a.sb_dp[o1]; r.dp2 = a.sb_dp[o2];
+    r.l1 = a.sb_lin[o1]; r.l2 = a.sb_lin[o2]; r.a1 = a.sb_ang[o1]; r.a2 = a.sb_ang[o2];
+    r.sa1 = a.si_a[o1]; r.sa2 = a.si_a[o2]; r.sb1 = a.si_b[o1]; r.sb2 = a.si_b[o2];
+    AVN_LOAD_FENCE();
+    const uint32_t S = a.m_stride;
+#pragma unroll
+    for (uint32_t k = 0; k < AVN_MAX_MANIFOLD_POINTS; ++k) {
+        const uint32_t s = k * S + m;
+        r.pa[k] = a.c_pa[s]; r.pb[k] = a.c_pb[s]; r.pd[k] = a.c_pd[s];
+        AVN_LOAD_FENCE();
+    }
+#pragma unroll
+    for (uint32_t k = 0; k < AVN_MAX_MANIFOLD_POINTS; ++k) r.pc[k] = a.c_pc[k * S + m];
+    AVN_LOAD_FENCE();
+    SolveDispatch<T, PASS == PASS_BIAS, 2, false>::run(a, a, m, global_bodies(a), b.x, b.y, r);
+}
+// Every kernel argument of a solve launch in scalar registers before the first vector load: ONE batch of scalar loads and one wait, where the compiler otherwise
+// sinks each argument's load into the block that first uses it (four dependent batches in front of and between the vector levels).
+template <class T> __device__ __forceinline__ void hold_args(const SolveArgs<T>& a) {
+    asm volatile("" ::"s"(a.m_bodies), "s"(a.c_h1), "s"(a.m_n), "s"(a.m_tv), "s"(a.c_pa), "s"(a.c_pb), "s"(a.c_pc), "s"(a.c_pd), "s"(a.sb_lin.p), "s"(a.sb_ang.p), "s"(a.sb_dp.p), "s"(a.sb_dq.p),
+                 "s"(a.si_a.p), "s"(a.si_b.p), "s"(a.m_stride), "s"(a.soft_dynamic.bias), "s"(a.soft_dynamic.mass_scale), "s"(a.soft_dynamic.impulse_scale), "s"(a.soft_non_dynamic.bias),
+                 "s"(a.soft_non_dynamic.mass_scale), "s"(a.soft_non_dynamic.impulse_scale), "s"(a.h_adj), "s"(a.max_overlap_solve_speed));
+}
+// the arguments of k_color_pass: the narrow block for the two passes that run 112 times a step, DW<T> + StepParams<T> for the others
+template <class T> struct WideArgs {
+    DW<T> w; StepParams<T> p;
+    WideArgs(const DW<T>& w_, const StepParams<T>& p_) : w(w_), p(p_) {}
+};
+// the live range of a colour (handle mode).  Behind hold_args the compiler no longer takes a plain load for a scalar one (the volatile asm may have written
+// memory for all it knows), so the solve passes read the two words through the constant address space: no kernel writes color_offsets while a pass runs.
+typedef const uint32_t __attribute__((address_space(4))) * ConstWords;
+template <class T> __device__ __forceinline__ void live_range(const WideArgs<T>& a, uint32_t color, uint32_t& base, uint32_t& end) { base = a.w.color_offsets[color]; end = a.w.color_offsets[color + 1]; }
+template <class T> __device__ __forceinline__ void live_range(const SolveArgs<T>& a, uint32_t color, uint32_t& base, uint32_t& end) {
+    const ConstWords offs = (ConstWords)(uintptr_t)a.color_offsets;
+    base = offs[color]; end = offs[color + 1];
+}
+template <class T, int PASS> struct ColorArgs : WideArgs<T> { using WideArgs<T>::WideArgs; };
+template <class T> struct ColorArgs<T, PASS_BIAS> : SolveArgs<T> { using SolveArgs<T>::SolveArgs; };
+template <class T> struct ColorArgs<T, PASS_RELAX> : SolveArgs<T> { using SolveArgs<T>::SolveArgs; };
+template <class T, int PASS> __device__ __forceinline__ void color_one(const WideArgs<T>& a, uint32_t m) { pass_one<T, PASS>(a.w, a.p, m); }
+template <class T, int PASS> __device__ __forceinline__ void color_one(const SolveArgs<T>& a, uint32_t m) { lane_pass<T, PASS>(a, m); }
 template <class T, int PASS>
-__global__ __launch_bounds__(CONTACT_THREADS) void k_color_pass(DW<T> w, StepParams<T> p, uint32_t color, uint32_t arg_base, uint32_t arg_end) {
+__global__ __launch_bounds__(CONTACT_THREADS) void k_color_pass(ColorArgs<T, PASS> a, uint32_t color, uint32_t arg_base, uint32_t arg_end) {
+    if constexpr (PASS == PASS_BIAS || PASS == PASS_RELAX) hold_args(a);
     // arg_end != 0: the colour range travels in the kernel arguments (one dependent scalar load less in a latency-bound
     // launch; the host re-captures the graph when the ranges change) -- used for host-uploaded manifold sets, which are
     // static between uploads.  arg_end == 0: read the live range from device memory (handle mode: colours drift every step).
     uint32_t base = arg_base, end = arg_end;
-    if (arg_end == 0u) { base = w.color_offsets[color]; end = w.color_offsets[color + 1]; }
+    if (arg_end == 0u) live_range(a, color, base, end);
     // block b runs on XCD b % 8; each XCD walks one contiguous eighth of the colour.  The eighths are cut from the colour's REAL
     // tile count, not from the launched grid: grids carry up to 25 % slack (colours drift between re-captures), and an eighth of
     // the padded grid would leave the last XCDs with the empty tail while the first ones carry 110 tiles instead of 88.
@@ -1117,7 +1232,7 @@ __global__ __launch_bounds__(CONTACT_THREADS) void k_color_pass(DW<T> w, StepPar
     const uint32_t blk = (blockIdx.x & 7u) * per + row;
     uint32_t m = base + blk * CONTACT_THREADS + threadIdx.x;
     if (m >= end) return;
-    pass_one<T, PASS>(w, p, m);
+    color_one<T, PASS>(a, m);
 }
 // The overflow colour: the reference solves it strictly serially in manifold_handles order (solver/plugin.rs:461-467).
 // Only the relative order of manifolds that SHARE A BODY can change a result, so the host turns the list into a level
@@ -1402,13 +1517,14 @@ template <class T, int PASS> static uint32_t launch_pass(const DW<T>& w, const S
         ++launches;
         if (forms && loop_pass) { forms->overflow_form = AVN_OVERFLOW_FORM_COMPONENT; forms->overflow_components = ovf.n_components; forms->overflow_levels = 0; forms->overflow_grid_blocks = ovf.n_components; }
     }
+    const ColorArgs<T, PASS> args(w, p);
     for (uint32_t c = 0; c < AVN_COLOR_OVERFLOW_INDEX; ++c)
         if (grid_blocks[c]) {
             uint32_t b = arg_offsets ? arg_offsets[c] : 0u, e = arg_offsets ? arg_offsets[c + 1] : 0u;
             if (arg_offsets && e == b) continue;  // (a captured range is exact: an empty colour needs no launch)
             uint32_t form = AVN_COLOUR_FORM_OCT;
             if (!((oct_mask >> c) & 1u) || !OctLaunch<T, PASS>::run(w, p, c, grid_blocks[c], b, e, s)) {
-                hipLaunchKernelGGL((k_color_pass<T, PASS>), dim3(grid_blocks[c]), dim3(CONTACT_THREADS), 0, s, w, p, c, b, e);
+                hipLaunchKernelGGL((k_color_pass<T, PASS>), dim3(grid_blocks[c]), dim3(CONTACT_THREADS), 0, s, args, c, b, e);
                 form = AVN_COLOUR_FORM_LANE;
             }
             ++launches;
